@@ -9,19 +9,25 @@ them).  ZMWs shard across ranks with no collective on the data
 path (weak scaling: per-GPU batch fixed).
 
 Timed region: from the first submit to the last result of K steps through the library's asynchronous
-boundary (ccsx_submit / ccsx_wait): batches start in page-locked HOST memory, go H2D, through every kernel, and their
+boundary (ccsx_submit / ccsx_wait): batches start in page-locked HOST memory (bases and pulse widths; the inter-pulse durations, which
+the engine uploads only for `--hifi-kinetics`, are page-locked only then), go H2D, through every kernel, and their
 results come back D2H into page-locked host memory; up to three batches are in flight, so the copies of batch k+1 / k-1 and
 the draft stage of batch k+1 run under the polish stage of batch k (two compute streams; `--serial-stages` = one).  `value`
 is that PCIe-inclusive rate.  `resident_zmws_per_s` is the same work counted over the kernels alone (HIP events: first kernel
 of the first timed batch to the last kernel of the last): the rate with inputs already in HBM.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, its duration measured live with HIP events on the
-stream it is launched on (ccsx_ticket_timings); with `--pmc` (run under `rocprofv3 --pmc ...`) nothing but the headline steps
-runs, so a counter pass profiles exactly this workload and `tools/mk_traffic.py` turns the passes into profiles/rNN_traffic.json,
-whose `head` field ties it to a commit; `cpu_baseline` times the CPU restatement (oracle, kind "port") on the host cores over a
-bounded sample of the same workload, and the reference `ccs` binary is probed for (command -v ccs) and, when present, RUN on
-the same synthetic subreads (timing + identity against the truth: `reference_ccs`).  `extra` carries the other BASELINE shapes
-(c1 / c4 / c5) through the same pipeline, a few steps each.
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: it synthesises the batches, warms up,
+times `--steps` steps, writes the last step's outputs when `--dump-outputs DIR` is given, and prints the line.  `roofline` is for
+the dominant kernel, its duration measured live with HIP events on the stream it is launched on (ccsx_ticket_timings), its traffic
+read from the committed PMC file; with `--pmc` (run under `rocprofv3 --pmc ...`) nothing but the headline steps runs, so a counter
+pass profiles exactly this workload and `tools/mk_traffic.py` turns the passes into profiles/rNN_traffic.json, whose `head` field
+ties it to a commit.
+
+`--full` adds everything else the benchmark measures: `cpu_baseline` times the CPU restatement (oracle, kind "port") on the host
+cores over a bounded sample of the same workload, and the reference `ccs` binary is probed for (command -v ccs) and, when present,
+RUN on the same synthetic subreads (timing + identity against the truth: `reference_ccs`); `extra` carries the other BASELINE
+shapes (c1 / c4 / c5) through the same pipeline, a few steps each; `gpu_clocks`, the un-overlapped upload time of one batch and,
+with several workers, every worker's H2D rate.
 """
 from __future__ import annotations
 
@@ -33,7 +39,9 @@ import subprocess
 import sys
 import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -163,23 +171,80 @@ def fit_zmws(zmws, passes, length, world, min_batches=2):
     return zmws
 
 
+SYNTH_SEED = 0xC0FFEE
+
+
+def synth_generate(api, zmws, passes, length, first_zmw_id):
+    """one synthetic batch as api.synth makes it (ccsx_synth_generate, seed SYNTH_SEED), still in the generator's buffers: hand it to synth_pin"""
+    plo, phi = (passes, passes) if isinstance(passes, int) else passes
+    llo, lhi = (length, length) if isinstance(length, int) else length
+    p = api.C.POINTER(api.CSynth)()
+    if api.lib().ccsx_synth_generate(zmws, first_zmw_id, plo, phi, llo, lhi, SYNTH_SEED, api.C.byref(p)) != 0:
+        raise RuntimeError(api.lib().ccsx_last_error().decode())
+    return p
+
+
+def synth_pin(api, np, p, pin=("bases", "pw", "ipd")):
+    """api.synth(...).pinned() of a generated batch without the pageable copy in between: the per-base arrays named in `pin` go from the
+    generator's buffers straight into page-locked memory, the other arrays are copied as api.synth copies them; the generator's buffers
+    are released"""
+    L, C = api.lib(), api.C
+    try:
+        s = p.contents
+        b = s.batch
+        n, R, NB = b.n_zmw, b.n_reads, b.n_bases
+
+        def cp(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True) if k else np.zeros(0, dt)
+        keep, per_base = [], {}
+        for name in ("bases", "pw", "ipd"):
+            if name not in pin:
+                per_base[name] = cp(getattr(b, name), NB, np.uint8)
+                continue
+            q = L.ccsx_alloc_pinned(max(1, NB))
+            if not q:
+                raise RuntimeError("ccsx_alloc_pinned failed: " + L.ccsx_last_error().decode())
+            keep.append(api._Pinned(q))
+            a = np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_uint8)), shape=(max(1, NB),))[:NB]
+            if NB:
+                a[:] = np.ctypeslib.as_array(getattr(b, name), shape=(NB,))
+            per_base[name] = a
+        tpl_off = cp(s.tpl_off, n + 1, np.int64)
+        out = api.Batch(cp(b.zmw_id, n, np.int32), cp(b.snr, 4 * n, np.float32).reshape(n, 4), cp(b.read_off, n + 1, np.int32),
+                        cp(b.base_off, R + 1, np.int64), per_base["bases"], per_base["pw"], per_base["ipd"], cp(b.flags, R, np.uint8),
+                        tpl_off=tpl_off, tpl=cp(s.tpl, int(tpl_off[-1]), np.uint8))
+        out._pinned = keep
+        return out
+    finally:
+        L.ccsx_synth_free(p)
+
+
 class Job:
     """one workload through the asynchronous boundary on this rank's GPU"""
 
     def __init__(self, api, np, rank, world, local_rank, zmws, passes, length, distinct, steps, warmup, depth, opts, keep_sample=0):
         self.api, self.np, self.zmws, self.depth = api, np, zmws, depth
         t0 = time.time()
-        first = api.synth(zmws, passes, length, seed=0xC0FFEE, first_zmw_id=rank * zmws)
-        batch_bytes = 4 * first.bases.nbytes                 # bases + pw + ipd page-locked, plus slack for the result buffers
+        g0 = synth_generate(api, zmws, passes, length, rank * zmws)
+        first_bases = int(g0.contents.batch.n_bases)
+        batch_bytes = 4 * first_bases                        # bases + pw + ipd, plus slack for the result buffers
         self.nb = max(1, min(distinct, steps + warmup, host_memory_budget() // max(1, batch_bytes * world)))
+
+        # the engine uploads ipd only for the kinetics kernel: without it ipd stays pageable (pinning and releasing it cost seconds, and nothing reads it)
+        pin = ("bases", "pw", "ipd") if opts.hifi_kinetics else ("bases", "pw")
+
+        def make(i):
+            return synth_pin(api, np, g0 if i == 0 else synth_generate(api, zmws, passes, length, (i * world + rank) * zmws), pin)
+        # a few batches at a time: the generator's own threads leave the host idle in its serial phases (merge, copies, page-locking).  Every
+        # batch is the same function of its seed and first ZMW id, so the inputs do not depend on the order they are made in.  While one is
+        # made it exists up to three times over (the generator's per-ZMW and merged arrays, the page-locked copy).
+        left = host_memory_budget() // max(1, world) - self.nb * 3 * first_bases
+        workers = max(1, min(3, self.nb, left // max(1, 9 * first_bases)))
+        with ThreadPoolExecutor(workers) as ex:
+            self.batches = list(ex.map(make, range(self.nb)))
+        first = self.batches[0]
         self.alg_bytes = first.algorithmic_bytes()           # SURVEY.md §8(d): 3*sum(len) + 48 + 2*L_out per ZMW
         self.sample0 = first.slice(0, min(zmws, keep_sample)) if keep_sample else None   # CPU baseline sample (pageable copy)
-        self.batches = [first.pinned()]
-        del first
-        for i in range(1, self.nb):
-            b = api.synth(zmws, passes, length, seed=0xC0FFEE, first_zmw_id=(i * world + rank) * zmws)
-            self.batches.append(b.pinned())
-            del b
         self.gen_s = time.time() - t0
         self.h = api.Handle(local_rank, opts=opts)
         kin = bool(opts.hifi_kinetics)
@@ -231,6 +296,44 @@ def stage_means(np, kt):
 def kernels_span_ms(kt):
     """device time from the first kernel of the first timed batch to the last kernel of the last one (HIP events)"""
     return max(t.end_ms for t in kt) - min(t.start_ms for t in kt)
+
+
+DUMP_BYTES = 64_000_000                 # --dump-outputs: all files together stay below this
+DUMP_SEED = 0x5EED                      # the fixed sample of ZMWs whose per-base outputs are written
+
+
+def dump_outputs(np, batch, res, kinetics, d):
+    """What the timed path handed its caller in the last timed step (one batch and its result buffers), as DIR/<name>.npy in float64 (integers)
+    or float32 (the library's float fields): every per-ZMW field of the batch in full, and the per-base fields (sequence, QVs, kinetics planes)
+    of a fixed, seeded sample of its ZMWs.  The sample is drawn against the batch's capacity layout, which depends on the inputs alone, so
+    every build dumps the same ZMWs; it holds as many as keep the files under DUMP_BYTES.  Returns the total bytes written."""
+    n = batch.n_zmw
+    out = {"zmw_id": batch.zmw_id.astype(np.float64)}
+    for name, a in (("status", res.status), ("seq_len", res.seq_len), ("np", res.np_), ("iters", res.iters), ("n_windows", res.n_windows),
+                    ("fn", res.fn), ("rn", res.rn)):
+        out[name] = a[:n].astype(np.float64)
+    out["rq"], out["ec"] = res.rq[:n].astype(np.float32), res.ec[:n].astype(np.float32)
+    cap = np.diff(res.seq_off[:n + 1])                       # bases reserved per ZMW (>= its consensus length)
+    planes = 2 + (4 if kinetics else 0)                       # seq, qual (+ fi, fp, ri, rp)
+    room = (DUMP_BYTES - sum(a.nbytes for a in out.values()) - 2 * 8 * (n + 1) - 64 * 1024) // (4 * planes)
+    perm = np.random.default_rng(DUMP_SEED).permutation(n)
+    pick = np.sort(perm[:int(np.searchsorted(np.cumsum(cap[perm]), room, side="right"))])
+    lens = res.seq_len[pick].astype(np.int64)
+    idx = np.concatenate([np.arange(o, o + l, dtype=np.int64) for o, l in zip(res.seq_off[pick], lens)] + [np.zeros(0, np.int64)])
+    out["sample_zmw"] = pick.astype(np.float64)
+    out["sample_seq_off"] = np.concatenate([[0], np.cumsum(lens)]).astype(np.float64)
+    out["seq"], out["qual"] = res.seq[idx].astype(np.float32), res.qual[idx].astype(np.float32)
+    if kinetics:
+        out["kinetics"] = res.kin[:, idx].astype(np.float32)   # [4, bases]: fi, fp, ri, rp
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in out.items():
+        p = os.path.join(d, name + ".npy")
+        np.save(p, a)
+        total += os.path.getsize(p)
+    if total > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs wrote {total} bytes, more than {DUMP_BYTES}")
+    return total
 
 
 def reference_concordance(api, np, ccs_bin, sample, cores, seconds, seed=0xC0FFEE):
@@ -299,23 +402,27 @@ def main():
     ap.add_argument("--hifi-kinetics", action="store_true", help="also run the N4 kinetics kernel (not part of the headline metric)")
     ap.add_argument("--disable-heuristics", action="store_true", help="polish every position (no candidate filter): A/B for the filter's cost")
     ap.add_argument("--serial-stages", action="store_true", help="draft and polish stage on ONE compute stream (A/B for the two-stage queue)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the CPU baseline sample")
-    ap.add_argument("--extra", default="c1,c4,c5", help="other BASELINE shapes reported under `extra` (N=1 only; '' = none)")
-    ap.add_argument("--extra-steps", type=int, default=4)
-    ap.add_argument("--pmc", action="store_true", help="counter-pass mode (under rocprofv3 --pmc): only the headline steps, no CPU baseline, no extras")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: CPU baseline, reference `ccs` probe, the other "
+                    "BASELINE shapes (`extra`), GPU clocks, the un-overlapped upload of one batch and, with several workers, every worker's H2D rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (worker 0 of rank 0: "
+                    "every per-ZMW field, and sequence / QVs / kinetics of a fixed seeded sample of its ZMWs) as DIR/<name>.npy, float32 / float64, under 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(--full) target wall time of the CPU baseline sample")
+    ap.add_argument("--extra", default="c1,c4,c5", help="(--full) other BASELINE shapes reported under `extra` (N=1 only; '' = none)")
+    ap.add_argument("--extra-steps", type=int, default=4, help="(--full) timed steps of every `extra` shape")
+    ap.add_argument("--pmc", action="store_true", help="counter-pass mode (under rocprofv3 --pmc): only the headline steps, even with --full")
     args = ap.parse_args()
+    full = args.full and not args.pmc
     wl = WORKLOADS[args.workload]
     args.passes = wl[0] if args.passes is None else args.passes
     args.length = wl[1] if args.length is None else args.length
     explicit_zmws = args.zmws > 0
     args.zmws = wl[2] if args.zmws <= 0 else args.zmws
     args.depth = max(1, min(3, args.depth))
-    if args.pmc:
+    if not full:
         args.no_cpu_baseline, args.extra = True, ""
 
     import numpy as np
-    import torch
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -325,8 +432,16 @@ def main():
     if launched and world != args.gpus:
         # (a line that says n_gpus = N must have run on N GPUs, and the other way round)
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus} (or run plain `python bench.py --gpus N`)")
-    # worker threads of THIS process and their devices: one (the rank's device) under a launcher, N without
+
+    import __graft_entry__ as graft
+    if not os.path.exists(graft.LIB):
+        graft.build()
+    from ccs_amd import api
+
+    # worker threads of THIS process and their devices: one (the rank's device) under a launcher, N without.  torch is imported only for the
+    # launcher's timing collectives: one process drives its devices through the library alone
     if launched and world > 1:
+        import torch
         import torch.distributed as dist
         local_rank = int(os.environ.get("CCSX_BENCH_DEVICE", local_rank))   # test hook: several ranks on one GPU (gloo)
         torch.cuda.set_device(local_rank)
@@ -340,20 +455,14 @@ def main():
         devices = [int(x) for x in env_dev.split(",")] if env_dev else list(range(args.gpus))
         if len(devices) != args.gpus:
             sys.exit(f"bench.py: CCSX_BENCH_DEVICES names {len(devices)} devices, --gpus {args.gpus}")
-        ndev = torch.cuda.device_count()
+        ndev = api.device_count()
         if max(devices) >= ndev:
             sys.exit(f"bench.py: --gpus {args.gpus} needs devices {devices}, this node has {ndev} (no figure is reported for GPUs that do not exist)")
         world = args.gpus
         local_rank = devices[0]
-        torch.cuda.set_device(local_rank)
     nloc = len(devices)
     if not explicit_zmws:
         args.zmws = fit_zmws(args.zmws, args.passes, args.length, world)
-
-    import __graft_entry__ as graft
-    if not os.path.exists(graft.LIB):
-        graft.build()
-    from ccs_amd import api
 
     rank_numa = None
     if launched and world > 1:
@@ -370,8 +479,10 @@ def main():
     def barrier():
         if dist is not None:
             dist.barrier()
-        for d in sorted(set(devices)):
-            torch.cuda.synchronize(d)
+            for d in sorted(set(devices)):
+                torch.cuda.synchronize(d)
+        for j in jobs:
+            j.h.sync()
 
     numa_bound = [None] * nloc                               # NUMA node every worker's thread was bound to (-1: not bound)
 
@@ -401,22 +512,26 @@ def main():
 
     # ---- the headline job: synthetic shards of every worker, distinct batches with distinct ZMW ids (deterministic), page-locked
     jobs = on_workers(lambda i: Job(api, np, rank + i, world, devices[i], args.zmws, args.passes, args.length, args.distinct, args.steps, args.warmup,
-                                    args.depth, make_opts(), keep_sample=4096 if i == 0 else 0))
+                                    args.depth, make_opts(), keep_sample=4096 if i == 0 and full else 0))
     job = jobs[0]
     h = job.h
     t0 = time.time()
     on_workers(lambda i: jobs[i].run(max(1, args.warmup), False))    # untimed: every hipMalloc of the engine happens here
     warm_s = time.time() - t0
     barrier()
+    setup_s = time.time() - T_START                          # start of the script to the start of the timed region
     t_origin = time.perf_counter()                           # ONE origin for every worker's timed region
     timed = on_workers(lambda i: jobs[i].run(args.steps, True, t_origin))
     barrier()
     elapsed, kt, (ok, rqsum, rqn, checks) = timed[0]
+    if args.dump_outputs and rank == 0:
+        last = args.steps - 1                                # the last timed step's batch and result buffers (Job.run submits nothing after it)
+        dump_outputs(np, job.batches[last % job.nb], job.results[last % job.depth], bool(args.hifi_kinetics), args.dump_outputs)
     per_gpu = [{"worker": i, "device": devices[i], "zmws_per_s": round(args.zmws * args.steps / timed[i][0], 2), "ms_per_step": round(timed[i][0] / args.steps * 1e3, 3),
                 "success_frac": timed[i][2][0] / (args.zmws * args.steps),
                 "numa_node": int(api.lib().ccsx_device_numa_node(devices[i])), "thread_bound_to_node": numa_bound[i],
                 "copies_hidden_frac": round(min(1.0, kernels_span_ms(timed[i][1]) * 1e-3 / timed[i][0]), 4)} for i in range(nloc)]
-    if nloc > 1 and not args.pmc:
+    if nloc > 1 and full:
         # every worker uploads one batch AT THE SAME TIME, nothing else running: the H2D rate a GPU gets while its neighbours pull too (cross-socket staging shows here)
         def h2d(i):
             b = jobs[i].batches[0]
@@ -428,14 +543,14 @@ def main():
         elapsed = max(t[0] for t in timed)                   # the job is done when its slowest worker is
         ok = sum(t[2][0] for t in timed) / nloc; checks = sum(t[2][3] for t in timed)
         rqsum = sum(t[2][1] for t in timed); rqn = sum(t[2][2] for t in timed)
-    clocks_after = gpu_clocks(local_rank) if rank == 0 else None     # right after the last timed kernel: the clocks the run settled at
+    clocks_after = gpu_clocks(local_rank) if rank == 0 and full else None     # right after the last timed kernel: the clocks the run settled at
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
     res0, upload_s = None, None
-    if not args.pmc:
+    if full:
         # un-overlapped copy times of one batch (context for the pipeline: what the copies would cost in the open)
         t0 = time.time(); h.upload(job.batches[0]); h.sync(); upload_s = time.time() - t0
         h.run(); h.sync()
@@ -508,23 +623,24 @@ def main():
             "stage_ms_note": "per batch, HIP events on the stream of each stage; with two compute streams the stages of consecutive batches overlap, "
                              "so ms_per_step < draft + align + polish + stitch; queue_ms = the batch waiting between the stages",
             "success_frac": ok / (args.zmws * args.steps), "mean_rq": rqsum / rqn if rqn else None, "consensus_bases": checks,
-            "host": {"synth_s": round(job.gen_s, 2), "warmup_s": round(warm_s, 2), "unoverlapped_upload_s": round(upload_s, 3) if upload_s else None,
+            "host": {"setup_s": round(setup_s, 2), "synth_s": round(job.gen_s, 2), "warmup_s": round(warm_s, 2), "unoverlapped_upload_s": round(upload_s, 3) if upload_s else None,
                      "copies_hidden_frac": round(min(1.0, span_ms * 1e-3 / elapsed), 4),
                      "bam_pipeline_note": "this bench feeds the engine from memory; the `ccs` driver's BAM side costs 0.85-0.94 CPU-s per 1000 ZMWs "
                                           "(BGZF inflate 0.57), i.e. ~28 host cores per MI355X at the engine's rate: 17.0-18.8k ZMWs/s BAM->BAM and 24-28k for "
                                           "the host side alone on this box's 16 usable threads (profiles/r03_cli_host_pipeline.txt, DESIGN.md 7)"},
-            "head": head,
-            "gpu_clocks": {"after_timed_region": clocks_after, "source": "rocm-smi --showclocks --showpower --showmaxpower --showperflevel"},
+            "head": head, "full": full,
         }
         cores = effective_cores()
-        # the reference tool, if the box has it (expected absent; bioconda pbccs): probed, and run when found
-        ccs_bin = shutil.which("ccs")
-        if ccs_bin and os.path.realpath(ccs_bin) == os.path.realpath(os.path.join(ROOT, "ccs_amd", "bin", "ccs")):
-            ccs_bin = None                                   # this repo's own driver is not the reference
-        if ccs_bin and not args.pmc and c2:
-            out["reference_ccs"] = reference_concordance(api, np, ccs_bin, job.sample0.slice(0, min(job.sample0.n_zmw, 4 * cores)), cores, args.cpu_seconds)
-        else:
-            out["reference_ccs"] = {"found": bool(ccs_bin), "path": ccs_bin, "note": "command -v ccs on this box: absent, nothing to run" if not ccs_bin else "present; concordance runs with the default c2 workload"}
+        if full:
+            out["gpu_clocks"] = {"after_timed_region": clocks_after, "source": "rocm-smi --showclocks --showpower --showmaxpower --showperflevel"}
+            # the reference tool, if the box has it (expected absent; bioconda pbccs): probed, and run when found
+            ccs_bin = shutil.which("ccs")
+            if ccs_bin and os.path.realpath(ccs_bin) == os.path.realpath(os.path.join(ROOT, "ccs_amd", "bin", "ccs")):
+                ccs_bin = None                               # this repo's own driver is not the reference
+            if ccs_bin and c2:
+                out["reference_ccs"] = reference_concordance(api, np, ccs_bin, job.sample0.slice(0, min(job.sample0.n_zmw, 4 * cores)), cores, args.cpu_seconds)
+            else:
+                out["reference_ccs"] = {"found": bool(ccs_bin), "path": ccs_bin, "note": "command -v ccs on this box: absent, nothing to run" if not ccs_bin else "present; concordance runs with the default c2 workload"}
         if not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N=1 only
             import oracle_lib
             sample0 = job.sample0
@@ -587,7 +703,7 @@ def main():
                     z_ = fit_zmws(z_, p_, l_, 1)
                     j2 = Job(api, np, 0, 1, local_rank, z_, p_, l_, 2, args.extra_steps, args.depth, args.depth, make_opts())
                     j2.run(args.depth, False)            # one untimed step per batch slot: all device buffers exist before the timed steps
-                    torch.cuda.synchronize()
+                    j2.h.sync()
                     el, kt2, (ok2, rs2, rn2, _) = j2.run(args.extra_steps, True)
                     sm = stage_means(np, kt2)
                     dom2 = max(names, key=lambda k: sm[k])

@@ -595,7 +595,7 @@ def test_bench_gpus_n_runs_n_workers_in_one_process(built):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["CCSX_BENCH_DEVICES"] = "0,0"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--zmws", "48", "--length", "2000", "--distinct", "2",
-           "--no-cpu-baseline", "--extra", ""]
+           "--no-cpu-baseline", "--extra", "", "--full"]        # --full: the per-worker H2D rates
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -623,6 +623,40 @@ def test_bench_gpus_n_runs_n_workers_in_one_process(built):
     assert p1.returncode == 0, p1.stderr[-2000:]
     o1 = json.loads([l for l in p1.stdout.splitlines() if l.startswith("{")][0])
     assert o1["n_gpus"] == 1 and "per_gpu" not in o1
+
+
+def test_bench_plain_run_dumps_its_last_step(built, tmp_path):
+    """a plain `bench.py` run times exactly --steps steps and measures nothing its headline does not need (no CPU baseline, reference probe, other
+    shapes or clocks: those are --full); --dump-outputs writes what the last timed step computed as float arrays, and that is the oracle's consensus
+    of the same batch"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CCSX_BENCH_DEVICES")}
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--zmws", "48", "--length", "2000", "--distinct", "2",
+           "--dump-outputs", str(d)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["full"] is False and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 48 * 3 / (out["ms_per_step"] * 3e-3)) / out["value"] < 1e-3
+    for k in ("cpu_baseline", "extra", "reference_ccs", "gpu_clocks"):
+        assert k not in out, k
+    files = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert all(f.endswith(".npy") for f in os.listdir(d)) and sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64_000_000
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    # steps 0, 1, 2 cycle through 2 distinct batches: the last step ran batch 0 again (ZMW ids 0..47)
+    batch = api.synth(48, 10, 2000, seed=0xC0FFEE, first_zmw_id=0)
+    assert np.array_equal(files["zmw_id"], batch.zmw_id)
+    ref = api.Results.allocate(batch)
+    O.consensus_batch(api.default_model(), api.default_opts(), batch, ref, nthreads=8)
+    assert np.array_equal(files["status"], ref.status) and np.array_equal(files["seq_len"], ref.seq_len) and np.array_equal(files["np"], ref.np_)
+    assert np.allclose(files["rq"], ref.rq, atol=1e-6, rtol=0) and len(files["sample_zmw"]) == 48
+    off = files["sample_seq_off"].astype(np.int64)
+    for i, z in enumerate(files["sample_zmw"].astype(np.int64)):
+        assert np.array_equal(files["seq"][off[i]:off[i + 1]], ref.sequence(z)) and np.array_equal(files["qual"][off[i]:off[i + 1]], ref.quals(z))
 
 
 def test_inserted_blocks_fuzz_matches_oracle(handle):

@@ -9,7 +9,7 @@ H=${2:-unknown}
 Z=${Z:-16384}
 D=$R/gpurun_out/prof_$T
 rm -rf $D; mkdir -p $D
-timeout 900 python $R/bench.py > $D/bench_default.json 2> $D/bench_default.err < /dev/null
+timeout 900 python $R/bench.py --full > $D/bench_default.json 2> $D/bench_default.err < /dev/null
 timeout 400 rocprofv3 --kernel-trace --stats -d $D/trace -o trace -- python $R/bench.py --pmc --steps 6 --warmup 1 --distinct 3 > $D/bench_trace.json 2> $D/bench_trace.err < /dev/null
 python $R/tools/trace_overlap.py $D/trace > $D/overlap.txt 2>&1
 for set in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES" "SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_LDS SQ_INSTS_SMEM" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS"; do
