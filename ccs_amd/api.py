@@ -78,6 +78,68 @@ class CDrafts(C.Structure):
 QV_ONLY = 1     # ccsx_polish_batch flag (CCSX_QV_ONLY)
 
 
+# ---- the heteroduplex finder (include/ccsx.h ccsx_hd_*; DESIGN.md §2 "Heteroduplex rule")
+HD_MAX_SITES, HD_WIN_SITES = 16, 8
+HD_UNTESTED, HD_DOUBLE_STRAND, HD_HETERODUPLEX = 0, 1, 2
+HD_VERDICT_NAMES = {0: "UNTESTED", 1: "DOUBLE_STRAND", 2: "HETERODUPLEX"}
+
+
+class HdOpts(C.Structure):
+    _fields_ = [("min_strand_passes", C.c_int32), ("min_sites", C.c_int32), ("min_indel", C.c_int32), ("min_alt_frac", C.c_float),
+                ("max_pvalue", C.c_double)]
+
+
+class HdSite(C.Structure):
+    _fields_ = [("column", C.c_int32), ("kind", C.c_int8), ("alt", C.c_int8), ("fwd_alt", C.c_uint8), ("fwd_n", C.c_uint8),
+                ("rev_alt", C.c_uint8), ("rev_n", C.c_uint8), ("pad_", C.c_uint8 * 2), ("p", C.c_double)]
+
+
+HD_SITE_DTYPE = np.dtype({"names": ["column", "kind", "alt", "fwd_alt", "fwd_n", "rev_alt", "rev_n", "p"],
+                          "formats": [np.int32, np.int8, np.int8, np.uint8, np.uint8, np.uint8, np.uint8, np.float64],
+                          "offsets": [0, 4, 5, 6, 7, 8, 9, 16], "itemsize": 24})
+
+
+class CHdReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32), ("verdict", C.POINTER(C.c_int32)), ("n_sub_sites", C.POINTER(C.c_int32)),
+                ("n_indel_sites", C.POINTER(C.c_int32)), ("n_listed", C.POINTER(C.c_int32)), ("min_p", C.POINTER(C.c_double)),
+                ("sites", C.POINTER(HdSite)), ("status", C.POINTER(C.c_int32))]
+
+
+def hd_opts_default() -> HdOpts:
+    o = HdOpts()
+    lib().ccsx_hd_opts_default(C.byref(o))
+    return o
+
+
+@dataclass
+class HdReport:
+    """ccsx_hd_report: one verdict per ZMW, the site counts and the listed sites (structured array [n_zmw, HD_MAX_SITES] of HD_SITE_DTYPE)."""
+    verdict: np.ndarray
+    n_sub_sites: np.ndarray
+    n_indel_sites: np.ndarray
+    n_listed: np.ndarray
+    min_p: np.ndarray
+    sites: np.ndarray
+    status: np.ndarray
+
+    @staticmethod
+    def allocate(n: int) -> "HdReport":
+        z = lambda: np.zeros(n, np.int32)
+        return HdReport(z(), z(), z(), z(), np.ones(n), np.zeros((n, HD_MAX_SITES), HD_SITE_DTYPE), z())
+
+    def c_struct(self) -> CHdReport:
+        r = CHdReport()
+        r.n_zmw = len(self.verdict)
+        r.verdict, r.n_sub_sites, r.n_indel_sites, r.n_listed, r.status = (
+            _ptr(a, C.c_int32) for a in (self.verdict, self.n_sub_sites, self.n_indel_sites, self.n_listed, self.status))
+        r.min_p = _ptr(self.min_p, C.c_double)
+        r.sites = self.sites.ctypes.data_as(C.POINTER(HdSite))
+        return r
+
+    def site_list(self, z: int) -> np.ndarray:
+        return self.sites[z, : int(self.n_listed[z])]
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("setup_ms", C.c_float), ("draft_ms", C.c_float), ("align_ms", C.c_float), ("polish_ms", C.c_float),
@@ -99,6 +161,7 @@ EXPORTS = [
     "ccsx_submit", "ccsx_wait", "ccsx_poll", "ccsx_ticket_timings",
     "ccsx_model_from_json", "ccsx_model_load", "ccsx_model_to_json", "ccsx_model_for_chemistry",
     "ccsx_build_flags", "ccsx_runtime_switches", "ccsx_pci_numa_node", "ccsx_device_numa_node", "ccsx_bind_thread_to_node", "ccsx_bind_thread_to_device", "ccsx_draft_layout", "ccsx_draft_batch", "ccsx_polish_batch", "ccsx_submit_draft", "ccsx_submit_polish",
+    "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
 ]
 
 _lib = None
@@ -150,6 +213,9 @@ def lib() -> C.CDLL:
         L.ccsx_polish_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(CResults), C.c_uint32]
         L.ccsx_submit_draft.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(C.c_int64)]
         L.ccsx_submit_polish.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(CResults), C.c_uint32, C.POINTER(C.c_int64)]
+        L.ccsx_hd_opts_default.restype = None
+        L.ccsx_hd_opts_default.argtypes = [C.POINTER(HdOpts)]
+        L.ccsx_hd_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(HdOpts), C.POINTER(CHdReport)]
         _lib = L
     return _lib
 
@@ -520,6 +586,14 @@ class Handle:
         self._check(self._L.ccsx_polish_batch(self._h, C.byref(cb), C.byref(cd), C.byref(cr), flags), "ccsx_polish_batch")
         return res
 
+    # ---- the third seam: the heteroduplex finder on caller-supplied drafts (no polish runs)
+    def hd(self, batch: Batch, drafts: "Drafts", opts: HdOpts | None = None) -> HdReport:
+        rep = HdReport.allocate(batch.n_zmw)
+        cb, cd, cr = batch.c_struct(), drafts.c_struct(), rep.c_struct()
+        o = opts if opts is not None else hd_opts_default()
+        self._check(self._L.ccsx_hd_batch(self._h, C.byref(cb), C.byref(cd), C.byref(o), C.byref(cr)), "ccsx_hd_batch")
+        return rep
+
     def upload(self, batch: Batch):
         self._keep = batch
         cb = batch.c_struct()
@@ -604,3 +678,67 @@ class Handle:
 
 def device_count() -> int:
     return lib().ccsx_device_count()
+
+
+def split_strands(batch: Batch, zmw_mask) -> tuple[Batch, np.ndarray, np.ndarray]:
+    """the selected ZMWs as single-strand ZMWs: for each, its forward passes (flags bit 0 clear) as one ZMW, then its reverse passes as the next, both
+    keeping zmw_id (the `ccs` driver's --by-strand split).  A strand without passes yields no ZMW.  Returns (batch, source ZMW index, strand 0/1) per new ZMW;
+    partial passes stay behind the full-length passes of their strand."""
+    sel = np.flatnonzero(np.asarray(zmw_mask, bool))
+    read_off, base_off, reads, src, strand = [0], [0], [], [], []
+    for z in sel:
+        r0, r1 = int(batch.read_off[z]), int(batch.read_off[z + 1])
+        for s in (0, 1):
+            rr = [r for r in range(r0, r1) if (int(batch.flags[r]) & 1) == s]
+            if not rr:
+                continue
+            rr = [r for r in rr if not batch.flags[r] & 2] + [r for r in rr if batch.flags[r] & 2]
+            reads += rr; src.append(int(z)); strand.append(s)
+            read_off.append(read_off[-1] + len(rr))
+    reads = np.array(reads, np.int64)
+    lens = (batch.base_off[reads + 1] - batch.base_off[reads]) if len(reads) else np.zeros(0, np.int64)
+    base_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    idx = np.concatenate([np.arange(batch.base_off[r], batch.base_off[r + 1]) for r in reads]) if len(reads) else np.zeros(0, np.int64)
+    src = np.array(src, np.int64)
+    out = Batch(np.ascontiguousarray(batch.zmw_id[src]), np.ascontiguousarray(batch.snr[src]), np.array(read_off, np.int32), base_off,
+                np.ascontiguousarray(batch.bases[idx]), np.ascontiguousarray(batch.pw[idx]), np.ascontiguousarray(batch.ipd[idx]),
+                np.ascontiguousarray(batch.flags[reads]))
+    return out, src, np.array(strand, np.int8)
+
+
+@dataclass
+class HdRecord:
+    """one read of the heteroduplex mode: the read group (DS = both strands, fwd / rev = one strand of a heteroduplex,
+    docs/faq/mode-heteroduplex-filtering.md:44-51) and its consensus"""
+    zmw: int
+    zmw_id: int
+    group: str
+    status: int
+    seq: np.ndarray
+    qual: np.ndarray
+    rq: float
+    np_: int
+
+
+def consensus_hd(handle: "Handle", batch: Batch, opts: HdOpts | None = None):
+    """the heteroduplex mode end to end: draft -> hd -> polish of the same drafts -> consensus of the strands of every HETERODUPLEX.  Returns
+    (records, report): one DS record per other ZMW (byte for byte what `consensus` gives), up to two (fwd, rev) per heteroduplex."""
+    drafts = handle.draft(batch)
+    rep = handle.hd(batch, drafts, opts)
+    res = handle.polish(batch, drafts)
+    het = rep.verdict == HD_HETERODUPLEX
+    strands = {}
+    if het.any():
+        sb, src, strand = split_strands(batch, het)
+        sres = handle.consensus(sb)
+        for i in range(sb.n_zmw):
+            strands[(int(src[i]), int(strand[i]))] = (sres, i)
+    recs = []
+    for z in range(batch.n_zmw):
+        parts = [("fwd", strands.get((z, 0))), ("rev", strands.get((z, 1)))] if het[z] else [("DS", (res, z))]
+        for group, got in parts:
+            if got is None:
+                continue
+            r, i = got
+            recs.append(HdRecord(z, int(batch.zmw_id[z]), group, int(r.status[i]), r.sequence(i).copy(), r.quals(i).copy(), float(r.rq[i]), int(r.np_[i])))
+    return recs, rep

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -108,6 +109,7 @@ struct Slot {
     DevBuf d_out_seq, d_out_qual, d_out_raw, d_out_i32 /* 6 x n */, d_out_f32 /* 2 x n */;
     DevBuf d_wtpl, d_wtmeta, d_wkin, d_out_kin;   // HiFi kinetics only
     DevBuf d_din_len, d_din_bb;                   // caller-supplied drafts (ccsx_polish_batch): lengths, orientation references
+    DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
@@ -129,7 +131,8 @@ struct Slot {
         DevBuf *bufs[] = {&d_snr, &d_read_off, &d_base_off, &d_bases, &d_pw, &d_ipd, &d_flags, &d_read_zmw, &d_vcap, &d_dcap, &d_seq_off,
                           &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
                           &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
-                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_din_len, &d_din_bb};
+                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_din_len, &d_din_bb,
+                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites};
         for (auto *b : bufs) b->release();
         read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
         read_off.release(); seq_off.release(); ent_off.release(); base_off.release();
@@ -158,6 +161,7 @@ struct ccsx_handle_s {
     ccsx_model model;
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
+    DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
     Slot slot[CCSX_SLOTS];
     int last = 0;                     // slot of the most recent stage / run (stage accessors, timings)
     int64_t next_ticket = 0;
@@ -176,7 +180,7 @@ static void destroy_handle(ccsx_handle h)
     for (auto &s : h->slot) s.release();
     if (h->ev_epoch) (void)hipEventDestroy(h->ev_epoch);
     if (h->ev_epoch_nx) (void)hipEventDestroy(h->ev_epoch_nx);
-    h->d_model.release(); h->d_poa.release(); h->d_align.release();
+    h->d_model.release(); h->d_poa.release(); h->d_align.release(); h->d_hd_lf.release();
     if (h->s_in) (void)hipStreamDestroy(h->s_in);
     if (h->s_draft && h->s_draft != h->s_comp) (void)hipStreamDestroy(h->s_draft);
     if (h->s_aux) (void)hipStreamDestroy(h->s_aux);
@@ -945,6 +949,70 @@ int ccsx_stage_align(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, int
             rstart[col] = ent[k];
         }
     }
+    return 0;
+}
+
+// ---- the heteroduplex finder: the third seam (include/ccsx.h).  Synchronous, on slot 0 like ccsx_upload / ccsx_run, so that the stage accessors report what it used.
+void ccsx_hd_opts_default(ccsx_hd_opts *o)
+{
+    if (!o) return;
+    o->min_strand_passes = 3; o->min_sites = 1; o->min_indel = 21; o->min_alt_frac = 0.5f; o->max_pvalue = 1e-3;   // DESIGN.md §2 "Heteroduplex rule": the study behind them
+}
+
+int ccsx_hd_rule_version(void) { return 1; }
+
+int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, const ccsx_hd_opts *o, ccsx_hd_report *out)
+{
+    if (!h || !b || !drafts || !out) { ccsx_set_error("ccsx_hd_batch: null argument"); return -1; }
+    ccsx_hd_opts hd;
+    if (o) hd = *o; else ccsx_hd_opts_default(&hd);
+    if (hd.min_strand_passes < 1 || hd.min_sites < 1 || hd.min_indel < 1 || hd.min_indel > 21 || !(hd.min_alt_frac >= 0.0f && hd.min_alt_frac <= 1.0f) ||
+        !(hd.max_pvalue >= 0.0 && hd.max_pvalue <= 1.0)) {
+        ccsx_set_error("ccsx_hd_batch: options out of range (min_strand_passes, min_sites >= 1; 1 <= min_indel <= 21; min_alt_frac, max_pvalue in [0, 1])"); return -1;
+    }
+    if (out->n_zmw != b->n_zmw || !out->verdict || !out->n_sub_sites || !out->n_indel_sites || !out->n_listed || !out->min_p || !out->sites) {
+        ccsx_set_error("ccsx_hd_batch: report arrays missing, or sized for another batch"); return -1;
+    }
+    if (h->poisoned) { ccsx_set_error("ccsx_hd_batch: an earlier submit failed after work had been enqueued; destroy the handle"); return -2; }
+    int rc = ccsx_upload(h, b);
+    if (rc) return rc;
+    Slot &S = h->slot[0];
+    if ((rc = check_drafts(S, drafts, true))) { S.staged = false; return rc; }
+    const int n = S.P.n_zmw;
+    const size_t wins = (size_t)S.P.total_wslots + 1;
+    if (!h->d_hd_lf.p) {                                     // log k!, a sequential sum of log(k) in double (the rule's table)
+        std::vector<double> lf(CCSX_HD_LF_N, 0.0);
+        for (int q = 1; q < CCSX_HD_LF_N; ++q) lf[q] = lf[q - 1] + std::log((double)q);
+        if (h->d_hd_lf.reserve(lf.size() * 8)) return -2;
+        HIPTRY(hipMemcpy(h->d_hd_lf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice));
+    }
+    if (S.d_din_len.reserve((size_t)n * 4) || S.d_din_bb.reserve((size_t)n * 4) || S.d_hd_wcnt.reserve(wins * 4) ||
+        S.d_hd_wrec.reserve(wins * CCSX_HD_WIN_SITES * sizeof(ccsx_hd_site)) || S.d_hd_wminp.reserve(wins * 8) ||
+        S.d_hd_isite.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site)) || S.d_hd_zi.reserve((size_t)n * 5 * 4) ||
+        S.d_hd_minp.reserve((size_t)n * 8) || S.d_hd_sites.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site))) { S.staged = false; return -2; }
+    HIPTRY(hipMemcpy(S.d_draft.p, drafts->seq, (size_t)S.seq_off[n], hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(S.d_din_len.p, drafts->len, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(S.d_din_bb.p, drafts->backbone, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPTRY(hipMemset(S.d_hd_sites.p, 0, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site)));
+    KParams &P = S.P;
+    P.din_len = (const int32_t *)S.d_din_len.p; P.din_bb = (const int32_t *)S.d_din_bb.p;
+    P.opts.no_fallback_draft = 1;                            // (the alignment's outcome on the caller's draft is final, as in the polish seam)
+    P.hd = hd; P.hd_lf = (const double *)h->d_hd_lf.p;
+    P.hd_wcnt = (int32_t *)S.d_hd_wcnt.p; P.hd_wrec = (ccsx_hd_site *)S.d_hd_wrec.p; P.hd_wminp = (double *)S.d_hd_wminp.p;
+    P.hd_isite = (ccsx_hd_site *)S.d_hd_isite.p; P.hd_zi = (int32_t *)S.d_hd_zi.p; P.hd_minp = (double *)S.d_hd_minp.p;
+    P.hd_sites = (ccsx_hd_site *)S.d_hd_sites.p;
+    S.mode = CCSX_RUN_HD;
+    rc = launch(h, S);
+    S.mode = CCSX_RUN_FUSED;                                 // (slot 0's next ccsx_run is the fused path again: ccsx_upload re-stages everything the finder changed)
+    if (rc) return rc;
+    if ((rc = ccsx_sync(h))) return rc;
+    HIPTRY(hipMemcpy(out->verdict, P.hd_zi, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out->n_sub_sites, P.hd_zi + n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out->n_indel_sites, P.hd_zi + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out->n_listed, P.hd_zi + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out->min_p, P.hd_minp, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(out->sites, P.hd_sites, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site), hipMemcpyDeviceToHost));
+    if (out->status) HIPTRY(hipMemcpy(out->status, P.zstat, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

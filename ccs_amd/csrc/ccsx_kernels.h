@@ -99,10 +99,24 @@ struct KParams {
     int32_t align16_slots;
     int32_t *retry_scratch;    // the 64-row retry's / split alignment's slots: behind k_align16's in the same buffer (the trace-backs run beside the next launch / the retry)
     int32_t align16_regions;   // 1, or 2 when the batch's quads take several launches: launch c uses region c & 1, so its trace-back runs under launch c + 1
+    // ---- heteroduplex finder (ccsx_hd_batch only; NULL otherwise).  Per-window outputs use the compact window index of k_wmap
+    ccsx_hd_opts hd;
+    const double *hd_lf;       // [CCSX_HD_LF_N] log k! (host-built, DESIGN.md §2 "Heteroduplex rule")
+    int32_t *hd_wcnt;          // [windows] substitution sites of the window
+    ccsx_hd_site *hd_wrec;     // [windows][CCSX_HD_WIN_SITES] the window's sites with the lowest columns, in column order
+    double *hd_wminp;          // [windows] smallest p of the window's sites (1 = none)
+    ccsx_hd_site *hd_isite;    // [n][CCSX_HD_MAX_SITES] large-indel sites with the lowest (column, kind)
+    int32_t *hd_zi;            // [5][n] verdict, sub sites, indel sites, listed, indel sites listed
+    double *hd_minp;           // [n]
+    ccsx_hd_site *hd_sites;    // [n][CCSX_HD_MAX_SITES]
 };
 
-// which stages ccsx_launch_all enqueues: the fused path, the draft stage alone (ccsx_draft_batch), or alignment cascade + polish on caller-supplied drafts
-enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2 };
+#define CCSX_HD_LF_N (2 * CCSX_MAX_PASSES + 1)   // log-factorials 0 .. 510: a Fisher table never holds more passes than that
+#define CCSX_HD_IMAX 49                          // rows of a segment the pileup aligns: template columns (<= 29) + min_indel - 1 (<= 20)
+
+// which stages ccsx_launch_all enqueues: the fused path, the draft stage alone (ccsx_draft_batch), alignment cascade + polish on caller-supplied drafts, or
+// alignment cascade + the heteroduplex finder on caller-supplied drafts (ccsx_hd_batch)
+enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2, CCSX_RUN_HD = 3 };
 
 const char *ccsx_launch_all(const KParams &P, hipStream_t st_draft, hipStream_t st_polish, hipEvent_t *ev /* [7] */, int mode = CCSX_RUN_FUSED,
                             hipStream_t st_aux = nullptr, hipEvent_t *ev_aux /* [7] */ = nullptr);   // NULL, or the name of the launch that failed; st_aux: second stream of the POA stage (half-batches)

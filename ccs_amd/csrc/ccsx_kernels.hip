@@ -3471,6 +3471,323 @@ __global__ __launch_bounds__(64) void k_stitch(KParams P)
 }
 
 // ------------------------------------------------------------------------------------------------
+// The heteroduplex finder (ccsx_hd_batch; DESIGN.md §2 "Heteroduplex rule", §4).  Runs after the alignment cascade and the window map of the polish seam, on
+// the same inputs k_polish gets (draft, window bounds, entry rows), before any insertion trim.  Three kernels:
+//   k_hd_pile     a group of HD_WG_WIN consecutive windows per one-wave workgroup: the unit-cost edit DP of every (pass, window) segment against the window
+//                 template, one segment per lane (the windows' segments are pooled, so at 10 passes the 64 lanes serve 6-7 windows at once), 2-bit moves in
+//                 LDS, the trace-back's core-column outcomes counted per strand with LDS integer atomics (independent of which lane ran which segment), then the
+//                 column test in the same workgroup: per window a site count, its lowest sites in column order and their smallest p
+//   k_hd_indel    one wave per ZMW: the 1-3-window length excesses from the entry rows, events merged over adjacent windows, their Fisher tests
+//   k_hd_verdict  one wave per ZMW: counts, the ordered site list (a merge of the per-window lists and the indel list: no global atomics) and the verdict
+#define HD_WG_WIN 16
+
+// two-sided Fisher exact p of [[a, nf - a], [c, nr - c]]: the tables with the same margins whose probability is <= p_obs (1 + 1e-7), summed in increasing
+// order of the top-left cell; log k! from the host's table (tests/hd_ref.py restates it operation for operation)
+__device__ double hd_fisher(const double *lf, int a, int nf, int c, int nr)
+{
+    const int m = a + c, N = nf + nr;
+    const double base = lf[nf] + lf[nr] + lf[m] + lf[N - m] - lf[N];
+    const double thr = exp(base - lf[a] - lf[nf - a] - lf[m - a] - lf[nr - m + a]) * (1.0 + 1e-7);
+    const int lo = m - nr > 0 ? m - nr : 0, hi = nf < m ? nf : m;
+    double p = 0.0;
+    for (int x = lo; x <= hi; ++x) {
+        const double px = exp(base - lf[x] - lf[nf - x] - lf[m - x] - lf[nr - m + x]);
+        if (px <= thr) p += px;
+    }
+    return p < 1.0 ? p : 1.0;
+}
+
+// window w of a ZMW: template draft[ws, we) and the indices of its two entry rows (the same expressions as k_polish)
+struct HdWin { int ws, we, iws, iwe; };
+__device__ __forceinline__ HdWin hd_win(const int32_t *wb, int nw, int Ld, int w)
+{
+    HdWin g;
+    g.ws = wb[w] - CCSX_WIN_OVERHANG; if (g.ws < 0) g.ws = 0;
+    g.we = wb[w + 1] + CCSX_WIN_OVERHANG; if (g.we > Ld) g.we = Ld;
+    g.iws = (w == 0) ? 0 : 2 * w - 1;
+    g.iwe = (w == nw - 1) ? 2 * nw - 1 : 2 * (w + 1);
+    return g;
+}
+
+__device__ __forceinline__ bool hd_site_less(const ccsx_hd_site &x, const ccsx_hd_site &y) { return x.column < y.column || (x.column == y.column && x.kind < y.kind); }
+
+__global__ __launch_bounds__(64) void k_hd_pile(KParams P)
+{
+    __shared__ uint64_t sMv[CCSX_HD_IMAX * 64];               // [row - 1][lane]: 2-bit moves of columns 1 .. 31 (0 diagonal, 1 deletion, 2 insertion)
+    __shared__ uint32_t sCnt[HD_WG_WIN][32][2][2];            // [window][column][strand]: A|C|G|T counts (a byte each), deletions
+    __shared__ uint64_t sTpl[HD_WG_WIN];                      // window template, 2 bits per column
+    __shared__ int sW[HD_WG_WIN][8];                          // z, ws, J, cs, ce, r0, fl0, iws | iwe << 16
+    __shared__ int sOff[HD_WG_WIN + 1];                       // first task (pass) of each window
+    const int lane = threadIdx.x;
+    const int nwin_all = P.wstart[P.n_zmw];
+    const int k0 = blockIdx.x * HD_WG_WIN;
+    if (k0 >= nwin_all) return;
+    for (int q = lane; q < HD_WG_WIN * 32 * 4; q += 64) (&sCnt[0][0][0][0])[q] = 0u;
+    int np = 0;
+    if (lane < HD_WG_WIN) {
+        const int k = k0 + lane;
+        if (k < nwin_all) {
+            const int z = P.wslot_zmw[k], nw = P.nwin[z], Ld = P.draft_len[z], w = k - P.wstart[z];
+            const int32_t *wb = P.wbounds + P.wb_off[z];
+            const HdWin g = hd_win(wb, nw, Ld, w);
+            const int J = g.we - g.ws;
+            const uint8_t *d = P.draft + P.seq_off[z];
+            uint64_t t = 0;
+            for (int j = 0; j < J && j < 31; ++j) t |= (uint64_t)(d[g.ws + j] & 3) << (2 * j);
+            const int r0 = P.read_off[z];
+            sTpl[lane] = t;
+            sW[lane][0] = z; sW[lane][1] = g.ws; sW[lane][2] = J; sW[lane][3] = wb[w] - g.ws; sW[lane][4] = wb[w + 1] - g.ws;
+            sW[lane][5] = r0; sW[lane][6] = P.flags[r0 + (P.zref[z] & 255)] & 1; sW[lane][7] = g.iws | (g.iwe << 16);
+            np = J <= 31 ? P.nreads_used[z] : 0;
+        }
+    }
+    const int incl = wave_scan_add_i32(np);                   // (lanes 16..63 add 0)
+    if (lane < HD_WG_WIN) sOff[lane + 1] = incl;
+    if (lane == 0) sOff[0] = 0;
+    __syncthreads();
+    const int T = sOff[HD_WG_WIN];
+    const int mi = P.hd.min_indel;
+    for (int t = lane; t < T; t += 64) {
+        int k = 0;
+        while (k < HD_WG_WIN - 1 && sOff[k + 1] <= t) ++k;
+        const int r = sW[k][5] + (t - sOff[k]);
+        if (!P.avalid[r]) continue;
+        const int64_t eo = P.ent_off[r], bo = P.base_off[r];
+        const int L = (int)(P.base_off[r + 1] - bo);
+        const int a = P.ent[eo + (sW[k][7] & 0xffff)], n = P.ent[eo + (sW[k][7] >> 16)] - a;
+        const int J = sW[k][2];
+        if (a < 0 || n < 0 || a + n > L || n > CCSX_HD_IMAX || n - J >= mi || J - n >= mi) continue;   // (rows of this pass only)
+        const int st = (P.flags[r] & 1) ^ sW[k][6];
+        // the segment in draft orientation, 2 bits per base (rows 1..32 in s0, 33..49 in s1)
+        uint64_t s0 = 0, s1 = 0;
+        for (int i = 0; i < n; ++i) {
+            const int b = st ? 3 - (P.bases[bo + (L - 1 - a - i)] & 3) : (P.bases[bo + a + i] & 3);
+            if (i < 32) s0 |= (uint64_t)b << (2 * i); else s1 |= (uint64_t)b << (2 * (i - 32));
+        }
+        const uint64_t tpl = sTpl[k];
+        int D[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) D[j] = j;
+        for (int i = 1; i <= n; ++i) {
+            const int rb = (int)((i <= 32 ? s0 >> (2 * (i - 1)) : s1 >> (2 * (i - 33))) & 3);
+            int diag = D[0], left = i;
+            D[0] = i;
+            uint64_t mv = 0;
+#pragma unroll
+            for (int j = 1; j < 32; ++j) {                    // tie order diagonal < deletion < insertion (strict compares)
+                const int up = D[j];
+                const int dv = diag + (rb != (int)((tpl >> (2 * (j - 1))) & 3) ? 1 : 0);
+                int best = dv, m = 0;
+                if (left + 1 < best) { best = left + 1; m = 1; }
+                if (up + 1 < best) { best = up + 1; m = 2; }
+                mv |= (uint64_t)m << (2 * (j - 1));
+                diag = up; D[j] = best; left = best;
+            }
+            sMv[(i - 1) * 64 + lane] = mv;
+        }
+        const int cs = sW[k][3], ce = sW[k][4];
+        int i = n, j = J;
+        while (i > 0 || j > 0) {
+            const int m = i == 0 ? 1 : (j == 0 ? 2 : (int)((sMv[(i - 1) * 64 + lane] >> (2 * (j - 1))) & 3));
+            if (m != 2) {
+                const int c = j - 1;
+                if (c >= cs && c < ce) {
+                    if (m == 0) {
+                        const int rb = (int)((i <= 32 ? s0 >> (2 * (i - 1)) : s1 >> (2 * (i - 33))) & 3);
+                        atomicAdd(&sCnt[k][c][st][0], 1u << (8 * rb));
+                    } else atomicAdd(&sCnt[k][c][st][1], 1u);
+                }
+                --j;
+            }
+            if (m != 1) --i;
+        }
+    }
+    __syncthreads();
+    // the column test: two windows per step, lane & 31 = the template column
+    const int c = lane & 31;
+    for (int k = lane >> 5; k < HD_WG_WIN; k += 2) {
+        const int kg = k0 + k;
+        bool site = false;
+        ccsx_hd_site rec;
+        rec.p = 1.0;
+        if (kg < nwin_all && c >= sW[k][3] && c < sW[k][4]) {
+            const uint32_t f4 = sCnt[k][c][0][0], r4 = sCnt[k][c][1][0];
+            const int nf = (int)((f4 & 255) + ((f4 >> 8) & 255) + ((f4 >> 16) & 255) + (f4 >> 24) + sCnt[k][c][0][1]);
+            const int nr = (int)((r4 & 255) + ((r4 >> 8) & 255) + ((r4 >> 16) & 255) + (r4 >> 24) + sCnt[k][c][1][1]);
+            const int db = (int)((sTpl[k] >> (2 * c)) & 3);
+            int alt = -1, best = 0;
+            for (int b = 0; b < 4; ++b) {
+                const int tot = (int)(((f4 >> (8 * b)) & 255) + ((r4 >> (8 * b)) & 255));
+                if (b != db && tot > best) { best = tot; alt = b; }
+            }
+            if (alt >= 0 && nf >= P.hd.min_strand_passes && nr >= P.hd.min_strand_passes) {
+                const int fa = (int)((f4 >> (8 * alt)) & 255), ra = (int)((r4 >> (8 * alt)) & 255);
+                const double fr = (double)P.hd.min_alt_frac;
+                if ((double)fa >= fr * (double)nf || (double)ra >= fr * (double)nr) {
+                    rec.p = hd_fisher(P.hd_lf, fa, nf, ra, nr);
+                    if (rec.p <= P.hd.max_pvalue) {
+                        site = true;
+                        rec.column = sW[k][1] + c; rec.kind = 0; rec.alt = (int8_t)alt;
+                        rec.fwd_alt = (uint8_t)fa; rec.fwd_n = (uint8_t)nf; rec.rev_alt = (uint8_t)ra; rec.rev_n = (uint8_t)nr;
+                        rec.pad_[0] = rec.pad_[1] = 0;
+                    }
+                }
+            }
+        }
+        const unsigned long long ball = __ballot(site);
+        const unsigned half = (unsigned)(ball >> (lane & 32));
+        const int pos = __popc(half & ((1u << c) - 1u)), cnt = __popc(half);
+        double mp = site ? rec.p : 1.0;
+        for (int o = 16; o >= 1; o >>= 1) { const double q = __shfl_xor(mp, o, 32); mp = q < mp ? q : mp; }
+        if (kg < nwin_all) {
+            if (site && pos < CCSX_HD_WIN_SITES) P.hd_wrec[(size_t)kg * CCSX_HD_WIN_SITES + pos] = rec;
+            if (c == 0) { P.hd_wcnt[kg] = cnt; P.hd_wminp[kg] = mp; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_hd_indel(KParams P)
+{
+    const int z = blockIdx.x, lane = threadIdx.x;
+    if (z >= P.n_zmw) return;
+    const int n = P.n_zmw;
+    ccsx_hd_site *out = P.hd_isite + (size_t)z * CCSX_HD_MAX_SITES;
+    const int nw = P.zstat[z] == CCSX_SUCCESS ? P.nwin[z] : 0;
+    const int Ld = P.draft_len[z], r0 = P.read_off[z], np = P.nreads_used[z], mi = P.hd.min_indel;
+    const int fl0 = P.flags[r0 + (P.zref[z] & 255)] & 1;
+    const int32_t *wb = P.wbounds + P.wb_off[z];
+    int n_ind = 0, listed = 0;
+    double minp = 1.0;
+    // per lane and group of 64 passes: event / coverage bits of the open insertion (bit 0, 1) and deletion (bit 2, 3) cluster
+    int state[4] = {0, 0, 0, 0};
+    int open_i = -1, open_d = -1;
+    for (int w = 0; w <= nw; ++w) {
+        int ev[4] = {0, 0, 0, 0};                              // bit 0 insertion event, bit 1 deletion event, bit 2 the one-window segment is valid
+        int anyI = 0, anyD = 0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int p = g * 64 + lane;
+            if (w < nw && p < np && P.avalid[r0 + p]) {
+                const int r = r0 + p;
+                const int64_t eo = P.ent_off[r];
+                const int L = (int)(P.base_off[r + 1] - P.base_off[r]);
+                const HdWin g0 = hd_win(wb, nw, Ld, w);
+                const int a = P.ent[eo + g0.iws];
+                int e = 0;
+                for (int s = 0; s < 3 && w + s < nw; ++s) {
+                    const HdWin g1 = hd_win(wb, nw, Ld, w + s);
+                    const int len = P.ent[eo + g1.iwe] - a;
+                    if (len < 0 || len > L) continue;
+                    const int ex = len - (g1.we - g0.ws);
+                    if (s == 0) e |= 4;
+                    if (ex >= mi) e |= 1;
+                    if (-ex >= mi) e |= 2;
+                }
+                ev[g] = e;
+            }
+            anyI |= __ballot(ev[g] & 1) != 0ull;
+            anyD |= __ballot(ev[g] & 2) != 0ull;
+        }
+        for (int sign = 0; sign < 2; ++sign) {
+            const int any = sign ? anyD : anyI;
+            int &open = sign ? open_d : open_i;
+            const int eb = sign ? 2 : 1, sh = 2 * sign;
+            if (any) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int e = (ev[g] & eb) ? 1 : 0, cv = (ev[g] & 4) ? 1 : 0;
+                    const int old = (state[g] >> sh) & 3;
+                    const int nv = open < 0 ? (e | (cv << 1)) : ((old & 1) | e) | ((old & 2) & (cv << 1));
+                    state[g] = (state[g] & ~(3 << sh)) | (nv << sh);
+                }
+                if (open < 0) open = w;
+            } else if (open >= 0) {                            // the cluster ended at w - 1: its Fisher table
+                int fa = 0, fn = 0, ra = 0, rn = 0;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int p = g * 64 + lane;
+                    const int sv = (state[g] >> sh) & 3;
+                    const int st = p < np ? ((P.flags[r0 + p] & 1) ^ fl0) : 0;
+                    const bool counted = p < np && sv != 0;
+                    fa += __popcll(__ballot(counted && (sv & 1) && !st)); fn += __popcll(__ballot(counted && !st));
+                    ra += __popcll(__ballot(counted && (sv & 1) && st));  rn += __popcll(__ballot(counted && st));
+                }
+                if (fn >= P.hd.min_strand_passes && rn >= P.hd.min_strand_passes) {
+                    const double p = hd_fisher(P.hd_lf, fa, fn, ra, rn);
+                    if (p <= P.hd.max_pvalue) {
+                        ++n_ind;
+                        minp = p < minp ? p : minp;
+                        if (lane == 0) {
+                            ccsx_hd_site s;
+                            s.column = wb[open]; s.kind = (int8_t)(1 + sign); s.alt = -1;
+                            s.fwd_alt = (uint8_t)fa; s.fwd_n = (uint8_t)fn; s.rev_alt = (uint8_t)ra; s.rev_n = (uint8_t)rn; s.pad_[0] = s.pad_[1] = 0; s.p = p;
+                            // the CCSX_HD_MAX_SITES lowest (column, kind), sorted (clusters close out of column order only across the two signs)
+                            int q = listed < CCSX_HD_MAX_SITES ? listed : CCSX_HD_MAX_SITES - 1;
+                            if (listed < CCSX_HD_MAX_SITES || hd_site_less(s, out[q])) {
+                                while (q > 0 && hd_site_less(s, out[q - 1])) { out[q] = out[q - 1]; --q; }
+                                out[q] = s;
+                            }
+                        }
+                        listed += listed < CCSX_HD_MAX_SITES ? 1 : 0;
+                    }
+                }
+                open = -1;
+            }
+        }
+    }
+    if (lane == 0) { P.hd_zi[2 * (size_t)n + z] = n_ind; P.hd_zi[4 * (size_t)n + z] = listed; P.hd_minp[z] = minp; }
+}
+
+__global__ __launch_bounds__(64) void k_hd_verdict(KParams P)
+{
+    __shared__ ccsx_hd_site sL[2 * CCSX_HD_MAX_SITES];        // [0, 16): substitution sites in column order, [16, 32): the indel list
+    const int z = blockIdx.x, lane = threadIdx.x;
+    if (z >= P.n_zmw) return;
+    const int n = P.n_zmw;
+    const bool ok = P.zstat[z] == CCSX_SUCCESS;
+    const int nw = ok ? P.nwin[z] : 0, a0 = P.wstart[z];
+    int nsub = 0, ns = 0;
+    double minp = P.hd_minp[z];
+    for (int w0 = 0; w0 < nw; w0 += 64) {
+        const int w = w0 + lane;
+        const int cnt = w < nw ? P.hd_wcnt[a0 + w] : 0;
+        double mp = w < nw ? P.hd_wminp[a0 + w] : 1.0;
+        for (int o = 32; o >= 1; o >>= 1) { const double q = __shfl_xor(mp, o); mp = q < mp ? q : mp; }
+        minp = mp < minp ? mp : minp;
+        nsub += wave_reduce_add_i32(cnt);
+        unsigned long long m = __ballot(cnt > 0);
+        while (m && ns < CCSX_HD_MAX_SITES) {                  // windows with sites, in order: ordered compaction of their lists
+            const int wl = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int kg = a0 + w0 + wl;
+            int c = P.hd_wcnt[kg];
+            c = c < CCSX_HD_WIN_SITES ? c : CCSX_HD_WIN_SITES;
+            c = c < CCSX_HD_MAX_SITES - ns ? c : CCSX_HD_MAX_SITES - ns;
+            if (lane < c) sL[ns + lane] = P.hd_wrec[(size_t)kg * CCSX_HD_WIN_SITES + lane];
+            ns += c;
+        }
+    }
+    const int nind = ok ? P.hd_zi[2 * (size_t)n + z] : 0, ni = ok ? P.hd_zi[4 * (size_t)n + z] : 0;
+    if (lane < ni) sL[CCSX_HD_MAX_SITES + lane] = P.hd_isite[(size_t)z * CCSX_HD_MAX_SITES + lane];
+    __syncthreads();
+    int listed = 0;
+    if (lane == 0) {                                           // merge the two sorted lists: the CCSX_HD_MAX_SITES lowest (column, kind)
+        ccsx_hd_site *out = P.hd_sites + (size_t)z * CCSX_HD_MAX_SITES;
+        int x = 0, y = 0;
+        while (listed < CCSX_HD_MAX_SITES && (x < ns || y < ni)) {
+            const bool take_sub = y >= ni || (x < ns && !hd_site_less(sL[CCSX_HD_MAX_SITES + y], sL[x]));
+            out[listed++] = take_sub ? sL[x++] : sL[CCSX_HD_MAX_SITES + y++];
+        }
+        const int fn = P.out_fn[z], rn = P.out_rn[z], msp = P.hd.min_strand_passes;
+        const int verdict = !ok ? CCSX_HD_UNTESTED
+                          : (nsub >= P.hd.min_sites || nind >= 1) ? CCSX_HD_HETERODUPLEX
+                          : (fn >= msp && rn >= msp) ? CCSX_HD_DOUBLE_STRAND : CCSX_HD_UNTESTED;
+        P.hd_zi[z] = verdict; P.hd_zi[(size_t)n + z] = ok ? nsub : 0; P.hd_zi[2 * (size_t)n + z] = nind; P.hd_zi[3 * (size_t)n + z] = listed;
+        P.hd_minp[z] = ok ? minp : 1.0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launch wrappers (called from ccsx_api.cpp, which is plain C++)
 static void trace_sync(hipStream_t st, const char *what)
 {
@@ -3521,15 +3838,16 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     // the second round of launches costs microseconds unless something failed)
     // CCSX_RUN_POLISH (the polish seam): the drafts are the caller's — k_draft_in instead of the generators, one alignment round whose outcome is final
     // (P.opts.no_fallback_draft is set for such a run)
-    if (mode == CCSX_RUN_POLISH) {
+    const bool caller_drafts = mode == CCSX_RUN_POLISH || mode == CCSX_RUN_HD;   // (ccsx_hd_batch: the polish seam's first half on the caller's drafts)
+    if (caller_drafts) {
         hipLaunchKernelGGL(k_draft_in, dim3(P.n_zmw), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_draft_in");
     }
-    for (int pass = 0; pass < ((P.opts.no_fallback_draft || mode == CCSX_RUN_POLISH) ? 1 : 3); ++pass) {
+    for (int pass = 0; pass < ((P.opts.no_fallback_draft || caller_drafts) ? 1 : 3); ++pass) {
         int cov = pass ? 2 * P.opts.max_poa_cov : P.opts.max_poa_cov;
         if (cov > PW_MAXREADS_SPEC) cov = PW_MAXREADS_SPEC;
         if (cov > P.max_reads) cov = P.max_reads;          // no ZMW of the batch has more passes
-        for (int z0 = 0; z0 < P.n_zmw && mode != CCSX_RUN_POLISH; z0 += P.poa_slots) {
+        for (int z0 = 0; z0 < P.n_zmw && !caller_drafts; z0 += P.poa_slots) {
             const int nb = (P.n_zmw - z0) < P.poa_slots ? (P.n_zmw - z0) : P.poa_slots;
             // the graphs [g0, g0 + ng) on stream s: initial graph, one DP (four graphs per wave) + one threading kernel per pass of the POA, heaviest path
             auto poa_range = [&](hipStream_t s, int g0, int ng, hipEvent_t after_first_dp, hipEvent_t before_first_dp) {
@@ -3619,6 +3937,20 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     LAUNCH_CHECK("k_wmap");
     hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
     LAUNCH_CHECK("k_wmap_fill");
+    if (mode == CCSX_RUN_HD) {                                     // the heteroduplex finder instead of the polish stage, on the same stream
+        if (ev) for (int k : {3, 6}) if (hipEventRecord(ev[k], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;   // (the grid covers the slot capacity, the map only the windows there are)
+        hipLaunchKernelGGL(k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_hd_pile");
+        hipLaunchKernelGGL(k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_hd_indel");
+        if (ev && hipEventRecord(ev[4], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        hipLaunchKernelGGL(k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_hd_verdict");
+        trace_sync(st, "k_hd");
+        if (ev && hipEventRecord(ev[5], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        return failed;
+    }
     if (ev) {
         if (hipEventRecord(ev[3], st) != hipSuccess && !failed) failed = "hipEventRecord";
         if (st_polish != st && hipStreamWaitEvent(st_polish, ev[3], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";

@@ -272,6 +272,41 @@ int         ccsx_stage_align(ccsx_handle h, int32_t read_index, int32_t *rstart,
                              int32_t *valid, int32_t *score);
 int         ccsx_stage_windows(ccsx_handle h, int32_t zmw_index, int32_t *bounds, int32_t cap, int32_t *n_windows);
 
+/* ---- the heteroduplex finder (docs/faq/mode-heteroduplex-filtering.md:25-33, docs/how-does-ccs-work.md:65-72; the rule: DESIGN.md §2 "Heteroduplex rule").
+ * ccsx_hd_batch is the third seam beside ccsx_draft_batch and ccsx_polish_batch: on the caller's drafts it runs the polish seam's alignment cascade and window map,
+ * then a strand-resolved substitution pileup and the large-indel test per window, and reduces them to one verdict per ZMW.  No polish runs.  Afterwards
+ * ccsx_stage_draft / ccsx_stage_windows / ccsx_stage_align report what it used.  The rule has its own version (ccsx_hd_rule_version): it changes no result of
+ * the consensus, so CCSX_SPEC_VERSION does not move.                                                                                                           */
+#define CCSX_HD_MAX_SITES 16     /* sites listed per ZMW: the ones with the lowest columns, in column order                                                   */
+#define CCSX_HD_WIN_SITES 8      /* substitution sites per window that can enter the list (the window's lowest columns); the counts cover all sites             */
+typedef struct ccsx_hd_opts {
+    int32_t min_strand_passes;   /* passes needed on EACH strand at a column / event (and for a DOUBLE_STRAND verdict)                                          */
+    int32_t min_sites;           /* substitution sites that make a heteroduplex                                                                                */
+    int32_t min_indel;           /* a length excess of at least this many bases over 1-3 windows is a large-indel event (1 ..  21)                                */
+    float   min_alt_frac;        /* the alternative base's share of a strand's outcomes, on at least one strand                                                  */
+    double  max_pvalue;          /* two-sided Fisher exact test of the alternative against the strands                                                          */
+} ccsx_hd_opts;
+enum ccsx_hd_verdict { CCSX_HD_UNTESTED = 0, CCSX_HD_DOUBLE_STRAND = 1, CCSX_HD_HETERODUPLEX = 2 };
+typedef struct ccsx_hd_site {
+    int32_t column;              /* draft column (substitution), first core column of the event's first window (large indel)                                    */
+    int8_t  kind;                /* 0 substitution, 1 large insertion, 2 large deletion                                                                        */
+    int8_t  alt;                 /* substitution: the alternative base 0..3; -1 for an indel                                                                    */
+    uint8_t fwd_alt, fwd_n, rev_alt, rev_n;   /* the Fisher table: passes with the alternative / passes counted, per strand relative to the draft                */
+    uint8_t pad_[2];
+    double  p;
+} ccsx_hd_site;
+typedef struct ccsx_hd_report {
+    int32_t n_zmw;
+    int32_t *verdict;            /* [n_zmw] enum ccsx_hd_verdict                                                                                               */
+    int32_t *n_sub_sites, *n_indel_sites, *n_listed;   /* [n_zmw]                                                                                               */
+    double  *min_p;              /* [n_zmw] smallest p of any site, 1 when there is none                                                                        */
+    ccsx_hd_site *sites;         /* [n_zmw * CCSX_HD_MAX_SITES]                                                                                                 */
+    int32_t *status;             /* [n_zmw] enum ccsx_status after the alignment cascade (anything but SUCCESS: UNTESTED); may be NULL                          */
+} ccsx_hd_report;
+void        ccsx_hd_opts_default(ccsx_hd_opts *o);
+int         ccsx_hd_rule_version(void);
+int         ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, const ccsx_hd_opts *o, ccsx_hd_report *out);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
