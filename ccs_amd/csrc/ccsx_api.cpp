@@ -117,8 +117,8 @@ struct Slot {
     hipEvent_t ev[7] = {}, ev_up = nullptr, ev_done = nullptr;   // ev[0..5]: stage boundaries, ev[6]: start of the polish stage
     hipEvent_t ev_aux[7] = {};                                   // second stream: fork / first DP done / join of the POA stage; k_align16 launch done x 2, its trace-back done x 2
     bool staged = false, ran = false, inflight = false;
-    bool tm_ok = false; ccsx_timings tm{};   // the slot's timings as taken by ccsx_wait (valid until the slot is staged again)
-    ccsx_results *res = nullptr;      // destination of an in-flight submit
+    bool tm_ok = false; ccsx_timings tm{};   // the slot's timings as taken by retire() (valid until the slot is staged again)
+    ccsx_results *res = nullptr;      // destination of an in-flight submit (cleared by retire(): the caller's struct is not touched again)
     ccsx_drafts *drafts_out = nullptr; // ... of an in-flight ccsx_submit_draft
     int mode = CCSX_RUN_FUSED;
     int64_t ticket = -1;
@@ -168,16 +168,62 @@ struct ccsx_handle_s {
     int handles_on_device = 1;        // share of the device's free memory this handle may take for scratch
 };
 
+// the host-side part of a finished slot's outputs: the capacity-layout offsets the caller's structs carry, and the drafts' backbone words without the cascade's marks
+static void finish_outputs(const Slot &S, ccsx_results *res, ccsx_drafts *d)
+{
+    const int n = S.P.n_zmw;
+    if (res && res->seq_off) std::memcpy(res->seq_off, S.seq_off.p, (size_t)(n + 1) * 8);
+    if (d) {
+        std::memcpy(d->seq_off, S.seq_off.p, (size_t)(n + 1) * 8);
+        if (d->win_off) for (int z = 0; z <= n; ++z) d->win_off[z] = S.wb_off[z];
+        for (int z = 0; z < n; ++z) d->backbone[z] &= 255;   // (the device word also carries the cascade's marks)
+    }
+}
+
+// stage durations of a slot's last run.  draft_ms = the first POA pass, align_ms = alignment cascade + accounting + the whole
+// fallback round (POA included), polish_ms from the polish stage's own start event (it may have queued behind the previous batch)
+static int slot_timings(ccsx_handle h, Slot &S, ccsx_timings *t)
+{
+    HIPTRY(hipEventSynchronize(S.ev[5]));
+    std::memset(t, 0, sizeof(*t));
+    HIPTRY(hipEventElapsedTime(&t->setup_ms, S.ev[0], S.ev[1]));
+    HIPTRY(hipEventElapsedTime(&t->draft_ms, S.ev[1], S.ev[2]));
+    HIPTRY(hipEventElapsedTime(&t->align_ms, S.ev[2], S.ev[3]));
+    HIPTRY(hipEventElapsedTime(&t->queue_ms, S.ev[3], S.ev[6]));
+    HIPTRY(hipEventElapsedTime(&t->polish_ms, S.ev[6], S.ev[4]));
+    HIPTRY(hipEventElapsedTime(&t->stitch_ms, S.ev[4], S.ev[5]));
+    HIPTRY(hipEventElapsedTime(&t->total_ms, S.ev[0], S.ev[5]));
+    float a = 0.0f, b = 0.0f;
+    HIPTRY(hipEventElapsedTime(&a, h->ev_epoch, S.ev[0]));
+    HIPTRY(hipEventElapsedTime(&b, h->ev_epoch, S.ev[5]));
+    t->start_ms = h->epoch_ms + (double)a; t->end_ms = h->epoch_ms + (double)b;
+    h->age_ms = b;                    // (the origin moves forward at the next submit that finds the handle idle: rebase_epoch)
+    return 0;
+}
+
+// The one way a slot stops being in flight (ccsx_wait, ccsx_poll when it first sees the batch done, a submit that reuses the slot, the synchronous calls,
+// destroy).  Its timings are taken NOW, as doubles against the current origin (a later rebase_epoch cannot invalidate them), together with the
+// polish workgroups its results report; then the host-side part of its outputs.  Afterwards nothing touches the ticket's caller structs again.
+static int retire(ccsx_handle h, Slot &S)
+{
+    if (!S.inflight) return 0;
+    HIPTRY(hipEventSynchronize(S.ev_done));
+    S.inflight = false;
+    S.tm_ok = S.ran && slot_timings(h, S, &S.tm) == 0;
+    if (S.tm_ok && S.res && S.res->n_windows) for (int z = 0; z < S.P.n_zmw; ++z) S.tm.polish_workgroups += S.res->n_windows[z];
+    finish_outputs(S, S.res, S.drafts_out);
+    S.res = nullptr; S.drafts_out = nullptr;
+    return 0;
+}
+
+static void drain_streams(ccsx_handle h) { for (hipStream_t s : {h->s_in, h->s_draft, h->s_aux, h->s_comp, h->s_out}) if (s) (void)hipStreamSynchronize(s); }
+
 static void destroy_handle(ccsx_handle h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->s_in) (void)hipStreamSynchronize(h->s_in);
-    if (h->s_draft) (void)hipStreamSynchronize(h->s_draft);
-    if (h->s_aux) (void)hipStreamSynchronize(h->s_aux);
-    if (h->s_comp) (void)hipStreamSynchronize(h->s_comp);
-    if (h->s_out) (void)hipStreamSynchronize(h->s_out);
-    for (auto &s : h->slot) s.release();
+    drain_streams(h);
+    for (auto &s : h->slot) { (void)retire(h, s); s.release(); }
     if (h->ev_epoch) (void)hipEventDestroy(h->ev_epoch);
     if (h->ev_epoch_nx) (void)hipEventDestroy(h->ev_epoch_nx);
     h->d_model.release(); h->d_poa.release(); h->d_align.release(); h->d_hd_lf.release();
@@ -589,19 +635,6 @@ static int enqueue_download(Slot &S, ccsx_results *res, hipStream_t s)
     return 0;
 }
 
-// the host-side part of a finished slot's outputs: the capacity-layout offsets the caller's structs carry, and the drafts' backbone words without the cascade's marks
-static void finish_outputs(Slot &S)
-{
-    if (S.res && S.res->seq_off) std::memcpy(S.res->seq_off, S.seq_off.p, (size_t)(S.P.n_zmw + 1) * 8);
-    if (ccsx_drafts *d = S.drafts_out) {
-        const int n = S.P.n_zmw;
-        std::memcpy(d->seq_off, S.seq_off.p, (size_t)(n + 1) * 8);
-        if (d->win_off) for (int z = 0; z <= n; ++z) d->win_off[z] = S.wb_off[z];
-        for (int z = 0; z < n; ++z) d->backbone[z] &= 255;   // (the device word also carries the cascade's marks)
-    }
-    S.drafts_out = nullptr;                              // (done once)
-}
-
 // ---- asynchronous pipeline -------------------------------------------------------------------------------
 // The origin of ccsx_timings.start_ms / end_ms moves forward every 5 minutes of handle lifetime so that HIP's float milliseconds keep their resolution.
 // not inside the getter (it stalled behind every queued download and relied on negative elapsed times for slots recorded before the new origin) — only when
@@ -618,7 +651,7 @@ static int rebase_epoch(ccsx_handle h)
     h->epoch_ms += (double)d;
     std::swap(h->ev_epoch, h->ev_epoch_nx);
     h->age_ms = 0.0f;
-    for (auto &S : h->slot) S.ran = false;               // events recorded before the new origin can no longer be measured against it; what ccsx_wait took (Slot::tm) stays readable
+    for (auto &S : h->slot) S.ran = false;               // events recorded before the new origin can no longer be measured against it; what retire() took (Slot::tm) stays readable
     return 0;
 }
 
@@ -630,6 +663,19 @@ static int check_drafts(const Slot &S, const ccsx_drafts *d, bool input)
     }
     if (!input && d->win_bounds && (!d->win_off || d->win_capacity < S.wb_off[n])) { ccsx_set_error("ccsx_drafts: win_bounds needs win_off and ccsx_draft_layout's capacity"); return -1; }
     if (input) for (int z = 0; z <= n; ++z) if (d->seq_off[z] != S.seq_off[z]) { ccsx_set_error("ccsx_polish_batch: drafts.seq_off is not the capacity layout of ccsx_draft_layout"); return -1; }
+    return 0;
+}
+
+// the caller's drafts (the polish seam, the heteroduplex finder), copied on `st`: bases into the slot's draft buffer, lengths + orientation references beside them
+static int upload_drafts(Slot &S, const ccsx_drafts *d, hipStream_t st)
+{
+    const int n = S.P.n_zmw;
+    if (S.d_din_len.reserve((size_t)n * 4) || S.d_din_bb.reserve((size_t)n * 4)) return -2;
+    HIPTRY(hipMemcpyAsync(S.d_draft.p, d->seq, (size_t)S.seq_off[n], hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(S.d_din_len.p, d->len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(S.d_din_bb.p, d->backbone, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    S.P.din_len = (const int32_t *)S.d_din_len.p; S.P.din_bb = (const int32_t *)S.d_din_bb.p;
+    S.P.opts.no_fallback_draft = 1;                       // (this slot's copy of the options: the alignment's outcome on a given draft is final)
     return 0;
 }
 
@@ -645,20 +691,14 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     HIPTRY(hipSetDevice(h->device));
     if (int rc0 = rebase_epoch(h)) return rc0;
     Slot &S = h->slot[h->next_ticket % CCSX_SLOTS];
-    if (S.inflight) {                                    // the slot's previous batch was never waited for: finish it first — INCLUDING the host-side part of its
-        HIPTRY(hipEventSynchronize(S.ev_done));          // outputs (offsets, the drafts' backbone words): the caller's buffers are complete whether or not it ever waits
-        S.inflight = false;
-        finish_outputs(S);
-    }
+    if (int rc0 = retire(h, S)) return rc0;              // (a batch never waited for: the caller's buffers are complete whether or not it ever waits)
     // A failure after the first enqueue must not leave copies or kernels running on a slot the next submit would rewrite
     // (ADVICE r02): drain every stream, mark the slot unusable and refuse further batches on this handle.
     auto fail = [&](int rc_) {
-        const std::string msg = ccsx_last_error();
-        (void)hipStreamSynchronize(h->s_in); (void)hipStreamSynchronize(h->s_draft); if (h->s_aux) (void)hipStreamSynchronize(h->s_aux); (void)hipStreamSynchronize(h->s_comp); (void)hipStreamSynchronize(h->s_out);
+        drain_streams(h);
         (void)hipGetLastError();
-        S.staged = false; S.ran = false; S.inflight = false; S.ticket = -1;
+        S.staged = false; S.ran = false; S.ticket = -1;
         h->poisoned = true;
-        ccsx_set_error(msg);
         return rc_;
     };
     int rc = stage(h, S, b, h->s_in);
@@ -668,15 +708,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     S.mode = mode;
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
 #define HIPTRY_F(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(-2); } } while (0)
-    if (mode == CCSX_RUN_POLISH) {                       // the caller's drafts: bases into the slot's draft buffer, lengths + orientation references beside them
-        const int n = S.P.n_zmw;
-        if (S.d_din_len.reserve((size_t)n * 4) || S.d_din_bb.reserve((size_t)n * 4)) return fail(-2);
-        HIPTRY_F(hipMemcpyAsync(S.d_draft.p, dr_in->seq, (size_t)S.seq_off[n], hipMemcpyHostToDevice, h->s_in));
-        HIPTRY_F(hipMemcpyAsync(S.d_din_len.p, dr_in->len, (size_t)n * 4, hipMemcpyHostToDevice, h->s_in));
-        HIPTRY_F(hipMemcpyAsync(S.d_din_bb.p, dr_in->backbone, (size_t)n * 4, hipMemcpyHostToDevice, h->s_in));
-        S.P.din_len = (const int32_t *)S.d_din_len.p; S.P.din_bb = (const int32_t *)S.d_din_bb.p;
-        S.P.opts.no_fallback_draft = 1;                   // (this slot's copy of the options: the alignment's outcome on a given draft is final)
-    }
+    if (mode == CCSX_RUN_POLISH && (rc = upload_drafts(S, dr_in, h->s_in))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_up, h->s_in));
     HIPTRY_F(hipStreamWaitEvent(h->s_draft, S.ev_up, 0));
     if ((rc = launch(h, S))) return fail(rc);
@@ -687,7 +719,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         const KParams &P = S.P;
         HIPTRY_F(hipMemcpyAsync(dr_out->status, P.zstat, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));
         HIPTRY_F(hipMemcpyAsync(dr_out->len, P.draft_len, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));
-        HIPTRY_F(hipMemcpyAsync(dr_out->backbone, P.zref, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));   // (low byte: masked in ccsx_wait)
+        HIPTRY_F(hipMemcpyAsync(dr_out->backbone, P.zref, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));   // (low byte: masked by retire)
         HIPTRY_F(hipMemcpyAsync(dr_out->seq, P.draft, (size_t)S.seq_off[n], hipMemcpyDeviceToHost, h->s_out));
         if (dr_out->n_windows) HIPTRY_F(hipMemcpyAsync(dr_out->n_windows, P.nwin, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));
         if (dr_out->win_bounds) HIPTRY_F(hipMemcpyAsync(dr_out->win_bounds, P.wbounds, (size_t)S.wb_off[n] * 4, hipMemcpyDeviceToHost, h->s_out));
@@ -732,67 +764,32 @@ static Slot *slot_of(ccsx_handle h, ccsx_ticket t)
     return S.ticket == t ? &S : nullptr;
 }
 
-static int slot_timings(ccsx_handle h, Slot &S, ccsx_timings *t);
-
 int ccsx_wait(ccsx_handle h, ccsx_ticket ticket)
 {
     Slot *S = slot_of(h, ticket);
     if (!S) { ccsx_set_error("ccsx_wait: unknown or recycled ticket"); return -1; }
     HIPTRY(hipSetDevice(h->device));
-    if (S->inflight) {
-        HIPTRY(hipEventSynchronize(S->ev_done));
-        S->inflight = false;
-        // (the ticket's timings are taken NOW, as doubles against the current origin — a later move of the origin (rebase_epoch) cannot invalidate them,
-        // and a caller may read them any time before the slot is reused)
-        S->tm_ok = S->ran && slot_timings(h, *S, &S->tm) == 0;
-        finish_outputs(*S);
-    }
-    return 0;
+    return retire(h, *S);
 }
 
 int ccsx_poll(ccsx_handle h, ccsx_ticket ticket)
 {
     Slot *S = slot_of(h, ticket);
     if (!S) { ccsx_set_error("ccsx_poll: unknown or recycled ticket"); return -1; }
-    if (!S->inflight) return 1;
     const hipError_t e = hipEventQuery(S->ev_done);
-    if (e == hipSuccess) return 1;
     if (e == hipErrorNotReady) return 0;
-    ccsx_set_error(std::string("ccsx_poll: ") + hipGetErrorString(e));
-    return -2;
-}
-
-// stage durations of a slot's last run.  draft_ms = the first POA pass, align_ms = alignment cascade + accounting + the whole
-// fallback round (POA included), polish_ms from the polish stage's own start event (it may have queued behind the previous batch)
-static int slot_timings(ccsx_handle h, Slot &S, ccsx_timings *t)
-{
-    HIPTRY(hipEventSynchronize(S.ev[5]));
-    std::memset(t, 0, sizeof(*t));
-    HIPTRY(hipEventElapsedTime(&t->setup_ms, S.ev[0], S.ev[1]));
-    HIPTRY(hipEventElapsedTime(&t->draft_ms, S.ev[1], S.ev[2]));
-    HIPTRY(hipEventElapsedTime(&t->align_ms, S.ev[2], S.ev[3]));
-    HIPTRY(hipEventElapsedTime(&t->queue_ms, S.ev[3], S.ev[6]));
-    HIPTRY(hipEventElapsedTime(&t->polish_ms, S.ev[6], S.ev[4]));
-    HIPTRY(hipEventElapsedTime(&t->stitch_ms, S.ev[4], S.ev[5]));
-    HIPTRY(hipEventElapsedTime(&t->total_ms, S.ev[0], S.ev[5]));
-    float a = 0.0f, b = 0.0f;
-    HIPTRY(hipEventElapsedTime(&a, h->ev_epoch, S.ev[0]));
-    HIPTRY(hipEventElapsedTime(&b, h->ev_epoch, S.ev[5]));
-    t->start_ms = h->epoch_ms + (double)a; t->end_ms = h->epoch_ms + (double)b;
-    h->age_ms = b;                    // (the origin moves forward at the next submit that finds the handle idle: rebase_epoch)
-    return 0;
+    if (e != hipSuccess) { ccsx_set_error(std::string("ccsx_poll: ") + hipGetErrorString(e)); return -2; }
+    HIPTRY(hipSetDevice(h->device));
+    return retire(h, *S) ? -2 : 1;
 }
 
 int ccsx_ticket_timings(ccsx_handle h, ccsx_ticket ticket, ccsx_timings *t)
 {
     Slot *S = slot_of(h, ticket);
     if (!S || !t || !(S->ran || S->tm_ok)) { ccsx_set_error("ccsx_ticket_timings: unknown ticket"); return -1; }
+    if (S->tm_ok) { *t = S->tm; return 0; }           // taken when the ticket was retired
     HIPTRY(hipSetDevice(h->device));
-    if (S->tm_ok) *t = S->tm;                         // taken when the ticket was waited for
-    else if (int rc = slot_timings(h, *S, t)) return rc;
-    t->polish_workgroups = 0;
-    if (!S->inflight && S->res && S->res->n_windows) for (int z = 0; z < S->P.n_zmw; ++z) t->polish_workgroups += S->res->n_windows[z];
-    return 0;
+    return slot_timings(h, *S, t);                    // (still in flight: the live events, no polish workgroups yet)
 }
 
 // ---- synchronous form (slot 0): parity tests, stage read-backs, the resident-input leg of the benchmark ----
@@ -800,11 +797,12 @@ int ccsx_upload(ccsx_handle h, const ccsx_batch *b)
 {
     if (!h) { ccsx_set_error("ccsx_upload: null handle"); return -1; }
     HIPTRY(hipSetDevice(h->device));
-    for (auto &S : h->slot) if (S.inflight) { HIPTRY(hipEventSynchronize(S.ev_done)); S.inflight = false; }
+    for (auto &S : h->slot) if (int rc = retire(h, S)) return rc;
     Slot &S = h->slot[0];
+    S.ticket = -1;                                       // (slot 0 is re-staged: its ticket is recycled, as by a submit; the other slots' tickets stay valid)
     const int rc = stage(h, S, b, h->s_comp);
     if (rc) { S.staged = false; return rc; }
-    S.mode = CCSX_RUN_FUSED; S.drafts_out = nullptr;
+    S.mode = CCSX_RUN_FUSED;
     HIPTRY(hipStreamSynchronize(h->s_comp));
     h->last = 0;
     return 0;
@@ -812,7 +810,7 @@ int ccsx_upload(ccsx_handle h, const ccsx_batch *b)
 
 int ccsx_run(ccsx_handle h)
 {
-    if (!h || !h->slot[0].staged) { ccsx_set_error("ccsx_run: no batch uploaded"); return -1; }
+    if (!h || !h->slot[0].staged || h->slot[0].mode != CCSX_RUN_FUSED) { ccsx_set_error("ccsx_run: no batch uploaded for the fused path: call ccsx_upload first"); return -1; }
     HIPTRY(hipSetDevice(h->device));
     h->last = 0;
     return launch(h, h->slot[0]);
@@ -852,14 +850,13 @@ int ccsx_sync(ccsx_handle h)
 
 int ccsx_download(ccsx_handle h, ccsx_results *res)
 {
-    if (!h || !h->slot[0].ran || !res) { ccsx_set_error("ccsx_download: nothing to download"); return -1; }
+    if (!h || !h->slot[0].ran || h->slot[0].mode != CCSX_RUN_FUSED || !res) { ccsx_set_error("ccsx_download: nothing to download: ccsx_upload + ccsx_run first"); return -1; }
     Slot &S = h->slot[0];
-    int rc = check_results(S, res, S.P.out_kin != nullptr);
-    if (rc) return rc;
+    if (int rc = check_results(S, res, S.P.out_kin != nullptr)) return rc;
     HIPTRY(hipSetDevice(h->device));
-    if ((rc = enqueue_download(S, res, h->s_comp))) return rc;
+    if (int rc = enqueue_download(S, res, h->s_comp)) return rc;
     HIPTRY(hipStreamSynchronize(h->s_comp));
-    if (res->seq_off) std::memcpy(res->seq_off, S.seq_off.p, (size_t)(S.P.n_zmw + 1) * 8);
+    finish_outputs(S, res, nullptr);
     return 0;
 }
 
@@ -887,13 +884,29 @@ int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)
     return 0;
 }
 
-// ---- stage access (parity tests; slot of the last synchronous run) ----
-int ccsx_stage_draft(ccsx_handle h, int32_t z, uint8_t *draft, int32_t cap, int32_t *len)
+// ---- stage access (parity tests): slot 0 as the last synchronous run left it (ccsx_run, ccsx_hd_batch) ----
+static int stage_guard(ccsx_handle h, int32_t i, bool read_index, const char *fn)
 {
-    if (!h || !h->slot[0].ran || z < 0 || z >= h->slot[0].P.n_zmw) { ccsx_set_error("ccsx_stage_draft: bad state/index"); return -1; }
-    Slot &S = h->slot[0];
+    if (!h || !h->slot[0].ran || i < 0 || i >= (read_index ? h->slot[0].P.n_reads : h->slot[0].P.n_zmw)) { ccsx_set_error(std::string(fn) + ": bad state/index"); return -1; }
     HIPTRY(hipSetDevice(h->device));
     HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+// ZMW z's window bounds into wb; returns their count for a draft of L bases (from the bounds: nwin may have been zeroed by a later status), or < 0
+static int stage_bounds(const Slot &S, int z, int32_t L, std::vector<int32_t> &wb)
+{
+    wb.resize(S.wb_off[z + 1] - S.wb_off[z]);
+    HIPTRY(hipMemcpy(wb.data(), S.P.wbounds + S.wb_off[z], wb.size() * 4, hipMemcpyDeviceToHost));
+    int nw = 0;
+    if (L > 0) while (nw + 1 < (int)wb.size() && wb[nw] < L) ++nw;
+    return nw;
+}
+
+int ccsx_stage_draft(ccsx_handle h, int32_t z, uint8_t *draft, int32_t cap, int32_t *len)
+{
+    if (int rc = stage_guard(h, z, false, "ccsx_stage_draft")) return rc;
+    const Slot &S = h->slot[0];
     int32_t L = 0;
     HIPTRY(hipMemcpy(&L, S.P.draft_len + z, 4, hipMemcpyDeviceToHost));
     if (L > cap) { ccsx_set_error("ccsx_stage_draft: buffer too small"); return -1; }
@@ -904,16 +917,12 @@ int ccsx_stage_draft(ccsx_handle h, int32_t z, uint8_t *draft, int32_t cap, int3
 
 int ccsx_stage_windows(ccsx_handle h, int32_t z, int32_t *bounds, int32_t cap, int32_t *n_windows)
 {
-    if (!h || !h->slot[0].ran || z < 0 || z >= h->slot[0].P.n_zmw) { ccsx_set_error("ccsx_stage_windows: bad state/index"); return -1; }
-    Slot &S = h->slot[0];
-    HIPTRY(hipSetDevice(h->device));
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    int32_t nw = 0, L = 0;
+    if (int rc = stage_guard(h, z, false, "ccsx_stage_windows")) return rc;
+    const Slot &S = h->slot[0];
+    int32_t L = 0; std::vector<int32_t> wb;
     HIPTRY(hipMemcpy(&L, S.P.draft_len + z, 4, hipMemcpyDeviceToHost));
-    // nwin may have been zeroed by a later status; recompute the count from the bounds array
-    std::vector<int32_t> wb(S.wb_off[z + 1] - S.wb_off[z]);
-    HIPTRY(hipMemcpy(wb.data(), S.P.wbounds + S.wb_off[z], wb.size() * 4, hipMemcpyDeviceToHost));
-    if (L > 0) while (nw + 1 < (int)wb.size() && wb[nw] < L) ++nw;
+    const int nw = stage_bounds(S, z, L, wb);
+    if (nw < 0) return nw;
     if (nw + 1 > cap) { ccsx_set_error("ccsx_stage_windows: buffer too small"); return -1; }
     for (int k = 0; k <= nw; ++k) bounds[k] = wb[k];
     *n_windows = nw;
@@ -924,12 +933,9 @@ int ccsx_stage_windows(ccsx_handle h, int32_t z, int32_t *bounds, int32_t cap, i
 // materialises the other columns).
 int ccsx_stage_align(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, int32_t *valid, int32_t *score)
 {
-    if (!h || !h->slot[0].ran || r < 0 || r >= h->slot[0].P.n_reads) { ccsx_set_error("ccsx_stage_align: bad state/index"); return -1; }
-    Slot &S = h->slot[0];
-    HIPTRY(hipSetDevice(h->device));
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    const int n = S.P.n_zmw;
-    int z = (int)(std::upper_bound(S.read_off.p, S.read_off.p + n + 1, r) - S.read_off.p) - 1;
+    if (int rc = stage_guard(h, r, true, "ccsx_stage_align")) return rc;
+    const Slot &S = h->slot[0];
+    const int z = (int)(std::upper_bound(S.read_off.p, S.read_off.p + S.P.n_zmw + 1, r) - S.read_off.p) - 1;
     uint8_t v = 0; int32_t sc = 0, L = 0;
     HIPTRY(hipMemcpy(&v, S.P.avalid + r, 1, hipMemcpyDeviceToHost));
     HIPTRY(hipMemcpy(&sc, S.P.ascore + r, 4, hipMemcpyDeviceToHost));
@@ -938,10 +944,9 @@ int ccsx_stage_align(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, int
     if (L + 1 > cap) { ccsx_set_error("ccsx_stage_align: buffer too small"); return -1; }
     for (int j = 0; j <= L; ++j) rstart[j] = -1;
     if (v) {
-        std::vector<int32_t> wb(S.wb_off[z + 1] - S.wb_off[z]);
-        HIPTRY(hipMemcpy(wb.data(), S.P.wbounds + S.wb_off[z], wb.size() * 4, hipMemcpyDeviceToHost));
-        int nw = 0;
-        while (nw + 1 < (int)wb.size() && wb[nw] < L) ++nw;
+        std::vector<int32_t> wb;
+        const int nw = stage_bounds(S, z, L, wb);
+        if (nw < 0) return nw;
         std::vector<int32_t> ent(2 * nw);
         HIPTRY(hipMemcpy(ent.data(), S.P.ent + S.ent_off[r], ent.size() * 4, hipMemcpyDeviceToHost));
         for (int k = 0; k < 2 * nw; ++k) {
@@ -977,7 +982,8 @@ int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts,
     int rc = ccsx_upload(h, b);
     if (rc) return rc;
     Slot &S = h->slot[0];
-    if ((rc = check_drafts(S, drafts, true))) { S.staged = false; return rc; }
+    S.mode = CCSX_RUN_HD;                                    // (slot 0 is the finder's now: ccsx_run / ccsx_download refuse it until the next ccsx_upload)
+    if ((rc = check_drafts(S, drafts, true))) return rc;
     const int n = S.P.n_zmw;
     const size_t wins = (size_t)S.P.total_wslots + 1;
     if (!h->d_hd_lf.p) {                                     // log k!, a sequential sum of log(k) in double (the rule's table)
@@ -986,26 +992,19 @@ int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts,
         if (h->d_hd_lf.reserve(lf.size() * 8)) return -2;
         HIPTRY(hipMemcpy(h->d_hd_lf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice));
     }
-    if (S.d_din_len.reserve((size_t)n * 4) || S.d_din_bb.reserve((size_t)n * 4) || S.d_hd_wcnt.reserve(wins * 4) ||
+    if (S.d_hd_wcnt.reserve(wins * 4) ||
         S.d_hd_wrec.reserve(wins * CCSX_HD_WIN_SITES * sizeof(ccsx_hd_site)) || S.d_hd_wminp.reserve(wins * 8) ||
         S.d_hd_isite.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site)) || S.d_hd_zi.reserve((size_t)n * 5 * 4) ||
-        S.d_hd_minp.reserve((size_t)n * 8) || S.d_hd_sites.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site))) { S.staged = false; return -2; }
-    HIPTRY(hipMemcpy(S.d_draft.p, drafts->seq, (size_t)S.seq_off[n], hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(S.d_din_len.p, drafts->len, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(S.d_din_bb.p, drafts->backbone, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPTRY(hipMemset(S.d_hd_sites.p, 0, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site)));
+        S.d_hd_minp.reserve((size_t)n * 8) || S.d_hd_sites.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site))) return -2;
+    if ((rc = upload_drafts(S, drafts, h->s_comp))) return rc;
+    HIPTRY(hipMemsetAsync(S.d_hd_sites.p, 0, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site), h->s_comp));
+    HIPTRY(hipStreamSynchronize(h->s_comp));
     KParams &P = S.P;
-    P.din_len = (const int32_t *)S.d_din_len.p; P.din_bb = (const int32_t *)S.d_din_bb.p;
-    P.opts.no_fallback_draft = 1;                            // (the alignment's outcome on the caller's draft is final, as in the polish seam)
     P.hd = hd; P.hd_lf = (const double *)h->d_hd_lf.p;
     P.hd_wcnt = (int32_t *)S.d_hd_wcnt.p; P.hd_wrec = (ccsx_hd_site *)S.d_hd_wrec.p; P.hd_wminp = (double *)S.d_hd_wminp.p;
     P.hd_isite = (ccsx_hd_site *)S.d_hd_isite.p; P.hd_zi = (int32_t *)S.d_hd_zi.p; P.hd_minp = (double *)S.d_hd_minp.p;
     P.hd_sites = (ccsx_hd_site *)S.d_hd_sites.p;
-    S.mode = CCSX_RUN_HD;
-    rc = launch(h, S);
-    S.mode = CCSX_RUN_FUSED;                                 // (slot 0's next ccsx_run is the fused path again: ccsx_upload re-stages everything the finder changed)
-    if (rc) return rc;
-    if ((rc = ccsx_sync(h))) return rc;
+    if ((rc = launch(h, S)) || (rc = ccsx_sync(h))) return rc;
     HIPTRY(hipMemcpy(out->verdict, P.hd_zi, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPTRY(hipMemcpy(out->n_sub_sites, P.hd_zi + n, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPTRY(hipMemcpy(out->n_indel_sites, P.hd_zi + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));

@@ -3815,6 +3815,7 @@ int ccsx_polish_lds(int max_reads, int *obs_bytes, int *gb_floats)
 
 // every launch status is captured: returns NULL, or the name of the first launch that failed (ccsx_api.cpp reports it)
 #define LAUNCH_CHECK(name) do { if (hipGetLastError() != hipSuccess && !failed) failed = name; } while (0)
+#define CALL_CHECK(fn, ...) do { if (fn(__VA_ARGS__) != hipSuccess && !failed) failed = #fn; } while (0)   // (a stream / event call)
 const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_polish, hipEvent_t *ev /* [7] or NULL */, int mode, hipStream_t st_aux, hipEvent_t *ev_aux /* [7] or NULL */)
 {
     // Two-stage queue of docs/img/ccs-impl.png ("Draft Stage" -> queue -> "Polish Stage"): the draft stage (tables, POA, alignment
@@ -3823,16 +3824,16 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     // stage of batch k (the register-only one-wave POA and the LDS-bound polish workgroups share the SIMDs); the shared POA /
     // alignment scratch is touched by the draft stage only, so `st` alone orders its users.  st_polish == st: serial stages.
     const char *failed = nullptr;
-    if (ev && hipEventRecord(ev[0], st) != hipSuccess) failed = "hipEventRecord";
-    if (hipMemsetAsync(P.ticket_poa, 0, 256, st) != hipSuccess && !failed) failed = "hipMemsetAsync";   // debug / phase-profile words (CCSX_DEBUG_CHECKS, CCSX_PROFILE_PHASES builds)
-    if (hipMemsetAsync(P.avalid, 0, (size_t)(P.n_reads > 0 ? P.n_reads : 1), st) != hipSuccess && !failed) failed = "hipMemsetAsync";   // passes beyond top_passes are never visited by a kernel
+    if (ev) CALL_CHECK(hipEventRecord, ev[0], st);
+    CALL_CHECK(hipMemsetAsync, P.ticket_poa, 0, 256, st);   // debug / phase-profile words (CCSX_DEBUG_CHECKS, CCSX_PROFILE_PHASES builds)
+    CALL_CHECK(hipMemsetAsync, P.avalid, 0, (size_t)(P.n_reads > 0 ? P.n_reads : 1), st);   // passes beyond top_passes are never visited by a kernel
     {
         int n = P.n_zmw * CCSX_NCTX;
         hipLaunchKernelGGL(k_setup, dim3((n + 255) / 256), dim3(256), 0, st, P);
         LAUNCH_CHECK("k_setup");
     }
     trace_sync(st, "k_setup");
-    if (ev) (void)hipEventRecord(ev[1], st);
+    if (ev) CALL_CHECK(hipEventRecord, ev[1], st);
     const size_t lds_read = (((size_t)P.maxL_max + 15) / 16) * 4 + 64 + 4 * (CCSX_MAX_PASSES + 1);   // the packed read; k_poa_init: the lengths of up to 255 passes
     // pass 0 = the draft; pass 1 = the fallback draft of the ZMWs k_post marked (their waves run, all others leave at once:
     // the second round of launches costs microseconds unless something failed)
@@ -3853,11 +3854,11 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
             auto poa_range = [&](hipStream_t s, int g0, int ng, hipEvent_t after_first_dp, hipEvent_t before_first_dp) {
                 hipLaunchKernelGGL(k_poa_init, dim3(ng), dim3(64), lds_read, s, P, z0, pass, g0);
                 LAUNCH_CHECK("k_poa_init");
-                if (before_first_dp && hipStreamWaitEvent(s, before_first_dp, 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";
+                if (before_first_dp) CALL_CHECK(hipStreamWaitEvent, s, before_first_dp, 0);
                 for (int rr = 1; rr < cov && pass < 2; ++rr) {
                     hipLaunchKernelGGL(k_poa_dp, dim3((ng + 3) / 4), dim3(64), 0, s, P, z0, pass, rr, g0 / 4);
                     LAUNCH_CHECK("k_poa_dp");
-                    if (rr == 1 && after_first_dp && hipEventRecord(after_first_dp, s) != hipSuccess && !failed) failed = "hipEventRecord";
+                    if (rr == 1 && after_first_dp) CALL_CHECK(hipEventRecord, after_first_dp, s);
                     hipLaunchKernelGGL(k_poa_thread, dim3(ng), dim3(64), lds_read, s, P, z0, pass, rr, g0);
                     LAUNCH_CHECK("k_poa_thread");
                 }
@@ -3870,18 +3871,18 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
             // waits for HBM, their registers and LDS fit one SIMD together (94 + 64 VGPRs), so the threading of one half runs under the DP of the other.
             if (st_aux && ev_aux && pass == 0 && cov > 1 && nb >= 4096) {
                 const int ha = ((nb / 2) + 3) & ~3;
-                if (hipEventRecord(ev_aux[0], st) != hipSuccess && !failed) failed = "hipEventRecord";
-                if (hipStreamWaitEvent(st_aux, ev_aux[0], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";
+                CALL_CHECK(hipEventRecord, ev_aux[0], st);
+                CALL_CHECK(hipStreamWaitEvent, st_aux, ev_aux[0], 0);
                 poa_range(st, 0, ha, ev_aux[1], nullptr);
                 poa_range(st_aux, ha, nb - ha, nullptr, ev_aux[1]);
-                if (hipEventRecord(ev_aux[2], st_aux) != hipSuccess && !failed) failed = "hipEventRecord";
-                if (hipStreamWaitEvent(st, ev_aux[2], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";
+                CALL_CHECK(hipEventRecord, ev_aux[2], st_aux);
+                CALL_CHECK(hipStreamWaitEvent, st, ev_aux[2], 0);
             } else poa_range(st, 0, nb, nullptr, nullptr);
         }
         trace_sync(st, "k_poa");
-        if (ev && pass == 0) (void)hipEventRecord(ev[2], st);
+        if (ev && pass == 0) CALL_CHECK(hipEventRecord, ev[2], st);
         // alignment cascade: four passes per wave in 16-row bands, then the 64-row retry of the few that failed there
-        if (hipMemsetAsync(P.align_retry, 0, 64, st) != hipSuccess && !failed) failed = "hipMemsetAsync";
+        CALL_CHECK(hipMemsetAsync, P.align_retry, 0, 64, st);
         bool tb_aside_out = false; int tb_launches = 0;
         {
             const size_t lds16 = 4 * (CH16 / 16 + 3) * sizeof(uint32_t);
@@ -3896,19 +3897,19 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
             for (int qb = 0; qb < P.n_quads; qb += P.align16_slots, ++c) {
                 const int nb = (P.n_quads - qb) < P.align16_slots ? (P.n_quads - qb) : P.align16_slots;
                 const int region = P.align16_regions > 1 ? (c & 1) : 0;
-                if (aside && c >= 2 && hipStreamWaitEvent(st, ev_aux[5 + (c & 1)], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";   // the region's last reader
-                if (aside && c >= 1 && P.align16_regions <= 1 && hipStreamWaitEvent(st, ev_aux[5 + ((c - 1) & 1)], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";   // (one region: in sequence)
+                if (aside && c >= 2) CALL_CHECK(hipStreamWaitEvent, st, ev_aux[5 + (c & 1)], 0);   // the region's last reader
+                if (aside && c >= 1 && P.align16_regions <= 1) CALL_CHECK(hipStreamWaitEvent, st, ev_aux[5 + ((c - 1) & 1)], 0);   // (one region: in sequence)
                 hipLaunchKernelGGL(k_align16, dim3(nb), dim3(64), lds16, st, P, qb, pass, region);
                 LAUNCH_CHECK("k_align16");
                 hipStream_t s_tb = st;
                 if (aside) {
-                    if (hipEventRecord(ev_aux[3 + (c & 1)], st) != hipSuccess && !failed) failed = "hipEventRecord";
-                    if (hipStreamWaitEvent(st_aux, ev_aux[3 + (c & 1)], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";
+                    CALL_CHECK(hipEventRecord, ev_aux[3 + (c & 1)], st);
+                    CALL_CHECK(hipStreamWaitEvent, st_aux, ev_aux[3 + (c & 1)], 0);
                     s_tb = st_aux; tb_aside = true;
                 }
                 hipLaunchKernelGGL(k_align16_tb, dim3((4 * nb + 63) / 64), dim3(64), 0, s_tb, P, qb, nb, region);   // one lane per pass: entry rows / dirty masks from the stored moves
                 LAUNCH_CHECK("k_align16_tb");
-                if (aside && hipEventRecord(ev_aux[5 + (c & 1)], st_aux) != hipSuccess && !failed) failed = "hipEventRecord";
+                if (aside) CALL_CHECK(hipEventRecord, ev_aux[5 + (c & 1)], st_aux);
             }
             tb_launches = c;
             tb_aside_out = tb_aside;
@@ -3925,12 +3926,12 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
             LAUNCH_CHECK("k_rescue");
         }
         if (tb_aside_out) for (int c = tb_launches > 2 ? tb_launches - 2 : 0; c < tb_launches; ++c)      // (the trace-backs run in order on one stream: the last one per region)
-            if (hipStreamWaitEvent(st, ev_aux[5 + (c & 1)], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";
+            CALL_CHECK(hipStreamWaitEvent, st, ev_aux[5 + (c & 1)], 0);
         hipLaunchKernelGGL(k_post, dim3((P.n_zmw + 255) / 256), dim3(256), 0, st, P, pass);
         LAUNCH_CHECK("k_post");
     }
     if (mode == CCSX_RUN_DRAFT) {                                   // the draft seam ends here: drafts, window bounds, alignments and statuses are final
-        if (ev) for (int k : {3, 6, 4, 5}) if (hipEventRecord(ev[k], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        if (ev) for (int k : {3, 6, 4, 5}) CALL_CHECK(hipEventRecord, ev[k], st);
         return failed;
     }
     hipLaunchKernelGGL(k_wmap, dim3(1), dim3(1024), 0, st, P);     // the batch's windows in compact order: the polish stage's grid map
@@ -3938,23 +3939,23 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
     LAUNCH_CHECK("k_wmap_fill");
     if (mode == CCSX_RUN_HD) {                                     // the heteroduplex finder instead of the polish stage, on the same stream
-        if (ev) for (int k : {3, 6}) if (hipEventRecord(ev[k], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        if (ev) for (int k : {3, 6}) CALL_CHECK(hipEventRecord, ev[k], st);
         const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;   // (the grid covers the slot capacity, the map only the windows there are)
         hipLaunchKernelGGL(k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_hd_pile");
         hipLaunchKernelGGL(k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_hd_indel");
-        if (ev && hipEventRecord(ev[4], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        if (ev) CALL_CHECK(hipEventRecord, ev[4], st);
         hipLaunchKernelGGL(k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_hd_verdict");
         trace_sync(st, "k_hd");
-        if (ev && hipEventRecord(ev[5], st) != hipSuccess && !failed) failed = "hipEventRecord";
+        if (ev) CALL_CHECK(hipEventRecord, ev[5], st);
         return failed;
     }
     if (ev) {
-        if (hipEventRecord(ev[3], st) != hipSuccess && !failed) failed = "hipEventRecord";
-        if (st_polish != st && hipStreamWaitEvent(st_polish, ev[3], 0) != hipSuccess && !failed) failed = "hipStreamWaitEvent";
-        (void)hipEventRecord(ev[6], st_polish);            // the polish stage starts here (after the queue between the stages)
+        CALL_CHECK(hipEventRecord, ev[3], st);
+        if (st_polish != st) CALL_CHECK(hipStreamWaitEvent, st_polish, ev[3], 0);
+        CALL_CHECK(hipEventRecord, ev[6], st_polish);            // the polish stage starts here (after the queue between the stages)
     } else if (st_polish != st && !failed) failed = "two streams need events";
     st = st_polish;
     // One workgroup per window slot.  A grid may not exceed 2^32 threads in all: 256 threads x 16.7 M slots — 8192 ZMWs of 30 passes x 20 kb have 10.8 M, and a
@@ -3977,9 +3978,9 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
         }
         trace_sync(st, "k_kinetics");
     }
-    if (ev) (void)hipEventRecord(ev[4], st);
+    if (ev) CALL_CHECK(hipEventRecord, ev[4], st);
     hipLaunchKernelGGL(k_stitch, dim3(P.n_zmw), dim3(64), 0, st, P);
     LAUNCH_CHECK("k_stitch");
-    if (ev && hipEventRecord(ev[5], st) != hipSuccess && !failed) failed = "hipEventRecord";
+    if (ev) CALL_CHECK(hipEventRecord, ev[5], st);
     return failed;
 }

@@ -216,8 +216,13 @@ int         ccsx_consensus_batch(ccsx_handle h, const ccsx_batch *b, ccsx_result
 
 /* asynchronous pipeline (submit / wait tickets).  ccsx_submit enqueues upload -> kernels -> download of one
  * batch on the handle's streams (H2D, draft stage, polish stage, D2H) and returns; up to three batches are in flight, so the
- * copies of batch k+1 / k-1 and the draft stage of batch k+1 run under the polish stage of batch k.  The batch arrays and the result buffers must stay valid (and
- * should be page-locked: ccsx_alloc_pinned) until ccsx_wait returns for that ticket.  Tickets complete in order.      */
+ * copies of batch k+1 / k-1 and the draft stage of batch k+1 run under the polish stage of batch k.  The batch arrays and the result buffers should be
+ * page-locked (ccsx_alloc_pinned).  Tickets complete in order.
+ * Lifetime: a ticket's batch, results and drafts structs (and the arrays they point to) must stay valid until the ticket is RETIRED: when ccsx_wait returns,
+ * when ccsx_poll first returns 1, when its slot is recycled (a later submit, or any synchronous call: ccsx_upload and the calls built on it), or when the
+ * handle is destroyed, whichever comes first.  Retiring completes the host-side outputs (seq_off; the drafts' seq_off, win_off and backbone) and takes the
+ * ticket's timings; afterwards the library never touches those structs again, and ccsx_ticket_timings reads only what was taken.  A synchronous call
+ * recycles slot 0's ticket: ccsx_wait / ccsx_poll on it fail ("unknown or recycled ticket"); the other slots' tickets stay valid, their outputs complete. */
 typedef int64_t ccsx_ticket;
 int         ccsx_submit(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket);
 int         ccsx_wait(ccsx_handle h, ccsx_ticket ticket);              /* results of that batch are in `res`   */
@@ -233,7 +238,7 @@ int         ccsx_ticket_timings(ccsx_handle h, ccsx_ticket ticket, ccsx_timings 
  * ccsx_polish_batch(ccsx_draft_batch(b)) returns byte for byte what ccsx_consensus_batch(b) returns (tests/test_gpu_parity.py).  A draft nothing maps to yields
  * a per-ZMW status (TOO_MANY_UNUSABLE, DRAFT_FAILURE for length 0 or a length beyond the slot), never an error of the call.                                   */
 /* Lifetime and memory: with the TICKETED forms the arrays of a ccsx_drafts are read (ccsx_submit_polish) / written (ccsx_submit_draft) by
- * asynchronous copies: they must stay valid until ccsx_wait returns for the ticket, and they should be page-locked (ccsx_alloc_pinned) — a copy from / to
+ * asynchronous copies: they must stay valid until the ticket is retired (see ccsx_submit), and they should be page-locked (ccsx_alloc_pinned) — a copy from / to
  * pageable memory blocks the submitting thread until the stage has finished, so "three in flight" degenerates to one at a time (correct, but serial).
  * As INPUT (ccsx_polish_batch / ccsx_submit_polish) only seq_off, len, seq and backbone are read; status, n_windows, win_bounds and win_off may be NULL.   */
 typedef struct ccsx_drafts {
@@ -259,7 +264,8 @@ int         ccsx_polish_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_dra
 int         ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket);
 int         ccsx_submit_polish(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, ccsx_results *res, uint32_t flags, ccsx_ticket *ticket);
 
-/* split form used by the benchmark (inputs resident in HBM when the timed region starts)        */
+/* split form used by the benchmark (inputs resident in HBM when the timed region starts).  ccsx_run / ccsx_download take slot 0 as ccsx_upload staged it:
+ * after ccsx_hd_batch (or a seam's ticket on slot 0) they fail until the next ccsx_upload                                                                      */
 int         ccsx_upload(ccsx_handle h, const ccsx_batch *b);           /* H2D + workspace sizing */
 int         ccsx_run(ccsx_handle h);                                   /* all kernels, async     */
 int         ccsx_sync(ccsx_handle h);                                  /* wait for the stream    */

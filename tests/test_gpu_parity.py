@@ -1286,6 +1286,91 @@ def test_seams_share_the_ticket_pipeline(handle):
 
 
 @pytest.mark.gpu
+def test_unwaited_draft_ticket_is_completed_when_its_slot_is_reused(handle):
+    """four draft-seam tickets, the first never waited for: the submit that reuses its slot retires it, so its drafts' seq_off, win_off and backbone
+    words (the cascade's marks masked off) are complete without a ccsx_wait"""
+    import ctypes as C
+    L = api.lib()
+    batches = [api.synth(4, 6, 700 + 100 * k, seed=80 + k) for k in range(4)]
+    want = handle.draft(batches[0])
+    drafts = [api.Drafts.allocate(b) for b in batches]
+    keep, tickets = [], []
+    for b, d in zip(batches, drafts):
+        d.seq_off[:] = -1; d.win_off[:] = -1; d.backbone[:] = -1   # (written by the engine, not left from ccsx_draft_layout)
+        cb, cd, t = b.c_struct(), d.c_struct(), C.c_int64()
+        assert L.ccsx_submit_draft(handle._h, C.byref(cb), C.byref(cd), C.byref(t)) == 0, L.ccsx_last_error()
+        keep.append((cb, cd)); tickets.append(t.value)
+    got = drafts[0]
+    assert np.array_equal(got.seq_off, want.seq_off) and np.array_equal(got.win_off, want.win_off)
+    assert (got.backbone < 256).all() and np.array_equal(got.backbone, want.backbone)
+    assert np.array_equal(got.status, want.status) and np.array_equal(got.len, want.len) and np.array_equal(got.n_windows, want.n_windows)
+    for z in range(batches[0].n_zmw):
+        assert np.array_equal(got.draft(z), want.draft(z)) and np.array_equal(got.windows(z), want.windows(z)), z
+    assert L.ccsx_wait(handle._h, tickets[0]) != 0 and b"recycled" in L.ccsx_last_error()
+    for t in tickets[1:]: assert L.ccsx_wait(handle._h, t) == 0
+
+
+@pytest.mark.gpu
+def test_upload_retires_unwaited_tickets_and_recycles_slot_0(built):
+    """two fused tickets on a fresh handle (slots 0 and 1), then ccsx_upload of a third batch with no wait: both tickets' outputs and timings are complete,
+    slot 0's ticket is recycled, slot 1's stays valid, and the synchronous path runs the uploaded batch"""
+    h = api.Handle(0)
+    bs = [api.synth(5, 6, 800 + 200 * k, seed=90 + k) for k in range(3)]
+    want = [h.consensus(b) for b in bs]
+    res = [api.Results.allocate(b, pinned=True) for b in bs[:2]]
+    for r in res: r.seq_off[:] = -1
+    pinned = [b.pinned() for b in bs[:2]]
+    t0, t1 = h.submit(pinned[0], res[0]), h.submit(pinned[1], res[1])
+    assert (t0, t1) == (0, 1)
+    h.upload(bs[2])
+    for r, w, b in zip(res, want, bs):
+        assert np.array_equal(r.seq_off, w.seq_off)
+        _same_results(r, w, b)
+    assert h.ticket_timings(t1).polish_workgroups == int(want[1].n_windows.sum())
+    with pytest.raises(RuntimeError, match="recycled"):
+        h.wait(t0)
+    assert h.wait(t1) is res[1]
+    h.run(); h.sync()
+    _same_results(h.download(), want[2], bs[2])
+    h.close()
+
+
+@pytest.mark.gpu
+def test_poll_retires_the_ticket(built):
+    """the first ccsx_poll that returns 1 retires the ticket: its outputs, seq_off included, are complete without a ccsx_wait"""
+    import time
+    h = api.Handle(0)
+    b = api.synth(5, 6, 800, seed=95)
+    want = h.consensus(b)
+    pb, r = b.pinned(), api.Results.allocate(b, pinned=True)
+    r.seq_off[:] = -1
+    t = h.submit(pb, r)
+    deadline = time.monotonic() + 5.0
+    while not h.poll(t):
+        assert time.monotonic() < deadline, "the ticket did not complete within 5 s"
+        time.sleep(0.002)
+    assert np.array_equal(r.seq_off, want.seq_off)
+    _same_results(r, want, b)
+    assert h.ticket_timings(t).polish_workgroups == int(want.n_windows.sum())
+    assert h.poll(t)
+    h.close()
+
+
+@pytest.mark.gpu
+def test_ticket_timings_do_not_read_caller_memory(handle):
+    """polish_workgroups is taken when the ticket is retired: overwriting the results afterwards does not change it"""
+    b = api.synth(5, 6, 800, seed=96)
+    r = api.Results.allocate(b)
+    t = handle.submit(b, r)
+    handle.wait(t)
+    total = int(r.n_windows.sum())
+    assert total > 0
+    r.n_windows[:] = 0
+    assert handle.ticket_timings(t).polish_workgroups == total
+    handle.release(t)
+
+
+@pytest.mark.gpu
 def test_timing_origin_moves_only_while_the_handle_is_idle(built):
     """the origin of ccsx_timings.start_ms / end_ms is moved forward at a submit that finds NO slot in flight (never inside the getter, never under pending
     tickets).  CCSX_EPOCH_REBASE_MS=0 forces a move at every idle submit: times stay monotone across moves, tickets in flight keep their timings."""

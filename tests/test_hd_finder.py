@@ -224,6 +224,34 @@ def test_hd_changes_nothing_else(built):
     h.close()
 
 
+@pytest.mark.gpu
+def test_hd_leaves_no_runnable_fused_state(built):
+    """after ccsx_hd_batch slot 0 holds the finder's configuration: ccsx_run and ccsx_download refuse it and name ccsx_upload, the stage accessors
+    still report the finder's stage, and ccsx_upload makes the slot a fused one again"""
+    import hd_synth
+    b = hd_synth.make(12, 6, 1500, seed=24, k_sub=3)[0]
+    h = api.Handle(0)
+    d = h.draft(b)
+    rep = h.hd(b, d)
+    stage = hd_ref.collect_stage(h, b, rep.status, d.backbone)
+    h._keep = b                                                    # (Handle.download sizes its buffers from the last uploaded batch)
+    for call in (h.run, h.download):
+        with pytest.raises(RuntimeError, match="ccsx_upload"):
+            call()
+    again = hd_ref.collect_stage(h, b, rep.status, d.backbone)
+    for z in range(b.n_zmw):
+        if rep.status[z] == 0:
+            assert np.array_equal(stage[z].draft, d.draft(z)), z
+        assert np.array_equal(stage[z].draft, again[z].draft) and np.array_equal(stage[z].wb, again[z].wb), z
+        for x, y in zip(stage[z].reads, again[z].reads):
+            assert x[2] == y[2] and np.array_equal(x[3], y[3]), z
+    assert (rep.status == 0).sum() >= 10
+    h.upload(b); h.run(); h.sync()
+    fused, ref = h.download(), h.consensus(b)
+    assert np.array_equal(fused.status, ref.status) and np.array_equal(fused.seq_len, ref.seq_len)
+    h.close()
+
+
 def _edit(a, b):
     import oracle_lib
     return oracle_lib.edit_distance(np.asarray(a, np.uint8), np.asarray(b, np.uint8))
