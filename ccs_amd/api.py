@@ -140,6 +140,80 @@ class HdReport:
         return self.sites[z, : int(self.n_listed[z])]
 
 
+class CPileup(C.Structure):
+    _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
+                ("mismatches", C.POINTER(C.c_uint8))]
+
+
+@dataclass
+class Pileup:
+    """ccsx_pileup: the per-base pileup summary (DESIGN.md §2 "Pileup summary"), planes indexed like Results.seq.  sa / sm / sx give one ZMW's
+    tags of docs/faq/bam-output.md:25-27: sa run-length encoded as uint32 (length, coverage) pairs, sm / sx as uint8 per base."""
+    seq_off: np.ndarray
+    seq_len: np.ndarray
+    coverage: np.ndarray
+    matches: np.ndarray
+    mismatches: np.ndarray
+
+    @staticmethod
+    def allocate(results: "Results", pinned: bool = False) -> "Pileup":
+        """three planes of the results' capacity; seq_off / seq_len are the results' own arrays (filled when the results are).  pinned=True: page-locked
+        planes for Handle.submit"""
+        cap = len(results.seq)
+        keep = []
+
+        def z():
+            if not pinned:
+                return np.zeros(cap, np.uint8)
+            p = lib().ccsx_alloc_pinned(max(1, cap))
+            if not p:
+                raise RuntimeError("ccsx_alloc_pinned failed: " + lib().ccsx_last_error().decode())
+            keep.append(_Pinned(p))
+            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(1, cap),))[:cap]
+            a[...] = 0
+            return a
+        pl = Pileup(results.seq_off, results.seq_len, z(), z(), z())
+        pl._pinned = keep
+        return pl
+
+    def c_struct(self) -> CPileup:
+        c = CPileup()
+        c.seq_capacity = len(self.coverage)
+        c.coverage, c.matches, c.mismatches = (_ptr(a, C.c_uint8) for a in (self.coverage, self.matches, self.mismatches))
+        return c
+
+    def _plane(self, a: np.ndarray, z: int) -> np.ndarray:
+        o = int(self.seq_off[z])
+        return a[o:o + int(self.seq_len[z])]
+
+    def cov(self, z: int) -> np.ndarray:
+        return self._plane(self.coverage, z)
+
+    def sm(self, z: int) -> np.ndarray:
+        return self._plane(self.matches, z)
+
+    def sx(self, z: int) -> np.ndarray:
+        return self._plane(self.mismatches, z)
+
+    def sa(self, z: int) -> np.ndarray:
+        return rle(self.cov(z))
+
+
+def rle(v: np.ndarray) -> np.ndarray:
+    """run-length encoding of a plane as the sa tag stores it: uint32 [length, value, length, value, ...]"""
+    v = np.asarray(v)
+    if len(v) == 0:
+        return np.zeros(0, np.uint32)
+    starts = np.flatnonzero(np.concatenate([[True], v[1:] != v[:-1]]))
+    lens = np.diff(np.concatenate([starts, [len(v)]]))
+    return np.stack([lens, v[starts]], axis=1).astype(np.uint32).reshape(-1)
+
+
+def unrle(pairs: np.ndarray) -> np.ndarray:
+    p = np.asarray(pairs, np.int64).reshape(-1, 2)
+    return np.repeat(p[:, 1], p[:, 0]).astype(np.uint8)
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("setup_ms", C.c_float), ("draft_ms", C.c_float), ("align_ms", C.c_float), ("polish_ms", C.c_float),
@@ -162,6 +236,7 @@ EXPORTS = [
     "ccsx_model_from_json", "ccsx_model_load", "ccsx_model_to_json", "ccsx_model_for_chemistry",
     "ccsx_build_flags", "ccsx_runtime_switches", "ccsx_pci_numa_node", "ccsx_device_numa_node", "ccsx_bind_thread_to_node", "ccsx_bind_thread_to_device", "ccsx_draft_layout", "ccsx_draft_batch", "ccsx_polish_batch", "ccsx_submit_draft", "ccsx_submit_polish",
     "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
+    "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished",
 ]
 
 _lib = None
@@ -216,6 +291,10 @@ def lib() -> C.CDLL:
         L.ccsx_hd_opts_default.restype = None
         L.ccsx_hd_opts_default.argtypes = [C.POINTER(HdOpts)]
         L.ccsx_hd_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(HdOpts), C.POINTER(CHdReport)]
+        L.ccsx_consensus_pileup.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CPileup)]
+        L.ccsx_submit_pileup.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CPileup), C.POINTER(C.c_int64)]
+        L.ccsx_stage_polished.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -594,6 +673,24 @@ class Handle:
         self._check(self._L.ccsx_hd_batch(self._h, C.byref(cb), C.byref(cd), C.byref(o), C.byref(cr)), "ccsx_hd_batch")
         return rep
 
+    # ---- the pileup summary (sa sm sx): the fused path plus per-base planes from the kinetics alignment
+    def consensus_pileup(self, batch: Batch) -> tuple["Results", "Pileup"]:
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        pile = Pileup.allocate(res)
+        cb, cr, cp = batch.c_struct(), res.c_struct(), pile.c_struct()
+        self._check(self._L.ccsx_consensus_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp)), "ccsx_consensus_pileup")
+        return res, pile
+
+    def stage_polished(self, z: int):
+        """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
+        cap = 1 << 14
+        tpl, meta = np.zeros(cap * 32, np.uint8), np.zeros(cap * 3, np.int32)
+        nw, nr, bb = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._L.ccsx_stage_polished(self._h, z, _ptr(tpl, C.c_uint8), _ptr(meta, C.c_int32), cap, C.byref(nw), C.byref(nr), C.byref(bb)),
+                    "ccsx_stage_polished")
+        n = nw.value
+        return tpl[: n * 32].reshape(n, 32).copy(), meta[: n * 3].reshape(n, 3).copy(), nr.value, bb.value
+
     def upload(self, batch: Batch):
         self._keep = batch
         cb = batch.c_struct()
@@ -617,13 +714,19 @@ class Handle:
         return t
 
     # ---- asynchronous pipeline (ccsx_submit / ccsx_wait): up to three batches in flight, copies under compute
-    def submit(self, batch: Batch, res: "Results") -> int:
+    def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None) -> int:
+        """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is"""
         cb, cr = batch.c_struct(), res.c_struct()
         t = C.c_int64()
-        self._check(self._L.ccsx_submit(self._h, C.byref(cb), C.byref(cr), C.byref(t)), "ccsx_submit")
+        if pileup is None:
+            self._check(self._L.ccsx_submit(self._h, C.byref(cb), C.byref(cr), C.byref(t)), "ccsx_submit")
+            cp = None
+        else:
+            cp = pileup.c_struct()
+            self._check(self._L.ccsx_submit_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp), C.byref(t)), "ccsx_submit_pileup")
         if not hasattr(self, "_inflight"):
             self._inflight = {}
-        self._inflight[t.value] = (batch, res, cb, cr)      # the C structs and arrays must outlive the ticket
+        self._inflight[t.value] = (batch, res, cb, cr, pileup, cp)      # the C structs and arrays must outlive the ticket
         return t.value
 
     def wait(self, ticket: int) -> "Results":

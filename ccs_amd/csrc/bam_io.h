@@ -665,6 +665,11 @@ struct RecordBuilder {
         b.push_back(t[0]); b.push_back(t[1]); b.push_back('B'); b.push_back('C'); u32(n);
         b.insert(b.end(), v, v + n);
     }
+    void tagBI(const char *t, const uint32_t *v, uint32_t n)
+    {
+        b.push_back(t[0]); b.push_back(t[1]); b.push_back('B'); b.push_back('I'); u32(n);
+        for (uint32_t i = 0; i < n; ++i) u32(v[i]);
+    }
     void finish(BgzfWriter &out)
     {
         const uint32_t bs = (uint32_t)b.size() - 4;

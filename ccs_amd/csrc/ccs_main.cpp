@@ -63,6 +63,7 @@ struct Options {
     bool by_strand = false;       // --by-strand: one consensus per strand (docs/faq/mode-by-strand.md:8-23)
     bool no_partial = false;      // --no-partial-passes: drop the subreads that are not flanked by adapters on both sides (as round 2 did)
     bool qv_binning = false;      // --qv-binning: 7-bin per-base QVs after rq is computed (docs/faq/qv-binning.md:19-31)
+    bool pileup = false;          // --pileup-summary: per-base tags sa sm sx (docs/faq/bam-output.md:25-27; opt-in here)
     bool suppress_reports = false; // --suppress-reports: no report / metrics files "per default" — a file that is NAMED is still written (docs/faq/sqiie.md:36-46)
     bool report_named = false, metrics_named = false;
     std::string metrics;          // --metrics-json (default <prefix>.zmw_metrics.json.gz)
@@ -123,11 +124,13 @@ struct Batch {
     int32_t n = 0; int64_t cap = 0;
     int32_t *status = nullptr, *seq_len = nullptr, *np = nullptr, *iters = nullptr, *n_windows = nullptr, *fn = nullptr, *rn = nullptr;
     uint8_t *seq = nullptr, *qual = nullptr, *kin = nullptr;   // kin: 4 planes (fi, fp, ri, rp) of cap bytes each (--hifi-kinetics)
+    uint8_t *pile = nullptr;      // 3 planes (coverage, matches, mismatches) of cap bytes each (--pileup-summary)
     float *rq = nullptr, *ec = nullptr;
     int dev = 0;                  // which device's packers / worker / staging pools handle the batch (index into the handle list)
     bool have_results = false;    // false: packing or the engine failed for this batch
     std::unique_ptr<struct Arena> in_arena, out_arena;
     ccsx_batch cb; ccsx_results cr; // the structs handed to ccsx_submit live as long as the ticket
+    ccsx_pileup cp{};               // ... and the one handed to ccsx_submit_pileup
 };
 
 template <class T> class Channel {
@@ -181,6 +184,7 @@ void usage()
                  "      --no-partial-passes   do not use the first / last (one-adapter) subread of a ZMW in the polish\n"
                  "      --qv-binning          write 7-bin per-base QVs (Q3 Q10 Q17 Q22 Q27 Q35 Q40)\n"
                  "      --hifi-kinetics       averaged per-strand kinetics: tags fi fp fn ri rp rn (ip pw with --by-strand)\n"
+                 "      --pileup-summary      per-base pileup tags: sa (run-length encoded coverage), sm (matches), sx (mismatches) [off]\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -236,6 +240,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--no-partial-passes") o.no_partial = true;
         else if (a == "--qv-binning") o.qv_binning = true;
         else if (a == "--hifi-kinetics") o.o.hifi_kinetics = 1;
+        else if (a == "--pileup-summary") o.pileup = true;
         else if (a == "--suppress-reports") o.suppress_reports = true;
         else if (a == "--model-file") o.model_file = need(a.c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
@@ -901,7 +906,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve(9 * n4 + (kin ? 6 : 2) * c1);
+                        uint8_t *o = b->out_arena->reserve(9 * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
                         b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
@@ -913,6 +918,10 @@ int main(int argc, char **argv)
                             b->kin = take(4 * c1);
                             // planes are cap bytes apart in the library's result layout
                             b->cr.fi = b->kin; b->cr.fp = b->kin + cap; b->cr.ri = b->kin + 2 * cap; b->cr.rp = b->kin + 3 * cap;
+                        }
+                        if (opt.pileup) {
+                            b->pile = take(3 * c1);
+                            b->cp = ccsx_pileup{cap, b->pile, b->pile + cap, b->pile + 2 * cap};
                         }
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
@@ -974,7 +983,7 @@ int main(int argc, char **argv)
                 if (inflight.size() >= 3) retire();
                 t0 = now();
                 ccsx_ticket t = -1;
-                if (ccsx_submit(h, &b->cb, &b->cr, &t)) {
+                if (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1004,6 +1013,7 @@ int main(int argc, char **argv)
             RecordBuilder rb;
             PbiIndex pbi; std::vector<uint64_t> marks;             // OUT.bam.pbi: one entry per HiFi record
             std::vector<uint8_t> kin_rev;
+            std::vector<uint32_t> sa_rle;
             std::shared_ptr<Batch> b;
             double last_progress = -1e30;
             std::string metrics = "{\n  \"zmws\": [\n";
@@ -1079,6 +1089,20 @@ int main(int argc, char **argv)
                             kin_rev.assign(rp, rp + nr); std::reverse(kin_rev.begin(), kin_rev.end());
                             rb.tagBC("rp", kin_rev.data(), nr); rb.tagi("rn", bt.rn[s]);
                         }
+                    }
+                    if (opt.pileup) {                               // docs/faq/bam-output.md:25-27; the rule: DESIGN.md §2 "Pileup summary"
+                        const size_t cap = (size_t)bt.cap;
+                        const uint8_t *cov = bt.pile + o;
+                        sa_rle.clear();
+                        for (int32_t q = 0; q < len;) {             // sa: <length>,<coverage>,... runs of equal coverage
+                            int32_t e = q + 1;
+                            while (e < len && cov[e] == cov[q]) ++e;
+                            sa_rle.push_back((uint32_t)(e - q)); sa_rle.push_back(cov[q]);
+                            q = e;
+                        }
+                        rb.tagBI("sa", sa_rle.data(), (uint32_t)sa_rle.size());
+                        rb.tagBC("sm", cov + cap, (uint32_t)len);
+                        rb.tagBC("sx", cov + 2 * cap, (uint32_t)len);
                     }
                     marks.push_back(outp->mark());
                     pbi.rg_id.push_back(0); pbi.q_start.push_back(0); pbi.q_end.push_back(len); pbi.hole.push_back(z.zm);

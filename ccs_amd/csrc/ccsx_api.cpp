@@ -107,7 +107,8 @@ struct Slot {
     DevBuf d_avalid, d_ascore, d_ent;
     DevBuf d_wseq, d_wqv, d_wsum, d_wmeta;
     DevBuf d_out_seq, d_out_qual, d_out_raw, d_out_i32 /* 6 x n */, d_out_f32 /* 2 x n */;
-    DevBuf d_wtpl, d_wtmeta, d_wkin, d_out_kin;   // HiFi kinetics only
+    DevBuf d_wtpl, d_wtmeta, d_wkin, d_out_kin;   // HiFi kinetics only (d_wtpl, d_wtmeta: also the pileup summary)
+    DevBuf d_wpile, d_out_pile;                   // pileup summary only (ccsx_consensus_pileup / ccsx_submit_pileup)
     DevBuf d_din_len, d_din_bb;                   // caller-supplied drafts (ccsx_polish_batch): lengths, orientation references
     DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
@@ -131,7 +132,7 @@ struct Slot {
         DevBuf *bufs[] = {&d_snr, &d_read_off, &d_base_off, &d_bases, &d_pw, &d_ipd, &d_flags, &d_read_zmw, &d_vcap, &d_dcap, &d_seq_off,
                           &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
                           &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
-                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_din_len, &d_din_bb,
+                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_din_len, &d_din_bb,
                           &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites};
         for (auto *b : bufs) b->release();
         read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
@@ -363,7 +364,8 @@ static int validate(const ccsx_batch *b)
 
 // Stage a batch into a slot: host-derived layout, device buffers, H2D copies enqueued on `st` (nothing waits here except
 // hipMalloc growth).  The batch's own arrays must stay valid until the copies have run (pinned arrays copy by DMA).
-static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st)
+// pile: this run also computes the pileup summary (its buffers are reserved and its pointers set only then).
+static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bool pile = false)
 {
     if (validate(b)) return -1;
     const bool kin = h->opts.hifi_kinetics != 0;
@@ -472,10 +474,9 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st)
     RES(S.d_wsum, (size_t)(total_wslots + 1) * 4); RES(S.d_wmeta, (size_t)(total_wslots + 1) * 16);
     RES(S.d_out_seq, (size_t)cap_total); RES(S.d_out_qual, (size_t)cap_total); RES(S.d_out_raw, (size_t)cap_total * 4);
     RES(S.d_out_i32, (size_t)n * 4 * 6); RES(S.d_out_f32, (size_t)n * 4 * 2);
-    if (kin) {
-        RES(S.d_wtpl, (size_t)(total_wslots + 1) * 32); RES(S.d_wtmeta, (size_t)(total_wslots + 1) * 4);
-        RES(S.d_wkin, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_kin, (size_t)cap_total * 4);
-    }
+    if (kin || pile) { RES(S.d_wtpl, (size_t)(total_wslots + 1) * 32); RES(S.d_wtmeta, (size_t)(total_wslots + 1) * 4); }
+    if (kin) { RES(S.d_wkin, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_kin, (size_t)cap_total * 4); }
+    if (pile) { RES(S.d_wpile, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_pile, (size_t)cap_total * 3); }
 
     // ---- resident POA graphs / alignment slots: as many as fit this handle's share of the free memory, never more than
     // the work.  The scratch is shared by the handle's batch slots; it only grows, and growing waits for the compute stream.
@@ -564,11 +565,13 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st)
     int32_t *oi = (int32_t *)S.d_out_i32.p;
     P.out_status = oi; P.out_len = oi + n; P.out_iters = oi + 2 * (size_t)n; P.out_nwin = oi + 3 * (size_t)n;
     P.out_fn = oi + 4 * (size_t)n; P.out_rn = oi + 5 * (size_t)n;
+    if (kin || pile) { P.wtpl = (uint8_t *)S.d_wtpl.p; P.wtmeta = (short2 *)S.d_wtmeta.p; }   // k_polish keeps the converged templates
     if (kin) {
         P.ipd = (const uint8_t *)S.d_ipd.p;
-        P.wtpl = (uint8_t *)S.d_wtpl.p; P.wtmeta = (short2 *)S.d_wtmeta.p; P.wkin = (uchar4 *)S.d_wkin.p;
+        P.wkin = (uchar4 *)S.d_wkin.p;
         P.out_kin = (uint8_t *)S.d_out_kin.p; P.kin_plane = cap_total;
     }
+    if (pile) { P.wpile = (uchar4 *)S.d_wpile.p; P.out_pile = (uint8_t *)S.d_out_pile.p; P.pile_plane = cap_total; }
     float *of = (float *)S.d_out_f32.p;
     P.out_rq = of; P.out_ec = of + n;
     S.staged = true; S.ran = false; S.tm_ok = false;
@@ -606,6 +609,24 @@ static int check_results(const Slot &S, const ccsx_results *res, bool have_kin)
         ccsx_set_error("ccsx_download: kinetics buffers given but the handle was created without opts.hifi_kinetics");
         return -1;
     }
+    return 0;
+}
+
+static int check_pile(const Slot &S, const ccsx_pileup *pile)
+{
+    if (!pile || !pile->coverage || !pile->matches || !pile->mismatches || pile->seq_capacity < S.seq_off[S.P.n_zmw]) {
+        ccsx_set_error("ccsx_pileup: missing planes, or smaller than the capacity layout (ccsx_result_layout)"); return -1;
+    }
+    return 0;
+}
+
+// the three planes of the pileup summary (the slot was staged with pile = true)
+static int enqueue_pile_download(const Slot &S, ccsx_pileup *pile, hipStream_t s)
+{
+    const size_t pl = (size_t)S.seq_off[S.P.n_zmw];
+    HIPTRY(hipMemcpyAsync(pile->coverage, S.P.out_pile, pl, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(pile->matches, S.P.out_pile + pl, pl, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(pile->mismatches, S.P.out_pile + 2 * pl, pl, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -680,7 +701,8 @@ static int upload_drafts(Slot &S, const ccsx_drafts *d, hipStream_t st)
 }
 
 // one batch through the handle's pipeline: the fused path (ccsx_submit), the draft seam or the polish seam
-static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags)
+static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
+                       ccsx_pileup *pile = nullptr)
 {
     if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) { ccsx_set_error("ccsx_submit: null argument"); return -1; }
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
@@ -701,9 +723,10 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         h->poisoned = true;
         return rc_;
     };
-    int rc = stage(h, S, b, h->s_in);
+    int rc = stage(h, S, b, h->s_in, pile != nullptr);
     if (rc) return rc == -1 ? (S.staged = false, rc) : fail(rc);     // -1: rejected by validation before anything was enqueued
     if (mode != CCSX_RUN_DRAFT && (rc = check_results(S, res, S.P.out_kin != nullptr))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
+    if (pile && (rc = check_pile(S, pile))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     if (mode != CCSX_RUN_FUSED && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     S.mode = mode;
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
@@ -724,6 +747,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         if (dr_out->n_windows) HIPTRY_F(hipMemcpyAsync(dr_out->n_windows, P.nwin, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));
         if (dr_out->win_bounds) HIPTRY_F(hipMemcpyAsync(dr_out->win_bounds, P.wbounds, (size_t)S.wb_off[n] * 4, hipMemcpyDeviceToHost, h->s_out));
     } else if ((rc = enqueue_download(S, res, h->s_out))) return fail(rc);
+    if (pile && (rc = enqueue_pile_download(S, pile, h->s_out))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -735,6 +759,11 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
 int ccsx_submit(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket)
 {
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0);
+}
+int ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile, ccsx_ticket *ticket)
+{
+    if (!pile) { ccsx_set_error("ccsx_submit_pileup: null argument"); return -1; }
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, pile);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
 {
@@ -793,20 +822,22 @@ int ccsx_ticket_timings(ccsx_handle h, ccsx_ticket ticket, ccsx_timings *t)
 }
 
 // ---- synchronous form (slot 0): parity tests, stage read-backs, the resident-input leg of the benchmark ----
-int ccsx_upload(ccsx_handle h, const ccsx_batch *b)
+static int upload_impl(ccsx_handle h, const ccsx_batch *b, bool pile)
 {
     if (!h) { ccsx_set_error("ccsx_upload: null handle"); return -1; }
     HIPTRY(hipSetDevice(h->device));
     for (auto &S : h->slot) if (int rc = retire(h, S)) return rc;
     Slot &S = h->slot[0];
     S.ticket = -1;                                       // (slot 0 is re-staged: its ticket is recycled, as by a submit; the other slots' tickets stay valid)
-    const int rc = stage(h, S, b, h->s_comp);
+    const int rc = stage(h, S, b, h->s_comp, pile);
     if (rc) { S.staged = false; return rc; }
     S.mode = CCSX_RUN_FUSED;
     HIPTRY(hipStreamSynchronize(h->s_comp));
     h->last = 0;
     return 0;
 }
+
+int ccsx_upload(ccsx_handle h, const ccsx_batch *b) { return upload_impl(h, b, false); }
 
 int ccsx_run(ccsx_handle h)
 {
@@ -867,6 +898,21 @@ int ccsx_consensus_batch(ccsx_handle h, const ccsx_batch *b, ccsx_results *res)
     if ((rc = ccsx_run(h))) return rc;
     if ((rc = ccsx_sync(h))) return rc;
     return ccsx_download(h, res);
+}
+
+int ccsx_pileup_rule_version(void) { return 1; }
+
+int ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile)
+{
+    if (!h || !b || !res || !pile) { ccsx_set_error("ccsx_consensus_pileup: null argument"); return -1; }
+    int rc;
+    if ((rc = upload_impl(h, b, true))) return rc;
+    Slot &S = h->slot[0];
+    if ((rc = check_pile(S, pile))) return rc;
+    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
+    if ((rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
 }
 
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)
@@ -954,6 +1000,32 @@ int ccsx_stage_align(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, int
             rstart[col] = ent[k];
         }
     }
+    return 0;
+}
+
+// the converged window templates k_polish kept (a run staged with kinetics or the pileup summary): per window the template, J and [cs, ce)
+int ccsx_stage_polished(ccsx_handle h, int32_t z, uint8_t *tpl, int32_t *meta, int32_t cap, int32_t *n_windows, int32_t *passes_used, int32_t *backbone)
+{
+    if (int rc = stage_guard(h, z, false, "ccsx_stage_polished")) return rc;
+    const Slot &S = h->slot[0];
+    if (!S.P.wtpl || S.mode != CCSX_RUN_FUSED) { ccsx_set_error("ccsx_stage_polished: the last synchronous run kept no window templates (ccsx_consensus_pileup first)"); return -1; }
+    if (!tpl || !meta || !n_windows || !passes_used || !backbone) { ccsx_set_error("ccsx_stage_polished: null argument"); return -1; }
+    int32_t st = 0, nw = 0, nr = 0, zr = 0;
+    HIPTRY(hipMemcpy(&st, S.P.zstat + z, 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(&nw, S.P.nwin + z, 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(&nr, S.P.nreads_used + z, 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(&zr, S.P.zref + z, 4, hipMemcpyDeviceToHost));
+    if (st != CCSX_SUCCESS) nw = 0;                      // (k_stitch stitches no window of such a ZMW)
+    if (nw > cap) { ccsx_set_error("ccsx_stage_polished: buffer too small"); return -1; }
+    if (nw > 0) {
+        const size_t w0 = (size_t)(S.wb_off[z] - z);
+        std::vector<short2> tm(nw); std::vector<int4> wm(nw);
+        HIPTRY(hipMemcpy(tpl, S.P.wtpl + w0 * 32, (size_t)nw * 32, hipMemcpyDeviceToHost));
+        HIPTRY(hipMemcpy(tm.data(), S.P.wtmeta + w0, (size_t)nw * sizeof(short2), hipMemcpyDeviceToHost));
+        HIPTRY(hipMemcpy(wm.data(), S.P.wmeta + w0, (size_t)nw * sizeof(int4), hipMemcpyDeviceToHost));
+        for (int w = 0; w < nw; ++w) { meta[3 * w] = tm[w].x; meta[3 * w + 1] = tm[w].y; meta[3 * w + 2] = tm[w].y + wm[w].x; }
+    }
+    *n_windows = nw; *passes_used = nr; *backbone = zr & 255;
     return 0;
 }
 

@@ -109,6 +109,10 @@ struct KParams {
     int32_t *hd_zi;            // [5][n] verdict, sub sites, indel sites, listed, indel sites listed
     double *hd_minp;           // [n]
     ccsx_hd_site *hd_sites;    // [n][CCSX_HD_MAX_SITES]
+    // ---- pileup summary (ccsx_consensus_pileup / ccsx_submit_pileup only; NULL otherwise).  Needs wtpl / wtmeta as kinetics does
+    uchar4 *wpile;             // [wslots][32] (coverage, matches, mismatches, 0) of the core positions
+    uint8_t *out_pile;         // 3 planes (coverage, matches, mismatches) of seq_off[n] bytes each
+    long long pile_plane;      // plane stride = seq_off[n]
 };
 
 #define CCSX_HD_LF_N (2 * CCSX_MAX_PASSES + 1)   // log-factorials 0 .. 510: a Fisher table never holds more passes than that

@@ -13,7 +13,9 @@
 //   k_polish      A1-A6 Arrow alpha/beta fill, candidate filter, mutation scoring, polish loop, QVs; one workgroup per window
 //                                                                                            (docs/how-does-ccs-work.md:57-61,80-106)
 //   k_kinetics    N4    HiFi kinetics of the converged windows                               (docs/faq/kinetics.md:8-18)
+//                       and / or the pileup summary (sa sm sx) from the same alignment         (docs/faq/bam-output.md:25-27)
 //   k_stitch      step10 concatenate window cores, rq / np / ec, status                      (docs/how-does-ccs-work.md:108-112)
+//   k_pile_stitch       the pileup summary's per-base planes (only with a pileup request)
 //
 // The arithmetic follows DESIGN.md §SPEC operation by operation (compiled with -ffp-contract=off, no
 // fast-math) so that sequences are bit-identical to the CPU restatement.  No MFMA: the recurrences are
@@ -3251,10 +3253,16 @@ __device__ __forceinline__ int kin_traceback_runs(int upm, unsigned long long nd
     return myrow;
 }
 
-__global__ __launch_bounds__(256) void k_kinetics(KParams P, int slot0)
+// KIN: the kinetics sums (--hifi-kinetics); PILE: the pileup summary (ccsx_consensus_pileup / ccsx_submit_pileup, DESIGN.md §2 "Pileup summary") — per core
+// column the passes with a usable segment, and of those the DIAG cells whose bases agree / differ.  Both read the ONE alignment below; <1, 0> is the kinetics
+// kernel as it always was.
+template <int KIN, int PILE>
+__global__ __launch_bounds__(256) void k_kinetics_t(KParams P, int slot0)
 {
     __shared__ uint8_t sT[2][32];
     __shared__ unsigned sK[2][3][32];                       // [strand][ipd, pw, count][forward column]
+    __shared__ unsigned sPM[2][32];                         // PILE: [match, mismatch][forward column]
+    __shared__ int sCov;                                    // PILE: passes with a usable segment (over all groups)
     __shared__ int sN[PW_MAXREADS], sOff[PW_MAXREADS];      // segment length (-1 = unusable), offset of the segment in the read
     __shared__ uint8_t sSt[PW_MAXREADS];
     __shared__ short2 sTask[PW_MAXREADS];
@@ -3271,7 +3279,9 @@ __global__ __launch_bounds__(256) void k_kinetics(KParams P, int slot0)
     const int r0 = P.read_off[z], nreads = P.nreads_used[z];
     const int idx_ws = (w == 0) ? 0 : 2 * w - 1, idx_we = (w == nw - 1) ? 2 * nw - 1 : 2 * (w + 1);
     if (tid < J) { const uint8_t b = P.wtpl[wi * 32 + tid]; sT[0][tid] = b; sT[1][J - 1 - tid] = (uint8_t)(3 - b); }
-    if (tid < 192) (&sK[0][0][0])[tid] = 0u;
+    if (KIN && tid < 192) (&sK[0][0][0])[tid] = 0u;
+    if (PILE && tid < 64) (&sPM[0][0])[tid] = 0u;
+    if (PILE && tid == 0) sCov = 0;
     // SPEC v5: up to CCSX_MAX_PASSES passes, taken in groups of PW_MAXREADS (the sums in sK run over all groups)
     for (int g0 = 0; g0 < nreads; g0 += PW_MAXREADS) {
     const int ng = nreads - g0 < PW_MAXREADS ? nreads - g0 : PW_MAXREADS;
@@ -3301,6 +3311,7 @@ __global__ __launch_bounds__(256) void k_kinetics(KParams P, int slot0)
         }
         if (pend >= 0) sTask[nt++] = make_short2((short)pend, (short)-1);
         sNT = nt;
+        if (PILE) { int nc = 0; for (int r = 0; r < ng; ++r) nc += sN[r] >= 0 ? 1 : 0; sCov += nc; }
     }
     __syncthreads();
     const int ntask = sNT;
@@ -3353,10 +3364,14 @@ __global__ __launch_bounds__(256) void k_kinetics(KParams P, int slot0)
         if (row < J && myrow >= 0) {
             const int jf = st ? J - 1 - row : row;
             const int64_t p = p0 + myrow;
-            if (jf >= cs && jf < ce && (P.bases[p] & 3) == t[row]) {
-                atomicAdd(&sK[st][0][jf], (unsigned)codec_v1_decode(P.ipd[p]));
-                atomicAdd(&sK[st][1][jf], (unsigned)codec_v1_decode(P.pw[p]));
-                atomicAdd(&sK[st][2][jf], 1u);
+            if (jf >= cs && jf < ce) {
+                const bool same = (P.bases[p] & 3) == t[row];
+                if (KIN && same) {
+                    atomicAdd(&sK[st][0][jf], (unsigned)codec_v1_decode(P.ipd[p]));
+                    atomicAdd(&sK[st][1][jf], (unsigned)codec_v1_decode(P.pw[p]));
+                    atomicAdd(&sK[st][2][jf], 1u);
+                }
+                if (PILE) atomicAdd(&sPM[same ? 0 : 1][jf], 1u);
             }
         }
     }
@@ -3364,10 +3379,13 @@ __global__ __launch_bounds__(256) void k_kinetics(KParams P, int slot0)
     __syncthreads();
     if (tid < ce - cs) {
         const int c = cs + tid;
-        uchar4 k;
-        k.x = (uint8_t)kin_mean_code(sK[0][0][c], sK[0][2][c]); k.y = (uint8_t)kin_mean_code(sK[0][1][c], sK[0][2][c]);
-        k.z = (uint8_t)kin_mean_code(sK[1][0][c], sK[1][2][c]); k.w = (uint8_t)kin_mean_code(sK[1][1][c], sK[1][2][c]);
-        P.wkin[wi * 32 + tid] = k;
+        if (KIN) {
+            uchar4 k;
+            k.x = (uint8_t)kin_mean_code(sK[0][0][c], sK[0][2][c]); k.y = (uint8_t)kin_mean_code(sK[0][1][c], sK[0][2][c]);
+            k.z = (uint8_t)kin_mean_code(sK[1][0][c], sK[1][2][c]); k.w = (uint8_t)kin_mean_code(sK[1][1][c], sK[1][2][c]);
+            P.wkin[wi * 32 + tid] = k;
+        }
+        if (PILE) P.wpile[wi * 32 + tid] = make_uchar4((uint8_t)sCov, (uint8_t)sPM[0][c], (uint8_t)sPM[1][c], 0);   // (<= CCSX_MAX_PASSES each)
     }
 }
 
@@ -3467,6 +3485,33 @@ __global__ __launch_bounds__(64) void k_stitch(KParams P)
         } else len = 0;
         P.out_status[z] = stat; P.out_len[z] = (int32_t)len; P.out_rq[z] = rq; P.out_ec[z] = ec;
         P.out_iters[z] = its; P.out_nwin[z] = nw;
+    }
+}
+
+// the pileup summary's planes (only with a pileup request; k_stitch itself is untouched): one wave per ZMW, the same windows and offsets as k_stitch —
+// a ZMW whose status before stitching is not SUCCESS has none, and nothing is written at or beyond the ZMW's capacity
+__global__ __launch_bounds__(64) void k_pile_stitch(KParams P)
+{
+    const int z = blockIdx.x, lane = threadIdx.x;
+    const int nw = (P.zstat[z] == CCSX_SUCCESS) ? P.nwin[z] : 0;
+    const size_t w0 = (size_t)(P.wb_off[z] - z);
+    const int64_t so = P.seq_off[z], cap = P.seq_off[z + 1] - so;
+    int64_t run = 0;
+    for (int wbase = 0; wbase < nw; wbase += LANES) {
+        const int w = wbase + lane;
+        const int len = w < nw ? P.wmeta[w0 + w].x : 0;
+        int pre = len;                                      // inclusive scan of the core lengths
+#pragma unroll
+        for (int s = 1; s < LANES; s <<= 1) { int o = __shfl_up(pre, s); if (lane >= s) pre += o; }
+        const int64_t off = run + pre - len;
+        for (int k = 0; k < len; ++k) {
+            if (off + k < cap) {
+                const uchar4 pp = P.wpile[(w0 + w) * 32 + k];
+                uint8_t *o = P.out_pile + so + off + k;
+                o[0] = pp.x; o[P.pile_plane] = pp.y; o[2 * P.pile_plane] = pp.z;
+            }
+        }
+        run += __shfl(pre, 63);
     }
 }
 
@@ -3970,17 +4015,23 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
         LAUNCH_CHECK("k_polish");
     }
     trace_sync(st, "k_polish");
-    if (P.opts.hifi_kinetics) {
+    if (P.opts.hifi_kinetics || P.wpile) {                 // one alignment per (pass, window) segment feeds kinetics, the pileup summary or both
+        const bool kin = P.opts.hifi_kinetics != 0, pile = P.wpile != nullptr;
+        auto kfn = kin ? (pile ? k_kinetics_t<1, 1> : k_kinetics_t<1, 0>) : k_kinetics_t<0, 1>;
         for (long long s0 = 0; s0 < P.total_wslots; s0 += max_blocks) {
             const unsigned nb = (unsigned)((P.total_wslots - s0) < max_blocks ? (P.total_wslots - s0) : max_blocks);
-            hipLaunchKernelGGL(k_kinetics, dim3((nb + 7u) & ~7u), dim3(256), 0, st, P, (int)s0);
-            LAUNCH_CHECK("k_kinetics");
+            hipLaunchKernelGGL(kfn, dim3((nb + 7u) & ~7u), dim3(256), 0, st, P, (int)s0);
+            LAUNCH_CHECK(kin ? (pile ? "k_kinetics_pile" : "k_kinetics") : "k_pileup");
         }
         trace_sync(st, "k_kinetics");
     }
     if (ev) CALL_CHECK(hipEventRecord, ev[4], st);
     hipLaunchKernelGGL(k_stitch, dim3(P.n_zmw), dim3(64), 0, st, P);
     LAUNCH_CHECK("k_stitch");
+    if (P.out_pile) {
+        hipLaunchKernelGGL(k_pile_stitch, dim3(P.n_zmw), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_pile_stitch");
+    }
     if (ev) CALL_CHECK(hipEventRecord, ev[5], st);
     return failed;
 }

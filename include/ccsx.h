@@ -313,6 +313,30 @@ void        ccsx_hd_opts_default(ccsx_hd_opts *o);
 int         ccsx_hd_rule_version(void);
 int         ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, const ccsx_hd_opts *o, ccsx_hd_report *out);
 
+/* ---- the pileup summary: per-base tags sa sm sx of docs/faq/bam-output.md:25-27 (the rule: DESIGN.md §2 "Pileup summary", its own version
+ * ccsx_pileup_rule_version; no result of the consensus changes).  After a window has converged, every used pass with a usable segment there (avalid,
+ * 0 <= n <= CCSX_IMAX: the passes the kinetics see) is aligned to the converged window template with the kinetics alignment; per consensus base
+ * `coverage` = such passes, `matches` / `mismatches` = those whose alignment puts a read base on the base (DIAG) that agrees / differs.  matches +
+ * mismatches <= coverage; coverage is constant over a window's core.  Planes are indexed like seq (orientation of SEQ, seq_off[z], seq_len[z] valid).
+ * ccsx_consensus_pileup = ccsx_consensus_batch + the planes (synchronous, slot 0); ccsx_submit_pileup = ccsx_submit + the planes: the arrays of `pile`
+ * follow the lifetime rule of `res` (see ccsx_submit) and should be page-locked.  Either works with or without opts.hifi_kinetics (one alignment feeds
+ * both).  Without a pileup request nothing of it runs.  (The polish seam with planes, ccsx_submit_polish + pileup, is not offered yet.)             */
+typedef struct ccsx_pileup {
+    int64_t  seq_capacity;       /* elements in each plane: the capacity layout of ccsx_result_layout (= ccsx_results.seq_capacity)              */
+    uint8_t *coverage;           /* [seq_capacity] passes covering the base (sa before run-length encoding)                                    */
+    uint8_t *matches;            /* [seq_capacity] aligned matches (sm)                                                                        */
+    uint8_t *mismatches;         /* [seq_capacity] aligned mismatches (sx)                                                                     */
+} ccsx_pileup;
+int         ccsx_pileup_rule_version(void);
+int         ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile);
+int         ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile, ccsx_ticket *ticket);
+/* the converged window templates of ZMW zmw_index after the last synchronous run that kept them (ccsx_consensus_pileup, or any synchronous run of a
+ * handle with opts.hifi_kinetics): tpl[w * 32 + k] (k < J), meta[w * 3 + 0..2] = J, core start cs, core end ce (the core is tpl[cs, ce)); n_windows = 0
+ * for a ZMW that failed before stitching.  passes_used = the ZMW's passes the engine used, backbone = the index (within the ZMW) of its strand reference.
+ * For parity tests (tests/pileup_ref.py).                                                                                                             */
+int         ccsx_stage_polished(ccsx_handle h, int32_t zmw_index, uint8_t *tpl, int32_t *meta, int32_t cap, int32_t *n_windows,
+                                int32_t *passes_used, int32_t *backbone);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
