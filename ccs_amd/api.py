@@ -10,6 +10,7 @@ docs/img/ccs-impl.png and the per-ZMW outputs of docs/faq/bam-output.md:9-30 (rq
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 import os
 from dataclasses import dataclass
 
@@ -214,6 +215,29 @@ def unrle(pairs: np.ndarray) -> np.ndarray:
     return np.repeat(p[:, 1], p[:, 0]).astype(np.uint8)
 
 
+class CExtras(C.Structure):
+    """ccsx_extras: optional outputs of the fused path (include/ccsx.h)"""
+    _fields_ = [("pile", C.POINTER(CPileup)), ("tandem_len", C.POINTER(C.c_int32)), ("min_tandem_repeat_length", C.c_int32), ("reserved", C.c_int32)]
+
+
+def tandem_buffer(n_zmw: int, pinned: bool = False) -> np.ndarray:
+    """an int32 [n_zmw] destination for tandem_len; pinned=True: page-locked (Handle.submit), kept alive by the array"""
+    if not pinned:
+        return np.zeros(n_zmw, np.int32)
+    p = lib().ccsx_alloc_pinned(max(1, n_zmw) * 4)
+    if not p:
+        raise RuntimeError("ccsx_alloc_pinned failed: " + lib().ccsx_last_error().decode())
+    owner = _Pinned(p)
+    a = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=(max(1, n_zmw),))[:n_zmw]
+    a[...] = 0
+    _PINNED_OWNERS[id(a)] = owner   # the page-locked block is freed with the array
+    weakref.finalize(a, _PINNED_OWNERS.pop, id(a), None)
+    return a
+
+
+_PINNED_OWNERS: dict = {}
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("setup_ms", C.c_float), ("draft_ms", C.c_float), ("align_ms", C.c_float), ("polish_ms", C.c_float),
@@ -237,6 +261,7 @@ EXPORTS = [
     "ccsx_build_flags", "ccsx_runtime_switches", "ccsx_pci_numa_node", "ccsx_device_numa_node", "ccsx_bind_thread_to_node", "ccsx_bind_thread_to_device", "ccsx_draft_layout", "ccsx_draft_batch", "ccsx_polish_batch", "ccsx_submit_draft", "ccsx_submit_polish",
     "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
     "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished",
+    "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
 ]
 
 _lib = None
@@ -295,6 +320,8 @@ def lib() -> C.CDLL:
         L.ccsx_submit_pileup.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CPileup), C.POINTER(C.c_int64)]
         L.ccsx_stage_polished.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.ccsx_consensus_extras.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras)]
+        L.ccsx_submit_extras.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -629,6 +656,15 @@ class Drafts:
         return self.win_bounds[o:o + int(self.n_windows[z]) + 1]
 
 
+def _extras(cp: "CPileup | None", tandem: "np.ndarray | None", min_len: int) -> CExtras:
+    ex = CExtras()
+    ex.pile = C.pointer(cp) if cp is not None else None
+    ex.tandem_len = _ptr(tandem, C.c_int32) if tandem is not None else None
+    ex.min_tandem_repeat_length = int(min_len)
+    ex.reserved = 0
+    return ex
+
+
 class Handle:
     """One consensus engine bound to one GPU (ccsx_create).  Not thread-safe: one per worker per GPU."""
 
@@ -681,6 +717,20 @@ class Handle:
         self._check(self._L.ccsx_consensus_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp)), "ccsx_consensus_pileup")
         return res, pile
 
+    # ---- optional outputs through ccsx_extras: tandem-repeat detection (DESIGN.md §2 "Tandem repeats") and / or the pileup summary
+    def consensus_extras(self, batch: Batch, tandem: bool = True, min_tandem_repeat_length: int = 0,
+                         pileup: bool = False) -> tuple["Results", "np.ndarray | None", "Pileup | None"]:
+        """ccsx_consensus_extras: (results, tandem_len [n_zmw] int32 or None, pileup or None).  min_tandem_repeat_length > 0: ZMWs whose deciding
+        draft has a masked run at least that long run with the heuristics off (as opts.disable_heuristics), the others as usual"""
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        tl = tandem_buffer(batch.n_zmw) if tandem else None
+        pile = Pileup.allocate(res) if pileup else None
+        cb, cr = batch.c_struct(), res.c_struct()
+        cp = pile.c_struct() if pile is not None else None
+        ex = _extras(cp, tl, min_tandem_repeat_length)
+        self._check(self._L.ccsx_consensus_extras(self._h, C.byref(cb), C.byref(cr), C.byref(ex)), "ccsx_consensus_extras")
+        return res, tl, pile
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -714,11 +764,20 @@ class Handle:
         return t
 
     # ---- asynchronous pipeline (ccsx_submit / ccsx_wait): up to three batches in flight, copies under compute
-    def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None) -> int:
-        """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is"""
+    def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None,
+               min_tandem_repeat_length: int = 0) -> int:
+        """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer,
+        pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras)"""
         cb, cr = batch.c_struct(), res.c_struct()
         t = C.c_int64()
-        if pileup is None:
+        ex = None
+        if tandem is not None or min_tandem_repeat_length:
+            if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
+                raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
+            cp = pileup.c_struct() if pileup is not None else None
+            ex = _extras(cp, tandem, min_tandem_repeat_length)
+            self._check(self._L.ccsx_submit_extras(self._h, C.byref(cb), C.byref(cr), C.byref(ex), C.byref(t)), "ccsx_submit_extras")
+        elif pileup is None:
             self._check(self._L.ccsx_submit(self._h, C.byref(cb), C.byref(cr), C.byref(t)), "ccsx_submit")
             cp = None
         else:
@@ -726,7 +785,7 @@ class Handle:
             self._check(self._L.ccsx_submit_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp), C.byref(t)), "ccsx_submit_pileup")
         if not hasattr(self, "_inflight"):
             self._inflight = {}
-        self._inflight[t.value] = (batch, res, cb, cr, pileup, cp)      # the C structs and arrays must outlive the ticket
+        self._inflight[t.value] = (batch, res, cb, cr, pileup, cp, tandem, ex)      # the C structs and arrays must outlive the ticket
         return t.value
 
     def wait(self, ticket: int) -> "Results":

@@ -64,6 +64,7 @@ struct Options {
     bool no_partial = false;      // --no-partial-passes: drop the subreads that are not flanked by adapters on both sides (as round 2 did)
     bool qv_binning = false;      // --qv-binning: 7-bin per-base QVs after rq is computed (docs/faq/qv-binning.md:19-31)
     bool pileup = false;          // --pileup-summary: per-base tags sa sm sx (docs/faq/bam-output.md:25-27; opt-in here)
+    int min_tandem = 0;           // --min-tandem-repeat-length: per-ZMW heuristics switch on sDUST (docs/faq/low-complexity.md:8-18; off here)
     bool suppress_reports = false; // --suppress-reports: no report / metrics files "per default" — a file that is NAMED is still written (docs/faq/sqiie.md:36-46)
     bool report_named = false, metrics_named = false;
     std::string metrics;          // --metrics-json (default <prefix>.zmw_metrics.json.gz)
@@ -125,12 +126,14 @@ struct Batch {
     int32_t *status = nullptr, *seq_len = nullptr, *np = nullptr, *iters = nullptr, *n_windows = nullptr, *fn = nullptr, *rn = nullptr;
     uint8_t *seq = nullptr, *qual = nullptr, *kin = nullptr;   // kin: 4 planes (fi, fp, ri, rp) of cap bytes each (--hifi-kinetics)
     uint8_t *pile = nullptr;      // 3 planes (coverage, matches, mismatches) of cap bytes each (--pileup-summary)
+    int32_t *tlen = nullptr;      // longest sDUST-masked run of each ZMW's deciding draft (--min-tandem-repeat-length)
     float *rq = nullptr, *ec = nullptr;
     int dev = 0;                  // which device's packers / worker / staging pools handle the batch (index into the handle list)
     bool have_results = false;    // false: packing or the engine failed for this batch
     std::unique_ptr<struct Arena> in_arena, out_arena;
     ccsx_batch cb; ccsx_results cr; // the structs handed to ccsx_submit live as long as the ticket
     ccsx_pileup cp{};               // ... and the one handed to ccsx_submit_pileup
+    ccsx_extras ex{};               // (ccsx_submit_extras reads it during the call only)
 };
 
 template <class T> class Channel {
@@ -185,6 +188,8 @@ void usage()
                  "      --qv-binning          write 7-bin per-base QVs (Q3 Q10 Q17 Q22 Q27 Q35 Q40)\n"
                  "      --hifi-kinetics       averaged per-strand kinetics: tags fi fp fn ri rp rn (ip pw with --by-strand)\n"
                  "      --pileup-summary      per-base pileup tags: sa (run-length encoded coverage), sm (matches), sx (mismatches) [off]\n"
+                 "      --min-tandem-repeat-length N  a ZMW whose draft holds a tandem repeat (sDUST) of >= N bases runs with --disable-heuristics\n"
+                 "                            for itself only; N > 0 [off: the reference's default is 1000]\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -241,6 +246,13 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--qv-binning") o.qv_binning = true;
         else if (a == "--hifi-kinetics") o.o.hifi_kinetics = 1;
         else if (a == "--pileup-summary") o.pileup = true;
+        else if (a == "--min-tandem-repeat-length") {
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n <= 0 || n > 0x7fffffffL) { std::fprintf(stderr, "ccs: --min-tandem-repeat-length needs a positive number of bases, got '%s'\n", v.c_str()); std::exit(2); }
+            o.min_tandem = (int)n;
+        }
         else if (a == "--suppress-reports") o.suppress_reports = true;
         else if (a == "--model-file") o.model_file = need(a.c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
@@ -478,6 +490,7 @@ struct Report {
     std::map<std::string, int64_t> fail;
     std::vector<int32_t> lens; std::vector<float> rqs; std::vector<int32_t> nps;   // one entry per written read
     int64_t bases_q30 = 0;        // written bases with a phred QV >= 30 ("Base quality >=Q30 (bp)", docs/faq/reports-aux-files.md:66)
+    int64_t tandem = 0;           // ZMWs flagged as tandem repeats (--min-tandem-repeat-length; docs/faq/reports-aux-files.md:22)
 };
 
 const char *fail_label(int st)
@@ -568,6 +581,7 @@ void write_report(const Options &o, const Report &r)
         std::fprintf(f, "ZMWs pass filters             : %" PRId64 " (%.2f%%)\n", r.pass, pct(r.pass, r.input));
         std::fprintf(f, "ZMWs fail filters             : %" PRId64 " (%.2f%%)\n", failed, pct(failed, r.input));
         std::fprintf(f, "ZMWs shortcut filters         : 0 (0.00%%)\n\n");
+        if (o.min_tandem > 0) std::fprintf(f, "ZMWs with tandem repeats      : %" PRId64 " (%.2f%%)\n\n", r.tandem, pct(r.tandem, r.input));
         std::fprintf(f, "Exclusive failed counts\n");
         for (const char *k : kFailOrder) {
             auto it = r.fail.find(k);
@@ -605,8 +619,10 @@ void write_report_json(const Options &o, const Report &r)
 {
     FILE *f = std::fopen(o.report_json.c_str(), "w");
     if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", o.report_json.c_str()); return; }
-    std::fprintf(f, "{\n  \"zmws_input\": %" PRId64 ",\n  \"zmws_pass_filters\": %" PRId64 ",\n  \"zmws_fail_filters\": %" PRId64 ",\n  \"zmws_shortcut_filters\": 0,\n  \"exclusive_failed_counts\": {",
+    std::fprintf(f, "{\n  \"zmws_input\": %" PRId64 ",\n  \"zmws_pass_filters\": %" PRId64 ",\n  \"zmws_fail_filters\": %" PRId64 ",\n  \"zmws_shortcut_filters\": 0,\n",
                  r.input, r.pass, r.input - r.pass);
+    if (o.min_tandem > 0) std::fprintf(f, "  \"zmws_with_tandem_repeats\": %" PRId64 ",\n", r.tandem);
+    std::fprintf(f, "  \"exclusive_failed_counts\": {");
     bool first = true;
     for (const char *k : kFailOrder) {
         auto it = r.fail.find(k);
@@ -906,7 +922,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve(9 * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
                         b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
@@ -922,6 +938,10 @@ int main(int argc, char **argv)
                         if (opt.pileup) {
                             b->pile = take(3 * c1);
                             b->cp = ccsx_pileup{cap, b->pile, b->pile + cap, b->pile + 2 * cap};
+                        }
+                        if (opt.min_tandem > 0) {
+                            b->tlen = (int32_t *)take(n4);
+                            b->ex = ccsx_extras{opt.pileup ? &b->cp : nullptr, b->tlen, opt.min_tandem, 0};
                         }
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
@@ -983,7 +1003,8 @@ int main(int argc, char **argv)
                 if (inflight.size() >= 3) retire();
                 t0 = now();
                 ccsx_ticket t = -1;
-                if (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t)) {
+                if (opt.min_tandem > 0 ? ccsx_submit_extras(h, &b->cb, &b->cr, &b->ex, &t)
+                                       : (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t))) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1039,13 +1060,15 @@ int main(int argc, char **argv)
                     int st = z.host_status;
                     const int s = bt.slot[i];
                     if (st == HS_OK) st = bt.have_results ? bt.status[s] : -1;      // -1: EXCEPTION_THROWN / "Unknown error" (engine failure)
+                    const bool tandem = opt.min_tandem > 0 && s >= 0 && bt.have_results && bt.tlen[s] >= opt.min_tandem;
+                    rep.tandem += tandem ? 1 : 0;
                     if (want_metrics) {
                         const bool have = (s >= 0 && bt.have_results);
                         const int32_t isz = (have && bt.seq_len[s] > 0) ? bt.seq_len[s] : z.median_len;
                         char line[512];
-                        std::snprintf(line, sizeof(line), "%s    {\"effective_coverage\": %.2f, \"has_tandem_repeat\": false, \"insert_size\": %d, \"num_full_passes\": %d, "
+                        std::snprintf(line, sizeof(line), "%s    {\"effective_coverage\": %.2f, \"has_tandem_repeat\": %s, \"insert_size\": %d, \"num_full_passes\": %d, "
                                       "\"polymerase_length\": %" PRId64 ", \"predicted_accuracy\": %.6f, \"status\": \"%s\", \"zmw\": \"%s/%d%s\"}",
-                                      first_metric ? "" : ",\n", have ? bt.ec[s] : 0.0f, isz, have ? bt.np[s] : z.n_full, z.polymerase_len,
+                                      first_metric ? "" : ",\n", have ? bt.ec[s] : 0.0f, tandem ? "true" : "false", isz, have ? bt.np[s] : z.n_full, z.polymerase_len,
                                       (have && bt.seq_len[s] > 0) ? bt.rq[s] : -1.0f, status_name(st), movie.c_str(), z.zm,
                                       z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                         metrics += line; first_metric = false;
@@ -1161,8 +1184,9 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "ccs: GPU workers (sum over %zu): waiting for input %.2f s, packing (pack threads) %.2f s, submit + wait %.2f s\n", handles.size(),
                          us_wait.load() * 1e-6, us_pack.load() * 1e-6, us_engine.load() * 1e-6);
         if (opt.log_level >= 1)
-            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)\n", rep.input, rep.pass, el,
-                         rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s");
+            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s\n", rep.input, rep.pass, el,
+                         rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",
+                         opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "");
         if (failed) {
             if (!err_msg.empty()) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
             // no plausible-looking partial output after a failed run

@@ -109,6 +109,7 @@ struct Slot {
     DevBuf d_out_seq, d_out_qual, d_out_raw, d_out_i32 /* 6 x n */, d_out_f32 /* 2 x n */;
     DevBuf d_wtpl, d_wtmeta, d_wkin, d_out_kin;   // HiFi kinetics only (d_wtpl, d_wtmeta: also the pileup summary)
     DevBuf d_wpile, d_out_pile;                   // pileup summary only (ccsx_consensus_pileup / ccsx_submit_pileup)
+    DevBuf d_tflag, d_tlen;                       // tandem repeats only (ccsx_extras with tandem_len or a threshold)
     DevBuf d_din_len, d_din_bb;                   // caller-supplied drafts (ccsx_polish_batch): lengths, orientation references
     DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
@@ -132,7 +133,7 @@ struct Slot {
         DevBuf *bufs[] = {&d_snr, &d_read_off, &d_base_off, &d_bases, &d_pw, &d_ipd, &d_flags, &d_read_zmw, &d_vcap, &d_dcap, &d_seq_off,
                           &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
                           &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
-                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_din_len, &d_din_bb,
+                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_tflag, &d_tlen, &d_din_len, &d_din_bb,
                           &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites};
         for (auto *b : bufs) b->release();
         read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
@@ -365,7 +366,8 @@ static int validate(const ccsx_batch *b)
 // Stage a batch into a slot: host-derived layout, device buffers, H2D copies enqueued on `st` (nothing waits here except
 // hipMalloc growth).  The batch's own arrays must stay valid until the copies have run (pinned arrays copy by DMA).
 // pile: this run also computes the pileup summary (its buffers are reserved and its pointers set only then).
-static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bool pile = false)
+// tandem: it also runs tandem-repeat detection (k_sdust), flagging ZMWs at min_tandem > 0 (the same rule for its buffers and pointers).
+static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bool pile = false, bool tandem = false, int min_tandem = 0)
 {
     if (validate(b)) return -1;
     const bool kin = h->opts.hifi_kinetics != 0;
@@ -435,6 +437,18 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bo
     }
     const int64_t total_wslots = (int64_t)S.wb_off[n] - n;
     if (total_wslots > 0x7fff0000ll) { ccsx_set_error("ccsx_upload: batch too large (more than 2^31 window slots): split it"); return -1; }
+    int32_t sdust_words = 0;
+    if (tandem) {
+        // k_sdust's LDS mask covers the longest draft the cascade aligns: status SUCCESS needs length <= opts.max_length, and no draft exceeds its slot
+        int64_t longest = 16;
+        for (int z = 0; z < n; ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
+        longest = std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, 16));
+        sdust_words = (int32_t)((longest + 31) / 32);
+        if ((int64_t)CCSX_SDUST_TABLE_BYTES + 4 * (int64_t)sdust_words > 160 * 1024) {
+            ccsx_set_error("tandem-repeat detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than a CU has (lower opts.max_length)");
+            return -1;
+        }
+    }
 
 #define UP(buf, src, bytes)                                                                                    \
     do {                                                                                                       \
@@ -477,6 +491,7 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bo
     if (kin || pile) { RES(S.d_wtpl, (size_t)(total_wslots + 1) * 32); RES(S.d_wtmeta, (size_t)(total_wslots + 1) * 4); }
     if (kin) { RES(S.d_wkin, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_kin, (size_t)cap_total * 4); }
     if (pile) { RES(S.d_wpile, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_pile, (size_t)cap_total * 3); }
+    if (tandem) { RES(S.d_tflag, (size_t)n * 4); RES(S.d_tlen, (size_t)n * 4); }
 
     // ---- resident POA graphs / alignment slots: as many as fit this handle's share of the free memory, never more than
     // the work.  The scratch is shared by the handle's batch slots; it only grows, and growing waits for the compute stream.
@@ -572,6 +587,7 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bo
         P.out_kin = (uint8_t *)S.d_out_kin.p; P.kin_plane = cap_total;
     }
     if (pile) { P.wpile = (uchar4 *)S.d_wpile.p; P.out_pile = (uint8_t *)S.d_out_pile.p; P.pile_plane = cap_total; }
+    if (tandem) { P.tflag = (int32_t *)S.d_tflag.p; P.tlen = (int32_t *)S.d_tlen.p; P.min_tandem = min_tandem; P.sdust_words = sdust_words; }
     float *of = (float *)S.d_out_f32.p;
     P.out_rq = of; P.out_ec = of + n;
     S.staged = true; S.ran = false; S.tm_ok = false;
@@ -701,9 +717,22 @@ static int upload_drafts(Slot &S, const ccsx_drafts *d, hipStream_t st)
 }
 
 // one batch through the handle's pipeline: the fused path (ccsx_submit), the draft seam or the polish seam
-static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
-                       ccsx_pileup *pile = nullptr)
+// what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
+static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
+    *tandem = false;
+    if (!ex) return 0;
+    if (ex->min_tandem_repeat_length < 0 || ex->reserved != 0) { ccsx_set_error("ccsx_extras: min_tandem_repeat_length must be >= 0 and reserved 0"); return -1; }
+    *tandem = ex->tandem_len != nullptr || ex->min_tandem_repeat_length > 0;
+    return 0;
+}
+
+static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
+                       const ccsx_extras *ex = nullptr)
+{
+    bool tandem = false;
+    if (extras_want(ex, &tandem)) return -1;
+    ccsx_pileup *pile = ex ? ex->pile : nullptr;
     if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) { ccsx_set_error("ccsx_submit: null argument"); return -1; }
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
     if (const char *e = std::getenv("CCSX_TEST_FAIL_SUBMIT"))        // fault injection for the driver's error-path test
@@ -723,7 +752,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         h->poisoned = true;
         return rc_;
     };
-    int rc = stage(h, S, b, h->s_in, pile != nullptr);
+    int rc = stage(h, S, b, h->s_in, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0);
     if (rc) return rc == -1 ? (S.staged = false, rc) : fail(rc);     // -1: rejected by validation before anything was enqueued
     if (mode != CCSX_RUN_DRAFT && (rc = check_results(S, res, S.P.out_kin != nullptr))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     if (pile && (rc = check_pile(S, pile))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
@@ -748,6 +777,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         if (dr_out->win_bounds) HIPTRY_F(hipMemcpyAsync(dr_out->win_bounds, P.wbounds, (size_t)S.wb_off[n] * 4, hipMemcpyDeviceToHost, h->s_out));
     } else if ((rc = enqueue_download(S, res, h->s_out))) return fail(rc);
     if (pile && (rc = enqueue_pile_download(S, pile, h->s_out))) return fail(rc);
+    if (tandem && ex->tandem_len) HIPTRY_F(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_out));
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -763,7 +793,12 @@ int ccsx_submit(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_tick
 int ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile, ccsx_ticket *ticket)
 {
     if (!pile) { ccsx_set_error("ccsx_submit_pileup: null argument"); return -1; }
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, pile);
+    const ccsx_extras ex = {pile, nullptr, 0, 0};
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, &ex);
+}
+int ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket)
+{
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
 {
@@ -822,14 +857,14 @@ int ccsx_ticket_timings(ccsx_handle h, ccsx_ticket ticket, ccsx_timings *t)
 }
 
 // ---- synchronous form (slot 0): parity tests, stage read-backs, the resident-input leg of the benchmark ----
-static int upload_impl(ccsx_handle h, const ccsx_batch *b, bool pile)
+static int upload_impl(ccsx_handle h, const ccsx_batch *b, bool pile, bool tandem = false, int min_tandem = 0)
 {
     if (!h) { ccsx_set_error("ccsx_upload: null handle"); return -1; }
     HIPTRY(hipSetDevice(h->device));
     for (auto &S : h->slot) if (int rc = retire(h, S)) return rc;
     Slot &S = h->slot[0];
     S.ticket = -1;                                       // (slot 0 is re-staged: its ticket is recycled, as by a submit; the other slots' tickets stay valid)
-    const int rc = stage(h, S, b, h->s_comp, pile);
+    const int rc = stage(h, S, b, h->s_comp, pile, tandem, min_tandem);
     if (rc) { S.staged = false; return rc; }
     S.mode = CCSX_RUN_FUSED;
     HIPTRY(hipStreamSynchronize(h->s_comp));
@@ -911,6 +946,25 @@ int ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res,
     if ((rc = check_pile(S, pile))) return rc;
     if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
     if ((rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+int ccsx_tandem_rule_version(void) { return 1; }
+
+int ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex)
+{
+    if (!h || !b || !res) { ccsx_set_error("ccsx_consensus_extras: null argument"); return -1; }
+    bool tandem = false;
+    if (extras_want(ex, &tandem)) return -1;
+    ccsx_pileup *pile = ex ? ex->pile : nullptr;
+    int rc;
+    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
+    Slot &S = h->slot[0];
+    if (pile && (rc = check_pile(S, pile))) return rc;
+    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
+    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
 }

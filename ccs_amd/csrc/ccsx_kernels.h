@@ -113,7 +113,17 @@ struct KParams {
     uchar4 *wpile;             // [wslots][32] (coverage, matches, mismatches, 0) of the core positions
     uint8_t *out_pile;         // 3 planes (coverage, matches, mismatches) of seq_off[n] bytes each
     long long pile_plane;      // plane stride = seq_off[n]
+    // ---- tandem repeats (ccsx_consensus_extras / ccsx_submit_extras with tandem_len or min_tandem_repeat_length; NULL otherwise): DESIGN.md §2 "Tandem repeats"
+    int32_t *tflag;            // [n] 0 = undecided; bit 0 = decided on the ZMW's deciding draft, bit 1 = flagged (its heuristics are off, as with opts.disable_heuristics)
+    int32_t *tlen;             // [n] longest run of sDUST-masked draft positions of the deciding draft (0: none decided)
+    int32_t min_tandem;        // flag threshold (<= 0: detect and report only)
+    int32_t sdust_words;       // k_sdust's LDS mask: 32-bit words, enough for the longest draft that is aligned
 };
+
+// k_sdust (DESIGN.md §2 "Tandem repeats"): window W bases, threshold T in tenths, dynamic LDS = two [64][64] word tables + two byte tables + the mask
+#define CCSX_SDUST_W 64
+#define CCSX_SDUST_T 20
+#define CCSX_SDUST_TABLE_BYTES (2 * 64 * 64 * 4 + 2 * 64 * 64)
 
 #define CCSX_HD_LF_N (2 * CCSX_MAX_PASSES + 1)   // log-factorials 0 .. 510: a Fisher table never holds more passes than that
 #define CCSX_HD_IMAX 49                          // rows of a segment the pileup aligns: template columns (<= 29) + min_indel - 1 (<= 20)

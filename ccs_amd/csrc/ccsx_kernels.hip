@@ -1463,7 +1463,7 @@ __global__ __launch_bounds__(64) void k_align16(KParams P, int qbase, int pass, 
     const int nused = rfl(P.nreads_used[z]);
     if (rfirst - r0 >= nused) return;
     const bool use = live && (r - r0 < nused);
-    if (P.opts.disable_heuristics) {                    // SPEC v5: --disable-heuristics aligns every pass with the 64-row band at once
+    if (P.opts.disable_heuristics || (P.tflag && (rfl(P.tflag[z]) & 2))) {   // SPEC v5: --disable-heuristics (or a tandem repeat: DESIGN.md §2) aligns every pass with the 64-row band at once
         if (l == 0 && use) { const int idx = atomicAdd(&P.align_retry[0], 1); P.align_retry[16 + idx] = r; }
         return;
     }
@@ -2483,7 +2483,8 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
             const unsigned neg = (unsigned)__ballot(inw && margin < 0);
             // positions within SKIP_SPREAD of a dirty majority are polished too
             const unsigned nearneg = neg | (neg << 1) | (neg << 2) | (neg << 3) | (neg >> 1) | (neg >> 2) | (neg >> 3);
-            const bool ok = inw && !P.opts.disable_heuristics && margin >= SKIP_MARGIN && !((nearneg >> lane) & 1u);
+            const bool noheur = P.opts.disable_heuristics || (P.tflag && (P.tflag[z] & 2));   // (a flagged tandem repeat: DESIGN.md §2)
+            const bool ok = inw && !noheur && margin >= SKIP_MARGIN && !((nearneg >> lane) & 1u);
             const unsigned ev = (unsigned)__ballot(ok);
             if (lane == 0) sCtl[7] = (int)ev;
             if (lane < 36) sPskip[lane] = inw ? skip_perr(margin, P.perr_floor) : 0.0f;
@@ -3858,6 +3859,115 @@ int ccsx_polish_lds(int max_reads, int *obs_bytes, int *gb_floats)
     return 0;
 }
 
+// ---- k_sdust: tandem-repeat detection on a ZMW's deciding draft (DESIGN.md §2 "Tandem repeats").  One wave per ZMW, longest first.
+// Symmetric DUST over triplets: for every end triplet e the suffixes [i, e] inside a window (e - i <= W - 3) are scored in order of growing length.
+// [i, e] is a perfect interval when its score S / k (S = pairs of equal triplets, k = triplets - 1) exceeds T / 10 and is at least the score of every
+// perfect interval inside it: the best perfect interval of every start with an earlier end (sBest) and the perfect suffixes of e found so far.  Lane l owns
+// a contiguous range of ends and first replays the W - 3 ends before it without output, starting no interval before its warm-up's first triplet: whether
+// an interval is perfect depends only on the intervals inside it, so the split is exact.  The masked bases of each end's perfect suffixes ([i_min, e + 2])
+// merge into runs that are ORed into an LDS bit mask; a scan of the mask finds the longest run.  Exact gate: a suffix has at most the pairs S_w of the whole
+// window [ilo, e], and a perfect one needs S > 2k, so only k < S_w / 2 is scored (about 14 of 61 suffixes on random sequence).  Per lane, in [slot][lane]
+// LDS cells (no bank conflicts): the ring of the last 64 triplets (bytes), the window's triplet counts (bytes), the counts of the current end's suffix (words
+// tagged with e, so nothing is cleared) and the best perfect interval per start (S << 8 | k, 0 = none).  tests/sdust_ref.py restates this operation for operation.
+__global__ __launch_bounds__(64) void k_sdust(KParams P, int pass)
+{
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= P.n_zmw) return;
+    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    if (rfl(P.tflag[z])) return;                                    // decided on an earlier draft of this ticket
+    if (pass && !(rfl(P.zref[z]) & ZREF_PASSBIT(pass))) return;     // later passes: only the ZMWs whose draft was redone
+    if (rfl(P.zstat[z]) != CCSX_SUCCESS) return;                    // no draft that the cascade aligns in this pass
+    uint32_t *sCnt = dyn_lds, *sBest = dyn_lds + 64 * 64, *sMask = dyn_lds + CCSX_SDUST_TABLE_BYTES / 4;
+    uint8_t *sTri = (uint8_t *)(dyn_lds + 2 * 64 * 64), *sWin = sTri + 64 * 64;
+    int Ld = rfl(P.draft_len[z]);
+    if (Ld > 32 * P.sdust_words) Ld = 0;                            // (bounds guard: the mask covers opts.max_length, the longest draft with status SUCCESS)
+    const int nwd = (Ld + 31) >> 5;
+    for (int w = lane; w < nwd; w += LANES) sMask[w] = 0;
+    __syncthreads();
+    const uint8_t *d = P.draft + P.seq_off[z];
+    const int nt = Ld - 2;                                          // triplets 0 .. nt - 1; ends 1 .. nt - 1
+    const int ch = nt >= 2 ? (nt - 1 + LANES - 1) / LANES : 0;
+    const int e0 = 1 + lane * ch, e1 = min(e0 + ch, nt);
+    if (e0 < e1) {
+        const int lo = e0 - (CCSX_SDUST_W - 3) > 0 ? e0 - (CCSX_SDUST_W - 3) : 0;   // the warm-up's first triplet
+        for (int q = 0; q < 64; ++q) { sCnt[q * 64 + lane] = 0xffffffffu; sBest[q * 64 + lane] = 0u; sWin[q * 64 + lane] = 0; }
+        int t = ((d[lo] & 3) << 4) | ((d[lo + 1] & 3) << 2) | (d[lo + 2] & 3);
+        sTri[(lo & 63) * 64 + lane] = (uint8_t)t;
+        sWin[t * 64 + lane] = 1;
+        uint32_t Sw = 0;                                            // pairs of equal triplets in the window [ilo, e]
+        int rs = -1, re = -2;                                       // the run of masked bases being merged
+        auto flush = [&](int a, int b) {                            // OR bases [a, b] into the mask
+            if (a < 0) return;
+            for (int w = a >> 5; w <= (b >> 5); ++w) {
+                const int lb = a - 32 * w > 0 ? a - 32 * w : 0, hb = b - 32 * w < 31 ? b - 32 * w : 31;
+                atomicOr(&sMask[w], (0xffffffffu >> (31 - hb)) & (0xffffffffu << lb));
+            }
+        };
+        for (int e = lo + 1; e < e1; ++e) {
+            t = ((t << 2) | (d[e + 2] & 3)) & 63;
+            if (e - (CCSX_SDUST_W - 2) >= lo) {                     // triplet e - 62 leaves the window
+                const int to = sTri[((e - (CCSX_SDUST_W - 2)) & 63) * 64 + lane];
+                const uint32_t co = sWin[to * 64 + lane] - 1u;
+                sWin[to * 64 + lane] = (uint8_t)co;
+                Sw -= co;
+            }
+            {
+                const uint32_t cn = sWin[t * 64 + lane];
+                sWin[t * 64 + lane] = (uint8_t)(cn + 1u);
+                Sw += cn;
+            }
+            sTri[(e & 63) * 64 + lane] = (uint8_t)t;
+            sBest[(e & 63) * 64 + lane] = 0u;                       // (the slot of start e - 64: out of every window from here on)
+            const uint32_t tag = (uint32_t)e << 8;
+            sCnt[t * 64 + lane] = tag | 1u;
+            int ilo = e - (CCSX_SDUST_W - 3) > lo ? e - (CCSX_SDUST_W - 3) : lo;
+            const int kmax = Sw > 0 ? (int)((Sw - 1u) >> 1) : 0;    // (the gate: longer suffixes cannot score above 2)
+            ilo = e - kmax > ilo ? e - kmax : ilo;
+            uint32_t S = 0, M = 0;
+            int imn = -1;
+            for (int i = e - 1; i >= ilo; --i) {
+                const uint32_t k = (uint32_t)(e - i);
+                const uint32_t ti = sTri[(i & 63) * 64 + lane];
+                const uint32_t w = sCnt[ti * 64 + lane];
+                const uint32_t c = (w & ~255u) == tag ? (w & 255u) : 0u;
+                S += c;
+                sCnt[ti * 64 + lane] = tag | (c + 1u);
+                const uint32_t b = sBest[(i & 63) * 64 + lane];
+                if (b && (!M || (b >> 8) * (M & 255u) > (M >> 8) * (b & 255u))) M = b;
+                if (S * 10u > (uint32_t)CCSX_SDUST_T * k && (!M || S * (M & 255u) >= (M >> 8) * k)) {
+                    M = (S << 8) | k;
+                    sBest[(i & 63) * 64 + lane] = M;
+                    imn = i;
+                }
+            }
+            if (e >= e0 && imn >= 0) {
+                if (rs >= 0 && imn <= re + 1) { rs = imn < rs ? imn : rs; re = e + 2; }
+                else { flush(rs, re); rs = imn; re = e + 2; }
+            }
+        }
+        flush(rs, re);
+    }
+    __syncthreads();
+    // the longest run: every lane summarises a contiguous range of bases, lane 0's loop joins the ranges in order
+    const int cb = (Ld + LANES - 1) / LANES;
+    const int p0 = min(lane * cb, Ld), p1 = min(p0 + cb, Ld);
+    int pre = 0, cur = 0, inner = 0, full = 1;
+    for (int p = p0; p < p1; ++p) {
+        if ((sMask[p >> 5] >> (p & 31)) & 1u) ++cur;
+        else { if (full) { pre = cur; full = 0; } inner = cur > inner ? cur : inner; cur = 0; }
+    }
+    if (full) pre = cur;
+    inner = cur > inner ? cur : inner;
+    int best = 0, run = 0;
+    for (int j = 0; j < LANES; ++j) {
+        const int pj = rl(pre, j);
+        if (rl(full, j)) run += pj;
+        else { best = imax(best, imax(run + pj, rl(inner, j))); run = rl(cur, j); }
+    }
+    best = imax(best, run);
+    if (lane == 0) { P.tlen[z] = best; P.tflag[z] = 1 | ((P.min_tandem > 0 && best >= P.min_tandem) ? 2 : 0); }
+}
+
 // every launch status is captured: returns NULL, or the name of the first launch that failed (ccsx_api.cpp reports it)
 #define LAUNCH_CHECK(name) do { if (hipGetLastError() != hipSuccess && !failed) failed = name; } while (0)
 #define CALL_CHECK(fn, ...) do { if (fn(__VA_ARGS__) != hipSuccess && !failed) failed = #fn; } while (0)   // (a stream / event call)
@@ -3872,6 +3982,7 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     if (ev) CALL_CHECK(hipEventRecord, ev[0], st);
     CALL_CHECK(hipMemsetAsync, P.ticket_poa, 0, 256, st);   // debug / phase-profile words (CCSX_DEBUG_CHECKS, CCSX_PROFILE_PHASES builds)
     CALL_CHECK(hipMemsetAsync, P.avalid, 0, (size_t)(P.n_reads > 0 ? P.n_reads : 1), st);   // passes beyond top_passes are never visited by a kernel
+    if (P.tflag) { CALL_CHECK(hipMemsetAsync, P.tflag, 0, (size_t)P.n_zmw * 4, st); CALL_CHECK(hipMemsetAsync, P.tlen, 0, (size_t)P.n_zmw * 4, st); }   // all undecided
     {
         int n = P.n_zmw * CCSX_NCTX;
         hipLaunchKernelGGL(k_setup, dim3((n + 255) / 256), dim3(256), 0, st, P);
@@ -3925,6 +4036,10 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
             } else poa_range(st, 0, nb, nullptr, nullptr);
         }
         trace_sync(st, "k_poa");
+        if (P.tflag) {                                      // tandem repeats: the ZMWs whose deciding draft this pass makes
+            hipLaunchKernelGGL(k_sdust, dim3(P.n_zmw), dim3(64), (size_t)CCSX_SDUST_TABLE_BYTES + (size_t)P.sdust_words * 4, st, P, pass);
+            LAUNCH_CHECK("k_sdust");
+        }
         if (ev && pass == 0) CALL_CHECK(hipEventRecord, ev[2], st);
         // alignment cascade: four passes per wave in 16-row bands, then the 64-row retry of the few that failed there
         CALL_CHECK(hipMemsetAsync, P.align_retry, 0, 64, st);

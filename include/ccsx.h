@@ -337,6 +337,28 @@ int         ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results 
 int         ccsx_stage_polished(ccsx_handle h, int32_t zmw_index, uint8_t *tpl, int32_t *meta, int32_t cap, int32_t *n_windows,
                                 int32_t *passes_used, int32_t *backbone);
 
+/* ---- optional outputs of the fused path beside the results: ccsx_extras (the structs above stay their pinned sizes; new outputs join this one).
+ *   pile                      the pileup summary planes (as ccsx_submit_pileup), or NULL.
+ *   tandem_len                [n_zmw] or NULL: per ZMW the longest run of sDUST-masked bases of its deciding draft (DESIGN.md §2 "Tandem repeats", rule
+ *                             version ccsx_tandem_rule_version): symmetric DUST, W = 64, T = 20 (score > 2.0), on the first draft the alignment cascade
+ *                             aligns passes to in this call (pass-0 POA draft, else the fallback or last-resort draft); 0 without such a draft.
+ *   min_tandem_repeat_length  > 0: a ZMW with tandem_len >= this value runs with opts.disable_heuristics for itself only (--min-tandem-repeat-length of
+ *                             docs/faq/low-complexity.md:8-18).  0: detection only (when tandem_len is given), no result changes.  < 0 is an error.
+ *   reserved                  must be 0.
+ * Detection runs when tandem_len is given or the threshold is > 0.  With a NULL ccsx_extras, or NULL pile and tandem_len and a threshold of 0, nothing new is
+ * launched, reserved or copied: the call is ccsx_consensus_batch / ccsx_submit.  ccsx_submit_extras is ticketed like ccsx_submit: the arrays behind `pile`
+ * and tandem_len follow the lifetime rule of `res` (they are written by the ticket's download) and should be page-locked; the ccsx_extras struct itself is
+ * read during the call only.  ccsx_consensus_extras is the synchronous form (slot 0).  The draft and polish seams and ccsx_hd_batch take no extras.   */
+typedef struct ccsx_extras {
+    ccsx_pileup *pile;
+    int32_t     *tandem_len;
+    int32_t      min_tandem_repeat_length;
+    int32_t      reserved;
+} ccsx_extras;
+int         ccsx_tandem_rule_version(void);
+int         ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex);
+int         ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
