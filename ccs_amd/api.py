@@ -23,8 +23,9 @@ BAND, MAXPRED, WIN_CORE, WIN_OVERHANG, JMAX, IMAX, MAX_ITER, NCTX, NOBS = 64, 7,
 
 STATUS_NAMES = {
     0: "SUCCESS", 1: "TOO_FEW_PASSES", 2: "DRAFT_FAILURE", 3: "TOO_MANY_UNUSABLE", 4: "NON_CONVERGENT",
-    5: "TOO_SHORT", 6: "TOO_LONG", 7: "LOW_RQ", 8: "EMPTY_WINDOW", 9: "CAPACITY",
+    5: "TOO_SHORT", 6: "TOO_LONG", 7: "LOW_RQ", 8: "EMPTY_WINDOW", 9: "CAPACITY", 10: "HETERODUPLEX",
 }
+HETERODUPLEX = 10   # CCSX_HETERODUPLEX: a ZMW the heteroduplex split kept out of the polish stage (ccsx_hd_request.split)
 
 
 class Model(C.Structure):
@@ -106,6 +107,11 @@ class CHdReport(C.Structure):
                 ("sites", C.POINTER(HdSite)), ("status", C.POINTER(C.c_int32))]
 
 
+class CHdRequest(C.Structure):
+    """ccsx_hd_request: the heteroduplex finder in the fused path (ccsx_consensus_hd / ccsx_submit_hd)"""
+    _fields_ = [("opts", C.POINTER(HdOpts)), ("report", C.POINTER(CHdReport)), ("split", C.c_int32), ("reserved", C.c_int32)]
+
+
 def hd_opts_default() -> HdOpts:
     o = HdOpts()
     lib().ccsx_hd_opts_default(C.byref(o))
@@ -124,9 +130,22 @@ class HdReport:
     status: np.ndarray
 
     @staticmethod
-    def allocate(n: int) -> "HdReport":
-        z = lambda: np.zeros(n, np.int32)
-        return HdReport(z(), z(), z(), z(), np.ones(n), np.zeros((n, HD_MAX_SITES), HD_SITE_DTYPE), z())
+    def allocate(n: int, pinned: bool = False) -> "HdReport":
+        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(hd=...), downloads into them asynchronously)"""
+        if not pinned:
+            z = lambda: np.zeros(n, np.int32)
+            return HdReport(z(), z(), z(), z(), np.ones(n), np.zeros((n, HD_MAX_SITES), HD_SITE_DTYPE), z())
+        keep = []
+
+        def z(count, dt):
+            a = _pinned_array(count, dt, keep)
+            a[...] = 0
+            return a
+        rep = HdReport(z(n, np.int32), z(n, np.int32), z(n, np.int32), z(n, np.int32), z(n, np.float64),
+                       z(n * HD_MAX_SITES, HD_SITE_DTYPE).reshape(n, HD_MAX_SITES), z(n, np.int32))
+        rep.min_p[...] = 1.0
+        rep._pinned = keep
+        return rep
 
     def c_struct(self) -> CHdReport:
         r = CHdReport()
@@ -238,6 +257,17 @@ def tandem_buffer(n_zmw: int, pinned: bool = False) -> np.ndarray:
 _PINNED_OWNERS: dict = {}
 
 
+def _pinned_array(count: int, dt, keep: list) -> np.ndarray:
+    """count elements of dt in one ccsx_alloc_pinned block, owned by an entry appended to keep"""
+    dt = np.dtype(dt)
+    nb = max(1, int(count) * dt.itemsize)
+    p = lib().ccsx_alloc_pinned(nb)
+    if not p:
+        raise RuntimeError("ccsx_alloc_pinned failed: " + lib().ccsx_last_error().decode())
+    keep.append(_Pinned(p))
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nb,))[: int(count) * dt.itemsize].view(dt)
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("setup_ms", C.c_float), ("draft_ms", C.c_float), ("align_ms", C.c_float), ("polish_ms", C.c_float),
@@ -262,6 +292,7 @@ EXPORTS = [
     "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
     "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished",
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
+    "ccsx_consensus_hd", "ccsx_submit_hd",
 ]
 
 _lib = None
@@ -322,6 +353,8 @@ def lib() -> C.CDLL:
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.ccsx_consensus_extras.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras)]
         L.ccsx_submit_extras.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(C.c_int64)]
+        L.ccsx_consensus_hd.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CHdRequest)]
+        L.ccsx_submit_hd.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CHdRequest), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -731,6 +764,23 @@ class Handle:
         self._check(self._L.ccsx_consensus_extras(self._h, C.byref(cb), C.byref(cr), C.byref(ex)), "ccsx_consensus_extras")
         return res, tl, pile
 
+    # ---- the heteroduplex finder in the fused path (ccsx_consensus_hd): the consensus and the finder's report of one run
+    def consensus_hd(self, batch: Batch, opts: HdOpts | None = None, split: bool = False, tandem: bool = False, min_tandem_repeat_length: int = 0,
+                     pileup: bool = False) -> tuple["Results", HdReport, "np.ndarray | None", "Pileup | None"]:
+        """(results, report, tandem_len or None, pileup or None).  split=True: a HETERODUPLEX ZMW is not polished (status HETERODUPLEX, no consensus);
+        split=False: detection only, the results are those of consensus_extras"""
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = HdReport.allocate(batch.n_zmw)
+        tl = tandem_buffer(batch.n_zmw) if tandem else None
+        pile = Pileup.allocate(res) if pileup else None
+        cb, cr, crep = batch.c_struct(), res.c_struct(), rep.c_struct()
+        cp = pile.c_struct() if pile is not None else None
+        ex = _extras(cp, tl, min_tandem_repeat_length) if (tandem or pileup or min_tandem_repeat_length) else None
+        o = opts if opts is not None else hd_opts_default()
+        q = CHdRequest(C.pointer(o), C.pointer(crep), int(bool(split)), 0)
+        self._check(self._L.ccsx_consensus_hd(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q)), "ccsx_consensus_hd")
+        return res, rep, tl, pile
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -765,15 +815,26 @@ class Handle:
 
     # ---- asynchronous pipeline (ccsx_submit / ccsx_wait): up to three batches in flight, copies under compute
     def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None,
-               min_tandem_repeat_length: int = 0) -> int:
+               min_tandem_repeat_length: int = 0, hd: "HdReport | None" = None, hd_opts: HdOpts | None = None, hd_split: bool = False) -> int:
         """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer,
-        pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras)"""
+        pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras).  hd: a report
+        (HdReport.allocate(n, pinned=True)) that receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish
+        stage (ccsx_submit_hd)"""
         cb, cr = batch.c_struct(), res.c_struct()
         t = C.c_int64()
         ex = None
-        if tandem is not None or min_tandem_repeat_length:
-            if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
-                raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
+        if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
+            raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
+        if hd is not None:
+            cp = pileup.c_struct() if pileup is not None else None
+            ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
+            o = hd_opts if hd_opts is not None else hd_opts_default()
+            crep = hd.c_struct()
+            q = CHdRequest(C.pointer(o), C.pointer(crep), int(bool(hd_split)), 0)
+            self._check(self._L.ccsx_submit_hd(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q), C.byref(t)),
+                        "ccsx_submit_hd")
+            ex = (ex, o, crep, q, hd)
+        elif tandem is not None or min_tandem_repeat_length:
             cp = pileup.c_struct() if pileup is not None else None
             ex = _extras(cp, tandem, min_tandem_repeat_length)
             self._check(self._L.ccsx_submit_extras(self._h, C.byref(cb), C.byref(cr), C.byref(ex), C.byref(t)), "ccsx_submit_extras")
@@ -904,3 +965,63 @@ def consensus_hd(handle: "Handle", batch: Batch, opts: HdOpts | None = None):
             r, i = got
             recs.append(HdRecord(z, int(batch.zmw_id[z]), group, int(r.status[i]), r.sequence(i).copy(), r.quals(i).copy(), float(r.rq[i]), int(r.np_[i])))
     return recs, rep
+
+
+def consensus_hd_stream(handle: "Handle", batches, opts: HdOpts | None = None):
+    """the heteroduplex mode, pipelined: every batch goes through ONE ticket with the finder and the split (ccsx_submit_hd, split = 1), and when that ticket
+    is retired its HETERODUPLEX ZMWs become a single-strand batch (split_strands) for an ordinary ticket.  At most three tickets are in flight (the handle's
+    slots); yields (records, report) per input batch, in input order, with exactly the records consensus_hd gives."""
+    from collections import deque
+    inflight = deque()                 # (ticket, input index, kind): retired oldest first, so the in-flight tickets are always the latest submitted
+    state, done, nxt = {}, {}, 0
+
+    def finish(i, sres=None, src=None, strand=None):
+        b, res, rep = state[i]["batch"], state[i]["res"], state[i]["rep"]
+        het = rep.verdict == HD_HETERODUPLEX
+        strands = {}
+        if sres is not None:
+            for k in range(len(src)):
+                strands[(int(src[k]), int(strand[k]))] = (sres, k)
+        recs = []
+        for z in range(b.n_zmw):
+            parts = [("fwd", strands.get((z, 0))), ("rev", strands.get((z, 1)))] if het[z] else [("DS", (res, z))]
+            for group, got in parts:
+                if got is None:
+                    continue
+                r, k = got
+                recs.append(HdRecord(z, int(b.zmw_id[z]), group, int(r.status[k]), r.sequence(k).copy(), r.quals(k).copy(), float(r.rq[k]), int(r.np_[k])))
+        done[i] = (recs, rep)
+        del state[i]
+
+    def retire_oldest():
+        t, i, kind = inflight.popleft()
+        handle.wait(t)
+        handle.release(t)
+        if kind == "strand":
+            st = state[i]
+            finish(i, st["sres"], st["src"], st["strand"])
+            return
+        het = state[i]["rep"].verdict == HD_HETERODUPLEX
+        if not het.any():
+            finish(i)
+            return
+        sb, src, strand = split_strands(state[i]["batch"], het)
+        sres = Results.allocate(sb, kinetics=bool(handle.opts.hifi_kinetics), pinned=True)
+        state[i].update(sres=sres, src=src, strand=strand)
+        inflight.append((handle.submit(sb, sres), i, "strand"))      # (one ticket was just retired: at most three in flight)
+
+    for i, b in enumerate(batches):
+        while len(inflight) >= 3:
+            retire_oldest()
+        res = Results.allocate(b, kinetics=bool(handle.opts.hifi_kinetics), pinned=True)
+        rep = HdReport.allocate(b.n_zmw, pinned=True)
+        state[i] = dict(batch=b, res=res, rep=rep)
+        inflight.append((handle.submit(b, res, hd=rep, hd_opts=opts, hd_split=True), i, "hd"))
+        while nxt in done:
+            yield done.pop(nxt)
+            nxt += 1
+    while inflight:
+        retire_oldest()
+        while nxt in done:
+            yield done.pop(nxt)
+            nxt += 1

@@ -716,6 +716,79 @@ static int upload_drafts(Slot &S, const ccsx_drafts *d, hipStream_t st)
     return 0;
 }
 
+// ---- the heteroduplex finder's host side, shared by ccsx_hd_batch (slot 0, caller drafts) and the fused path (ccsx_hd_request)
+static int hd_opts_check(const ccsx_hd_opts *o, ccsx_hd_opts *hd, const char *fn)
+{
+    if (o) *hd = *o; else ccsx_hd_opts_default(hd);
+    if (hd->min_strand_passes < 1 || hd->min_sites < 1 || hd->min_indel < 1 || hd->min_indel > 21 || !(hd->min_alt_frac >= 0.0f && hd->min_alt_frac <= 1.0f) ||
+        !(hd->max_pvalue >= 0.0 && hd->max_pvalue <= 1.0)) {
+        ccsx_set_error(std::string(fn) + ": options out of range (min_strand_passes, min_sites >= 1; 1 <= min_indel <= 21; min_alt_frac, max_pvalue in [0, 1])"); return -1;
+    }
+    return 0;
+}
+
+static int hd_report_check(const ccsx_hd_report *out, int n_zmw, const char *fn)
+{
+    if (out->n_zmw != n_zmw || !out->verdict || !out->n_sub_sites || !out->n_indel_sites || !out->n_listed || !out->min_p || !out->sites) {
+        ccsx_set_error(std::string(fn) + ": report arrays missing, or sized for another batch"); return -1;
+    }
+    return 0;
+}
+
+static int hd_request_check(const ccsx_hd_request *q, const ccsx_batch *b, ccsx_hd_opts *hd, const char *fn)
+{
+    if (!q || !q->report) { ccsx_set_error(std::string(fn) + ": null request or report"); return -1; }
+    if (q->reserved != 0 || (q->split != 0 && q->split != 1)) { ccsx_set_error(std::string(fn) + ": split must be 0 or 1 and reserved 0"); return -1; }
+    if (hd_opts_check(q->opts, hd, fn)) return -1;
+    return hd_report_check(q->report, b->n_zmw, fn);
+}
+
+// log k!, a sequential sum of log(k) in double (the rule's table), built once per handle by a synchronous copy BEFORE the first kernel that reads it is
+// enqueued: no in-flight work reads it while it is written, and it is never written again
+static int hd_table(ccsx_handle h)
+{
+    if (h->d_hd_lf.p) return 0;
+    std::vector<double> lf(CCSX_HD_LF_N, 0.0);
+    for (int q = 1; q < CCSX_HD_LF_N; ++q) lf[q] = lf[q - 1] + std::log((double)q);
+    if (h->d_hd_lf.reserve(lf.size() * 8)) return -2;
+    HIPTRY(hipMemcpy(h->d_hd_lf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the finder's buffers of a staged slot (about 200 bytes per window slot: the per-window site records dominate), its options and pointers; the sites
+// list is cleared on `st` (entries beyond n_listed stay zero).  stage() clears KParams, so a later run of the slot without a request has none of it.
+static int hd_attach(ccsx_handle h, Slot &S, const ccsx_hd_opts &hd, int split, hipStream_t st)
+{
+    const int n = S.P.n_zmw;
+    const size_t wins = (size_t)S.P.total_wslots + 1;
+    if (S.d_hd_wcnt.reserve(wins * 4) ||
+        S.d_hd_wrec.reserve(wins * CCSX_HD_WIN_SITES * sizeof(ccsx_hd_site)) || S.d_hd_wminp.reserve(wins * 8) ||
+        S.d_hd_isite.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site)) || S.d_hd_zi.reserve((size_t)n * 6 * 4) ||
+        S.d_hd_minp.reserve((size_t)n * 8) || S.d_hd_sites.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site))) return -2;
+    HIPTRY(hipMemsetAsync(S.d_hd_sites.p, 0, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site), st));
+    KParams &P = S.P;
+    P.hd = hd; P.hd_split = split; P.hd_lf = (const double *)h->d_hd_lf.p;
+    P.hd_wcnt = (int32_t *)S.d_hd_wcnt.p; P.hd_wrec = (ccsx_hd_site *)S.d_hd_wrec.p; P.hd_wminp = (double *)S.d_hd_wminp.p;
+    P.hd_isite = (ccsx_hd_site *)S.d_hd_isite.p; P.hd_zi = (int32_t *)S.d_hd_zi.p; P.hd_minp = (double *)S.d_hd_minp.p;
+    P.hd_sites = (ccsx_hd_site *)S.d_hd_sites.p;
+    return 0;
+}
+
+// the report of a fused run (status: the one after the cascade, which k_hd_verdict keeps before a split)
+static int enqueue_hd_download(const Slot &S, ccsx_hd_report *out, hipStream_t s)
+{
+    const int n = S.P.n_zmw;
+    const KParams &P = S.P;
+    HIPTRY(hipMemcpyAsync(out->verdict, P.hd_zi, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(out->n_sub_sites, P.hd_zi + n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(out->n_indel_sites, P.hd_zi + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(out->n_listed, P.hd_zi + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(out->min_p, P.hd_minp, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(out->sites, P.hd_sites, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site), hipMemcpyDeviceToHost, s));
+    if (out->status) HIPTRY(hipMemcpyAsync(out->status, P.hd_zi + 5 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // one batch through the handle's pipeline: the fused path (ccsx_submit), the draft seam or the polish seam
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
@@ -728,11 +801,13 @@ static int extras_want(const ccsx_extras *ex, bool *tandem)
 }
 
 static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
-                       const ccsx_extras *ex = nullptr)
+                       const ccsx_extras *ex = nullptr, const ccsx_hd_request *hdq = nullptr)
 {
     bool tandem = false;
     if (extras_want(ex, &tandem)) return -1;
     ccsx_pileup *pile = ex ? ex->pile : nullptr;
+    ccsx_hd_opts hdo{};
+    if (hdq && b && hd_request_check(hdq, b, &hdo, "ccsx_submit_hd")) return -1;   // (the request is checked with or without a handle)
     if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) { ccsx_set_error("ccsx_submit: null argument"); return -1; }
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
     if (const char *e = std::getenv("CCSX_TEST_FAIL_SUBMIT"))        // fault injection for the driver's error-path test
@@ -743,6 +818,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     if (int rc0 = rebase_epoch(h)) return rc0;
     Slot &S = h->slot[h->next_ticket % CCSX_SLOTS];
     if (int rc0 = retire(h, S)) return rc0;              // (a batch never waited for: the caller's buffers are complete whether or not it ever waits)
+    if (hdq) if (int rc0 = hd_table(h)) return rc0;      // (before anything of this ticket is enqueued)
     // A failure after the first enqueue must not leave copies or kernels running on a slot the next submit would rewrite
     // (ADVICE r02): drain every stream, mark the slot unusable and refuse further batches on this handle.
     auto fail = [&](int rc_) {
@@ -761,6 +837,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
 #define HIPTRY_F(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(-2); } } while (0)
     if (mode == CCSX_RUN_POLISH && (rc = upload_drafts(S, dr_in, h->s_in))) return fail(rc);
+    if (hdq && (rc = hd_attach(h, S, hdo, hdq->split, h->s_in))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_up, h->s_in));
     HIPTRY_F(hipStreamWaitEvent(h->s_draft, S.ev_up, 0));
     if ((rc = launch(h, S))) return fail(rc);
@@ -778,6 +855,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     } else if ((rc = enqueue_download(S, res, h->s_out))) return fail(rc);
     if (pile && (rc = enqueue_pile_download(S, pile, h->s_out))) return fail(rc);
     if (tandem && ex->tandem_len) HIPTRY_F(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_out));
+    if (hdq && (rc = enqueue_hd_download(S, hdq->report, h->s_out))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -799,6 +877,11 @@ int ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
 int ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket)
 {
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex);
+}
+int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket)
+{
+    if (!hd) { ccsx_set_error("ccsx_submit_hd: null request or report"); return -1; }
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, hd);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
 {
@@ -969,6 +1052,29 @@ int ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res,
     return 0;
 }
 
+int ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd)
+{
+    ccsx_hd_opts hdo{};
+    if (b && hd_request_check(hd, b, &hdo, "ccsx_consensus_hd")) return -1;   // (the request is checked with or without a handle)
+    if (!h || !b || !res || !hd) { ccsx_set_error("ccsx_consensus_hd: null argument"); return -1; }
+    bool tandem = false;
+    if (extras_want(ex, &tandem)) return -1;
+    ccsx_pileup *pile = ex ? ex->pile : nullptr;
+    int rc;
+    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
+    Slot &S = h->slot[0];
+    if (pile && (rc = check_pile(S, pile))) return rc;
+    if ((rc = check_results(S, res, S.P.out_kin != nullptr))) return rc;
+    if ((rc = hd_table(h)) || (rc = hd_attach(h, S, hdo, hd->split, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));             // (ccsx_run enqueues on the draft stream, which does not wait for s_comp)
+    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
+    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
+    if ((rc = enqueue_hd_download(S, hd->report, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)
 {
     if (!h || !t) { ccsx_set_error("ccsx_get_timings: no completed run"); return -1; }
@@ -1096,14 +1202,7 @@ int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts,
 {
     if (!h || !b || !drafts || !out) { ccsx_set_error("ccsx_hd_batch: null argument"); return -1; }
     ccsx_hd_opts hd;
-    if (o) hd = *o; else ccsx_hd_opts_default(&hd);
-    if (hd.min_strand_passes < 1 || hd.min_sites < 1 || hd.min_indel < 1 || hd.min_indel > 21 || !(hd.min_alt_frac >= 0.0f && hd.min_alt_frac <= 1.0f) ||
-        !(hd.max_pvalue >= 0.0 && hd.max_pvalue <= 1.0)) {
-        ccsx_set_error("ccsx_hd_batch: options out of range (min_strand_passes, min_sites >= 1; 1 <= min_indel <= 21; min_alt_frac, max_pvalue in [0, 1])"); return -1;
-    }
-    if (out->n_zmw != b->n_zmw || !out->verdict || !out->n_sub_sites || !out->n_indel_sites || !out->n_listed || !out->min_p || !out->sites) {
-        ccsx_set_error("ccsx_hd_batch: report arrays missing, or sized for another batch"); return -1;
-    }
+    if (hd_opts_check(o, &hd, "ccsx_hd_batch") || hd_report_check(out, b->n_zmw, "ccsx_hd_batch")) return -1;
     if (h->poisoned) { ccsx_set_error("ccsx_hd_batch: an earlier submit failed after work had been enqueued; destroy the handle"); return -2; }
     int rc = ccsx_upload(h, b);
     if (rc) return rc;
@@ -1111,25 +1210,10 @@ int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts,
     S.mode = CCSX_RUN_HD;                                    // (slot 0 is the finder's now: ccsx_run / ccsx_download refuse it until the next ccsx_upload)
     if ((rc = check_drafts(S, drafts, true))) return rc;
     const int n = S.P.n_zmw;
-    const size_t wins = (size_t)S.P.total_wslots + 1;
-    if (!h->d_hd_lf.p) {                                     // log k!, a sequential sum of log(k) in double (the rule's table)
-        std::vector<double> lf(CCSX_HD_LF_N, 0.0);
-        for (int q = 1; q < CCSX_HD_LF_N; ++q) lf[q] = lf[q - 1] + std::log((double)q);
-        if (h->d_hd_lf.reserve(lf.size() * 8)) return -2;
-        HIPTRY(hipMemcpy(h->d_hd_lf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice));
-    }
-    if (S.d_hd_wcnt.reserve(wins * 4) ||
-        S.d_hd_wrec.reserve(wins * CCSX_HD_WIN_SITES * sizeof(ccsx_hd_site)) || S.d_hd_wminp.reserve(wins * 8) ||
-        S.d_hd_isite.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site)) || S.d_hd_zi.reserve((size_t)n * 5 * 4) ||
-        S.d_hd_minp.reserve((size_t)n * 8) || S.d_hd_sites.reserve((size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site))) return -2;
+    if ((rc = hd_table(h)) || (rc = hd_attach(h, S, hd, 0, h->s_comp))) return rc;
     if ((rc = upload_drafts(S, drafts, h->s_comp))) return rc;
-    HIPTRY(hipMemsetAsync(S.d_hd_sites.p, 0, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site), h->s_comp));
     HIPTRY(hipStreamSynchronize(h->s_comp));
     KParams &P = S.P;
-    P.hd = hd; P.hd_lf = (const double *)h->d_hd_lf.p;
-    P.hd_wcnt = (int32_t *)S.d_hd_wcnt.p; P.hd_wrec = (ccsx_hd_site *)S.d_hd_wrec.p; P.hd_wminp = (double *)S.d_hd_wminp.p;
-    P.hd_isite = (ccsx_hd_site *)S.d_hd_isite.p; P.hd_zi = (int32_t *)S.d_hd_zi.p; P.hd_minp = (double *)S.d_hd_minp.p;
-    P.hd_sites = (ccsx_hd_site *)S.d_hd_sites.p;
     if ((rc = launch(h, S)) || (rc = ccsx_sync(h))) return rc;
     HIPTRY(hipMemcpy(out->verdict, P.hd_zi, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPTRY(hipMemcpy(out->n_sub_sites, P.hd_zi + n, (size_t)n * 4, hipMemcpyDeviceToHost));

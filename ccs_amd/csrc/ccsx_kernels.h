@@ -99,14 +99,15 @@ struct KParams {
     int32_t align16_slots;
     int32_t *retry_scratch;    // the 64-row retry's / split alignment's slots: behind k_align16's in the same buffer (the trace-backs run beside the next launch / the retry)
     int32_t align16_regions;   // 1, or 2 when the batch's quads take several launches: launch c uses region c & 1, so its trace-back runs under launch c + 1
-    // ---- heteroduplex finder (ccsx_hd_batch only; NULL otherwise).  Per-window outputs use the compact window index of k_wmap
+    // ---- heteroduplex finder (ccsx_hd_batch, or a fused run with a ccsx_hd_request; NULL otherwise).  Per-window outputs use the compact window index of k_wmap
     ccsx_hd_opts hd;
+    int32_t hd_split;          // fused run only: a HETERODUPLEX ZMW gets status CCSX_HETERODUPLEX and no windows (k_hd_verdict), the window map is rebuilt
     const double *hd_lf;       // [CCSX_HD_LF_N] log k! (host-built, DESIGN.md §2 "Heteroduplex rule")
     int32_t *hd_wcnt;          // [windows] substitution sites of the window
     ccsx_hd_site *hd_wrec;     // [windows][CCSX_HD_WIN_SITES] the window's sites with the lowest columns, in column order
     double *hd_wminp;          // [windows] smallest p of the window's sites (1 = none)
     ccsx_hd_site *hd_isite;    // [n][CCSX_HD_MAX_SITES] large-indel sites with the lowest (column, kind)
-    int32_t *hd_zi;            // [5][n] verdict, sub sites, indel sites, listed, indel sites listed
+    int32_t *hd_zi;            // [6][n] verdict, sub sites, indel sites, listed, indel sites listed, status after the cascade (before a split)
     double *hd_minp;           // [n]
     ccsx_hd_site *hd_sites;    // [n][CCSX_HD_MAX_SITES]
     // ---- pileup summary (ccsx_consensus_pileup / ccsx_submit_pileup only; NULL otherwise).  Needs wtpl / wtmeta as kinetics does

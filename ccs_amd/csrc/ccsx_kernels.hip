@@ -3829,7 +3829,12 @@ __global__ __launch_bounds__(64) void k_hd_verdict(KParams P)
                           : (nsub >= P.hd.min_sites || nind >= 1) ? CCSX_HD_HETERODUPLEX
                           : (fn >= msp && rn >= msp) ? CCSX_HD_DOUBLE_STRAND : CCSX_HD_UNTESTED;
         P.hd_zi[z] = verdict; P.hd_zi[(size_t)n + z] = ok ? nsub : 0; P.hd_zi[2 * (size_t)n + z] = nind; P.hd_zi[3 * (size_t)n + z] = listed;
+        P.hd_zi[5 * (size_t)n + z] = P.zstat[z];
         P.hd_minp[z] = ok ? minp : 1.0;
+        // the split (fused run, ccsx_hd_request.split): the ZMW leaves the polish stage here — no windows, so the rebuilt window map gives k_polish /
+        // k_kinetics nothing of it and k_stitch reports the status with an empty consensus (fn / rn stay as k_post counted them).  Only this ZMW's words
+        // are written, after every lane has read them.
+        if (P.hd_split && verdict == CCSX_HD_HETERODUPLEX) { P.zstat[z] = CCSX_HETERODUPLEX; P.nwin[z] = 0; }
     }
 }
 
@@ -4098,6 +4103,25 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     LAUNCH_CHECK("k_wmap");
     hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
     LAUNCH_CHECK("k_wmap_fill");
+    if (mode == CCSX_RUN_FUSED && P.hd_zi) {
+        // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft stage
+        // and runs under the previous batch's polish stage.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the
+        // cascade and the entry rows (k_polish trims large insertions in LDS only).  It reads no shared POA / alignment scratch.
+        const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;
+        hipLaunchKernelGGL(k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_hd_pile");
+        hipLaunchKernelGGL(k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_hd_indel");
+        hipLaunchKernelGGL(k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
+        LAUNCH_CHECK("k_hd_verdict");
+        if (P.hd_split) {                                          // the split ZMWs have no windows now: the polish stage's map without them
+            hipLaunchKernelGGL(k_wmap, dim3(1), dim3(1024), 0, st, P);
+            LAUNCH_CHECK("k_wmap");
+            hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
+            LAUNCH_CHECK("k_wmap_fill");
+        }
+        trace_sync(st, "k_hd");
+    }
     if (mode == CCSX_RUN_HD) {                                     // the heteroduplex finder instead of the polish stage, on the same stream
         if (ev) for (int k : {3, 6}) CALL_CHECK(hipEventRecord, ev[k], st);
         const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;   // (the grid covers the slot capacity, the map only the windows there are)

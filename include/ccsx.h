@@ -56,7 +56,8 @@ enum ccsx_status {
     CCSX_TOO_LONG              = 6,
     CCSX_LOW_RQ                = 7,  /* predicted accuracy below opts.min_rq                          */
     CCSX_EMPTY_WINDOW          = 8,  /* EMPTY_WINDOW_DURING_POLISHING                                 */
-    CCSX_CAPACITY              = 9   /* the polished consensus outgrew its buffer (1.25 x longest subread + 64): reported, never truncated */
+    CCSX_CAPACITY              = 9,  /* the polished consensus outgrew its buffer (1.25 x longest subread + 64): reported, never truncated */
+    CCSX_HETERODUPLEX          = 10  /* ccsx_hd_request.split: the finder's verdict was HETERODUPLEX, the ZMW was not polished (see there)    */
 };
 
 /* ---- Arrow model parameter blob (interface of docs/faq/chemistry.md:27-56 the "arrow" json files) ----
@@ -358,6 +359,28 @@ typedef struct ccsx_extras {
 int         ccsx_tandem_rule_version(void);
 int         ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex);
 int         ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket);
+
+/* The finder in the fused path: ccsx_consensus_hd (synchronous, slot 0) and ccsx_submit_hd (ticketed like ccsx_submit) are ccsx_consensus_extras /
+ * ccsx_submit_extras (ex may be NULL) plus the finder, whose three kernels run in the draft stage after the window map, on what k_polish is given: the ZMW's
+ * final draft (pass-0 POA, fallback or last resort), its window bounds, its status after the cascade and the entry rows (DESIGN.md §2 "Heteroduplex rule").
+ * The report equals ccsx_hd_batch's on the drafts of ccsx_draft_batch, field for field (report.status: the status after the cascade, before a split).
+ *   opts      NULL = ccsx_hd_opts_default; the ranges of ccsx_hd_batch.
+ *   report    required, sized for the batch; its arrays follow the lifetime rule of `res` (written by the ticket's download) and should be page-locked.
+ *   split     0: detection only, every result is byte for byte that of the same call without a request.  1: a ZMW whose verdict is HETERODUPLEX is not
+ *             polished: status CCSX_HETERODUPLEX, seq_len = n_windows = iters = 0, rq = ec = 0, np = fn + rn and fn / rn as the accounting counted them
+ *             (the values of a ZMW that fails before polishing); its kinetics and pileup planes are not written.  Every other ZMW is as with split = 0.
+ *   reserved  must be 0 (and split 0 or 1).
+ * The request struct is read during the call only.  Per batch slot the finder's buffers take about 200 bytes per window slot (1.7 GB at 16384 ZMWs x 10 kb);
+ * they are reserved by the first request on that slot.  Without a request nothing of the finder is launched, reserved or copied.  The draft and polish
+ * seams and the ccsx_upload / ccsx_run form take no request.                                                                                             */
+typedef struct ccsx_hd_request {
+    const ccsx_hd_opts *opts;
+    ccsx_hd_report     *report;
+    int32_t             split;
+    int32_t             reserved;
+} ccsx_hd_request;
+int         ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd);
+int         ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket);
 
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
