@@ -160,6 +160,61 @@ class HdReport:
         return self.sites[z, : int(self.n_listed[z])]
 
 
+# ---- adapter palindromes (include/ccsx.h ccsx_fold_*; DESIGN.md §2 "Adapter palindromes")
+FOLD_UNTESTED, FOLD_NONE, FOLD_PALINDROME = 0, 1, 2
+
+
+class FoldOpts(C.Structure):
+    _fields_ = [("max_occ", C.c_int32), ("min_hits", C.c_int32), ("min_arm", C.c_int32), ("min_span_tenths", C.c_int32), ("end_slack", C.c_int32)]
+
+
+class CFoldReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32), ("verdict", C.POINTER(C.c_int32)), ("fold", C.POINTER(C.c_int32)), ("hits", C.POINTER(C.c_int32)),
+                ("span", C.POINTER(C.c_int32))]
+
+
+class CFoldRequest(C.Structure):
+    """ccsx_fold_request: adapter-palindrome detection in the fused path (ccsx_consensus_fold / ccsx_submit_fold)"""
+    _fields_ = [("opts", C.POINTER(FoldOpts)), ("report", C.POINTER(CFoldReport)), ("reserved", C.c_int32 * 2)]
+
+
+def fold_opts_default() -> FoldOpts:
+    o = FoldOpts()
+    lib().ccsx_fold_opts_default(C.byref(o))
+    return o
+
+
+@dataclass
+class FoldReport:
+    """ccsx_fold_report: per ZMW the verdict (FOLD_*), the fold centre in draft coordinates (-1: no hit), the hits and the span of the winning bins."""
+    verdict: np.ndarray
+    fold: np.ndarray
+    hits: np.ndarray
+    span: np.ndarray
+
+    @staticmethod
+    def allocate(n: int, pinned: bool = False) -> "FoldReport":
+        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(fold=...), downloads into them asynchronously)"""
+        keep = []
+        z = (lambda: _pinned_array(n, np.int32, keep)) if pinned else (lambda: np.empty(n, np.int32))
+        rep = FoldReport(z(), z(), z(), z())
+        for a in (rep.verdict, rep.fold, rep.hits, rep.span):
+            a[...] = 0
+        rep._pinned = keep
+        return rep
+
+    def c_struct(self) -> CFoldReport:
+        r = CFoldReport()
+        r.n_zmw = len(self.verdict)
+        r.verdict, r.fold, r.hits, r.span = (_ptr(a, C.c_int32) for a in (self.verdict, self.fold, self.hits, self.span))
+        return r
+
+
+def _fold_request(opts: "FoldOpts | None", crep: CFoldReport) -> tuple[CFoldRequest, FoldOpts]:
+    o = opts if opts is not None else fold_opts_default()
+    return CFoldRequest(C.pointer(o), C.pointer(crep), (C.c_int32 * 2)(0, 0)), o
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -293,6 +348,7 @@ EXPORTS = [
     "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished",
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
     "ccsx_consensus_hd", "ccsx_submit_hd",
+    "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
 ]
 
 _lib = None
@@ -355,6 +411,10 @@ def lib() -> C.CDLL:
         L.ccsx_submit_extras.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(C.c_int64)]
         L.ccsx_consensus_hd.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CHdRequest)]
         L.ccsx_submit_hd.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CHdRequest), C.POINTER(C.c_int64)]
+        L.ccsx_fold_opts_default.restype = None
+        L.ccsx_fold_opts_default.argtypes = [C.POINTER(FoldOpts)]
+        L.ccsx_consensus_fold.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest)]
+        L.ccsx_submit_fold.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -781,6 +841,15 @@ class Handle:
         self._check(self._L.ccsx_consensus_hd(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q)), "ccsx_consensus_hd")
         return res, rep, tl, pile
 
+    # ---- adapter palindromes in the fused path (ccsx_consensus_fold): the consensus and the detector's report of one run (detection only)
+    def consensus_fold(self, batch: Batch, opts: FoldOpts | None = None) -> tuple["Results", FoldReport]:
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = FoldReport.allocate(batch.n_zmw)
+        cb, cr, crep = batch.c_struct(), res.c_struct(), rep.c_struct()
+        q, _o = _fold_request(opts, crep)
+        self._check(self._L.ccsx_consensus_fold(self._h, C.byref(cb), C.byref(cr), None, C.byref(q)), "ccsx_consensus_fold")
+        return res, rep
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -815,17 +884,29 @@ class Handle:
 
     # ---- asynchronous pipeline (ccsx_submit / ccsx_wait): up to three batches in flight, copies under compute
     def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None,
-               min_tandem_repeat_length: int = 0, hd: "HdReport | None" = None, hd_opts: HdOpts | None = None, hd_split: bool = False) -> int:
+               min_tandem_repeat_length: int = 0, hd: "HdReport | None" = None, hd_opts: HdOpts | None = None, hd_split: bool = False,
+               fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None) -> int:
         """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer,
         pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras).  hd: a report
         (HdReport.allocate(n, pinned=True)) that receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish
-        stage (ccsx_submit_hd)"""
+        stage (ccsx_submit_hd).  fold: a report (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts (ccsx_submit_fold;
+        not combined with hd)"""
         cb, cr = batch.c_struct(), res.c_struct()
         t = C.c_int64()
         ex = None
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
-        if hd is not None:
+        if hd is not None and fold is not None:
+            raise ValueError("the heteroduplex and the adapter-palindrome requests are not combined")
+        if fold is not None:
+            cp = pileup.c_struct() if pileup is not None else None
+            ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
+            crep = fold.c_struct()
+            q, o = _fold_request(fold_opts, crep)
+            self._check(self._L.ccsx_submit_fold(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q), C.byref(t)),
+                        "ccsx_submit_fold")
+            ex = (ex, o, crep, q, fold)
+        elif hd is not None:
             cp = pileup.c_struct() if pileup is not None else None
             ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
             o = hd_opts if hd_opts is not None else hd_opts_default()

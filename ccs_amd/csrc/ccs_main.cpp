@@ -73,9 +73,10 @@ struct Options {
     std::string log_file;         // --log-file: log lines go there instead of stderr (docs/faq/sqiie.md:40)
     double refresh_rate = 5.0;    // --refresh-rate: seconds between progress lines at --log-level INFO (docs/faq/reports-aux-files.md:176-177)
     int log_level = 1;
+    std::string fail_reads;       // --fail-reads FAIL.bam: one representative read per ZMW without a HiFi read, with the ff tag (docs/faq/fail-reads.md)
 };
 
-enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103 };
+enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103, HS_ADAPTER_PALINDROME = 104 };
 
 struct ZmwIn {
     int32_t zm = 0;
@@ -86,6 +87,8 @@ struct ZmwIn {
     int strand_tag = 0;           // --by-strand: 1 = /fwd, 2 = /rev
     int64_t polymerase_len = 0;   // zmw_metrics: bases of all subreads of the ZMW
     int32_t median_len = 0, n_full = 0;
+    std::string fl_name;          // --fail-reads: the median-length full-length subread (ties: the first in file order), kept before the filters clear `reads`
+    std::vector<uint8_t> fl_seq;
 };
 
 // page-locked staging of one GPU worker (bases / pw / ipd of the batch in flight), grown geometrically and reused
@@ -127,6 +130,7 @@ struct Batch {
     uint8_t *seq = nullptr, *qual = nullptr, *kin = nullptr;   // kin: 4 planes (fi, fp, ri, rp) of cap bytes each (--hifi-kinetics)
     uint8_t *pile = nullptr;      // 3 planes (coverage, matches, mismatches) of cap bytes each (--pileup-summary)
     int32_t *tlen = nullptr;      // longest sDUST-masked run of each ZMW's deciding draft (--min-tandem-repeat-length)
+    int32_t *fold = nullptr;      // --fail-reads: the adapter-palindrome report (verdict, fold, hits, span; n each)
     float *rq = nullptr, *ec = nullptr;
     int dev = 0;                  // which device's packers / worker / staging pools handle the batch (index into the handle list)
     bool have_results = false;    // false: packing or the engine failed for this batch
@@ -134,6 +138,7 @@ struct Batch {
     ccsx_batch cb; ccsx_results cr; // the structs handed to ccsx_submit live as long as the ticket
     ccsx_pileup cp{};               // ... and the one handed to ccsx_submit_pileup
     ccsx_extras ex{};               // (ccsx_submit_extras reads it during the call only)
+    ccsx_fold_report frep{}; ccsx_fold_request freq{};   // (ccsx_submit_fold: the report's arrays are in out_arena)
 };
 
 template <class T> class Channel {
@@ -190,6 +195,8 @@ void usage()
                  "      --pileup-summary      per-base pileup tags: sa (run-length encoded coverage), sm (matches), sx (mismatches) [off]\n"
                  "      --min-tandem-repeat-length N  a ZMW whose draft holds a tandem repeat (sDUST) of >= N bases runs with --disable-heuristics\n"
                  "                            for itself only; N > 0 [off: the reference's default is 1000]\n"
+                 "      --fail-reads F.bam    also write one read per ZMW that yields no HiFi read, with the ff tag: 0x1 below --min-rq, 0x20 adapter\n"
+                 "                            palindrome (such reads leave the main output), 0x8 the median full-length subread of a ZMW without a consensus\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -254,6 +261,7 @@ bool parse(int argc, char **argv, Options &o)
             o.min_tandem = (int)n;
         }
         else if (a == "--suppress-reports") o.suppress_reports = true;
+        else if (a == "--fail-reads") o.fail_reads = need(a.c_str());
         else if (a == "--model-file") o.model_file = need(a.c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
         else if (a == "--metrics-json") { o.metrics = need(a.c_str()); o.metrics_named = true; }
@@ -268,6 +276,12 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if (!o.fail_reads.empty()) {
+        if (o.fail_reads.size() < 5 || o.fail_reads.compare(o.fail_reads.size() - 4, 4, ".bam") != 0) {
+            std::fprintf(stderr, "ccs: --fail-reads needs a path ending in .bam, got '%s'\n", o.fail_reads.c_str()); std::exit(2);
+        }
+        if (o.by_strand) { std::fprintf(stderr, "ccs: --fail-reads combined with --by-strand is not supported\n"); std::exit(2); }
     }
     // --top-passes 0 = unlimited (docs/faq/accuracy-vs-passes.md:49-52); the engine takes up to CCSX_MAX_PASSES = 255 per ZMW (SPEC v5)
     if (o.o.top_passes <= 0) o.o.top_passes = CCSX_MAX_PASSES;
@@ -381,6 +395,17 @@ void finish_zmw(ZmwIn &z, const Options &o)
 {
     for (auto &r : z.reads) z.polymerase_len += (int64_t)r.size() + 45;   // + adapter between consecutive subreads
     if (z.reads.empty()) { z.host_status = HS_NO_SUBREADS; return; }
+    if (!o.fail_reads.empty()) {                                  // fail record 0x8: the median-length full-length subread (ties: the first in file order)
+        std::vector<uint32_t> fl;
+        for (auto &r : z.reads) if ((r.cx < 0) || ((r.cx & 3) == 3)) fl.push_back(r.len);
+        if (!fl.empty()) {
+            std::vector<uint32_t> s1 = fl;
+            std::nth_element(s1.begin(), s1.begin() + s1.size() / 2, s1.end());
+            const uint32_t m = s1[s1.size() / 2];
+            for (auto &r : z.reads)
+                if (((r.cx < 0) || ((r.cx & 3) == 3)) && r.len == m) { z.fl_name = r.name; z.fl_seq.resize(r.len); r.decode_bases(z.fl_seq.data()); break; }
+        }
+    }
     {
         std::vector<size_t> s0;
         for (auto &r : z.reads) s0.push_back(r.size());
@@ -491,6 +516,7 @@ struct Report {
     std::vector<int32_t> lens; std::vector<float> rqs; std::vector<int32_t> nps;   // one entry per written read
     int64_t bases_q30 = 0;        // written bases with a phred QV >= 30 ("Base quality >=Q30 (bp)", docs/faq/reports-aux-files.md:66)
     int64_t tandem = 0;           // ZMWs flagged as tandem repeats (--min-tandem-repeat-length; docs/faq/reports-aux-files.md:22)
+    int64_t fail_records = 0;     // records written to --fail-reads
 };
 
 const char *fail_label(int st)
@@ -507,6 +533,7 @@ const char *fail_label(int st)
         case CCSX_LOW_RQ: return "CCS below minimum RQ";
         case CCSX_EMPTY_WINDOW: return "Empty coverage windows";
         case CCSX_CAPACITY: return "Consensus outgrew its buffer";
+        case HS_ADAPTER_PALINDROME: return "CCS adapter palindrome";
         default: return "Unknown error";
     }
 }
@@ -526,6 +553,7 @@ const char *status_name(int st)
         case CCSX_LOW_RQ: return "POOR_QUALITY";
         case CCSX_EMPTY_WINDOW: return "EMPTY_WINDOW_DURING_POLISHING";
         case CCSX_CAPACITY: return "CAPACITY";
+        case HS_ADAPTER_PALINDROME: return "ADAPTER_PALINDROME";
         default: return "EXCEPTION_THROWN";
     }
 }
@@ -535,6 +563,17 @@ const char *status_name(int st)
 const char *const kFailOrder[] = {"Below SNR threshold", "Median length filter", "Lacking full passes", "Draft generation error",
                                   "Draft above --max-length", "Draft below --min-length", "Reads failed polishing", "Empty coverage windows",
                                   "CCS did not converge", "CCS below minimum RQ", "Consensus outgrew its buffer", "Unknown error"};
+
+// the rows printed: with --fail-reads also "CCS adapter palindrome" (now a failure) and "ZMW with full-length subread" (the 0x8 records), where the reference lists them
+std::vector<const char *> fail_order(const Options &o)
+{
+    std::vector<const char *> v;
+    for (const char *k : kFailOrder) {
+        if (!o.fail_reads.empty() && std::string(k) == "CCS below minimum RQ") { v.push_back("CCS adapter palindrome"); v.push_back("ZMW with full-length subread"); }
+        v.push_back(k);
+    }
+    return v;
+}
 
 // statistics of one class of written reads (docs/faq/reports-aux-files.md:52-64: HiFi = predicted accuracy >= Q20, "<Q20", ">=Q30")
 struct ReadClass {
@@ -583,7 +622,7 @@ void write_report(const Options &o, const Report &r)
         std::fprintf(f, "ZMWs shortcut filters         : 0 (0.00%%)\n\n");
         if (o.min_tandem > 0) std::fprintf(f, "ZMWs with tandem repeats      : %" PRId64 " (%.2f%%)\n\n", r.tandem, pct(r.tandem, r.input));
         std::fprintf(f, "Exclusive failed counts\n");
-        for (const char *k : kFailOrder) {
+        for (const char *k : fail_order(o)) {
             auto it = r.fail.find(k);
             const int64_t c = it == r.fail.end() ? 0 : it->second;
             if (c == 0 && std::string(k) == "Consensus outgrew its buffer") continue;      // (not a row of the reference: shown only when it happened)
@@ -624,7 +663,7 @@ void write_report_json(const Options &o, const Report &r)
     if (o.min_tandem > 0) std::fprintf(f, "  \"zmws_with_tandem_repeats\": %" PRId64 ",\n", r.tandem);
     std::fprintf(f, "  \"exclusive_failed_counts\": {");
     bool first = true;
-    for (const char *k : kFailOrder) {
+    for (const char *k : fail_order(o)) {
         auto it = r.fail.find(k);
         std::fprintf(f, "%s\n    \"%s\": %" PRId64, first ? "" : ",", k, it == r.fail.end() ? (int64_t)0 : it->second);
         first = false;
@@ -896,6 +935,7 @@ int main(int argc, char **argv)
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto us_since = [](std::chrono::steady_clock::time_point t) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count(); };
         const bool kin = opt.o.hifi_kinetics != 0;
+        const bool fail_reads = !opt.fail_reads.empty();
         std::vector<std::thread> packers;
         const size_t n_packers = std::max<size_t>(1, handles.size()) * (size_t)opt.workers_per_gpu;
         std::vector<std::atomic<int>> packers_left(ndev_q);
@@ -922,7 +962,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
                         b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
@@ -942,6 +982,12 @@ int main(int argc, char **argv)
                         if (opt.min_tandem > 0) {
                             b->tlen = (int32_t *)take(n4);
                             b->ex = ccsx_extras{opt.pileup ? &b->cp : nullptr, b->tlen, opt.min_tandem, 0};
+                        } else if (opt.pileup) b->ex = ccsx_extras{&b->cp, nullptr, 0, 0};
+                        if (fail_reads) {
+                            int32_t *fv = (int32_t *)take(n4), *ff = (int32_t *)take(n4), *fh = (int32_t *)take(n4), *fs = (int32_t *)take(n4);
+                            b->fold = fv;
+                            b->frep = ccsx_fold_report{n, fv, ff, fh, fs};
+                            b->freq = ccsx_fold_request{nullptr, &b->frep, {0, 0}};
                         }
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
@@ -1003,7 +1049,8 @@ int main(int argc, char **argv)
                 if (inflight.size() >= 3) retire();
                 t0 = now();
                 ccsx_ticket t = -1;
-                if (opt.min_tandem > 0 ? ccsx_submit_extras(h, &b->cb, &b->cr, &b->ex, &t)
+                if (fail_reads ? ccsx_submit_fold(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &t)
+                    : opt.min_tandem > 0 ? ccsx_submit_extras(h, &b->cb, &b->cr, &b->ex, &t)
                                        : (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t))) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
@@ -1027,6 +1074,9 @@ int main(int argc, char **argv)
             gzFile gzq = nullptr;
             if (fastq) { gzq = gzopen(opt.out.c_str(), "wb4"); if (!gzq) throw std::runtime_error("cannot create " + opt.out); }
             else outp.reset(new BgzfWriter(opt.out, pool));
+            std::unique_ptr<BgzfWriter> failp;                      // --fail-reads: FAIL.bam under the main output's header, FAIL.bam.pbi beside it
+            if (fail_reads) failp.reset(new BgzfWriter(opt.fail_reads, pool));
+            PbiIndex fpbi; std::vector<uint64_t> fmarks;
             std::string fq;
             bool header_done = false;
             std::map<int64_t, std::shared_ptr<Batch>> hold;
@@ -1047,11 +1097,53 @@ int main(int argc, char **argv)
             static const uint8_t qvbin[94] = {3,3,3,3,3,3,3, 10,10,10,10,10,10,10, 17,17,17,17,17,17, 22,22,22,22,22, 27,27,27,27,27,
                                               35,35,35,35,35,35,35,35,35,35, 40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,
                                               40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40};
+            // a CCS record of ZMW slot s as the main output writes it (tags the run asks for); the caller adds its own and finishes it
+            auto build = [&](const ZmwIn &z, Batch &bt, int s) {
+                const int64_t o = bt.seq_off[s]; const int32_t len = bt.seq_len[s];
+                const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
+                rb.begin(qname, bt.seq + o, bt.qual + o, (uint32_t)len);
+                rb.tagZ("RG", "ccsamd01");
+                rb.tagf("ec", bt.ec[s]);
+                rb.tagi("np", bt.np[s]);
+                rb.tagf("rq", bt.rq[s]);
+                rb.tagBf("sn", z.snr, 4);
+                rb.tagi("zm", z.zm);
+                if (opt.o.hifi_kinetics) {                      // docs/faq/kinetics.md:8-18, tag table docs/faq/bam-output.md:13-23
+                    const size_t cap = (size_t)bt.cap;
+                    const uint8_t *fi = bt.kin + o, *fp = fi + cap, *ri = fp + cap, *rp = ri + cap;
+                    const uint32_t nf = bt.fn[s] > 0 ? (uint32_t)len : 0, nr = bt.rn[s] > 0 ? (uint32_t)len : 0;   // a strand without passes: empty lists
+                    if (z.strand_tag) {                         // single-strand record: its own strand is the forward pair
+                        rb.tagBC("ip", fi, nf); rb.tagBC("pw", fp, nf);
+                    } else {
+                        rb.tagBC("fi", fi, nf); rb.tagBC("fp", fp, nf); rb.tagi("fn", bt.fn[s]);
+                        kin_rev.assign(ri, ri + nr); std::reverse(kin_rev.begin(), kin_rev.end());   // reverse strand: its own orientation
+                        rb.tagBC("ri", kin_rev.data(), nr);
+                        kin_rev.assign(rp, rp + nr); std::reverse(kin_rev.begin(), kin_rev.end());
+                        rb.tagBC("rp", kin_rev.data(), nr); rb.tagi("rn", bt.rn[s]);
+                    }
+                }
+                if (opt.pileup) {                               // docs/faq/bam-output.md:25-27; the rule: DESIGN.md §2 "Pileup summary"
+                    const size_t cap = (size_t)bt.cap;
+                    const uint8_t *cov = bt.pile + o;
+                    sa_rle.clear();
+                    for (int32_t q = 0; q < len;) {             // sa: <length>,<coverage>,... runs of equal coverage
+                        int32_t e = q + 1;
+                        while (e < len && cov[e] == cov[q]) ++e;
+                        sa_rle.push_back((uint32_t)(e - q)); sa_rle.push_back(cov[q]);
+                        q = e;
+                    }
+                    rb.tagBI("sa", sa_rle.data(), (uint32_t)sa_rle.size());
+                    rb.tagBC("sm", cov + cap, (uint32_t)len);
+                    rb.tagBC("sx", cov + 2 * cap, (uint32_t)len);
+                }
+            };
             auto emit = [&](Batch &bt) {
-                if (!header_done && !fastq) {
-                    write_header(*outp, "@HD\tVN:1.6\tSO:unknown\tpb:5.0.0\n@RG\tID:ccsamd01\tPL:PACBIO\tDS:READTYPE=CCS" +
-                                          std::string(opt.o.hifi_kinetics && opt.by_strand ? ";Ipd:CodecV1=ip;PulseWidth:CodecV1=pw" : "") + "\tPU:" + movie +
-                                          "\tPM:SEQUELII\n@PG\tID:ccs\tPN:ccs\tVN:amd-mi355x-r1\tDS:Generate circular consensus sequences (ccs) from subreads.\n");
+                if (!header_done) {
+                    const std::string text = "@HD\tVN:1.6\tSO:unknown\tpb:5.0.0\n@RG\tID:ccsamd01\tPL:PACBIO\tDS:READTYPE=CCS" +
+                                             std::string(opt.o.hifi_kinetics && opt.by_strand ? ";Ipd:CodecV1=ip;PulseWidth:CodecV1=pw" : "") + "\tPU:" + movie +
+                                             "\tPM:SEQUELII\n@PG\tID:ccs\tPN:ccs\tVN:amd-mi355x-r1\tDS:Generate circular consensus sequences (ccs) from subreads.\n";
+                    if (!fastq) write_header(*outp, text);
+                    if (failp) write_header(*failp, text);
                 }
                 header_done = true;
                 for (size_t i = 0; i < bt.zmws.size(); ++i) {
@@ -1060,6 +1152,10 @@ int main(int argc, char **argv)
                     int st = z.host_status;
                     const int s = bt.slot[i];
                     if (st == HS_OK) st = bt.have_results ? bt.status[s] : -1;      // -1: EXCEPTION_THROWN / "Unknown error" (engine failure)
+                    const int engine_st = st;
+                    // --fail-reads: a palindrome with a consensus is a failure of its own (DESIGN.md §2 "Adapter palindromes")
+                    if (fail_reads && s >= 0 && bt.have_results && bt.fold[s] == CCSX_FOLD_PALINDROME && (st == CCSX_SUCCESS || st == CCSX_LOW_RQ))
+                        st = HS_ADAPTER_PALINDROME;
                     const bool tandem = opt.min_tandem > 0 && s >= 0 && bt.have_results && bt.tlen[s] >= opt.min_tandem;
                     rep.tandem += tandem ? 1 : 0;
                     if (want_metrics) {
@@ -1074,9 +1170,36 @@ int main(int argc, char **argv)
                         metrics += line; first_metric = false;
                         flush_metrics(false);
                     }
-                    if (st != CCSX_SUCCESS) { rep.fail[fail_label(st)]++; continue; }
+                    const int64_t o = s >= 0 ? bt.seq_off[s] : 0; const int32_t len = (s >= 0 && bt.have_results) ? bt.seq_len[s] : 0;
+                    if (st != CCSX_SUCCESS) {
+                        rep.fail[fail_label(st)]++;
+                        if (!fail_reads) continue;
+                        if ((engine_st == CCSX_LOW_RQ || st == HS_ADAPTER_PALINDROME) && len > 0) {     // a consensus: as the main writer builds it, plus ff
+                            if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }
+                            build(z, bt, s);
+                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (st == HS_ADAPTER_PALINDROME ? 0x20 : 0));
+                            fmarks.push_back(failp->mark());
+                            fpbi.rg_id.push_back(0); fpbi.q_start.push_back(0); fpbi.q_end.push_back(len); fpbi.hole.push_back(z.zm);
+                            fpbi.read_qual.push_back(bt.rq[s]); fpbi.ctxt.push_back(0);
+                            rb.finish(*failp); ++rep.fail_records;
+                        } else if (!z.fl_seq.empty()) {             // no consensus, at least one full pass: the median full-length subread
+                            rep.fail["ZMW with full-length subread"]++;
+                            const int32_t n = (int32_t)z.fl_seq.size();
+                            rb.begin(z.fl_name, z.fl_seq.data(), nullptr, (uint32_t)n);
+                            rb.tagZ("RG", "ccsamd01");
+                            rb.tagi("np", z.n_full);
+                            rb.tagf("rq", -1.0f);
+                            rb.tagBf("sn", z.snr, 4);
+                            rb.tagi("zm", z.zm);
+                            rb.tagi("ff", 0x8);
+                            fmarks.push_back(failp->mark());
+                            fpbi.rg_id.push_back(0); fpbi.q_start.push_back(0); fpbi.q_end.push_back(n); fpbi.hole.push_back(z.zm);
+                            fpbi.read_qual.push_back(-1.0f); fpbi.ctxt.push_back(0);
+                            rb.finish(*failp); ++rep.fail_records;
+                        }
+                        continue;
+                    }
                     ++rep.pass;
-                    const int64_t o = bt.seq_off[s]; const int32_t len = bt.seq_len[s];
                     if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }   // after rq (qv-binning.md:19-21)
                     // "Base quality >=Q30 (bp)" is a statement about the HiFi yield (docs/faq/reports-aux-files.md:66: 62,526 of the 63,881 HiFi bases while <Q20 reads
                     // are present): only reads with rq >= 0.99 count, and the percentage is taken over their bases
@@ -1092,41 +1215,7 @@ int main(int argc, char **argv)
                         rep.lens.push_back(len); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]);
                         continue;
                     }
-                    rb.begin(qname, bt.seq + o, bt.qual + o, (uint32_t)len);
-                    rb.tagZ("RG", "ccsamd01");
-                    rb.tagf("ec", bt.ec[s]);
-                    rb.tagi("np", bt.np[s]);
-                    rb.tagf("rq", bt.rq[s]);
-                    rb.tagBf("sn", z.snr, 4);
-                    rb.tagi("zm", z.zm);
-                    if (opt.o.hifi_kinetics) {                      // docs/faq/kinetics.md:8-18, tag table docs/faq/bam-output.md:13-23
-                        const size_t cap = (size_t)bt.cap;
-                        const uint8_t *fi = bt.kin + o, *fp = fi + cap, *ri = fp + cap, *rp = ri + cap;
-                        const uint32_t nf = bt.fn[s] > 0 ? (uint32_t)len : 0, nr = bt.rn[s] > 0 ? (uint32_t)len : 0;   // a strand without passes: empty lists
-                        if (z.strand_tag) {                         // single-strand record: its own strand is the forward pair
-                            rb.tagBC("ip", fi, nf); rb.tagBC("pw", fp, nf);
-                        } else {
-                            rb.tagBC("fi", fi, nf); rb.tagBC("fp", fp, nf); rb.tagi("fn", bt.fn[s]);
-                            kin_rev.assign(ri, ri + nr); std::reverse(kin_rev.begin(), kin_rev.end());   // reverse strand: its own orientation
-                            rb.tagBC("ri", kin_rev.data(), nr);
-                            kin_rev.assign(rp, rp + nr); std::reverse(kin_rev.begin(), kin_rev.end());
-                            rb.tagBC("rp", kin_rev.data(), nr); rb.tagi("rn", bt.rn[s]);
-                        }
-                    }
-                    if (opt.pileup) {                               // docs/faq/bam-output.md:25-27; the rule: DESIGN.md §2 "Pileup summary"
-                        const size_t cap = (size_t)bt.cap;
-                        const uint8_t *cov = bt.pile + o;
-                        sa_rle.clear();
-                        for (int32_t q = 0; q < len;) {             // sa: <length>,<coverage>,... runs of equal coverage
-                            int32_t e = q + 1;
-                            while (e < len && cov[e] == cov[q]) ++e;
-                            sa_rle.push_back((uint32_t)(e - q)); sa_rle.push_back(cov[q]);
-                            q = e;
-                        }
-                        rb.tagBI("sa", sa_rle.data(), (uint32_t)sa_rle.size());
-                        rb.tagBC("sm", cov + cap, (uint32_t)len);
-                        rb.tagBC("sx", cov + 2 * cap, (uint32_t)len);
-                    }
+                    build(z, bt, s);
                     marks.push_back(outp->mark());
                     pbi.rg_id.push_back(0); pbi.q_start.push_back(0); pbi.q_end.push_back(len); pbi.hole.push_back(z.zm);
                     pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
@@ -1159,6 +1248,12 @@ int main(int argc, char **argv)
                 for (uint64_t m : marks) pbi.file_offset.push_back((int64_t)outp->virtual_offset(m));
                 write_pbi(opt.out + ".pbi", pool, pbi);
             }
+            if (failp) {
+                if (!header_done) write_header(*failp, "@HD\tVN:1.6\tSO:unknown\tpb:5.0.0\n@RG\tID:ccsamd01\tPL:PACBIO\tDS:READTYPE=CCS\tPU:unknown\n");
+                failp->close();
+                for (uint64_t m : fmarks) fpbi.file_offset.push_back((int64_t)failp->virtual_offset(m));
+                write_pbi(opt.fail_reads + ".pbi", pool, fpbi);
+            }
             if (gzm) { metrics += "\n  ]\n}\n"; flush_metrics(true); gzclose(gzm); }
             } catch (const std::exception &e) {
                 fail(std::string("writing ") + opt.out + ": " + e.what());
@@ -1184,14 +1279,16 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "ccs: GPU workers (sum over %zu): waiting for input %.2f s, packing (pack threads) %.2f s, submit + wait %.2f s\n", handles.size(),
                          us_wait.load() * 1e-6, us_pack.load() * 1e-6, us_engine.load() * 1e-6);
         if (opt.log_level >= 1)
-            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s\n", rep.input, rep.pass, el,
+            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",
-                         opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "");
+                         opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "",
+                         opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str());
         if (failed) {
             if (!err_msg.empty()) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
             // no plausible-looking partial output after a failed run
             std::remove(opt.out.c_str());
             std::remove((opt.out + ".pbi").c_str());
+            if (!opt.fail_reads.empty()) { std::remove(opt.fail_reads.c_str()); std::remove((opt.fail_reads + ".pbi").c_str()); }
             std::fprintf(stderr, "ccs: run failed, %s removed\n", opt.out.c_str());
         }
         return failed ? 1 : 0;

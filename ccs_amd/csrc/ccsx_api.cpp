@@ -112,6 +112,7 @@ struct Slot {
     DevBuf d_tflag, d_tlen;                       // tandem repeats only (ccsx_extras with tandem_len or a threshold)
     DevBuf d_din_len, d_din_bb;                   // caller-supplied drafts (ccsx_polish_batch): lengths, orientation references
     DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
+    DevBuf d_fold;                                // adapter palindromes only (ccsx_fold_request): [4][n] report
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
@@ -134,7 +135,7 @@ struct Slot {
                           &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
                           &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
                           &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_tflag, &d_tlen, &d_din_len, &d_din_bb,
-                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites};
+                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites, &d_fold};
         for (auto *b : bufs) b->release();
         read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
         read_off.release(); seq_off.release(); ent_off.release(); base_off.release();
@@ -789,6 +790,43 @@ static int enqueue_hd_download(const Slot &S, ccsx_hd_report *out, hipStream_t s
     return 0;
 }
 
+// ---- adapter palindromes' host side (ccsx_fold_request): argument checks before anything is enqueued, buffers and pointers of a staged slot, the report's download
+static int fold_request_check(const ccsx_fold_request *q, const ccsx_batch *b, ccsx_fold_opts *o, const char *fn)
+{
+    if (!q || !q->report) { ccsx_set_error(std::string(fn) + ": null request or report"); return -1; }
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": reserved must be 0"); return -1; }
+    if (q->opts) *o = *q->opts; else ccsx_fold_opts_default(o);
+    if (o->max_occ < 1 || o->max_occ > 64 || o->min_hits < 1 || o->min_arm < 1 || o->min_span_tenths < 0 || o->min_span_tenths > 10 || o->end_slack < 0) {
+        ccsx_set_error(std::string(fn) + ": options out of range (1 <= max_occ <= 64; min_hits, min_arm >= 1; 0 <= min_span_tenths <= 10; end_slack >= 0)"); return -1;
+    }
+    const ccsx_fold_report *r = q->report;
+    if (r->n_zmw != b->n_zmw || !r->verdict || !r->fold || !r->hits || !r->span) { ccsx_set_error(std::string(fn) + ": report arrays missing, or sized for another batch"); return -1; }
+    return 0;
+}
+
+// k_fold's LDS histogram covers the longest draft the cascade aligns (status SUCCESS needs length <= opts.max_length, and no draft exceeds its slot); -1 when
+// that is beyond its LDS bound (nothing enqueued yet by this call's request)
+static int fold_attach(ccsx_handle h, Slot &S, const ccsx_fold_opts &o)
+{
+    const int n = S.P.n_zmw;
+    int64_t longest = 16;
+    for (int z = 0; z < n; ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
+    longest = std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, 16));
+    const int64_t bins = ((2 * longest - CCSX_FOLD_K - 1) >> 6) + 2;
+    if (bins > CCSX_FOLD_MAX_BINS) { ccsx_set_error("adapter-palindrome detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
+    if (S.d_fold.reserve((size_t)n * 16)) return -2;
+    S.P.fold = o; S.P.fold_zi = (int32_t *)S.d_fold.p; S.P.fold_bins = (int32_t)bins;
+    return 0;
+}
+
+static int enqueue_fold_download(const Slot &S, ccsx_fold_report *r, hipStream_t s)
+{
+    const size_t n = (size_t)S.P.n_zmw;
+    int32_t *dst[4] = {r->verdict, r->fold, r->hits, r->span};
+    for (int k = 0; k < 4; ++k) HIPTRY(hipMemcpyAsync(dst[k], S.P.fold_zi + k * n, n * 4, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // one batch through the handle's pipeline: the fused path (ccsx_submit), the draft seam or the polish seam
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
@@ -801,13 +839,15 @@ static int extras_want(const ccsx_extras *ex, bool *tandem)
 }
 
 static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
-                       const ccsx_extras *ex = nullptr, const ccsx_hd_request *hdq = nullptr)
+                       const ccsx_extras *ex = nullptr, const ccsx_hd_request *hdq = nullptr, const ccsx_fold_request *fq = nullptr)
 {
     bool tandem = false;
     if (extras_want(ex, &tandem)) return -1;
     ccsx_pileup *pile = ex ? ex->pile : nullptr;
     ccsx_hd_opts hdo{};
     if (hdq && b && hd_request_check(hdq, b, &hdo, "ccsx_submit_hd")) return -1;   // (the request is checked with or without a handle)
+    ccsx_fold_opts fo{};
+    if (fq && b && fold_request_check(fq, b, &fo, "ccsx_submit_fold")) return -1;
     if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) { ccsx_set_error("ccsx_submit: null argument"); return -1; }
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
     if (const char *e = std::getenv("CCSX_TEST_FAIL_SUBMIT"))        // fault injection for the driver's error-path test
@@ -833,6 +873,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     if (mode != CCSX_RUN_DRAFT && (rc = check_results(S, res, S.P.out_kin != nullptr))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     if (pile && (rc = check_pile(S, pile))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     if (mode != CCSX_RUN_FUSED && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
+    if (fq && (rc = fold_attach(h, S, fo))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc == -1 ? rc : fail(rc); }
     S.mode = mode;
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
 #define HIPTRY_F(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(-2); } } while (0)
@@ -856,6 +897,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     if (pile && (rc = enqueue_pile_download(S, pile, h->s_out))) return fail(rc);
     if (tandem && ex->tandem_len) HIPTRY_F(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_out));
     if (hdq && (rc = enqueue_hd_download(S, hdq->report, h->s_out))) return fail(rc);
+    if (fq && (rc = enqueue_fold_download(S, fq->report, h->s_out))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -882,6 +924,11 @@ int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const 
 {
     if (!hd) { ccsx_set_error("ccsx_submit_hd: null request or report"); return -1; }
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, hd);
+}
+int ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket)
+{
+    if (!fold) { ccsx_set_error("ccsx_submit_fold: null request or report"); return -1; }
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, nullptr, fold);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
 {
@@ -1071,6 +1118,36 @@ int ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, con
     if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
     if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
     if ((rc = enqueue_hd_download(S, hd->report, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+void ccsx_fold_opts_default(ccsx_fold_opts *o)
+{
+    if (!o) return;
+    o->max_occ = 8; o->min_hits = 12; o->min_arm = 200; o->min_span_tenths = 8; o->end_slack = 100;   // DESIGN.md §2 "Adapter palindromes": the study behind them
+}
+
+int ccsx_fold_rule_version(void) { return 1; }
+
+int ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold)
+{
+    ccsx_fold_opts fo{};
+    if (b && fold_request_check(fold, b, &fo, "ccsx_consensus_fold")) return -1;   // (the request is checked with or without a handle)
+    if (!h || !b || !res || !fold) { ccsx_set_error("ccsx_consensus_fold: null argument"); return -1; }
+    bool tandem = false;
+    if (extras_want(ex, &tandem)) return -1;
+    ccsx_pileup *pile = ex ? ex->pile : nullptr;
+    int rc;
+    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
+    Slot &S = h->slot[0];
+    if (pile && (rc = check_pile(S, pile))) return rc;
+    if ((rc = check_results(S, res, S.P.out_kin != nullptr))) return rc;
+    if ((rc = fold_attach(h, S, fo))) return rc;
+    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
+    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
+    if ((rc = enqueue_fold_download(S, fold->report, h->s_comp))) return rc;
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
 }

@@ -119,7 +119,20 @@ struct KParams {
     int32_t *tlen;             // [n] longest run of sDUST-masked draft positions of the deciding draft (0: none decided)
     int32_t min_tandem;        // flag threshold (<= 0: detect and report only)
     int32_t sdust_words;       // k_sdust's LDS mask: 32-bit words, enough for the longest draft that is aligned
+    // ---- adapter palindromes (ccsx_consensus_fold / ccsx_submit_fold; NULL otherwise): DESIGN.md §2 "Adapter palindromes"
+    ccsx_fold_opts fold;
+    int32_t *fold_zi;          // [4][n] verdict, fold, hits, span
+    int32_t fold_bins;         // k_fold's LDS histogram: anti-diagonal bins of the longest draft that is aligned (+ 1 empty bin)
 };
+
+// k_fold (DESIGN.md §2 "Adapter palindromes"): k-mer length, sampled positions that enter, and the LDS hash table of one pass over the samples
+#define CCSX_FOLD_K        15
+#define CCSX_FOLD_NS_MAX   8192
+#define CCSX_FOLD_THREADS  256
+#define CCSX_FOLD_SLOTS    2048    // open-addressing table of canonical codes
+#define CCSX_FOLD_CAP      1536    // distinct codes and kept members one pass holds; beyond that the samples are split into more passes
+#define CCSX_FOLD_MAX_BINS 6656    // the histogram's LDS bound (drafts up to 212 kb): with k_fold's 37.9 KB of static LDS a launch stays within the
+                                   // 64 KiB it gets without raising its dynamic-LDS attribute (drafts are at most ~82 kb: 1.25 x 65535-base subreads)
 
 // k_sdust (DESIGN.md §2 "Tandem repeats"): window W bases, threshold T in tenths, dynamic LDS = two [64][64] word tables + two byte tables + the mask
 #define CCSX_SDUST_W 64

@@ -3973,6 +3973,180 @@ __global__ __launch_bounds__(64) void k_sdust(KParams P, int pass)
     if (lane == 0) { P.tlen[z] = best; P.tflag[z] = 1 | ((P.min_tandem > 0 && best >= P.min_tandem) ? 2 : 0); }
 }
 
+// ---- k_fold: adapter palindromes on a ZMW's final draft (DESIGN.md §2 "Adapter palindromes").  One 256-thread workgroup per ZMW, longest first.
+// Thread t owns a contiguous range of k-mer positions and rolls the forward and reverse-complement codes over it; every scan below re-reads the draft, so no
+// per-sample state outlives a pass.  (1) The sampled positions are counted per thread; a scan of the counts finds the last position that enters (the NS_MAX-th
+// sample).  (2) The samples are split by their hash into passes (normally one): per pass an open-addressing LDS table counts every canonical code of the pass
+// (integer atomics), a second scan links the positions of the kept codes (count <= max_occ) into per-code lists, and every kept position walks its code's list
+// for the earlier positions of the other orientation: each hit's anti-diagonal bin is counted in the LDS histogram.  A pass with more than CCSX_FOLD_CAP distinct
+// codes or kept positions restarts the vote with twice the passes, so no sample is ever dropped.  (3) The winning pair of bins, a max-reduction over (H, -b).
+// (4) The hits again (the table is kept when there is one pass), now reducing min / max of D, i and j over the winning bins.  Counts, minima and maxima only:
+// the result does not depend on thread order.  tests/fold_ref.py restates the rule.
+__device__ __forceinline__ uint32_t fold_fmix32(uint32_t h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
+
+__global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
+{
+    constexpr int K = CCSX_FOLD_K, NT = CCSX_FOLD_THREADS, T = CCSX_FOLD_SLOTS, CAP = CCSX_FOLD_CAP;
+    constexpr uint32_t NIL = 0xffffu, KMASK = (1u << (2 * K)) - 1u;
+    static_assert((T & (T - 1)) == 0 && T == 2048 && CAP < T && CAP < (int)NIL, "k_fold: the slot hash takes the top 11 bits");
+    __shared__ uint32_t sKey[T];          // canonical code + 1 (0 = empty)
+    __shared__ uint32_t sCnt[T];          // samples of the pass with that code
+    __shared__ uint32_t sHead[T];         // first linked position of the code (NIL = none)
+    __shared__ uint32_t sMem[CAP];        // linked position: i << 1 | (F != C)
+    __shared__ uint16_t sNext[CAP], sSlot[CAP];
+    __shared__ uint32_t sScan[NT];
+    __shared__ int sV[10];                // 0 codes, 1 linked, 2 overflow, 3 last position that enters, 4..9 min D, max D, min i, max i, min j, max j
+    __shared__ unsigned long long sBest;
+    uint32_t *sHist = dyn_lds;            // [fold_bins] hits per anti-diagonal bin
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= P.n_zmw) return;
+    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    const size_t n = (size_t)P.n_zmw;
+    const int L = rfl(P.draft_len[z]);
+    const int npos = L >= K ? L - K + 1 : 0;
+    const int nb = npos > 0 ? ((2 * L - K - 1) >> 6) + 1 : 0;       // bins of this draft's anti-diagonals
+    if (rfl(P.zstat[z]) != CCSX_SUCCESS || nb + 1 > P.fold_bins) {   // untested (the second: a bounds guard, the histogram covers opts.max_length)
+        if (tid == 0) { P.fold_zi[z] = CCSX_FOLD_UNTESTED; P.fold_zi[n + z] = -1; P.fold_zi[2 * n + z] = 0; P.fold_zi[3 * n + z] = 0; }
+        return;
+    }
+    const uint8_t *d = P.draft + P.seq_off[z];
+    const int ch = (npos + NT - 1) / NT;
+    const int p0 = min(tid * ch, npos), p1 = min(p0 + ch, npos);
+    // fn(i, F, C, h) for every sampled position i of this thread's range up to `last`
+    auto scan = [&](int last, auto fn) {
+        const int e = min(p1, last + 1);
+        if (p0 >= e) return;
+        uint32_t F = 0u, R = 0u;
+        for (int t = 0; t < K - 1; ++t) { const uint32_t b = d[p0 + t] & 3u; F = (F << 2) | b; R = (R >> 2) | ((3u - b) << (2 * K - 2)); }
+        for (int i = p0; i < e; ++i) {
+            const uint32_t b = d[i + K - 1] & 3u;
+            F = ((F << 2) | b) & KMASK;
+            R = (R >> 2) | ((3u - b) << (2 * K - 2));
+            const uint32_t C = F < R ? F : R, h = fold_fmix32(C);
+            if ((h & 7u) == 0u) fn(i, F, C, h);
+        }
+    };
+    // (1) the last position that enters
+    int cnt = 0;
+    scan(npos - 1, [&](int, uint32_t, uint32_t, uint32_t) { ++cnt; });
+    sScan[tid] = (uint32_t)cnt;
+    if (tid == 0) sV[3] = npos - 1;
+    __syncthreads();
+    for (int o = 1; o < NT; o <<= 1) {
+        const uint32_t v = tid >= o ? sScan[tid - o] : 0u;
+        __syncthreads();
+        sScan[tid] += v;
+        __syncthreads();
+    }
+    const int incl = (int)sScan[tid], excl = incl - cnt, total = (int)sScan[NT - 1];
+    if (excl < CCSX_FOLD_NS_MAX && incl >= CCSX_FOLD_NS_MAX) {        // this range holds the NS_MAX-th sample
+        int k = CCSX_FOLD_NS_MAX - excl;
+        scan(npos - 1, [&](int i, uint32_t, uint32_t, uint32_t) { if (--k == 0) sV[3] = i; });
+    }
+    __syncthreads();
+    const int last = sV[3];
+    const int ns = min(total, CCSX_FOLD_NS_MAX);
+    const uint32_t max_occ = (uint32_t)P.fold.max_occ;
+    // (2) pass p of nparts (a power of two): the table and the linked positions; false (for every thread) when it overflowed
+    auto build = [&](int p, int nparts) -> bool {
+        for (int s = tid; s < T; s += NT) { sKey[s] = 0u; sCnt[s] = 0u; sHead[s] = NIL; }
+        if (tid == 0) { sV[0] = 0; sV[1] = 0; sV[2] = 0; }
+        __syncthreads();
+        scan(last, [&](int, uint32_t, uint32_t C, uint32_t h) {
+            if ((int)((h >> 3) & (uint32_t)(nparts - 1)) != p) return;
+            const uint32_t key = C + 1u;
+            int s = (int)(h >> 21);
+            for (int probe = 0; probe < T; ++probe, s = (s + 1) & (T - 1)) {
+                uint32_t k = sKey[s];
+                if (k == 0u) {
+                    k = atomicCAS(&sKey[s], 0u, key);
+                    if (k == 0u) { if (atomicAdd(&sV[0], 1) >= CAP) sV[2] = 1; k = key; }
+                }
+                if (k == key) { atomicAdd(&sCnt[s], 1u); return; }
+            }
+            sV[2] = 1;                                              // (the table is full)
+        });
+        __syncthreads();
+        if (sV[2]) { __syncthreads(); return false; }
+        scan(last, [&](int i, uint32_t F, uint32_t C, uint32_t h) {
+            if ((int)((h >> 3) & (uint32_t)(nparts - 1)) != p) return;
+            const uint32_t key = C + 1u;
+            int s = (int)(h >> 21);
+            while (sKey[s] != key) s = (s + 1) & (T - 1);           // (inserted above)
+            if (sCnt[s] > max_occ) return;
+            const int m = atomicAdd(&sV[1], 1);
+            if (m >= CAP) { sV[2] = 1; return; }
+            sMem[m] = ((uint32_t)i << 1) | (F != C ? 1u : 0u);
+            sSlot[m] = (uint16_t)s;
+            sNext[m] = (uint16_t)atomicExch(&sHead[s], (uint32_t)m);
+        });
+        __syncthreads();
+        const bool ok = sV[2] == 0;
+        __syncthreads();
+        return ok;
+    };
+    // fn(i, j, D) for every hit of the current pass, counted by its later position j
+    auto hits = [&](auto fn) {
+        const int nm = sV[1];
+        for (int m = tid; m < nm; m += NT) {
+            const uint32_t vj = sMem[m];
+            const int j = (int)(vj >> 1);
+            for (uint32_t q = sHead[sSlot[m]]; q != NIL; q = sNext[q]) {
+                const uint32_t vi = sMem[q];
+                const int i = (int)(vi >> 1);
+                if (((vi ^ vj) & 1u) && i + K <= j) fn(i, j, i + j + K - 1);
+            }
+        }
+    };
+    int nparts = 1;
+    while (nparts * CAP < ns) nparts <<= 1;
+    for (;;) {
+        for (int b = tid; b <= nb; b += NT) sHist[b] = 0u;
+        bool ok = true;
+        for (int p = 0; p < nparts && ok; ++p) {
+            ok = build(p, nparts);
+            if (ok) { hits([&](int, int, int D) { atomicAdd(&sHist[D >> 6], 1u); }); __syncthreads(); }
+        }
+        if (ok) break;
+        nparts <<= 1;
+    }
+    // (3) b* = argmax over b of H(b) = hist[b] + hist[b + 1], ties to the smallest b
+    if (tid == 0) sBest = 0ull;
+    __syncthreads();
+    unsigned long long best = 0ull;
+    for (int b = tid; b < nb; b += NT) {
+        const unsigned long long key = ((unsigned long long)(sHist[b] + sHist[b + 1]) << 32) | (0xffffffffu - (uint32_t)b);
+        best = key > best ? key : best;
+    }
+    if (best >> 32) atomicMax(&sBest, best);
+    __syncthreads();
+    const int H = (int)(sBest >> 32);
+    if (H == 0) {
+        if (tid == 0) { P.fold_zi[z] = CCSX_FOLD_NONE; P.fold_zi[n + z] = -1; P.fold_zi[2 * n + z] = 0; P.fold_zi[3 * n + z] = 0; }
+        return;
+    }
+    const int bs = (int)(0xffffffffu - (uint32_t)(sBest & 0xffffffffull));
+    // (4) the extent of the winning hits
+    if (tid == 0) { sV[4] = 0x7fffffff; sV[5] = -1; sV[6] = 0x7fffffff; sV[7] = -1; sV[8] = 0x7fffffff; sV[9] = -1; }
+    __syncthreads();
+    auto extent = [&](int i, int j, int D) {
+        if ((D >> 6) != bs && (D >> 6) != bs + 1) return;
+        atomicMin(&sV[4], D); atomicMax(&sV[5], D); atomicMin(&sV[6], i); atomicMax(&sV[7], i); atomicMin(&sV[8], j); atomicMax(&sV[9], j);
+    };
+    if (nparts == 1) hits(extent);
+    else for (int p = 0; p < nparts; ++p) { (void)build(p, nparts); hits(extent); __syncthreads(); }
+    __syncthreads();
+    if (tid == 0) {
+        const ccsx_fold_opts &o = P.fold;
+        const int fold = (sV[4] + sV[5]) / 4;
+        const int span = min(sV[7] - sV[6], sV[9] - sV[8]) + K;
+        const int shorter = min(fold, L - fold);
+        const bool reach = fold <= L - fold ? sV[6] <= o.end_slack : sV[9] + K >= L - o.end_slack;
+        const bool pal = H >= o.min_hits && span >= o.min_arm && 10 * span >= o.min_span_tenths * shorter && reach;
+        P.fold_zi[z] = pal ? CCSX_FOLD_PALINDROME : CCSX_FOLD_NONE; P.fold_zi[n + z] = fold; P.fold_zi[2 * n + z] = H; P.fold_zi[3 * n + z] = span;
+    }
+}
+
 // every launch status is captured: returns NULL, or the name of the first launch that failed (ccsx_api.cpp reports it)
 #define LAUNCH_CHECK(name) do { if (hipGetLastError() != hipSuccess && !failed) failed = name; } while (0)
 #define CALL_CHECK(fn, ...) do { if (fn(__VA_ARGS__) != hipSuccess && !failed) failed = #fn; } while (0)   // (a stream / event call)
@@ -4103,6 +4277,12 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     LAUNCH_CHECK("k_wmap");
     hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
     LAUNCH_CHECK("k_wmap_fill");
+    if (mode == CCSX_RUN_FUSED && P.fold_zi) {
+        // adapter palindromes (ccsx_submit_fold / ccsx_consensus_fold): on the draft stream, on the final drafts and statuses k_polish is given; writes its report only
+        hipLaunchKernelGGL(k_fold, dim3(P.n_zmw), dim3(CCSX_FOLD_THREADS), (size_t)P.fold_bins * 4, st, P);
+        LAUNCH_CHECK("k_fold");
+        trace_sync(st, "k_fold");
+    }
     if (mode == CCSX_RUN_FUSED && P.hd_zi) {
         // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft stage
         // and runs under the previous batch's polish stage.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the

@@ -382,6 +382,40 @@ typedef struct ccsx_hd_request {
 int         ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd);
 int         ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket);
 
+/* ---- adapter palindromes (docs/faq/fail-reads.md: fail class 0x20 "CCS adapter palindrome"; the rule: DESIGN.md §2 "Adapter palindromes", its own version
+ * ccsx_fold_rule_version).  A missed adapter makes every pass read X . A . rc(X) through the hairpin; the engine polishes that into a confident consensus.  k_fold
+ * self-aligns the ZMW's final draft (what k_polish is given: pass-0 POA, fallback or last resort) against its reverse complement with sampled 15-mers and votes on
+ * the fold's anti-diagonal; integer arithmetic only.  Detection only: every result byte equals the same call without the request.
+ *   ccsx_consensus_fold  synchronous (slot 0): ccsx_consensus_extras (ex may be NULL) + the report.
+ *   ccsx_submit_fold     ticketed like ccsx_submit_extras: the report's arrays follow the lifetime rule of `res` (written by the ticket's download) and should be
+ *                        page-locked; the request and options structs are read during the call only.
+ * A NULL request or report, a report sized for another batch, nonzero reserved words or thresholds out of range are errors of the call: nothing is enqueued.
+ * Without a request nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered.                                            */
+typedef struct ccsx_fold_opts {
+    int32_t max_occ;             /* a canonical 15-mer sampled more often than this is dropped everywhere (1 .. 64)                                              */
+    int32_t min_hits;            /* hits in the winning pair of anti-diagonal bins (>= 1)                                                                        */
+    int32_t min_arm;             /* bases the hits span on each arm (>= 1)                                                                                       */
+    int32_t min_span_tenths;     /* the span covers at least this many tenths of the shorter arm (0 .. 10)                                                       */
+    int32_t end_slack;           /* the shorter arm's hits reach its end of the draft within this many bases (>= 0)                                              */
+} ccsx_fold_opts;
+enum ccsx_fold_verdict { CCSX_FOLD_UNTESTED = 0, CCSX_FOLD_NONE = 1, CCSX_FOLD_PALINDROME = 2 };
+typedef struct ccsx_fold_report {
+    int32_t  n_zmw;
+    int32_t *verdict;            /* [n_zmw] enum ccsx_fold_verdict (UNTESTED: the status after the cascade is not SUCCESS)                                        */
+    int32_t *fold;               /* [n_zmw] fold centre in draft coordinates, -1 when there is no hit                                                             */
+    int32_t *hits;               /* [n_zmw] hits in the winning pair of anti-diagonal bins                                                                        */
+    int32_t *span;               /* [n_zmw] bases the winning hits span, the shorter of the two arms' extents (0 without a hit)                                   */
+} ccsx_fold_report;
+typedef struct ccsx_fold_request {
+    const ccsx_fold_opts *opts;  /* NULL = ccsx_fold_opts_default                                                                                                 */
+    ccsx_fold_report     *report;
+    int32_t               reserved[2];   /* must be 0                                                                                                            */
+} ccsx_fold_request;
+void        ccsx_fold_opts_default(ccsx_fold_opts *o);
+int         ccsx_fold_rule_version(void);
+int         ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold);
+int         ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
