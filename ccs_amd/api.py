@@ -215,6 +215,113 @@ def _fold_request(opts: "FoldOpts | None", crep: CFoldReport) -> tuple[CFoldRequ
     return CFoldRequest(C.pointer(o), C.pointer(crep), (C.c_int32 * 2)(0, 0)), o
 
 
+# ---- adapter screen (include/ccsx.h ccsx_adapter_*; DESIGN.md §2 "Adapter screen")
+ADAPTER_CONCAT, ADAPTER_NEAR_END = 1, 2
+ADAPTER_MAX_PATTERNS, ADAPTER_MIN_LEN, ADAPTER_MAX_LEN, ADAPTER_MAX_HITS = 8, 16, 64, 16
+ADAPTER_HIT = np.dtype([("start", np.int32), ("end", np.int32), ("search", np.uint8), ("dist", np.uint8), ("pad_", np.uint8, 2)])
+
+
+class AdapterOpts(C.Structure):
+    _fields_ = [("max_dist_pct", C.c_int32), ("min_copies", C.c_int32), ("max_insert", C.c_int32), ("end_slack", C.c_int32)]
+
+
+class AdapterSet(C.Structure):
+    """ccsx_adapter_set: up to 8 adapters of 16 .. 64 codes 0 .. 3; each is searched as given and as its reverse complement"""
+    _fields_ = [("n_adapters", C.c_int32), ("len", C.c_int32 * ADAPTER_MAX_PATTERNS), ("seq", (C.c_uint8 * ADAPTER_MAX_LEN) * ADAPTER_MAX_PATTERNS)]
+
+    @staticmethod
+    def from_strings(seqs) -> "AdapterSet":
+        """from ACGT strings (either case) or arrays of codes; lengths and the count are checked by the call that takes the set"""
+        seqs = list(seqs)
+        if len(seqs) > ADAPTER_MAX_PATTERNS:
+            raise ValueError(f"at most {ADAPTER_MAX_PATTERNS} adapters")
+        s = AdapterSet()
+        s.n_adapters = len(seqs)
+        for a, q in enumerate(seqs):
+            codes = ["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q]
+            if len(codes) > ADAPTER_MAX_LEN:
+                raise ValueError(f"adapter {a}: more than {ADAPTER_MAX_LEN} bases")
+            s.len[a] = len(codes)
+            for i, c in enumerate(codes):
+                s.seq[a][i] = c
+        return s
+
+    @staticmethod
+    def default() -> "AdapterSet":
+        s = AdapterSet()
+        if lib().ccsx_adapter_set_default(C.byref(s)) != 0:
+            raise RuntimeError("ccsx_adapter_set_default failed")
+        return s
+
+    def strings(self) -> list:
+        return ["".join("ACGT"[self.seq[a][i]] for i in range(self.len[a])) for a in range(self.n_adapters)]
+
+
+class CAdapterReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in ("tested", "verdict", "n_hits", "n_listed", "covered", "max_gap", "first_start",
+                                                                              "last_end", "min_dist")] + [("hits", C.c_void_p)]
+
+
+class CAdapterRequest(C.Structure):
+    """ccsx_adapter_request: the adapter screen in the fused path (ccsx_consensus_screen / ccsx_submit_screen)"""
+    _fields_ = [("adapters", C.POINTER(AdapterSet)), ("opts", C.POINTER(AdapterOpts)), ("report", C.POINTER(CAdapterReport)), ("reserved", C.c_int32 * 2)]
+
+
+def adapter_opts_default() -> AdapterOpts:
+    o = AdapterOpts()
+    lib().ccsx_adapter_opts_default(C.byref(o))
+    return o
+
+
+@dataclass
+class AdapterReport:
+    """ccsx_adapter_report: per ZMW tested (0 / 1), the verdict bits (ADAPTER_CONCAT | ADAPTER_NEAR_END), the aggregates over every hit, and the first 16 hits
+    in increasing (end, search) as a structured array [n_zmw, 16] (ADAPTER_HIT)"""
+    tested: np.ndarray
+    verdict: np.ndarray
+    n_hits: np.ndarray
+    n_listed: np.ndarray
+    covered: np.ndarray
+    max_gap: np.ndarray
+    first_start: np.ndarray
+    last_end: np.ndarray
+    min_dist: np.ndarray
+    hits: np.ndarray
+
+    INT_FIELDS = ("tested", "verdict", "n_hits", "n_listed", "covered", "max_gap", "first_start", "last_end", "min_dist")
+
+    @staticmethod
+    def allocate(n: int, pinned: bool = False) -> "AdapterReport":
+        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(adapters=...), downloads into them asynchronously)"""
+        keep = []
+        z = (lambda: _pinned_array(n, np.int32, keep)) if pinned else (lambda: np.empty(n, np.int32))
+        hits = _pinned_array(n * ADAPTER_MAX_HITS, ADAPTER_HIT, keep) if pinned else np.empty(n * ADAPTER_MAX_HITS, ADAPTER_HIT)
+        rep = AdapterReport(*(z() for _ in AdapterReport.INT_FIELDS), hits.reshape(n, ADAPTER_MAX_HITS))
+        for k in AdapterReport.INT_FIELDS:
+            getattr(rep, k)[...] = 0
+        rep.hits.view(np.uint8)[...] = 0
+        rep._pinned = keep
+        return rep
+
+    def c_struct(self) -> CAdapterReport:
+        r = CAdapterReport()
+        r.n_zmw = len(self.verdict)
+        for k in AdapterReport.INT_FIELDS:
+            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
+        r.hits = self.hits.ctypes.data
+        return r
+
+    def listed(self, z: int) -> list:
+        """the listed hits of ZMW z as (start, end, search, dist)"""
+        return [(int(h["start"]), int(h["end"]), int(h["search"]), int(h["dist"])) for h in self.hits[z, : int(self.n_listed[z])]]
+
+
+def _adapter_request(aset: "AdapterSet | None", opts: "AdapterOpts | None", crep: CAdapterReport):
+    a = aset if aset is not None else AdapterSet.default()
+    o = opts if opts is not None else adapter_opts_default()
+    return CAdapterRequest(C.pointer(a), C.pointer(o), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (a, o)
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -349,6 +456,7 @@ EXPORTS = [
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
     "ccsx_consensus_hd", "ccsx_submit_hd",
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
+    "ccsx_adapter_opts_default", "ccsx_adapter_rule_version", "ccsx_adapter_set_default", "ccsx_consensus_screen", "ccsx_submit_screen",
 ]
 
 _lib = None
@@ -415,6 +523,12 @@ def lib() -> C.CDLL:
         L.ccsx_fold_opts_default.argtypes = [C.POINTER(FoldOpts)]
         L.ccsx_consensus_fold.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest)]
         L.ccsx_submit_fold.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(C.c_int64)]
+        L.ccsx_adapter_opts_default.restype = None
+        L.ccsx_adapter_opts_default.argtypes = [C.POINTER(AdapterOpts)]
+        L.ccsx_adapter_set_default.argtypes = [C.POINTER(AdapterSet)]
+        L.ccsx_consensus_screen.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest)]
+        L.ccsx_submit_screen.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest),
+                                         C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -850,6 +964,30 @@ class Handle:
         self._check(self._L.ccsx_consensus_fold(self._h, C.byref(cb), C.byref(cr), None, C.byref(q)), "ccsx_consensus_fold")
         return res, rep
 
+    # ---- both draft detectors in one run (ccsx_consensus_screen): adapter palindromes and / or the adapter screen, with the optional outputs of ccsx_extras
+    def consensus_screen(self, batch: Batch, fold: "bool | FoldOpts" = False, adapters: "AdapterSet | None" = None, opts: "AdapterOpts | None" = None,
+                         tandem: bool = False, min_tandem_repeat_length: int = 0, pileup: bool = False):
+        """(results, fold report or None, adapter report or None, tandem_len or None, pileup or None).  fold: True or a FoldOpts asks for the palindrome
+        report; adapters: an AdapterSet asks for the adapter screen (AdapterSet.default() = the SMRTbell hairpin), opts its AdapterOpts.  Detection only"""
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        tl = tandem_buffer(batch.n_zmw) if tandem else None
+        pile = Pileup.allocate(res) if pileup else None
+        cb, cr = batch.c_struct(), res.c_struct()
+        cp = pile.c_struct() if pile is not None else None
+        ex = _extras(cp, tl, min_tandem_repeat_length) if (tandem or pileup or min_tandem_repeat_length) else None
+        frep = arep = fq = aq = None
+        if fold:
+            frep = FoldReport.allocate(batch.n_zmw)
+            cfr = frep.c_struct()
+            fq, _fo = _fold_request(fold if isinstance(fold, FoldOpts) else None, cfr)
+        if adapters is not None:
+            arep = AdapterReport.allocate(batch.n_zmw)
+            car = arep.c_struct()
+            aq, _ao = _adapter_request(adapters, opts, car)
+        self._check(self._L.ccsx_consensus_screen(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None,
+                                                  C.byref(fq) if fq is not None else None, C.byref(aq) if aq is not None else None), "ccsx_consensus_screen")
+        return res, frep, arep, tl, pile
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -885,12 +1023,14 @@ class Handle:
     # ---- asynchronous pipeline (ccsx_submit / ccsx_wait): up to three batches in flight, copies under compute
     def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None,
                min_tandem_repeat_length: int = 0, hd: "HdReport | None" = None, hd_opts: HdOpts | None = None, hd_split: bool = False,
-               fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None) -> int:
+               fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None, adapters: "AdapterReport | None" = None,
+               adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None) -> int:
         """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer,
         pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras).  hd: a report
         (HdReport.allocate(n, pinned=True)) that receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish
         stage (ccsx_submit_hd).  fold: a report (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts (ccsx_submit_fold;
-        not combined with hd)"""
+        not combined with hd).  adapters: a report (AdapterReport.allocate(n, pinned=True)) that receives the adapter screen of adapter_set (None: the built-in
+        set) under adapter_opts, alone or together with fold (ccsx_submit_screen; not combined with hd)"""
         cb, cr = batch.c_struct(), res.c_struct()
         t = C.c_int64()
         ex = None
@@ -898,7 +1038,19 @@ class Handle:
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
             raise ValueError("the heteroduplex and the adapter-palindrome requests are not combined")
-        if fold is not None:
+        if hd is not None and adapters is not None:
+            raise ValueError("the heteroduplex request and the adapter screen are not combined")
+        if adapters is not None:
+            cp = pileup.c_struct() if pileup is not None else None
+            ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
+            cfr = fold.c_struct() if fold is not None else None
+            fq = _fold_request(fold_opts, cfr) if fold is not None else None
+            car = adapters.c_struct()
+            aq = _adapter_request(adapter_set, adapter_opts, car)
+            self._check(self._L.ccsx_submit_screen(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None,
+                                                   C.byref(fq[0]) if fq is not None else None, C.byref(aq[0]), C.byref(t)), "ccsx_submit_screen")
+            ex = (ex, cfr, fq, fold, car, aq, adapters)
+        elif fold is not None:
             cp = pileup.c_struct() if pileup is not None else None
             ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
             crep = fold.c_struct()

@@ -15,7 +15,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <cstring>
+#include <fstream>
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -74,9 +76,12 @@ struct Options {
     double refresh_rate = 5.0;    // --refresh-rate: seconds between progress lines at --log-level INFO (docs/faq/reports-aux-files.md:176-177)
     int log_level = 1;
     std::string fail_reads;       // --fail-reads FAIL.bam: one representative read per ZMW without a HiFi read, with the ff tag (docs/faq/fail-reads.md)
+    std::string adapters;         // --adapters FILE.fasta|default: screen the drafts for adapter sequence (fail classes 0x10, 0x40); needs --fail-reads
+    ccsx_adapter_set adapter_set{};   // ... the set it names
 };
 
-enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103, HS_ADAPTER_PALINDROME = 104 };
+enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103, HS_ADAPTER_PALINDROME = 104, HS_ADAPTER_CONCAT = 105,
+                  HS_ADAPTER_NEAR_END = 106 };
 
 struct ZmwIn {
     int32_t zm = 0;
@@ -139,6 +144,7 @@ struct Batch {
     ccsx_pileup cp{};               // ... and the one handed to ccsx_submit_pileup
     ccsx_extras ex{};               // (ccsx_submit_extras reads it during the call only)
     ccsx_fold_report frep{}; ccsx_fold_request freq{};   // (ccsx_submit_fold: the report's arrays are in out_arena)
+    ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_submit_screen: the report's arrays are in out_arena)
 };
 
 template <class T> class Channel {
@@ -197,6 +203,9 @@ void usage()
                  "                            for itself only; N > 0 [off: the reference's default is 1000]\n"
                  "      --fail-reads F.bam    also write one read per ZMW that yields no HiFi read, with the ff tag: 0x1 below --min-rq, 0x20 adapter\n"
                  "                            palindrome (such reads leave the main output), 0x8 the median full-length subread of a ZMW without a consensus\n"
+                 "      --adapters F|default  with --fail-reads: screen every draft for the adapters of FASTA file F (up to 8 records of 16-64 bases) or for the\n"
+                 "                            built-in SMRTbell adapter; reads made of adapter copies (ff 0x10) or with an adapter close to an end (ff 0x40)\n"
+                 "                            leave the main output for F.bam [off]\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -217,6 +226,41 @@ void usage()
                  "      --write-synthetic N,P,L[,seed]  write a synthetic subreads.bam to OUT (no IN)\n"
                  "      --dump-zmws                     list ZMWs after the step-1 filters (no GPU, no OUT)\n"
                  "      --host-only                     read, filter and pack IN into batch staging, no engine (no GPU, no OUT): host throughput\n");
+}
+
+// --adapters: "default" = the built-in set; otherwise a FASTA of 1 .. 8 records of 16 .. 64 bases, ACGT in either case.  false + a message that names the record
+bool load_adapters(const std::string &path, ccsx_adapter_set &set, std::string &err)
+{
+    if (path == "default") return ccsx_adapter_set_default(&set) == 0;
+    std::ifstream f(path);
+    if (!f) { err = "cannot open the file"; return false; }
+    std::memset(&set, 0, sizeof set);
+    std::vector<std::string> names;
+    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + names[k] + ")"; };
+    std::string line;
+    while (std::getline(f, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            names.push_back(line.substr(0, 60));
+            if (names.size() > CCSX_ADAPTER_MAX_PATTERNS) { err = where(names.size() - 1) + ": more than 8 records"; return false; }
+            continue;
+        }
+        if (names.empty()) { err = "sequence before the first '>' line"; return false; }
+        const size_t a = names.size() - 1;
+        for (char c : line) {
+            const int u = std::toupper((unsigned char)c);
+            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
+            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
+            if (set.len[a] >= CCSX_ADAPTER_MAX_LEN) { err = where(a) + ": more than 64 bases"; return false; }
+            set.seq[a][set.len[a]++] = (uint8_t)code;
+        }
+    }
+    if (names.empty()) { err = "no FASTA record"; return false; }
+    set.n_adapters = (int32_t)names.size();
+    for (size_t k = 0; k < names.size(); ++k)
+        if (set.len[k] < CCSX_ADAPTER_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 16"; return false; }
+    return true;
 }
 
 bool parse(int argc, char **argv, Options &o)
@@ -262,6 +306,7 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (a == "--suppress-reports") o.suppress_reports = true;
         else if (a == "--fail-reads") o.fail_reads = need(a.c_str());
+        else if (a == "--adapters") o.adapters = need(a.c_str());
         else if (a == "--model-file") o.model_file = need(a.c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
         else if (a == "--metrics-json") { o.metrics = need(a.c_str()); o.metrics_named = true; }
@@ -282,6 +327,11 @@ bool parse(int argc, char **argv, Options &o)
             std::fprintf(stderr, "ccs: --fail-reads needs a path ending in .bam, got '%s'\n", o.fail_reads.c_str()); std::exit(2);
         }
         if (o.by_strand) { std::fprintf(stderr, "ccs: --fail-reads combined with --by-strand is not supported\n"); std::exit(2); }
+    }
+    if (!o.adapters.empty()) {
+        if (o.fail_reads.empty()) { std::fprintf(stderr, "ccs: --adapters needs --fail-reads (the reads it flags are written there)\n"); std::exit(2); }
+        std::string err;
+        if (!load_adapters(o.adapters, o.adapter_set, err)) { std::fprintf(stderr, "ccs: --adapters %s: %s\n", o.adapters.c_str(), err.c_str()); std::exit(2); }
     }
     // --top-passes 0 = unlimited (docs/faq/accuracy-vs-passes.md:49-52); the engine takes up to CCSX_MAX_PASSES = 255 per ZMW (SPEC v5)
     if (o.o.top_passes <= 0) o.o.top_passes = CCSX_MAX_PASSES;
@@ -534,6 +584,8 @@ const char *fail_label(int st)
         case CCSX_EMPTY_WINDOW: return "Empty coverage windows";
         case CCSX_CAPACITY: return "Consensus outgrew its buffer";
         case HS_ADAPTER_PALINDROME: return "CCS adapter palindrome";
+        case HS_ADAPTER_CONCAT: return "CCS adapter concatenation";
+        case HS_ADAPTER_NEAR_END: return "CCS adapter near end";
         default: return "Unknown error";
     }
 }
@@ -554,6 +606,8 @@ const char *status_name(int st)
         case CCSX_EMPTY_WINDOW: return "EMPTY_WINDOW_DURING_POLISHING";
         case CCSX_CAPACITY: return "CAPACITY";
         case HS_ADAPTER_PALINDROME: return "ADAPTER_PALINDROME";
+        case HS_ADAPTER_CONCAT: return "ADAPTER_CONCATENATION";
+        case HS_ADAPTER_NEAR_END: return "ADAPTER_NEAR_END";
         default: return "EXCEPTION_THROWN";
     }
 }
@@ -569,7 +623,11 @@ std::vector<const char *> fail_order(const Options &o)
 {
     std::vector<const char *> v;
     for (const char *k : kFailOrder) {
-        if (!o.fail_reads.empty() && std::string(k) == "CCS below minimum RQ") { v.push_back("CCS adapter palindrome"); v.push_back("ZMW with full-length subread"); }
+        if (!o.fail_reads.empty() && std::string(k) == "CCS below minimum RQ") {
+            v.push_back("CCS adapter palindrome");
+            if (!o.adapters.empty()) { v.push_back("CCS adapter concatenation"); v.push_back("CCS adapter near end"); }   // (--adapters: the screen's two classes)
+            v.push_back("ZMW with full-length subread");
+        }
         v.push_back(k);
     }
     return v;
@@ -936,6 +994,7 @@ int main(int argc, char **argv)
         auto us_since = [](std::chrono::steady_clock::time_point t) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count(); };
         const bool kin = opt.o.hifi_kinetics != 0;
         const bool fail_reads = !opt.fail_reads.empty();
+        const bool screen = !opt.adapters.empty();                  // (needs fail_reads)
         std::vector<std::thread> packers;
         const size_t n_packers = std::max<size_t>(1, handles.size()) * (size_t)opt.workers_per_gpu;
         std::vector<std::atomic<int>> packers_left(ndev_q);
@@ -962,7 +1021,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
                         b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
@@ -988,6 +1047,13 @@ int main(int argc, char **argv)
                             b->fold = fv;
                             b->frep = ccsx_fold_report{n, fv, ff, fh, fs};
                             b->freq = ccsx_fold_request{nullptr, &b->frep, {0, 0}};
+                        }
+                        if (screen) {
+                            int32_t *a9[9];
+                            for (auto &p : a9) p = (int32_t *)take(n4);
+                            ccsx_adapter_hit *hits = (ccsx_adapter_hit *)take(3 * CCSX_ADAPTER_MAX_HITS * n4);
+                            b->arep = ccsx_adapter_report{n, a9[0], a9[1], a9[2], a9[3], a9[4], a9[5], a9[6], a9[7], a9[8], hits};
+                            b->areq = ccsx_adapter_request{&opt.adapter_set, nullptr, &b->arep, {0, 0}};
                         }
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
@@ -1049,7 +1115,8 @@ int main(int argc, char **argv)
                 if (inflight.size() >= 3) retire();
                 t0 = now();
                 ccsx_ticket t = -1;
-                if (fail_reads ? ccsx_submit_fold(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &t)
+                if (screen ? ccsx_submit_screen(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &b->areq, &t)
+                    : fail_reads ? ccsx_submit_fold(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &t)
                     : opt.min_tandem > 0 ? ccsx_submit_extras(h, &b->cb, &b->cr, &b->ex, &t)
                                        : (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t))) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
@@ -1156,6 +1223,10 @@ int main(int argc, char **argv)
                     // --fail-reads: a palindrome with a consensus is a failure of its own (DESIGN.md §2 "Adapter palindromes")
                     if (fail_reads && s >= 0 && bt.have_results && bt.fold[s] == CCSX_FOLD_PALINDROME && (st == CCSX_SUCCESS || st == CCSX_LOW_RQ))
                         st = HS_ADAPTER_PALINDROME;
+                    // --adapters: a tested ZMW with a consensus and a verdict of the screen fails too; counted under the first that holds of palindrome,
+                    // concatenation, near end (DESIGN.md §2 "Adapter screen")
+                    const int abits = (screen && s >= 0 && bt.have_results && bt.arep.tested[s] && (engine_st == CCSX_SUCCESS || engine_st == CCSX_LOW_RQ)) ? bt.arep.verdict[s] : 0;
+                    if (abits && st != HS_ADAPTER_PALINDROME) st = (abits & CCSX_ADAPTER_CONCAT) ? HS_ADAPTER_CONCAT : HS_ADAPTER_NEAR_END;
                     const bool tandem = opt.min_tandem > 0 && s >= 0 && bt.have_results && bt.tlen[s] >= opt.min_tandem;
                     rep.tandem += tandem ? 1 : 0;
                     if (want_metrics) {
@@ -1174,10 +1245,11 @@ int main(int argc, char **argv)
                     if (st != CCSX_SUCCESS) {
                         rep.fail[fail_label(st)]++;
                         if (!fail_reads) continue;
-                        if ((engine_st == CCSX_LOW_RQ || st == HS_ADAPTER_PALINDROME) && len > 0) {     // a consensus: as the main writer builds it, plus ff
+                        if ((engine_st == CCSX_LOW_RQ || st == HS_ADAPTER_PALINDROME || abits) && len > 0) {     // a consensus: as the main writer builds it, plus ff
                             if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }
                             build(z, bt, s);
-                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (st == HS_ADAPTER_PALINDROME ? 0x20 : 0));
+                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (st == HS_ADAPTER_PALINDROME ? 0x20 : 0) | ((abits & CCSX_ADAPTER_CONCAT) ? 0x10 : 0) |
+                                              ((abits & CCSX_ADAPTER_NEAR_END) ? 0x40 : 0));
                             fmarks.push_back(failp->mark());
                             fpbi.rg_id.push_back(0); fpbi.q_start.push_back(0); fpbi.q_end.push_back(len); fpbi.hole.push_back(z.zm);
                             fpbi.read_qual.push_back(bt.rq[s]); fpbi.ctxt.push_back(0);

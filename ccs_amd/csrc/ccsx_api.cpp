@@ -113,6 +113,7 @@ struct Slot {
     DevBuf d_din_len, d_din_bb;                   // caller-supplied drafts (ccsx_polish_batch): lengths, orientation references
     DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
     DevBuf d_fold;                                // adapter palindromes only (ccsx_fold_request): [4][n] report
+    DevBuf d_adapt;                               // adapter screen only (ccsx_adapter_request): [9][n] report + [n][16] hits
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
@@ -135,7 +136,7 @@ struct Slot {
                           &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
                           &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
                           &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_tflag, &d_tlen, &d_din_len, &d_din_bb,
-                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites, &d_fold};
+                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites, &d_fold, &d_adapt};
         for (auto *b : bufs) b->release();
         read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
         read_off.release(); seq_off.release(); ent_off.release(); base_off.release();
@@ -827,6 +828,62 @@ static int enqueue_fold_download(const Slot &S, ccsx_fold_report *r, hipStream_t
     return 0;
 }
 
+// ---- the adapter screen's host side (ccsx_adapter_request): the same three steps.  The checked set and options are copied into `set` / `o`
+static int adapter_request_check(const ccsx_adapter_request *q, const ccsx_batch *b, ccsx_adapter_set *set, ccsx_adapter_opts *o, const char *fn)
+{
+    if (!q || !q->report) { ccsx_set_error(std::string(fn) + ": null adapter request or report"); return -1; }
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": adapter request: reserved must be 0"); return -1; }
+    if (!q->adapters) { ccsx_set_error(std::string(fn) + ": null adapter set"); return -1; }
+    if (q->opts) *o = *q->opts; else ccsx_adapter_opts_default(o);
+    if (o->max_dist_pct < 0 || o->max_dist_pct > 30 || o->min_copies < 1 || o->max_insert < 0 || o->end_slack < 0) {
+        ccsx_set_error(std::string(fn) + ": adapter options out of range (0 <= max_dist_pct <= 30; min_copies >= 1; max_insert, end_slack >= 0)"); return -1;
+    }
+    *set = *q->adapters;
+    if (set->n_adapters < 1 || set->n_adapters > CCSX_ADAPTER_MAX_PATTERNS) { ccsx_set_error(std::string(fn) + ": n_adapters outside 1 .. 8"); return -1; }
+    for (int a = 0; a < set->n_adapters; ++a) {
+        if (set->len[a] < CCSX_ADAPTER_MIN_LEN || set->len[a] > CCSX_ADAPTER_MAX_LEN) {
+            ccsx_set_error(std::string(fn) + ": adapter " + std::to_string(a) + ": length outside 16 .. 64"); return -1;
+        }
+        for (int i = 0; i < set->len[a]; ++i)
+            if (set->seq[a][i] > 3) { ccsx_set_error(std::string(fn) + ": adapter " + std::to_string(a) + ": code above 3"); return -1; }
+    }
+    const ccsx_adapter_report *r = q->report;
+    if (r->n_zmw != b->n_zmw || !r->tested || !r->verdict || !r->n_hits || !r->n_listed || !r->covered || !r->max_gap || !r->first_start || !r->last_end ||
+        !r->min_dist || !r->hits) { ccsx_set_error(std::string(fn) + ": adapter report arrays missing, or sized for another batch"); return -1; }
+    return 0;
+}
+
+// k_adapter's two LDS bitmaps are sized from the longest draft the cascade aligns (status SUCCESS needs length <= opts.max_length, and no draft exceeds its
+// slot), so a handle opened with a larger max_length gets larger bitmaps; -1 when that is beyond their LDS bound (nothing enqueued yet by this call's request)
+static int adapter_attach(ccsx_handle h, Slot &S, const ccsx_adapter_set &set, const ccsx_adapter_opts &o)
+{
+    static_assert(sizeof(ccsx_adapter_hit) == 12, "k_adapter writes a hit as three words");
+    const int n = S.P.n_zmw;
+    int64_t longest = 32;
+    for (int z = 0; z < n; ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
+    longest = std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, 32));
+    const int64_t words = (longest + 31) >> 5;
+    if (words > CCSX_ADAPTER_MAX_WORDS) { ccsx_set_error("adapter screen: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
+    if (S.d_adapt.reserve((size_t)n * (9 * 4 + CCSX_ADAPTER_MAX_HITS * sizeof(ccsx_adapter_hit)))) return -2;
+    KParams &P = S.P;
+    P.adapt = o; P.adapt_zi = (int32_t *)S.d_adapt.p; P.adapt_hits = P.adapt_zi + (size_t)9 * n; P.adapt_words = (int32_t)words; P.adapt_n = set.n_adapters;
+    for (int a = 0; a < CCSX_ADAPTER_MAX_PATTERNS; ++a) {
+        P.adapt_len[a] = a < set.n_adapters ? (uint8_t)set.len[a] : 0;
+        for (int w = 0; w < 4; ++w) P.adapt_seq[a][w] = 0u;
+        for (int i = 0; a < set.n_adapters && i < set.len[a]; ++i) P.adapt_seq[a][i >> 4] |= (uint32_t)set.seq[a][i] << (2 * (i & 15));
+    }
+    return 0;
+}
+
+static int enqueue_adapter_download(const Slot &S, ccsx_adapter_report *r, hipStream_t s)
+{
+    const size_t n = (size_t)S.P.n_zmw;
+    int32_t *dst[9] = {r->tested, r->verdict, r->n_hits, r->n_listed, r->covered, r->max_gap, r->first_start, r->last_end, r->min_dist};
+    for (int k = 0; k < 9; ++k) HIPTRY(hipMemcpyAsync(dst[k], S.P.adapt_zi + k * n, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->hits, S.P.adapt_hits, n * CCSX_ADAPTER_MAX_HITS * sizeof(ccsx_adapter_hit), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // one batch through the handle's pipeline: the fused path (ccsx_submit), the draft seam or the polish seam
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
@@ -839,7 +896,8 @@ static int extras_want(const ccsx_extras *ex, bool *tandem)
 }
 
 static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
-                       const ccsx_extras *ex = nullptr, const ccsx_hd_request *hdq = nullptr, const ccsx_fold_request *fq = nullptr)
+                       const ccsx_extras *ex = nullptr, const ccsx_hd_request *hdq = nullptr, const ccsx_fold_request *fq = nullptr, const ccsx_adapter_request *aq = nullptr,
+                       const char *fn = "ccsx_submit_fold")
 {
     bool tandem = false;
     if (extras_want(ex, &tandem)) return -1;
@@ -847,7 +905,9 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     ccsx_hd_opts hdo{};
     if (hdq && b && hd_request_check(hdq, b, &hdo, "ccsx_submit_hd")) return -1;   // (the request is checked with or without a handle)
     ccsx_fold_opts fo{};
-    if (fq && b && fold_request_check(fq, b, &fo, "ccsx_submit_fold")) return -1;
+    if (fq && b && fold_request_check(fq, b, &fo, fn)) return -1;
+    ccsx_adapter_set aset; ccsx_adapter_opts ao{};
+    if (aq && b && adapter_request_check(aq, b, &aset, &ao, fn)) return -1;
     if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) { ccsx_set_error("ccsx_submit: null argument"); return -1; }
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
     if (const char *e = std::getenv("CCSX_TEST_FAIL_SUBMIT"))        // fault injection for the driver's error-path test
@@ -874,6 +934,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     if (pile && (rc = check_pile(S, pile))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     if (mode != CCSX_RUN_FUSED && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
     if (fq && (rc = fold_attach(h, S, fo))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc == -1 ? rc : fail(rc); }
+    if (aq && (rc = adapter_attach(h, S, aset, ao))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc == -1 ? rc : fail(rc); }
     S.mode = mode;
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
 #define HIPTRY_F(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(-2); } } while (0)
@@ -898,6 +959,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     if (tandem && ex->tandem_len) HIPTRY_F(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_out));
     if (hdq && (rc = enqueue_hd_download(S, hdq->report, h->s_out))) return fail(rc);
     if (fq && (rc = enqueue_fold_download(S, fq->report, h->s_out))) return fail(rc);
+    if (aq && (rc = enqueue_adapter_download(S, aq->report, h->s_out))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -929,6 +991,11 @@ int ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cons
 {
     if (!fold) { ccsx_set_error("ccsx_submit_fold: null request or report"); return -1; }
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, nullptr, fold);
+}
+int ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
+                       ccsx_ticket *ticket)
+{
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, nullptr, fold, adapters, "ccsx_submit_screen");
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
 {
@@ -1148,6 +1215,50 @@ int ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
     if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
     if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
     if ((rc = enqueue_fold_download(S, fold->report, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+void ccsx_adapter_opts_default(ccsx_adapter_opts *o)
+{
+    if (!o) return;
+    o->max_dist_pct = 20; o->min_copies = 2; o->max_insert = 100; o->end_slack = 200;   // DESIGN.md §2 "Adapter screen": the reasons for them
+}
+
+int ccsx_adapter_rule_version(void) { return 1; }
+
+int ccsx_adapter_set_default(ccsx_adapter_set *s)
+{
+    if (!s) { ccsx_set_error("ccsx_adapter_set_default: null argument"); return -1; }
+    static const char hairpin[] = "ATCTCTCTCTTTTCCTCCTCCTCCGTTGTTGTTGTTGAGAGAGAT";   // the 45-base SMRTbell adapter
+    std::memset(s, 0, sizeof *s);
+    s->n_adapters = 1; s->len[0] = (int32_t)(sizeof hairpin - 1);
+    for (int i = 0; i < s->len[0]; ++i) s->seq[0][i] = (uint8_t)(hairpin[i] == 'A' ? 0 : hairpin[i] == 'C' ? 1 : hairpin[i] == 'G' ? 2 : 3);
+    return 0;
+}
+
+int ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters)
+{
+    ccsx_fold_opts fo{};
+    ccsx_adapter_set aset; ccsx_adapter_opts ao{};
+    if (fold && b && fold_request_check(fold, b, &fo, "ccsx_consensus_screen")) return -1;   // (the requests are checked with or without a handle)
+    if (adapters && b && adapter_request_check(adapters, b, &aset, &ao, "ccsx_consensus_screen")) return -1;
+    if (!h || !b || !res) { ccsx_set_error("ccsx_consensus_screen: null argument"); return -1; }
+    bool tandem = false;
+    if (extras_want(ex, &tandem)) return -1;
+    ccsx_pileup *pile = ex ? ex->pile : nullptr;
+    int rc;
+    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
+    Slot &S = h->slot[0];
+    if (pile && (rc = check_pile(S, pile))) return rc;
+    if ((rc = check_results(S, res, S.P.out_kin != nullptr))) return rc;
+    if (fold && (rc = fold_attach(h, S, fo))) return rc;
+    if (adapters && (rc = adapter_attach(h, S, aset, ao))) return rc;
+    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
+    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
+    if (fold && (rc = enqueue_fold_download(S, fold->report, h->s_comp))) return rc;
+    if (adapters && (rc = enqueue_adapter_download(S, adapters->report, h->s_comp))) return rc;
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
 }

@@ -123,7 +123,21 @@ struct KParams {
     ccsx_fold_opts fold;
     int32_t *fold_zi;          // [4][n] verdict, fold, hits, span
     int32_t fold_bins;         // k_fold's LDS histogram: anti-diagonal bins of the longest draft that is aligned (+ 1 empty bin)
+    // ---- adapter screen (ccsx_consensus_screen / ccsx_submit_screen with an adapter request; NULL otherwise): DESIGN.md §2 "Adapter screen"
+    ccsx_adapter_opts adapt;
+    int32_t *adapt_zi;         // [9][n] tested, verdict, n_hits, n_listed, covered, max_gap, first_start, last_end, min_dist
+    int32_t *adapt_hits;       // [n][CCSX_ADAPTER_MAX_HITS][3] start, end, search | dist << 8 (the bytes of ccsx_adapter_hit)
+    int32_t adapt_words;       // k_adapter's two LDS bitmaps: 32-bit words each, enough for the longest draft that is aligned
+    int32_t adapt_n;           // adapters (searches = 2 x)
+    uint8_t adapt_len[CCSX_ADAPTER_MAX_PATTERNS];
+    uint32_t adapt_seq[CCSX_ADAPTER_MAX_PATTERNS][4];   // 2 bits per base, base i at bits 2 (i & 15) of word i >> 4
 };
+
+// k_adapter (DESIGN.md §2 "Adapter screen"): draft bases a lane owns per search, its workgroup, the hit keys one pass buffers in LDS and the bitmaps' LDS bound
+#define CCSX_ADAPTER_CHUNK     128
+#define CCSX_ADAPTER_THREADS   256
+#define CCSX_ADAPTER_BUF       1024
+#define CCSX_ADAPTER_MAX_WORDS 6144   // 2 bitmaps x 24 KiB (drafts up to 196 kb) + 12.4 KB of static LDS stay within the 64 KiB a launch gets by default
 
 // k_fold (DESIGN.md §2 "Adapter palindromes"): k-mer length, sampled positions that enter, and the LDS hash table of one pass over the samples
 #define CCSX_FOLD_K        15

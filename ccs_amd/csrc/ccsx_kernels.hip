@@ -4147,6 +4147,194 @@ __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
     }
 }
 
+// ---- k_adapter: the adapter screen on a ZMW's final draft (DESIGN.md §2 "Adapter screen").  One 256-thread workgroup per ZMW, longest first.  Myers' bit-vector
+// column update, one 64-bit word per search.  A lane owns one (search, chunk of CCSX_ADAPTER_CHUNK draft bases): it starts from the all-ones vertical state m + k
+// bases before its chunk (after that warm-up every value <= k is exact and so is the predicate E <= k: a fresh start can only over-estimate, and a match of distance
+// <= k spans at most m + k draft bases) and owns the runs that START inside its chunk, following such a run past the chunk's end until it closes, so every hit is
+// found by exactly one lane.  The hit's start is the owning lane's second pass: the reversed pattern against the reversed draft, anchored at the end.  Aggregates
+// are LDS atomic add / min / max / or (counts, minima, maxima and a bitmap of the union: nothing depends on lane order).  The list: every hit's key (end, search,
+// dist, length) goes to an LDS buffer; when the buffer overflows (a draft made of adapters) the pass is repeated for the hits that end at or before the 16th set
+// bit of a bitmap of the ends (at most 16 ends x 16 searches, so that pass cannot overflow).  The 16 smallest keys are selected by rank.  tests/adapter_ref.py
+// restates the rule.
+struct AdapterCol { unsigned long long Pv, Mv; int score; };
+
+__device__ __forceinline__ void adapter_step(AdapterCol &c, unsigned long long Eq, unsigned long long top, unsigned long long anchored)
+{
+    const unsigned long long Xv = Eq | c.Mv;
+    const unsigned long long Xh = (((Eq & c.Pv) + c.Pv) ^ c.Pv) | Eq;
+    unsigned long long Ph = c.Mv | ~(Xh | c.Pv);
+    unsigned long long Mh = c.Pv & Xh;
+    c.score += (Ph & top) ? 1 : 0;
+    c.score -= (Mh & top) ? 1 : 0;
+    Ph = (Ph << 1) | anchored;                                      // (anchored: row 0 of the table charges the start, its horizontal difference is +1)
+    Mh <<= 1;
+    c.Pv = Mh | ~(Xv | Ph);
+    c.Mv = Ph & Xv;
+}
+
+__global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
+{
+    constexpr int NT = CCSX_ADAPTER_THREADS, CH = CCSX_ADAPTER_CHUNK, CAP = CCSX_ADAPTER_BUF, MAXS = 2 * CCSX_ADAPTER_MAX_PATTERNS, NH = CCSX_ADAPTER_MAX_HITS;
+    __shared__ unsigned long long sPeq[MAXS][4], sPeqR[MAXS][4];   // match masks of every search, and of its reversed pattern
+    __shared__ unsigned long long sBuf[CAP];                       // hit keys: end << 32 | search << 24 | dist << 16 | end - start
+    __shared__ int sSeg[NT][3];                                    // the zero-run scan's segments: leading zeros, trailing zeros, longest inner run
+    __shared__ int sM[MAXS];                                       // pattern lengths
+    __shared__ int sV[8];                                          // 0 n_hits, 1 first_start, 2 last_end, 3 min_dist, 4 covered, 5 buffered keys, 6 bound on the ends
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= P.n_zmw) return;
+    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    const size_t n = (size_t)P.n_zmw;
+    const int L = rfl(P.draft_len[z]);
+    const int words = (L + 31) >> 5;
+    int32_t *out = P.adapt_zi + z;
+    int32_t *list = P.adapt_hits + (size_t)z * NH * 3;
+    if (rfl(P.zstat[z]) != CCSX_SUCCESS || words > P.adapt_words) {  // untested (the second: a bounds guard, the bitmaps cover opts.max_length)
+        if (tid == 0) { out[0] = 0; out[n] = 0; out[2 * n] = 0; out[3 * n] = 0; out[4 * n] = 0; out[5 * n] = 0; out[6 * n] = -1; out[7 * n] = -1; out[8 * n] = 255; }
+        if (tid < NH * 3) list[tid] = 0;
+        return;
+    }
+    uint32_t *sUnion = dyn_lds, *sEnds = dyn_lds + P.adapt_words;   // bit b: draft base b is inside a hit / a hit ends at b + 1
+    const uint8_t *d = P.draft + P.seq_off[z];
+    const int S = 2 * P.adapt_n;
+    if (tid < S * 4) {
+        const int s = tid >> 2, code = tid & 3, a = s >> 1, m = P.adapt_len[a];
+        unsigned long long f = 0ull, r = 0ull;
+        for (int i = 0; i < m; ++i) {
+            const int q = (s & 1) ? m - 1 - i : i;
+            int b = (int)((P.adapt_seq[a][q >> 4] >> (2 * (q & 15))) & 3u);
+            if (s & 1) b = 3 - b;
+            if (b == code) { f |= 1ull << i; r |= 1ull << (m - 1 - i); }
+        }
+        sPeq[s][code] = f; sPeqR[s][code] = r;
+        if (code == 0) sM[s] = m;
+    }
+    for (int w = tid; w < words; w += NT) { sUnion[w] = 0u; sEnds[w] = 0u; }
+    if (tid == 0) { sV[0] = 0; sV[1] = 0x7fffffff; sV[2] = -1; sV[3] = 255; sV[4] = 0; sV[5] = 0; sV[6] = 0x7fffffff; }
+    __syncthreads();
+    const int nchunks = (L + CH - 1) / CH;
+    // every hit of this thread's (search, chunk) items that ends at or before `bound`: fn(start, end, search, dist)
+    auto scan = [&](int bound, auto fn) {
+        for (int it = tid; it < nchunks * S; it += NT) {
+            const int c = it / S, s = it - c * S;
+            const int lo = c * CH, hi = min(L, lo + CH);
+            if (lo >= bound) continue;                               // (its hits end beyond lo)
+            const int m = sM[s], k = m * P.adapt.max_dist_pct / 100;
+            const unsigned long long top = 1ull << (m - 1);
+            const unsigned long long e0 = sPeq[s][0], e1 = sPeq[s][1], e2 = sPeq[s][2], e3 = sPeq[s][3];
+            AdapterCol col{~0ull, 0ull, m};
+            bool prev = false, own = false, done = false;
+            int best = 0, end = 0;
+            // a closed run of this lane: its start by the anchored second pass
+            auto emit = [&]() {
+                if (end > bound) return;
+                AdapterCol rc{~0ull, 0ull, m};
+                const int xmax = min(end, m + best);
+                int x = 0;
+                while (x < xmax) {
+                    const int b = d[end - 1 - x] & 3;
+                    ++x;
+                    adapter_step(rc, sPeqR[s][b], top, 1ull);
+                    if (x >= m - best && rc.score == best) break;
+                }
+                fn(end - x, end, s, best);
+            };
+            int j = max(0, lo - (m + k));
+            while (j < L && !done) {
+                const int nb = min(8, L - j);
+                uint8_t ch[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) ch[q] = q < nb ? d[j + q] : (uint8_t)0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    if (q >= nb || done) continue;
+                    const int b = ch[q] & 3;
+                    adapter_step(col, b == 0 ? e0 : b == 1 ? e1 : b == 2 ? e2 : e3, top, 0ull);
+                    const int jj = j + q + 1;                       // E[jj] = col.score
+                    const bool ok = col.score <= k;
+                    if (jj > lo) {
+                        if (ok && !prev) { own = true; best = col.score; end = jj; }          // (jj <= hi: the lane stops at hi outside an owned run)
+                        else if (ok && own && col.score < best) { best = col.score; end = jj; }
+                        else if (!ok && prev && own) { emit(); own = false; }
+                        if (jj >= hi && !own) done = true;
+                    }
+                    prev = ok;
+                }
+                j += nb;
+            }
+            if (own) emit();                                         // (the run reaches the draft's end)
+        }
+    };
+    scan(0x7fffffff, [&](int start, int end, int s, int dist) {
+        atomicAdd(&sV[0], 1); atomicMin(&sV[1], start); atomicMax(&sV[2], end); atomicMin(&sV[3], dist);
+        for (int w = start >> 5; w <= (end - 1) >> 5; ++w) {
+            const int b0 = max(start, w << 5) & 31, b1 = min(end, (w + 1) << 5) - (w << 5);   // bits [b0, b1) of word w
+            atomicOr(&sUnion[w], (b1 == 32 ? 0xffffffffu : (1u << b1) - 1u) & ~((1u << b0) - 1u));
+        }
+        atomicOr(&sEnds[(end - 1) >> 5], 1u << ((end - 1) & 31));
+        const int i = atomicAdd(&sV[5], 1);
+        if (i < CAP) sBuf[i] = ((unsigned long long)end << 32) | ((unsigned long long)s << 24) | ((unsigned long long)dist << 16) | (unsigned long long)(end - start);
+    });
+    __syncthreads();
+    const int n_hits = sV[0];
+    if (n_hits > CAP) {                                              // the buffer overflowed: again, for the hits up to the 16th end
+        if (tid == 0) {
+            int seen = 0, bound = L;
+            for (int w = 0; w < words && seen < NH; ++w)
+                for (uint32_t v = sEnds[w]; v && seen < NH; v &= v - 1u)
+                    if (++seen == NH) bound = (w << 5) + __builtin_ctz(v) + 1;
+            sV[6] = bound; sV[5] = 0;
+        }
+        __syncthreads();
+        scan(sV[6], [&](int start, int end, int s, int dist) {
+            const int i = atomicAdd(&sV[5], 1);
+            if (i < CAP) sBuf[i] = ((unsigned long long)end << 32) | ((unsigned long long)s << 24) | ((unsigned long long)dist << 16) | (unsigned long long)(end - start);
+        });
+        __syncthreads();
+    }
+    // the list: the keys of rank < 16
+    const int nk = min(sV[5], CAP), n_listed = min(n_hits, NH);
+    for (int i = tid; i < nk; i += NT) {
+        const unsigned long long key = sBuf[i];
+        int rank = 0;
+        for (int q = 0; q < nk && rank < NH; ++q) rank += sBuf[q] < key ? 1 : 0;
+        if (rank < NH) {
+            const int end = (int)(key >> 32);
+            list[rank * 3] = end - (int)(key & 0xffffu); list[rank * 3 + 1] = end; list[rank * 3 + 2] = (int)((key >> 24) & 0xffu) | ((int)((key >> 16) & 0xffu) << 8);
+        }
+    }
+    if (tid < NH && tid >= n_listed) { list[tid * 3] = 0; list[tid * 3 + 1] = 0; list[tid * 3 + 2] = 0; }
+    // covered and max_gap from the union
+    int cov = 0;
+    for (int w = tid; w < words; w += NT) cov += __popc(sUnion[w]);
+    if (cov) atomicAdd(&sV[4], cov);
+    {
+        const int seg = (L + NT - 1) / NT, a = min(tid * seg, L), b = min(a + seg, L);
+        int lead = -1, run = 0, inner = 0;
+        for (int i = a; i < b; ++i) {
+            if ((sUnion[i >> 5] >> (i & 31)) & 1u) { if (lead < 0) lead = run; inner = max(inner, run); run = 0; }
+            else ++run;
+        }
+        sSeg[tid][0] = lead < 0 ? b - a : lead; sSeg[tid][1] = run; sSeg[tid][2] = lead < 0 ? -1 : inner;   // (-1: the segment has no covered base)
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0, gap = 0;
+        for (int t = 0; t < NT; ++t) {
+            if (sSeg[t][2] < 0) { run += sSeg[t][0]; continue; }
+            gap = max(gap, max(run + sSeg[t][0], sSeg[t][2]));
+            run = sSeg[t][1];
+        }
+        gap = max(gap, run);
+        const ccsx_adapter_opts &o = P.adapt;
+        const int first = n_hits ? sV[1] : -1, last = sV[2];
+        int v = 0;
+        if (n_hits >= o.min_copies && gap <= o.max_insert) v |= CCSX_ADAPTER_CONCAT;
+        if (n_hits >= 1 && (first <= o.end_slack || last >= L - o.end_slack)) v |= CCSX_ADAPTER_NEAR_END;
+        out[0] = 1; out[n] = v; out[2 * n] = n_hits; out[3 * n] = n_listed; out[4 * n] = sV[4]; out[5 * n] = gap; out[6 * n] = first; out[7 * n] = last;
+        out[8 * n] = sV[3];
+    }
+}
+
 // every launch status is captured: returns NULL, or the name of the first launch that failed (ccsx_api.cpp reports it)
 #define LAUNCH_CHECK(name) do { if (hipGetLastError() != hipSuccess && !failed) failed = name; } while (0)
 #define CALL_CHECK(fn, ...) do { if (fn(__VA_ARGS__) != hipSuccess && !failed) failed = #fn; } while (0)   // (a stream / event call)
@@ -4282,6 +4470,12 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
         hipLaunchKernelGGL(k_fold, dim3(P.n_zmw), dim3(CCSX_FOLD_THREADS), (size_t)P.fold_bins * 4, st, P);
         LAUNCH_CHECK("k_fold");
         trace_sync(st, "k_fold");
+    }
+    if (mode == CCSX_RUN_FUSED && P.adapt_zi) {
+        // the adapter screen (ccsx_submit_screen / ccsx_consensus_screen): as k_fold, on the draft stream and on the final drafts and statuses; writes its report only
+        hipLaunchKernelGGL(k_adapter, dim3(P.n_zmw), dim3(CCSX_ADAPTER_THREADS), (size_t)P.adapt_words * 8, st, P);
+        LAUNCH_CHECK("k_adapter");
+        trace_sync(st, "k_adapter");
     }
     if (mode == CCSX_RUN_FUSED && P.hd_zi) {
         // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft stage

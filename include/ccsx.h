@@ -416,6 +416,64 @@ int         ccsx_fold_rule_version(void);
 int         ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold);
 int         ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket);
 
+/* ---- adapter screen (docs/faq/fail-reads.md: fail classes 0x10 "adapter concatenation" and 0x40 "adapters close to either end"; the rule: DESIGN.md §2 "Adapter
+ * screen", its own version ccsx_adapter_rule_version).  SMRTbell adapter sequence the instrument's adapter finder missed sits inside the read the engine polishes.
+ * k_adapter searches the ZMW's final draft (what k_polish is given: pass-0 POA, fallback or last resort) for every caller-supplied adapter and its reverse
+ * complement by unit-cost edit distance (semi-global, bit-parallel); integer arithmetic only.  Detection only: every result byte equals the same call without the
+ * request.
+ *   ccsx_consensus_screen  synchronous (slot 0): ccsx_consensus_fold + the adapter request; either request may be NULL (both NULL = ccsx_consensus_extras).
+ *   ccsx_submit_screen     ticketed like ccsx_submit_fold: the reports' arrays follow the lifetime rule of `res` (written by the ticket's download) and should be
+ *                          page-locked; the request, set and options structs are read during the call only.
+ * A NULL report, a report sized for another batch, nonzero reserved words, options or pattern lengths out of range, a code above 3 or n_adapters outside 1 .. 8 are
+ * errors of the call: nothing is enqueued.  Without a request nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered.     */
+#define CCSX_ADAPTER_MAX_PATTERNS 8
+#define CCSX_ADAPTER_MIN_LEN      16
+#define CCSX_ADAPTER_MAX_LEN      64
+#define CCSX_ADAPTER_MAX_HITS     16
+#define CCSX_ADAPTER_CONCAT       1   /* verdict bit: n_hits >= min_copies and max_gap <= max_insert (fail class 0x10)                                          */
+#define CCSX_ADAPTER_NEAR_END     2   /* verdict bit: a hit starts within end_slack of the draft's start or ends within end_slack of its end (fail class 0x40)  */
+typedef struct ccsx_adapter_opts {
+    int32_t max_dist_pct;        /* a search of m bases matches at up to floor(m * max_dist_pct / 100) edits (0 .. 30)                                           */
+    int32_t min_copies;          /* CONCAT: at least this many hits (>= 1)                                                                                       */
+    int32_t max_insert;          /* CONCAT: no stretch of the draft outside every hit is longer than this (>= 0)                                                 */
+    int32_t end_slack;           /* NEAR_END: distance of a hit to an end of the draft (>= 0)                                                                    */
+} ccsx_adapter_opts;
+typedef struct ccsx_adapter_set {
+    int32_t n_adapters;          /* 1 .. CCSX_ADAPTER_MAX_PATTERNS; search 2a = adapter a as given, search 2a + 1 = its reverse complement                       */
+    int32_t len[CCSX_ADAPTER_MAX_PATTERNS];                        /* CCSX_ADAPTER_MIN_LEN .. CCSX_ADAPTER_MAX_LEN                                                */
+    uint8_t seq[CCSX_ADAPTER_MAX_PATTERNS][CCSX_ADAPTER_MAX_LEN];  /* codes 0 .. 3 (A C G T)                                                                      */
+} ccsx_adapter_set;
+typedef struct ccsx_adapter_hit {
+    int32_t start, end;          /* the shortest best match, draft[start, end)                                                                                   */
+    uint8_t search, dist, pad_[2];
+} ccsx_adapter_hit;
+typedef struct ccsx_adapter_report {
+    int32_t  n_zmw;
+    int32_t *tested;             /* [n_zmw] 1: the status after the cascade is SUCCESS (verdict 0 then means clean); 0: untested                                  */
+    int32_t *verdict;            /* [n_zmw] CCSX_ADAPTER_CONCAT | CCSX_ADAPTER_NEAR_END                                                                            */
+    int32_t *n_hits;             /* [n_zmw] hits of all searches (not capped)                                                                                      */
+    int32_t *n_listed;           /* [n_zmw] min(n_hits, CCSX_ADAPTER_MAX_HITS)                                                                                     */
+    int32_t *covered;            /* [n_zmw] draft bases inside a hit                                                                                               */
+    int32_t *max_gap;            /* [n_zmw] longest stretch of draft bases outside every hit (the draft's length without a hit)                                    */
+    int32_t *first_start;        /* [n_zmw] smallest start (-1 without a hit)                                                                                      */
+    int32_t *last_end;           /* [n_zmw] largest end (-1 without a hit)                                                                                         */
+    int32_t *min_dist;           /* [n_zmw] smallest dist (255 without a hit)                                                                                      */
+    ccsx_adapter_hit *hits;      /* [n_zmw * CCSX_ADAPTER_MAX_HITS] the first hits in increasing (end, search); zero beyond n_listed                               */
+} ccsx_adapter_report;
+typedef struct ccsx_adapter_request {
+    const ccsx_adapter_set  *adapters;
+    const ccsx_adapter_opts *opts;       /* NULL = ccsx_adapter_opts_default                                                                                     */
+    ccsx_adapter_report     *report;
+    int32_t                  reserved[2];   /* must be 0                                                                                                         */
+} ccsx_adapter_request;
+void        ccsx_adapter_opts_default(ccsx_adapter_opts *o);
+int         ccsx_adapter_rule_version(void);
+int         ccsx_adapter_set_default(ccsx_adapter_set *s);   /* the 45-base SMRTbell hairpin adapter; 0, or -1 for a NULL argument */
+int         ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
+                                  const ccsx_adapter_request *adapters);
+int         ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
+                               const ccsx_adapter_request *adapters, ccsx_ticket *ticket);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
