@@ -1174,8 +1174,24 @@ int orc_polish_window(const float *ME, const float *INS, const float *DL,
                       uint8_t *out_seq, float *out_perr, float *out_qv, int32_t *out_len,
                       int32_t *out_nvalid, int32_t *out_nonconv, float *out_delta /* [256] optional */)
 {
+    g_perr_floor = perr_floor_of(0);     /* a stage entry point reports with the default floor, whatever whole-ZMW call ran last on this thread */
     return polish_window_impl(ME, INS, DL, tpl, J0, cs, ce, lf, rf, nreads, obs, I, strand, 0u, NULL, NULL, NULL, 0.0f, out_seq, out_perr, out_qv,
                               out_len, out_nvalid, out_nonconv, out_delta, NULL, NULL);
+}
+/* the same with the reporting floor of opts.max_qv (<= 0: the default) and, qv_only != 0, one scoring round without applying anything (CCSX_QV_ONLY);
+ * the floor is back at its default and qv_only off when it returns */
+int orc_polish_window_qv(const float *ME, const float *INS, const float *DL,
+                      const uint8_t *tpl, int J0, int cs, int ce, int lf, int rf,
+                      int nreads, const uint8_t *const *obs, const int32_t *I, const uint8_t *strand, int max_qv, int qv_only,
+                      uint8_t *out_seq, float *out_perr, float *out_qv, int32_t *out_len,
+                      int32_t *out_nvalid, int32_t *out_nonconv, float *out_delta /* [256] optional */)
+{
+    const int qv0 = g_qv_only;
+    g_perr_floor = perr_floor_of(max_qv); g_qv_only = qv_only;
+    int it = polish_window_impl(ME, INS, DL, tpl, J0, cs, ce, lf, rf, nreads, obs, I, strand, 0u, NULL, NULL, NULL, 0.0f, out_seq, out_perr, out_qv,
+                                out_len, out_nvalid, out_nonconv, out_delta, NULL, NULL);
+    g_perr_floor = perr_floor_of(0); g_qv_only = qv0;
+    return it;
 }
 /* the same with the candidate filter: ev0 bit c = position c may be skipped, skip_p[c] its reported p_err */
 int orc_polish_window_ev(const float *ME, const float *INS, const float *DL,
@@ -1185,6 +1201,7 @@ int orc_polish_window_ev(const float *ME, const float *INS, const float *DL,
                       uint8_t *out_seq, float *out_perr, float *out_qv, int32_t *out_len,
                       int32_t *out_nvalid, int32_t *out_nonconv, float *out_delta /* [256] optional */)
 {
+    g_perr_floor = perr_floor_of(0);
     return polish_window_impl(ME, INS, DL, tpl, J0, cs, ce, lf, rf, nreads, obs, I, strand, ev0, skip_p, NULL, NULL, 0.0f, out_seq, out_perr, out_qv,
                               out_len, out_nvalid, out_nonconv, out_delta, NULL, NULL);
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/golden_v7.npz: inputs + expected outputs of the hot path at SPEC version 7.  Round 5 made two steps: v6 = the banded alpha /
+"""Generates tests/golden/golden_v8.npz: inputs + expected outputs of the hot path at SPEC version 8.  Round 5 made two steps: v6 = the banded alpha /
 beta fill — every array of golden_v6.npz equalled its counterpart in round 4's golden_v5.npz (the band is exactly free, profiles/r05_band_study.txt; `--compare
 OLD.npz` checks such a claim) — and v7 = honest QVs (skip-probability floor Q50, repeat-count floor): against v6 only qual / raw_qv / rq (and the statuses that
 follow from rq) change, sequences, np, ec, iterations and windows do not (`--compare OLD.npz --qv-only`).

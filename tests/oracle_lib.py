@@ -92,8 +92,17 @@ def windows(draft):
     return b[: n + 1].copy()
 
 
-def polish_window(ME, INS, DL, tpl, cs, ce, lf, rf, obs_list, strand):
-    """obs_list[r]: uint8 array of native-orientation obs codes, or None if the read is unusable here."""
+def zparams(model, snr):
+    """A7: (MU[16], VAR[16]) of the z-score gate for one ZMW (orc_zparams)"""
+    MU, VAR = np.zeros(NCTX, np.float32), np.zeros(NCTX, np.float32)
+    snr = np.ascontiguousarray(snr, np.float32)
+    lib().orc_zparams(C.byref(model), _p(snr, C.c_float), _p(MU, C.c_float), _p(VAR, C.c_float))
+    return MU, VAR
+
+
+def polish_window(ME, INS, DL, tpl, cs, ce, lf, rf, obs_list, strand, max_qv=None, qv_only=False):
+    """obs_list[r]: uint8 array of native-orientation obs codes, or None if the read is unusable here.
+    max_qv / qv_only: through orc_polish_window_qv (the reporting floor of opts.max_qv; one scoring round, nothing applied)."""
     n = len(obs_list)
     tpl = np.ascontiguousarray(tpl, np.uint8)
     bufs = [np.ascontiguousarray(o if o is not None else np.zeros(1, np.uint8), np.uint8) for o in obs_list]
@@ -105,10 +114,13 @@ def polish_window(ME, INS, DL, tpl, cs, ce, lf, rf, obs_list, strand):
     qv = np.zeros(JMAX + 1, np.float32)
     ln, nv, nc = C.c_int32(), C.c_int32(), C.c_int32()
     delta = np.zeros(256, np.float32)
-    it = lib().orc_polish_window(_p(ME, C.c_float), _p(INS, C.c_float), _p(DL, C.c_float), _p(tpl, C.c_uint8), len(tpl),
-                                 int(cs), int(ce), int(lf), int(rf), n, ptrs, _p(I, C.c_int32), _p(st, C.c_uint8), _p(seq, C.c_uint8),
-                                 _p(perr, C.c_float), _p(qv, C.c_float), C.byref(ln), C.byref(nv), C.byref(nc),
-                                 _p(delta, C.c_float))
+    head = (_p(ME, C.c_float), _p(INS, C.c_float), _p(DL, C.c_float), _p(tpl, C.c_uint8), len(tpl),
+            int(cs), int(ce), int(lf), int(rf), n, ptrs, _p(I, C.c_int32), _p(st, C.c_uint8))
+    tail = (_p(seq, C.c_uint8), _p(perr, C.c_float), _p(qv, C.c_float), C.byref(ln), C.byref(nv), C.byref(nc), _p(delta, C.c_float))
+    if max_qv is None and not qv_only:
+        it = lib().orc_polish_window(*head, *tail)
+    else:
+        it = lib().orc_polish_window_qv(*head, int(max_qv or 0), int(bool(qv_only)), *tail)
     k = ln.value
     return dict(seq=seq[:k].copy(), perr=perr[:k].copy(), qv=qv[:k].copy(), nvalid=nv.value, nonconv=nc.value,
                 iters=it, delta=delta)

@@ -709,7 +709,10 @@ def test_fallback_draft_matches_oracle(built):
         else:
             ok = set(np.nonzero((res.status == 0) | (res.status == 7))[0].tolist())
         h.close()
-    assert len(lost) >= 2 and lost <= ok                      # what is lost without the fallback gets a consensus with it (HiFi or LOW_RQ)@pytest.mark.gpu
+    assert len(lost) >= 2 and lost <= ok                      # what is lost without the fallback gets a consensus with it (HiFi or LOW_RQ)
+
+
+@pytest.mark.gpu
 def test_split_alignment_keeps_passes_with_large_blocks(handle):
     """SPEC "split alignment" on the GPU (k_rescue): passes with a 60 / 150 / 400 base foreign block fail the banded alignment, are
     split into prefix + insertion + suffix, keep serving every window (the block is trimmed in its window) — np counts them, the
