@@ -872,6 +872,31 @@ def _extras(cp: "CPileup | None", tandem: "np.ndarray | None", min_len: int) -> 
     return ex
 
 
+def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None, min_tandem_repeat_length: int = 0,
+              hd: "HdReport | None" = None, hd_opts: "HdOpts | None" = None, hd_split: bool = False,
+              fold: "FoldReport | None" = None, fold_opts: "FoldOpts | None" = None,
+              adapters: "AdapterReport | None" = None, adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None):
+    """The ctypes side of what one fused run is asked for beside the consensus: (CExtras, CHdRequest, CFoldRequest, CAdapterRequest, keep), each request None
+    where its report (for the extras: all of pileup, tandem and the threshold) is.  keep owns every array and struct the requests point to: it must
+    outlive the call, or the ticket"""
+    keep = [pileup, tandem, hd, fold, adapters]
+
+    def own(x):
+        keep.append(x)
+        return x
+    ex = hq = fq = aq = None
+    if pileup is not None or tandem is not None or min_tandem_repeat_length:
+        ex = own(_extras(own(pileup.c_struct()) if pileup is not None else None, tandem, min_tandem_repeat_length))
+    if hd is not None:
+        o = own(hd_opts if hd_opts is not None else hd_opts_default())
+        hq = own(CHdRequest(C.pointer(o), C.pointer(own(hd.c_struct())), int(bool(hd_split)), 0))
+    if fold is not None:
+        fq = own(_fold_request(fold_opts, own(fold.c_struct())))[0]
+    if adapters is not None:
+        aq = own(_adapter_request(adapter_set, adapter_opts, own(adapters.c_struct())))[0]
+    return ex, hq, fq, aq, keep
+
+
 class Handle:
     """One consensus engine bound to one GPU (ccsx_create).  Not thread-safe: one per worker per GPU."""
 
@@ -924,18 +949,19 @@ class Handle:
         self._check(self._L.ccsx_consensus_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp)), "ccsx_consensus_pileup")
         return res, pile
 
+    def _outputs(self, batch: Batch, tandem: bool, pileup: bool):
+        """what a synchronous fused run fills: (results, tandem_len or None, pileup or None)"""
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        return res, tandem_buffer(batch.n_zmw) if tandem else None, Pileup.allocate(res) if pileup else None
+
     # ---- optional outputs through ccsx_extras: tandem-repeat detection (DESIGN.md §2 "Tandem repeats") and / or the pileup summary
     def consensus_extras(self, batch: Batch, tandem: bool = True, min_tandem_repeat_length: int = 0,
                          pileup: bool = False) -> tuple["Results", "np.ndarray | None", "Pileup | None"]:
         """ccsx_consensus_extras: (results, tandem_len [n_zmw] int32 or None, pileup or None).  min_tandem_repeat_length > 0: ZMWs whose deciding
         draft has a masked run at least that long run with the heuristics off (as opts.disable_heuristics), the others as usual"""
-        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
-        tl = tandem_buffer(batch.n_zmw) if tandem else None
-        pile = Pileup.allocate(res) if pileup else None
-        cb, cr = batch.c_struct(), res.c_struct()
-        cp = pile.c_struct() if pile is not None else None
-        ex = _extras(cp, tl, min_tandem_repeat_length)
-        self._check(self._L.ccsx_consensus_extras(self._h, C.byref(cb), C.byref(cr), C.byref(ex)), "ccsx_consensus_extras")
+        res, tl, pile = self._outputs(batch, tandem, pileup)
+        ex, _, _, _, _keep = _requests(pile, tl, min_tandem_repeat_length)
+        self._check(self._L.ccsx_consensus_extras(self._h, batch.c_struct(), res.c_struct(), ex), "ccsx_consensus_extras")
         return res, tl, pile
 
     # ---- the heteroduplex finder in the fused path (ccsx_consensus_hd): the consensus and the finder's report of one run
@@ -943,25 +969,18 @@ class Handle:
                      pileup: bool = False) -> tuple["Results", HdReport, "np.ndarray | None", "Pileup | None"]:
         """(results, report, tandem_len or None, pileup or None).  split=True: a HETERODUPLEX ZMW is not polished (status HETERODUPLEX, no consensus);
         split=False: detection only, the results are those of consensus_extras"""
-        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        res, tl, pile = self._outputs(batch, tandem, pileup)
         rep = HdReport.allocate(batch.n_zmw)
-        tl = tandem_buffer(batch.n_zmw) if tandem else None
-        pile = Pileup.allocate(res) if pileup else None
-        cb, cr, crep = batch.c_struct(), res.c_struct(), rep.c_struct()
-        cp = pile.c_struct() if pile is not None else None
-        ex = _extras(cp, tl, min_tandem_repeat_length) if (tandem or pileup or min_tandem_repeat_length) else None
-        o = opts if opts is not None else hd_opts_default()
-        q = CHdRequest(C.pointer(o), C.pointer(crep), int(bool(split)), 0)
-        self._check(self._L.ccsx_consensus_hd(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q)), "ccsx_consensus_hd")
+        ex, q, _, _, _keep = _requests(pile, tl, min_tandem_repeat_length, hd=rep, hd_opts=opts, hd_split=split)
+        self._check(self._L.ccsx_consensus_hd(self._h, batch.c_struct(), res.c_struct(), ex, q), "ccsx_consensus_hd")
         return res, rep, tl, pile
 
     # ---- adapter palindromes in the fused path (ccsx_consensus_fold): the consensus and the detector's report of one run (detection only)
     def consensus_fold(self, batch: Batch, opts: FoldOpts | None = None) -> tuple["Results", FoldReport]:
         res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
         rep = FoldReport.allocate(batch.n_zmw)
-        cb, cr, crep = batch.c_struct(), res.c_struct(), rep.c_struct()
-        q, _o = _fold_request(opts, crep)
-        self._check(self._L.ccsx_consensus_fold(self._h, C.byref(cb), C.byref(cr), None, C.byref(q)), "ccsx_consensus_fold")
+        _, _, q, _, _keep = _requests(fold=rep, fold_opts=opts)
+        self._check(self._L.ccsx_consensus_fold(self._h, batch.c_struct(), res.c_struct(), None, q), "ccsx_consensus_fold")
         return res, rep
 
     # ---- both draft detectors in one run (ccsx_consensus_screen): adapter palindromes and / or the adapter screen, with the optional outputs of ccsx_extras
@@ -969,23 +988,12 @@ class Handle:
                          tandem: bool = False, min_tandem_repeat_length: int = 0, pileup: bool = False):
         """(results, fold report or None, adapter report or None, tandem_len or None, pileup or None).  fold: True or a FoldOpts asks for the palindrome
         report; adapters: an AdapterSet asks for the adapter screen (AdapterSet.default() = the SMRTbell hairpin), opts its AdapterOpts.  Detection only"""
-        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
-        tl = tandem_buffer(batch.n_zmw) if tandem else None
-        pile = Pileup.allocate(res) if pileup else None
-        cb, cr = batch.c_struct(), res.c_struct()
-        cp = pile.c_struct() if pile is not None else None
-        ex = _extras(cp, tl, min_tandem_repeat_length) if (tandem or pileup or min_tandem_repeat_length) else None
-        frep = arep = fq = aq = None
-        if fold:
-            frep = FoldReport.allocate(batch.n_zmw)
-            cfr = frep.c_struct()
-            fq, _fo = _fold_request(fold if isinstance(fold, FoldOpts) else None, cfr)
-        if adapters is not None:
-            arep = AdapterReport.allocate(batch.n_zmw)
-            car = arep.c_struct()
-            aq, _ao = _adapter_request(adapters, opts, car)
-        self._check(self._L.ccsx_consensus_screen(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None,
-                                                  C.byref(fq) if fq is not None else None, C.byref(aq) if aq is not None else None), "ccsx_consensus_screen")
+        res, tl, pile = self._outputs(batch, tandem, pileup)
+        frep = FoldReport.allocate(batch.n_zmw) if fold else None
+        arep = AdapterReport.allocate(batch.n_zmw) if adapters is not None else None
+        ex, _, fq, aq, _keep = _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
+                                         adapters=arep, adapter_set=adapters, adapter_opts=opts)
+        self._check(self._L.ccsx_consensus_screen(self._h, batch.c_struct(), res.c_struct(), ex, fq, aq), "ccsx_consensus_screen")
         return res, frep, arep, tl, pile
 
     def stage_polished(self, z: int):
@@ -1031,55 +1039,31 @@ class Handle:
         stage (ccsx_submit_hd).  fold: a report (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts (ccsx_submit_fold;
         not combined with hd).  adapters: a report (AdapterReport.allocate(n, pinned=True)) that receives the adapter screen of adapter_set (None: the built-in
         set) under adapter_opts, alone or together with fold (ccsx_submit_screen; not combined with hd)"""
-        cb, cr = batch.c_struct(), res.c_struct()
-        t = C.c_int64()
-        ex = None
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
             raise ValueError("the heteroduplex and the adapter-palindrome requests are not combined")
         if hd is not None and adapters is not None:
             raise ValueError("the heteroduplex request and the adapter screen are not combined")
-        if adapters is not None:
-            cp = pileup.c_struct() if pileup is not None else None
-            ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
-            cfr = fold.c_struct() if fold is not None else None
-            fq = _fold_request(fold_opts, cfr) if fold is not None else None
-            car = adapters.c_struct()
-            aq = _adapter_request(adapter_set, adapter_opts, car)
-            self._check(self._L.ccsx_submit_screen(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None,
-                                                   C.byref(fq[0]) if fq is not None else None, C.byref(aq[0]), C.byref(t)), "ccsx_submit_screen")
-            ex = (ex, cfr, fq, fold, car, aq, adapters)
-        elif fold is not None:
-            cp = pileup.c_struct() if pileup is not None else None
-            ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
-            crep = fold.c_struct()
-            q, o = _fold_request(fold_opts, crep)
-            self._check(self._L.ccsx_submit_fold(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q), C.byref(t)),
-                        "ccsx_submit_fold")
-            ex = (ex, o, crep, q, fold)
-        elif hd is not None:
-            cp = pileup.c_struct() if pileup is not None else None
-            ex = _extras(cp, tandem, min_tandem_repeat_length) if (tandem is not None or pileup is not None or min_tandem_repeat_length) else None
-            o = hd_opts if hd_opts is not None else hd_opts_default()
-            crep = hd.c_struct()
-            q = CHdRequest(C.pointer(o), C.pointer(crep), int(bool(hd_split)), 0)
-            self._check(self._L.ccsx_submit_hd(self._h, C.byref(cb), C.byref(cr), C.byref(ex) if ex is not None else None, C.byref(q), C.byref(t)),
-                        "ccsx_submit_hd")
-            ex = (ex, o, crep, q, hd)
+        ex, hq, fq, aq, keep = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts)
+        # the narrowest entry point that expresses the request (so that every exported ccsx_submit_* is in use)
+        if aq is not None:
+            name, extra = "ccsx_submit_screen", (ex, fq, aq)
+        elif fq is not None:
+            name, extra = "ccsx_submit_fold", (ex, fq)
+        elif hq is not None:
+            name, extra = "ccsx_submit_hd", (ex, hq)
         elif tandem is not None or min_tandem_repeat_length:
-            cp = pileup.c_struct() if pileup is not None else None
-            ex = _extras(cp, tandem, min_tandem_repeat_length)
-            self._check(self._L.ccsx_submit_extras(self._h, C.byref(cb), C.byref(cr), C.byref(ex), C.byref(t)), "ccsx_submit_extras")
-        elif pileup is None:
-            self._check(self._L.ccsx_submit(self._h, C.byref(cb), C.byref(cr), C.byref(t)), "ccsx_submit")
-            cp = None
+            name, extra = "ccsx_submit_extras", (ex,)
+        elif pileup is not None:
+            name, extra = "ccsx_submit_pileup", (ex.pile,)
         else:
-            cp = pileup.c_struct()
-            self._check(self._L.ccsx_submit_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp), C.byref(t)), "ccsx_submit_pileup")
+            name, extra = "ccsx_submit", ()
+        cb, cr, t = batch.c_struct(), res.c_struct(), C.c_int64()
+        self._check(getattr(self._L, name)(self._h, cb, cr, *extra, t), name)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
-        self._inflight[t.value] = (batch, res, cb, cr, pileup, cp, tandem, ex)      # the C structs and arrays must outlive the ticket
+        self._inflight[t.value] = (batch, res, cb, cr, keep)      # the C structs and arrays must outlive the ticket
         return t.value
 
     def wait(self, ticket: int) -> "Results":

@@ -341,6 +341,25 @@ int ccsx_destroy(ccsx_handle h)
     return 0;
 }
 
+// What a fused run carries beside the consensus: the optional outputs of a ccsx_extras and the three requests, already checked and copied (build_wants).
+// An empty one asks for nothing.
+struct Wants {
+    ccsx_pileup *pile = nullptr;
+    int32_t *tandem_len = nullptr; bool tandem = false; int min_tandem = 0;   // tandem: k_sdust runs (a length array to fill, or a threshold > 0)
+    const ccsx_hd_request *hd = nullptr; ccsx_hd_opts hd_opts{};
+    const ccsx_fold_request *fold = nullptr; ccsx_fold_opts fold_opts{};
+    const ccsx_adapter_request *adapters = nullptr; ccsx_adapter_set adapter_set{}; ccsx_adapter_opts adapter_opts{};
+};
+
+// the longest draft of a slot's batch that can reach status SUCCESS (that needs length <= opts.max_length, and no draft exceeds its slot), at least `floor`:
+// what the LDS of k_sdust, k_fold and k_adapter is sized for
+static int64_t longest_draft(ccsx_handle h, const Slot &S, int32_t floor)
+{
+    int64_t longest = floor;
+    for (size_t z = 0; z < S.dcap.size(); ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
+    return std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, floor));
+}
+
 static int validate(const ccsx_batch *b)
 {
     if (!b || b->n_zmw <= 0 || !b->read_off || !b->base_off || !b->bases || !b->pw || !b->flags || !b->snr) {
@@ -367,11 +386,12 @@ static int validate(const ccsx_batch *b)
 
 // Stage a batch into a slot: host-derived layout, device buffers, H2D copies enqueued on `st` (nothing waits here except
 // hipMalloc growth).  The batch's own arrays must stay valid until the copies have run (pinned arrays copy by DMA).
-// pile: this run also computes the pileup summary (its buffers are reserved and its pointers set only then).
-// tandem: it also runs tandem-repeat detection (k_sdust), flagging ZMWs at min_tandem > 0 (the same rule for its buffers and pointers).
-static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bool pile = false, bool tandem = false, int min_tandem = 0)
+// W.pile: this run also computes the pileup summary (its buffers are reserved and its pointers set only then).
+// W.tandem: it also runs tandem-repeat detection (k_sdust), flagging ZMWs at W.min_tandem > 0 (the same rule for its buffers and pointers).
+static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, const Wants &W)
 {
     if (validate(b)) return -1;
+    const bool pile = W.pile != nullptr, tandem = W.tandem;
     const bool kin = h->opts.hifi_kinetics != 0;
     if (kin && !b->ipd) { ccsx_set_error("ccsx_upload: opts.hifi_kinetics needs batch.ipd"); return -1; }
     const int n = b->n_zmw, R = b->n_reads;
@@ -441,10 +461,7 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bo
     if (total_wslots > 0x7fff0000ll) { ccsx_set_error("ccsx_upload: batch too large (more than 2^31 window slots): split it"); return -1; }
     int32_t sdust_words = 0;
     if (tandem) {
-        // k_sdust's LDS mask covers the longest draft the cascade aligns: status SUCCESS needs length <= opts.max_length, and no draft exceeds its slot
-        int64_t longest = 16;
-        for (int z = 0; z < n; ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
-        longest = std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, 16));
+        const int64_t longest = longest_draft(h, S, 16);      // k_sdust's LDS mask covers the longest draft the cascade aligns
         sdust_words = (int32_t)((longest + 31) / 32);
         if ((int64_t)CCSX_SDUST_TABLE_BYTES + 4 * (int64_t)sdust_words > 160 * 1024) {
             ccsx_set_error("tandem-repeat detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than a CU has (lower opts.max_length)");
@@ -589,7 +606,7 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, bo
         P.out_kin = (uint8_t *)S.d_out_kin.p; P.kin_plane = cap_total;
     }
     if (pile) { P.wpile = (uchar4 *)S.d_wpile.p; P.out_pile = (uint8_t *)S.d_out_pile.p; P.pile_plane = cap_total; }
-    if (tandem) { P.tflag = (int32_t *)S.d_tflag.p; P.tlen = (int32_t *)S.d_tlen.p; P.min_tandem = min_tandem; P.sdust_words = sdust_words; }
+    if (tandem) { P.tflag = (int32_t *)S.d_tflag.p; P.tlen = (int32_t *)S.d_tlen.p; P.min_tandem = W.min_tandem; P.sdust_words = sdust_words; }
     float *of = (float *)S.d_out_f32.p;
     P.out_rq = of; P.out_ec = of + n;
     S.staged = true; S.ran = false; S.tm_ok = false;
@@ -805,14 +822,12 @@ static int fold_request_check(const ccsx_fold_request *q, const ccsx_batch *b, c
     return 0;
 }
 
-// k_fold's LDS histogram covers the longest draft the cascade aligns (status SUCCESS needs length <= opts.max_length, and no draft exceeds its slot); -1 when
-// that is beyond its LDS bound (nothing enqueued yet by this call's request)
+// k_fold's LDS histogram covers the longest draft the cascade aligns (longest_draft); -1 when that is beyond its LDS bound (nothing enqueued yet by this
+// call's request)
 static int fold_attach(ccsx_handle h, Slot &S, const ccsx_fold_opts &o)
 {
     const int n = S.P.n_zmw;
-    int64_t longest = 16;
-    for (int z = 0; z < n; ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
-    longest = std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, 16));
+    const int64_t longest = longest_draft(h, S, 16);
     const int64_t bins = ((2 * longest - CCSX_FOLD_K - 1) >> 6) + 2;
     if (bins > CCSX_FOLD_MAX_BINS) { ccsx_set_error("adapter-palindrome detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
     if (S.d_fold.reserve((size_t)n * 16)) return -2;
@@ -853,15 +868,13 @@ static int adapter_request_check(const ccsx_adapter_request *q, const ccsx_batch
     return 0;
 }
 
-// k_adapter's two LDS bitmaps are sized from the longest draft the cascade aligns (status SUCCESS needs length <= opts.max_length, and no draft exceeds its
-// slot), so a handle opened with a larger max_length gets larger bitmaps; -1 when that is beyond their LDS bound (nothing enqueued yet by this call's request)
+// k_adapter's two LDS bitmaps are sized from the longest draft the cascade aligns (longest_draft), so a handle opened with a larger max_length gets larger
+// bitmaps; -1 when that is beyond their LDS bound (nothing enqueued yet by this call's request)
 static int adapter_attach(ccsx_handle h, Slot &S, const ccsx_adapter_set &set, const ccsx_adapter_opts &o)
 {
     static_assert(sizeof(ccsx_adapter_hit) == 12, "k_adapter writes a hit as three words");
     const int n = S.P.n_zmw;
-    int64_t longest = 32;
-    for (int z = 0; z < n; ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
-    longest = std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, 32));
+    const int64_t longest = longest_draft(h, S, 32);
     const int64_t words = (longest + 31) >> 5;
     if (words > CCSX_ADAPTER_MAX_WORDS) { ccsx_set_error("adapter screen: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
     if (S.d_adapt.reserve((size_t)n * (9 * 4 + CCSX_ADAPTER_MAX_HITS * sizeof(ccsx_adapter_hit)))) return -2;
@@ -884,7 +897,6 @@ static int enqueue_adapter_download(const Slot &S, ccsx_adapter_report *r, hipSt
     return 0;
 }
 
-// one batch through the handle's pipeline: the fused path (ccsx_submit), the draft seam or the polish seam
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
@@ -895,20 +907,53 @@ static int extras_want(const ccsx_extras *ex, bool *tandem)
     return 0;
 }
 
-static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
-                       const ccsx_extras *ex = nullptr, const ccsx_hd_request *hdq = nullptr, const ccsx_fold_request *fq = nullptr, const ccsx_adapter_request *aq = nullptr,
-                       const char *fn = "ccsx_submit_fold")
+static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string(fn) + ": " + what); return -1; }
+
+// The Wants of one call of the exported function `fn` (NULL extras or request: none of it).  Enqueues nothing and needs no handle: the requests are checked
+// first, each refused by its own message, then the extras; the caller's null-argument check follows (without a batch there is nothing to measure a report
+// against, and that check refuses the call).
+static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters, const ccsx_batch *b,
+                       const char *fn, Wants *W)
 {
-    bool tandem = false;
-    if (extras_want(ex, &tandem)) return -1;
-    ccsx_pileup *pile = ex ? ex->pile : nullptr;
-    ccsx_hd_opts hdo{};
-    if (hdq && b && hd_request_check(hdq, b, &hdo, "ccsx_submit_hd")) return -1;   // (the request is checked with or without a handle)
-    ccsx_fold_opts fo{};
-    if (fq && b && fold_request_check(fq, b, &fo, fn)) return -1;
-    ccsx_adapter_set aset; ccsx_adapter_opts ao{};
-    if (aq && b && adapter_request_check(aq, b, &aset, &ao, fn)) return -1;
-    if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) { ccsx_set_error("ccsx_submit: null argument"); return -1; }
+    *W = Wants{};
+    if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
+    if (fold && b && fold_request_check(fold, b, &W->fold_opts, fn)) return -1;
+    if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
+    if (extras_want(ex, &W->tandem)) return -1;
+    W->hd = hd; W->fold = fold; W->adapters = adapters;
+    if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
+    return 0;
+}
+
+// What W asks for on a staged slot: checks, buffers and pointers, in the order of what can still be refused.  -1 only while this call has enqueued nothing
+// (the pileup planes, the LDS bounds of k_fold and k_adapter), -2 otherwise; the one step that enqueues (the finder's memset, on `st`) comes last.
+static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
+{
+    int rc;
+    if (W.pile && (rc = check_pile(S, W.pile))) return rc;
+    if (W.fold && (rc = fold_attach(h, S, W.fold_opts))) return rc;
+    if (W.adapters && (rc = adapter_attach(h, S, W.adapter_set, W.adapter_opts))) return rc;
+    if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
+    return 0;
+}
+
+// everything W receives beside the ccsx_results, copied on `s`
+static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
+{
+    int rc;
+    if (W.pile && (rc = enqueue_pile_download(S, W.pile, s))) return rc;
+    if (W.tandem_len) HIPTRY(hipMemcpyAsync(W.tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, s));
+    if (W.hd && (rc = enqueue_hd_download(S, W.hd->report, s))) return rc;
+    if (W.fold && (rc = enqueue_fold_download(S, W.fold->report, s))) return rc;
+    if (W.adapters && (rc = enqueue_adapter_download(S, W.adapters->report, s))) return rc;
+    return 0;
+}
+
+// one batch through the handle's pipeline: the fused path (ccsx_submit and its variants, with their Wants), the draft seam or the polish seam
+static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
+                       const Wants &W, const char *fn)
+{
+    if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) return refuse(fn, "null argument");
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
     if (const char *e = std::getenv("CCSX_TEST_FAIL_SUBMIT"))        // fault injection for the driver's error-path test
         if (std::atoll(e) == (long long)h->next_ticket) { ++h->next_ticket; ccsx_set_error("injected failure (CCSX_TEST_FAIL_SUBMIT)"); return -2; }
@@ -918,7 +963,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     if (int rc0 = rebase_epoch(h)) return rc0;
     Slot &S = h->slot[h->next_ticket % CCSX_SLOTS];
     if (int rc0 = retire(h, S)) return rc0;              // (a batch never waited for: the caller's buffers are complete whether or not it ever waits)
-    if (hdq) if (int rc0 = hd_table(h)) return rc0;      // (before anything of this ticket is enqueued)
+    if (W.hd) if (int rc0 = hd_table(h)) return rc0;     // (its synchronous copy before anything of this ticket is enqueued; attach() then finds it built)
     // A failure after the first enqueue must not leave copies or kernels running on a slot the next submit would rewrite
     // (ADVICE r02): drain every stream, mark the slot unusable and refuse further batches on this handle.
     auto fail = [&](int rc_) {
@@ -928,18 +973,16 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         h->poisoned = true;
         return rc_;
     };
-    int rc = stage(h, S, b, h->s_in, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0);
+    auto unstage = [&](int rc_) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc_; };   // refused after staging, before anything else was enqueued
+    int rc = stage(h, S, b, h->s_in, W);
     if (rc) return rc == -1 ? (S.staged = false, rc) : fail(rc);     // -1: rejected by validation before anything was enqueued
-    if (mode != CCSX_RUN_DRAFT && (rc = check_results(S, res, S.P.out_kin != nullptr))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
-    if (pile && (rc = check_pile(S, pile))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
-    if (mode != CCSX_RUN_FUSED && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc; }
-    if (fq && (rc = fold_attach(h, S, fo))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc == -1 ? rc : fail(rc); }
-    if (aq && (rc = adapter_attach(h, S, aset, ao))) { (void)hipStreamSynchronize(h->s_in); S.staged = false; return rc == -1 ? rc : fail(rc); }
+    if (mode != CCSX_RUN_DRAFT && (rc = check_results(S, res, S.P.out_kin != nullptr))) return unstage(rc);
+    if (mode != CCSX_RUN_FUSED && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) return unstage(rc);
+    if ((rc = attach(h, S, W, h->s_in))) return rc == -1 ? unstage(rc) : fail(rc);
     S.mode = mode;
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
 #define HIPTRY_F(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(-2); } } while (0)
     if (mode == CCSX_RUN_POLISH && (rc = upload_drafts(S, dr_in, h->s_in))) return fail(rc);
-    if (hdq && (rc = hd_attach(h, S, hdo, hdq->split, h->s_in))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_up, h->s_in));
     HIPTRY_F(hipStreamWaitEvent(h->s_draft, S.ev_up, 0));
     if ((rc = launch(h, S))) return fail(rc);
@@ -955,11 +998,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         if (dr_out->n_windows) HIPTRY_F(hipMemcpyAsync(dr_out->n_windows, P.nwin, (size_t)n * 4, hipMemcpyDeviceToHost, h->s_out));
         if (dr_out->win_bounds) HIPTRY_F(hipMemcpyAsync(dr_out->win_bounds, P.wbounds, (size_t)S.wb_off[n] * 4, hipMemcpyDeviceToHost, h->s_out));
     } else if ((rc = enqueue_download(S, res, h->s_out))) return fail(rc);
-    if (pile && (rc = enqueue_pile_download(S, pile, h->s_out))) return fail(rc);
-    if (tandem && ex->tandem_len) HIPTRY_F(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_out));
-    if (hdq && (rc = enqueue_hd_download(S, hdq->report, h->s_out))) return fail(rc);
-    if (fq && (rc = enqueue_fold_download(S, fq->report, h->s_out))) return fail(rc);
-    if (aq && (rc = enqueue_adapter_download(S, aq->report, h->s_out))) return fail(rc);
+    if ((rc = enqueue_wants_download(S, W, h->s_out))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -968,42 +1007,50 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     return 0;
 }
 
+// the fused entry points: the Wants of the call (requests, then extras), the argument this entry point may not be given as NULL, the submit
 int ccsx_submit(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket)
 {
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0);
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, Wants{}, __func__);
 }
 int ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile, ccsx_ticket *ticket)
 {
-    if (!pile) { ccsx_set_error("ccsx_submit_pileup: null argument"); return -1; }
     const ccsx_extras ex = {pile, nullptr, 0, 0};
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, &ex);
+    Wants W;
+    if (build_wants(&ex, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket)
 {
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex);
+    Wants W;
+    if (build_wants(ex, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket)
 {
-    if (!hd) { ccsx_set_error("ccsx_submit_hd: null request or report"); return -1; }
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, hd);
+    Wants W;
+    if (build_wants(ex, hd, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket)
 {
-    if (!fold) { ccsx_set_error("ccsx_submit_fold: null request or report"); return -1; }
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, nullptr, fold);
+    Wants W;
+    if (build_wants(ex, nullptr, fold, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                        ccsx_ticket *ticket)
 {
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, ex, nullptr, fold, adapters, "ccsx_submit_screen");
+    Wants W;
+    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
 {
-    return submit_impl(h, b, nullptr, ticket, CCSX_RUN_DRAFT, drafts, nullptr, 0);
+    return submit_impl(h, b, nullptr, ticket, CCSX_RUN_DRAFT, drafts, nullptr, 0, Wants{}, __func__);
 }
 int ccsx_submit_polish(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, ccsx_results *res, uint32_t flags, ccsx_ticket *ticket)
 {
-    return submit_impl(h, b, res, ticket, CCSX_RUN_POLISH, nullptr, drafts, flags);
+    return submit_impl(h, b, res, ticket, CCSX_RUN_POLISH, nullptr, drafts, flags, Wants{}, __func__);
 }
 int ccsx_draft_batch(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts)
 {
@@ -1054,14 +1101,14 @@ int ccsx_ticket_timings(ccsx_handle h, ccsx_ticket ticket, ccsx_timings *t)
 }
 
 // ---- synchronous form (slot 0): parity tests, stage read-backs, the resident-input leg of the benchmark ----
-static int upload_impl(ccsx_handle h, const ccsx_batch *b, bool pile, bool tandem = false, int min_tandem = 0)
+static int upload_impl(ccsx_handle h, const ccsx_batch *b, const Wants &W)
 {
     if (!h) { ccsx_set_error("ccsx_upload: null handle"); return -1; }
     HIPTRY(hipSetDevice(h->device));
     for (auto &S : h->slot) if (int rc = retire(h, S)) return rc;
     Slot &S = h->slot[0];
     S.ticket = -1;                                       // (slot 0 is re-staged: its ticket is recycled, as by a submit; the other slots' tickets stay valid)
-    const int rc = stage(h, S, b, h->s_comp, pile, tandem, min_tandem);
+    const int rc = stage(h, S, b, h->s_comp, W);
     if (rc) { S.staged = false; return rc; }
     S.mode = CCSX_RUN_FUSED;
     HIPTRY(hipStreamSynchronize(h->s_comp));
@@ -1069,7 +1116,7 @@ static int upload_impl(ccsx_handle h, const ccsx_batch *b, bool pile, bool tande
     return 0;
 }
 
-int ccsx_upload(ccsx_handle h, const ccsx_batch *b) { return upload_impl(h, b, false); }
+int ccsx_upload(ccsx_handle h, const ccsx_batch *b) { return upload_impl(h, b, Wants{}); }
 
 int ccsx_run(ccsx_handle h)
 {
@@ -1134,59 +1181,45 @@ int ccsx_consensus_batch(ccsx_handle h, const ccsx_batch *b, ccsx_results *res)
 
 int ccsx_pileup_rule_version(void) { return 1; }
 
-int ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile)
+// The synchronous form of a fused run with its Wants, for the exported function `fn`: upload, every check and attachment that can still refuse the call, the
+// run, the downloads.
+static int consensus_sync(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const Wants &W, const char *fn)
 {
-    if (!h || !b || !res || !pile) { ccsx_set_error("ccsx_consensus_pileup: null argument"); return -1; }
+    if (!h || !b || !res) return refuse(fn, "null argument");
     int rc;
-    if ((rc = upload_impl(h, b, true))) return rc;
+    if ((rc = upload_impl(h, b, W))) return rc;
     Slot &S = h->slot[0];
-    if ((rc = check_pile(S, pile))) return rc;
+    if ((rc = check_results(S, res, S.P.out_kin != nullptr)) || (rc = attach(h, S, W, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));             // (attach may have enqueued on s_comp; ccsx_run enqueues on the draft stream, which does not wait for it)
     if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
-    if ((rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
+    if ((rc = enqueue_wants_download(S, W, h->s_comp))) return rc;
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
+}
+
+// the synchronous entry points: as the ticketed ones, the Wants of the call, the argument this entry point may not be given as NULL, the driver
+int ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_pileup *pile)
+{
+    const ccsx_extras ex = {pile, nullptr, 0, 0};
+    Wants W;
+    if (build_wants(&ex, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
+    return consensus_sync(h, b, res, W, __func__);
 }
 
 int ccsx_tandem_rule_version(void) { return 1; }
 
 int ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex)
 {
-    if (!h || !b || !res) { ccsx_set_error("ccsx_consensus_extras: null argument"); return -1; }
-    bool tandem = false;
-    if (extras_want(ex, &tandem)) return -1;
-    ccsx_pileup *pile = ex ? ex->pile : nullptr;
-    int rc;
-    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
-    Slot &S = h->slot[0];
-    if (pile && (rc = check_pile(S, pile))) return rc;
-    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
-    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
-    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    return 0;
+    Wants W;
+    if (build_wants(ex, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
 }
 
 int ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd)
 {
-    ccsx_hd_opts hdo{};
-    if (b && hd_request_check(hd, b, &hdo, "ccsx_consensus_hd")) return -1;   // (the request is checked with or without a handle)
-    if (!h || !b || !res || !hd) { ccsx_set_error("ccsx_consensus_hd: null argument"); return -1; }
-    bool tandem = false;
-    if (extras_want(ex, &tandem)) return -1;
-    ccsx_pileup *pile = ex ? ex->pile : nullptr;
-    int rc;
-    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
-    Slot &S = h->slot[0];
-    if (pile && (rc = check_pile(S, pile))) return rc;
-    if ((rc = check_results(S, res, S.P.out_kin != nullptr))) return rc;
-    if ((rc = hd_table(h)) || (rc = hd_attach(h, S, hdo, hd->split, h->s_comp))) return rc;
-    HIPTRY(hipStreamSynchronize(h->s_comp));             // (ccsx_run enqueues on the draft stream, which does not wait for s_comp)
-    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
-    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
-    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
-    if ((rc = enqueue_hd_download(S, hd->report, h->s_comp))) return rc;
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    return 0;
+    Wants W;
+    if (build_wants(ex, hd, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
+    return consensus_sync(h, b, res, W, __func__);
 }
 
 void ccsx_fold_opts_default(ccsx_fold_opts *o)
@@ -1199,24 +1232,9 @@ int ccsx_fold_rule_version(void) { return 1; }
 
 int ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold)
 {
-    ccsx_fold_opts fo{};
-    if (b && fold_request_check(fold, b, &fo, "ccsx_consensus_fold")) return -1;   // (the request is checked with or without a handle)
-    if (!h || !b || !res || !fold) { ccsx_set_error("ccsx_consensus_fold: null argument"); return -1; }
-    bool tandem = false;
-    if (extras_want(ex, &tandem)) return -1;
-    ccsx_pileup *pile = ex ? ex->pile : nullptr;
-    int rc;
-    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
-    Slot &S = h->slot[0];
-    if (pile && (rc = check_pile(S, pile))) return rc;
-    if ((rc = check_results(S, res, S.P.out_kin != nullptr))) return rc;
-    if ((rc = fold_attach(h, S, fo))) return rc;
-    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
-    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
-    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
-    if ((rc = enqueue_fold_download(S, fold->report, h->s_comp))) return rc;
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    return 0;
+    Wants W;
+    if (build_wants(ex, nullptr, fold, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
+    return consensus_sync(h, b, res, W, __func__);
 }
 
 void ccsx_adapter_opts_default(ccsx_adapter_opts *o)
@@ -1239,28 +1257,9 @@ int ccsx_adapter_set_default(ccsx_adapter_set *s)
 
 int ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters)
 {
-    ccsx_fold_opts fo{};
-    ccsx_adapter_set aset; ccsx_adapter_opts ao{};
-    if (fold && b && fold_request_check(fold, b, &fo, "ccsx_consensus_screen")) return -1;   // (the requests are checked with or without a handle)
-    if (adapters && b && adapter_request_check(adapters, b, &aset, &ao, "ccsx_consensus_screen")) return -1;
-    if (!h || !b || !res) { ccsx_set_error("ccsx_consensus_screen: null argument"); return -1; }
-    bool tandem = false;
-    if (extras_want(ex, &tandem)) return -1;
-    ccsx_pileup *pile = ex ? ex->pile : nullptr;
-    int rc;
-    if ((rc = upload_impl(h, b, pile != nullptr, tandem, tandem ? ex->min_tandem_repeat_length : 0))) return rc;
-    Slot &S = h->slot[0];
-    if (pile && (rc = check_pile(S, pile))) return rc;
-    if ((rc = check_results(S, res, S.P.out_kin != nullptr))) return rc;
-    if (fold && (rc = fold_attach(h, S, fo))) return rc;
-    if (adapters && (rc = adapter_attach(h, S, aset, ao))) return rc;
-    if ((rc = ccsx_run(h)) || (rc = ccsx_sync(h)) || (rc = ccsx_download(h, res))) return rc;
-    if (pile && (rc = enqueue_pile_download(S, pile, h->s_comp))) return rc;
-    if (tandem && ex->tandem_len) HIPTRY(hipMemcpyAsync(ex->tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, h->s_comp));
-    if (fold && (rc = enqueue_fold_download(S, fold->report, h->s_comp))) return rc;
-    if (adapters && (rc = enqueue_adapter_download(S, adapters->report, h->s_comp))) return rc;
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    return 0;
+    Wants W;
+    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
 }
 
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)
@@ -1397,19 +1396,12 @@ int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts,
     Slot &S = h->slot[0];
     S.mode = CCSX_RUN_HD;                                    // (slot 0 is the finder's now: ccsx_run / ccsx_download refuse it until the next ccsx_upload)
     if ((rc = check_drafts(S, drafts, true))) return rc;
-    const int n = S.P.n_zmw;
     if ((rc = hd_table(h)) || (rc = hd_attach(h, S, hd, 0, h->s_comp))) return rc;
     if ((rc = upload_drafts(S, drafts, h->s_comp))) return rc;
     HIPTRY(hipStreamSynchronize(h->s_comp));
-    KParams &P = S.P;
     if ((rc = launch(h, S)) || (rc = ccsx_sync(h))) return rc;
-    HIPTRY(hipMemcpy(out->verdict, P.hd_zi, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(out->n_sub_sites, P.hd_zi + n, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(out->n_indel_sites, P.hd_zi + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(out->n_listed, P.hd_zi + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(out->min_p, P.hd_minp, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(out->sites, P.hd_sites, (size_t)n * CCSX_HD_MAX_SITES * sizeof(ccsx_hd_site), hipMemcpyDeviceToHost));
-    if (out->status) HIPTRY(hipMemcpy(out->status, P.zstat, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if ((rc = enqueue_hd_download(S, out, h->s_comp))) return rc;   // (status: k_hd_verdict's copy of it, written for every ZMW in this mode too)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
 }
 

@@ -4477,17 +4477,22 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
         LAUNCH_CHECK("k_adapter");
         trace_sync(st, "k_adapter");
     }
-    if (mode == CCSX_RUN_FUSED && P.hd_zi) {
-        // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft stage
-        // and runs under the previous batch's polish stage.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the
-        // cascade and the entry rows (k_polish trims large insertions in LDS only).  It reads no shared POA / alignment scratch.
-        const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;
+    // the heteroduplex finder's three kernels on the draft stream (the fused path with a request, ccsx_hd_batch), `before_verdict` recorded between the last two
+    auto hd_kernels = [&](hipEvent_t before_verdict) {
+        const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;   // (the grid covers the slot capacity, the map only the windows there are)
         hipLaunchKernelGGL(k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_hd_pile");
         hipLaunchKernelGGL(k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_hd_indel");
+        if (before_verdict) CALL_CHECK(hipEventRecord, before_verdict, st);
         hipLaunchKernelGGL(k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
         LAUNCH_CHECK("k_hd_verdict");
+    };
+    if (mode == CCSX_RUN_FUSED && P.hd_zi) {
+        // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft stage
+        // and runs under the previous batch's polish stage.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the
+        // cascade and the entry rows (k_polish trims large insertions in LDS only).  It reads no shared POA / alignment scratch.
+        hd_kernels(nullptr);
         if (P.hd_split) {                                          // the split ZMWs have no windows now: the polish stage's map without them
             hipLaunchKernelGGL(k_wmap, dim3(1), dim3(1024), 0, st, P);
             LAUNCH_CHECK("k_wmap");
@@ -4498,14 +4503,7 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     }
     if (mode == CCSX_RUN_HD) {                                     // the heteroduplex finder instead of the polish stage, on the same stream
         if (ev) for (int k : {3, 6}) CALL_CHECK(hipEventRecord, ev[k], st);
-        const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;   // (the grid covers the slot capacity, the map only the windows there are)
-        hipLaunchKernelGGL(k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_hd_pile");
-        hipLaunchKernelGGL(k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_hd_indel");
-        if (ev) CALL_CHECK(hipEventRecord, ev[4], st);
-        hipLaunchKernelGGL(k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_hd_verdict");
+        hd_kernels(ev ? ev[4] : nullptr);
         trace_sync(st, "k_hd");
         if (ev) CALL_CHECK(hipEventRecord, ev[5], st);
         return failed;
