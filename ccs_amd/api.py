@@ -322,6 +322,90 @@ def _adapter_request(aset: "AdapterSet | None", opts: "AdapterOpts | None", crep
     return CAdapterRequest(C.pointer(a), C.pointer(o), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (a, o)
 
 
+# ---- control screen (include/ccsx.h ccsx_control_*; DESIGN.md §2 "Control screen")
+CONTROL_UNTESTED, CONTROL_NONE, CONTROL_FOUND = 0, 1, 2
+CONTROL_MIN_LEN, CONTROL_MAX_LEN = 64, 4096
+
+
+class ControlOpts(C.Structure):
+    _fields_ = [("max_occ", C.c_int32), ("min_matched", C.c_int32), ("min_ctl_tenths", C.c_int32), ("min_draft_tenths", C.c_int32)]
+
+
+class ControlSeq(C.Structure):
+    """ccsx_control_seq: the spike-in control, 64 .. 4096 codes 0 .. 3 (the length and the codes are checked by the call that takes it)"""
+    _fields_ = [("len", C.c_int32), ("reserved", C.c_int32), ("seq", C.POINTER(C.c_uint8))]
+
+    @staticmethod
+    def from_codes(codes) -> "ControlSeq":
+        a = np.ascontiguousarray(np.asarray(codes, np.uint8))
+        s = ControlSeq(len(a), 0, _ptr(a, C.c_uint8))
+        s._codes = a                                               # (the struct points into it)
+        return s
+
+    @staticmethod
+    def from_string(seq: str) -> "ControlSeq":
+        """from an ACGT string (either case)"""
+        return ControlSeq.from_codes(["ACGT".index(c) for c in seq.upper()])
+
+    def codes(self) -> np.ndarray:
+        return np.ctypeslib.as_array(self.seq, (self.len,)).copy()
+
+
+class CControlReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in ("verdict", "strand", "hits", "matched", "ctl_start", "ctl_end", "draft_start",
+                                                                              "draft_end")]
+
+
+class CControlRequest(C.Structure):
+    """ccsx_control_request: the control screen in the fused path (ccsx_consensus_control / ccsx_submit_control)"""
+    _fields_ = [("control", C.POINTER(ControlSeq)), ("opts", C.POINTER(ControlOpts)), ("report", C.POINTER(CControlReport)), ("reserved", C.c_int32 * 2)]
+
+
+def control_opts_default() -> ControlOpts:
+    o = ControlOpts()
+    lib().ccsx_control_opts_default(C.byref(o))
+    return o
+
+
+@dataclass
+class ControlReport:
+    """ccsx_control_report: per ZMW the verdict (CONTROL_*), the strand (-1: no hit), the hits of the winning pair of diagonal bins, the distinct control
+    positions among them and the control and draft bases they span"""
+    verdict: np.ndarray
+    strand: np.ndarray
+    hits: np.ndarray
+    matched: np.ndarray
+    ctl_start: np.ndarray
+    ctl_end: np.ndarray
+    draft_start: np.ndarray
+    draft_end: np.ndarray
+
+    FIELDS = ("verdict", "strand", "hits", "matched", "ctl_start", "ctl_end", "draft_start", "draft_end")
+
+    @staticmethod
+    def allocate(n: int, pinned: bool = False) -> "ControlReport":
+        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(control=...), downloads into them asynchronously)"""
+        keep = []
+        z = (lambda: _pinned_array(n, np.int32, keep)) if pinned else (lambda: np.empty(n, np.int32))
+        rep = ControlReport(*(z() for _ in ControlReport.FIELDS))
+        for k in ControlReport.FIELDS:
+            getattr(rep, k)[...] = 0
+        rep._pinned = keep
+        return rep
+
+    def c_struct(self) -> CControlReport:
+        r = CControlReport()
+        r.n_zmw = len(self.verdict)
+        for k in ControlReport.FIELDS:
+            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
+        return r
+
+
+def _control_request(seq: ControlSeq, opts: "ControlOpts | None", crep: CControlReport):
+    o = opts if opts is not None else control_opts_default()
+    return CControlRequest(C.pointer(seq), C.pointer(o), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (seq, o)
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -457,6 +541,7 @@ EXPORTS = [
     "ccsx_consensus_hd", "ccsx_submit_hd",
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
     "ccsx_adapter_opts_default", "ccsx_adapter_rule_version", "ccsx_adapter_set_default", "ccsx_consensus_screen", "ccsx_submit_screen",
+    "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
 ]
 
 _lib = None
@@ -529,6 +614,12 @@ def lib() -> C.CDLL:
         L.ccsx_consensus_screen.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest)]
         L.ccsx_submit_screen.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest),
                                          C.POINTER(C.c_int64)]
+        L.ccsx_control_opts_default.restype = None
+        L.ccsx_control_opts_default.argtypes = [C.POINTER(ControlOpts)]
+        L.ccsx_consensus_control.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest),
+                                             C.POINTER(CControlRequest)]
+        L.ccsx_submit_control.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest),
+                                          C.POINTER(CControlRequest), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -996,6 +1087,23 @@ class Handle:
         self._check(self._L.ccsx_consensus_screen(self._h, batch.c_struct(), res.c_struct(), ex, fq, aq), "ccsx_consensus_screen")
         return res, frep, arep, tl, pile
 
+    # ---- the control screen (ccsx_consensus_control), alone or with the other draft detectors and the optional outputs of ccsx_extras
+    def consensus_control(self, batch: Batch, control: ControlSeq, opts: "ControlOpts | None" = None, fold: "bool | FoldOpts" = False,
+                          adapters: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, tandem: bool = False,
+                          min_tandem_repeat_length: int = 0, pileup: bool = False):
+        """(results, control report, fold report or None, adapter report or None, tandem_len or None, pileup or None).  control: the spike-in control
+        (ControlSeq.from_string / from_codes), opts its ControlOpts; the other arguments as consensus_screen.  Detection only"""
+        res, tl, pile = self._outputs(batch, tandem, pileup)
+        crep = ControlReport.allocate(batch.n_zmw)
+        frep = FoldReport.allocate(batch.n_zmw) if fold else None
+        arep = AdapterReport.allocate(batch.n_zmw) if adapters is not None else None
+        ex, _, fq, aq, _keep = _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
+                                         adapters=arep, adapter_set=adapters, adapter_opts=adapter_opts)
+        ccrep = crep.c_struct()
+        cq, _keep2 = _control_request(control, opts, ccrep)
+        self._check(self._L.ccsx_consensus_control(self._h, batch.c_struct(), res.c_struct(), ex, fq, aq, cq), "ccsx_consensus_control")
+        return res, crep, frep, arep, tl, pile
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -1032,22 +1140,36 @@ class Handle:
     def submit(self, batch: Batch, res: "Results", pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None,
                min_tandem_repeat_length: int = 0, hd: "HdReport | None" = None, hd_opts: HdOpts | None = None, hd_split: bool = False,
                fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None, adapters: "AdapterReport | None" = None,
-               adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None) -> int:
+               adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, control: "ControlReport | None" = None,
+               control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None) -> int:
         """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer,
         pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras).  hd: a report
         (HdReport.allocate(n, pinned=True)) that receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish
         stage (ccsx_submit_hd).  fold: a report (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts (ccsx_submit_fold;
         not combined with hd).  adapters: a report (AdapterReport.allocate(n, pinned=True)) that receives the adapter screen of adapter_set (None: the built-in
-        set) under adapter_opts, alone or together with fold (ccsx_submit_screen; not combined with hd)"""
+        set) under adapter_opts, alone or together with fold (ccsx_submit_screen; not combined with hd).  control: a report (ControlReport.allocate(n,
+        pinned=True)) that receives the control screen for control_seq under control_opts, alone or with fold and adapters (ccsx_submit_control; not combined
+        with hd).  Every ticket carries its own control: tickets in flight may screen for different ones"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
             raise ValueError("the heteroduplex and the adapter-palindrome requests are not combined")
         if hd is not None and adapters is not None:
             raise ValueError("the heteroduplex request and the adapter screen are not combined")
+        if control is not None and hd is not None:
+            raise ValueError("the heteroduplex request and the control screen are not combined")
+        if control is not None and control_seq is None:
+            raise ValueError("control: a control_seq is needed (there is no built-in control)")
         ex, hq, fq, aq, keep = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts)
+        cq = None
+        if control is not None:
+            ccrep = control.c_struct()
+            cq, k2 = _control_request(control_seq, control_opts, ccrep)
+            keep += [control, ccrep, cq, k2]
         # the narrowest entry point that expresses the request (so that every exported ccsx_submit_* is in use)
-        if aq is not None:
+        if cq is not None:
+            name, extra = "ccsx_submit_control", (ex, fq, aq, cq)
+        elif aq is not None:
             name, extra = "ccsx_submit_screen", (ex, fq, aq)
         elif fq is not None:
             name, extra = "ccsx_submit_fold", (ex, fq)

@@ -78,10 +78,13 @@ struct Options {
     std::string fail_reads;       // --fail-reads FAIL.bam: one representative read per ZMW without a HiFi read, with the ff tag (docs/faq/fail-reads.md)
     std::string adapters;         // --adapters FILE.fasta|default: screen the drafts for adapter sequence (fail classes 0x10, 0x40); needs --fail-reads
     ccsx_adapter_set adapter_set{};   // ... the set it names
+    std::string control;          // --control FILE.fasta: screen the drafts for the spike-in control (fail class 0x2); control ZMWs leave the main output
+    std::vector<uint8_t> control_codes;   // ... its bases
+    ccsx_control_seq control_seq{};       // ... as the requests name them
 };
 
 enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103, HS_ADAPTER_PALINDROME = 104, HS_ADAPTER_CONCAT = 105,
-                  HS_ADAPTER_NEAR_END = 106 };
+                  HS_ADAPTER_NEAR_END = 106, HS_CONTROL_SUCCESS = 107, HS_CONTROL_FAILURE = 108 };
 
 struct ZmwIn {
     int32_t zm = 0;
@@ -145,6 +148,7 @@ struct Batch {
     ccsx_extras ex{};               // (ccsx_submit_extras reads it during the call only)
     ccsx_fold_report frep{}; ccsx_fold_request freq{};   // (ccsx_submit_fold: the report's arrays are in out_arena)
     ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_submit_screen: the report's arrays are in out_arena)
+    ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_submit_control: the report's arrays are in out_arena)
 };
 
 template <class T> class Channel {
@@ -206,6 +210,9 @@ void usage()
                  "      --adapters F|default  with --fail-reads: screen every draft for the adapters of FASTA file F (up to 8 records of 16-64 bases) or for the\n"
                  "                            built-in SMRTbell adapter; reads made of adapter copies (ff 0x10) or with an adapter close to an end (ff 0x40)\n"
                  "                            leave the main output for F.bam [off]\n"
+                 "      --control F.fasta     screen every draft for the spike-in control of FASTA file F (one record of 64-4096 bases); control ZMWs leave\n"
+                 "                            the main output and are counted as 'ZMW with control success / failure'; with --fail-reads those with a\n"
+                 "                            consensus are written to F.bam with ff 0x2 [off: there is no built-in control]\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -263,6 +270,36 @@ bool load_adapters(const std::string &path, ccsx_adapter_set &set, std::string &
     return true;
 }
 
+// --control: a FASTA of exactly one record of 64 .. 4096 bases, ACGT in either case.  false + a message that names what is wrong
+bool load_control(const std::string &path, std::vector<uint8_t> &codes, std::string &err)
+{
+    std::ifstream f(path);
+    if (!f) { err = "cannot open the file"; return false; }
+    codes.clear();
+    int records = 0;
+    std::string line, name;
+    while (std::getline(f, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            if (++records > 1) { err = "record 2 (" + line.substr(0, 60) + "): more than one record"; return false; }
+            name = line.substr(0, 60);
+            continue;
+        }
+        if (!records) { err = "sequence before the first '>' line"; return false; }
+        for (char c : line) {
+            const int u = std::toupper((unsigned char)c);
+            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
+            if (code < 0) { err = "record 1 (" + name + "): '" + std::string(1, c) + "' is not one of ACGT"; return false; }
+            if (codes.size() >= CCSX_CONTROL_MAX_LEN) { err = "record 1 (" + name + "): more than 4096 bases"; return false; }
+            codes.push_back((uint8_t)code);
+        }
+    }
+    if (!records) { err = "no FASTA record"; return false; }
+    if (codes.size() < CCSX_CONTROL_MIN_LEN) { err = "record 1 (" + name + "): " + std::to_string(codes.size()) + " bases, fewer than 64"; return false; }
+    return true;
+}
+
 bool parse(int argc, char **argv, Options &o)
 {
     ccsx_opts_default(&o.o);
@@ -307,6 +344,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--suppress-reports") o.suppress_reports = true;
         else if (a == "--fail-reads") o.fail_reads = need(a.c_str());
         else if (a == "--adapters") o.adapters = need(a.c_str());
+        else if (a == "--control") o.control = need(a.c_str());
         else if (a == "--model-file") o.model_file = need(a.c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
         else if (a == "--metrics-json") { o.metrics = need(a.c_str()); o.metrics_named = true; }
@@ -332,6 +370,11 @@ bool parse(int argc, char **argv, Options &o)
         if (o.fail_reads.empty()) { std::fprintf(stderr, "ccs: --adapters needs --fail-reads (the reads it flags are written there)\n"); std::exit(2); }
         std::string err;
         if (!load_adapters(o.adapters, o.adapter_set, err)) { std::fprintf(stderr, "ccs: --adapters %s: %s\n", o.adapters.c_str(), err.c_str()); std::exit(2); }
+    }
+    if (!o.control.empty()) {
+        std::string err;
+        if (!load_control(o.control, o.control_codes, err)) { std::fprintf(stderr, "ccs: --control %s: %s\n", o.control.c_str(), err.c_str()); std::exit(2); }
+        o.control_seq = ccsx_control_seq{(int32_t)o.control_codes.size(), 0, o.control_codes.data()};
     }
     // --top-passes 0 = unlimited (docs/faq/accuracy-vs-passes.md:49-52); the engine takes up to CCSX_MAX_PASSES = 255 per ZMW (SPEC v5)
     if (o.o.top_passes <= 0) o.o.top_passes = CCSX_MAX_PASSES;
@@ -567,6 +610,7 @@ struct Report {
     int64_t bases_q30 = 0;        // written bases with a phred QV >= 30 ("Base quality >=Q30 (bp)", docs/faq/reports-aux-files.md:66)
     int64_t tandem = 0;           // ZMWs flagged as tandem repeats (--min-tandem-repeat-length; docs/faq/reports-aux-files.md:22)
     int64_t fail_records = 0;     // records written to --fail-reads
+    int64_t control = 0;          // ZMWs the control screen found (--control), whatever their final status
 };
 
 const char *fail_label(int st)
@@ -586,6 +630,8 @@ const char *fail_label(int st)
         case HS_ADAPTER_PALINDROME: return "CCS adapter palindrome";
         case HS_ADAPTER_CONCAT: return "CCS adapter concatenation";
         case HS_ADAPTER_NEAR_END: return "CCS adapter near end";
+        case HS_CONTROL_SUCCESS: return "ZMW with control success";
+        case HS_CONTROL_FAILURE: return "ZMW with control failure";
         default: return "Unknown error";
     }
 }
@@ -608,17 +654,20 @@ const char *status_name(int st)
         case HS_ADAPTER_PALINDROME: return "ADAPTER_PALINDROME";
         case HS_ADAPTER_CONCAT: return "ADAPTER_CONCATENATION";
         case HS_ADAPTER_NEAR_END: return "ADAPTER_NEAR_END";
+        case HS_CONTROL_SUCCESS: return "CONTROL_SUCCESS";
+        case HS_CONTROL_FAILURE: return "CONTROL_FAILURE";
         default: return "EXCEPTION_THROWN";
     }
 }
 
 // the rows of "Exclusive failed counts" this path can produce, in the order of docs/faq/reports-aux-files.md:24-46 (the rows of the subsystems
-// outside this path — heteroduplex, coverage drops, adapter / control classes — cannot occur and are not listed)
+// outside this path — heteroduplex, coverage drops, and without their options the adapter / control classes — cannot occur and are not listed)
 const char *const kFailOrder[] = {"Below SNR threshold", "Median length filter", "Lacking full passes", "Draft generation error",
                                   "Draft above --max-length", "Draft below --min-length", "Reads failed polishing", "Empty coverage windows",
                                   "CCS did not converge", "CCS below minimum RQ", "Consensus outgrew its buffer", "Unknown error"};
 
-// the rows printed: with --fail-reads also "CCS adapter palindrome" (now a failure) and "ZMW with full-length subread" (the 0x8 records), where the reference lists them
+// the rows printed: with --fail-reads also "CCS adapter palindrome" (now a failure) and "ZMW with full-length subread" (the 0x8 records), with --control the two
+// control rows, where the reference lists them
 std::vector<const char *> fail_order(const Options &o)
 {
     std::vector<const char *> v;
@@ -628,6 +677,7 @@ std::vector<const char *> fail_order(const Options &o)
             if (!o.adapters.empty()) { v.push_back("CCS adapter concatenation"); v.push_back("CCS adapter near end"); }   // (--adapters: the screen's two classes)
             v.push_back("ZMW with full-length subread");
         }
+        if (!o.control.empty() && std::string(k) == "CCS below minimum RQ") { v.push_back("ZMW with control failure"); v.push_back("ZMW with control success"); }
         v.push_back(k);
     }
     return v;
@@ -995,6 +1045,7 @@ int main(int argc, char **argv)
         const bool kin = opt.o.hifi_kinetics != 0;
         const bool fail_reads = !opt.fail_reads.empty();
         const bool screen = !opt.adapters.empty();                  // (needs fail_reads)
+        const bool control = !opt.control.empty();
         std::vector<std::thread> packers;
         const size_t n_packers = std::max<size_t>(1, handles.size()) * (size_t)opt.workers_per_gpu;
         std::vector<std::atomic<int>> packers_left(ndev_q);
@@ -1021,7 +1072,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
                         b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
@@ -1054,6 +1105,12 @@ int main(int argc, char **argv)
                             ccsx_adapter_hit *hits = (ccsx_adapter_hit *)take(3 * CCSX_ADAPTER_MAX_HITS * n4);
                             b->arep = ccsx_adapter_report{n, a9[0], a9[1], a9[2], a9[3], a9[4], a9[5], a9[6], a9[7], a9[8], hits};
                             b->areq = ccsx_adapter_request{&opt.adapter_set, nullptr, &b->arep, {0, 0}};
+                        }
+                        if (control) {
+                            int32_t *c8[8];
+                            for (auto &p : c8) p = (int32_t *)take(n4);
+                            b->crep = ccsx_control_report{n, c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]};
+                            b->creq = ccsx_control_request{&opt.control_seq, nullptr, &b->crep, {0, 0}};
                         }
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
@@ -1115,7 +1172,9 @@ int main(int argc, char **argv)
                 if (inflight.size() >= 3) retire();
                 t0 = now();
                 ccsx_ticket t = -1;
-                if (screen ? ccsx_submit_screen(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &b->areq, &t)
+                const ccsx_extras *ex = (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr;
+                if (control ? ccsx_submit_control(h, &b->cb, &b->cr, ex, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr, &b->creq, &t)
+                    : screen ? ccsx_submit_screen(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &b->areq, &t)
                     : fail_reads ? ccsx_submit_fold(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &t)
                     : opt.min_tandem > 0 ? ccsx_submit_extras(h, &b->cb, &b->cr, &b->ex, &t)
                                        : (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t))) {
@@ -1227,6 +1286,11 @@ int main(int argc, char **argv)
                     // concatenation, near end (DESIGN.md §2 "Adapter screen")
                     const int abits = (screen && s >= 0 && bt.have_results && bt.arep.tested[s] && (engine_st == CCSX_SUCCESS || engine_st == CCSX_LOW_RQ)) ? bt.arep.verdict[s] : 0;
                     if (abits && st != HS_ADAPTER_PALINDROME) st = (abits & CCSX_ADAPTER_CONCAT) ? HS_ADAPTER_CONCAT : HS_ADAPTER_NEAR_END;
+                    // --control: a ZMW the screen found is a control molecule whatever became of it afterwards, and is counted as one before any adapter class
+                    // (DESIGN.md §2 "Control screen")
+                    const bool pal = st == HS_ADAPTER_PALINDROME;
+                    const bool ctl = control && s >= 0 && bt.have_results && bt.crep.verdict[s] == CCSX_CONTROL_FOUND;
+                    if (ctl) { st = engine_st == CCSX_SUCCESS ? HS_CONTROL_SUCCESS : HS_CONTROL_FAILURE; ++rep.control; }
                     const bool tandem = opt.min_tandem > 0 && s >= 0 && bt.have_results && bt.tlen[s] >= opt.min_tandem;
                     rep.tandem += tandem ? 1 : 0;
                     if (want_metrics) {
@@ -1245,10 +1309,10 @@ int main(int argc, char **argv)
                     if (st != CCSX_SUCCESS) {
                         rep.fail[fail_label(st)]++;
                         if (!fail_reads) continue;
-                        if ((engine_st == CCSX_LOW_RQ || st == HS_ADAPTER_PALINDROME || abits) && len > 0) {     // a consensus: as the main writer builds it, plus ff
+                        if ((engine_st == CCSX_LOW_RQ || pal || abits || ctl) && len > 0) {     // a consensus: as the main writer builds it, plus ff
                             if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }
                             build(z, bt, s);
-                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (st == HS_ADAPTER_PALINDROME ? 0x20 : 0) | ((abits & CCSX_ADAPTER_CONCAT) ? 0x10 : 0) |
+                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (ctl ? 0x2 : 0) | (pal ? 0x20 : 0) | ((abits & CCSX_ADAPTER_CONCAT) ? 0x10 : 0) |
                                               ((abits & CCSX_ADAPTER_NEAR_END) ? 0x40 : 0));
                             fmarks.push_back(failp->mark());
                             fpbi.rg_id.push_back(0); fpbi.q_start.push_back(0); fpbi.q_end.push_back(len); fpbi.hole.push_back(z.zm);
@@ -1351,10 +1415,11 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "ccs: GPU workers (sum over %zu): waiting for input %.2f s, packing (pack threads) %.2f s, submit + wait %.2f s\n", handles.size(),
                          us_wait.load() * 1e-6, us_pack.load() * 1e-6, us_engine.load() * 1e-6);
         if (opt.log_level >= 1)
-            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s\n", rep.input, rep.pass, el,
+            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",
                          opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "",
-                         opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str());
+                         opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str(),
+                         control ? (", " + std::to_string(rep.control) + " control ZMWs").c_str() : "");
         if (failed) {
             if (!err_msg.empty()) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
             // no plausible-looking partial output after a failed run

@@ -114,9 +114,11 @@ struct Slot {
     DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
     DevBuf d_fold;                                // adapter palindromes only (ccsx_fold_request): [4][n] report
     DevBuf d_adapt;                               // adapter screen only (ccsx_adapter_request): [9][n] report + [n][16] hits
+    DevBuf d_ctl;                                 // control screen only (ccsx_control_request): the slot's own index, then the [8][n] report
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
+    PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
     KParams P;
     hipEvent_t ev[7] = {}, ev_up = nullptr, ev_done = nullptr;   // ev[0..5]: stage boundaries, ev[6]: start of the polish stage
     hipEvent_t ev_aux[7] = {};                                   // second stream: fork / first DP done / join of the POA stage; k_align16 launch done x 2, its trace-back done x 2
@@ -136,10 +138,10 @@ struct Slot {
                           &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
                           &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
                           &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_tflag, &d_tlen, &d_din_len, &d_din_bb,
-                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites, &d_fold, &d_adapt};
+                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites, &d_fold, &d_adapt, &d_ctl};
         for (auto *b : bufs) b->release();
         read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
-        read_off.release(); seq_off.release(); ent_off.release(); base_off.release();
+        read_off.release(); seq_off.release(); ent_off.release(); base_off.release(); ctl_index.release();
         for (auto &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         for (auto &e : ev_aux) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_up) { (void)hipEventDestroy(ev_up); ev_up = nullptr; }
@@ -349,10 +351,11 @@ struct Wants {
     const ccsx_hd_request *hd = nullptr; ccsx_hd_opts hd_opts{};
     const ccsx_fold_request *fold = nullptr; ccsx_fold_opts fold_opts{};
     const ccsx_adapter_request *adapters = nullptr; ccsx_adapter_set adapter_set{}; ccsx_adapter_opts adapter_opts{};
+    const ccsx_control_request *control = nullptr; ccsx_control_opts control_opts{}; std::vector<uint8_t> control_seq;
 };
 
 // the longest draft of a slot's batch that can reach status SUCCESS (that needs length <= opts.max_length, and no draft exceeds its slot), at least `floor`:
-// what the LDS of k_sdust, k_fold and k_adapter is sized for
+// what the LDS of k_sdust, k_fold, k_adapter and k_control is sized for
 static int64_t longest_draft(ccsx_handle h, const Slot &S, int32_t floor)
 {
     int64_t longest = floor;
@@ -897,6 +900,82 @@ static int enqueue_adapter_download(const Slot &S, ccsx_adapter_report *r, hipSt
     return 0;
 }
 
+// ---- the control screen's host side (ccsx_control_request): the same three steps.  The checked sequence and options are copied into `seq` / `o`
+static int control_request_check(const ccsx_control_request *q, const ccsx_batch *b, std::vector<uint8_t> *seq, ccsx_control_opts *o, const char *fn)
+{
+    if (!q || !q->report) { ccsx_set_error(std::string(fn) + ": null control request or report"); return -1; }
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": control request: reserved must be 0"); return -1; }
+    if (!q->control || !q->control->seq) { ccsx_set_error(std::string(fn) + ": null control sequence"); return -1; }
+    if (q->control->reserved != 0) { ccsx_set_error(std::string(fn) + ": control sequence: reserved must be 0"); return -1; }
+    if (q->opts) *o = *q->opts; else ccsx_control_opts_default(o);
+    if (o->max_occ < 1 || o->max_occ > 64 || o->min_matched < 1 || o->min_ctl_tenths < 0 || o->min_ctl_tenths > 10 || o->min_draft_tenths < 0 || o->min_draft_tenths > 10) {
+        ccsx_set_error(std::string(fn) + ": control options out of range (1 <= max_occ <= 64; min_matched >= 1; 0 <= min_ctl_tenths, min_draft_tenths <= 10)"); return -1;
+    }
+    const int32_t M = q->control->len;
+    if (M < CCSX_CONTROL_MIN_LEN || M > CCSX_CONTROL_MAX_LEN) { ccsx_set_error(std::string(fn) + ": control length outside 64 .. 4096"); return -1; }
+    for (int32_t i = 0; i < M; ++i)
+        if (q->control->seq[i] > 3) { ccsx_set_error(std::string(fn) + ": control: code above 3"); return -1; }
+    seq->assign(q->control->seq, q->control->seq + M);
+    const ccsx_control_report *r = q->report;
+    if (r->n_zmw != b->n_zmw || !r->verdict || !r->strand || !r->hits || !r->matched || !r->ctl_start || !r->ctl_end || !r->draft_start || !r->draft_end) {
+        ccsx_set_error(std::string(fn) + ": control report arrays missing, or sized for another batch"); return -1;
+    }
+    return 0;
+}
+
+// The index k_control reads (ccsx_kernels.h), into idx[CCSX_CONTROL_INDEX_WORDS]: every 15-mer position of the control in increasing (code, position), without the
+// codes that occur more than max_occ times.  The order is total, so the same control and max_occ give the same bytes.
+static void control_index_build(const std::vector<uint8_t> &c, int max_occ, uint32_t *idx)
+{
+    const int M = (int)c.size(), K = CCSX_FOLD_K, np_ = M - K + 1;
+    std::vector<uint64_t> key((size_t)np_);                     // code << 16 | position
+    uint32_t F = 0u;
+    for (int i = 0; i < M; ++i) {
+        F = ((F << 2) | c[i]) & ((1u << (2 * K)) - 1u);
+        if (i >= K - 1) key[i - K + 1] = ((uint64_t)F << 16) | (uint64_t)(i - K + 1);
+    }
+    std::sort(key.begin(), key.end());
+    std::fill(idx, idx + CCSX_CONTROL_POS_WORD, 0xffffffffu);
+    std::fill(idx + CCSX_CONTROL_POS_WORD, idx + CCSX_CONTROL_INDEX_WORDS, 0u);
+    uint16_t *pos = reinterpret_cast<uint16_t *>(idx + CCSX_CONTROL_POS_WORD);
+    uint32_t *filt = idx + CCSX_CONTROL_FILTER_WORD;
+    int m = 0;
+    for (int a = 0, e; a < np_; a = e) {
+        for (e = a + 1; e < np_ && (key[e] >> 16) == (key[a] >> 16); ++e) {}
+        if (e - a > max_occ) continue;
+        const uint32_t code = (uint32_t)(key[a] >> 16), hsh = ccsx_fmix32(code) & (uint32_t)(CCSX_CONTROL_FILTER_BITS - 1);
+        filt[hsh >> 5] |= 1u << (hsh & 31u);
+        for (int k = a; k < e; ++k, ++m) { idx[m] = code; pos[m] = (uint16_t)(key[k] & 0xffffu); }
+    }
+}
+
+// k_control's two LDS histograms cover the longest draft the cascade aligns (longest_draft); -1 when that is beyond their LDS bound (nothing enqueued yet by this
+// call's request).  The index is the slot's own, in page-locked memory that lives as long as the slot: its copy is enqueued on `st` with the slot's other uploads,
+// and a slot is only staged again after its ticket has been retired, so no ticket in flight reads an index another one replaces.
+static int control_attach(ccsx_handle h, Slot &S, const std::vector<uint8_t> &seq, const ccsx_control_opts &o, hipStream_t st)
+{
+    const int n = S.P.n_zmw, M = (int)seq.size();
+    const int64_t longest = longest_draft(h, S, 16);
+    const int64_t bins = ((longest - CCSX_FOLD_K + M - CCSX_FOLD_K) >> 6) + 2;
+    if (bins > CCSX_CONTROL_MAX_BINS) { ccsx_set_error("control screen: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
+    if (S.d_ctl.reserve((size_t)CCSX_CONTROL_INDEX_WORDS * 4 + (size_t)n * 32) || S.ctl_index.resize(CCSX_CONTROL_INDEX_WORDS)) return -2;
+    control_index_build(seq, o.max_occ, S.ctl_index.p);
+    KParams &P = S.P;
+    P.ctl = o; P.ctl_index = (const uint32_t *)S.d_ctl.p; P.ctl_zi = (int32_t *)S.d_ctl.p + CCSX_CONTROL_INDEX_WORDS; P.ctl_len = M; P.ctl_bins = (int32_t)bins;
+    if (hipError_t e = hipMemcpyAsync(S.d_ctl.p, S.ctl_index.p, (size_t)CCSX_CONTROL_INDEX_WORDS * 4, hipMemcpyHostToDevice, st)) {
+        ccsx_set_error(std::string("control screen: index upload: ") + hipGetErrorString(e)); return -2;
+    }
+    return 0;
+}
+
+static int enqueue_control_download(const Slot &S, ccsx_control_report *r, hipStream_t s)
+{
+    const size_t n = (size_t)S.P.n_zmw;
+    int32_t *dst[8] = {r->verdict, r->strand, r->hits, r->matched, r->ctl_start, r->ctl_end, r->draft_start, r->draft_end};
+    for (int k = 0; k < 8; ++k) HIPTRY(hipMemcpyAsync(dst[k], S.P.ctl_zi + k * n, n * 4, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
@@ -913,26 +992,29 @@ static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string
 // first, each refused by its own message, then the extras; the caller's null-argument check follows (without a batch there is nothing to measure a report
 // against, and that check refuses the call).
 static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters, const ccsx_batch *b,
-                       const char *fn, Wants *W)
+                       const char *fn, Wants *W, const ccsx_control_request *control = nullptr)
 {
     *W = Wants{};
     if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
     if (fold && b && fold_request_check(fold, b, &W->fold_opts, fn)) return -1;
     if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
+    if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
-    W->hd = hd; W->fold = fold; W->adapters = adapters;
+    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
 
 // What W asks for on a staged slot: checks, buffers and pointers, in the order of what can still be refused.  -1 only while this call has enqueued nothing
-// (the pileup planes, the LDS bounds of k_fold and k_adapter), -2 otherwise; the one step that enqueues (the finder's memset, on `st`) comes last.
+// (the pileup planes, the LDS bounds of k_fold, k_adapter and k_control), -2 otherwise; the steps that enqueue on `st` (the control index's upload, after its own
+// LDS check, and the finder's memset) come last.
 static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
 {
     int rc;
     if (W.pile && (rc = check_pile(S, W.pile))) return rc;
     if (W.fold && (rc = fold_attach(h, S, W.fold_opts))) return rc;
     if (W.adapters && (rc = adapter_attach(h, S, W.adapter_set, W.adapter_opts))) return rc;
+    if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
     return 0;
 }
@@ -946,6 +1028,7 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
     if (W.hd && (rc = enqueue_hd_download(S, W.hd->report, s))) return rc;
     if (W.fold && (rc = enqueue_fold_download(S, W.fold->report, s))) return rc;
     if (W.adapters && (rc = enqueue_adapter_download(S, W.adapters->report, s))) return rc;
+    if (W.control && (rc = enqueue_control_download(S, W.control->report, s))) return rc;
     return 0;
 }
 
@@ -1042,6 +1125,13 @@ int ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, co
 {
     Wants W;
     if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
+                        const ccsx_control_request *control, ccsx_ticket *ticket)
+{
+    Wants W;
+    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W, control)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
@@ -1259,6 +1349,22 @@ int ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res,
 {
     Wants W;
     if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
+void ccsx_control_opts_default(ccsx_control_opts *o)
+{
+    if (!o) return;
+    o->max_occ = 4; o->min_matched = 30; o->min_ctl_tenths = 5; o->min_draft_tenths = 8;   // DESIGN.md §2 "Control screen": the study behind them
+}
+
+int ccsx_control_rule_version(void) { return 1; }
+
+int ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
+                           const ccsx_control_request *control)
+{
+    Wants W;
+    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W, control)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 

@@ -131,6 +131,12 @@ struct KParams {
     int32_t adapt_n;           // adapters (searches = 2 x)
     uint8_t adapt_len[CCSX_ADAPTER_MAX_PATTERNS];
     uint32_t adapt_seq[CCSX_ADAPTER_MAX_PATTERNS][4];   // 2 bits per base, base i at bits 2 (i & 15) of word i >> 4
+    // ---- control screen (ccsx_consensus_control / ccsx_submit_control with a control request; NULL otherwise): DESIGN.md §2 "Control screen"
+    ccsx_control_opts ctl;
+    int32_t *ctl_zi;           // [8][n] verdict, strand, hits, matched, ctl_start, ctl_end, draft_start, draft_end
+    const uint32_t *ctl_index; // [CCSX_CONTROL_INDEX_WORDS] the slot's own copy of the control's index (ccsx_control_index_build)
+    int32_t ctl_len;           // M
+    int32_t ctl_bins;          // k_control's two LDS histograms: diagonal bins each, enough for the longest draft that is aligned (+ 1 empty bin)
 };
 
 // k_adapter (DESIGN.md §2 "Adapter screen"): draft bases a lane owns per search, its workgroup, the hit keys one pass buffers in LDS and the bitmaps' LDS bound
@@ -147,6 +153,19 @@ struct KParams {
 #define CCSX_FOLD_CAP      1536    // distinct codes and kept members one pass holds; beyond that the samples are split into more passes
 #define CCSX_FOLD_MAX_BINS 6656    // the histogram's LDS bound (drafts up to 212 kb): with k_fold's 37.9 KB of static LDS a launch stays within the
                                    // 64 KiB it gets without raising its dynamic-LDS attribute (drafts are at most ~82 kb: 1.25 x 65535-base subreads)
+
+// k_control (DESIGN.md §2 "Control screen"): the index of a control of M <= CCSX_CONTROL_MAX_LEN bases as the host builds it and every workgroup copies it to LDS.
+//   words [0, 4096)     the codes of the kept 15-mers in increasing (code, position), padded with 0xffffffff (no code: a code has 30 bits)
+//   words [4096, 6144)  their positions, 16 bits each, in the same order
+//   words [6144, 7168)  a prefilter: bit (fold_fmix32(code) & 32767) is set for every kept code; a look-up that passes it still compares the exact code
+#define CCSX_CONTROL_THREADS     256
+#define CCSX_CONTROL_POS_WORD    CCSX_CONTROL_MAX_LEN
+#define CCSX_CONTROL_FILTER_WORD (CCSX_CONTROL_MAX_LEN + CCSX_CONTROL_MAX_LEN / 2)
+#define CCSX_CONTROL_FILTER_BITS 32768
+#define CCSX_CONTROL_INDEX_WORDS (CCSX_CONTROL_FILTER_WORD + CCSX_CONTROL_FILTER_BITS / 32)
+#define CCSX_CONTROL_MAX_BINS    4352   // per orientation; the histograms' LDS bound (drafts up to 274 kb): 2 x 17 KiB + k_control's 29.2 KB of static LDS stay
+                                        // within the 64 KiB a launch gets by default
+static inline __host__ __device__ uint32_t ccsx_fmix32(uint32_t h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
 
 // k_sdust (DESIGN.md §2 "Tandem repeats"): window W bases, threshold T in tenths, dynamic LDS = two [64][64] word tables + two byte tables + the mask
 #define CCSX_SDUST_W 64

@@ -4147,6 +4147,117 @@ __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
     }
 }
 
+// ---- k_control: the control screen on a ZMW's final draft (DESIGN.md §2 "Control screen").  One 256-thread workgroup per ZMW, longest first.  The workgroup
+// copies the control's index (ccsx_kernels.h: sorted codes, their positions, a prefilter bitmap; 28 KiB, L2-resident for the whole launch) into LDS.  Thread t owns a
+// contiguous range of k-mer positions and rolls F and R over it as k_fold's scan does; each code passes the prefilter bit, then a 12-step lower bound over the
+// padded code array, and every index entry with exactly that code is a hit (a kept code has at most max_occ entries).  (1) Every hit's diagonal bin is counted in
+// one of two LDS histograms.  (2) The winning (orientation, pair of bins), a max-reduction over (H, orientation 0 first, -b).  (3) The hits again, now only the
+// winning ones: their control positions set bits of an LDS bitmap (matched = its population count, the control extent its first and last bit), the draft extent is
+// a per-thread min / max joined by one atomic each.  Counts, minima, maxima and a bitmap only: the result does not depend on thread order.  tests/control_ref.py
+// restates the rule.
+__global__ __launch_bounds__(CCSX_CONTROL_THREADS) void k_control(KParams P)
+{
+    constexpr int K = CCSX_FOLD_K, NT = CCSX_CONTROL_THREADS, CAP = CCSX_CONTROL_MAX_LEN;
+    constexpr uint32_t KMASK = (1u << (2 * K)) - 1u;
+    static_assert((CAP & (CAP - 1)) == 0 && CAP <= 65536 && CCSX_CONTROL_INDEX_WORDS % 4 == 0, "k_control: a power-of-two code array, 16-bit positions, 16-byte copies");
+    __shared__ __attribute__((aligned(16))) uint32_t sIdx[CCSX_CONTROL_INDEX_WORDS];
+    __shared__ uint32_t sSeen[CAP / 32];  // bit j: control position j is among the winning hits
+    __shared__ int sV[5];                 // 0 min i, 1 max i, 2 matched, 3 min j, 4 max j
+    __shared__ unsigned long long sBest;
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= P.n_zmw) return;
+    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    const size_t n = (size_t)P.n_zmw;
+    int32_t *out = P.ctl_zi + z;
+    const int L = rfl(P.draft_len[z]), M = P.ctl_len, bins = P.ctl_bins;
+    const int npos = L >= K ? L - K + 1 : 0;
+    const int nb = npos > 0 ? ((L - K + M - K) >> 6) + 1 : 0;       // bins of this draft's diagonals
+    auto report = [&](int verdict, int strand, int hits, int matched, int cs, int ce, int ds, int de) {
+        out[0] = verdict; out[n] = strand; out[2 * n] = hits; out[3 * n] = matched; out[4 * n] = cs; out[5 * n] = ce; out[6 * n] = ds; out[7 * n] = de;
+    };
+    if (rfl(P.zstat[z]) != CCSX_SUCCESS || nb + 1 > bins) {        // untested (the second: a bounds guard, the histograms cover opts.max_length)
+        if (tid == 0) report(CCSX_CONTROL_UNTESTED, -1, 0, 0, 0, 0, 0, 0);
+        return;
+    }
+    if (npos == 0) {
+        if (tid == 0) report(CCSX_CONTROL_NONE, -1, 0, 0, 0, 0, 0, 0);
+        return;
+    }
+    uint32_t *sHist = dyn_lds;            // [2][bins] hits per diagonal bin of orientation 0, 1
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(P.ctl_index);
+        uint4 *dst = reinterpret_cast<uint4 *>(sIdx);
+        for (int w = tid; w < CCSX_CONTROL_INDEX_WORDS / 4; w += NT) dst[w] = src[w];
+    }
+    for (int b = tid; b < 2 * bins; b += NT) sHist[b] = 0u;
+    for (int w = tid; w < CAP / 32; w += NT) sSeen[w] = 0u;
+    if (tid == 0) { sV[0] = 0x7fffffff; sV[1] = -1; sV[2] = 0; sV[3] = 0x7fffffff; sV[4] = -1; sBest = 0ull; }
+    __syncthreads();
+    const uint32_t *sCode = sIdx, *sFilt = sIdx + CCSX_CONTROL_FILTER_WORD;
+    const uint16_t *sPos = reinterpret_cast<const uint16_t *>(sIdx + CCSX_CONTROL_POS_WORD);
+    const uint8_t *d = P.draft + P.seq_off[z];
+    const int ch = (npos + NT - 1) / NT;
+    const int p0 = min(tid * ch, npos), p1 = min(p0 + ch, npos);
+    // fn(o, i, j, dg) for every hit of this thread's range: orientation, draft position, control position, diagonal
+    auto scan = [&](auto fn) {
+        if (p0 >= p1) return;
+        auto lookup = [&](uint32_t code, int o, int i, int u) {
+            const uint32_t h = ccsx_fmix32(code) & (uint32_t)(CCSX_CONTROL_FILTER_BITS - 1);
+            if (!((sFilt[h >> 5] >> (h & 31u)) & 1u)) return;
+            int lo = 0;
+            for (int s = CAP >> 1; s > 0; s >>= 1) lo += sCode[lo + s - 1] < code ? s : 0;   // entries below `code` (the padding is above every code)
+            for (int e = lo; sCode[e] == code; ++e) { const int j = (int)sPos[e]; fn(o, i, j, u - j + (M - K)); }
+        };
+        uint32_t F = 0u, R = 0u;
+        for (int t = 0; t < K - 1; ++t) { const uint32_t b = d[p0 + t] & 3u; F = (F << 2) | b; R = (R >> 2) | ((3u - b) << (2 * K - 2)); }
+        for (int i = p0; i < p1; ++i) {
+            const uint32_t b = d[i + K - 1] & 3u;
+            F = ((F << 2) | b) & KMASK;
+            R = (R >> 2) | ((3u - b) << (2 * K - 2));
+            lookup(F, 0, i, i);
+            lookup(R, 1, i, (L - K) - i);
+        }
+    };
+    // (1) the vote
+    scan([&](int o, int, int, int dg) { atomicAdd(&sHist[o * bins + (dg >> 6)], 1u); });
+    __syncthreads();
+    // (2) (o*, b*) = argmax of H(o, b) = hist[o][b] + hist[o][b + 1], ties to orientation 0, then to the smallest b
+    unsigned long long best = 0ull;
+    for (int q = tid; q < 2 * nb; q += NT) {
+        const int o = q >= nb ? 1 : 0, b = q - o * nb;
+        const unsigned long long key = ((unsigned long long)(sHist[o * bins + b] + sHist[o * bins + b + 1]) << 32) | ((uint32_t)(1 - o) << 31) | (0x7fffffffu - (uint32_t)b);
+        best = key > best ? key : best;
+    }
+    if (best >> 32) atomicMax(&sBest, best);
+    __syncthreads();
+    const int H = (int)(sBest >> 32);
+    if (H == 0) {
+        if (tid == 0) report(CCSX_CONTROL_NONE, -1, 0, 0, 0, 0, 0, 0);
+        return;
+    }
+    const int os = 1 - (int)((sBest >> 31) & 1ull), bs = (int)(0x7fffffffu - (uint32_t)(sBest & 0x7fffffffull));
+    // (3) the winning hits: distinct control positions and the two extents
+    int imin = 0x7fffffff, imax = -1;
+    scan([&](int o, int i, int j, int dg) {
+        if (o != os || ((dg >> 6) != bs && (dg >> 6) != bs + 1)) return;
+        atomicOr(&sSeen[j >> 5], 1u << (j & 31));
+        imin = i < imin ? i : imin; imax = i > imax ? i : imax;
+    });
+    if (imax >= 0) { atomicMin(&sV[0], imin); atomicMax(&sV[1], imax); }
+    __syncthreads();
+    for (int w = tid; w < CAP / 32; w += NT) {
+        const uint32_t m = sSeen[w];
+        if (m) { atomicAdd(&sV[2], __popc(m)); atomicMin(&sV[3], w * 32 + __ffs((int)m) - 1); atomicMax(&sV[4], w * 32 + 31 - __clz((int)m)); }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const ccsx_control_opts &o = P.ctl;
+        const int cs = sV[3], ce = sV[4] + K, ds = sV[0], de = sV[1] + K;
+        const bool found = sV[2] >= o.min_matched && 10 * (ce - cs) >= o.min_ctl_tenths * M && 10ll * (de - ds) >= (long long)o.min_draft_tenths * L;
+        report(found ? CCSX_CONTROL_FOUND : CCSX_CONTROL_NONE, os, H, sV[2], cs, ce, ds, de);
+    }
+}
+
 // ---- k_adapter: the adapter screen on a ZMW's final draft (DESIGN.md §2 "Adapter screen").  One 256-thread workgroup per ZMW, longest first.  Myers' bit-vector
 // column update, one 64-bit word per search.  A lane owns one (search, chunk of CCSX_ADAPTER_CHUNK draft bases): it starts from the all-ones vertical state m + k
 // bases before its chunk (after that warm-up every value <= k is exact and so is the predicate E <= k: a fresh start can only over-estimate, and a match of distance
@@ -4476,6 +4587,13 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
         hipLaunchKernelGGL(k_adapter, dim3(P.n_zmw), dim3(CCSX_ADAPTER_THREADS), (size_t)P.adapt_words * 8, st, P);
         LAUNCH_CHECK("k_adapter");
         trace_sync(st, "k_adapter");
+    }
+    if (mode == CCSX_RUN_FUSED && P.ctl_zi) {
+        // the control screen (ccsx_submit_control / ccsx_consensus_control): as k_fold and k_adapter, on the draft stream and on the final drafts and statuses;
+        // writes its report only
+        hipLaunchKernelGGL(k_control, dim3(P.n_zmw), dim3(CCSX_CONTROL_THREADS), (size_t)P.ctl_bins * 8, st, P);
+        LAUNCH_CHECK("k_control");
+        trace_sync(st, "k_control");
     }
     // the heteroduplex finder's three kernels on the draft stream (the fused path with a request, ccsx_hd_batch), `before_verdict` recorded between the last two
     auto hd_kernels = [&](hipEvent_t before_verdict) {

@@ -474,6 +474,54 @@ int         ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_resul
 int         ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
                                const ccsx_adapter_request *adapters, ccsx_ticket *ticket);
 
+/* ---- control screen (docs/faq/fail-reads.md: fail class 0x2 "control reads"; docs/faq/reports-aux-files.md "ZMW with control success / failure"; the rule:
+ * DESIGN.md §2 "Control screen", its own version ccsx_control_rule_version).  A spike-in control molecule is polished into a confident consensus like any sample.
+ * k_control looks every 15-mer of the ZMW's final draft (what k_polish is given: pass-0 POA, fallback or last resort) up, in both orientations, in an index of the
+ * caller-supplied control sequence and votes on the diagonal; integer arithmetic only.  Detection only: every result byte equals the same call without the
+ * request.  There is no built-in control sequence.
+ *   ccsx_consensus_control  synchronous (slot 0): ccsx_consensus_screen + the control request; any of ex, fold, adapters and control may be NULL (all NULL =
+ *                           ccsx_consensus_extras).
+ *   ccsx_submit_control     ticketed like ccsx_submit_screen: the reports' arrays follow the lifetime rule of `res` (written by the ticket's download) and should
+ *                           be page-locked; the request, sequence and options structs are read during the call only (every ticket carries its own index: tickets
+ *                           in flight may screen for different controls).
+ * A NULL report or control sequence, a report sized for another batch, nonzero reserved words, a length outside 64 .. 4096, a code above 3 or options out of range
+ * are errors of the call: nothing is enqueued.  Without a request nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered. */
+#define CCSX_CONTROL_MIN_LEN 64
+#define CCSX_CONTROL_MAX_LEN 4096
+typedef struct ccsx_control_opts {
+    int32_t max_occ;             /* a 15-mer that occurs more often than this in the control is dropped from its index (1 .. 64)                                 */
+    int32_t min_matched;         /* CONTROL: distinct control positions among the winning hits (>= 1)                                                            */
+    int32_t min_ctl_tenths;      /* CONTROL: the winning hits span at least this many tenths of the control (0 .. 10)                                            */
+    int32_t min_draft_tenths;    /* CONTROL: ... and of the draft (0 .. 10): the molecule is the control, it does not merely contain a stretch of it             */
+} ccsx_control_opts;
+typedef struct ccsx_control_seq {
+    int32_t        len;          /* CCSX_CONTROL_MIN_LEN .. CCSX_CONTROL_MAX_LEN                                                                                 */
+    int32_t        reserved;     /* must be 0                                                                                                                    */
+    const uint8_t *seq;          /* codes 0 .. 3 (A C G T)                                                                                                       */
+} ccsx_control_seq;
+enum ccsx_control_verdict { CCSX_CONTROL_UNTESTED = 0, CCSX_CONTROL_NONE = 1, CCSX_CONTROL_FOUND = 2 };
+typedef struct ccsx_control_report {
+    int32_t  n_zmw;
+    int32_t *verdict;            /* [n_zmw] enum ccsx_control_verdict (UNTESTED: the status after the cascade is not SUCCESS)                                     */
+    int32_t *strand;             /* [n_zmw] 0: the draft reads as the control, 1: as its reverse complement, -1: no hit                                           */
+    int32_t *hits;               /* [n_zmw] hits in the winning pair of diagonal bins                                                                             */
+    int32_t *matched;            /* [n_zmw] distinct control positions among them                                                                                 */
+    int32_t *ctl_start, *ctl_end;       /* [n_zmw] control bases the winning hits span                                                                            */
+    int32_t *draft_start, *draft_end;   /* [n_zmw] draft bases they span, in the draft's own orientation for either strand                                        */
+} ccsx_control_report;
+typedef struct ccsx_control_request {
+    const ccsx_control_seq  *control;
+    const ccsx_control_opts *opts;       /* NULL = ccsx_control_opts_default                                                                                     */
+    ccsx_control_report     *report;
+    int32_t                  reserved[2];   /* must be 0                                                                                                         */
+} ccsx_control_request;
+void        ccsx_control_opts_default(ccsx_control_opts *o);
+int         ccsx_control_rule_version(void);
+int         ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
+                                   const ccsx_adapter_request *adapters, const ccsx_control_request *control);
+int         ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
+                                const ccsx_adapter_request *adapters, const ccsx_control_request *control, ccsx_ticket *ticket);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
