@@ -536,7 +536,7 @@ EXPORTS = [
     "ccsx_model_from_json", "ccsx_model_load", "ccsx_model_to_json", "ccsx_model_for_chemistry",
     "ccsx_build_flags", "ccsx_runtime_switches", "ccsx_pci_numa_node", "ccsx_device_numa_node", "ccsx_bind_thread_to_node", "ccsx_bind_thread_to_device", "ccsx_draft_layout", "ccsx_draft_batch", "ccsx_polish_batch", "ccsx_submit_draft", "ccsx_submit_polish",
     "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
-    "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished",
+    "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished", "ccsx_stage_align_ev",
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
     "ccsx_consensus_hd", "ccsx_submit_hd",
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
@@ -572,6 +572,8 @@ def lib() -> C.CDLL:
         L.ccsx_stage_align.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.ccsx_stage_windows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
+        L.ccsx_stage_align_ev.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_uint8), C.c_int32]
         L.ccsx_synth_generate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_uint64, C.POINTER(C.POINTER(CSynth))]
         L.ccsx_synth_free.argtypes = [C.POINTER(CSynth)]
@@ -1218,6 +1220,13 @@ class Handle:
         v, s = C.c_int32(), C.c_int32()
         self._check(self._L.ccsx_stage_align(self._h, r, _ptr(buf, C.c_int32), ld + 1, C.byref(v), C.byref(s)), "ccsx_stage_align")
         return buf, v.value, s.value
+
+    def stage_align_ev(self, r: int, ld: int):
+        """stage_align plus dirty[ld] (uint8): the pass's pile-up evidence per draft position, as k_polish reads it (all 1 for a split or partial pass)"""
+        buf, dirty = np.zeros(ld + 1, np.int32), np.zeros(max(ld, 1), np.uint8)
+        v, s = C.c_int32(), C.c_int32()
+        self._check(self._L.ccsx_stage_align_ev(self._h, r, _ptr(buf, C.c_int32), ld + 1, C.byref(v), C.byref(s), _ptr(dirty, C.c_uint8), ld), "ccsx_stage_align_ev")
+        return buf, v.value, s.value, dirty[:ld]
 
     def stage_windows(self, z: int) -> np.ndarray:
         cap = 1 << 14

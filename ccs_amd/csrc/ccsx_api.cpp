@@ -1456,6 +1456,31 @@ int ccsx_stage_align(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, int
     return 0;
 }
 
+// ccsx_stage_align and the dirty masks of the same pass, unpacked per draft position: interval k covers the positions col(k - 1) .. col(k) - 1, bit p - col(k - 1)
+// (what k_polish's load_meta shifts together for a window)
+int ccsx_stage_align_ev(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, int32_t *valid, int32_t *score, uint8_t *dirty, int32_t dirty_cap)
+{
+    if (!rstart || !valid || !score || !dirty) { ccsx_set_error("ccsx_stage_align_ev: null argument"); return -1; }
+    if (int rc = ccsx_stage_align(h, r, rstart, cap, valid, score)) return rc;
+    const Slot &S = h->slot[0];
+    const int z = (int)(std::upper_bound(S.read_off.p, S.read_off.p + S.P.n_zmw + 1, r) - S.read_off.p) - 1;
+    int32_t L = 0;
+    HIPTRY(hipMemcpy(&L, S.P.draft_len + z, 4, hipMemcpyDeviceToHost));
+    if (L > dirty_cap) { ccsx_set_error("ccsx_stage_align_ev: buffer too small"); return -1; }
+    for (int p = 0; p < L; ++p) dirty[p] = 0;
+    if (*valid) {
+        std::vector<int32_t> wb;
+        const int nw = stage_bounds(S, z, L, wb);
+        if (nw < 0) return nw;
+        std::vector<uint32_t> dm(2 * nw);
+        HIPTRY(hipMemcpy(dm.data(), S.P.dmask + S.ent_off[r], dm.size() * 4, hipMemcpyDeviceToHost));
+        auto col = [&](int k) { return (k == 0) ? 0 : (k == 2 * nw - 1) ? L : wb[(k + 1) >> 1] + ((k & 1) ? -CCSX_WIN_OVERHANG : CCSX_WIN_OVERHANG); };
+        for (int k = 1; k < 2 * nw; ++k)
+            for (int p = col(k - 1); p < col(k); ++p) dirty[p] = (p - col(k - 1) < 32) ? (uint8_t)((dm[k] >> (p - col(k - 1))) & 1u) : 0;
+    }
+    return 0;
+}
+
 // the converged window templates k_polish kept (a run staged with kinetics or the pileup summary): per window the template, J and [cs, ce)
 int ccsx_stage_polished(ccsx_handle h, int32_t z, uint8_t *tpl, int32_t *meta, int32_t cap, int32_t *n_windows, int32_t *passes_used, int32_t *backbone)
 {

@@ -1413,8 +1413,8 @@ __device__ __forceinline__ AlignEnd align_pass(const KParams &P, const uint32_t 
 // step 3, first attempt of the alignment cascade (SPEC "alignment cascade"): FOUR passes of one ZMW per wave, each in a 16-row band
 // that lives in one 16-lane DPP row — row shifts, the insertion-chain scan and the column maximum are native row operations
 // (row_shr / row_shl with the hardware's fill, 4-step scans), the band position is a per-lane value that is uniform inside a row.
-// The band follows the best row, so this finds the path of the 64-row band unless an indel run of more than ~8 rows occurs
-// (bit-identical consensus on the test sets); a pass that is not valid here goes on a list for the 64-row retry (k_align), and
+// The band follows the best row, so this finds the path of the 64-row band unless an insertion run of more than 5 or a deleted stretch
+// of 6 or more bases occurs (tests/align_lab.py; bit-identical consensus on the test sets); a pass that is not valid here goes on a list for the 64-row retry (k_align), and
 // from there to the split alignment.  Same cell recurrence as align_pass.
 // Round 5 (second session): the cells no longer carry (origin, dirty bits) through the DP — three values to shift, select and permute per cell instead of one.
 // Every cell's MOVE goes to HBM instead (2 bits: diagonal match / diagonal mismatch / deletion / insertion; a lane shifts the two predicate masks of a column into a

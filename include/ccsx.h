@@ -278,6 +278,12 @@ int         ccsx_stage_draft(ccsx_handle h, int32_t zmw_index, uint8_t *draft, i
 int         ccsx_stage_align(ccsx_handle h, int32_t read_index, int32_t *rstart, int32_t cap,
                              int32_t *valid, int32_t *score);
 int         ccsx_stage_windows(ccsx_handle h, int32_t zmw_index, int32_t *bounds, int32_t cap, int32_t *n_windows);
+/* ccsx_stage_align plus the pass's pile-up evidence: rstart / valid / score exactly as ccsx_stage_align reports them, and dirty[p] (p < draft length <= dirty_cap)
+ * = 1 iff the pass's dirty bit of draft position p is set, unpacked on the host from the per-interval masks the alignment kernels leave (interval k = the positions
+ * from window-edge column k - 1 up to edge column k, bit p - column(k - 1)): the bits as k_polish's candidate filter reads them for that pass.  Every position of a
+ * split or partial pass is 1; dirty[] of a pass that is not valid is 0.  For parity tests (tests/test_align_gpu.py).                                            */
+int         ccsx_stage_align_ev(ccsx_handle h, int32_t read_index, int32_t *rstart, int32_t cap, int32_t *valid, int32_t *score,
+                                uint8_t *dirty, int32_t dirty_cap);
 
 /* ---- the heteroduplex finder (docs/faq/mode-heteroduplex-filtering.md:25-33, docs/how-does-ccs-work.md:65-72; the rule: DESIGN.md §2 "Heteroduplex rule").
  * ccsx_hd_batch is the third seam beside ccsx_draft_batch and ccsx_polish_batch: on the caller's drafts it runs the polish seam's alignment cascade and window map,

@@ -109,6 +109,9 @@ static void orc_counts_flush(void)
         orc_cnt[k] = 0;
     }
 }
+/* the calling thread's tallies into the global sums now: for a caller that drives the per-pass functions (orc_align_ev_w, orc_align_rescue, orc_align_partial)
+ * itself and reads orc_counts_get after each pass */
+void orc_counts_sync(void) { orc_counts_flush(); }
 static __thread int g_poa_scores[64], g_poa_nscores = 0;   /* test hook: end scores of the passes threaded into the last POA */
 int orc_poa_last_scores(int *out) { for (int i = 0; i < g_poa_nscores; ++i) out[i] = g_poa_scores[i]; return g_poa_nscores; }
 #define MAX_PASSES 255      /* passes of a ZMW that are used (include/ccsx.h CCSX_MAX_PASSES) */
@@ -574,7 +577,7 @@ int orc_poa_draft(int nreads, const int64_t *base_off, const uint8_t *bases, con
 static int align_ev_band(const uint8_t *r, int I, const uint8_t *d, int Ld, int32_t *rstart, int32_t *score_out, uint8_t *dirty,
                          const int32_t *need, int nneed, int *sat_out);
 /* SPEC "alignment cascade": the banded global alignment is first tried with ALIGN_BAND1 rows (the band follows the best row, so
- * this finds the same path as the wide band unless an indel run of more than ~ALIGN_BAND1/2 rows occurs); a pass that is not valid
+ * this finds the same path as the wide band unless an insertion run of more than 5 or a deleted stretch of 6 or more bases occurs: DESIGN.md §2); a pass that is not valid
  * in the narrow band is aligned again with BAND rows (and, failing that, by the split alignment).                             */
 int orc_windows(const uint8_t *d, int Ld, int32_t *b, int cap);
 /* SPEC v5 "band saturation": a pass whose narrow-band alignment is valid is STILL aligned again with BAND rows when the narrow band

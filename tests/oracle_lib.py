@@ -242,3 +242,73 @@ def edit_distance(a, b, band=400):
 
 def spec_version():
     return int(lib().orc_spec_version())
+
+
+def need_cols(draft):
+    """the window-edge columns 0, b1 - 2, b1 + 2, ..., Ld of a draft (the `need` list of the alignment functions), from windows()"""
+    wb = windows(draft)
+    return np.array([0] + [int(b) + s for b in wb[1:-1] for s in (-2, 2)] + [len(draft)], np.int32)
+
+
+def _align_call(fn, read, draft, need, *mid):
+    r = np.ascontiguousarray(read, np.uint8)
+    d = np.ascontiguousarray(draft, np.uint8)
+    need = np.ascontiguousarray(need, np.int32)
+    rs = np.full(len(d) + 1, -1, np.int32)
+    dirty = np.zeros(len(d) + 1, np.uint8)
+    sc = C.c_int32()
+    v = fn(_p(r, C.c_uint8), len(r), _p(d, C.c_uint8), len(d), _p(need, C.c_int32), len(need), *mid, _p(rs, C.c_int32), C.byref(sc), _p(dirty, C.c_uint8))
+    if not v: dirty[:] = 0
+    return rs, int(v), sc.value, dirty[: len(d)]
+
+
+def align_ev_w(read_oriented, draft, need, wide=0):
+    """orc_align_ev_w: the 16-row attempt with its saturation triggers, then 64 rows (wide = 1: 64 rows at once) -> (rstart, valid, score, dirty)"""
+    return _align_call(lib().orc_align_ev_w, read_oriented, draft, need, int(wide))
+
+
+def align_rescue(read_oriented, draft, need):
+    """orc_align_rescue: the split and the double split -> (rstart, valid, score, dirty)"""
+    return _align_call(lib().orc_align_rescue, read_oriented, draft, need)
+
+
+def align_partial(read_oriented, draft, need, from_end):
+    """orc_align_partial: a pass anchored at the draft's start (from_end = 0) or end -> (rstart, valid, score, dirty)"""
+    return _align_call(lib().orc_align_partial, read_oriented, draft, need, int(from_end))
+
+
+def sat_triggers(rows=1, gain=1):
+    """the two band-saturation triggers of the 16-row attempt (SPEC v5): rows = 0 switches (a) off, a very negative gain (b); the defaults restore the SPEC"""
+    lib().orc_set_sat_rows(int(rows)); lib().orc_set_sat_gain(int(gain))
+
+
+ROUTES = ("narrow", "wide_invalid", "wide_saturated", "split", "split_s0", "split_sLd", "split2", "partial", "lost")
+
+
+def route(read_oriented, draft, partial=None, wide=0):
+    """The alignment cascade of orc_consensus_zmw for ONE pass (oriented like the draft), between counts_reset() and counts(): which way it went — one of ROUTES
+    (or "wide" where wide = 1 skipped the 16-row attempt) — and the oracle's (rstart, valid, score, dirty) of that way.  partial: None for a full-length pass, else
+    from_end of a partial one."""
+    L = lib()
+    need = need_cols(draft)
+    L.orc_counts_sync(); counts_reset()
+    if partial is not None:
+        out = align_partial(read_oriented, draft, need, partial) if len(need) >= 2 else (np.full(len(draft) + 1, -1, np.int32), 0, 0, np.zeros(len(draft), np.uint8))
+        L.orc_counts_sync(); c = counts()
+        assert c["partial_used"] == out[1]
+        return ("partial" if out[1] else "lost",) + out
+    out = align_ev_w(read_oriented, draft, need, wide)
+    first = out[1]
+    if not first and len(read_oriented) - len(draft) > 24 and len(need) >= 3:
+        res = align_rescue(read_oriented, draft, need)
+        if res[1]: out = res                                  # (a pass the rescue does not take either keeps the 64-row attempt's score)
+    L.orc_counts_sync(); c = counts()
+    if first: name = "wide" if wide else "narrow" if not c["retry64"] else "wide_saturated" if c["saturated"] else "wide_invalid"
+    elif not out[1]: name = "lost"
+    elif c["split2"]: name = "split2"
+    elif c["split_s0"]: name = "split_s0"
+    elif c["split_sLd"]: name = "split_sLd"
+    else:
+        assert c["split"] == 1
+        name = "split"
+    return (name,) + out
