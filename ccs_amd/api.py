@@ -118,43 +118,55 @@ def hd_opts_default() -> HdOpts:
     return o
 
 
-@dataclass
-class HdReport:
-    """ccsx_hd_report: one verdict per ZMW, the site counts and the listed sites (structured array [n_zmw, HD_MAX_SITES] of HD_SITE_DTYPE)."""
-    verdict: np.ndarray
-    n_sub_sites: np.ndarray
-    n_indel_sites: np.ndarray
-    n_listed: np.ndarray
-    min_p: np.ndarray
-    sites: np.ndarray
-    status: np.ndarray
+class _PlaneReport:
+    """What the reports of the optional analyses share.  PLANES lists the arrays as (name, dtype, per-ZMW shape); each is an attribute of that name, [n_zmw, *shape],
+    and the pointer of that name in CSTRUCT, the report's ctypes struct.  Plain classes, not dataclasses: built by allocate() or from the arrays in PLANES
+    order, without keyword construction, __repr__ or field-wise __eq__ (compare the arrays); _pinned holds the page-locked blocks, empty when not pinned."""
+    PLANES: tuple = ()
+    CSTRUCT = None
 
-    @staticmethod
-    def allocate(n: int, pinned: bool = False) -> "HdReport":
-        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(hd=...), downloads into them asynchronously)"""
-        if not pinned:
-            z = lambda: np.zeros(n, np.int32)
-            return HdReport(z(), z(), z(), z(), np.ones(n), np.zeros((n, HD_MAX_SITES), HD_SITE_DTYPE), z())
+    def __init__(self, *arrays):
+        for (k, _, _), a in zip(self.PLANES, arrays, strict=True):
+            setattr(self, k, a)
+
+    @classmethod
+    def allocate(cls, n: int, pinned: bool = False):
+        """every array zeroed.  pinned=True: page-locked arrays (the ticketed form, Handle.submit, downloads into them asynchronously)"""
         keep = []
 
-        def z(count, dt):
-            a = _pinned_array(count, dt, keep)
-            a[...] = 0
-            return a
-        rep = HdReport(z(n, np.int32), z(n, np.int32), z(n, np.int32), z(n, np.int32), z(n, np.float64),
-                       z(n * HD_MAX_SITES, HD_SITE_DTYPE).reshape(n, HD_MAX_SITES), z(n, np.int32))
-        rep.min_p[...] = 1.0
+        def z(dt, shape):
+            count = n * int(np.prod(shape, dtype=np.int64))
+            a = _pinned_array(count, dt, keep) if pinned else np.empty(count, dt)
+            a.view(np.uint8)[...] = 0
+            return a.reshape((n,) + shape)
+        rep = cls(*(z(dt, shape) for _, dt, shape in cls.PLANES))
         rep._pinned = keep
         return rep
 
-    def c_struct(self) -> CHdReport:
-        r = CHdReport()
+    def c_struct(self):
+        r = self.CSTRUCT()
         r.n_zmw = len(self.verdict)
-        r.verdict, r.n_sub_sites, r.n_indel_sites, r.n_listed, r.status = (
-            _ptr(a, C.c_int32) for a in (self.verdict, self.n_sub_sites, self.n_indel_sites, self.n_listed, self.status))
-        r.min_p = _ptr(self.min_p, C.c_double)
-        r.sites = self.sites.ctypes.data_as(C.POINTER(HdSite))
+        types = dict(self.CSTRUCT._fields_)
+        for k, _, _ in self.PLANES:
+            setattr(r, k, getattr(self, k).ctypes.data_as(types[k]))
         return r
+
+
+def _int_planes(*names) -> tuple:
+    return tuple((k, np.int32, ()) for k in names)
+
+
+class HdReport(_PlaneReport):
+    """ccsx_hd_report: one verdict per ZMW, the site counts and the listed sites (structured array [n_zmw, HD_MAX_SITES] of HD_SITE_DTYPE)."""
+    PLANES = _int_planes("verdict", "n_sub_sites", "n_indel_sites", "n_listed") + (("min_p", np.float64, ()), ("sites", HD_SITE_DTYPE, (HD_MAX_SITES,))) \
+        + _int_planes("status")
+    CSTRUCT = CHdReport
+
+    @classmethod
+    def allocate(cls, n: int, pinned: bool = False) -> "HdReport":
+        rep = super().allocate(n, pinned)
+        rep.min_p[...] = 1.0
+        return rep
 
     def site_list(self, z: int) -> np.ndarray:
         return self.sites[z, : int(self.n_listed[z])]
@@ -184,30 +196,10 @@ def fold_opts_default() -> FoldOpts:
     return o
 
 
-@dataclass
-class FoldReport:
+class FoldReport(_PlaneReport):
     """ccsx_fold_report: per ZMW the verdict (FOLD_*), the fold centre in draft coordinates (-1: no hit), the hits and the span of the winning bins."""
-    verdict: np.ndarray
-    fold: np.ndarray
-    hits: np.ndarray
-    span: np.ndarray
-
-    @staticmethod
-    def allocate(n: int, pinned: bool = False) -> "FoldReport":
-        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(fold=...), downloads into them asynchronously)"""
-        keep = []
-        z = (lambda: _pinned_array(n, np.int32, keep)) if pinned else (lambda: np.empty(n, np.int32))
-        rep = FoldReport(z(), z(), z(), z())
-        for a in (rep.verdict, rep.fold, rep.hits, rep.span):
-            a[...] = 0
-        rep._pinned = keep
-        return rep
-
-    def c_struct(self) -> CFoldReport:
-        r = CFoldReport()
-        r.n_zmw = len(self.verdict)
-        r.verdict, r.fold, r.hits, r.span = (_ptr(a, C.c_int32) for a in (self.verdict, self.fold, self.hits, self.span))
-        return r
+    PLANES = _int_planes("verdict", "fold", "hits", "span")
+    CSTRUCT = CFoldReport
 
 
 def _fold_request(opts: "FoldOpts | None", crep: CFoldReport) -> tuple[CFoldRequest, FoldOpts]:
@@ -273,43 +265,12 @@ def adapter_opts_default() -> AdapterOpts:
     return o
 
 
-@dataclass
-class AdapterReport:
+class AdapterReport(_PlaneReport):
     """ccsx_adapter_report: per ZMW tested (0 / 1), the verdict bits (ADAPTER_CONCAT | ADAPTER_NEAR_END), the aggregates over every hit, and the first 16 hits
     in increasing (end, search) as a structured array [n_zmw, 16] (ADAPTER_HIT)"""
-    tested: np.ndarray
-    verdict: np.ndarray
-    n_hits: np.ndarray
-    n_listed: np.ndarray
-    covered: np.ndarray
-    max_gap: np.ndarray
-    first_start: np.ndarray
-    last_end: np.ndarray
-    min_dist: np.ndarray
-    hits: np.ndarray
-
     INT_FIELDS = ("tested", "verdict", "n_hits", "n_listed", "covered", "max_gap", "first_start", "last_end", "min_dist")
-
-    @staticmethod
-    def allocate(n: int, pinned: bool = False) -> "AdapterReport":
-        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(adapters=...), downloads into them asynchronously)"""
-        keep = []
-        z = (lambda: _pinned_array(n, np.int32, keep)) if pinned else (lambda: np.empty(n, np.int32))
-        hits = _pinned_array(n * ADAPTER_MAX_HITS, ADAPTER_HIT, keep) if pinned else np.empty(n * ADAPTER_MAX_HITS, ADAPTER_HIT)
-        rep = AdapterReport(*(z() for _ in AdapterReport.INT_FIELDS), hits.reshape(n, ADAPTER_MAX_HITS))
-        for k in AdapterReport.INT_FIELDS:
-            getattr(rep, k)[...] = 0
-        rep.hits.view(np.uint8)[...] = 0
-        rep._pinned = keep
-        return rep
-
-    def c_struct(self) -> CAdapterReport:
-        r = CAdapterReport()
-        r.n_zmw = len(self.verdict)
-        for k in AdapterReport.INT_FIELDS:
-            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
-        r.hits = self.hits.ctypes.data
-        return r
+    PLANES = _int_planes(*INT_FIELDS) + (("hits", ADAPTER_HIT, (ADAPTER_MAX_HITS,)),)
+    CSTRUCT = CAdapterReport
 
     def listed(self, z: int) -> list:
         """the listed hits of ZMW z as (start, end, search, dist)"""
@@ -367,38 +328,12 @@ def control_opts_default() -> ControlOpts:
     return o
 
 
-@dataclass
-class ControlReport:
+class ControlReport(_PlaneReport):
     """ccsx_control_report: per ZMW the verdict (CONTROL_*), the strand (-1: no hit), the hits of the winning pair of diagonal bins, the distinct control
     positions among them and the control and draft bases they span"""
-    verdict: np.ndarray
-    strand: np.ndarray
-    hits: np.ndarray
-    matched: np.ndarray
-    ctl_start: np.ndarray
-    ctl_end: np.ndarray
-    draft_start: np.ndarray
-    draft_end: np.ndarray
-
     FIELDS = ("verdict", "strand", "hits", "matched", "ctl_start", "ctl_end", "draft_start", "draft_end")
-
-    @staticmethod
-    def allocate(n: int, pinned: bool = False) -> "ControlReport":
-        """pinned=True: page-locked arrays (the ticketed form, Handle.submit(control=...), downloads into them asynchronously)"""
-        keep = []
-        z = (lambda: _pinned_array(n, np.int32, keep)) if pinned else (lambda: np.empty(n, np.int32))
-        rep = ControlReport(*(z() for _ in ControlReport.FIELDS))
-        for k in ControlReport.FIELDS:
-            getattr(rep, k)[...] = 0
-        rep._pinned = keep
-        return rep
-
-    def c_struct(self) -> CControlReport:
-        r = CControlReport()
-        r.n_zmw = len(self.verdict)
-        for k in ControlReport.FIELDS:
-            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
-        return r
+    PLANES = _int_planes(*FIELDS)
+    CSTRUCT = CControlReport
 
 
 def _control_request(seq: ControlSeq, opts: "ControlOpts | None", crep: CControlReport):
@@ -968,16 +903,17 @@ def _extras(cp: "CPileup | None", tandem: "np.ndarray | None", min_len: int) -> 
 def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None, min_tandem_repeat_length: int = 0,
               hd: "HdReport | None" = None, hd_opts: "HdOpts | None" = None, hd_split: bool = False,
               fold: "FoldReport | None" = None, fold_opts: "FoldOpts | None" = None,
-              adapters: "AdapterReport | None" = None, adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None):
-    """The ctypes side of what one fused run is asked for beside the consensus: (CExtras, CHdRequest, CFoldRequest, CAdapterRequest, keep), each request None
-    where its report (for the extras: all of pileup, tandem and the threshold) is.  keep owns every array and struct the requests point to: it must
-    outlive the call, or the ticket"""
-    keep = [pileup, tandem, hd, fold, adapters]
+              adapters: "AdapterReport | None" = None, adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None,
+              control: "ControlReport | None" = None, control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None):
+    """The ctypes side of what one fused run is asked for beside the consensus: (CExtras, CHdRequest, CFoldRequest, CAdapterRequest, CControlRequest, keep), each
+    request None where its report (for the extras: all of pileup, tandem and the threshold) is.  keep owns every array and struct the requests point to: it
+    must outlive the call, or the ticket"""
+    keep = [pileup, tandem, hd, fold, adapters, control]
 
     def own(x):
         keep.append(x)
         return x
-    ex = hq = fq = aq = None
+    ex = hq = fq = aq = cq = None
     if pileup is not None or tandem is not None or min_tandem_repeat_length:
         ex = own(_extras(own(pileup.c_struct()) if pileup is not None else None, tandem, min_tandem_repeat_length))
     if hd is not None:
@@ -987,7 +923,9 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
         fq = own(_fold_request(fold_opts, own(fold.c_struct())))[0]
     if adapters is not None:
         aq = own(_adapter_request(adapter_set, adapter_opts, own(adapters.c_struct())))[0]
-    return ex, hq, fq, aq, keep
+    if control is not None:
+        cq = own(_control_request(control_seq, control_opts, own(control.c_struct())))[0]
+    return ex, hq, fq, aq, cq, keep
 
 
 class Handle:
@@ -1006,6 +944,15 @@ class Handle:
     def _check(self, rc, what):
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
+
+    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket):
+        """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
+        ccsx_*_hd with a heteroduplex request, which combines with none of the screens, else ccsx_*_control (NULL: not asked for).  Returns the C structs"""
+        ex, hq, fq, aq, cq, _keep = requests
+        name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
+        cb, cr = batch.c_struct(), res.c_struct()
+        self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
+        return cb, cr
 
     def consensus(self, batch: Batch) -> Results:
         res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
@@ -1038,8 +985,7 @@ class Handle:
     def consensus_pileup(self, batch: Batch) -> tuple["Results", "Pileup"]:
         res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
         pile = Pileup.allocate(res)
-        cb, cr, cp = batch.c_struct(), res.c_struct(), pile.c_struct()
-        self._check(self._L.ccsx_consensus_pileup(self._h, C.byref(cb), C.byref(cr), C.byref(cp)), "ccsx_consensus_pileup")
+        self._fused("consensus", batch, res, _requests(pile))
         return res, pile
 
     def _outputs(self, batch: Batch, tandem: bool, pileup: bool):
@@ -1053,8 +999,7 @@ class Handle:
         """ccsx_consensus_extras: (results, tandem_len [n_zmw] int32 or None, pileup or None).  min_tandem_repeat_length > 0: ZMWs whose deciding
         draft has a masked run at least that long run with the heuristics off (as opts.disable_heuristics), the others as usual"""
         res, tl, pile = self._outputs(batch, tandem, pileup)
-        ex, _, _, _, _keep = _requests(pile, tl, min_tandem_repeat_length)
-        self._check(self._L.ccsx_consensus_extras(self._h, batch.c_struct(), res.c_struct(), ex), "ccsx_consensus_extras")
+        self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length))
         return res, tl, pile
 
     # ---- the heteroduplex finder in the fused path (ccsx_consensus_hd): the consensus and the finder's report of one run
@@ -1064,16 +1009,14 @@ class Handle:
         split=False: detection only, the results are those of consensus_extras"""
         res, tl, pile = self._outputs(batch, tandem, pileup)
         rep = HdReport.allocate(batch.n_zmw)
-        ex, q, _, _, _keep = _requests(pile, tl, min_tandem_repeat_length, hd=rep, hd_opts=opts, hd_split=split)
-        self._check(self._L.ccsx_consensus_hd(self._h, batch.c_struct(), res.c_struct(), ex, q), "ccsx_consensus_hd")
+        self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length, hd=rep, hd_opts=opts, hd_split=split))
         return res, rep, tl, pile
 
     # ---- adapter palindromes in the fused path (ccsx_consensus_fold): the consensus and the detector's report of one run (detection only)
     def consensus_fold(self, batch: Batch, opts: FoldOpts | None = None) -> tuple["Results", FoldReport]:
         res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
         rep = FoldReport.allocate(batch.n_zmw)
-        _, _, q, _, _keep = _requests(fold=rep, fold_opts=opts)
-        self._check(self._L.ccsx_consensus_fold(self._h, batch.c_struct(), res.c_struct(), None, q), "ccsx_consensus_fold")
+        self._fused("consensus", batch, res, _requests(fold=rep, fold_opts=opts))
         return res, rep
 
     # ---- both draft detectors in one run (ccsx_consensus_screen): adapter palindromes and / or the adapter screen, with the optional outputs of ccsx_extras
@@ -1084,9 +1027,8 @@ class Handle:
         res, tl, pile = self._outputs(batch, tandem, pileup)
         frep = FoldReport.allocate(batch.n_zmw) if fold else None
         arep = AdapterReport.allocate(batch.n_zmw) if adapters is not None else None
-        ex, _, fq, aq, _keep = _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
-                                         adapters=arep, adapter_set=adapters, adapter_opts=opts)
-        self._check(self._L.ccsx_consensus_screen(self._h, batch.c_struct(), res.c_struct(), ex, fq, aq), "ccsx_consensus_screen")
+        self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
+                                                       adapters=arep, adapter_set=adapters, adapter_opts=opts))
         return res, frep, arep, tl, pile
 
     # ---- the control screen (ccsx_consensus_control), alone or with the other draft detectors and the optional outputs of ccsx_extras
@@ -1099,11 +1041,9 @@ class Handle:
         crep = ControlReport.allocate(batch.n_zmw)
         frep = FoldReport.allocate(batch.n_zmw) if fold else None
         arep = AdapterReport.allocate(batch.n_zmw) if adapters is not None else None
-        ex, _, fq, aq, _keep = _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
-                                         adapters=arep, adapter_set=adapters, adapter_opts=adapter_opts)
-        ccrep = crep.c_struct()
-        cq, _keep2 = _control_request(control, opts, ccrep)
-        self._check(self._L.ccsx_consensus_control(self._h, batch.c_struct(), res.c_struct(), ex, fq, aq, cq), "ccsx_consensus_control")
+        self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
+                                                       adapters=arep, adapter_set=adapters, adapter_opts=adapter_opts,
+                                                       control=crep, control_seq=control, control_opts=opts))
         return res, crep, frep, arep, tl, pile
 
     def stage_polished(self, z: int):
@@ -1144,14 +1084,13 @@ class Handle:
                fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None, adapters: "AdapterReport | None" = None,
                adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, control: "ControlReport | None" = None,
                control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None) -> int:
-        """pileup: also the pileup summary's planes (ccsx_submit_pileup), complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer,
-        pinned) that receives tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs (ccsx_submit_extras).  hd: a report
-        (HdReport.allocate(n, pinned=True)) that receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish
-        stage (ccsx_submit_hd).  fold: a report (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts (ccsx_submit_fold;
-        not combined with hd).  adapters: a report (AdapterReport.allocate(n, pinned=True)) that receives the adapter screen of adapter_set (None: the built-in
-        set) under adapter_opts, alone or together with fold (ccsx_submit_screen; not combined with hd).  control: a report (ControlReport.allocate(n,
-        pinned=True)) that receives the control screen for control_seq under control_opts, alone or with fold and adapters (ccsx_submit_control; not combined
-        with hd).  Every ticket carries its own control: tickets in flight may screen for different ones"""
+        """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
+        tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
+        receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd).  fold: a report
+        (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts.  adapters: a report (AdapterReport.allocate(n, pinned=True))
+        that receives the adapter screen of adapter_set (None: the built-in set) under adapter_opts.  control: a report (ControlReport.allocate(n,
+        pinned=True)) that receives the control screen for control_seq under control_opts.  fold, adapters and control go alone or together
+        (ccsx_submit_control), none of them with hd.  Every ticket carries its own control: tickets in flight may screen for different ones"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
@@ -1162,32 +1101,13 @@ class Handle:
             raise ValueError("the heteroduplex request and the control screen are not combined")
         if control is not None and control_seq is None:
             raise ValueError("control: a control_seq is needed (there is no built-in control)")
-        ex, hq, fq, aq, keep = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts)
-        cq = None
-        if control is not None:
-            ccrep = control.c_struct()
-            cq, k2 = _control_request(control_seq, control_opts, ccrep)
-            keep += [control, ccrep, cq, k2]
-        # the narrowest entry point that expresses the request (so that every exported ccsx_submit_* is in use)
-        if cq is not None:
-            name, extra = "ccsx_submit_control", (ex, fq, aq, cq)
-        elif aq is not None:
-            name, extra = "ccsx_submit_screen", (ex, fq, aq)
-        elif fq is not None:
-            name, extra = "ccsx_submit_fold", (ex, fq)
-        elif hq is not None:
-            name, extra = "ccsx_submit_hd", (ex, hq)
-        elif tandem is not None or min_tandem_repeat_length:
-            name, extra = "ccsx_submit_extras", (ex,)
-        elif pileup is not None:
-            name, extra = "ccsx_submit_pileup", (ex.pile,)
-        else:
-            name, extra = "ccsx_submit", ()
-        cb, cr, t = batch.c_struct(), res.c_struct(), C.c_int64()
-        self._check(getattr(self._L, name)(self._h, cb, cr, *extra, t), name)
+        requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
+                             control, control_seq, control_opts)
+        t = C.c_int64()
+        cb, cr = self._fused("submit", batch, res, requests, t)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
-        self._inflight[t.value] = (batch, res, cb, cr, keep)      # the C structs and arrays must outlive the ticket
+        self._inflight[t.value] = (batch, res, cb, cr, requests)  # the C structs and arrays must outlive the ticket
         return t.value
 
     def wait(self, ticket: int) -> "Results":

@@ -143,12 +143,12 @@ struct Batch {
     int dev = 0;                  // which device's packers / worker / staging pools handle the batch (index into the handle list)
     bool have_results = false;    // false: packing or the engine failed for this batch
     std::unique_ptr<struct Arena> in_arena, out_arena;
-    ccsx_batch cb; ccsx_results cr; // the structs handed to ccsx_submit live as long as the ticket
-    ccsx_pileup cp{};               // ... and the one handed to ccsx_submit_pileup
-    ccsx_extras ex{};               // (ccsx_submit_extras reads it during the call only)
-    ccsx_fold_report frep{}; ccsx_fold_request freq{};   // (ccsx_submit_fold: the report's arrays are in out_arena)
-    ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_submit_screen: the report's arrays are in out_arena)
-    ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_submit_control: the report's arrays are in out_arena)
+    ccsx_batch cb; ccsx_results cr; // the structs handed to ccsx_submit_control live as long as the ticket
+    ccsx_pileup cp{};               // ... and so does the pileup the extras point to
+    ccsx_extras ex{};               // (read during the call only)
+    ccsx_fold_report frep{}; ccsx_fold_request freq{};   // --fail-reads (ccsx_fold_request: the report's arrays are in out_arena)
+    ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_adapter_request: the report's arrays are in out_arena)
+    ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_control_request: the report's arrays are in out_arena)
 };
 
 template <class T> class Channel {
@@ -1074,6 +1074,7 @@ int main(int argc, char **argv)
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
                         uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
+                        auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
                         b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
                         b->rq = (float *)take(n4); b->ec = (float *)take(n4);
@@ -1094,21 +1095,19 @@ int main(int argc, char **argv)
                             b->ex = ccsx_extras{opt.pileup ? &b->cp : nullptr, b->tlen, opt.min_tandem, 0};
                         } else if (opt.pileup) b->ex = ccsx_extras{&b->cp, nullptr, 0, 0};
                         if (fail_reads) {
-                            int32_t *fv = (int32_t *)take(n4), *ff = (int32_t *)take(n4), *fh = (int32_t *)take(n4), *fs = (int32_t *)take(n4);
-                            b->fold = fv;
-                            b->frep = ccsx_fold_report{n, fv, ff, fh, fs};
+                            const auto f = planes(4);
+                            b->fold = f[0];
+                            b->frep = ccsx_fold_report{n, f[0], f[1], f[2], f[3]};
                             b->freq = ccsx_fold_request{nullptr, &b->frep, {0, 0}};
                         }
                         if (screen) {
-                            int32_t *a9[9];
-                            for (auto &p : a9) p = (int32_t *)take(n4);
+                            const auto a9 = planes(9);
                             ccsx_adapter_hit *hits = (ccsx_adapter_hit *)take(3 * CCSX_ADAPTER_MAX_HITS * n4);
                             b->arep = ccsx_adapter_report{n, a9[0], a9[1], a9[2], a9[3], a9[4], a9[5], a9[6], a9[7], a9[8], hits};
                             b->areq = ccsx_adapter_request{&opt.adapter_set, nullptr, &b->arep, {0, 0}};
                         }
                         if (control) {
-                            int32_t *c8[8];
-                            for (auto &p : c8) p = (int32_t *)take(n4);
+                            const auto c8 = planes(8);
                             b->crep = ccsx_control_report{n, c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]};
                             b->creq = ccsx_control_request{&opt.control_seq, nullptr, &b->crep, {0, 0}};
                         }
@@ -1172,12 +1171,9 @@ int main(int argc, char **argv)
                 if (inflight.size() >= 3) retire();
                 t0 = now();
                 ccsx_ticket t = -1;
-                const ccsx_extras *ex = (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr;
-                if (control ? ccsx_submit_control(h, &b->cb, &b->cr, ex, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr, &b->creq, &t)
-                    : screen ? ccsx_submit_screen(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &b->areq, &t)
-                    : fail_reads ? ccsx_submit_fold(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, &b->freq, &t)
-                    : opt.min_tandem > 0 ? ccsx_submit_extras(h, &b->cb, &b->cr, &b->ex, &t)
-                                       : (opt.pileup ? ccsx_submit_pileup(h, &b->cb, &b->cr, &b->cp, &t) : ccsx_submit(h, &b->cb, &b->cr, &t))) {
+                // the most general submit: NULL for the extras and for every request this run did not ask for (the narrower entry points stage the same)
+                if (ccsx_submit_control(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr,
+                                        screen ? &b->areq : nullptr, control ? &b->creq : nullptr, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -361,6 +362,22 @@ static int64_t longest_draft(ccsx_handle h, const Slot &S, int32_t floor)
     int64_t longest = floor;
     for (size_t z = 0; z < S.dcap.size(); ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
     return std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, floor));
+}
+
+// `units`: the LDS units (histogram bins, bitmap words) a draft screen's kernel needs for the slot's longest draft; -1, refused under the screen's name, when they
+// exceed what its LDS holds (nothing has been enqueued by the request then)
+static int64_t screen_units(int64_t longest, int64_t units, int64_t max_units, const char *screen)
+{
+    if (units <= max_units) return units;
+    ccsx_set_error(std::string(screen) + ": drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)");
+    return -1;
+}
+
+// a report of [k][n] int32 planes into the caller's k arrays, copied on `s`
+static int download_planes(std::initializer_list<int32_t *> dst, const int32_t *src, size_t n, hipStream_t s)
+{
+    for (int32_t *d : dst) { HIPTRY(hipMemcpyAsync(d, src, n * 4, hipMemcpyDeviceToHost, s)); src += n; }
+    return 0;
 }
 
 static int validate(const ccsx_batch *b)
@@ -825,24 +842,13 @@ static int fold_request_check(const ccsx_fold_request *q, const ccsx_batch *b, c
     return 0;
 }
 
-// k_fold's LDS histogram covers the longest draft the cascade aligns (longest_draft); -1 when that is beyond its LDS bound (nothing enqueued yet by this
-// call's request)
+// k_fold's LDS histogram covers the longest draft the cascade aligns (screen_units); -1 when that is beyond its LDS bound
 static int fold_attach(ccsx_handle h, Slot &S, const ccsx_fold_opts &o)
 {
-    const int n = S.P.n_zmw;
-    const int64_t longest = longest_draft(h, S, 16);
-    const int64_t bins = ((2 * longest - CCSX_FOLD_K - 1) >> 6) + 2;
-    if (bins > CCSX_FOLD_MAX_BINS) { ccsx_set_error("adapter-palindrome detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
-    if (S.d_fold.reserve((size_t)n * 16)) return -2;
+    const int64_t l = longest_draft(h, S, 16), bins = screen_units(l, ((2 * l - CCSX_FOLD_K - 1) >> 6) + 2, CCSX_FOLD_MAX_BINS, "adapter-palindrome detection");
+    if (bins < 0) return -1;
+    if (S.d_fold.reserve((size_t)S.P.n_zmw * 16)) return -2;
     S.P.fold = o; S.P.fold_zi = (int32_t *)S.d_fold.p; S.P.fold_bins = (int32_t)bins;
-    return 0;
-}
-
-static int enqueue_fold_download(const Slot &S, ccsx_fold_report *r, hipStream_t s)
-{
-    const size_t n = (size_t)S.P.n_zmw;
-    int32_t *dst[4] = {r->verdict, r->fold, r->hits, r->span};
-    for (int k = 0; k < 4; ++k) HIPTRY(hipMemcpyAsync(dst[k], S.P.fold_zi + k * n, n * 4, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -871,15 +877,14 @@ static int adapter_request_check(const ccsx_adapter_request *q, const ccsx_batch
     return 0;
 }
 
-// k_adapter's two LDS bitmaps are sized from the longest draft the cascade aligns (longest_draft), so a handle opened with a larger max_length gets larger
-// bitmaps; -1 when that is beyond their LDS bound (nothing enqueued yet by this call's request)
+// k_adapter's two LDS bitmaps are sized from the longest draft the cascade aligns (screen_units), so a handle opened with a larger max_length gets larger
+// bitmaps; -1 when that is beyond their LDS bound
 static int adapter_attach(ccsx_handle h, Slot &S, const ccsx_adapter_set &set, const ccsx_adapter_opts &o)
 {
     static_assert(sizeof(ccsx_adapter_hit) == 12, "k_adapter writes a hit as three words");
     const int n = S.P.n_zmw;
-    const int64_t longest = longest_draft(h, S, 32);
-    const int64_t words = (longest + 31) >> 5;
-    if (words > CCSX_ADAPTER_MAX_WORDS) { ccsx_set_error("adapter screen: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
+    const int64_t l = longest_draft(h, S, 32), words = screen_units(l, (l + 31) >> 5, CCSX_ADAPTER_MAX_WORDS, "adapter screen");
+    if (words < 0) return -1;
     if (S.d_adapt.reserve((size_t)n * (9 * 4 + CCSX_ADAPTER_MAX_HITS * sizeof(ccsx_adapter_hit)))) return -2;
     KParams &P = S.P;
     P.adapt = o; P.adapt_zi = (int32_t *)S.d_adapt.p; P.adapt_hits = P.adapt_zi + (size_t)9 * n; P.adapt_words = (int32_t)words; P.adapt_n = set.n_adapters;
@@ -888,15 +893,6 @@ static int adapter_attach(ccsx_handle h, Slot &S, const ccsx_adapter_set &set, c
         for (int w = 0; w < 4; ++w) P.adapt_seq[a][w] = 0u;
         for (int i = 0; a < set.n_adapters && i < set.len[a]; ++i) P.adapt_seq[a][i >> 4] |= (uint32_t)set.seq[a][i] << (2 * (i & 15));
     }
-    return 0;
-}
-
-static int enqueue_adapter_download(const Slot &S, ccsx_adapter_report *r, hipStream_t s)
-{
-    const size_t n = (size_t)S.P.n_zmw;
-    int32_t *dst[9] = {r->tested, r->verdict, r->n_hits, r->n_listed, r->covered, r->max_gap, r->first_start, r->last_end, r->min_dist};
-    for (int k = 0; k < 9; ++k) HIPTRY(hipMemcpyAsync(dst[k], S.P.adapt_zi + k * n, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->hits, S.P.adapt_hits, n * CCSX_ADAPTER_MAX_HITS * sizeof(ccsx_adapter_hit), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -949,15 +945,14 @@ static void control_index_build(const std::vector<uint8_t> &c, int max_occ, uint
     }
 }
 
-// k_control's two LDS histograms cover the longest draft the cascade aligns (longest_draft); -1 when that is beyond their LDS bound (nothing enqueued yet by this
-// call's request).  The index is the slot's own, in page-locked memory that lives as long as the slot: its copy is enqueued on `st` with the slot's other uploads,
-// and a slot is only staged again after its ticket has been retired, so no ticket in flight reads an index another one replaces.
+// k_control's two LDS histograms cover the longest draft the cascade aligns (screen_units); -1 when that is beyond their LDS bound.  The index is the slot's
+// own, in page-locked memory that lives as long as the slot: its copy is enqueued on `st` with the slot's other uploads, and a slot is only staged again after
+// its ticket has been retired, so no ticket in flight reads an index another one replaces.
 static int control_attach(ccsx_handle h, Slot &S, const std::vector<uint8_t> &seq, const ccsx_control_opts &o, hipStream_t st)
 {
     const int n = S.P.n_zmw, M = (int)seq.size();
-    const int64_t longest = longest_draft(h, S, 16);
-    const int64_t bins = ((longest - CCSX_FOLD_K + M - CCSX_FOLD_K) >> 6) + 2;
-    if (bins > CCSX_CONTROL_MAX_BINS) { ccsx_set_error("control screen: drafts of up to " + std::to_string(longest) + " bases need more LDS than it has (lower opts.max_length)"); return -1; }
+    const int64_t l = longest_draft(h, S, 16), bins = screen_units(l, ((l - CCSX_FOLD_K + M - CCSX_FOLD_K) >> 6) + 2, CCSX_CONTROL_MAX_BINS, "control screen");
+    if (bins < 0) return -1;
     if (S.d_ctl.reserve((size_t)CCSX_CONTROL_INDEX_WORDS * 4 + (size_t)n * 32) || S.ctl_index.resize(CCSX_CONTROL_INDEX_WORDS)) return -2;
     control_index_build(seq, o.max_occ, S.ctl_index.p);
     KParams &P = S.P;
@@ -965,14 +960,6 @@ static int control_attach(ccsx_handle h, Slot &S, const std::vector<uint8_t> &se
     if (hipError_t e = hipMemcpyAsync(S.d_ctl.p, S.ctl_index.p, (size_t)CCSX_CONTROL_INDEX_WORDS * 4, hipMemcpyHostToDevice, st)) {
         ccsx_set_error(std::string("control screen: index upload: ") + hipGetErrorString(e)); return -2;
     }
-    return 0;
-}
-
-static int enqueue_control_download(const Slot &S, ccsx_control_report *r, hipStream_t s)
-{
-    const size_t n = (size_t)S.P.n_zmw;
-    int32_t *dst[8] = {r->verdict, r->strand, r->hits, r->matched, r->ctl_start, r->ctl_end, r->draft_start, r->draft_end};
-    for (int k = 0; k < 8; ++k) HIPTRY(hipMemcpyAsync(dst[k], S.P.ctl_zi + k * n, n * 4, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -991,8 +978,8 @@ static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string
 // The Wants of one call of the exported function `fn` (NULL extras or request: none of it).  Enqueues nothing and needs no handle: the requests are checked
 // first, each refused by its own message, then the extras; the caller's null-argument check follows (without a batch there is nothing to measure a report
 // against, and that check refuses the call).
-static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters, const ccsx_batch *b,
-                       const char *fn, Wants *W, const ccsx_control_request *control = nullptr)
+static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
+                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W)
 {
     *W = Wants{};
     if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
@@ -1023,12 +1010,24 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
 static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
 {
     int rc;
+    const size_t n = (size_t)S.P.n_zmw;
     if (W.pile && (rc = enqueue_pile_download(S, W.pile, s))) return rc;
-    if (W.tandem_len) HIPTRY(hipMemcpyAsync(W.tandem_len, S.P.tlen, (size_t)S.P.n_zmw * 4, hipMemcpyDeviceToHost, s));
+    if (W.tandem_len) HIPTRY(hipMemcpyAsync(W.tandem_len, S.P.tlen, n * 4, hipMemcpyDeviceToHost, s));
     if (W.hd && (rc = enqueue_hd_download(S, W.hd->report, s))) return rc;
-    if (W.fold && (rc = enqueue_fold_download(S, W.fold->report, s))) return rc;
-    if (W.adapters && (rc = enqueue_adapter_download(S, W.adapters->report, s))) return rc;
-    if (W.control && (rc = enqueue_control_download(S, W.control->report, s))) return rc;
+    if (W.fold) {
+        const ccsx_fold_report *r = W.fold->report;
+        if ((rc = download_planes({r->verdict, r->fold, r->hits, r->span}, S.P.fold_zi, n, s))) return rc;
+    }
+    if (W.adapters) {
+        const ccsx_adapter_report *r = W.adapters->report;
+        if ((rc = download_planes({r->tested, r->verdict, r->n_hits, r->n_listed, r->covered, r->max_gap, r->first_start, r->last_end, r->min_dist},
+                                  S.P.adapt_zi, n, s))) return rc;
+        HIPTRY(hipMemcpyAsync(r->hits, S.P.adapt_hits, n * CCSX_ADAPTER_MAX_HITS * sizeof(ccsx_adapter_hit), hipMemcpyDeviceToHost, s));
+    }
+    if (W.control) {
+        const ccsx_control_report *r = W.control->report;
+        if ((rc = download_planes({r->verdict, r->strand, r->hits, r->matched, r->ctl_start, r->ctl_end, r->draft_start, r->draft_end}, S.P.ctl_zi, n, s))) return rc;
+    }
     return 0;
 }
 
@@ -1099,39 +1098,39 @@ int ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
 {
     const ccsx_extras ex = {pile, nullptr, 0, 0};
     Wants W;
-    if (build_wants(&ex, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
+    if (build_wants(&ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
+    if (build_wants(ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, hd, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
+    if (build_wants(ex, hd, nullptr, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
+    if (build_wants(ex, nullptr, fold, nullptr, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                        ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W)) return -1;
+    if (build_wants(ex, nullptr, fold, adapters, nullptr, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                         const ccsx_control_request *control, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W, control)) return -1;
+    if (build_wants(ex, nullptr, fold, adapters, control, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
@@ -1292,7 +1291,7 @@ int ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res,
 {
     const ccsx_extras ex = {pile, nullptr, 0, 0};
     Wants W;
-    if (build_wants(&ex, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
+    if (build_wants(&ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1301,14 +1300,14 @@ int ccsx_tandem_rule_version(void) { return 1; }
 int ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex)
 {
     Wants W;
-    if (build_wants(ex, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
+    if (build_wants(ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
 int ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd)
 {
     Wants W;
-    if (build_wants(ex, hd, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
+    if (build_wants(ex, hd, nullptr, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1323,7 +1322,7 @@ int ccsx_fold_rule_version(void) { return 1; }
 int ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
+    if (build_wants(ex, nullptr, fold, nullptr, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1348,7 +1347,7 @@ int ccsx_adapter_set_default(ccsx_adapter_set *s)
 int ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W)) return -1;
+    if (build_wants(ex, nullptr, fold, adapters, nullptr, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1364,7 +1363,7 @@ int ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res
                            const ccsx_control_request *control)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, b, __func__, &W, control)) return -1;
+    if (build_wants(ex, nullptr, fold, adapters, control, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 

@@ -157,7 +157,7 @@ struct KParams {
 // k_control (DESIGN.md §2 "Control screen"): the index of a control of M <= CCSX_CONTROL_MAX_LEN bases as the host builds it and every workgroup copies it to LDS.
 //   words [0, 4096)     the codes of the kept 15-mers in increasing (code, position), padded with 0xffffffff (no code: a code has 30 bits)
 //   words [4096, 6144)  their positions, 16 bits each, in the same order
-//   words [6144, 7168)  a prefilter: bit (fold_fmix32(code) & 32767) is set for every kept code; a look-up that passes it still compares the exact code
+//   words [6144, 7168)  a prefilter: bit (ccsx_fmix32(code) & 32767) is set for every kept code; a look-up that passes it still compares the exact code
 #define CCSX_CONTROL_THREADS     256
 #define CCSX_CONTROL_POS_WORD    CCSX_CONTROL_MAX_LEN
 #define CCSX_CONTROL_FILTER_WORD (CCSX_CONTROL_MAX_LEN + CCSX_CONTROL_MAX_LEN / 2)

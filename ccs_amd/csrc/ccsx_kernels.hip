@@ -3982,12 +3982,59 @@ __global__ __launch_bounds__(64) void k_sdust(KParams P, int pass)
 // codes or kept positions restarts the vote with twice the passes, so no sample is ever dropped.  (3) The winning pair of bins, a max-reduction over (H, -b).
 // (4) The hits again (the table is kept when there is one pass), now reducing min / max of D, i and j over the winning bins.  Counts, minima and maxima only:
 // the result does not depend on thread order.  tests/fold_ref.py restates the rule.
-__device__ __forceinline__ uint32_t fold_fmix32(uint32_t h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
+//
+// What the three draft screens (k_fold, k_adapter, k_control) share.  screen_zmw: the workgroup's ZMW (z < 0: none), its final draft's length and number of
+// 15-mer positions, and whether the cascade left it SUCCESS; a kernel tests the ZMW when that holds and its own LDS bound does.
+struct ScreenZmw { int z, L, npos; bool success; };
+__device__ __forceinline__ ScreenZmw screen_zmw(const KParams &P)
+{
+    if ((int)blockIdx.x >= P.n_zmw) return {-1, 0, 0, false};
+    const int z = rfl(P.zmw_perm[blockIdx.x]), L = rfl(P.draft_len[z]);
+    return {z, L, L >= CCSX_FOLD_K ? L - CCSX_FOLD_K + 1 : 0, rfl(P.zstat[z]) == CCSX_SUCCESS};
+}
+
+// one row of a report of [k][n] planes: out = plane 0's entry of the ZMW
+template <class... V> __device__ __forceinline__ void put_planes(int32_t *out, size_t n, V... v) { size_t j = 0; ((out[j++ * n] = (int32_t)v), ...); }
+
+// thread tid's contiguous share [p0, p1) of `count` positions split over nt threads (the last shares are short or empty)
+__device__ __forceinline__ void thread_share(int count, int nt, int tid, int &p0, int &p1) { const int ch = (count + nt - 1) / nt; p0 = min(tid * ch, count); p1 = min(p0 + ch, count); }
+
+// fn(i, F, R) for the 15-mer at every position i of [p0, e) of the draft d: F its code, R its reverse complement's, both rolled (a K - 1-base warm-up first)
+template <class Fn> __device__ __forceinline__ void kmer_scan(const uint8_t *d, int p0, int e, Fn fn)
+{
+    constexpr int K = CCSX_FOLD_K;
+    constexpr uint32_t KMASK = (1u << (2 * K)) - 1u;
+    if (p0 >= e) return;
+    uint32_t F = 0u, R = 0u;
+    for (int t = 0; t < K - 1; ++t) { const uint32_t b = d[p0 + t] & 3u; F = (F << 2) | b; R = (R >> 2) | ((3u - b) << (2 * K - 2)); }
+    for (int i = p0; i < e; ++i) {
+        const uint32_t b = d[i + K - 1] & 3u;
+        F = ((F << 2) | b) & KMASK;
+        R = (R >> 2) | ((3u - b) << (2 * K - 2));
+        fn(i, F, R);
+    }
+}
+
+// q* = argmax over the pairs of adjacent bins q in [0, nq) of their hits pair(q), ties to the smallest q: returns q* and H = its hits, or -1 and 0 when no pair
+// has a hit.  A max-reduction over (H, -q) through *sBest, which the workgroup has zeroed before its last barrier.  It holds a __syncthreads():
+// every thread of the workgroup calls it, in uniform control flow, and every thread gets the same value.
+template <class Pair> __device__ __forceinline__ int best_pair(unsigned long long *sBest, int nq, int nt, Pair pair, int &H)
+{
+    unsigned long long best = 0ull;
+    for (int q = (int)threadIdx.x; q < nq; q += nt) {
+        const unsigned long long key = ((unsigned long long)pair(q) << 32) | (0xffffffffu - (uint32_t)q);
+        best = key > best ? key : best;
+    }
+    if (best >> 32) atomicMax(sBest, best);
+    __syncthreads();
+    H = (int)(*sBest >> 32);
+    return H ? (int)(0xffffffffu - (uint32_t)(*sBest & 0xffffffffull)) : -1;
+}
 
 __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
 {
     constexpr int K = CCSX_FOLD_K, NT = CCSX_FOLD_THREADS, T = CCSX_FOLD_SLOTS, CAP = CCSX_FOLD_CAP;
-    constexpr uint32_t NIL = 0xffffu, KMASK = (1u << (2 * K)) - 1u;
+    constexpr uint32_t NIL = 0xffffu;
     static_assert((T & (T - 1)) == 0 && T == 2048 && CAP < T && CAP < (int)NIL, "k_fold: the slot hash takes the top 11 bits");
     __shared__ uint32_t sKey[T];          // canonical code + 1 (0 = empty)
     __shared__ uint32_t sCnt[T];          // samples of the pass with that code
@@ -3999,38 +4046,31 @@ __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
     __shared__ unsigned long long sBest;
     uint32_t *sHist = dyn_lds;            // [fold_bins] hits per anti-diagonal bin
     const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= P.n_zmw) return;
-    const int z = rfl(P.zmw_perm[blockIdx.x]);
-    const size_t n = (size_t)P.n_zmw;
-    const int L = rfl(P.draft_len[z]);
-    const int npos = L >= K ? L - K + 1 : 0;
+    const ScreenZmw zm = screen_zmw(P);
+    if (zm.z < 0) return;
+    const int L = zm.L, npos = zm.npos;
     const int nb = npos > 0 ? ((2 * L - K - 1) >> 6) + 1 : 0;       // bins of this draft's anti-diagonals
-    if (rfl(P.zstat[z]) != CCSX_SUCCESS || nb + 1 > P.fold_bins) {   // untested (the second: a bounds guard, the histogram covers opts.max_length)
-        if (tid == 0) { P.fold_zi[z] = CCSX_FOLD_UNTESTED; P.fold_zi[n + z] = -1; P.fold_zi[2 * n + z] = 0; P.fold_zi[3 * n + z] = 0; }
+    const size_t n = (size_t)P.n_zmw;
+    int32_t *out = P.fold_zi + zm.z;
+    if (!zm.success || nb + 1 > P.fold_bins) {                       // untested (the second: a bounds guard, the histogram covers opts.max_length)
+        if (tid == 0) put_planes(out, n, CCSX_FOLD_UNTESTED, -1, 0, 0);
         return;
     }
-    const uint8_t *d = P.draft + P.seq_off[z];
-    const int ch = (npos + NT - 1) / NT;
-    const int p0 = min(tid * ch, npos), p1 = min(p0 + ch, npos);
+    const uint8_t *d = P.draft + P.seq_off[zm.z];
+    int p0, p1;
+    thread_share(npos, NT, tid, p0, p1);
     // fn(i, F, C, h) for every sampled position i of this thread's range up to `last`
     auto scan = [&](int last, auto fn) {
-        const int e = min(p1, last + 1);
-        if (p0 >= e) return;
-        uint32_t F = 0u, R = 0u;
-        for (int t = 0; t < K - 1; ++t) { const uint32_t b = d[p0 + t] & 3u; F = (F << 2) | b; R = (R >> 2) | ((3u - b) << (2 * K - 2)); }
-        for (int i = p0; i < e; ++i) {
-            const uint32_t b = d[i + K - 1] & 3u;
-            F = ((F << 2) | b) & KMASK;
-            R = (R >> 2) | ((3u - b) << (2 * K - 2));
-            const uint32_t C = F < R ? F : R, h = fold_fmix32(C);
+        kmer_scan(d, p0, min(p1, last + 1), [&](int i, uint32_t F, uint32_t R) {
+            const uint32_t C = F < R ? F : R, h = ccsx_fmix32(C);
             if ((h & 7u) == 0u) fn(i, F, C, h);
-        }
+        });
     };
     // (1) the last position that enters
     int cnt = 0;
     scan(npos - 1, [&](int, uint32_t, uint32_t, uint32_t) { ++cnt; });
     sScan[tid] = (uint32_t)cnt;
-    if (tid == 0) sV[3] = npos - 1;
+    if (tid == 0) { sV[3] = npos - 1; sBest = 0ull; }
     __syncthreads();
     for (int o = 1; o < NT; o <<= 1) {
         const uint32_t v = tid >= o ? sScan[tid - o] : 0u;
@@ -4111,21 +4151,12 @@ __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
         nparts <<= 1;
     }
     // (3) b* = argmax over b of H(b) = hist[b] + hist[b + 1], ties to the smallest b
-    if (tid == 0) sBest = 0ull;
-    __syncthreads();
-    unsigned long long best = 0ull;
-    for (int b = tid; b < nb; b += NT) {
-        const unsigned long long key = ((unsigned long long)(sHist[b] + sHist[b + 1]) << 32) | (0xffffffffu - (uint32_t)b);
-        best = key > best ? key : best;
-    }
-    if (best >> 32) atomicMax(&sBest, best);
-    __syncthreads();
-    const int H = (int)(sBest >> 32);
+    int H;
+    const int bs = best_pair(&sBest, nb, NT, [&](int b) { return sHist[b] + sHist[b + 1]; }, H);
     if (H == 0) {
-        if (tid == 0) { P.fold_zi[z] = CCSX_FOLD_NONE; P.fold_zi[n + z] = -1; P.fold_zi[2 * n + z] = 0; P.fold_zi[3 * n + z] = 0; }
+        if (tid == 0) put_planes(out, n, CCSX_FOLD_NONE, -1, 0, 0);
         return;
     }
-    const int bs = (int)(0xffffffffu - (uint32_t)(sBest & 0xffffffffull));
     // (4) the extent of the winning hits
     if (tid == 0) { sV[4] = 0x7fffffff; sV[5] = -1; sV[6] = 0x7fffffff; sV[7] = -1; sV[8] = 0x7fffffff; sV[9] = -1; }
     __syncthreads();
@@ -4143,7 +4174,7 @@ __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
         const int shorter = min(fold, L - fold);
         const bool reach = fold <= L - fold ? sV[6] <= o.end_slack : sV[9] + K >= L - o.end_slack;
         const bool pal = H >= o.min_hits && span >= o.min_arm && 10 * span >= o.min_span_tenths * shorter && reach;
-        P.fold_zi[z] = pal ? CCSX_FOLD_PALINDROME : CCSX_FOLD_NONE; P.fold_zi[n + z] = fold; P.fold_zi[2 * n + z] = H; P.fold_zi[3 * n + z] = span;
+        put_planes(out, n, pal ? CCSX_FOLD_PALINDROME : CCSX_FOLD_NONE, fold, H, span);
     }
 }
 
@@ -4158,29 +4189,21 @@ __global__ __launch_bounds__(CCSX_FOLD_THREADS) void k_fold(KParams P)
 __global__ __launch_bounds__(CCSX_CONTROL_THREADS) void k_control(KParams P)
 {
     constexpr int K = CCSX_FOLD_K, NT = CCSX_CONTROL_THREADS, CAP = CCSX_CONTROL_MAX_LEN;
-    constexpr uint32_t KMASK = (1u << (2 * K)) - 1u;
     static_assert((CAP & (CAP - 1)) == 0 && CAP <= 65536 && CCSX_CONTROL_INDEX_WORDS % 4 == 0, "k_control: a power-of-two code array, 16-bit positions, 16-byte copies");
     __shared__ __attribute__((aligned(16))) uint32_t sIdx[CCSX_CONTROL_INDEX_WORDS];
     __shared__ uint32_t sSeen[CAP / 32];  // bit j: control position j is among the winning hits
     __shared__ int sV[5];                 // 0 min i, 1 max i, 2 matched, 3 min j, 4 max j
     __shared__ unsigned long long sBest;
-    const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= P.n_zmw) return;
-    const int z = rfl(P.zmw_perm[blockIdx.x]);
-    const size_t n = (size_t)P.n_zmw;
-    int32_t *out = P.ctl_zi + z;
-    const int L = rfl(P.draft_len[z]), M = P.ctl_len, bins = P.ctl_bins;
-    const int npos = L >= K ? L - K + 1 : 0;
+    const int tid = threadIdx.x, M = P.ctl_len, bins = P.ctl_bins;
+    const ScreenZmw zm = screen_zmw(P);
+    if (zm.z < 0) return;
+    const int L = zm.L, npos = zm.npos;
     const int nb = npos > 0 ? ((L - K + M - K) >> 6) + 1 : 0;       // bins of this draft's diagonals
-    auto report = [&](int verdict, int strand, int hits, int matched, int cs, int ce, int ds, int de) {
-        out[0] = verdict; out[n] = strand; out[2 * n] = hits; out[3 * n] = matched; out[4 * n] = cs; out[5 * n] = ce; out[6 * n] = ds; out[7 * n] = de;
-    };
-    if (rfl(P.zstat[z]) != CCSX_SUCCESS || nb + 1 > bins) {        // untested (the second: a bounds guard, the histograms cover opts.max_length)
-        if (tid == 0) report(CCSX_CONTROL_UNTESTED, -1, 0, 0, 0, 0, 0, 0);
-        return;
-    }
-    if (npos == 0) {
-        if (tid == 0) report(CCSX_CONTROL_NONE, -1, 0, 0, 0, 0, 0, 0);
+    const bool tested = zm.success && nb + 1 <= bins;               // (the second: a bounds guard, the histograms cover opts.max_length)
+    const size_t n = (size_t)P.n_zmw;
+    int32_t *out = P.ctl_zi + zm.z;
+    if (!tested || npos == 0) {                                      // (npos == 0: too short for one 15-mer)
+        if (tid == 0) put_planes(out, n, tested ? CCSX_CONTROL_NONE : CCSX_CONTROL_UNTESTED, -1, 0, 0, 0, 0, 0, 0);
         return;
     }
     uint32_t *sHist = dyn_lds;            // [2][bins] hits per diagonal bin of orientation 0, 1
@@ -4195,12 +4218,11 @@ __global__ __launch_bounds__(CCSX_CONTROL_THREADS) void k_control(KParams P)
     __syncthreads();
     const uint32_t *sCode = sIdx, *sFilt = sIdx + CCSX_CONTROL_FILTER_WORD;
     const uint16_t *sPos = reinterpret_cast<const uint16_t *>(sIdx + CCSX_CONTROL_POS_WORD);
-    const uint8_t *d = P.draft + P.seq_off[z];
-    const int ch = (npos + NT - 1) / NT;
-    const int p0 = min(tid * ch, npos), p1 = min(p0 + ch, npos);
+    const uint8_t *d = P.draft + P.seq_off[zm.z];
+    int p0, p1;
+    thread_share(npos, NT, tid, p0, p1);
     // fn(o, i, j, dg) for every hit of this thread's range: orientation, draft position, control position, diagonal
     auto scan = [&](auto fn) {
-        if (p0 >= p1) return;
         auto lookup = [&](uint32_t code, int o, int i, int u) {
             const uint32_t h = ccsx_fmix32(code) & (uint32_t)(CCSX_CONTROL_FILTER_BITS - 1);
             if (!((sFilt[h >> 5] >> (h & 31u)) & 1u)) return;
@@ -4208,34 +4230,20 @@ __global__ __launch_bounds__(CCSX_CONTROL_THREADS) void k_control(KParams P)
             for (int s = CAP >> 1; s > 0; s >>= 1) lo += sCode[lo + s - 1] < code ? s : 0;   // entries below `code` (the padding is above every code)
             for (int e = lo; sCode[e] == code; ++e) { const int j = (int)sPos[e]; fn(o, i, j, u - j + (M - K)); }
         };
-        uint32_t F = 0u, R = 0u;
-        for (int t = 0; t < K - 1; ++t) { const uint32_t b = d[p0 + t] & 3u; F = (F << 2) | b; R = (R >> 2) | ((3u - b) << (2 * K - 2)); }
-        for (int i = p0; i < p1; ++i) {
-            const uint32_t b = d[i + K - 1] & 3u;
-            F = ((F << 2) | b) & KMASK;
-            R = (R >> 2) | ((3u - b) << (2 * K - 2));
-            lookup(F, 0, i, i);
-            lookup(R, 1, i, (L - K) - i);
-        }
+        kmer_scan(d, p0, p1, [&](int i, uint32_t F, uint32_t R) { lookup(F, 0, i, i); lookup(R, 1, i, (L - K) - i); });
     };
     // (1) the vote
     scan([&](int o, int, int, int dg) { atomicAdd(&sHist[o * bins + (dg >> 6)], 1u); });
     __syncthreads();
     // (2) (o*, b*) = argmax of H(o, b) = hist[o][b] + hist[o][b + 1], ties to orientation 0, then to the smallest b
-    unsigned long long best = 0ull;
-    for (int q = tid; q < 2 * nb; q += NT) {
-        const int o = q >= nb ? 1 : 0, b = q - o * nb;
-        const unsigned long long key = ((unsigned long long)(sHist[o * bins + b] + sHist[o * bins + b + 1]) << 32) | ((uint32_t)(1 - o) << 31) | (0x7fffffffu - (uint32_t)b);
-        best = key > best ? key : best;
-    }
-    if (best >> 32) atomicMax(&sBest, best);
-    __syncthreads();
-    const int H = (int)(sBest >> 32);
+    // (as one index q = o * nb + b: the smallest q of a tie is orientation 0's, then the smallest b)
+    int H;
+    const int qs = best_pair(&sBest, 2 * nb, NT, [&](int q) { const int w = q >= nb ? q - nb + bins : q; return sHist[w] + sHist[w + 1]; }, H);
     if (H == 0) {
-        if (tid == 0) report(CCSX_CONTROL_NONE, -1, 0, 0, 0, 0, 0, 0);
+        if (tid == 0) put_planes(out, n, CCSX_CONTROL_NONE, -1, 0, 0, 0, 0, 0, 0);
         return;
     }
-    const int os = 1 - (int)((sBest >> 31) & 1ull), bs = (int)(0x7fffffffu - (uint32_t)(sBest & 0x7fffffffull));
+    const int os = qs >= nb ? 1 : 0, bs = qs - os * nb;
     // (3) the winning hits: distinct control positions and the two extents
     int imin = 0x7fffffff, imax = -1;
     scan([&](int o, int i, int j, int dg) {
@@ -4254,7 +4262,7 @@ __global__ __launch_bounds__(CCSX_CONTROL_THREADS) void k_control(KParams P)
         const ccsx_control_opts &o = P.ctl;
         const int cs = sV[3], ce = sV[4] + K, ds = sV[0], de = sV[1] + K;
         const bool found = sV[2] >= o.min_matched && 10 * (ce - cs) >= o.min_ctl_tenths * M && 10ll * (de - ds) >= (long long)o.min_draft_tenths * L;
-        report(found ? CCSX_CONTROL_FOUND : CCSX_CONTROL_NONE, os, H, sV[2], cs, ce, ds, de);
+        put_planes(out, n, found ? CCSX_CONTROL_FOUND : CCSX_CONTROL_NONE, os, H, sV[2], cs, ce, ds, de);
     }
 }
 
@@ -4292,15 +4300,14 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
     __shared__ int sM[MAXS];                                       // pattern lengths
     __shared__ int sV[8];                                          // 0 n_hits, 1 first_start, 2 last_end, 3 min_dist, 4 covered, 5 buffered keys, 6 bound on the ends
     const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= P.n_zmw) return;
-    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    const ScreenZmw zm = screen_zmw(P);
+    if (zm.z < 0) return;
+    const int z = zm.z, L = zm.L, words = (L + 31) >> 5;
     const size_t n = (size_t)P.n_zmw;
-    const int L = rfl(P.draft_len[z]);
-    const int words = (L + 31) >> 5;
     int32_t *out = P.adapt_zi + z;
     int32_t *list = P.adapt_hits + (size_t)z * NH * 3;
-    if (rfl(P.zstat[z]) != CCSX_SUCCESS || words > P.adapt_words) {  // untested (the second: a bounds guard, the bitmaps cover opts.max_length)
-        if (tid == 0) { out[0] = 0; out[n] = 0; out[2 * n] = 0; out[3 * n] = 0; out[4 * n] = 0; out[5 * n] = 0; out[6 * n] = -1; out[7 * n] = -1; out[8 * n] = 255; }
+    if (!zm.success || words > P.adapt_words) {                      // untested (the second: a bounds guard, the bitmaps cover opts.max_length)
+        if (tid == 0) put_planes(out, n, 0, 0, 0, 0, 0, 0, -1, -1, 255);
         if (tid < NH * 3) list[tid] = 0;
         return;
     }
@@ -4419,7 +4426,8 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
     for (int w = tid; w < words; w += NT) cov += __popc(sUnion[w]);
     if (cov) atomicAdd(&sV[4], cov);
     {
-        const int seg = (L + NT - 1) / NT, a = min(tid * seg, L), b = min(a + seg, L);
+        int a, b;
+        thread_share(L, NT, tid, a, b);
         int lead = -1, run = 0, inner = 0;
         for (int i = a; i < b; ++i) {
             if ((sUnion[i >> 5] >> (i & 31)) & 1u) { if (lead < 0) lead = run; inner = max(inner, run); run = 0; }
@@ -4441,8 +4449,7 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
         int v = 0;
         if (n_hits >= o.min_copies && gap <= o.max_insert) v |= CCSX_ADAPTER_CONCAT;
         if (n_hits >= 1 && (first <= o.end_slack || last >= L - o.end_slack)) v |= CCSX_ADAPTER_NEAR_END;
-        out[0] = 1; out[n] = v; out[2 * n] = n_hits; out[3 * n] = n_listed; out[4 * n] = sV[4]; out[5 * n] = gap; out[6 * n] = first; out[7 * n] = last;
-        out[8 * n] = sV[3];
+        put_planes(out, n, 1, v, n_hits, n_listed, sV[4], gap, first, last, sV[3]);
     }
 }
 
@@ -4576,24 +4583,16 @@ const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_pol
     LAUNCH_CHECK("k_wmap");
     hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
     LAUNCH_CHECK("k_wmap_fill");
-    if (mode == CCSX_RUN_FUSED && P.fold_zi) {
-        // adapter palindromes (ccsx_submit_fold / ccsx_consensus_fold): on the draft stream, on the final drafts and statuses k_polish is given; writes its report only
-        hipLaunchKernelGGL(k_fold, dim3(P.n_zmw), dim3(CCSX_FOLD_THREADS), (size_t)P.fold_bins * 4, st, P);
-        LAUNCH_CHECK("k_fold");
-        trace_sync(st, "k_fold");
-    }
-    if (mode == CCSX_RUN_FUSED && P.adapt_zi) {
-        // the adapter screen (ccsx_submit_screen / ccsx_consensus_screen): as k_fold, on the draft stream and on the final drafts and statuses; writes its report only
-        hipLaunchKernelGGL(k_adapter, dim3(P.n_zmw), dim3(CCSX_ADAPTER_THREADS), (size_t)P.adapt_words * 8, st, P);
-        LAUNCH_CHECK("k_adapter");
-        trace_sync(st, "k_adapter");
-    }
-    if (mode == CCSX_RUN_FUSED && P.ctl_zi) {
-        // the control screen (ccsx_submit_control / ccsx_consensus_control): as k_fold and k_adapter, on the draft stream and on the final drafts and statuses;
-        // writes its report only
-        hipLaunchKernelGGL(k_control, dim3(P.n_zmw), dim3(CCSX_CONTROL_THREADS), (size_t)P.ctl_bins * 8, st, P);
-        LAUNCH_CHECK("k_control");
-        trace_sync(st, "k_control");
+    // The draft screens a fused run was asked for (the requests of ccsx_submit_control / ccsx_consensus_control and their narrower forms): adapter palindromes,
+    // the adapter screen, the control screen.  On the draft stream, on the final drafts and statuses k_polish is given; each writes its report only.
+    const struct { const void *report; void (*kernel)(KParams); int threads; size_t lds; const char *name; } screens[] = {
+        {P.fold_zi, k_fold, CCSX_FOLD_THREADS, (size_t)P.fold_bins * 4, "k_fold"},
+        {P.adapt_zi, k_adapter, CCSX_ADAPTER_THREADS, (size_t)P.adapt_words * 8, "k_adapter"},
+        {P.ctl_zi, k_control, CCSX_CONTROL_THREADS, (size_t)P.ctl_bins * 8, "k_control"}};
+    for (const auto &s : screens) if (mode == CCSX_RUN_FUSED && s.report) {
+        hipLaunchKernelGGL(s.kernel, dim3(P.n_zmw), dim3(s.threads), s.lds, st, P);
+        LAUNCH_CHECK(s.name);
+        trace_sync(st, s.name);
     }
     // the heteroduplex finder's three kernels on the draft stream (the fused path with a request, ccsx_hd_batch), `before_verdict` recorded between the last two
     auto hd_kernels = [&](hipEvent_t before_verdict) {

@@ -221,12 +221,14 @@ def _same(a, b, z):
 
 def _mix(seed=MIX_SEED):
     """(batch, kind name per ZMW): 96 ZMWs of every control_synth kind around TEST_CONTROL, 3-10 passes, random parts of 300-12000 bases, and one random
-    template of 42 kb at 3 passes"""
+    template of 42 kb at 3 passes, and the short random drafts of scan_edges"""
     import control_synth as S
+    import scan_edges
     rng = np.random.default_rng(seed)
     b1, k1 = S.make(96, (3, 10), (300, 12000), seed)
     long = S.from_templates([S.template(rng, "random", 42000, S.encode(S.TEST_CONTROL))], [3], rng)
-    return api.concat([b1, long]), [S.KINDS[k] for k in k1] + ["long"]
+    short = scan_edges.batch()
+    return api.concat([b1, long, short]), [S.KINDS[k] for k in k1] + ["long"] + ["short"] * short.n_zmw
 
 
 def _check_report(d, rep, control, o=None):
@@ -251,8 +253,9 @@ def _opts(d):
 @pytest.mark.gpu
 def test_report_equals_the_restatement_and_results_do_not_change(built):
     """The oracle on the CPU for MIX_SEED (a final status that is not a draft-stage failure = tested): 97 of 97 ZMWs, 16 of 16 of every kind and the 42 kb
-    one (70 SUCCESS, 27 LOW_RQ)"""
+    one (70 SUCCESS, 27 LOW_RQ); the 8 short ZMWs of scan_edges besides"""
     import control_synth as S
+    import scan_edges
     b, kinds = _mix()
     c = S.encode(S.TEST_CONTROL)
     seq = api.ControlSeq.from_string(S.TEST_CONTROL)
@@ -269,6 +272,7 @@ def test_report_equals_the_restatement_and_results_do_not_change(built):
         zs = [z for z in range(b.n_zmw) if kinds[z] == kind]
         assert 2 * sum(z in tested for z in zs) >= len(zs), (kind, [int(d.status[z]) for z in zs])
     assert max(len(d.draft(z)) for z in tested) > 40000
+    scan_edges.assert_every_class(len(d.draft(z)) for z in tested)
     # detection only: every result byte, the fold and adapter reports, the pileup planes and tandem_len equal the call without the control request
     for z in range(b.n_zmw):
         _same(res, ref, z)

@@ -190,12 +190,14 @@ def _same(a, b, z):
 
 
 def _mix(seed=61):
-    """every fold_synth class, drafts long enough for two table passes (15 kb), and homopolymer drafts with more than NS_MAX sampled positions"""
+    """every fold_synth class, drafts long enough for two table passes (15 kb), homopolymer drafts with more than NS_MAX sampled positions, the two cap
+    templates (the last two ZMWs), and before them the short drafts of scan_edges"""
     import fold_synth
+    import scan_edges
     rng = np.random.default_rng(seed)
     poly = [np.concatenate([rng.integers(0, 4, 500).astype(np.uint8), np.zeros(9500, np.uint8), rng.integers(0, 4, 500).astype(np.uint8)]) for _ in range(4)]
     return api.concat([fold_synth.make(40, (5, 9), (1500, 6000), seed=seed)[0], fold_synth.make(10, 5, (14000, 16000), seed=seed + 1)[0],
-                       _from_templates(poly, 6, seed), _from_templates(_cap_templates(), 8, seed + 2)])
+                       _from_templates(poly, 6, seed), scan_edges.batch(), _from_templates(_cap_templates(), 8, seed + 2)])
 
 
 CAP_Y = None
@@ -255,12 +257,14 @@ def _check_report(d, rep, o=None):
 @pytest.mark.gpu
 def test_report_equals_the_restatement_and_results_do_not_change(built):
     import fold_synth
+    import scan_edges
     b = _mix()
     h = api.Handle(0)
     d = h.draft(b)
     ref = h.consensus(b)
     res, rep = h.consensus_fold(b)
     assert _check_report(d, rep) > 40
+    scan_edges.assert_every_class(len(d.draft(z)) for z in range(b.n_zmw) if d.status[z] == 0)
     assert max(len(R.sampled_positions(d.draft(z))[0]) for z in range(b.n_zmw) if d.status[z] == 0) == R.NS_MAX   # the cap was reached
     assert max(len(R.sampled_positions(d.draft(z))[0]) for z in range(40, 50) if d.status[z] == 0) > 1536            # several table passes
     for z in range(b.n_zmw):
