@@ -38,9 +38,15 @@
 
 namespace {
 
+// a device buffer and a page-locked host array (below) free themselves: a slot's buffers are named where they are declared and nowhere else.  Their owners die in
+// destroy_handle(), with the handle's device current and its streams drained
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t bytes)
     {
         if (bytes <= cap) return 0;
@@ -73,6 +79,10 @@ struct DevBuf {
 template <typename T> struct PinVec {
     T *p = nullptr;
     size_t cap = 0, n = 0;
+    PinVec() = default;
+    PinVec(const PinVec &) = delete;
+    PinVec &operator=(const PinVec &) = delete;
+    ~PinVec() { release(); }
     int assign(size_t count, T fill)
     {
         if (resize(count)) return -2;
@@ -98,13 +108,21 @@ template <typename T> struct PinVec {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = n = 0; }
 };
 
+// the batch-level figures of a staged batch, each computed once: the largest per-ZMW capacities (ccsx_zmw_caps), the most passes of a ZMW after the top_passes
+// cap, k_align16's work items, and the totals of the capacity layout
+struct BatchTotals {
+    int64_t maxL_max = 1, vcap_max = 1, dcap_max = 0;
+    int need_max = 2, nr_max = 1, n_quads = 0;
+    int64_t total_wslots = 0, cap_total = 0;
+};
+
 struct Slot {
     // inputs
     DevBuf d_snr, d_read_off, d_base_off, d_bases, d_pw, d_ipd, d_flags;
     // layout
     DevBuf d_read_zmw, d_vcap, d_dcap, d_seq_off, d_wb_off, d_ent_off, d_wslot, d_zperm, d_rperm, d_quads, d_retry;
     // state
-    DevBuf d_tabME, d_tabINS, d_tabDL, d_tabZ, d_dmask, d_draft, d_zmw_i32 /* 6 x n int32 */, d_wbounds, d_ticket;
+    DevBuf d_tabME, d_tabINS, d_tabDL, d_tabZ, d_dmask, d_draft, d_zmw_i32 /* 7 x n int32 */, d_wbounds, d_ticket;
     DevBuf d_avalid, d_ascore, d_ent;
     DevBuf d_wseq, d_wqv, d_wsum, d_wmeta;
     DevBuf d_out_seq, d_out_qual, d_out_raw, d_out_i32 /* 6 x n */, d_out_f32 /* 2 x n */;
@@ -129,20 +147,10 @@ struct Slot {
     ccsx_drafts *drafts_out = nullptr; // ... of an in-flight ccsx_submit_draft
     int mode = CCSX_RUN_FUSED;
     int64_t ticket = -1;
-    // scratch this batch needs per resident POA graph / alignment
-    size_t poa_slot_bytes = 0, align_slot_i32 = 0, align16_slot_i32 = 0;
-    int align16_regions = 1;
+    BatchTotals T;                    // batch-level figures of the staged batch (layout)
 
-    void release()
+    void release()                    // (the buffers free themselves)
     {
-        DevBuf *bufs[] = {&d_snr, &d_read_off, &d_base_off, &d_bases, &d_pw, &d_ipd, &d_flags, &d_read_zmw, &d_vcap, &d_dcap, &d_seq_off,
-                          &d_wb_off, &d_ent_off, &d_wslot, &d_zperm, &d_rperm, &d_quads, &d_retry, &d_tabME, &d_tabINS, &d_tabDL, &d_tabZ, &d_dmask, &d_draft,
-                          &d_zmw_i32, &d_wbounds, &d_ticket, &d_avalid, &d_ascore, &d_ent, &d_wseq, &d_wqv, &d_wsum, &d_wmeta, &d_out_seq,
-                          &d_out_qual, &d_out_raw, &d_out_i32, &d_out_f32, &d_wtpl, &d_wtmeta, &d_wkin, &d_out_kin, &d_wpile, &d_out_pile, &d_tflag, &d_tlen, &d_din_len, &d_din_bb,
-                          &d_hd_wcnt, &d_hd_wrec, &d_hd_wminp, &d_hd_isite, &d_hd_zi, &d_hd_minp, &d_hd_sites, &d_fold, &d_adapt, &d_ctl};
-        for (auto *b : bufs) b->release();
-        read_zmw.release(); vcap.release(); dcap.release(); zperm.release(); rperm.release(); quads.release(); qperm.release(); wb_off.release();
-        read_off.release(); seq_off.release(); ent_off.release(); base_off.release(); ctl_index.release();
         for (auto &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         for (auto &e : ev_aux) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_up) { (void)hipEventDestroy(ev_up); ev_up = nullptr; }
@@ -153,6 +161,15 @@ struct Slot {
 // POA / alignment scratch is sized from the free memory of the device; handles created on the same device by
 // different host threads must not all claim the same free bytes: sizing is serialised per process.
 std::mutex g_scratch_mutex;
+
+// a buffer of [k][n] planes, reserved for the k pointers of `dst`, which are set to its planes in order
+template <typename T> int carve_planes(std::initializer_list<T **> dst, DevBuf &buf, size_t n)
+{
+    if (buf.reserve(dst.size() * n * sizeof(T))) return -2;
+    T *p = (T *)buf.p;
+    for (T **d : dst) { *d = p; p += n; }
+    return 0;
+}
 
 }  // namespace
 
@@ -233,13 +250,12 @@ static void destroy_handle(ccsx_handle h)
     for (auto &s : h->slot) { (void)retire(h, s); s.release(); }
     if (h->ev_epoch) (void)hipEventDestroy(h->ev_epoch);
     if (h->ev_epoch_nx) (void)hipEventDestroy(h->ev_epoch_nx);
-    h->d_model.release(); h->d_poa.release(); h->d_align.release(); h->d_hd_lf.release();
     if (h->s_in) (void)hipStreamDestroy(h->s_in);
     if (h->s_draft && h->s_draft != h->s_comp) (void)hipStreamDestroy(h->s_draft);
     if (h->s_aux) (void)hipStreamDestroy(h->s_aux);
     if (h->s_comp) (void)hipStreamDestroy(h->s_comp);
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
-    delete h;
+    delete h;                         // frees every buffer of the handle and its slots (they were drained above; hipFree needs no stream)
 }
 
 extern "C" {
@@ -359,9 +375,7 @@ struct Wants {
 // what the LDS of k_sdust, k_fold, k_adapter and k_control is sized for
 static int64_t longest_draft(ccsx_handle h, const Slot &S, int32_t floor)
 {
-    int64_t longest = floor;
-    for (size_t z = 0; z < S.dcap.size(); ++z) longest = std::max<int64_t>(longest, S.dcap[z]);
-    return std::min<int64_t>(longest, std::max<int32_t>(h->opts.max_length, floor));
+    return std::min<int64_t>(std::max<int64_t>(floor, S.T.dcap_max), std::max<int32_t>(h->opts.max_length, floor));
 }
 
 // `units`: the LDS units (histogram bins, bitmap words) a draft screen's kernel needs for the slot's longest draft; -1, refused under the screen's name, when they
@@ -404,231 +418,243 @@ static int validate(const ccsx_batch *b)
     return 0;
 }
 
+// ---- staging a batch: the steps of stage(), in its order.  Each returns 0, -1 (the batch is refused; no step has enqueued anything yet) or -2 ----
+
+// The host-derived layout of the batch in the slot's page-locked arrays, and its batch-level figures.  `top`: the passes of a ZMW the engine uses (ccsx_top_passes).
+// First the capacity layout: per ZMW its capacities (ccsx_zmw_caps) and the offsets they add up to, per pass its ZMW and its entry-row slots.  Then the launch
+// order, longest first (stable within 256-base classes, so a uniform batch keeps its input order and its locality): mixed batches (BASELINE configs[4]: 1-25 kb,
+// 3-50 passes) otherwise end on a few long stragglers.
+static int layout(Slot &S, const ccsx_batch *b, int top, BatchTotals *out)
+{
+    const int n = b->n_zmw, R = b->n_reads;
+    if (S.read_zmw.resize(R > 0 ? R : 1) || S.vcap.resize(n) || S.dcap.resize(n) || S.seq_off.assign(n + 1, 0) || S.wb_off.assign(n + 1, 0) ||
+        S.ent_off.assign(R + 1, 0) || S.read_off.resize(n + 1) || S.base_off.resize(R + 1) || S.zperm.resize(n) || S.rperm.resize(R > 0 ? R : 1))
+        return -2;
+    BatchTotals &T = *out;
+    T = BatchTotals{};
+    ccsx_for_each_zmw_caps(b, [&](int z, const ccsx_zmw_caps &c) {
+        S.dcap[z] = (int32_t)c.dcap;
+        S.vcap[z] = (int32_t)c.vcap;
+        S.seq_off[z + 1] = S.seq_off[z] + S.dcap[z];
+        S.wb_off[z + 1] = S.wb_off[z] + (int32_t)c.wcap;
+        const int need = 2 * ((int)c.wcap - 1);                    // window-edge columns of a pass
+        for (int r = b->read_off[z]; r < b->read_off[z + 1]; ++r) {
+            S.read_zmw[r] = z;
+            S.ent_off[r + 1] = S.ent_off[r] + ((need + 3) & ~3);   // (a multiple of 4: k_align16_tb stores four entries at a time)
+        }
+        T.nr_max = std::max(T.nr_max, std::min(b->read_off[z + 1] - b->read_off[z], top)); T.need_max = std::max(T.need_max, need);
+        T.maxL_max = std::max(T.maxL_max, c.maxL); T.vcap_max = std::max<int64_t>(T.vcap_max, S.vcap[z]); T.dcap_max = std::max<int64_t>(T.dcap_max, S.dcap[z]);
+    });
+    if (T.maxL_max > 65535) { ccsx_set_error("ccsx_upload: subreads longer than 65535 bases are not supported"); return -1; }
+    std::memcpy(S.read_off.p, b->read_off, (size_t)(n + 1) * 4);
+    std::memcpy(S.base_off.p, b->base_off, (size_t)(R + 1) * 8);
+    T.total_wslots = (int64_t)S.wb_off[n] - n; T.cap_total = S.seq_off[n];
+    auto order_by = [](PinVec<int32_t> &perm, size_t cnt_items, auto len_of) {
+        const int NBK = 258;
+        std::vector<int32_t> cnt(NBK + 1, 0);
+        auto cls = [&](int64_t l) { int c = (int)(l >> 8); return NBK - 1 - (c > NBK - 1 ? NBK - 1 : c); };   // descending length
+        for (size_t i = 0; i < cnt_items; ++i) ++cnt[cls(len_of(i)) + 1];
+        for (int i = 0; i < NBK; ++i) cnt[i + 1] += cnt[i];
+        for (size_t i = 0; i < cnt_items; ++i) perm[cnt[cls(len_of(i))]++] = (int32_t)i;
+    };
+    order_by(S.zperm, (size_t)n, [&](size_t z) { return (int64_t)S.dcap[z]; });
+    if (R > 0) order_by(S.rperm, (size_t)R, [&](size_t r) { return b->base_off[r + 1] - b->base_off[r]; });
+    // k_align16's work items: up to four consecutive passes of one ZMW (of the passes the engine uses), longest first
+    std::vector<int32_t> qpack; std::vector<int64_t> qlen;
+    for (int z = 0; z < n; ++z) {
+        const int r0 = b->read_off[z];
+        int nr = std::min(b->read_off[z + 1] - r0, top);
+        while (nr > 0 && (b->flags[r0 + nr - 1] & 2)) --nr;   // partial passes are aligned by k_rescue (anchored at one end), not here
+        for (int g = 0; g < nr; g += 4) {
+            const int c = std::min(4, nr - g);
+            int64_t ml = 0;
+            for (int q = 0; q < c; ++q) ml = std::max<int64_t>(ml, b->base_off[r0 + g + q + 1] - b->base_off[r0 + g + q]);
+            qpack.push_back(((r0 + g) << 2) | (c - 1)); qlen.push_back(ml);
+        }
+    }
+    T.n_quads = (int)qpack.size();
+    if (S.quads.resize(T.n_quads > 0 ? T.n_quads : 1)) return -2;
+    if (T.n_quads > 0) {
+        if (S.qperm.resize(T.n_quads)) return -2;
+        order_by(S.qperm, (size_t)T.n_quads, [&](size_t q) { return qlen[q]; });
+        for (int q = 0; q < T.n_quads; ++q) S.quads[q] = qpack[S.qperm[q]];
+    }
+    if (T.total_wslots > 0x7fff0000ll) { ccsx_set_error("ccsx_upload: batch too large (more than 2^31 window slots): split it"); return -1; }
+    return 0;
+}
+
+// the words of k_sdust's LDS mask, which covers the longest draft the cascade aligns; -1, refused, when mask and tables exceed a CU's LDS
+static int32_t sdust_mask_words(ccsx_handle h, const Slot &S)
+{
+    const int64_t longest = longest_draft(h, S, 16), words = (longest + 31) / 32;
+    if ((int64_t)CCSX_SDUST_TABLE_BYTES + 4 * words <= 160 * 1024) return (int32_t)words;
+    ccsx_set_error("tandem-repeat detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than a CU has (lower opts.max_length)");
+    return -1;
+}
+
+// a slot buffer of `bytes`, and the KParams pointer `dst` to it: a buffer's size and its binding are written once, here
+#define RES(dst, buf, bytes) do { if ((buf).reserve(bytes)) return -2; (dst) = (decltype(dst))(buf).p; } while (0)
+
+// the batch's arrays and the slot's layout into their device buffers, bound to P: H2D copies enqueued on `st`, in this order
+static int upload_inputs(Slot &S, const ccsx_batch *b, bool kin, hipStream_t st, KParams &P)
+{
+    const size_t n = (size_t)b->n_zmw, R = (size_t)b->n_reads, R1 = R > 0 ? R : 1, NB = (size_t)b->n_bases;
+#define UP(dst, buf, src, bytes) do { RES(dst, buf, bytes); HIPTRY(hipMemcpyAsync((buf).p, (src), (bytes), hipMemcpyHostToDevice, st)); } while (0)
+    UP(P.snr, S.d_snr, b->snr, n * 16);
+    UP(P.read_off, S.d_read_off, b->read_off, (n + 1) * 4);
+    UP(P.base_off, S.d_base_off, b->base_off, (R + 1) * 8);
+    UP(P.bases, S.d_bases, b->bases, NB);
+    UP(P.pw, S.d_pw, b->pw, NB);
+    if (kin) UP(P.ipd, S.d_ipd, b->ipd, NB);
+    UP(P.flags, S.d_flags, b->flags, R1);
+    UP(P.read_zmw, S.d_read_zmw, S.read_zmw.p, R1 * 4);
+    UP(P.vcap, S.d_vcap, S.vcap.p, n * 4);
+    UP(P.dcap, S.d_dcap, S.dcap.p, n * 4);
+    UP(P.seq_off, S.d_seq_off, S.seq_off.p, (n + 1) * 8);
+    UP(P.wb_off, S.d_wb_off, S.wb_off.p, (n + 1) * 4);
+    UP(P.ent_off, S.d_ent_off, S.ent_off.p, (R + 1) * 8);
+    UP(P.zmw_perm, S.d_zperm, S.zperm.p, S.zperm.size() * 4);
+    UP(P.read_perm, S.d_rperm, S.rperm.p, S.rperm.size() * 4);
+    UP(P.quads, S.d_quads, S.quads.p, S.quads.size() * 4);
+#undef UP
+    return 0;
+}
+
+// the slot's per-ZMW state, per-window and per-pass working arrays and outputs, sized by the layout and bound to P; the optional analyses' only when they run
+static int reserve_state(Slot &S, size_t n, size_t R, bool kin, bool pile, bool tandem, KParams &P)
+{
+    const size_t R1 = R > 0 ? R : 1, wins = (size_t)S.T.total_wslots + 1, cap = (size_t)S.T.cap_total, ents = (size_t)(S.ent_off[R] + 1);
+    RES(P.tabME, S.d_tabME, n * 192 * 4); RES(P.tabINS, S.d_tabINS, n * 192 * 4); RES(P.tabDL, S.d_tabDL, n * 16 * 4); RES(P.tabZ, S.d_tabZ, n * 32 * 4);
+    RES(P.draft, S.d_draft, cap);
+    if (carve_planes<int32_t>({&P.draft_len, &P.nwin, &P.zstat, &P.nreads_used, &P.np, &P.zref, &P.nfull}, S.d_zmw_i32, n)) return -2;
+    RES(P.wbounds, S.d_wbounds, (size_t)S.wb_off[n] * 4);
+    RES(P.wslot_zmw, S.d_wslot, wins * 4 + (n + 2) * 4);      // compact window map + first index per ZMW, built by k_wmap
+    P.wstart = P.wslot_zmw + wins;
+    RES(P.ticket_poa, S.d_ticket, 256);
+    P.ticket_align = P.ticket_poa + 1; P.debug = P.ticket_poa + 4; P.phase = (unsigned long long *)(P.ticket_poa + 16);
+    RES(P.avalid, S.d_avalid, R1); RES(P.ascore, S.d_ascore, R1 * 4);
+    RES(P.align_retry, S.d_retry, (R1 + 16) * 4);
+    RES(P.ent, S.d_ent, ents * 4); RES(P.dmask, S.d_dmask, ents * 4);
+    RES(P.wseq, S.d_wseq, wins * 32); RES(P.wqv, S.d_wqv, wins * 32 * 4);
+    RES(P.wsum, S.d_wsum, wins * 4); RES(P.wmeta, S.d_wmeta, wins * 16);
+    RES(P.out_seq, S.d_out_seq, cap); RES(P.out_qual, S.d_out_qual, cap); RES(P.out_raw, S.d_out_raw, cap * 4);
+    if (carve_planes<int32_t>({&P.out_status, &P.out_len, &P.out_iters, &P.out_nwin, &P.out_fn, &P.out_rn}, S.d_out_i32, n)) return -2;
+    if (carve_planes<float>({&P.out_rq, &P.out_ec}, S.d_out_f32, n)) return -2;
+    if (kin || pile) { RES(P.wtpl, S.d_wtpl, wins * 32); RES(P.wtmeta, S.d_wtmeta, wins * 4); }   // k_polish keeps the converged templates
+    if (kin) { RES(P.wkin, S.d_wkin, wins * 32 * 4); RES(P.out_kin, S.d_out_kin, cap * 4); P.kin_plane = S.T.cap_total; }
+    if (pile) { RES(P.wpile, S.d_wpile, wins * 32 * 4); RES(P.out_pile, S.d_out_pile, cap * 3); P.pile_plane = S.T.cap_total; }
+    if (tandem) { RES(P.tflag, S.d_tflag, n * 4); RES(P.tlen, S.d_tlen, n * 4); }
+    return 0;
+}
+#undef RES
+
+// ---- the shared POA / alignment scratch: what a batch needs per resident POA graph / retry alignment / k_align16 quad, how many of each it gets
+struct SlotSizes { size_t poa_bytes, align_i32, align16_i32; };
+struct ScratchPlan { int poa_slots, align_slots, align16_slots, align16_regions; };
+
+static SlotSizes scratch_slot_sizes(const BatchTotals &T)
+{
+    // per vertex CCSX_POA_BYTES_PER_VERTEX (ccsx_kernels.h; the kernels' layout static_asserts the same figure) + the pass's path + the state block;
+    // (origin, dirty bits) per cell and edge + band starts + best cell (score, row, entry row) per edge;
+    // k_align16 stores a quad's moves instead (2 bits per band row and column + 2 bits of band step and an edge flag per column: 18 words per block of 16 draft
+    // columns and pass): four passes' moves + the four final band starts, padded, for the draft CAPACITY of the batch's longest insert
+    return {(((size_t)T.vcap_max + 64) * CCSX_POA_BYTES_PER_VERTEX + (size_t)T.maxL_max * 4 + 1024 + 255) & ~(size_t)255,
+            (size_t)T.need_max * 128 + 4 * (size_t)T.need_max + 64,
+            (size_t)4 * (size_t)ccsx_tb_stride((int)T.dcap_max) + 16};
+}
+
+// the sizing expressions of the plan (plan_scratch) and of the clamps after a failed growth (launch)
+static size_t slots_that_fit(size_t room, size_t per_slot, size_t at_least) { return std::max(at_least, room / per_slot); }
+static size_t align16_words(int regions, int slots, size_t slot_i32) { return (size_t)regions * slots * slot_i32; }   // k_align16's part of the alignment scratch: the retry's slots lie behind it
+
+// Resident POA graphs / alignment slots for a batch of n ZMWs, R passes and n_quads quads within `budget` bytes: as many as fit, never more than the work.
+// opt_poa_slots: opts.poa_slots; one_region, max16: the process's CCSX_A16_ONE_REGION and CCSX_ALIGN16_MAX_SLOTS.
+static ScratchPlan plan_scratch(size_t budget, int n, int R, int n_quads, const SlotSizes &sz, int opt_poa_slots, bool one_region, int max16)
+{
+    ScratchPlan p;
+    p.poa_slots = std::min(opt_poa_slots > 0 ? opt_poa_slots : 16384, n);   // four graphs per wave: 16384 = 4 waves per SIMD
+    p.poa_slots = (int)std::min<size_t>((size_t)p.poa_slots, slots_that_fit(budget * 3 / 4, sz.poa_bytes, 1));
+    p.align_slots = std::min(4096, std::max(R, 2));             // the 64-row retry and the split alignment (two slots per pass) run grid-stride loops of <= 4096 workgroups
+    p.align_slots = (int)std::min<size_t>((size_t)p.align_slots, slots_that_fit(budget / 16, sz.align_i32 * 4, 2));
+    // every quad of the batch in ONE launch if that fits 12 GB (16384 ZMWs x 10 passes x 10 kb: 9.3 GB); a batch of long inserts and many passes takes a few
+    // equal launches instead of tens of GB of scratch (a launch's trace-back still has thousands of waves)
+    const size_t fit = slots_that_fit(std::min<size_t>(budget / 8, (size_t)12 << 30), sz.align16_i32 * 4, 1), nq = (size_t)std::max(n_quads, 1);
+    auto equal_launches = [nq](size_t at_most) { const size_t launches = (nq + at_most - 1) / at_most; return (int)((nq + launches - 1) / launches); };
+    p.align16_regions = 1;
+    if (nq <= fit) p.align16_slots = (int)nq;
+    else if (one_region) p.align16_slots = equal_launches(fit);   // (A/B switch: equal launches in ONE region, in sequence)
+    else { p.align16_slots = equal_launches(std::max<size_t>(1, fit / 2)); p.align16_regions = 2; }   // two regions of half the space: launch c's trace-back runs under launch c + 1
+    if (max16 > 0 && p.align16_slots > max16) { p.align16_slots = max16; p.align16_regions = 2; }     // test hook: forces several launches
+    return p;
+}
+
+// the shared scratch as the handle holds it now, for the slots P has
+static void bind_scratch(ccsx_handle h, KParams &P)
+{
+    P.poa_scratch = (uint8_t *)h->d_poa.p; P.align_scratch = (int32_t *)h->d_align.p;
+    P.retry_scratch = P.align_scratch + align16_words(P.align16_regions, P.align16_slots, P.align16_slot_i32);
+}
+
+// The plan for this handle's share of the device's free memory, bound to P, and the scratch grown to it.  The scratch is shared by the handle's batch slots; it only grows,
+// and growing waits for the draft and polish streams.
+static int grow_scratch(ccsx_handle h, int n, int R, const BatchTotals &T, KParams &P)
+{
+    const SlotSizes sz = scratch_slot_sizes(T);
+    static const bool one_region = [] { const char *e = getenv("CCSX_A16_ONE_REGION"); return e && e[0] == '1'; }();
+    static const int max16 = [] { const char *e = getenv("CCSX_ALIGN16_MAX_SLOTS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
+    std::lock_guard<std::mutex> lk(g_scratch_mutex);
+    size_t freeb = 0, totalb = 0;
+    HIPTRY(hipMemGetInfo(&freeb, &totalb));
+    freeb /= (size_t)h->handles_on_device;
+    freeb += h->d_poa.cap + h->d_align.cap;                      // what we already hold is reusable
+    ScratchPlan p = plan_scratch(freeb > (size_t)6 << 30 ? freeb - ((size_t)4 << 30) : freeb / 2, n, R, T.n_quads, sz, h->opts.poa_slots, one_region, max16);
+    const size_t need_align = ((size_t)p.align_slots * sz.align_i32 + align16_words(p.align16_regions, p.align16_slots, sz.align16_i32)) * 4;
+    if ((size_t)p.poa_slots * sz.poa_bytes > h->d_poa.cap || need_align > h->d_align.cap) {
+        HIPTRY(hipStreamSynchronize(h->s_draft));                // kernels of an earlier batch may still use the old scratch
+        HIPTRY(hipStreamSynchronize(h->s_comp));
+        for (int attempt = 0;; ++attempt) {                      // another process / handle may have taken the memory meanwhile
+            if (h->d_poa.reserve((size_t)p.poa_slots * sz.poa_bytes) == 0) break;
+            if (attempt >= 4 || p.poa_slots <= 1) return -2;
+            p.poa_slots = std::max(1, p.poa_slots / 2);
+        }
+        if (h->d_align.reserve(need_align)) return -2;
+    }
+    P.poa_slot_bytes = sz.poa_bytes; P.poa_slots = p.poa_slots;
+    P.align_slot_i32 = sz.align_i32; P.align_slots = p.align_slots;
+    P.align16_slot_i32 = sz.align16_i32; P.align16_slots = p.align16_slots; P.align16_regions = p.align16_regions;
+    bind_scratch(h, P);
+    return 0;
+}
+
 // Stage a batch into a slot: host-derived layout, device buffers, H2D copies enqueued on `st` (nothing waits here except
 // hipMalloc growth).  The batch's own arrays must stay valid until the copies have run (pinned arrays copy by DMA).
 // W.pile: this run also computes the pileup summary (its buffers are reserved and its pointers set only then).
 // W.tandem: it also runs tandem-repeat detection (k_sdust), flagging ZMWs at W.min_tandem > 0 (the same rule for its buffers and pointers).
+// The slot's KParams are built from nothing (the requests' part is attach()'s) and replace the old ones only when every step has succeeded.
 static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, const Wants &W)
 {
     if (validate(b)) return -1;
-    const bool pile = W.pile != nullptr, tandem = W.tandem;
-    const bool kin = h->opts.hifi_kinetics != 0;
+    const bool kin = h->opts.hifi_kinetics != 0, pile = W.pile != nullptr;
     if (kin && !b->ipd) { ccsx_set_error("ccsx_upload: opts.hifi_kinetics needs batch.ipd"); return -1; }
     const int n = b->n_zmw, R = b->n_reads;
-    const int64_t NB = b->n_bases;
-    // ---- host-derived layout
-    if (S.read_zmw.resize(R > 0 ? R : 1) || S.vcap.resize(n) || S.dcap.resize(n) || S.seq_off.assign(n + 1, 0) || S.wb_off.assign(n + 1, 0) ||
-        S.ent_off.assign(R + 1, 0) || S.read_off.resize(n + 1) || S.base_off.resize(R + 1) || S.zperm.resize(n) || S.rperm.resize(R > 0 ? R : 1))
-        return -2;
-    int64_t maxL_max = 1, vcap_max = 1; int need_max = 2, nr_max = 1, nr_min = 1 << 30, n_quads = 0;
-    for (int z = 0; z < n; ++z) {
-        int64_t maxL = 0;
-        int nr = b->read_off[z + 1] - b->read_off[z];
-        { const int top = (h->opts.top_passes <= 0 || h->opts.top_passes > CCSX_MAX_PASSES) ? CCSX_MAX_PASSES : h->opts.top_passes; if (nr > top) nr = top; }
-        nr_max = std::max(nr_max, nr); nr_min = std::min(nr_min, nr);
-        for (int r = b->read_off[z]; r < b->read_off[z + 1]; ++r) {
-            S.read_zmw[r] = z;
-            const int64_t L = b->base_off[r + 1] - b->base_off[r];
-            if (L > maxL) maxL = L;
-        }
-        S.dcap[z] = (int32_t)ccsx_draft_cap(maxL);
-        S.vcap[z] = (int32_t)ccsx_vertex_cap(maxL);
-        const int wcap = S.dcap[z] / (CCSX_WIN_CORE - 3) + 4;   // cores are 19..25 columns (SPEC windows)
-        S.seq_off[z + 1] = S.seq_off[z] + S.dcap[z];
-        S.wb_off[z + 1] = S.wb_off[z] + wcap;
-        for (int r = b->read_off[z]; r < b->read_off[z + 1]; ++r) S.ent_off[r + 1] = S.ent_off[r] + ((2 * (wcap - 1) + 3) & ~3);   // (a multiple of 4: k_align16_tb stores four entries at a time)
-        maxL_max = std::max(maxL_max, maxL); vcap_max = std::max<int64_t>(vcap_max, S.vcap[z]); need_max = std::max(need_max, 2 * (wcap - 1));
-    }
-    if (maxL_max > 65535) { ccsx_set_error("ccsx_upload: subreads longer than 65535 bases are not supported"); return -1; }
-    std::memcpy(S.read_off.p, b->read_off, (size_t)(n + 1) * 4);
-    std::memcpy(S.base_off.p, b->base_off, (size_t)(R + 1) * 8);
-    // launch order: longest first (stable within 256-base classes, so a uniform batch keeps its input order and its
-    // locality).  Mixed batches (BASELINE configs[4]: 1-25 kb, 3-50 passes) otherwise end on a few long stragglers.
-    {
-        auto order_by = [](PinVec<int32_t> &perm, size_t cnt_items, auto len_of) {
-            const int NBK = 258;
-            std::vector<int32_t> cnt(NBK + 1, 0);
-            auto cls = [&](int64_t l) { int c = (int)(l >> 8); return NBK - 1 - (c > NBK - 1 ? NBK - 1 : c); };   // descending length
-            for (size_t i = 0; i < cnt_items; ++i) ++cnt[cls(len_of(i)) + 1];
-            for (int i = 0; i < NBK; ++i) cnt[i + 1] += cnt[i];
-            for (size_t i = 0; i < cnt_items; ++i) perm[cnt[cls(len_of(i))]++] = (int32_t)i;
-        };
-        order_by(S.zperm, (size_t)n, [&](size_t z) { return (int64_t)S.dcap[z]; });
-        if (R > 0) order_by(S.rperm, (size_t)R, [&](size_t r) { return b->base_off[r + 1] - b->base_off[r]; });
-        // k_align16's work items: up to four consecutive passes of one ZMW (of the passes the engine uses), longest first
-        std::vector<int32_t> qpack; std::vector<int64_t> qlen;
-        const int top = (h->opts.top_passes <= 0 || h->opts.top_passes > CCSX_MAX_PASSES) ? CCSX_MAX_PASSES : h->opts.top_passes;
-        for (int z = 0; z < n; ++z) {
-            const int r0 = b->read_off[z];
-            int nr = std::min(b->read_off[z + 1] - r0, top);
-            while (nr > 0 && (b->flags[r0 + nr - 1] & 2)) --nr;   // partial passes are aligned by k_rescue (anchored at one end), not here
-            for (int g = 0; g < nr; g += 4) {
-                const int c = std::min(4, nr - g);
-                int64_t ml = 0;
-                for (int q = 0; q < c; ++q) ml = std::max<int64_t>(ml, b->base_off[r0 + g + q + 1] - b->base_off[r0 + g + q]);
-                qpack.push_back(((r0 + g) << 2) | (c - 1)); qlen.push_back(ml);
-            }
-        }
-        n_quads = (int)qpack.size();
-        if (S.quads.resize(n_quads > 0 ? n_quads : 1)) return -2;
-        if (n_quads > 0) {
-            if (S.qperm.resize(n_quads)) return -2;
-            order_by(S.qperm, (size_t)n_quads, [&](size_t q) { return qlen[q]; });
-            for (int q = 0; q < n_quads; ++q) S.quads[q] = qpack[S.qperm[q]];
-        }
-    }
-    const int64_t total_wslots = (int64_t)S.wb_off[n] - n;
-    if (total_wslots > 0x7fff0000ll) { ccsx_set_error("ccsx_upload: batch too large (more than 2^31 window slots): split it"); return -1; }
-    int32_t sdust_words = 0;
-    if (tandem) {
-        const int64_t longest = longest_draft(h, S, 16);      // k_sdust's LDS mask covers the longest draft the cascade aligns
-        sdust_words = (int32_t)((longest + 31) / 32);
-        if ((int64_t)CCSX_SDUST_TABLE_BYTES + 4 * (int64_t)sdust_words > 160 * 1024) {
-            ccsx_set_error("tandem-repeat detection: drafts of up to " + std::to_string(longest) + " bases need more LDS than a CU has (lower opts.max_length)");
-            return -1;
-        }
-    }
-
-#define UP(buf, src, bytes)                                                                                    \
-    do {                                                                                                       \
-        if ((buf).reserve(bytes)) return -2;                                                                   \
-        HIPTRY(hipMemcpyAsync((buf).p, (src), (bytes), hipMemcpyHostToDevice, st));                             \
-    } while (0)
-    UP(S.d_snr, b->snr, (size_t)n * 16);
-    UP(S.d_read_off, b->read_off, (size_t)(n + 1) * 4);
-    UP(S.d_base_off, b->base_off, (size_t)(R + 1) * 8);
-    UP(S.d_bases, b->bases, (size_t)NB);
-    UP(S.d_pw, b->pw, (size_t)NB);
-    if (kin) UP(S.d_ipd, b->ipd, (size_t)NB);
-    UP(S.d_flags, b->flags, (size_t)(R > 0 ? R : 1));
-    UP(S.d_read_zmw, S.read_zmw.p, (size_t)(R > 0 ? R : 1) * 4);
-    UP(S.d_vcap, S.vcap.p, (size_t)n * 4);
-    UP(S.d_dcap, S.dcap.p, (size_t)n * 4);
-    UP(S.d_seq_off, S.seq_off.p, (size_t)(n + 1) * 8);
-    UP(S.d_wb_off, S.wb_off.p, (size_t)(n + 1) * 4);
-    UP(S.d_ent_off, S.ent_off.p, (size_t)(R + 1) * 8);
-    UP(S.d_zperm, S.zperm.p, S.zperm.size() * 4);
-    UP(S.d_rperm, S.rperm.p, S.rperm.size() * 4);
-    UP(S.d_quads, S.quads.p, S.quads.size() * 4);
-#undef UP
-
-    const int64_t cap_total = S.seq_off[n];
-#define RES(buf, bytes) do { if ((buf).reserve(bytes)) return -2; } while (0)
-    RES(S.d_tabME, (size_t)n * 192 * 4); RES(S.d_tabINS, (size_t)n * 192 * 4); RES(S.d_tabDL, (size_t)n * 16 * 4); RES(S.d_tabZ, (size_t)n * 32 * 4);
-    RES(S.d_draft, (size_t)cap_total);
-    RES(S.d_zmw_i32, (size_t)n * 4 * 7);   // draft_len, nwin, zstat, nreads_used, np, zref, nfull
-    RES(S.d_wbounds, (size_t)S.wb_off[n] * 4);
-    RES(S.d_wslot, (size_t)(total_wslots + 1) * 4 + ((size_t)n + 2) * 4);      // compact window map + first index per ZMW, built by k_wmap
-    RES(S.d_ticket, 256);
-    RES(S.d_avalid, (size_t)(R > 0 ? R : 1)); RES(S.d_ascore, (size_t)(R > 0 ? R : 1) * 4);
-    RES(S.d_retry, ((size_t)(R > 0 ? R : 1) + 16) * 4);
-    RES(S.d_ent, (size_t)(S.ent_off[R] + 1) * 4); RES(S.d_dmask, (size_t)(S.ent_off[R] + 1) * 4);
-    RES(S.d_wseq, (size_t)(total_wslots + 1) * 32); RES(S.d_wqv, (size_t)(total_wslots + 1) * 32 * 4);
-    RES(S.d_wsum, (size_t)(total_wslots + 1) * 4); RES(S.d_wmeta, (size_t)(total_wslots + 1) * 16);
-    RES(S.d_out_seq, (size_t)cap_total); RES(S.d_out_qual, (size_t)cap_total); RES(S.d_out_raw, (size_t)cap_total * 4);
-    RES(S.d_out_i32, (size_t)n * 4 * 6); RES(S.d_out_f32, (size_t)n * 4 * 2);
-    if (kin || pile) { RES(S.d_wtpl, (size_t)(total_wslots + 1) * 32); RES(S.d_wtmeta, (size_t)(total_wslots + 1) * 4); }
-    if (kin) { RES(S.d_wkin, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_kin, (size_t)cap_total * 4); }
-    if (pile) { RES(S.d_wpile, (size_t)(total_wslots + 1) * 32 * 4); RES(S.d_out_pile, (size_t)cap_total * 3); }
-    if (tandem) { RES(S.d_tflag, (size_t)n * 4); RES(S.d_tlen, (size_t)n * 4); }
-
-    // ---- resident POA graphs / alignment slots: as many as fit this handle's share of the free memory, never more than
-    // the work.  The scratch is shared by the handle's batch slots; it only grows, and growing waits for the compute stream.
-    // (per vertex CCSX_POA_BYTES_PER_VERTEX, ccsx_kernels.h; the kernels' layout static_asserts the same figure) + the pass's path + the state block
-    S.poa_slot_bytes = (((size_t)vcap_max + 64) * CCSX_POA_BYTES_PER_VERTEX + (size_t)maxL_max * 4 + 1024 + 255) & ~(size_t)255;
-    S.align_slot_i32 = (size_t)need_max * 128 + 4 * (size_t)need_max + 64;   // (origin, dirty bits) per cell and edge + band starts + best cell (score, row, entry row) per edge
-    // k_align16 stores a quad's moves instead (2 bits per band row and column + 2 bits of band step and an edge flag per column: 18 words per block of 16 draft columns and pass)
-    int64_t dcap_max = 16;
-    for (int z = 0; z < n; ++z) dcap_max = std::max<int64_t>(dcap_max, S.dcap[z]);
-    S.align16_slot_i32 = (size_t)4 * (size_t)ccsx_tb_stride((int)dcap_max) + 16;        // (four passes' moves + the four final band starts, padded)
-    int poa_slots, align_slots, align16_slots;
-    {
-        std::lock_guard<std::mutex> lk(g_scratch_mutex);
-        size_t freeb = 0, totalb = 0;
-        HIPTRY(hipMemGetInfo(&freeb, &totalb));
-        freeb /= (size_t)h->handles_on_device;
-        freeb += h->d_poa.cap + h->d_align.cap;                      // what we already hold is reusable
-        const size_t budget = freeb > (size_t)6 << 30 ? freeb - ((size_t)4 << 30) : freeb / 2;
-        poa_slots = h->opts.poa_slots > 0 ? h->opts.poa_slots : 16384;   // four graphs per wave: 16384 = 4 waves per SIMD
-        poa_slots = std::min(poa_slots, n);
-        poa_slots = (int)std::min<size_t>((size_t)poa_slots, std::max<size_t>(1, (budget * 3 / 4) / S.poa_slot_bytes));
-        align_slots = std::min(4096, std::max(R, 2));             // the 64-row retry and the split alignment (two slots per pass) run grid-stride loops of <= 4096 workgroups
-        align_slots = (int)std::min<size_t>((size_t)align_slots, std::max<size_t>(2, (budget / 16) / (S.align_slot_i32 * 4)));
-        // every quad of the batch in ONE launch if that fits 12 GB (16384 ZMWs x 10 passes x 10 kb: 9.3 GB — the slot is sized for the draft CAPACITY of the batch's
-        // longest insert); a batch of long inserts and many passes takes a few equal launches instead of tens of GB of scratch (a launch's trace-back still has
-        // thousands of waves)
-        int align16_regions = 1;
-        {
-            const size_t fit = std::max<size_t>(1, std::min<size_t>(budget / 8, (size_t)12 << 30) / (S.align16_slot_i32 * 4));
-            const size_t nq = (size_t)std::max(n_quads, 1);
-            static const bool one_region = [] { const char *e = getenv("CCSX_A16_ONE_REGION"); return e && e[0] == '1'; }();   // (A/B switch: equal launches in ONE region, in sequence)
-            if (nq <= fit) align16_slots = (int)nq;
-            else if (one_region) { const size_t launches = (nq + fit - 1) / fit; align16_slots = (int)((nq + launches - 1) / launches); }
-            else {                                                       // two regions of half the space: launch c's trace-back runs under launch c + 1
-                const size_t half = std::max<size_t>(1, fit / 2), launches = (nq + half - 1) / half;
-                align16_slots = (int)((nq + launches - 1) / launches);
-                align16_regions = 2;
-            }
-        }
-        static const int max16 = [] { const char *e = getenv("CCSX_ALIGN16_MAX_SLOTS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();   // test hook: forces several launches
-        if (max16 > 0 && align16_slots > max16) { align16_slots = max16; align16_regions = 2; }
-        const size_t need_align = ((size_t)align_slots * S.align_slot_i32 + (size_t)align16_regions * align16_slots * S.align16_slot_i32) * 4;   // the retry's slots behind k_align16's
-        S.align16_regions = align16_regions;
-        if ((size_t)poa_slots * S.poa_slot_bytes > h->d_poa.cap || need_align > h->d_align.cap) {
-            HIPTRY(hipStreamSynchronize(h->s_draft));                // kernels of an earlier batch may still use the old scratch
-            HIPTRY(hipStreamSynchronize(h->s_comp));
-            for (int attempt = 0;; ++attempt) {                      // another process / handle may have taken the memory meanwhile
-                if (h->d_poa.reserve((size_t)poa_slots * S.poa_slot_bytes) == 0) break;
-                if (attempt >= 4 || poa_slots <= 1) return -2;
-                poa_slots = std::max(1, poa_slots / 2);
-            }
-            RES(h->d_align, need_align);
-        }
-    }
-#undef RES
-
-    KParams &P = S.P;
+    int rc;
+    if ((rc = layout(S, b, ccsx_top_passes(h->opts.top_passes), &S.T))) return rc;
+    const BatchTotals &T = S.T;
+    KParams P;
     std::memset(&P, 0, sizeof(P));
-    P.n_zmw = n; P.n_reads = R; P.maxL_max = (int32_t)maxL_max; P.vcap_max = (int32_t)vcap_max; P.need_max = need_max; P.max_reads = nr_max;
-    (void)nr_min;
+    if (W.tandem) {
+        P.min_tandem = W.min_tandem;
+        if ((P.sdust_words = sdust_mask_words(h, S)) < 0) return -1;
+    }
+    if ((rc = upload_inputs(S, b, kin, st, P)) || (rc = reserve_state(S, (size_t)n, (size_t)R, kin, pile, W.tandem, P))) return rc;
+    if ((rc = grow_scratch(h, n, R, T, P))) return rc;
+    P.n_zmw = n; P.n_reads = R; P.maxL_max = (int32_t)T.maxL_max; P.vcap_max = (int32_t)T.vcap_max; P.need_max = T.need_max; P.max_reads = T.nr_max;
+    P.n_quads = T.n_quads; P.total_wslots = T.total_wslots;
     P.opts = h->opts;
     P.perr_floor = ccsx_perr_floor(h->opts.max_qv);
     P.model = (const ccsx_model *)h->d_model.p;
-    P.snr = (const float *)S.d_snr.p; P.read_off = (const int32_t *)S.d_read_off.p; P.base_off = (const int64_t *)S.d_base_off.p;
-    P.bases = (const uint8_t *)S.d_bases.p; P.pw = (const uint8_t *)S.d_pw.p; P.flags = (const uint8_t *)S.d_flags.p;
-    P.read_zmw = (const int32_t *)S.d_read_zmw.p; P.vcap = (const int32_t *)S.d_vcap.p; P.dcap = (const int32_t *)S.d_dcap.p;
-    P.seq_off = (const int64_t *)S.d_seq_off.p; P.wb_off = (const int32_t *)S.d_wb_off.p; P.ent_off = (const int64_t *)S.d_ent_off.p; P.wslot_zmw = (int32_t *)S.d_wslot.p; P.wstart = P.wslot_zmw + (total_wslots + 1);
-    P.zmw_perm = (const int32_t *)S.d_zperm.p; P.read_perm = (const int32_t *)S.d_rperm.p;
-    P.quads = (const int32_t *)S.d_quads.p; P.n_quads = n_quads; P.align_retry = (int32_t *)S.d_retry.p;
-    P.tabME = (float *)S.d_tabME.p; P.tabINS = (float *)S.d_tabINS.p; P.tabDL = (float *)S.d_tabDL.p; P.tabZ = (float *)S.d_tabZ.p;
-    P.draft = (uint8_t *)S.d_draft.p;
-    int32_t *zi = (int32_t *)S.d_zmw_i32.p;
-    P.draft_len = zi; P.nwin = zi + n; P.zstat = zi + 2 * (size_t)n; P.nreads_used = zi + 3 * (size_t)n; P.np = zi + 4 * (size_t)n; P.zref = zi + 5 * (size_t)n; P.nfull = zi + 6 * (size_t)n;
-    P.wbounds = (int32_t *)S.d_wbounds.p;
-    P.ticket_poa = (int32_t *)S.d_ticket.p; P.ticket_align = P.ticket_poa + 1; P.debug = P.ticket_poa + 4; P.phase = (unsigned long long *)(P.ticket_poa + 16);
-    P.poa_scratch = (uint8_t *)h->d_poa.p; P.poa_slot_bytes = S.poa_slot_bytes; P.poa_slots = poa_slots;
-    P.align_scratch = (int32_t *)h->d_align.p; P.align_slot_i32 = S.align_slot_i32; P.align_slots = align_slots;
-    P.align16_slot_i32 = S.align16_slot_i32; P.align16_slots = align16_slots;
-    P.align16_regions = S.align16_regions;
-    P.retry_scratch = P.align_scratch + (size_t)S.align16_regions * align16_slots * S.align16_slot_i32;
-    P.avalid = (uint8_t *)S.d_avalid.p; P.ascore = (int32_t *)S.d_ascore.p; P.ent = (int32_t *)S.d_ent.p; P.dmask = (uint32_t *)S.d_dmask.p;
-    P.total_wslots = total_wslots;
-    if (ccsx_polish_lds(nr_max, &P.pw_obs_bytes, &P.pw_gb_floats)) { ccsx_set_error("ccsx_upload: cannot size the polish kernel's LDS"); return -2; }
-    P.wseq = (uint8_t *)S.d_wseq.p; P.wqv = (float *)S.d_wqv.p; P.wsum = (float *)S.d_wsum.p; P.wmeta = (int4 *)S.d_wmeta.p;
-    P.out_seq = (uint8_t *)S.d_out_seq.p; P.out_qual = (uint8_t *)S.d_out_qual.p; P.out_raw = (float *)S.d_out_raw.p;
-    int32_t *oi = (int32_t *)S.d_out_i32.p;
-    P.out_status = oi; P.out_len = oi + n; P.out_iters = oi + 2 * (size_t)n; P.out_nwin = oi + 3 * (size_t)n;
-    P.out_fn = oi + 4 * (size_t)n; P.out_rn = oi + 5 * (size_t)n;
-    if (kin || pile) { P.wtpl = (uint8_t *)S.d_wtpl.p; P.wtmeta = (short2 *)S.d_wtmeta.p; }   // k_polish keeps the converged templates
-    if (kin) {
-        P.ipd = (const uint8_t *)S.d_ipd.p;
-        P.wkin = (uchar4 *)S.d_wkin.p;
-        P.out_kin = (uint8_t *)S.d_out_kin.p; P.kin_plane = cap_total;
-    }
-    if (pile) { P.wpile = (uchar4 *)S.d_wpile.p; P.out_pile = (uint8_t *)S.d_out_pile.p; P.pile_plane = cap_total; }
-    if (tandem) { P.tflag = (int32_t *)S.d_tflag.p; P.tlen = (int32_t *)S.d_tlen.p; P.min_tandem = W.min_tandem; P.sdust_words = sdust_words; }
-    float *of = (float *)S.d_out_f32.p;
-    P.out_rq = of; P.out_ec = of + n;
+    if (ccsx_polish_lds(T.nr_max, &P.pw_obs_bytes, &P.pw_gb_floats)) { ccsx_set_error("ccsx_upload: cannot size the polish kernel's LDS"); return -2; }
+    S.P = P;
     S.staged = true; S.ran = false; S.tm_ok = false;
     return 0;
 }
@@ -637,18 +663,17 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, co
 static int launch(ccsx_handle h, Slot &S)
 {
     (void)hipGetLastError();
-    // the shared scratch may have been re-allocated (a later, larger batch) since this slot was staged
-    S.P.poa_scratch = (uint8_t *)h->d_poa.p; S.P.align_scratch = (int32_t *)h->d_align.p;
-    if ((size_t)S.P.poa_slots * S.P.poa_slot_bytes > h->d_poa.cap) S.P.poa_slots = (int)std::max<size_t>(1, h->d_poa.cap / S.P.poa_slot_bytes);
-    {   // (the scratch only grows, so what was sized at staging still fits; the clamps are for a failed growth)
-        const size_t words = h->d_align.cap / 4, reg = (size_t)std::max(1, S.P.align16_regions);
-        if ((size_t)S.P.align_slots * S.P.align_slot_i32 + reg * S.P.align16_slots * S.P.align16_slot_i32 > words) {
-            if ((size_t)S.P.align_slots * S.P.align_slot_i32 > words / 2) S.P.align_slots = (int)std::max<size_t>(1, (words / 2) / S.P.align_slot_i32);
-            const size_t used = (size_t)S.P.align_slots * S.P.align_slot_i32, left = words > used ? words - used : 0;
-            S.P.align16_slots = (int)std::max<size_t>(1, left / (reg * S.P.align16_slot_i32));
-        }
-        S.P.retry_scratch = S.P.align_scratch + reg * S.P.align16_slots * S.P.align16_slot_i32;
+    // The shared scratch may have been re-allocated (a later, larger batch) since this slot was staged.  It only grows, so what was planned at staging still fits;
+    // the clamps are for a failed growth, and only ever shrink the plan to what the buffers hold.
+    KParams &P = S.P;
+    if ((size_t)P.poa_slots * P.poa_slot_bytes > h->d_poa.cap) P.poa_slots = (int)slots_that_fit(h->d_poa.cap, P.poa_slot_bytes, 1);
+    const size_t words = h->d_align.cap / 4;
+    if ((size_t)P.align_slots * P.align_slot_i32 + align16_words(P.align16_regions, P.align16_slots, P.align16_slot_i32) > words) {
+        if ((size_t)P.align_slots * P.align_slot_i32 > words / 2) P.align_slots = (int)slots_that_fit(words / 2, P.align_slot_i32, 1);
+        const size_t used = (size_t)P.align_slots * P.align_slot_i32, left = words > used ? words - used : 0;
+        P.align16_slots = (int)slots_that_fit(left, (size_t)P.align16_regions * P.align16_slot_i32, 1);
     }
+    bind_scratch(h, P);
     if (!h->d_poa.p || !h->d_align.p) { ccsx_set_error("kernel launch refused: the POA / alignment scratch is not allocated (an earlier allocation failed)"); return -2; }
     const char *failed = ccsx_launch_all(S.P, h->s_draft, h->s_comp, S.ev, S.mode, h->s_aux, h->s_aux ? S.ev_aux : nullptr);
     if (failed) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }

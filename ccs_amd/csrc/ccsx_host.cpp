@@ -151,39 +151,24 @@ int ccsx_bind_thread_to_node(int node)
     return node;
 }
 
+// the capacity layout of a batch's results, and of a ccsx_drafts object: the draft slots are those of the results, a ZMW's window bounds take its wcap words
+// (ccsx_zmw_caps, ccsx_internal.h: the arithmetic of the engine's own slots)
 int64_t ccsx_result_layout(const ccsx_batch *b, int64_t *seq_off)
 {
-    int64_t off = 0;
-    for (int z = 0; z < b->n_zmw; ++z) {
-        seq_off[z] = off;
-        int64_t maxL = 0;
-        for (int r = b->read_off[z]; r < b->read_off[z + 1]; ++r) {
-            const int64_t L = b->base_off[r + 1] - b->base_off[r];
-            if (L > maxL) maxL = L;
-        }
-        off += ccsx_draft_cap(maxL);
-    }
-    seq_off[b->n_zmw] = off;
-    return off;
+    int64_t cap = 0;
+    ccsx_draft_layout(b, seq_off, nullptr, &cap, nullptr);
+    return cap;
 }
 
-// layout of a ccsx_drafts object: the draft slots are those of the results (capacity layout), a ZMW's window bounds take dcap / 19 + 4 words
-// (cores are 19..25 columns: SPEC windows) — the same arithmetic as the engine's own slots (ccsx_api.cpp stage())
 void ccsx_draft_layout(const ccsx_batch *b, int64_t *seq_off, int64_t *win_off, int64_t *seq_capacity, int64_t *win_capacity)
 {
     int64_t off = 0, woff = 0;
-    for (int z = 0; z < b->n_zmw; ++z) {
+    ccsx_for_each_zmw_caps(b, [&](int z, const ccsx_zmw_caps &c) {
         if (seq_off) seq_off[z] = off;
         if (win_off) win_off[z] = woff;
-        int64_t maxL = 0;
-        for (int r = b->read_off[z]; r < b->read_off[z + 1]; ++r) {
-            const int64_t L = b->base_off[r + 1] - b->base_off[r];
-            if (L > maxL) maxL = L;
-        }
-        const int64_t dcap = ccsx_draft_cap(maxL);
-        off += dcap;
-        woff += dcap / (CCSX_WIN_CORE - 3) + 4;
-    }
+        off += c.dcap;
+        woff += c.wcap;
+    });
     if (seq_off) seq_off[b->n_zmw] = off;
     if (win_off) win_off[b->n_zmw] = woff;
     if (seq_capacity) *seq_capacity = off;

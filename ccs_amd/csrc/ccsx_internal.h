@@ -1,7 +1,10 @@
 // ccsx_internal.h — shared between the host and device translation units of libccsx.so
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
+
+#include "ccsx.h"
 
 void ccsx_set_error(const std::string &s);
 
@@ -9,3 +12,22 @@ void ccsx_set_error(const std::string &s);
 static inline int64_t ccsx_draft_cap(int64_t maxL) { return maxL + maxL / 4 + 64; }
 // POA vertex capacity for the same ZMW
 static inline int64_t ccsx_vertex_cap(int64_t maxL) { return (5 * maxL) / 2 + 256; }
+
+// The capacity layout: everything a ZMW is given follows from its longest pass.  wcap: the words of its window bounds, one more than its window slots (cores are
+// 19..25 columns: SPEC windows).  The engine's slots (ccsx_api.cpp) and the layouts a caller sizes its buffers by (ccsx_result_layout, ccsx_draft_layout) are this
+// one definition.
+struct ccsx_zmw_caps { int64_t maxL, dcap, vcap, wcap; };
+static inline ccsx_zmw_caps ccsx_caps_of(int64_t maxL)
+{
+    const int64_t dcap = ccsx_draft_cap(maxL);
+    return {maxL, dcap, ccsx_vertex_cap(maxL), dcap / (CCSX_WIN_CORE - 3) + 4};
+}
+// f(z, caps of ZMW z) for every ZMW of a batch, in order
+template <typename F> static inline void ccsx_for_each_zmw_caps(const ccsx_batch *b, F f)
+{
+    for (int z = 0; z < b->n_zmw; ++z) {
+        int64_t maxL = 0;
+        for (int r = b->read_off[z]; r < b->read_off[z + 1]; ++r) maxL = std::max<int64_t>(maxL, b->base_off[r + 1] - b->base_off[r]);
+        f(z, ccsx_caps_of(maxL));
+    }
+}

@@ -19,6 +19,9 @@ static inline float ccsx_perr_floor(int max_qv) { return max_qv == 50 ? 1e-5f : 
 static inline __host__ __device__ int ccsx_tb_blocks(int Ld) { return (Ld + 15) >> 4; }
 static inline __host__ __device__ int ccsx_tb_stride(int Ld) { return (ccsx_tb_blocks(Ld) * CCSX_TB_WORDS_PER_BLOCK + 3) & ~3; }
 
+// passes of a ZMW the engine uses, for opts.top_passes: <= 0 (all of them) and anything above CCSX_MAX_PASSES mean CCSX_MAX_PASSES (SPEC v5)
+static inline __host__ __device__ int ccsx_top_passes(int top_passes) { return (top_passes <= 0 || top_passes > CCSX_MAX_PASSES) ? CCSX_MAX_PASSES : top_passes; }
+
 struct KParams {
     int32_t n_zmw, n_reads;
     int32_t maxL_max;          // longest subread of the batch

@@ -516,7 +516,7 @@ __global__ __launch_bounds__(64) void k_poa_init(KParams P, int z0, int pass, in
     const int r0 = rfl(P.read_off[z]);
     int nreads = rfl(P.read_off[z + 1]) - r0;
     {   // SPEC v5: at most CCSX_MAX_PASSES = 255 passes are used (--top-passes 0 = all of them)
-        const int top = (P.opts.top_passes <= 0 || P.opts.top_passes > PW_MAXREADS_SPEC) ? PW_MAXREADS_SPEC : P.opts.top_passes;
+        const int top = ccsx_top_passes(P.opts.top_passes);
         if (nreads > top) nreads = top;
     }
     // SPEC "partial passes" (flag bit 1; they follow the ZMW's full-length passes): not in the draft, not counted as passes
@@ -612,7 +612,7 @@ __global__ __launch_bounds__(64) void k_draft_in(KParams P)
     const int r0 = rfl(P.read_off[z]);
     int nreads = rfl(P.read_off[z + 1]) - r0;
     {
-        const int top = (P.opts.top_passes <= 0 || P.opts.top_passes > PW_MAXREADS_SPEC) ? PW_MAXREADS_SPEC : P.opts.top_passes;
+        const int top = ccsx_top_passes(P.opts.top_passes);
         if (nreads > top) nreads = top;
     }
     const int nall = nreads;
