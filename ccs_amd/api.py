@@ -449,6 +449,10 @@ def _pinned_array(count: int, dt, keep: list) -> np.ndarray:
     return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nb,))[: int(count) * dt.itemsize].view(dt)
 
 
+class DeflateBlock(C.Structure):
+    _fields_ = [("in_off", C.c_int64), ("in_len", C.c_int32), ("out_len", C.c_int32), ("out_off", C.c_int64)]
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("setup_ms", C.c_float), ("draft_ms", C.c_float), ("align_ms", C.c_float), ("polish_ms", C.c_float),
@@ -477,6 +481,8 @@ EXPORTS = [
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
     "ccsx_adapter_opts_default", "ccsx_adapter_rule_version", "ccsx_adapter_set_default", "ccsx_consensus_screen", "ccsx_submit_screen",
     "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
+    "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
+    "ccsx_inflate_blocks_host",
 ]
 
 _lib = None
@@ -557,6 +563,13 @@ def lib() -> C.CDLL:
                                              C.POINTER(CControlRequest)]
         L.ccsx_submit_control.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest),
                                           C.POINTER(CControlRequest), C.POINTER(C.c_int64)]
+        _call = [C.POINTER(C.c_uint8), C.c_int64, C.POINTER(DeflateBlock), C.c_int32, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int32)]
+        L.ccsx_inflater_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        L.ccsx_inflater_destroy.argtypes = [C.c_void_p]
+        L.ccsx_inflate_blocks.argtypes = [C.c_void_p] + _call
+        L.ccsx_inflate_submit.argtypes = [C.c_void_p] + _call + [C.POINTER(C.c_int64)]
+        L.ccsx_inflate_wait.argtypes = [C.c_void_p, C.c_int64]
+        L.ccsx_inflate_blocks_host.argtypes = _call
         _lib = L
     return _lib
 
@@ -1293,3 +1306,116 @@ def consensus_hd_stream(handle: "Handle", batches, opts: HdOpts | None = None):
         while nxt in done:
             yield done.pop(nxt)
             nxt += 1
+
+
+# ---- BGZF inflate (include/ccsx.h "BGZF inflate on the device"; DESIGN.md §2 "BGZF inflate")
+INFLATE_MAX_OUT = 65536
+INFLATE_STATUS_NAMES = ["OK", "TRUNCATED_INPUT", "BAD_BLOCK_TYPE", "BAD_STORED_LENGTH", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "OUTPUT_OVERRUN",
+                        "OUTPUT_SHORT"]
+
+
+def bgzf_split(data: bytes) -> list:
+    """The blocks of a BGZF byte string as (payload, isize, crc32): payload = the raw DEFLATE stream between the gzip member's header and its 8-byte trailer"""
+    out, at = [], 0
+    while at < len(data):
+        if len(data) - at < 18 or data[at:at + 2] != b"\x1f\x8b" or not data[at + 3] & 4:
+            raise ValueError(f"not a BGZF block at byte {at}")
+        xlen = int.from_bytes(data[at + 10:at + 12], "little")
+        bsize, p = 0, at + 12
+        while p + 4 <= at + 12 + xlen:
+            sl = int.from_bytes(data[p + 2:p + 4], "little")
+            if data[p:p + 2] == b"BC" and p + 6 <= at + 12 + xlen:
+                bsize = int.from_bytes(data[p + 4:p + 6], "little") + 1
+            p += 4 + sl
+        if not bsize or bsize < 12 + xlen + 8 or at + bsize > len(data):
+            raise ValueError(f"truncated or malformed BGZF block at byte {at}")
+        end = at + bsize
+        out.append((data[at + 12 + xlen:end - 8], int.from_bytes(data[end - 4:end], "little"), int.from_bytes(data[end - 8:end - 4], "little")))
+        at = end
+    return out
+
+
+class InflateCall:
+    """The buffers of one inflate call: payloads packed back to back (gap bytes apart) in src, outputs packed (guard bytes before, between and behind them) in dst"""
+
+    def __init__(self, payloads, out_lens, guard: int = 0, gap: int = 0, fill: int = 0):
+        n = len(payloads)
+        assert n == len(out_lens)
+        self.blocks = (DeflateBlock * max(n, 1))()
+        src, ioff, ooff = bytearray(), 0, guard
+        for i, (p, ol) in enumerate(zip(payloads, out_lens)):
+            self.blocks[i] = DeflateBlock(ioff, len(p), int(ol), ooff)
+            src += p + b"\0" * gap
+            ioff += len(p) + gap
+            ooff += int(ol) + guard
+        self.n, self.guard = n, guard
+        self.src = np.frombuffer(bytes(src) or b"\0", dtype=np.uint8).copy()
+        self.src_len = len(src)
+        self.dst = np.full(max(ooff, 1), fill, dtype=np.uint8)
+        self.dst_len = ooff
+        self.status = np.full(max(n, 1), -1, dtype=np.int32)
+
+    def args(self):
+        return (_ptr(self.src, C.c_uint8), self.src_len, self.blocks, self.n, _ptr(self.dst, C.c_uint8), self.dst_len, _ptr(self.status, C.c_int32))
+
+    def output(self, i: int) -> bytes:
+        b = self.blocks[i]
+        return self.dst[b.out_off:b.out_off + b.out_len].tobytes()
+
+    def outputs(self) -> bytes:
+        return b"".join(self.output(i) for i in range(self.n))
+
+
+def inflate_host(payloads, out_lens, **layout):
+    """ccsx_inflate_blocks_host: the decoder of k_inflate on the calling thread, no device.  Returns (the outputs concatenated, status array, the call)"""
+    call = InflateCall(payloads, out_lens, **layout)
+    if lib().ccsx_inflate_blocks_host(*call.args()) != 0:
+        raise RuntimeError("ccsx_inflate_blocks_host failed: " + lib().ccsx_last_error().decode())
+    return call.outputs(), call.status[:call.n].copy(), call
+
+
+class Inflater:
+    """One BGZF inflater bound to one GPU (ccsx_inflater_create): its own stream and buffers, nothing shared with a Handle.  Not thread-safe."""
+
+    def __init__(self, device: int = 0, max_in_bytes: int = 1 << 21, max_out_bytes: int = 1 << 23, max_blocks: int = 256):
+        self._L = lib()
+        self._f = C.c_void_p()
+        self.max_in_bytes, self.max_out_bytes, self.max_blocks = max_in_bytes, max_out_bytes, max_blocks
+        if self._L.ccsx_inflater_create(device, max_in_bytes, max_out_bytes, max_blocks, C.byref(self._f)) != 0:
+            raise RuntimeError("ccsx_inflater_create failed: " + self._L.ccsx_last_error().decode())
+        self._calls = {}
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
+
+    def submit(self, call: InflateCall) -> int:
+        t = C.c_int64()
+        self._check(self._L.ccsx_inflate_submit(self._f, *call.args(), C.byref(t)), "ccsx_inflate_submit")
+        self._calls[t.value] = call      # the call's arrays stay alive until the ticket is waited for
+        return t.value
+
+    def wait(self, ticket: int) -> InflateCall:
+        self._check(self._L.ccsx_inflate_wait(self._f, ticket), "ccsx_inflate_wait")
+        return self._calls.pop(ticket)
+
+    def run(self, call: InflateCall) -> InflateCall:
+        self._check(self._L.ccsx_inflate_blocks(self._f, *call.args()), "ccsx_inflate_blocks")
+        return call
+
+    def inflate(self, blocks, out_lens):
+        """blocks: raw DEFLATE payloads; out_lens: the bytes each inflates to.  Returns (the outputs concatenated, status array); the bytes of a block whose
+        status is not OK are unspecified"""
+        call = self.run(InflateCall(blocks, out_lens))
+        return call.outputs(), call.status[:call.n].copy()
+
+    def close(self):
+        if self._f:
+            self._L.ccsx_inflater_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

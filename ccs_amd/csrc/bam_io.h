@@ -173,6 +173,13 @@ public:
         if (map_) munmap((void *)map_, size_);
         if (fd_ >= 0) ::close(fd_);
     }
+    // Another back end for the inflate step of a slab (ccs --gpu-inflate).  The slab job hands it the slab's compressed bytes and, per non-empty block, where the
+    // raw DEFLATE payload lies in them and where its bytes go in the slab's buffer (a Span is laid out like ccsx_deflate_block); it fills one status per span
+    // (0 = inflated) and returns true, or returns false to decline the slab (beyond its capacities): the job then inflates on the host as without it.  It throws
+    // on an error of its own.  The CRC check, the error texts and everything behind the slab are the host path's.  Set it before the first read.
+    struct Span { int64_t in_off; int32_t in_len, out_len; int64_t out_off; };
+    typedef std::function<bool(const uint8_t *src, size_t src_len, const std::vector<Span> &spans, uint8_t *dst, size_t dst_len, std::vector<int32_t> &status)> InflateBackend;
+    void set_inflate_backend(InflateBackend f) { backend_ = std::move(f); }
     // read exactly n bytes; returns false on clean EOF at a record boundary (n bytes not available)
     bool read(void *dst, size_t n)
     {
@@ -230,10 +237,39 @@ private:
                 foff_ += bsize; comp += bsize;
             }
             const uint8_t *map = map_;
-            pending_.push_back(pool_.submit([map, blks, raw]() -> Slab {
+            const InflateBackend backend = backend_;
+            pending_.push_back(pool_.submit([map, blks, raw, backend]() -> Slab {
                 Slab out = std::make_shared<std::vector<uint8_t>>(raw);
                 size_t at = 0;
                 const LibDeflate &ld = LibDeflate::get();
+                if (backend && !blks.empty()) {
+                    std::vector<Span> spans;
+                    std::vector<const uint8_t *> crc_at;
+                    bool fits = true;
+                    for (const Blk &b : blks) {
+                        const uint8_t *h = map + b.off;
+                        const size_t xlen = h[10] | (h[11] << 8), off = 12 + xlen;
+                        const uint8_t *t = h + b.size - 4;
+                        const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
+                        if (isize == 0) continue;
+                        if (isize > 65536) { fits = false; break; }          // (not BGZF: the host's decoder takes blocks of any size)
+                        if (at + isize > out->size()) throw std::runtime_error("BGZF block sizes are inconsistent");
+                        spans.push_back({(int64_t)(b.off - blks[0].off + off), (int32_t)(b.size - off - 8), (int32_t)isize, (int64_t)at});
+                        crc_at.push_back(h + b.size - 8);
+                        at += isize;
+                    }
+                    std::vector<int32_t> status(spans.size(), 0);
+                    if (fits && backend(map + blks[0].off, blks.back().off + blks.back().size - blks[0].off, spans, out->data(), out->size(), status)) {
+                        for (size_t k = 0; k < spans.size(); ++k) {           // block by block, as the host path reports: does not inflate, else its CRC
+                            if (status[k] != 0) throw std::runtime_error("BGZF block does not inflate");
+                            const uint8_t *c = crc_at[k];
+                            if (ld.crc(out->data() + spans[k].out_off, (size_t)spans[k].out_len) != ((uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24)))
+                                throw std::runtime_error("BGZF block fails its CRC32");
+                        }
+                        return out;
+                    }
+                    at = 0;
+                }
                 if (ld.ok) {                                    // whole-buffer inflate of every block of the slab
                     thread_local struct Dec { void *d = nullptr; ~Dec() { if (d) LibDeflate::get().free_decompressor(d); } } td;
                     if (!td.d) td.d = ld.alloc_decompressor();
@@ -288,6 +324,7 @@ private:
         return true;
     }
     ThreadPool &pool_;
+    InflateBackend backend_;
     int depth_;
     int fd_ = -1;
     const uint8_t *map_ = nullptr;

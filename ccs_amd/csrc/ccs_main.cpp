@@ -61,6 +61,7 @@ struct Options {
     bool all_gpus = false;
     std::string write_synth;      // "N,P,L[,seed]" -> write a synthetic subreads.bam to `out`
     bool dump = false;            // print one line per ZMW after the step-1 filters, no GPU
+    bool gpu_inflate = false;     // --gpu-inflate: the BGZF blocks of IN are inflated by k_inflate (experimental)
     bool host_only = false;       // reader -> filters -> packing into staging, no engine and no output: what the host side alone sustains
     bool by_strand = false;       // --by-strand: one consensus per strand (docs/faq/mode-by-strand.md:8-23)
     bool no_partial = false;      // --no-partial-passes: drop the subreads that are not flanked by adapters on both sides (as round 2 did)
@@ -229,6 +230,8 @@ void usage()
                  "      --log-file F          write log lines to F instead of stderr\n"
                  "      --refresh-rate S      seconds between progress lines at --log-level INFO [5]\n"
                  "      --max-qv Q            largest per-base QV reported; rq follows [50 = this build's calibrated cap; 93 = the reference's range]\n"
+                 "      --gpu-inflate         inflate the BGZF blocks of IN on the GPU (k_inflate) instead of on the host threads; the CRC32 check, every\n"
+                 "                            error and every output byte stay as they are [off; experimental]\n"
                  "  test helpers (not in the reference):\n"
                  "      --write-synthetic N,P,L[,seed]  write a synthetic subreads.bam to OUT (no IN)\n"
                  "      --dump-zmws                     list ZMWs after the step-1 filters (no GPU, no OUT)\n"
@@ -329,6 +332,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--write-synthetic") o.write_synth = need(a.c_str());
         else if (a == "--dump-zmws") o.dump = true;
         else if (a == "--host-only") o.host_only = true;
+        else if (a == "--gpu-inflate") o.gpu_inflate = true;
         else if (a == "--by-strand") o.by_strand = true;
         else if (a == "--no-partial-passes") o.no_partial = true;
         else if (a == "--qv-binning") o.qv_binning = true;
@@ -800,6 +804,45 @@ void write_hifi_summary(const Options &o, const Report &r)
     std::fclose(f);
 }
 
+// --gpu-inflate: the inflaters the reader's slab jobs share.  A job takes one (waits when all are busy: that pool thread then serves neither the record decode nor
+// the output's deflate, which share the pool), inflates its slab with one synchronous call and hands it back.  COUNT = 4: a slab is one short kernel between two
+// copies of a few MB, so four in flight keep the copy engines and the kernel overlapped.  The reader's look-ahead is what it is without the flag (2 * threads + 4
+// slabs); it was not tuned for it.  A slab is ~1 MB of blocks and inflates to ~2.6 MB on subread BAMs (ratio 2 - 4 for BAM in general): MAX_OUT = 6 MB covers a
+// ratio of 5.7; a slab beyond an inflater's capacities is declined and inflated on the host.  Page-locked memory: 4 inflaters x 2 call slots x 7 MB = 57 MB.
+struct GpuInflaters {
+    static constexpr int COUNT = 4;
+    static constexpr int64_t MAX_IN = (1 << 20) + (1 << 16) + 64, MAX_OUT = 6 << 20;
+    static constexpr int32_t MAX_BLOCKS = 4096;
+    static_assert(sizeof(BgzfReader::Span) == sizeof(ccsx_deflate_block) && offsetof(BgzfReader::Span, out_off) == offsetof(ccsx_deflate_block, out_off) &&
+                  offsetof(BgzfReader::Span, in_len) == offsetof(ccsx_deflate_block, in_len) && offsetof(BgzfReader::Span, out_len) == offsetof(ccsx_deflate_block, out_len),
+                  "BgzfReader::Span is ccsx_deflate_block");
+    std::vector<ccsx_inflater> all, free_;
+    std::mutex m;
+    std::condition_variable cv;
+    ~GpuInflaters() { for (ccsx_inflater f : all) ccsx_inflater_destroy(f); }
+    bool create(int device)
+    {
+        for (int i = 0; i < COUNT; ++i) {
+            ccsx_inflater f = nullptr;
+            if (ccsx_inflater_create(device, MAX_IN, MAX_OUT, MAX_BLOCKS, &f)) return false;
+            all.push_back(f); free_.push_back(f);
+        }
+        return true;
+    }
+    bool inflate(const uint8_t *src, size_t src_len, const std::vector<BgzfReader::Span> &spans, uint8_t *dst, size_t dst_len, std::vector<int32_t> &status)
+    {
+        if ((int64_t)src_len > MAX_IN || (int64_t)dst_len > MAX_OUT || spans.size() > (size_t)MAX_BLOCKS) return false;
+        ccsx_inflater f;
+        { std::unique_lock<std::mutex> l(m); cv.wait(l, [this] { return !free_.empty(); }); f = free_.back(); free_.pop_back(); }
+        const int rc = ccsx_inflate_blocks(f, src, (int64_t)src_len, reinterpret_cast<const ccsx_deflate_block *>(spans.data()), (int32_t)spans.size(), dst, (int64_t)dst_len, status.data());
+        const std::string err = rc ? ccsx_last_error() : "";
+        { std::lock_guard<std::mutex> l(m); free_.push_back(f); }
+        cv.notify_one();
+        if (rc) throw std::runtime_error("--gpu-inflate: " + err);
+        return true;
+    }
+};
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -816,7 +859,21 @@ int main(int argc, char **argv)
         ThreadPool pool(nthreads);
         if (!opt.write_synth.empty()) return write_synthetic(opt, pool);
 
+        // ---- --gpu-inflate: a free list of inflaters (declared before the reader, whose slab jobs use them)
+        GpuInflaters gpu_inflaters;
         BgzfReader in(opt.in, pool);
+        if (opt.gpu_inflate) {
+            if ((opt.host_only || opt.dump) && ccsx_device_count() <= 0) {
+                if (opt.log_level >= 2) std::fprintf(stderr, "ccs: --gpu-inflate ignored: no engine runs (--host-only, --dump-zmws) and no device is present\n");
+            } else {
+                if (ccsx_device_count() <= 0) { std::fprintf(stderr, "ccs: no gfx950 GPU available (this build has no CPU consensus path)\n"); return 1; }
+                const int dev = opt.gpus.empty() ? 0 : opt.gpus[0];
+                if (!gpu_inflaters.create(dev)) { std::fprintf(stderr, "ccs: %s\n", ccsx_last_error()); return 1; }
+                if (opt.log_level >= 2) std::fprintf(stderr, "ccs: --gpu-inflate: %d inflaters on device %d\n", GpuInflaters::COUNT, dev);
+                in.set_inflate_backend([&gpu_inflaters](const uint8_t *src, size_t src_len, const std::vector<BgzfReader::Span> &spans, uint8_t *dst, size_t dst_len,
+                                                        std::vector<int32_t> &status) { return gpu_inflaters.inflate(src, src_len, spans, dst, dst_len, status); });
+            }
+        }
         BamHeader hdr; read_header(in, hdr);
 
         // ---- model parameters: --model-file, else by the chemistry triple of the header (docs/faq/chemistry.md:27-56);
@@ -1138,6 +1195,8 @@ int main(int argc, char **argv)
         }
 
         // ---- GPU workers: one per device; up to three batches in flight through the asynchronous boundary
+        struct { long long tickets = 0, zmws = 0; double draft = 0, polish = 0, queue = 0, total = 0, first = 0, last = 0; } eng;   // ticket timings, --log-level INFO
+        std::mutex eng_m;
         std::vector<std::thread> workers;
         for (size_t wd = 0; wd < handles.size(); ++wd) workers.emplace_back([&, wd] {
             ccsx_handle h = handles[wd];
@@ -1150,7 +1209,17 @@ int main(int argc, char **argv)
                 auto fr = std::move(inflight.front()); inflight.pop_front();
                 std::shared_ptr<Batch> &b = fr.second;
                 if (ccsx_wait(h, fr.first)) fail(std::string("consensus engine: ") + ccsx_last_error());
-                else b->have_results = true;
+                else {
+                    b->have_results = true;
+                    ccsx_timings tm;
+                    if (opt.log_level >= 2 && ccsx_ticket_timings(h, fr.first, &tm) == 0) {       // the engine's own device times of this ticket (HIP events)
+                        std::lock_guard<std::mutex> l(eng_m);
+                        eng.tickets += 1; eng.zmws += b->n;
+                        eng.draft += tm.draft_ms + tm.align_ms; eng.polish += tm.polish_ms; eng.queue += tm.queue_ms; eng.total += tm.total_ms;
+                        if (eng.tickets == 1 || tm.start_ms < eng.first) eng.first = tm.start_ms;
+                        if (eng.tickets == 1 || tm.end_ms > eng.last) eng.last = tm.end_ms;
+                    }
+                }
                 in_pool.put(std::move(b->in_arena));                // inputs are on the device (and consumed): the staging is free again
                 b->bases = b->pw = b->ipd = nullptr;
                 us_engine += us_since(t0);
@@ -1410,6 +1479,12 @@ int main(int argc, char **argv)
         if (opt.log_level >= 2)
             std::fprintf(stderr, "ccs: GPU workers (sum over %zu): waiting for input %.2f s, packing (pack threads) %.2f s, submit + wait %.2f s\n", handles.size(),
                          us_wait.load() * 1e-6, us_pack.load() * 1e-6, us_engine.load() * 1e-6);
+        if (opt.log_level >= 2 && eng.tickets > 0 && handles.size() == 1) {
+            const double k = 1000.0 / (double)std::max<long long>(eng.zmws, 1);
+            std::fprintf(stderr, "ccs: engine (ticket timings, %lld tickets, %lld ZMWs): first kernel to last %.1f ms = %.2f ms per 1000 ZMWs; per 1000 ZMWs on the device: "
+                                 "draft + align %.2f ms, polish %.2f ms, between the stages %.2f ms, ticket start to end %.2f ms\n",
+                         eng.tickets, eng.zmws, eng.last - eng.first, (eng.last - eng.first) * k, eng.draft * k, eng.polish * k, eng.queue * k, eng.total * k);
+        }
         if (opt.log_level >= 1)
             std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",

@@ -32,7 +32,7 @@ const char *ccsx_last_error(void) { return g_last_error.c_str(); }
 const char *ccsx_runtime_switches(void)
 {
     static const char *names[] = {"CCSX_STAGE_PRIO", "CCSX_POA_SPLIT", "CCSX_SERIAL_STAGES", "CCSX_A16_ONE_REGION", "CCSX_ALIGN16_MAX_SLOTS", "CCSX_TB_ASIDE",
-                                  "CCSX_POLISH_MAX_BLOCKS", "CCSX_EPOCH_REBASE_MS", "CCSX_TRACE", "CCSX_NUMA"};
+                                  "CCSX_POLISH_MAX_BLOCKS", "CCSX_EPOCH_REBASE_MS", "CCSX_TRACE", "CCSX_NUMA", "CCSX_INFLATE_PRIO"};
     static thread_local std::string out;
     out.clear();
     for (const char *n : names)

@@ -528,6 +528,50 @@ int         ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_resu
 int         ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
                                 const ccsx_adapter_request *adapters, const ccsx_control_request *control, ccsx_ticket *ticket);
 
+/* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
+ * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
+ * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one
+ * inflater per caller thread.  Two calls may be in flight (ccsx_inflate_submit / ccsx_inflate_wait); tickets complete in order.
+ *   blocks[i]   in_off / in_len: the raw DEFLATE payload in src (the caller strips BGZF's header — 18 bytes as htslib writes it — and the 8-byte trailer);
+ *               out_off / out_len: where its bytes go in dst; out_len (the trailer's ISIZE) <= CCSX_INFLATE_MAX_OUT.
+ *   status[i]   enum ccsx_inflate_status.  A corrupt block is never an error of the call (as a failed ZMW is not, elsewhere in this ABI): the other blocks of the
+ *               call are inflated.  The bytes of dst[out_off, out_off + out_len) of a block whose status is not OK are unspecified; no byte of dst outside the
+ *               blocks' output ranges is written.  CRC32 stays with the caller.
+ * Argument errors (< 0, ccsx_last_error) fail the call before anything is enqueued: a null argument, a block outside src or dst, overlapping output ranges,
+ * out_len > CCSX_INFLATE_MAX_OUT, src_len / dst_len / n_blocks beyond the inflater's capacities, two tickets already in flight.
+ * src and dst may be any host memory: the library copies through its own page-locked staging (a page-locked src / dst makes that host copy faster, nothing else).
+ * src, blocks, dst and status must stay valid until the ticket is waited for.
+ * The stream's priority is the device's lowest by default (CCSX_INFLATE_PRIO=high|low|none overrides; DESIGN.md §7 has the measurement).
+ * ccsx_inflate_blocks_host runs the same decoder (inflate_core.h) on the calling thread, without a device: the reference of the tests.                        */
+#define CCSX_INFLATE_MAX_OUT 65536
+#ifndef CCSX_INFLATE_STATUS_DEFINED
+#define CCSX_INFLATE_STATUS_DEFINED
+enum ccsx_inflate_status {
+    CCSX_INFLATE_OK                = 0,
+    CCSX_INFLATE_TRUNCATED_INPUT   = 1,  /* the stream needs bits beyond in_len                                              */
+    CCSX_INFLATE_BAD_BLOCK_TYPE    = 2,  /* BTYPE 3                                                                          */
+    CCSX_INFLATE_BAD_STORED_LENGTH = 3,  /* LEN != ~NLEN                                                                     */
+    CCSX_INFLATE_BAD_CODE_LENGTHS  = 4,  /* over- or under-subscribed code (except zlib's one-code distance tree), a repeat
+                                            without a previous length or past the end, more than 286 / 30 codes, no end-of-block code */
+    CCSX_INFLATE_BAD_SYMBOL        = 5,  /* a code that stands for no symbol (litlen 286/287, distance 30/31, unassigned)     */
+    CCSX_INFLATE_BAD_DISTANCE      = 6,  /* a match reaches before the start of this stream's output                         */
+    CCSX_INFLATE_OUTPUT_OVERRUN    = 7,  /* the stream holds more than out_len bytes                                          */
+    CCSX_INFLATE_OUTPUT_SHORT      = 8   /* the final block ended before out_len bytes                                        */
+};
+#endif
+typedef struct ccsx_inflater_s *ccsx_inflater;
+typedef struct ccsx_deflate_block { int64_t in_off; int32_t in_len; int32_t out_len; int64_t out_off; } ccsx_deflate_block;
+int         ccsx_inflate_rule_version(void);
+int         ccsx_inflater_create(int device, int64_t max_in_bytes, int64_t max_out_bytes, int32_t max_blocks, ccsx_inflater *out);
+int         ccsx_inflater_destroy(ccsx_inflater f);
+int         ccsx_inflate_blocks(ccsx_inflater f, const uint8_t *src, int64_t src_len, const ccsx_deflate_block *blocks, int32_t n_blocks,
+                                uint8_t *dst, int64_t dst_len, int32_t *status);                        /* synchronous: submit + wait */
+int         ccsx_inflate_submit(ccsx_inflater f, const uint8_t *src, int64_t src_len, const ccsx_deflate_block *blocks, int32_t n_blocks,
+                                uint8_t *dst, int64_t dst_len, int32_t *status, ccsx_ticket *ticket);
+int         ccsx_inflate_wait(ccsx_inflater f, ccsx_ticket ticket);
+int         ccsx_inflate_blocks_host(const uint8_t *src, int64_t src_len, const ccsx_deflate_block *blocks, int32_t n_blocks,
+                                     uint8_t *dst, int64_t dst_len, int32_t *status);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
