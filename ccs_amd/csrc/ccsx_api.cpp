@@ -139,8 +139,8 @@ struct Slot {
     PinVec<int64_t> seq_off, ent_off, base_off;
     PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
     KParams P;
-    hipEvent_t ev[7] = {}, ev_up = nullptr, ev_done = nullptr;   // ev[0..5]: stage boundaries, ev[6]: start of the polish stage
-    hipEvent_t ev_aux[7] = {};                                   // second stream: fork / first DP done / join of the POA stage; k_align16 launch done x 2, its trace-back done x 2
+    hipEvent_t ev[CCSX_EV_COUNT] = {}, ev_up = nullptr, ev_done = nullptr;   // ev: the stage events (ccsx_stage_event)
+    hipEvent_t ev_aux[CCSX_ORD_COUNT] = {};                                  // the ordering events of the second stream (ccsx_order_event)
     bool staged = false, ran = false, inflight = false;
     bool tm_ok = false; ccsx_timings tm{};   // the slot's timings as taken by retire() (valid until the slot is staged again)
     ccsx_results *res = nullptr;      // destination of an in-flight submit (cleared by retire(): the caller's struct is not touched again)
@@ -208,18 +208,18 @@ static void finish_outputs(const Slot &S, ccsx_results *res, ccsx_drafts *d)
 // fallback round (POA included), polish_ms from the polish stage's own start event (it may have queued behind the previous batch)
 static int slot_timings(ccsx_handle h, Slot &S, ccsx_timings *t)
 {
-    HIPTRY(hipEventSynchronize(S.ev[5]));
+    HIPTRY(hipEventSynchronize(S.ev[CCSX_EV_END]));
     std::memset(t, 0, sizeof(*t));
-    HIPTRY(hipEventElapsedTime(&t->setup_ms, S.ev[0], S.ev[1]));
-    HIPTRY(hipEventElapsedTime(&t->draft_ms, S.ev[1], S.ev[2]));
-    HIPTRY(hipEventElapsedTime(&t->align_ms, S.ev[2], S.ev[3]));
-    HIPTRY(hipEventElapsedTime(&t->queue_ms, S.ev[3], S.ev[6]));
-    HIPTRY(hipEventElapsedTime(&t->polish_ms, S.ev[6], S.ev[4]));
-    HIPTRY(hipEventElapsedTime(&t->stitch_ms, S.ev[4], S.ev[5]));
-    HIPTRY(hipEventElapsedTime(&t->total_ms, S.ev[0], S.ev[5]));
+    HIPTRY(hipEventElapsedTime(&t->setup_ms, S.ev[CCSX_EV_START], S.ev[CCSX_EV_TABLES_DONE]));
+    HIPTRY(hipEventElapsedTime(&t->draft_ms, S.ev[CCSX_EV_TABLES_DONE], S.ev[CCSX_EV_DRAFT_DONE]));
+    HIPTRY(hipEventElapsedTime(&t->align_ms, S.ev[CCSX_EV_DRAFT_DONE], S.ev[CCSX_EV_DRAFT_STAGE_DONE]));
+    HIPTRY(hipEventElapsedTime(&t->queue_ms, S.ev[CCSX_EV_DRAFT_STAGE_DONE], S.ev[CCSX_EV_POLISH_START]));
+    HIPTRY(hipEventElapsedTime(&t->polish_ms, S.ev[CCSX_EV_POLISH_START], S.ev[CCSX_EV_POLISH_DONE]));
+    HIPTRY(hipEventElapsedTime(&t->stitch_ms, S.ev[CCSX_EV_POLISH_DONE], S.ev[CCSX_EV_END]));
+    HIPTRY(hipEventElapsedTime(&t->total_ms, S.ev[CCSX_EV_START], S.ev[CCSX_EV_END]));
     float a = 0.0f, b = 0.0f;
-    HIPTRY(hipEventElapsedTime(&a, h->ev_epoch, S.ev[0]));
-    HIPTRY(hipEventElapsedTime(&b, h->ev_epoch, S.ev[5]));
+    HIPTRY(hipEventElapsedTime(&a, h->ev_epoch, S.ev[CCSX_EV_START]));
+    HIPTRY(hipEventElapsedTime(&b, h->ev_epoch, S.ev[CCSX_EV_END]));
     t->start_ms = h->epoch_ms + (double)a; t->end_ms = h->epoch_ms + (double)b;
     h->age_ms = b;                    // (the origin moves forward at the next submit that finds the handle idle: rebase_epoch)
     return 0;
@@ -675,7 +675,7 @@ static int launch(ccsx_handle h, Slot &S)
     }
     bind_scratch(h, P);
     if (!h->d_poa.p || !h->d_align.p) { ccsx_set_error("kernel launch refused: the POA / alignment scratch is not allocated (an earlier allocation failed)"); return -2; }
-    const char *failed = ccsx_launch_all(S.P, h->s_draft, h->s_comp, S.ev, S.mode, h->s_aux, h->s_aux ? S.ev_aux : nullptr);
+    const char *failed = ccsx_launch_all(S.P, {h->s_draft, h->s_comp, h->s_aux, S.ev, h->s_aux ? S.ev_aux : nullptr}, S.mode);
     if (failed) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
     S.ran = true;
     return 0;
@@ -1093,8 +1093,8 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     HIPTRY_F(hipEventRecord(S.ev_up, h->s_in));
     HIPTRY_F(hipStreamWaitEvent(h->s_draft, S.ev_up, 0));
     if ((rc = launch(h, S))) return fail(rc);
-    // ev[5] (end of the last kernel) doubles as the "results ready" event of the download stream
-    HIPTRY_F(hipStreamWaitEvent(h->s_out, S.ev[5], 0));
+    // CCSX_EV_END (end of the last kernel) doubles as the "results ready" event of the download stream
+    HIPTRY_F(hipStreamWaitEvent(h->s_out, S.ev[CCSX_EV_END], 0));
     if (mode == CCSX_RUN_DRAFT) {
         const int n = S.P.n_zmw;
         const KParams &P = S.P;

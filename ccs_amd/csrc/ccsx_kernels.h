@@ -182,8 +182,37 @@ static inline __host__ __device__ uint32_t ccsx_fmix32(uint32_t h) { h ^= h >> 1
 // alignment cascade + the heteroduplex finder on caller-supplied drafts (ccsx_hd_batch)
 enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2, CCSX_RUN_HD = 3 };
 
-const char *ccsx_launch_all(const KParams &P, hipStream_t st_draft, hipStream_t st_polish, hipEvent_t *ev /* [7] */, int mode = CCSX_RUN_FUSED,
-                            hipStream_t st_aux = nullptr, hipEvent_t *ev_aux /* [7] */ = nullptr);   // NULL, or the name of the launch that failed; st_aux: second stream of the POA stage (half-batches)
+// The stage events of a batch (Slot::ev, timing enabled), in the values they have always had — in time order POLISH_START lies between DRAFT_STAGE_DONE and
+// POLISH_DONE.  ccsx_launch_all records each of them exactly once on every path, in time order, so that ccsx_timings may read all seven after any run.
+enum ccsx_stage_event {
+    CCSX_EV_START = 0,             // before the batch's first call; setup_ms runs from here
+    CCSX_EV_TABLES_DONE = 1,       // after k_setup; draft_ms runs from here
+    CCSX_EV_DRAFT_DONE = 2,        // after the first POA round (and its k_sdust); align_ms — cascade, accounting, the whole fallback rounds — runs from here
+    CCSX_EV_DRAFT_STAGE_DONE = 3,  // after the draft stream's last kernel: the polish stream waits for it; queue_ms runs from here
+    CCSX_EV_POLISH_DONE = 4,       // after polish and kinetics / pileup; stitch_ms runs from here
+    CCSX_EV_END = 5,               // after the last kernel: total_ms ends here, and the download stream waits for it ("results ready")
+    CCSX_EV_POLISH_START = 6,      // on the polish stream once DRAFT_STAGE_DONE has passed (it may have queued behind the previous batch); polish_ms runs from here
+    CCSX_EV_COUNT
+};
+// The ordering events of a batch (Slot::ev_aux, no timing): what the draft stream and the second stream tell each other inside one ccsx_launch_all.
+enum ccsx_order_event {
+    CCSX_ORD_POA_FORK = 0,         // draft stream -> second stream: the second half-batch of the POA may start
+    CCSX_ORD_FIRST_DP_DONE = 1,    // first half's first k_poa_dp done: the second half stays one DP behind
+    CCSX_ORD_POA_JOIN = 2,         // second stream -> draft stream: the second half's draft is made
+    CCSX_ORD_ALIGN16_DONE_0 = 3,   // k_align16 launch c done (c even): its trace-back may start on the second stream
+    CCSX_ORD_ALIGN16_DONE_1 = 4,   // ... (c odd)
+    CCSX_ORD_TB_DONE_0 = 5,        // the trace-back of launch c done (c even): the launch's scratch region is free, its entry rows are written
+    CCSX_ORD_TB_DONE_1 = 6,        // ... (c odd)
+    CCSX_ORD_COUNT
+};
+
+// where ccsx_launch_all enqueues: the draft stage on `draft`, the polish stage on `polish` (the same stream: serial stages), half of a large POA round and the
+// trace-backs of k_align16 on `aux` (NULL, or ev_aux NULL: everything on `draft`).  ev: [CCSX_EV_COUNT], or NULL with one stream; ev_aux: [CCSX_ORD_COUNT]
+struct ccsx_launch_queues {
+    hipStream_t draft, polish, aux;
+    hipEvent_t *ev, *ev_aux;
+};
+const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode);   // NULL, or the name of the launch that failed
 int ccsx_kernel_is_experiment();         // built with -DCCSX_EXPERIMENT (timing studies: wrong results)
 const char *ccsx_kernel_build_flags();   // "" for a product build; the experiment switches this translation unit was compiled with otherwise
 int ccsx_polish_lds(int max_reads, int *obs_bytes, int *gb_floats);

@@ -3840,14 +3840,6 @@ __global__ __launch_bounds__(64) void k_hd_verdict(KParams P)
 
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from ccsx_api.cpp, which is plain C++)
-static void trace_sync(hipStream_t st, const char *what)
-{
-    static const bool on = getenv("CCSX_TRACE") != nullptr;     // debugging aid: serialise and name every launch
-    if (!on) return;
-    hipError_t e = hipStreamSynchronize(st);
-    fprintf(stderr, "[ccsx] %s done: %s\n", what, hipGetErrorString(e));
-}
-
 // dynamic LDS of k_polish: [reads][68] observations (a byte each) for the largest ZMW of the batch (at most one group of PW_MAXREADS), the rest of the workgroup's
 // budget holds gamma/beta of one chunk of reads
 int ccsx_polish_lds(int max_reads, int *obs_bytes, int *gb_floats)
@@ -4453,213 +4445,277 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
     }
 }
 
-// every launch status is captured: returns NULL, or the name of the first launch that failed (ccsx_api.cpp reports it)
-#define LAUNCH_CHECK(name) do { if (hipGetLastError() != hipSuccess && !failed) failed = name; } while (0)
-#define CALL_CHECK(fn, ...) do { if (fn(__VA_ARGS__) != hipSuccess && !failed) failed = #fn; } while (0)   // (a stream / event call)
-const char *ccsx_launch_all(const KParams &P, hipStream_t st, hipStream_t st_polish, hipEvent_t *ev /* [7] or NULL */, int mode, hipStream_t st_aux, hipEvent_t *ev_aux /* [7] or NULL */)
-{
-    // Two-stage queue of docs/img/ccs-impl.png ("Draft Stage" -> queue -> "Polish Stage"): the draft stage (tables, POA, alignment
-    // cascade, accounting) is enqueued on `st`, the polish stage (polish, kinetics, stitch) on `st_polish`, which waits for the
-    // draft stage's last kernel through ev[3].  With two different streams the draft stage of batch k+1 runs UNDER the polish
-    // stage of batch k (the register-only one-wave POA and the LDS-bound polish workgroups share the SIMDs); the shared POA /
-    // alignment scratch is touched by the draft stage only, so `st` alone orders its users.  st_polish == st: serial stages.
-    const char *failed = nullptr;
-    if (ev) CALL_CHECK(hipEventRecord, ev[0], st);
-    CALL_CHECK(hipMemsetAsync, P.ticket_poa, 0, 256, st);   // debug / phase-profile words (CCSX_DEBUG_CHECKS, CCSX_PROFILE_PHASES builds)
-    CALL_CHECK(hipMemsetAsync, P.avalid, 0, (size_t)(P.n_reads > 0 ? P.n_reads : 1), st);   // passes beyond top_passes are never visited by a kernel
-    if (P.tflag) { CALL_CHECK(hipMemsetAsync, P.tflag, 0, (size_t)P.n_zmw * 4, st); CALL_CHECK(hipMemsetAsync, P.tlen, 0, (size_t)P.n_zmw * 4, st); }   // all undecided
+// ------------------------------------------------------------------------------------------------
+// The launch schedule of a batch: ccsx_launch_all at the end lists its stages, Schedule holds them.
+namespace {
+
+// the schedule's environment switches (ccsx_host.cpp lists them for ccsx_runtime_switches(); results never depend on them)
+struct LaunchSwitches {
+    bool trace;             // CCSX_TRACE: debugging aid: serialise and name every launch
+    bool tb_aside;          // CCSX_TB_ASIDE=0: the trace-backs of k_align16 stay on the draft stream (A/B switch)
+    long long max_blocks;   // CCSX_POLISH_MAX_BLOCKS: a test hook that forces the polish stage's per-slot grids into small pieces.  A multiple of 8 (the kernels
+                            // take their windows in XCD-contiguous order), ignored unless > 8
+    LaunchSwitches()
     {
-        int n = P.n_zmw * CCSX_NCTX;
-        hipLaunchKernelGGL(k_setup, dim3((n + 255) / 256), dim3(256), 0, st, P);
-        LAUNCH_CHECK("k_setup");
+        const char *aside = getenv("CCSX_TB_ASIDE"), *blocks = getenv("CCSX_POLISH_MAX_BLOCKS");
+        const long long v = blocks ? atoll(blocks) : 0;
+        trace = getenv("CCSX_TRACE") != nullptr;
+        tb_aside = !(aside && aside[0] == '0');
+        max_blocks = v > 8 ? (v & ~7ll) : (1ll << 24) - 256;
     }
-    trace_sync(st, "k_setup");
-    if (ev) CALL_CHECK(hipEventRecord, ev[1], st);
-    const size_t lds_read = (((size_t)P.maxL_max + 15) / 16) * 4 + 64 + 4 * (CCSX_MAX_PASSES + 1);   // the packed read; k_poa_init: the lengths of up to 255 passes
-    // pass 0 = the draft; pass 1 = the fallback draft of the ZMWs k_post marked (their waves run, all others leave at once:
-    // the second round of launches costs microseconds unless something failed)
-    // CCSX_RUN_POLISH (the polish seam): the drafts are the caller's — k_draft_in instead of the generators, one alignment round whose outcome is final
-    // (P.opts.no_fallback_draft is set for such a run)
-    const bool caller_drafts = mode == CCSX_RUN_POLISH || mode == CCSX_RUN_HD;   // (ccsx_hd_batch: the polish seam's first half on the caller's drafts)
-    if (caller_drafts) {
-        hipLaunchKernelGGL(k_draft_in, dim3(P.n_zmw), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_draft_in");
+};
+
+// [0, total) in order, in pieces of at most `max`: fn(first, count)
+template <typename T, typename F> inline void for_each_piece(T total, T max, F fn)
+{
+    for (T first = 0; first < total; first += max) fn(first, (total - first) < max ? (total - first) : max);
+}
+
+struct Schedule {
+    const KParams &P;
+    const ccsx_launch_queues &q;
+    const LaunchSwitches &sw;
+    const hipStream_t st;         // the draft stream: everything but the polish stage and what runs beside it on q.aux
+    const bool second_stream;     // q.aux and its events are there
+    // CCSX_RUN_POLISH (the polish seam), CCSX_RUN_HD (ccsx_hd_batch: the polish seam's first half): the drafts are the caller's — k_draft_in instead of the
+    // generators, one alignment round whose outcome is final (P.opts.no_fallback_draft is set for such a run)
+    const bool caller_drafts;
+    const size_t lds_read;        // the packed read; k_poa_init: the lengths of up to 255 passes
+    const char *failed = nullptr;
+
+    Schedule(const KParams &P_, const ccsx_launch_queues &q_, int mode, const LaunchSwitches &sw_)
+        : P(P_), q(q_), sw(sw_), st(q_.draft), second_stream(q_.aux && q_.ev_aux), caller_drafts(mode == CCSX_RUN_POLISH || mode == CCSX_RUN_HD),
+          lds_read((((size_t)P_.maxL_max + 15) / 16) * 4 + 64 + 4 * (CCSX_MAX_PASSES + 1)) {}
+
+    // ---- every status is captured: `failed` is the name of the first launch or call that failed (ccsx_api.cpp reports it)
+    void check(hipError_t e, const char *name) { if (e != hipSuccess && !failed) failed = name; }
+    template <typename... KA, typename... A>
+    void launch(const char *name, void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &... args)
+    {
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+        check(hipGetLastError(), name);
     }
-    for (int pass = 0; pass < ((P.opts.no_fallback_draft || caller_drafts) ? 1 : 3); ++pass) {
+    void record(hipEvent_t e, hipStream_t s) { check(hipEventRecord(e, s), "hipEventRecord"); }
+    void wait(hipStream_t s, hipEvent_t e) { check(hipStreamWaitEvent(s, e, 0), "hipStreamWaitEvent"); }
+    void memset(void *p, size_t bytes, hipStream_t s) { check(hipMemsetAsync(p, 0, bytes, s), "hipMemsetAsync"); }
+    void trace_sync(hipStream_t s, const char *what) const
+    {
+        if (!sw.trace) return;
+        hipError_t e = hipStreamSynchronize(s);
+        fprintf(stderr, "[ccsx] %s done: %s\n", what, hipGetErrorString(e));
+    }
+
+    // ---- the stage events (ccsx_kernels.h).  Every one of them is recorded exactly once on every path through ccsx_launch_all, in the order below, so that
+    // ccsx_timings never reads an event that was not recorded or was left from an earlier batch.  A run that ends early, or has no polish stage, records the
+    // events of the stages it leaves out back to back on the draft stream (close_timing): those stages then take no time.
+    // Who records what: START and TABLES_DONE tables(); DRAFT_DONE draft_stage(), in its pass 0; DRAFT_STAGE_DONE, POLISH_START, POLISH_DONE and END
+    // polish_stage() in a full run, close_timing alone in the draft seam; in ccsx_hd_batch close_timing the first two, hd_finder(true) POLISH_DONE,
+    // ccsx_launch_all END.
+    void stage_event(ccsx_stage_event k, hipStream_t s) { if (q.ev) record(q.ev[k], s); }
+    void close_timing(ccsx_stage_event from, ccsx_stage_event to)
+    {
+        static const ccsx_stage_event in_time_order[] = {CCSX_EV_START, CCSX_EV_TABLES_DONE, CCSX_EV_DRAFT_DONE, CCSX_EV_DRAFT_STAGE_DONE,
+                                                         CCSX_EV_POLISH_START, CCSX_EV_POLISH_DONE, CCSX_EV_END};
+        bool in = false;
+        for (ccsx_stage_event k : in_time_order) {
+            in = in || k == from;
+            if (in) stage_event(k, st);
+            if (k == to) break;
+        }
+    }
+    hipEvent_t align16_done(int c) const { return q.ev_aux[CCSX_ORD_ALIGN16_DONE_0 + (c & 1)]; }   // (launch c of k_align16 uses the events and the region c & 1)
+    hipEvent_t tb_done(int c) const { return q.ev_aux[CCSX_ORD_TB_DONE_0 + (c & 1)]; }
+
+    void tables()
+    {
+        stage_event(CCSX_EV_START, st);
+        memset(P.ticket_poa, 256, st);   // debug / phase-profile words (CCSX_DEBUG_CHECKS, CCSX_PROFILE_PHASES builds)
+        memset(P.avalid, (size_t)(P.n_reads > 0 ? P.n_reads : 1), st);   // passes beyond top_passes are never visited by a kernel
+        if (P.tflag) { memset(P.tflag, (size_t)P.n_zmw * 4, st); memset(P.tlen, (size_t)P.n_zmw * 4, st); }   // all undecided
+        launch("k_setup", k_setup, dim3((P.n_zmw * CCSX_NCTX + 255) / 256), dim3(256), 0, st, P);
+        trace_sync(st, "k_setup");
+        stage_event(CCSX_EV_TABLES_DONE, st);
+    }
+
+    // one round of draft generation over the batch, in chunks of the POA scratch's slots
+    void poa_round(int pass)
+    {
         int cov = pass ? 2 * P.opts.max_poa_cov : P.opts.max_poa_cov;
         if (cov > PW_MAXREADS_SPEC) cov = PW_MAXREADS_SPEC;
         if (cov > P.max_reads) cov = P.max_reads;          // no ZMW of the batch has more passes
-        for (int z0 = 0; z0 < P.n_zmw && !caller_drafts; z0 += P.poa_slots) {
-            const int nb = (P.n_zmw - z0) < P.poa_slots ? (P.n_zmw - z0) : P.poa_slots;
+        for_each_piece(P.n_zmw, P.poa_slots, [&](int z0, int nb) {
             // the graphs [g0, g0 + ng) on stream s: initial graph, one DP (four graphs per wave) + one threading kernel per pass of the POA, heaviest path
             auto poa_range = [&](hipStream_t s, int g0, int ng, hipEvent_t after_first_dp, hipEvent_t before_first_dp) {
-                hipLaunchKernelGGL(k_poa_init, dim3(ng), dim3(64), lds_read, s, P, z0, pass, g0);
-                LAUNCH_CHECK("k_poa_init");
-                if (before_first_dp) CALL_CHECK(hipStreamWaitEvent, s, before_first_dp, 0);
+                launch("k_poa_init", k_poa_init, dim3(ng), dim3(64), lds_read, s, P, z0, pass, g0);
+                if (before_first_dp) wait(s, before_first_dp);
                 for (int rr = 1; rr < cov && pass < 2; ++rr) {
-                    hipLaunchKernelGGL(k_poa_dp, dim3((ng + 3) / 4), dim3(64), 0, s, P, z0, pass, rr, g0 / 4);
-                    LAUNCH_CHECK("k_poa_dp");
-                    if (rr == 1 && after_first_dp) CALL_CHECK(hipEventRecord, after_first_dp, s);
-                    hipLaunchKernelGGL(k_poa_thread, dim3(ng), dim3(64), lds_read, s, P, z0, pass, rr, g0);
-                    LAUNCH_CHECK("k_poa_thread");
+                    launch("k_poa_dp", k_poa_dp, dim3((ng + 3) / 4), dim3(64), 0, s, P, z0, pass, rr, g0 / 4);
+                    if (rr == 1 && after_first_dp) record(after_first_dp, s);
+                    launch("k_poa_thread", k_poa_thread, dim3(ng), dim3(64), lds_read, s, P, z0, pass, rr, g0);
                 }
-                if (pass < 2) {                            // (pass 2 = last resort: k_poa_init writes the draft itself)
-                    hipLaunchKernelGGL(k_poa_finish, dim3(ng), dim3(64), 0, s, P, z0, pass, g0);
-                    LAUNCH_CHECK("k_poa_finish");
-                }
+                if (pass < 2) launch("k_poa_finish", k_poa_finish, dim3(ng), dim3(64), 0, s, P, z0, pass, g0);   // (pass 2 = last resort: k_poa_init writes the draft itself)
             };
             // Pass 0 of a large batch runs as TWO half-batches on two streams, the second one a DP behind the first: k_poa_dp saturates the VALU and k_poa_thread
             // waits for HBM, their registers and LDS fit one SIMD together (94 + 64 VGPRs), so the threading of one half runs under the DP of the other.
-            if (st_aux && ev_aux && pass == 0 && cov > 1 && nb >= 4096) {
+            if (second_stream && pass == 0 && cov > 1 && nb >= 4096) {
                 const int ha = ((nb / 2) + 3) & ~3;
-                CALL_CHECK(hipEventRecord, ev_aux[0], st);
-                CALL_CHECK(hipStreamWaitEvent, st_aux, ev_aux[0], 0);
-                poa_range(st, 0, ha, ev_aux[1], nullptr);
-                poa_range(st_aux, ha, nb - ha, nullptr, ev_aux[1]);
-                CALL_CHECK(hipEventRecord, ev_aux[2], st_aux);
-                CALL_CHECK(hipStreamWaitEvent, st, ev_aux[2], 0);
+                record(q.ev_aux[CCSX_ORD_POA_FORK], st);
+                wait(q.aux, q.ev_aux[CCSX_ORD_POA_FORK]);
+                poa_range(st, 0, ha, q.ev_aux[CCSX_ORD_FIRST_DP_DONE], nullptr);
+                poa_range(q.aux, ha, nb - ha, nullptr, q.ev_aux[CCSX_ORD_FIRST_DP_DONE]);
+                record(q.ev_aux[CCSX_ORD_POA_JOIN], q.aux);
+                wait(st, q.ev_aux[CCSX_ORD_POA_JOIN]);
             } else poa_range(st, 0, nb, nullptr, nullptr);
-        }
-        trace_sync(st, "k_poa");
-        if (P.tflag) {                                      // tandem repeats: the ZMWs whose deciding draft this pass makes
-            hipLaunchKernelGGL(k_sdust, dim3(P.n_zmw), dim3(64), (size_t)CCSX_SDUST_TABLE_BYTES + (size_t)P.sdust_words * 4, st, P, pass);
-            LAUNCH_CHECK("k_sdust");
-        }
-        if (ev && pass == 0) CALL_CHECK(hipEventRecord, ev[2], st);
-        // alignment cascade: four passes per wave in 16-row bands, then the 64-row retry of the few that failed there
-        CALL_CHECK(hipMemsetAsync, P.align_retry, 0, 64, st);
-        bool tb_aside_out = false; int tb_launches = 0;
-        {
-            const size_t lds16 = 4 * (CH16 / 16 + 3) * sizeof(uint32_t);
-            // The trace-back of a launch runs on the second stream: beside the NEXT launch of k_align16 (a batch whose quads take several launches has two
-            // scratch regions, launch c uses region c & 1 and waits for the trace-back of launch c - 2) and, the last one, beside the 64-row retry and the split
-            // alignment — those read the retry list the 16-row kernel wrote, not the entries the trace-back writes, and their scratch lies behind the stored
-            // moves.  k_post waits for all of them.  (A trace-back is a long dependent walk of few waves: 42 % of k_align16's time on the 3-50-pass mix.)
-            static const bool aside_ok = [] { const char *e = getenv("CCSX_TB_ASIDE"); return !(e && e[0] == '0'); }();   // (A/B switch)
-            const bool aside = aside_ok && st_aux && ev_aux && pass == 0 && P.n_quads >= 4096;
-            bool tb_aside = false;
-            int c = 0;
-            for (int qb = 0; qb < P.n_quads; qb += P.align16_slots, ++c) {
-                const int nb = (P.n_quads - qb) < P.align16_slots ? (P.n_quads - qb) : P.align16_slots;
-                const int region = P.align16_regions > 1 ? (c & 1) : 0;
-                if (aside && c >= 2) CALL_CHECK(hipStreamWaitEvent, st, ev_aux[5 + (c & 1)], 0);   // the region's last reader
-                if (aside && c >= 1 && P.align16_regions <= 1) CALL_CHECK(hipStreamWaitEvent, st, ev_aux[5 + ((c - 1) & 1)], 0);   // (one region: in sequence)
-                hipLaunchKernelGGL(k_align16, dim3(nb), dim3(64), lds16, st, P, qb, pass, region);
-                LAUNCH_CHECK("k_align16");
-                hipStream_t s_tb = st;
-                if (aside) {
-                    CALL_CHECK(hipEventRecord, ev_aux[3 + (c & 1)], st);
-                    CALL_CHECK(hipStreamWaitEvent, st_aux, ev_aux[3 + (c & 1)], 0);
-                    s_tb = st_aux; tb_aside = true;
-                }
-                hipLaunchKernelGGL(k_align16_tb, dim3((4 * nb + 63) / 64), dim3(64), 0, s_tb, P, qb, nb, region);   // one lane per pass: entry rows / dirty masks from the stored moves
-                LAUNCH_CHECK("k_align16_tb");
-                if (aside) CALL_CHECK(hipEventRecord, ev_aux[5 + (c & 1)], st_aux);
-            }
-            tb_launches = c;
-            tb_aside_out = tb_aside;
-        }
-        {
-            const int g = P.align_slots < 1 ? 1 : (P.align_slots > 4096 ? 4096 : P.align_slots);
-            hipLaunchKernelGGL(k_align, dim3(g), dim3(64), lds_read, st, P, pass);
-            LAUNCH_CHECK("k_align");
-        }
+        });
+    }
+
+    // alignment cascade: four passes per wave in 16-row bands, then the 64-row retry of the few that failed there, then the split alignment
+    void align_cascade(int pass)
+    {
+        memset(P.align_retry, 64, st);
+        const size_t lds16 = 4 * (CH16 / 16 + 3) * sizeof(uint32_t);
+        // The trace-back of a launch runs on the second stream: beside the NEXT launch of k_align16 (a batch whose quads take several launches has two
+        // scratch regions, launch c uses region c & 1 and waits for the trace-back of launch c - 2) and, the last one, beside the 64-row retry and the split
+        // alignment — those read the retry list the 16-row kernel wrote, not the entries the trace-back writes, and their scratch lies behind the stored
+        // moves.  The cascade ends with the waits for all of them.  (A trace-back is a long dependent walk of few waves: 42 % of k_align16's time on the 3-50-pass mix.)
+        const bool aside = sw.tb_aside && second_stream && pass == 0 && P.n_quads >= 4096;
+        int launches = 0;
+        for_each_piece(P.n_quads, P.align16_slots, [&](int qb, int nb) {
+            const int c = launches++;
+            const int region = P.align16_regions > 1 ? (c & 1) : 0;
+            if (aside && c >= 2) wait(st, tb_done(c));                                  // the region's last reader
+            if (aside && c >= 1 && P.align16_regions <= 1) wait(st, tb_done(c - 1));   // (one region: in sequence)
+            launch("k_align16", k_align16, dim3(nb), dim3(64), lds16, st, P, qb, pass, region);
+            if (aside) { record(align16_done(c), st); wait(q.aux, align16_done(c)); }
+            launch("k_align16_tb", k_align16_tb, dim3((4 * nb + 63) / 64), dim3(64), 0, aside ? q.aux : st, P, qb, nb, region);   // one lane per pass: entry rows / dirty masks from the stored moves
+            if (aside) record(tb_done(c), q.aux);
+        });
+        launch("k_align", k_align, dim3(P.align_slots < 1 ? 1 : (P.align_slots > 4096 ? 4096 : P.align_slots)), dim3(64), lds_read, st, P, pass);
         trace_sync(st, "k_align");
-        if (P.align_slots >= 2) {                          // the split alignment uses two scratch slots per workgroup
-            const int g = P.align_slots / 2 > 2048 ? 2048 : P.align_slots / 2;
-            hipLaunchKernelGGL(k_rescue, dim3(g), dim3(64), lds_read, st, P, pass);
-            LAUNCH_CHECK("k_rescue");
+        if (P.align_slots >= 2)                            // the split alignment uses two scratch slots per workgroup
+            launch("k_rescue", k_rescue, dim3(P.align_slots / 2 > 2048 ? 2048 : P.align_slots / 2), dim3(64), lds_read, st, P, pass);
+        if (aside) for (int c = launches > 2 ? launches - 2 : 0; c < launches; ++c) wait(st, tb_done(c));   // (the trace-backs run in order on one stream: the last one per region)
+    }
+
+    // pass 0 = the draft; passes 1, 2 = the fallback drafts of the ZMWs k_post marked (their waves run, all others leave at once: a further round of launches
+    // costs microseconds unless something failed)
+    void draft_stage()
+    {
+        if (caller_drafts) launch("k_draft_in", k_draft_in, dim3(P.n_zmw), dim3(64), 0, st, P);
+        const int passes = (P.opts.no_fallback_draft || caller_drafts) ? 1 : 3;
+        for (int pass = 0; pass < passes; ++pass) {
+            if (!caller_drafts) poa_round(pass);
+            trace_sync(st, "k_poa");
+            if (P.tflag)                                    // tandem repeats: the ZMWs whose deciding draft this pass makes
+                launch("k_sdust", k_sdust, dim3(P.n_zmw), dim3(64), (size_t)CCSX_SDUST_TABLE_BYTES + (size_t)P.sdust_words * 4, st, P, pass);
+            if (pass == 0) stage_event(CCSX_EV_DRAFT_DONE, st);
+            align_cascade(pass);
+            launch("k_post", k_post, dim3((P.n_zmw + 255) / 256), dim3(256), 0, st, P, pass);
         }
-        if (tb_aside_out) for (int c = tb_launches > 2 ? tb_launches - 2 : 0; c < tb_launches; ++c)      // (the trace-backs run in order on one stream: the last one per region)
-            CALL_CHECK(hipStreamWaitEvent, st, ev_aux[5 + (c & 1)], 0);
-        hipLaunchKernelGGL(k_post, dim3((P.n_zmw + 255) / 256), dim3(256), 0, st, P, pass);
-        LAUNCH_CHECK("k_post");
     }
-    if (mode == CCSX_RUN_DRAFT) {                                   // the draft seam ends here: drafts, window bounds, alignments and statuses are final
-        if (ev) for (int k : {3, 6, 4, 5}) CALL_CHECK(hipEventRecord, ev[k], st);
-        return failed;
+
+    // the batch's windows in compact order: the polish stage's grid map
+    void window_map()
+    {
+        launch("k_wmap", k_wmap, dim3(1), dim3(1024), 0, st, P);
+        launch("k_wmap_fill", k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
     }
-    hipLaunchKernelGGL(k_wmap, dim3(1), dim3(1024), 0, st, P);     // the batch's windows in compact order: the polish stage's grid map
-    LAUNCH_CHECK("k_wmap");
-    hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
-    LAUNCH_CHECK("k_wmap_fill");
+
     // The draft screens a fused run was asked for (the requests of ccsx_submit_control / ccsx_consensus_control and their narrower forms): adapter palindromes,
     // the adapter screen, the control screen.  On the draft stream, on the final drafts and statuses k_polish is given; each writes its report only.
-    const struct { const void *report; void (*kernel)(KParams); int threads; size_t lds; const char *name; } screens[] = {
-        {P.fold_zi, k_fold, CCSX_FOLD_THREADS, (size_t)P.fold_bins * 4, "k_fold"},
-        {P.adapt_zi, k_adapter, CCSX_ADAPTER_THREADS, (size_t)P.adapt_words * 8, "k_adapter"},
-        {P.ctl_zi, k_control, CCSX_CONTROL_THREADS, (size_t)P.ctl_bins * 8, "k_control"}};
-    for (const auto &s : screens) if (mode == CCSX_RUN_FUSED && s.report) {
-        hipLaunchKernelGGL(s.kernel, dim3(P.n_zmw), dim3(s.threads), s.lds, st, P);
-        LAUNCH_CHECK(s.name);
-        trace_sync(st, s.name);
+    void draft_screens()
+    {
+        const struct { const void *report; void (*kernel)(KParams); int threads; size_t lds; const char *name; } screens[] = {
+            {P.fold_zi, k_fold, CCSX_FOLD_THREADS, (size_t)P.fold_bins * 4, "k_fold"},
+            {P.adapt_zi, k_adapter, CCSX_ADAPTER_THREADS, (size_t)P.adapt_words * 8, "k_adapter"},
+            {P.ctl_zi, k_control, CCSX_CONTROL_THREADS, (size_t)P.ctl_bins * 8, "k_control"}};
+        for (const auto &s : screens) if (s.report) {
+            launch(s.name, s.kernel, dim3(P.n_zmw), dim3(s.threads), s.lds, st, P);
+            trace_sync(st, s.name);
+        }
     }
-    // the heteroduplex finder's three kernels on the draft stream (the fused path with a request, ccsx_hd_batch), `before_verdict` recorded between the last two
-    auto hd_kernels = [&](hipEvent_t before_verdict) {
+
+    // The heteroduplex finder's three kernels on the draft stream.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the
+    // cascade and the entry rows (k_polish trims large insertions in LDS only).  It reads no shared POA / alignment scratch.
+    // in_place_of_polish (ccsx_hd_batch): the verdict is what the run has for a stitch, CCSX_EV_POLISH_DONE is recorded before it.
+    void hd_finder(bool in_place_of_polish)
+    {
         const long long groups = (P.total_wslots + HD_WG_WIN - 1) / HD_WG_WIN;   // (the grid covers the slot capacity, the map only the windows there are)
-        hipLaunchKernelGGL(k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_hd_pile");
-        hipLaunchKernelGGL(k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_hd_indel");
-        if (before_verdict) CALL_CHECK(hipEventRecord, before_verdict, st);
-        hipLaunchKernelGGL(k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_hd_verdict");
-    };
-    if (mode == CCSX_RUN_FUSED && P.hd_zi) {
-        // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft stage
-        // and runs under the previous batch's polish stage.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the
-        // cascade and the entry rows (k_polish trims large insertions in LDS only).  It reads no shared POA / alignment scratch.
-        hd_kernels(nullptr);
-        if (P.hd_split) {                                          // the split ZMWs have no windows now: the polish stage's map without them
-            hipLaunchKernelGGL(k_wmap, dim3(1), dim3(1024), 0, st, P);
-            LAUNCH_CHECK("k_wmap");
-            hipLaunchKernelGGL(k_wmap_fill, dim3((P.n_zmw + 3) / 4), dim3(256), 0, st, P);
-            LAUNCH_CHECK("k_wmap_fill");
+        launch("k_hd_pile", k_hd_pile, dim3((unsigned)(groups > 0 ? groups : 1)), dim3(64), 0, st, P);
+        launch("k_hd_indel", k_hd_indel, dim3(P.n_zmw), dim3(64), 0, st, P);
+        if (in_place_of_polish) stage_event(CCSX_EV_POLISH_DONE, st);
+        launch("k_hd_verdict", k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
+    }
+
+    // Two-stage queue of docs/img/ccs-impl.png ("Draft Stage" -> queue -> "Polish Stage"): the draft stage (tables, POA, alignment cascade, accounting, screens)
+    // is enqueued on the draft stream, the polish stage (polish, kinetics, stitch) on the polish stream, which waits for the draft stage's last kernel through
+    // CCSX_EV_DRAFT_STAGE_DONE.  With two different streams the draft stage of batch k+1 runs UNDER the polish stage of batch k (the register-only one-wave POA
+    // and the LDS-bound polish workgroups share the SIMDs); the shared POA / alignment scratch is touched by the draft stage only, so the draft stream alone
+    // orders its users.  The same stream for both: serial stages.
+    void polish_stage()
+    {
+        const hipStream_t sp = q.polish;
+        if (q.ev) {
+            record(q.ev[CCSX_EV_DRAFT_STAGE_DONE], st);
+            if (sp != st) wait(sp, q.ev[CCSX_EV_DRAFT_STAGE_DONE]);
+            record(q.ev[CCSX_EV_POLISH_START], sp);         // the polish stage starts here (after the queue between the stages)
+        } else if (sp != st && !failed) failed = "two streams need events";
+        // One workgroup per window slot.  A grid may not exceed 2^32 threads in all: 256 threads x 16.7 M slots — 8192 ZMWs of 30 passes x 20 kb have 10.8 M, and a
+        // larger batch would silently lose its tail (round 4 met exactly this with a 512-thread experiment: 75 % of the ZMWs "failed").  The slots are therefore
+        // launched in pieces of at most 2^24 - 256 workgroups (just under the limit, so that a 16384-ZMW batch of 10 kb inserts — 8.5 M slots of capacity — is ONE launch:
+        // the profile's per-launch average and bench.py's per-batch duration then describe the same thing; LaunchSwitches::max_blocks forces small pieces).
+        for_each_piece(P.total_wslots, sw.max_blocks, [&](long long s0, long long nb) {
+            launch("k_polish", k_polish_t<PW_THREADS, PW_MINWAVES, PW_CHUNK_READS>, dim3(((unsigned)nb + 7u) & ~7u), dim3(PW_THREADS),
+                   (size_t)P.pw_obs_bytes + (size_t)P.pw_gb_floats * 4, sp, P, (int)s0);
+        });
+        trace_sync(sp, "k_polish");
+        if (P.opts.hifi_kinetics || P.wpile) {             // one alignment per (pass, window) segment feeds kinetics, the pileup summary or both
+            const bool kin = P.opts.hifi_kinetics != 0, pile = P.wpile != nullptr;
+            const auto kfn = kin ? (pile ? k_kinetics_t<1, 1> : k_kinetics_t<1, 0>) : k_kinetics_t<0, 1>;
+            const char *const name = kin ? (pile ? "k_kinetics_pile" : "k_kinetics") : "k_pileup";
+            for_each_piece(P.total_wslots, sw.max_blocks, [&](long long s0, long long nb) {
+                launch(name, kfn, dim3(((unsigned)nb + 7u) & ~7u), dim3(256), 0, sp, P, (int)s0);
+            });
+            trace_sync(sp, "k_kinetics");
         }
-        trace_sync(st, "k_hd");
+        stage_event(CCSX_EV_POLISH_DONE, sp);
+        launch("k_stitch", k_stitch, dim3(P.n_zmw), dim3(64), 0, sp, P);
+        if (P.out_pile) launch("k_pile_stitch", k_pile_stitch, dim3(P.n_zmw), dim3(64), 0, sp, P);
+        stage_event(CCSX_EV_END, sp);
     }
-    if (mode == CCSX_RUN_HD) {                                     // the heteroduplex finder instead of the polish stage, on the same stream
-        if (ev) for (int k : {3, 6}) CALL_CHECK(hipEventRecord, ev[k], st);
-        hd_kernels(ev ? ev[4] : nullptr);
-        trace_sync(st, "k_hd");
-        if (ev) CALL_CHECK(hipEventRecord, ev[5], st);
-        return failed;
+};
+
+}  // namespace
+
+// The four run modes share one schedule and leave it at three places.  No stage synchronises with the host.
+const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode)
+{
+    static const LaunchSwitches switches;
+    Schedule s(P, q, mode, switches);
+    s.tables();
+    s.draft_stage();
+    if (mode == CCSX_RUN_DRAFT) {                           // the draft seam ends here: drafts, window bounds, alignments and statuses are final
+        s.close_timing(CCSX_EV_DRAFT_STAGE_DONE, CCSX_EV_END);
+        return s.failed;
     }
-    if (ev) {
-        CALL_CHECK(hipEventRecord, ev[3], st);
-        if (st_polish != st) CALL_CHECK(hipStreamWaitEvent, st_polish, ev[3], 0);
-        CALL_CHECK(hipEventRecord, ev[6], st_polish);            // the polish stage starts here (after the queue between the stages)
-    } else if (st_polish != st && !failed) failed = "two streams need events";
-    st = st_polish;
-    // One workgroup per window slot.  A grid may not exceed 2^32 threads in all: 256 threads x 16.7 M slots — 8192 ZMWs of 30 passes x 20 kb have 10.8 M, and a
-    // larger batch would silently lose its tail (round 4 met exactly this with a 512-thread experiment: 75 % of the ZMWs "failed").  The slots are therefore
-    // launched in pieces of at most 2^24 - 256 workgroups (just under the limit, so that a 16384-ZMW batch of 10 kb inserts — 8.5 M slots of capacity — is ONE launch:
-    // the profile's per-launch average and bench.py's per-batch duration then describe the same thing; CCSX_POLISH_MAX_BLOCKS: a test hook that forces small pieces).
-    static const long long max_blocks = [] { const char *e = getenv("CCSX_POLISH_MAX_BLOCKS"); long long v = e ? atoll(e) : 0; return v > 8 ? (v & ~7ll) : (1ll << 24) - 256; }();   // (a multiple of 8: the kernels take their windows in XCD-contiguous order)
-    for (long long s0 = 0; s0 < P.total_wslots; s0 += max_blocks) {
-        const unsigned nb = (unsigned)((P.total_wslots - s0) < max_blocks ? (P.total_wslots - s0) : max_blocks);
-        hipLaunchKernelGGL((k_polish_t<PW_THREADS, PW_MINWAVES, PW_CHUNK_READS>), dim3((nb + 7u) & ~7u), dim3(PW_THREADS),
-                           (size_t)P.pw_obs_bytes + (size_t)P.pw_gb_floats * 4, st, P, (int)s0);
-        LAUNCH_CHECK("k_polish");
-    }
-    trace_sync(st, "k_polish");
-    if (P.opts.hifi_kinetics || P.wpile) {                 // one alignment per (pass, window) segment feeds kinetics, the pileup summary or both
-        const bool kin = P.opts.hifi_kinetics != 0, pile = P.wpile != nullptr;
-        auto kfn = kin ? (pile ? k_kinetics_t<1, 1> : k_kinetics_t<1, 0>) : k_kinetics_t<0, 1>;
-        for (long long s0 = 0; s0 < P.total_wslots; s0 += max_blocks) {
-            const unsigned nb = (unsigned)((P.total_wslots - s0) < max_blocks ? (P.total_wslots - s0) : max_blocks);
-            hipLaunchKernelGGL(kfn, dim3((nb + 7u) & ~7u), dim3(256), 0, st, P, (int)s0);
-            LAUNCH_CHECK(kin ? (pile ? "k_kinetics_pile" : "k_kinetics") : "k_pileup");
+    s.window_map();
+    if (mode == CCSX_RUN_FUSED) {
+        s.draft_screens();
+        if (P.hd_zi) {
+            // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft
+            // stage and runs under the previous batch's polish stage
+            s.hd_finder(false);
+            if (P.hd_split) s.window_map();                 // the split ZMWs have no windows now: the polish stage's map without them
+            s.trace_sync(q.draft, "k_hd");
         }
-        trace_sync(st, "k_kinetics");
     }
-    if (ev) CALL_CHECK(hipEventRecord, ev[4], st);
-    hipLaunchKernelGGL(k_stitch, dim3(P.n_zmw), dim3(64), 0, st, P);
-    LAUNCH_CHECK("k_stitch");
-    if (P.out_pile) {
-        hipLaunchKernelGGL(k_pile_stitch, dim3(P.n_zmw), dim3(64), 0, st, P);
-        LAUNCH_CHECK("k_pile_stitch");
+    if (mode == CCSX_RUN_HD) {                              // the heteroduplex finder instead of the polish stage, on the same stream
+        s.close_timing(CCSX_EV_DRAFT_STAGE_DONE, CCSX_EV_POLISH_START);
+        s.hd_finder(true);
+        s.trace_sync(q.draft, "k_hd");
+        s.stage_event(CCSX_EV_END, q.draft);
+        return s.failed;
     }
-    if (ev) CALL_CHECK(hipEventRecord, ev[5], st);
-    return failed;
+    s.polish_stage();
+    return s.failed;
 }

@@ -1374,6 +1374,41 @@ def test_ticket_timings_do_not_read_caller_memory(handle):
 
 
 @pytest.mark.gpu
+def test_every_run_mode_records_every_stage_event(built):
+    """a fused ticket, a draft-seam ticket, a polish-seam ticket and a ccsx_hd_batch call each leave all seven stage durations readable: the getter returns 0,
+    every figure is finite and >= 0, and total_ms is no shorter than any part — every stage event was recorded, in order, on every path of the launch
+    schedule.  (ccsx_hd_batch is synchronous and has no ticket: ccsx_get_timings reads its slot's events.)"""
+    import ctypes as C, math
+    L = api.lib()
+    h = api.Handle(0)
+    b = api.synth(8, 3, 500, seed=97)
+
+    def check(tm, what):
+        parts = [tm.setup_ms, tm.draft_ms, tm.align_ms, tm.queue_ms, tm.polish_ms, tm.stitch_ms]
+        print(what, parts, tm.total_ms)
+        assert all(math.isfinite(x) and x >= 0 for x in parts + [tm.total_ms]), (what, parts, tm.total_ms)
+        assert all(tm.total_ms >= x for x in parts), (what, parts, tm.total_ms)
+
+    def ticket(t, what):
+        tm = api.Timings()
+        assert L.ccsx_wait(h._h, t.value) == 0, L.ccsx_last_error()
+        assert L.ccsx_ticket_timings(h._h, t.value, C.byref(tm)) == 0, L.ccsx_last_error()
+        check(tm, what)
+
+    r, d = api.Results.allocate(b), api.Drafts.allocate(b)
+    cb, cr, cd, t = b.c_struct(), r.c_struct(), d.c_struct(), C.c_int64()
+    assert L.ccsx_submit(h._h, C.byref(cb), C.byref(cr), C.byref(t)) == 0, L.ccsx_last_error()
+    ticket(t, "fused")
+    assert L.ccsx_submit_draft(h._h, C.byref(cb), C.byref(cd), C.byref(t)) == 0, L.ccsx_last_error()
+    ticket(t, "draft seam")
+    assert L.ccsx_submit_polish(h._h, C.byref(cb), C.byref(cd), C.byref(cr), 0, C.byref(t)) == 0, L.ccsx_last_error()
+    ticket(t, "polish seam")
+    h.hd(b, d)
+    check(h.timings(), "ccsx_hd_batch")
+    h.close()
+
+
+@pytest.mark.gpu
 def test_timing_origin_moves_only_while_the_handle_is_idle(built):
     """the origin of ccsx_timings.start_ms / end_ms is moved forward at a submit that finds NO slot in flight (never inside the getter, never under pending
     tickets).  CCSX_EPOCH_REBASE_MS=0 forces a move at every idle submit: times stay monotone across moves, tickets in flight keep their timings."""
