@@ -461,6 +461,120 @@ class Timings(C.Structure):
     ]
 
 
+# ---- model training (include/ccsx.h ccsx_train_*, ccsx_fitter_*; DESIGN.md §2 "Model training")
+TRAIN_FRAC = 32
+
+
+class CTrainCounts(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32), ("reserved", C.c_int32), ("match", C.POINTER(C.c_int64)), ("stay", C.POINTER(C.c_int64)),
+                ("del_", C.POINTER(C.c_int64)), ("loglik", C.POINTER(C.c_int64)), ("n_pairs", C.POINTER(C.c_int32)), ("n_gated", C.POINTER(C.c_int32)),
+                ("n_bases", C.POINTER(C.c_int32)), ("status", C.POINTER(C.c_int32))]
+
+
+class FitOpts(C.Structure):
+    _fields_ = [("degree", C.c_int32), ("snr_bins", C.c_int32), ("min_events", C.c_double), ("pseudo", C.c_double)]
+
+
+class FitReport(C.Structure):
+    _fields_ = [("pairs", C.c_int64), ("gated", C.c_int64), ("bases", C.c_int64), ("loglik_per_base", C.c_double), ("contexts_kept", C.c_int32),
+                ("snr_lo", C.c_float), ("snr_hi", C.c_float), ("max_change", C.c_double)]
+
+
+def fit_opts_default() -> FitOpts:
+    o = FitOpts()
+    lib().ccsx_fit_opts_default(C.byref(o))
+    return o
+
+
+class TrainCounts:
+    """ccsx_train_counts: per ZMW the posterior event counts x 2^32 (match, stay [n, 16, 12], del_ [n, 16]; `del` is a Python keyword), loglik x 65536,
+    the pair / gated-pair / base counts and the status after the cascade."""
+    PLANES = (("match", np.int64, (NCTX, NOBS)), ("stay", np.int64, (NCTX, NOBS)), ("del_", np.int64, (NCTX,)), ("loglik", np.int64, ()),
+              ("n_pairs", np.int32, ()), ("n_gated", np.int32, ()), ("n_bases", np.int32, ()), ("status", np.int32, ()))
+
+    def __init__(self, n: int):
+        for k, dt, shape in self.PLANES:
+            setattr(self, k, np.zeros((n,) + shape, dt))
+
+    @classmethod
+    def allocate(cls, batch: "Batch | int") -> "TrainCounts":
+        return cls(batch if isinstance(batch, int) else batch.n_zmw)
+
+    @property
+    def n_zmw(self) -> int:
+        return len(self.loglik)
+
+    def c_struct(self) -> CTrainCounts:
+        c = CTrainCounts()
+        c.n_zmw = self.n_zmw; c.reserved = 0
+        types = dict(CTrainCounts._fields_)
+        for k, _, _ in self.PLANES:
+            setattr(c, k, getattr(self, k).ctypes.data_as(types[k]))
+        return c
+
+    def add(self, other: "TrainCounts") -> "TrainCounts":
+        """the exact int64 sum, ZMW by ZMW (the status is kept)"""
+        assert other.n_zmw == self.n_zmw
+        for k, _, _ in self.PLANES[:-1]:
+            getattr(self, k)[...] += getattr(other, k)
+        return self
+
+    def rows(self, zs) -> "TrainCounts":
+        """the ZMWs `zs`, in that order, as a new object"""
+        zs = np.asarray(zs, np.int64)
+        out = TrainCounts(len(zs))
+        for k, _, _ in self.PLANES:
+            getattr(out, k)[...] = getattr(self, k)[zs]
+        return out
+
+
+def train_pair_host(model: Model, snr, tpl, left_flank: int, cs: int, ce: int, obs, min_zscore: float = 0.0, out=None, J: "int | None" = None, n: "int | None" = None):
+    """ccsx_train_pair_host: one pair on the host.  Returns (rc, match[16, 12], stay[16, 12], del[16], loglik[1]) — the int64 arrays of `out` (the same tuple without
+    rc), which are added to, or fresh zeroed ones.  rc: 1 counted, 0 gated, < 0 bad argument.  J / n override the array lengths (argument tests)"""
+    snr = np.ascontiguousarray(snr, np.float32); tpl = np.ascontiguousarray(tpl, np.uint8); obs = np.ascontiguousarray(obs, np.uint8)
+    m, s, d, ll = out if out is not None else (np.zeros((NCTX, NOBS), np.int64), np.zeros((NCTX, NOBS), np.int64), np.zeros(NCTX, np.int64), np.zeros(1, np.int64))
+    rc = lib().ccsx_train_pair_host(C.byref(model), _ptr(snr, C.c_float), _ptr(tpl, C.c_uint8), len(tpl) if J is None else J, int(left_flank), int(cs), int(ce),
+                                    _ptr(obs, C.c_uint8), len(obs) if n is None else n, float(min_zscore), _ptr(m, C.c_int64), _ptr(s, C.c_int64),
+                                    _ptr(d, C.c_int64), _ptr(ll, C.c_int64))
+    return rc, m, s, d, ll
+
+
+class Fitter:
+    """ccsx_fitter: the M-step.  Fitter(start, opts).add(counts, snr) ... .finish() -> (Model, FitReport); host only, no device."""
+
+    def __init__(self, start: Model, opts: "FitOpts | None" = None):
+        self._L = lib()
+        self._f = C.c_void_p()
+        o = opts if opts is not None else fit_opts_default()
+        if self._L.ccsx_fitter_create(C.byref(start), C.byref(o), C.byref(self._f)) != 0:
+            raise RuntimeError("ccsx_fitter_create failed: " + self._L.ccsx_last_error().decode())
+
+    def add(self, counts: TrainCounts, snr) -> "Fitter":
+        snr = np.ascontiguousarray(snr, np.float32)
+        assert snr.shape == (counts.n_zmw, 4)
+        cc = counts.c_struct()
+        if self._L.ccsx_fitter_add(self._f, C.byref(cc), _ptr(snr, C.c_float)) != 0:
+            raise RuntimeError("ccsx_fitter_add failed: " + self._L.ccsx_last_error().decode())
+        return self
+
+    def finish(self) -> "tuple[Model, FitReport]":
+        m, rep = Model(), FitReport()
+        if self._L.ccsx_fitter_finish(self._f, C.byref(m), C.byref(rep)) != 0:
+            raise RuntimeError("ccsx_fitter_finish failed: " + self._L.ccsx_last_error().decode())
+        return m, rep
+
+    def close(self):
+        if self._f:
+            self._L.ccsx_fitter_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CSynth(C.Structure):
     _fields_ = [("batch", CBatch), ("tpl_off", C.POINTER(C.c_int64)), ("tpl", C.POINTER(C.c_uint8))]
 
@@ -483,6 +597,8 @@ EXPORTS = [
     "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
     "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
     "ccsx_inflate_blocks_host",
+    "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
+    "ccsx_fit_opts_default", "ccsx_fitter_create", "ccsx_fitter_add", "ccsx_fitter_finish", "ccsx_fitter_destroy",
 ]
 
 _lib = None
@@ -570,6 +686,16 @@ def lib() -> C.CDLL:
         L.ccsx_inflate_submit.argtypes = [C.c_void_p] + _call + [C.POINTER(C.c_int64)]
         L.ccsx_inflate_wait.argtypes = [C.c_void_p, C.c_int64]
         L.ccsx_inflate_blocks_host.argtypes = _call
+        _i64p = C.POINTER(C.c_int64)
+        L.ccsx_train_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(CTrainCounts)]
+        L.ccsx_train_pair_host.argtypes = [C.POINTER(Model), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_uint8), C.c_int32, C.c_float, _i64p, _i64p, _i64p, _i64p]
+        L.ccsx_fit_opts_default.restype = None
+        L.ccsx_fit_opts_default.argtypes = [C.POINTER(FitOpts)]
+        L.ccsx_fitter_create.argtypes = [C.POINTER(Model), C.POINTER(FitOpts), C.POINTER(C.c_void_p)]
+        L.ccsx_fitter_add.argtypes = [C.c_void_p, C.POINTER(CTrainCounts), C.POINTER(C.c_float)]
+        L.ccsx_fitter_finish.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(FitReport)]
+        L.ccsx_fitter_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -993,6 +1119,13 @@ class Handle:
         o = opts if opts is not None else hd_opts_default()
         self._check(self._L.ccsx_hd_batch(self._h, C.byref(cb), C.byref(cd), C.byref(o), C.byref(cr)), "ccsx_hd_batch")
         return rep
+
+    # ---- the fourth seam: the training counts on caller-supplied drafts (no polish runs; DESIGN.md §2 "Model training")
+    def train_counts(self, batch: Batch, drafts: "Drafts") -> TrainCounts:
+        tc = TrainCounts.allocate(batch)
+        cb, cd, cc = batch.c_struct(), drafts.c_struct(), tc.c_struct()
+        self._check(self._L.ccsx_train_batch(self._h, C.byref(cb), C.byref(cd), C.byref(cc)), "ccsx_train_batch")
+        return tc
 
     # ---- the pileup summary (sa sm sx): the fused path plus per-base planes from the kinetics alignment
     def consensus_pileup(self, batch: Batch) -> tuple["Results", "Pileup"]:

@@ -82,6 +82,11 @@ struct Options {
     std::string control;          // --control FILE.fasta: screen the drafts for the spike-in control (fail class 0x2); control ZMWs leave the main output
     std::vector<uint8_t> control_codes;   // ... its bases
     ccsx_control_seq control_seq{};       // ... as the requests name them
+    std::string fit_model;        // --fit-model OUT.json: the training mode (DESIGN.md §2 "Model training"): no consensus output
+    int fit_iterations = 3;       // --fit-iterations: EM iterations over the file
+    double fit_min_rq = 0.999;    // --fit-min-rq: a polished consensus is a truth to measure passes against from this predicted accuracy on
+    long long fit_max_zmws = 0;   // --fit-max-zmws: ZMWs (after the step-1 filters) that are used, 0 = all
+    int fit_degree = -1;          // --fit-degree: polynomial degree of the transition weights (-1: the fitter's default)
 };
 
 enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103, HS_ADAPTER_PALINDROME = 104, HS_ADAPTER_CONCAT = 105,
@@ -235,7 +240,17 @@ void usage()
                  "  test helpers (not in the reference):\n"
                  "      --write-synthetic N,P,L[,seed]  write a synthetic subreads.bam to OUT (no IN)\n"
                  "      --dump-zmws                     list ZMWs after the step-1 filters (no GPU, no OUT)\n"
-                 "      --host-only                     read, filter and pack IN into batch staging, no engine (no GPU, no OUT): host throughput\n");
+                 "      --host-only                     read, filter and pack IN into batch staging, no engine (no GPU, no OUT): host throughput\n"
+                 "model training (ccs --fit-model OUT.json IN.subreads.bam; one GPU, no HiFi output):\n"
+                 "      --fit-model OUT.json  fit the Arrow parameter set to the subreads of IN by EM and write it as a ccsx-1 json with the header's chemistry\n"
+                 "                            triple: per iteration every batch is drafted and polished, the passes are measured against the polished reads of at\n"
+                 "                            least --fit-min-rq (posterior event counts, k_train), and the fitter makes the next model.  Starts from the\n"
+                 "                            chemistry's model or --model-file.  Not with a second positional, several GPUs, --chunk or any option of the\n"
+                 "                            output side (--fail-reads, --by-strand, --control, --adapters, reports, tags, --gpu-inflate): usage errors\n"
+                 "      --fit-iterations N    EM iterations (default 3)\n"
+                 "      --fit-min-rq X        predicted accuracy a polished read needs to serve as a truth (default 0.999)\n"
+                 "      --fit-max-zmws N      use the first N ZMWs that pass the filters (default 0 = all)\n"
+                 "      --fit-degree D        polynomial degree of the transition weights in the SNR, 0 .. 3 (default 1)\n");
 }
 
 // --adapters: "default" = the built-in set; otherwise a FASTA of 1 .. 8 records of 16 .. 64 bases, ACGT in either case.  false + a message that names the record
@@ -350,6 +365,11 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--adapters") o.adapters = need(a.c_str());
         else if (a == "--control") o.control = need(a.c_str());
         else if (a == "--model-file") o.model_file = need(a.c_str());
+        else if (a == "--fit-model") o.fit_model = need(a.c_str());
+        else if (a == "--fit-iterations") o.fit_iterations = std::atoi(need(a.c_str()).c_str());
+        else if (a == "--fit-min-rq") o.fit_min_rq = std::atof(need(a.c_str()).c_str());
+        else if (a == "--fit-max-zmws") o.fit_max_zmws = std::atoll(need(a.c_str()).c_str());
+        else if (a == "--fit-degree") o.fit_degree = std::atoi(need(a.c_str()).c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
         else if (a == "--metrics-json") { o.metrics = need(a.c_str()); o.metrics_named = true; }
         else if (a == "--report-json") o.report_json = need(a.c_str());
@@ -363,6 +383,23 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if (!o.fit_model.empty()) {                              // the training mode takes nothing of the output side: refused before any of those options is looked at
+        auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --fit-model %s\n", what); std::exit(2); };
+        if (!o.fail_reads.empty()) refuse("combined with --fail-reads is not supported");
+        if (o.by_strand) refuse("combined with --by-strand is not supported");
+        if (o.gpus.size() > 1) refuse("runs on one GPU: --gpus with more than one device is not supported");
+        if (o.fit_iterations < 1 || o.fit_max_zmws < 0 || o.fit_degree > 3 || o.fit_degree < -1 || !(o.fit_min_rq >= 0.0 && o.fit_min_rq <= 1.0))
+            refuse("options out of range (--fit-iterations >= 1, --fit-max-zmws >= 0, --fit-degree 0 .. 3, --fit-min-rq in [0, 1])");
+        if (o.dump || o.host_only) refuse("combined with --dump-zmws or --host-only is not supported");
+        // nothing of the output side runs in this mode: an option that would be ignored is refused, not dropped silently
+        if (!o.control.empty() || !o.adapters.empty()) refuse("runs no draft screen: --control and --adapters are not supported with it");
+        if (o.gpu_inflate) refuse("combined with --gpu-inflate is not supported");
+        if (o.report_named || o.metrics_named || !o.report_json.empty() || !o.hifi_summary.empty() || o.suppress_reports)
+            refuse("writes no reports: --report-file, --metrics-json, --report-json, --hifi-summary-json and --suppress-reports are not supported with it");
+        if (o.pileup || o.qv_binning || o.o.hifi_kinetics || o.min_tandem > 0)
+            refuse("writes no reads: --pileup-summary, --qv-binning, --hifi-kinetics and --min-tandem-repeat-length are not supported with it");
+        if (o.chunk_n > 1) refuse("reads the whole file: --chunk is not supported with it");
     }
     if (!o.fail_reads.empty()) {
         if (o.fail_reads.size() < 5 || o.fail_reads.compare(o.fail_reads.size() - 4, 4, ".bam") != 0) {
@@ -387,6 +424,12 @@ bool parse(int argc, char **argv, Options &o)
         o.o.top_passes = CCSX_MAX_PASSES;
     }
     if (!o.write_synth.empty()) { if (pos.size() != 1) return false; o.out = pos[0]; return true; }
+    if (!o.fit_model.empty()) {                              // the training mode: one positional, one GPU, nothing of the output side
+        auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --fit-model %s\n", what); std::exit(2); };
+        if (pos.size() != 1) refuse("takes one positional, IN.subreads.bam: it writes OUT.json and no reads");
+        o.in = pos[0]; if (o.batch < 0) o.batch = 0;
+        return true;
+    }
     if (o.dump || o.host_only) { if (pos.size() != 1) return false; o.in = pos[0]; if (o.batch < 0) o.batch = 0; return true; }
     if (pos.size() != 2) return false;
     o.in = pos[0]; o.out = pos[1];
@@ -845,6 +888,78 @@ struct GpuInflaters {
 
 }  // namespace
 
+// ---- ccs --fit-model: EM over the packed batches of the file, serial, on one GPU (DESIGN.md §2 "Model training").  Per iteration a handle with the current
+// model; per batch the draft seam, the polish seam, drafts made of the polished reads that are good enough to be a truth, the training counts on them, the
+// fitter.  h0: the handle main() made with the start model (iteration 1 uses it; it is destroyed here, `h0` is cleared).  0, or 1 after an engine failure (no json).
+static int fit_model(const Options &opt, ccsx_handle &h0, const ccsx_model &start, const std::vector<std::shared_ptr<Batch>> &batches, const std::string &bk,
+              const std::string &sk, const std::string &bc)
+{
+    auto engine_failed = [&](const char *what) { std::fprintf(stderr, "ccs: --fit-model: %s: %s\n", what, ccsx_last_error()); return 1; };
+    if (batches.empty()) { std::fprintf(stderr, "ccs: --fit-model: no ZMW of %s passes the filters\n", opt.in.c_str()); return 1; }
+    const int dev = opt.gpus.empty() ? 0 : opt.gpus[0];
+    ccsx_fit_opts fo; ccsx_fit_opts_default(&fo);
+    if (opt.fit_degree >= 0) fo.degree = opt.fit_degree;
+    ccsx_model cur = start;
+    for (int it = 1; it <= opt.fit_iterations; ++it) {
+        ccsx_handle h = h0; h0 = nullptr;
+        if (!h && ccsx_create(dev, &cur, &opt.o, &h)) return engine_failed("ccsx_create");
+        ccsx_fitter fit = nullptr;
+        if (ccsx_fitter_create(&cur, &fo, &fit)) { ccsx_destroy(h); return engine_failed("ccsx_fitter_create"); }
+        long long used = 0;
+        int rc = 0;
+        for (const auto &b : batches) {
+            const int n = b->n;
+            std::vector<int64_t> seq_off(n + 1), win_off(n + 1);
+            int64_t scap = 0, wcap = 0;
+            ccsx_draft_layout(&b->cb, seq_off.data(), win_off.data(), &scap, &wcap);
+            std::vector<int32_t> i32((size_t)n * 16);
+            std::vector<uint8_t> dseq((size_t)scap), rseq((size_t)scap), rqual((size_t)scap), tseq((size_t)scap);
+            std::vector<float> f32((size_t)n * 2);
+            int32_t *I = i32.data();
+            ccsx_drafts dr{n, scap, 0, seq_off.data(), nullptr, I, I + n, dseq.data(), I + 2 * n, nullptr, nullptr};
+            ccsx_results res{n, scap, seq_off.data(), I + 3 * n, I + 4 * n, rseq.data(), rqual.data(), nullptr, f32.data(), I + 5 * n, f32.data() + n, I + 6 * n, I + 7 * n};
+            res.fn = I + 8 * n; res.rn = I + 9 * n;
+            if (ccsx_draft_batch(h, &b->cb, &dr)) { rc = engine_failed("ccsx_draft_batch"); break; }
+            if (ccsx_polish_batch(h, &b->cb, &dr, &res, 0)) { rc = engine_failed("ccsx_polish_batch"); break; }
+            // the truths: the polished reads of the ZMWs that succeeded with rq >= --fit-min-rq, in the draft call's orientation; none for the rest
+            ccsx_drafts tr{n, scap, 0, seq_off.data(), nullptr, nullptr, I + 10 * n, tseq.data(), I + 2 * n, nullptr, nullptr};
+            for (int z = 0; z < n; ++z) {
+                const bool ok = res.status[z] == CCSX_SUCCESS && (double)res.rq[z] >= opt.fit_min_rq && res.seq_len[z] > 0;
+                tr.len[z] = ok ? res.seq_len[z] : 0;
+                if (ok) { std::memcpy(tseq.data() + seq_off[z], rseq.data() + seq_off[z], (size_t)res.seq_len[z]); ++used; }
+            }
+            std::vector<int64_t> tab((size_t)n * 401);
+            ccsx_train_counts tc{n, 0, tab.data(), tab.data() + (size_t)n * 192, tab.data() + (size_t)n * 384, tab.data() + (size_t)n * 400, I + 11 * n, I + 12 * n,
+                                 I + 13 * n, I + 14 * n};
+            if (ccsx_train_batch(h, &b->cb, &tr, &tc)) { rc = engine_failed("ccsx_train_batch"); break; }
+            if (ccsx_fitter_add(fit, &tc, b->snr.data())) { rc = engine_failed("ccsx_fitter_add"); break; }
+        }
+        ccsx_model next;
+        ccsx_fit_report rep{};
+        if (!rc && ccsx_fitter_finish(fit, &next, &rep)) rc = engine_failed("ccsx_fitter_finish");
+        ccsx_fitter_destroy(fit);
+        ccsx_destroy(h);
+        if (rc) return rc;
+        if (opt.log_level >= 2)
+            std::fprintf(stderr, "ccs: --fit-model iteration %d: %lld ZMWs used, %lld pairs, %lld gated, log2-likelihood per base %.5f, largest parameter change %.3g\n", it, used,
+                         (long long)rep.pairs, (long long)rep.gated, rep.loglik_per_base, rep.max_change);
+        if (rep.pairs == 0) { std::fprintf(stderr, "ccs: --fit-model: no pair was counted (no polished read reaches --fit-min-rq %.4f?)\n", opt.fit_min_rq); return 1; }
+        cur = next;
+    }
+    const std::string name = ("fit-" + std::string(start.name, strnlen(start.name, sizeof(start.name)))).substr(0, sizeof(cur.name) - 1);   // (cut to 31 characters)
+    std::memset(cur.name, 0, sizeof(cur.name));
+    std::memcpy(cur.name, name.data(), name.size());
+    const int64_t need = ccsx_model_to_json(&cur, bk.empty() ? nullptr : bk.c_str(), sk.empty() ? nullptr : sk.c_str(), bc.empty() ? nullptr : bc.c_str(), nullptr, 0);
+    if (need <= 0) return engine_failed("ccsx_model_to_json");
+    std::string text((size_t)need + 1, '\0');
+    ccsx_model_to_json(&cur, bk.empty() ? nullptr : bk.c_str(), sk.empty() ? nullptr : sk.c_str(), bc.empty() ? nullptr : bc.c_str(), &text[0], need + 1);
+    FILE *f = std::fopen(opt.fit_model.c_str(), "w");
+    if (!f || std::fwrite(text.c_str(), 1, std::strlen(text.c_str()), f) != std::strlen(text.c_str()) || std::fclose(f)) {
+        std::fprintf(stderr, "ccs: cannot write %s\n", opt.fit_model.c_str()); return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     Options opt;
@@ -879,7 +994,7 @@ int main(int argc, char **argv)
         // ---- model parameters: --model-file, else by the chemistry triple of the header (docs/faq/chemistry.md:27-56);
         // "Abort if chemistry information is missing in BAM header" (docs/changelog.md:66)
         ccsx_model model;
-        std::string chem_desc;
+        std::string chem_desc, chem_bk, chem_sk, chem_bc;   // (the triple: --fit-model writes it into OUT.json)
         if (!opt.dump && !opt.host_only) {
             auto ds_value = [&](const char *key) -> std::string {
                 const size_t rg = hdr.text.find("@RG");
@@ -889,6 +1004,7 @@ int main(int argc, char **argv)
                 return hdr.text.substr(a, e == std::string::npos ? std::string::npos : e - a);
             };
             const std::string bk = ds_value("BINDINGKIT"), sk = ds_value("SEQUENCINGKIT"), bc = ds_value("BASECALLERVERSION");
+            chem_bk = bk; chem_sk = sk; chem_bc = bc;
             if (!opt.model_file.empty()) {
                 if (ccsx_model_load(opt.model_file.c_str(), &model)) { std::fprintf(stderr, "ccs: %s\n", ccsx_last_error()); return 1; }
                 chem_desc = std::string(model.name) + " (" + opt.model_file + ")";
@@ -908,6 +1024,7 @@ int main(int argc, char **argv)
         if (!opt.dump && !opt.host_only) {
             const int ndev = ccsx_device_count();
             if (ndev <= 0) { std::fprintf(stderr, "ccs: no gfx950 GPU available (this build has no CPU consensus path)\n"); return 1; }
+            if (opt.all_gpus && !opt.fit_model.empty() && ndev > 1) { std::fprintf(stderr, "ccs: --fit-model runs on one GPU: --gpus all names %d\n", ndev); return 2; }
             if (opt.all_gpus) for (int d = 0; d < ndev; ++d) opt.gpus.push_back(d);
             if (opt.gpus.empty()) opt.gpus.push_back(0);
             for (int d : opt.gpus) {
@@ -936,6 +1053,7 @@ int main(int argc, char **argv)
 
         // an exception on any pipeline thread ends the run with a message and exit code 1 (the other threads are drained, not killed)
         std::atomic<int> failed{0};
+        std::atomic<int> enough{0};                           // --fit-max-zmws: the training mode has the ZMWs it wants, the reader stops
         std::mutex err_m;
         std::string err_msg;
         auto fail = [&](const std::string &m) { std::lock_guard<std::mutex> l(err_m); if (!failed.exchange(1)) err_msg = m; };
@@ -1062,7 +1180,7 @@ int main(int argc, char **argv)
                 auto t0 = std::chrono::steady_clock::now();
                 const bool more = !chunk_done && read_raw_chunk(in, *raw);
                 rd_us[0] += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-                if (failed) break;                                  // an engine / writer failure ends the run: stop feeding it
+                if (failed || enough) break;                        // an engine / writer failure ends the run: stop feeding it (or --fit-max-zmws is reached)
                 if (more) pending.push_back(pool.submit([raw] { return decode_chunk(std::shared_ptr<const RawChunk>(raw)); }));
                 while (!pending.empty() && (!more || pending.size() > (size_t)(2 * pool.size() + 4))) {
                     t0 = std::chrono::steady_clock::now();
@@ -1074,7 +1192,7 @@ int main(int argc, char **argv)
                 }
                 if (!more) break;
             }
-            if (!chunk_done) {                                     // (a finished chunk ends inside the next chunk's first ZMW)
+            if (!chunk_done && !enough) {                          // (a finished chunk ends inside the next chunk's first ZMW)
                 flush_zmw();
                 if (have_pbi && (seen_records != pbi_chunk_records || pbi_next_hole != -1 || !chunk_done))
                     throw std::runtime_error(opt.in + ".pbi does not match the BAM (the file ends before the chunk does: stale index?)");
@@ -1192,6 +1310,32 @@ int main(int argc, char **argv)
                         nz / el, nthreads, n_packers, nbatches);
             if (failed) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
             return failed ? 1 : 0;
+        }
+
+        if (!opt.fit_model.empty()) {                         // the training mode: keep the packed batches, iterate over them (fit_model below)
+            std::vector<std::shared_ptr<Batch>> kept;
+            long long have_zmws = 0;
+            std::thread sink([&] {
+                std::shared_ptr<Batch> b;
+                while (to_gpu_q[0]->pop(b)) {
+                    if (b->n <= 0 || enough) continue;
+                    if (opt.fit_max_zmws > 0 && have_zmws + b->n >= opt.fit_max_zmws) {      // the batch's first ZMWs: the arrays are CSR, a prefix is a batch
+                        const int n = (int)(opt.fit_max_zmws - have_zmws);
+                        b->n = n; b->cb.n_zmw = n; b->cb.n_reads = b->read_off[n]; b->cb.n_bases = b->base_off[b->read_off[n]];
+                        enough = 1;
+                    }
+                    have_zmws += b->n;
+                    kept.push_back(b);
+                }
+            });
+            reader.join();
+            for (auto &w : packers) w.join();
+            sink.join();
+            int rc = failed ? 1 : 0;
+            if (failed) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
+            else rc = fit_model(opt, handles[0], model, kept, chem_bk, chem_sk, chem_bc);
+            if (handles[0]) ccsx_destroy(handles[0]);
+            return rc;
         }
 
         // ---- GPU workers: one per device; up to three batches in flight through the asynchronous boundary

@@ -131,6 +131,7 @@ struct Slot {
     DevBuf d_tflag, d_tlen;                       // tandem repeats only (ccsx_extras with tandem_len or a threshold)
     DevBuf d_din_len, d_din_bb;                   // caller-supplied drafts (ccsx_polish_batch): lengths, orientation references
     DevBuf d_hd_wcnt, d_hd_wrec, d_hd_wminp, d_hd_isite, d_hd_zi, d_hd_minp, d_hd_sites;   // heteroduplex finder only (ccsx_hd_batch)
+    DevBuf d_train;                               // model training only (ccsx_train_batch): [n][400] + [n] int64, then [3][n] int32
     DevBuf d_fold;                                // adapter palindromes only (ccsx_fold_request): [4][n] report
     DevBuf d_adapt;                               // adapter screen only (ccsx_adapter_request): [9][n] report + [n][16] hits
     DevBuf d_ctl;                                 // control screen only (ccsx_control_request): the slot's own index, then the [8][n] report
@@ -1556,6 +1557,44 @@ int ccsx_hd_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts,
     HIPTRY(hipStreamSynchronize(h->s_comp));
     if ((rc = launch(h, S)) || (rc = ccsx_sync(h))) return rc;
     if ((rc = enqueue_hd_download(S, out, h->s_comp))) return rc;   // (status: k_hd_verdict's copy of it, written for every ZMW in this mode too)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+// ---- the model training's counts: the fourth seam (include/ccsx.h; DESIGN.md §2 "Model training").  Synchronous, on slot 0 like ccsx_hd_batch, and by the same path.
+int ccsx_train_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, ccsx_train_counts *out)
+{
+    const char *fn = "ccsx_train_batch";
+    if (!h || !b || !drafts || !out) return refuse(fn, "null argument");
+    if (out->reserved != 0) return refuse(fn, "reserved must be 0");
+    if (out->n_zmw != b->n_zmw || !out->match || !out->stay || !out->del || !out->loglik || !out->n_pairs || !out->n_gated || !out->n_bases || !out->status)
+        return refuse(fn, "counts arrays missing, or sized for another batch");
+    if (h->poisoned) { ccsx_set_error("ccsx_train_batch: an earlier submit failed after work had been enqueued; destroy the handle"); return -2; }
+    int rc = ccsx_upload(h, b);
+    if (rc) return rc;
+    Slot &S = h->slot[0];
+    S.mode = CCSX_RUN_TRAIN;                                 // (slot 0 is the training's now: ccsx_run / ccsx_download refuse it until the next ccsx_upload)
+    if ((rc = check_drafts(S, drafts, true))) return rc;
+    const size_t n = (size_t)S.P.n_zmw;
+    if (S.d_train.reserve((n + 1) * ((CCSX_NCTX * CCSX_NOBS * 2 + CCSX_NCTX + 1) * 8 + 3 * 4))) return -2;   // (k_train's launch zeroes it on the stream)
+    S.P.train_tab = (int64_t *)S.d_train.p;
+    S.P.train_ll = S.P.train_tab + n * (CCSX_NCTX * CCSX_NOBS * 2 + CCSX_NCTX);
+    S.P.train_zi = (int32_t *)(S.P.train_ll + n);
+    if ((rc = upload_drafts(S, drafts, h->s_comp))) return rc;
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    if ((rc = launch(h, S)) || (rc = ccsx_sync(h))) return rc;
+    // the ZMW's table is [match 192 | stay 192 | del 16]: three strided copies, then the planes
+    const size_t row = (CCSX_NCTX * CCSX_NOBS * 2 + CCSX_NCTX) * 8;
+    if (n) {
+        HIPTRY(hipMemcpy2DAsync(out->match, 192 * 8, S.P.train_tab, row, 192 * 8, n, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpy2DAsync(out->stay, 192 * 8, S.P.train_tab + 192, row, 192 * 8, n, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpy2DAsync(out->del, 16 * 8, S.P.train_tab + 384, row, 16 * 8, n, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->loglik, S.P.train_ll, n * 8, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->n_pairs, S.P.train_zi, n * 4, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->n_gated, S.P.train_zi + n, n * 4, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->n_bases, S.P.train_zi + 2 * n, n * 4, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->status, S.P.zstat, n * 4, hipMemcpyDeviceToHost, h->s_comp));   // the status after the cascade
+    }
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
 }

@@ -140,6 +140,10 @@ struct KParams {
     const uint32_t *ctl_index; // [CCSX_CONTROL_INDEX_WORDS] the slot's own copy of the control's index (ccsx_control_index_build)
     int32_t ctl_len;           // M
     int32_t ctl_bins;          // k_control's two LDS histograms: diagonal bins each, enough for the longest draft that is aligned (+ 1 empty bin)
+    // ---- model training (ccsx_train_batch; NULL otherwise): DESIGN.md §2 "Model training".  Zeroed on the stream before k_train
+    int64_t *train_tab;        // [n][400] posterior event counts x 2^32: match[16][12], stay[16][12], del[16]
+    int64_t *train_ll;         // [n] log2-likelihood of the counted pairs x 65536, range shift removed
+    int32_t *train_zi;         // [3][n] counted pairs, gated pairs, read bases of the counted pairs
 };
 
 // k_adapter (DESIGN.md §2 "Adapter screen"): draft bases a lane owns per search, its workgroup, the hit keys one pass buffers in LDS and the bitmaps' LDS bound
@@ -179,8 +183,9 @@ static inline __host__ __device__ uint32_t ccsx_fmix32(uint32_t h) { h ^= h >> 1
 #define CCSX_HD_IMAX 49                          // rows of a segment the pileup aligns: template columns (<= 29) + min_indel - 1 (<= 20)
 
 // which stages ccsx_launch_all enqueues: the fused path, the draft stage alone (ccsx_draft_batch), alignment cascade + polish on caller-supplied drafts, or
-// alignment cascade + the heteroduplex finder on caller-supplied drafts (ccsx_hd_batch)
-enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2, CCSX_RUN_HD = 3 };
+// alignment cascade + the heteroduplex finder on caller-supplied drafts (ccsx_hd_batch), or alignment cascade + the training counts on caller-supplied drafts
+// (ccsx_train_batch)
+enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2, CCSX_RUN_HD = 3, CCSX_RUN_TRAIN = 4 };
 
 // The stage events of a batch (Slot::ev, timing enabled), in the values they have always had — in time order POLISH_START lies between DRAFT_STAGE_DONE and
 // POLISH_DONE.  ccsx_launch_all records each of them exactly once on every path, in time order, so that ccsx_timings may read all seven after any run.
@@ -213,6 +218,7 @@ struct ccsx_launch_queues {
     hipEvent_t *ev, *ev_aux;
 };
 const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode);   // NULL, or the name of the launch that failed
+const char *ccsx_train_launch(const KParams &P, hipStream_t st, long long max_blocks);   // ccsx_train.hip: the count buffers zeroed + k_train; NULL, or what failed
 int ccsx_kernel_is_experiment();         // built with -DCCSX_EXPERIMENT (timing studies: wrong results)
 const char *ccsx_kernel_build_flags();   // "" for a product build; the experiment switches this translation unit was compiled with otherwise
 int ccsx_polish_lds(int max_reads, int *obs_bytes, int *gb_floats);

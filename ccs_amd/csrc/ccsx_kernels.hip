@@ -4477,14 +4477,14 @@ struct Schedule {
     const LaunchSwitches &sw;
     const hipStream_t st;         // the draft stream: everything but the polish stage and what runs beside it on q.aux
     const bool second_stream;     // q.aux and its events are there
-    // CCSX_RUN_POLISH (the polish seam), CCSX_RUN_HD (ccsx_hd_batch: the polish seam's first half): the drafts are the caller's — k_draft_in instead of the
-    // generators, one alignment round whose outcome is final (P.opts.no_fallback_draft is set for such a run)
+    // CCSX_RUN_POLISH (the polish seam), CCSX_RUN_HD (ccsx_hd_batch: the polish seam's first half), CCSX_RUN_TRAIN (ccsx_train_batch: the same first half): the
+    // drafts are the caller's — k_draft_in instead of the generators, one alignment round whose outcome is final (P.opts.no_fallback_draft is set for such a run)
     const bool caller_drafts;
     const size_t lds_read;        // the packed read; k_poa_init: the lengths of up to 255 passes
     const char *failed = nullptr;
 
     Schedule(const KParams &P_, const ccsx_launch_queues &q_, int mode, const LaunchSwitches &sw_)
-        : P(P_), q(q_), sw(sw_), st(q_.draft), second_stream(q_.aux && q_.ev_aux), caller_drafts(mode == CCSX_RUN_POLISH || mode == CCSX_RUN_HD),
+        : P(P_), q(q_), sw(sw_), st(q_.draft), second_stream(q_.aux && q_.ev_aux), caller_drafts(mode == CCSX_RUN_POLISH || mode == CCSX_RUN_HD || mode == CCSX_RUN_TRAIN),
           lds_read((((size_t)P_.maxL_max + 15) / 16) * 4 + 64 + 4 * (CCSX_MAX_PASSES + 1)) {}
 
     // ---- every status is captured: `failed` is the name of the first launch or call that failed (ccsx_api.cpp reports it)
@@ -4510,7 +4510,7 @@ struct Schedule {
     // events of the stages it leaves out back to back on the draft stream (close_timing): those stages then take no time.
     // Who records what: START and TABLES_DONE tables(); DRAFT_DONE draft_stage(), in its pass 0; DRAFT_STAGE_DONE, POLISH_START, POLISH_DONE and END
     // polish_stage() in a full run, close_timing alone in the draft seam; in ccsx_hd_batch close_timing the first two, hd_finder(true) POLISH_DONE,
-    // ccsx_launch_all END.
+    // ccsx_launch_all END; in ccsx_train_batch close_timing the first two, train_counts() POLISH_DONE and END.
     void stage_event(ccsx_stage_event k, hipStream_t s) { if (q.ev) record(q.ev[k], s); }
     void close_timing(ccsx_stage_event from, ccsx_stage_event to)
     {
@@ -4647,6 +4647,17 @@ struct Schedule {
         launch("k_hd_verdict", k_hd_verdict, dim3(P.n_zmw), dim3(64), 0, st, P);
     }
 
+    // The training counts in place of the polish stage (ccsx_train_batch), on the draft stream: the slot's count buffers zeroed, then k_train (ccsx_train.hip) over
+    // the window slots, in the polish stage's launch pieces.  Nothing follows it: POLISH_DONE and END are recorded back to back.
+    void train_counts()
+    {
+        const char *what = ccsx_train_launch(P, st, sw.max_blocks);
+        if (what && !failed) failed = what;
+        trace_sync(st, "k_train");
+        stage_event(CCSX_EV_POLISH_DONE, st);
+        stage_event(CCSX_EV_END, st);
+    }
+
     // Two-stage queue of docs/img/ccs-impl.png ("Draft Stage" -> queue -> "Polish Stage"): the draft stage (tables, POA, alignment cascade, accounting, screens)
     // is enqueued on the draft stream, the polish stage (polish, kinetics, stitch) on the polish stream, which waits for the draft stage's last kernel through
     // CCSX_EV_DRAFT_STAGE_DONE.  With two different streams the draft stage of batch k+1 runs UNDER the polish stage of batch k (the register-only one-wave POA
@@ -4687,7 +4698,7 @@ struct Schedule {
 
 }  // namespace
 
-// The four run modes share one schedule and leave it at three places.  No stage synchronises with the host.
+// The five run modes share one schedule and leave it at four places.  No stage synchronises with the host.
 const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode)
 {
     static const LaunchSwitches switches;
@@ -4714,6 +4725,11 @@ const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int m
         s.hd_finder(true);
         s.trace_sync(q.draft, "k_hd");
         s.stage_event(CCSX_EV_END, q.draft);
+        return s.failed;
+    }
+    if (mode == CCSX_RUN_TRAIN) {                           // the training counts instead of the polish stage, on the same stream
+        s.close_timing(CCSX_EV_DRAFT_STAGE_DONE, CCSX_EV_POLISH_START);
+        s.train_counts();
         return s.failed;
     }
     s.polish_stage();

@@ -572,6 +572,61 @@ int         ccsx_inflate_wait(ccsx_inflater f, ccsx_ticket ticket);
 int         ccsx_inflate_blocks_host(const uint8_t *src, int64_t src_len, const ccsx_deflate_block *blocks, int32_t n_blocks,
                                      uint8_t *dst, int64_t dst_len, int32_t *status);
 
+/* ---- model training: Baum-Welch counts on the device, the M-step on the host (the rule: DESIGN.md §2 "Model training", its own version ccsx_train_rule_version;
+ * no result of the consensus changes).  A pair is (window of a ZMW, pass): the window k_polish would cut on the caller's draft, the pass's segment between the
+ * window's two entry rows.  Per pair the FULL forward and backward matrices are filled (no band), the pair is gated (alpha / beta agreement, opts.min_zscore), and
+ * the posterior probability of every match, stay and deletion event of the window's core columns is added, in 2^-CCSX_TRAIN_FRAC fixed point, to the ZMW's
+ * tables.  Every sum is an integer sum: the tables do not depend on the order or grouping in which pairs ran, and per-ZMW tables of several calls add exactly.
+ *   ccsx_train_batch      the fourth seam beside ccsx_draft_batch, ccsx_polish_batch and ccsx_hd_batch: synchronous, slot 0.  On the caller's drafts — the truth
+ *                         the passes are measured against: known templates, or a consensus the caller trusts — it runs the polish seam's alignment cascade and
+ *                         window map, then k_train in place of the polish.  A ZMW whose status after the cascade is not SUCCESS contributes zeros.  Afterwards
+ *                         ccsx_stage_draft / ccsx_stage_windows / ccsx_stage_align report what it used; ccsx_run and ccsx_download refuse slot 0 until the next
+ *                         ccsx_upload.  A null argument, nonzero `reserved`, counts sized for another batch or a poisoned handle are errors of the call: nothing
+ *                         is enqueued.  The count buffers (3.2 KB per ZMW) are reserved by the first call; without one nothing is reserved, launched or copied.
+ *   ccsx_train_pair_host  the same rule for ONE pair on the calling thread, no device (train_core.h: the code the kernel shares): the reference of the tests.  The
+ *                         template is given in the pass's orientation (the caller reverse-complements it and swaps the flanks for a reverse-strand pass), J =
+ *                         1 .. CCSX_JMAX columns, core [cs, ce), left_flank 0 .. 3 or 4 = none; obs: n = 0 .. CCSX_IMAX codes 0 .. 11.  Adds to match[192],
+ *                         stay[192], del[16], *loglik; returns 1 counted, 0 gated, < 0 bad argument (nothing added).
+ *   stay[k][o]            holds both stay events of context k: outcome base = the context's current base is a branch, any other base a stick.
+ * The fitter is the M-step, host only.  Emissions: a row's counts plus `pseudo` per cell, normalised; a row with fewer than min_events events keeps the starting
+ * row.  Transitions: each ZMW's row of context k goes into the bin of clamp(snr[cur(k)], start.snr_lo, start.snr_hi) out of snr_bins equal bins over the start
+ * model's range; per bin with at least min_events matches r_move = N_move / N_match (the model's w) for branch, stick and deletion, fitted at the bins' CENTRES by
+ * least squares weighted with N_match, polynomial degree min(degree, populated bins - 1); a context without a populated bin keeps its polynomials.  The fitted
+ * snr_lo / snr_hi are the centres of the first and last populated bin of any context (equal when one bin is populated; a start model with snr_lo == snr_hi is
+ * accepted: every row is then in bin 0, at that point).  All accumulation is integer: the fitted model is a pure function of the
+ * multiset of (counts row, SNR) pairs, whatever the order or grouping of ccsx_fitter_add.  ccsx_fitter_finish may be called more than once.                       */
+#define CCSX_TRAIN_FRAC 32
+typedef struct ccsx_train_counts {
+    int32_t  n_zmw, reserved;          /* reserved must be 0 */
+    int64_t *match, *stay;             /* [n_zmw][16][12] events x 2^CCSX_TRAIN_FRAC */
+    int64_t *del;                      /* [n_zmw][16] */
+    int64_t *loglik;                   /* [n_zmw] log2-likelihood of the counted pairs x 65536, range shift removed */
+    int32_t *n_pairs, *n_gated, *n_bases, *status;   /* [n_zmw]; status = enum ccsx_status after the cascade (as ccsx_hd_report.status) */
+} ccsx_train_counts;
+int         ccsx_train_rule_version(void);
+int         ccsx_train_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *drafts, ccsx_train_counts *out);
+int         ccsx_train_pair_host(const ccsx_model *m, const float snr[4], const uint8_t *tpl, int32_t J, int32_t left_flank, int32_t cs, int32_t ce,
+                                 const uint8_t *obs, int32_t n, float min_zscore, int64_t match[192], int64_t stay[192], int64_t del[16], int64_t *loglik);
+typedef struct ccsx_fit_opts {
+    int32_t degree;                    /* polynomial degree of the transition weights, 0 .. 3 (default 1) */
+    int32_t snr_bins;                  /* 4 .. 256 (default 64) */
+    double  min_events;                /* events a row / matches a bin needs (default 200) */
+    double  pseudo;                    /* added to every emission cell (default 0.5) */
+} ccsx_fit_opts;
+typedef struct ccsx_fit_report {
+    int64_t pairs, gated, bases;       /* sums over everything added */
+    double  loglik_per_base;           /* log2-likelihood per read base of the counted pairs, under the model the counts were made with */
+    int32_t contexts_kept;             /* contexts whose match-emission row kept its starting values (fewer than min_events matches) */
+    float   snr_lo, snr_hi;            /* of the fitted model */
+    double  max_change;                /* largest |new - old| of any emission probability and of any transition weight at a populated bin's centre */
+} ccsx_fit_report;
+typedef struct ccsx_fitter_s *ccsx_fitter;
+void        ccsx_fit_opts_default(ccsx_fit_opts *o);
+int         ccsx_fitter_create(const ccsx_model *start, const ccsx_fit_opts *o, ccsx_fitter *out);   /* o NULL = the defaults */
+int         ccsx_fitter_add(ccsx_fitter f, const ccsx_train_counts *c, const float *snr);            /* snr: [n_zmw][4] */
+int         ccsx_fitter_finish(ccsx_fitter f, ccsx_model *out, ccsx_fit_report *rep);                /* rep may be NULL */
+int         ccsx_fitter_destroy(ccsx_fitter f);
+
 /* deterministic synthetic subread generator (SURVEY.md §8d / BASELINE.md §3).  Caller frees with ccsx_synth_free */
 typedef struct ccsx_synth {
     ccsx_batch batch;            /* arrays are owned by this object                             */
