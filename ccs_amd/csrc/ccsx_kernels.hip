@@ -2302,10 +2302,11 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     __shared__ int sI[PW_MAXREADS], sGoff[PW_MAXREADS], sBoff[PW_MAXREADS];   // segment length; where gamma / beta (i, j) = sGB[off + i * pitch + j] of the chunk's reads start
     __shared__ int sBand[PW_MAXREADS];                       // the read's band and layout (SPEC v6): pitch | rowsz << 8 | bw << 16 | (dlo + 128) << 24
     __shared__ unsigned sDirty[PW_MAXREADS];                 // window-relative pile-up dirty bits of each read
-    __shared__ uint8_t sStrand[PW_MAXREADS], sValid[PW_MAXREADS];
+    __shared__ uint8_t sStrand[PW_MAXREADS], sRend[PW_MAXREADS];   // sRend[first read of a chunk] = the chunk's end (see plan_chunks)
     __shared__ unsigned sZdrop[(CCSX_MAX_PASSES + 32) / 32]; // z-score gate, one BIT per pass (all groups; a group is one word): decided on the draft window (round 0), then kept
     __shared__ float sBase[PW_MAXREADS], sB00[PW_MAXREADS];   // alpha(I,J) / beta(0,0) of the chunk's reads (the fill's two halves meet here)
-    __shared__ short2 sTask[PW_MAXREADS];                    // fill tasks: (read A, read B or -1)
+    __shared__ short2 sTask[PW_MAXREADS];                    // .x: the fill tasks of a chunk (a read each: long units, then quad members), listed from the chunk's first read on;
+                                                             // .y at a chunk's first read: its long units | quad members << 8
     __shared__ int sDeltaI[256];                             // fixed-point sums of the per-read gains; converted in place to float
     float *sDelta = (float *)sDeltaI;                        // (each thread converts its own entry after the scoring barrier)
     __shared__ uint8_t sMvalid[256];
@@ -2509,6 +2510,47 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     if (tid == 0) { sCtl[0] = xr_c0; sCtl[1] = xr_c1; sCtl[2] = xr_c2; sCtl[7] = xr_c7; }
     __syncthreads();
 #endif
+    // ---- the chunk plan of the resident group (lane = read), made by ONE wave, once per round and after every reload of a group inside a round: its inputs are
+    // sI[], J, S and the LDS budget, all known when the round's J is.  The greedy walk — a chunk takes reads while their gamma/beta fit the budget, at most
+    // PWCH of them — runs over all chunks by prefix sum and ballots and leaves, per read: sGoff / sBoff / sBand (sGoff = -1: no segment); per chunk, at its first
+    // read rb: the end sRend[rb], the fill tasks sTask[rb ..].x (a read is in exactly one chunk, so the slices never overlap) and their counts in sTask[rb].y.
+    // The barrier that opens every chunk publishes the plan; the other waves only read it.  (Until round 6 every wave recomputed the plan of every chunk.)
+    // sGoff / sBoff hold the segment start / the untrimmed length until here: the caller has a barrier between load_obs and the plan.
+    auto plan_chunks = [&](int ng, int J, int S) {
+        int r = lane;
+        asm volatile("" : "+v"(r));                          // (opaque: what the plan derives from the lane is formed here, not hoisted out of the rounds into registers that spill)
+        const int n0 = r < ng ? sI[r] : -1;
+        const FillBand fb = fill_band_of(n0 >= 0 ? n0 : 0, J, S);
+        const int need0 = (2 * n0 + 3) * fb.rowsz;                       // gamma rows 0..n, beta rows 0..n+1 (row n+1: zeros)
+        // a short segment whose band leaves a lane time to change rows (see the quad sweep) shares a wave with three others; the rest — more than
+        // 31 bases, or |I - J| >= 5 — takes a wave of its own (rare)
+        const bool qd0 = n0 <= 31 && fb.bw <= FILL16_MAXBW;
+        const unsigned long long lower = (1ull << r) - 1ull;
+        for (int rb = 0; rb < ng;) {
+            const bool cand = n0 >= 0 && r >= rb;
+            const int need = cand ? need0 : 0;
+            const int incl = wave_scan_add_i32(need);
+            const unsigned long long bcand = __ballot(cand);
+            const unsigned long long over = __ballot(cand && (incl > GB_FLOATS || (PWCH > 0 && __popcll(bcand & lower) >= PWCH)));
+            const int rend_ = over ? (int)__ffsll((long long)over) - 1 : ng;                 // the first read that does not fit any more
+            if (r >= rb && r < rend_) {
+                if (!cand) sGoff[r] = -1;
+                else {
+                    const int off = incl - need;
+                    sGoff[r] = off + fb.org; sBoff[r] = off + (n0 + 1) * fb.rowsz + fb.org;
+                    sBand[r] = fb.pitch | (fb.rowsz << 8) | (fb.bw << 16) | ((fb.dlo + 128) << 24);
+                }
+            }
+            const bool inchunk = cand && r < rend_;
+            const bool qd = inchunk && qd0, lng = inchunk && !qd0;
+            const unsigned long long bl = __ballot(lng), bs = __ballot(qd);
+            const int nl_ = __popcll(bl);
+            if (lng) sTask[rb + __popcll(bl & lower)].x = (short)r;
+            if (qd) sTask[rb + nl_ + __popcll(bs & lower)].x = (short)r;
+            if (r == rb) { sRend[rb] = (uint8_t)rend_; sTask[rb].y = (short)(nl_ | (__popcll(bs) << 8)); }
+            rb = rfl(rend_);
+        }
+    };
     int iters = 0, nonconv = 0;
     unsigned skmask = 0;                                     // positions skipped in the current round (wave-uniform)
     int nvalid_last = 0, nvfull_last = 0;                    // usable reads of the last round: all / full-length passes only
@@ -2523,6 +2565,9 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                                                              // lane-to-lane address stride is S - 1, which must be odd to be bank-conflict free
         if (tid < J) sT[1][tid] = (uint8_t)(3 - sT[0][J - 1 - tid]);
         __syncthreads();
+        // the chunk plan of the round, when the round's first group is the one in LDS (nearly always: a ZMW of more than PW_MAXREADS passes ends a round on its
+        // last group and plans after the reload below).  The last wave: it has no share in the z-score sums of round 0
+        if (wave == (PWT / 64) - 1 && resident == 0) plan_chunks(nreads < PW_MAXREADS ? nreads : PW_MAXREADS, J, S);
         auto tbase = [&](int sd, int j) -> int { return (int)sT[sd][j]; };   // base j of the window template on strand sd
         const int lfr = (rf < 4) ? 3 - rf : 4;
         // z-score expectation of the window template on each strand, summed in column order (SPEC); the gate is decided in round 0
@@ -2615,41 +2660,14 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
             const int tf = load_meta(g0, ng);
             load_obs(ng, tf);
             resident = g0;
+            __syncthreads();                                 // (load_obs read the segment starts and untrimmed lengths that the plan overwrites)
+            if (wave == (PWT / 64) - 1) plan_chunks(ng, J, S);
         }
         int rbeg = 0;
         while (rbeg < ng) {
-            __syncthreads();
-            int rend, nlong, nshort;
-            {   // lane = read: the greedy plan by prefix sum and ballots.  EVERY wave computes it (identical values, benign identical
-                // LDS writes): a wave then reads only what it wrote itself, so no barrier is needed before the fill
-                const int r = lane;
-                const int n = (r >= rbeg && r < ng) ? sI[r] : -1;
-                const bool cand = n >= 0;
-                const FillBand fb = fill_band_of(cand ? n : 0, J, S);
-                const int need = cand ? (2 * n + 3) * fb.rowsz : 0;          // gamma rows 0..n, beta rows 0..n+1 (row n+1: zeros)
-                const int incl = wave_scan_add_i32(need);
-                const unsigned long long bcand = __ballot(cand);
-                const unsigned long long over = __ballot(cand && (incl > GB_FLOATS || (PWCH > 0 && __popcll(bcand & ((1ull << lane) - 1ull)) >= PWCH)));
-                const int rend_ = over ? (int)__ffsll((long long)over) - 1 : ng;             // the first read that does not fit any more
-                if (r >= rbeg && r < rend_) {
-                    if (!cand) { sGoff[r] = -1; sValid[r] = 0; }
-                    else {
-                        const int off = incl - need;
-                        sGoff[r] = off + fb.org; sBoff[r] = off + (n + 1) * fb.rowsz + fb.org;
-                        sBand[r] = fb.pitch | (fb.rowsz << 8) | (fb.bw << 16) | ((fb.dlo + 128) << 24);
-                    }
-                }
-                const bool inchunk = cand && r < rend_;
-                // a short segment whose band leaves a lane time to change rows (see the quad sweep) shares a wave with three others; the rest — more than
-                // 31 bases, or |I - J| >= 5 — takes a wave of its own (rare)
-                const bool qd = inchunk && n <= 31 && fb.bw <= FILL16_MAXBW, lng = inchunk && !qd;
-                const unsigned long long bl = __ballot(lng), bs = __ballot(qd);
-                const unsigned long long lower = (1ull << lane) - 1ull;
-                const int nl_ = __popcll(bl);
-                if (lng) sTask[__popcll(bl & lower)] = make_short2((short)r, (short)-1);
-                if (qd) sTask[nl_ + __popcll(bs & lower)] = make_short2((short)r, (short)0);
-                rend = rfl(rend_); nlong = rfl(nl_); nshort = rfl(__popcll(bs));
-            }
+            __syncthreads();                                 // (publishes the chunk plan, too)
+            const int rend = rfl((int)sRend[rbeg]), ntasks = rfl((int)sTask[rbeg].y), nlong = ntasks & 255, nshort = ntasks >> 8;
+            const short2 *const cTask = sTask + rbeg;        // the chunk's fill tasks
             PHASE(2);
             // ---- A1/A2: fill (SPEC v6: on the band of diagonals only).  Work units, one wave each, every unit ONE anti-diagonal sweep:
             //   quad units — FOUR short reads per wave, one per 16-lane DPP row, alpha and beta of a quad on different waves;
@@ -2679,7 +2697,7 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                 const int g4 = lane >> 4, l16 = lane & 15;
                 const int qi = rpq * quad + g4;
                 const bool have = g4 < rpq && qi < nshort;
-                const int myr = sTask[nlong + (have ? qi : rpq * quad)].x;
+                const int myr = cTask[nlong + (have ? qi : rpq * quad)].x;
                 const int I = sI[myr], sd = sStrand[myr], band = sBand[myr];
                 const int pitch = band & 255, rowsz = (band >> 8) & 255, bdlo = (int)((unsigned)band >> 24) - 128, bdhi = bdlo + ((band >> 16) & 255) - 1;
                 const int row0 = l16, row1 = l16 + 16;
@@ -2688,7 +2706,7 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                 const int jlo1 = (row1 + bdlo > 0) ? row1 + bdlo : 0, jhi1 = (row1 + bdhi < J) ? row1 + bdhi : J;
                 int Tmax = 0;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { const int iq = rfl(sI[rfl((int)sTask[nlong + ((q < rpq && rpq * quad + q < nshort) ? rpq * quad + q : rpq * quad)].x)]); Tmax = iq > Tmax ? iq : Tmax; }
+                for (int q = 0; q < 4; ++q) { const int iq = rfl(sI[rfl((int)cTask[nlong + ((q < rpq && rpq * quad + q < nshort) ? rpq * quad + q : rpq * quad)].x)]); Tmax = iq > Tmax ? iq : Tmax; }
                 Tmax += J;
                 const int NEVER = 1 << 20;
 #define LDPR(ROWP, OFF) (*(const float2 *)((ROWP) + (OFF)))
@@ -2777,7 +2795,7 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
               } else {
                 // ---- long unit: one read per wave, lane = row, the plain loop (alpha-only or beta-only)
                 const int tk = (fu - 2 * nquad) >> 1, mode = 1 + ((fu - 2 * nquad) & 1);      // 1: alpha only, 2: beta only
-                const int myr = rfl((int)sTask[tk].x);
+                const int myr = rfl((int)cTask[tk].x);
                 const int row = lane;
                 const int I = rfl(sI[myr]);
                 const int Tmax = I + J;
@@ -2856,7 +2874,9 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
             }
             __syncthreads();
             PHASE(3);
-            // read validity (lane = read; every wave computes the same values): alpha/beta agreement, the z-score gate of round 0
+            // read validity (lane = read; every wave computes the same values): alpha/beta agreement, the z-score gate of round 0.  The two logarithms are repeated
+            // in every wave on purpose: taking them once, in the fill unit's lane that holds the value, and loading them here was measured at -0.2 ms of 291 alone and
+            // + 1.8 ms on top of the once-per-round chunk plan (profiles/polish_once_per_round.txt): nothing
             int vOk = 0; float vLa = 0.0f;
             if (lane >= rbeg && lane < rend && sGoff[lane] >= 0) {
                 const float aIJ = sBase[lane], b00 = sB00[lane];
@@ -3044,13 +3064,16 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         // ---- A5: greedy selection (wave 0; lane l owns m = l, l+64, l+128, l+192 which share position l&31)
         if (wave == 0) {
             int candmask = 0;
-            for (int k = 0; k < 4; ++k) { int m = lane + 64 * k; if (sMvalid[m] && sDelta[m] > MUT_EPS) candmask |= 1 << k; }
+            float dk[4];                                     // the lane's four gains stay in registers over the loop
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int m = lane + 64 * k; dk[k] = sDelta[m]; if (sMvalid[m] && dk[k] > MUT_EPS) candmask |= 1 << k; }
             int Jn = J, nacc = 0;
             unsigned accpos = 0;                             // positions of the accepted mutations (at most one per position: they are >= MUT_SEP apart)
             int accm = 0;                                    // lane c (< 32): the mutation accepted at position c
             for (;;) {
                 float bd = -1.0f; int bm = 1 << 20;
-                for (int k = 0; k < 4; ++k) if (candmask & (1 << k)) { int m = lane + 64 * k; float dv = sDelta[m]; if (dv > bd) { bd = dv; bm = m; } }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) if (candmask & (1 << k)) { const int m = lane + 64 * k; const float dv = dk[k]; if (dv > bd) { bd = dv; bm = m; } }
                 const float wmax = wave_max_f32(bd);
                 if (!(wmax > 0.0f)) break;
                 const int msel = wave_min_i32((bd == wmax) ? bm : (1 << 20));
@@ -3142,14 +3165,17 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         if ((skmask >> c) & 1u) p = sPskip[c];              // skipped by the candidate filter: error probability from the pile-up margin
         else {
             float s = (((unsigned)sCtl[7] >> c) & 1u) ? sPskip[c] : 0.0f;   // quiet homopolymer position: its untested mutations
-            for (int sl = 0; sl < 8; ++sl) {
-                int m = sl * 32 + c;
-                if (sMvalid[m]) s = s + sDelta[m];
-            }
-            if (c == J - 1) for (int sl = 4; sl < 8; ++sl) {
-                int m = sl * 32 + J;
-                if (sMvalid[m]) s = s + sDelta[m];
-            }
+            // all loads of the position first, then the sum in the SPEC's slot order: a term that is not enumerated enters as + 0.0f, which leaves the
+            // non-negative finite s as it is (a chain of eight to twelve dependent load pairs before)
+            const bool lastc = c == J - 1;                   // the insertions after the last column follow it
+            const int ce_ = lastc ? J : c;
+            float dv[12]; bool mv[12];
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) { const int m = sl * 32 + c; mv[sl] = sMvalid[m] != 0; dv[sl] = sDelta[m]; }
+#pragma unroll
+            for (int sl = 4; sl < 8; ++sl) { const int m = sl * 32 + ce_; mv[sl + 4] = lastc && sMvalid[m] != 0; dv[sl + 4] = sDelta[m]; }
+#pragma unroll
+            for (int q = 0; q < 12; ++q) s = s + (mv[q] ? dv[q] : 0.0f);
             p = __fdiv_rn(s, 1.0f + s);
         }
         if (any_tract) {
