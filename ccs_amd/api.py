@@ -24,6 +24,7 @@ BAND, MAXPRED, WIN_CORE, WIN_OVERHANG, JMAX, IMAX, MAX_ITER, NCTX, NOBS = 64, 7,
 STATUS_NAMES = {
     0: "SUCCESS", 1: "TOO_FEW_PASSES", 2: "DRAFT_FAILURE", 3: "TOO_MANY_UNUSABLE", 4: "NON_CONVERGENT",
     5: "TOO_SHORT", 6: "TOO_LONG", 7: "LOW_RQ", 8: "EMPTY_WINDOW", 9: "CAPACITY", 10: "HETERODUPLEX",
+    11: "DRAFT_TOO_DIFFERENT", 12: "INSUFFICIENT_SPANS", 13: "COVERAGE_DROPS", 14: "READS_FAILED_POLISHING",
 }
 HETERODUPLEX = 10   # CCSX_HETERODUPLEX: a ZMW the heteroduplex split kept out of the polish stage (ccsx_hd_request.split)
 
@@ -341,6 +342,46 @@ def _control_request(seq: ControlSeq, opts: "ControlOpts | None", crep: CControl
     return CControlRequest(C.pointer(seq), C.pointer(o), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (seq, o)
 
 
+# ---- coverage screen (include/ccsx.h ccsx_coverage_*; DESIGN.md §2 "Coverage rule")
+COVERAGE_UNTESTED, COVERAGE_NONE, COVERAGE_DRAFT_TOO_DIFFERENT, COVERAGE_INSUFFICIENT_SPANS, COVERAGE_COVERAGE_DROPS, COVERAGE_READS_FAILED_POLISHING = range(6)
+COVERAGE_GATE_ALL = 0x3c                         # every gate bit: verdict v = 2 .. 5 -> status 9 + v
+DRAFT_TOO_DIFFERENT, INSUFFICIENT_SPANS, COVERAGE_DROPS, READS_FAILED_POLISHING = 11, 12, 13, 14   # CCSX_* statuses of the gate
+
+
+class CoverageOpts(C.Structure):
+    _fields_ = [("drop_percent", C.c_int32), ("block", C.c_int32), ("min_spans", C.c_int32), ("max_lost_percent", C.c_int32)]
+
+
+class CCoverageReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in ("verdict", "np_aligned", "spans", "cov_max", "clean_min", "drop_window", "drop_windows",
+                                                                              "reach_sum", "used_sum", "used_min")]
+
+
+class CCoverageRequest(C.Structure):
+    """ccsx_coverage_request: the coverage screen in the fused path (ccsx_consensus_requests / ccsx_submit_requests)"""
+    _fields_ = [("opts", C.POINTER(CoverageOpts)), ("report", C.POINTER(CCoverageReport)), ("gate", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
+def coverage_opts_default() -> CoverageOpts:
+    o = CoverageOpts()
+    lib().ccsx_coverage_opts_default(C.byref(o))
+    return o
+
+
+class CoverageReport(_PlaneReport):
+    """ccsx_coverage_report: per ZMW the verdict (COVERAGE_*) and the counts behind it.  PRE: the planes known before the polish, POST: those after it"""
+    PRE = ("verdict", "np_aligned", "spans", "cov_max", "clean_min", "drop_window", "drop_windows")
+    POST = ("reach_sum", "used_sum", "used_min")
+    FIELDS = PRE + POST
+    PLANES = _int_planes(*FIELDS)
+    CSTRUCT = CCoverageReport
+
+
+def _coverage_request(opts: "CoverageOpts | None", gate: int, crep: CCoverageReport):
+    o = opts if opts is not None else coverage_opts_default()
+    return CCoverageRequest(C.pointer(o), C.pointer(crep), int(gate), (C.c_int32 * 2)(0, 0)), o
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -418,6 +459,12 @@ def unrle(pairs: np.ndarray) -> np.ndarray:
 class CExtras(C.Structure):
     """ccsx_extras: optional outputs of the fused path (include/ccsx.h)"""
     _fields_ = [("pile", C.POINTER(CPileup)), ("tandem_len", C.POINTER(C.c_int32)), ("min_tandem_repeat_length", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CRequests(C.Structure):
+    """ccsx_requests: every optional request of the fused path (ccsx_consensus_requests / ccsx_submit_requests); any member may be NULL"""
+    _fields_ = [("ex", C.POINTER(CExtras)), ("fold", C.POINTER(CFoldRequest)), ("adapters", C.POINTER(CAdapterRequest)), ("control", C.POINTER(CControlRequest)),
+                ("coverage", C.POINTER(CCoverageRequest)), ("reserved", C.c_void_p * 3)]
 
 
 def tandem_buffer(n_zmw: int, pinned: bool = False) -> np.ndarray:
@@ -595,6 +642,7 @@ EXPORTS = [
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
     "ccsx_adapter_opts_default", "ccsx_adapter_rule_version", "ccsx_adapter_set_default", "ccsx_consensus_screen", "ccsx_submit_screen",
     "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
+    "ccsx_coverage_opts_default", "ccsx_coverage_rule_version", "ccsx_consensus_requests", "ccsx_submit_requests",
     "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
     "ccsx_inflate_blocks_host",
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
@@ -679,6 +727,10 @@ def lib() -> C.CDLL:
                                              C.POINTER(CControlRequest)]
         L.ccsx_submit_control.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest), C.POINTER(CAdapterRequest),
                                           C.POINTER(CControlRequest), C.POINTER(C.c_int64)]
+        L.ccsx_coverage_opts_default.restype = None
+        L.ccsx_coverage_opts_default.argtypes = [C.POINTER(CoverageOpts)]
+        L.ccsx_consensus_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests)]
+        L.ccsx_submit_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(C.c_int64)]
         _call = [C.POINTER(C.c_uint8), C.c_int64, C.POINTER(DeflateBlock), C.c_int32, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int32)]
         L.ccsx_inflater_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
         L.ccsx_inflater_destroy.argtypes = [C.c_void_p]
@@ -1043,11 +1095,12 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
               hd: "HdReport | None" = None, hd_opts: "HdOpts | None" = None, hd_split: bool = False,
               fold: "FoldReport | None" = None, fold_opts: "FoldOpts | None" = None,
               adapters: "AdapterReport | None" = None, adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None,
-              control: "ControlReport | None" = None, control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None):
+              control: "ControlReport | None" = None, control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None,
+              coverage: "CoverageReport | None" = None, coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, via_requests: bool = False):
     """The ctypes side of what one fused run is asked for beside the consensus: (CExtras, CHdRequest, CFoldRequest, CAdapterRequest, CControlRequest, keep), each
     request None where its report (for the extras: all of pileup, tandem and the threshold) is.  keep owns every array and struct the requests point to: it
-    must outlive the call, or the ticket"""
-    keep = [pileup, tandem, hd, fold, adapters, control]
+    must outlive the call, or the ticket.  With a coverage report, or via_requests, keep ends with the CRequests that carries them all (ccsx_*_requests)"""
+    keep = [pileup, tandem, hd, fold, adapters, control, coverage]
 
     def own(x):
         keep.append(x)
@@ -1064,6 +1117,14 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
         aq = own(_adapter_request(adapter_set, adapter_opts, own(adapters.c_struct())))[0]
     if control is not None:
         cq = own(_control_request(control_seq, control_opts, own(control.c_struct())))[0]
+    if coverage is not None or via_requests:
+        if hq is not None:
+            raise ValueError("the heteroduplex request goes through ccsx_*_hd, not through ccsx_requests")
+        vq = own(_coverage_request(coverage_opts, coverage_gate, own(coverage.c_struct())))[0] if coverage is not None else None
+
+        def p(x):
+            return C.pointer(x) if x is not None else None
+        keep.append(CRequests(p(ex), p(fq), p(aq), p(cq), p(vq), (C.c_void_p * 3)()))
     return ex, hq, fq, aq, cq, keep
 
 
@@ -1086,9 +1147,12 @@ class Handle:
 
     def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
-        ccsx_*_hd with a heteroduplex request, which combines with none of the screens, else ccsx_*_control (NULL: not asked for).  Returns the C structs"""
+        ccsx_*_hd with a heteroduplex request, which combines with none of the screens, ccsx_*_requests when _requests made a CRequests (a coverage request,
+        or via_requests), else ccsx_*_control (NULL: not asked for).  Returns the C structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
+        if _keep and isinstance(_keep[-1], CRequests):
+            name, args = f"ccsx_{form}_requests", (_keep[-1],)
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
         return cb, cr
@@ -1192,6 +1256,24 @@ class Handle:
                                                        control=crep, control_seq=control, control_opts=opts))
         return res, crep, frep, arep, tl, pile
 
+    # ---- the coverage screen (ccsx_consensus_requests), alone or with the draft detectors and the optional outputs of ccsx_extras
+    def consensus_coverage(self, batch: Batch, opts: "CoverageOpts | None" = None, gate: int = 0, control: "ControlSeq | None" = None,
+                           control_opts: "ControlOpts | None" = None, fold: "bool | FoldOpts" = False, adapters: "AdapterSet | None" = None,
+                           adapter_opts: "AdapterOpts | None" = None, tandem: bool = False, min_tandem_repeat_length: int = 0, pileup: bool = False):
+        """(results, coverage report, control report or None, fold report or None, adapter report or None, tandem_len or None, pileup or None).  opts: the
+        CoverageOpts (None: the defaults); gate: bit v set gives a ZMW with verdict v = 2 .. 5 the status 9 + v and no consensus (COVERAGE_GATE_ALL: all four),
+        0: detection only.  The other arguments as consensus_control (control: a ControlSeq asks for the control screen)"""
+        res, tl, pile = self._outputs(batch, tandem, pileup)
+        vrep = CoverageReport.allocate(batch.n_zmw)
+        crep = ControlReport.allocate(batch.n_zmw) if control is not None else None
+        frep = FoldReport.allocate(batch.n_zmw) if fold else None
+        arep = AdapterReport.allocate(batch.n_zmw) if adapters is not None else None
+        self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length, fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
+                                                       adapters=arep, adapter_set=adapters, adapter_opts=adapter_opts,
+                                                       control=crep, control_seq=control, control_opts=control_opts,
+                                                       coverage=vrep, coverage_opts=opts, coverage_gate=gate))
+        return res, vrep, crep, frep, arep, tl, pile
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -1229,14 +1311,17 @@ class Handle:
                min_tandem_repeat_length: int = 0, hd: "HdReport | None" = None, hd_opts: HdOpts | None = None, hd_split: bool = False,
                fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None, adapters: "AdapterReport | None" = None,
                adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, control: "ControlReport | None" = None,
-               control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None) -> int:
+               control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None, coverage: "CoverageReport | None" = None,
+               coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
         receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd).  fold: a report
         (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts.  adapters: a report (AdapterReport.allocate(n, pinned=True))
         that receives the adapter screen of adapter_set (None: the built-in set) under adapter_opts.  control: a report (ControlReport.allocate(n,
         pinned=True)) that receives the control screen for control_seq under control_opts.  fold, adapters and control go alone or together
-        (ccsx_submit_control), none of them with hd.  Every ticket carries its own control: tickets in flight may screen for different ones"""
+        (ccsx_submit_control), none of them with hd.  Every ticket carries its own control: tickets in flight may screen for different ones.  coverage: a
+        report (CoverageReport.allocate(n, pinned=True)) that receives the coverage screen under coverage_opts and coverage_gate (ccsx_submit_requests; with or
+        without the other screens, not with hd); every ticket carries its own options and gate"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
@@ -1247,8 +1332,10 @@ class Handle:
             raise ValueError("the heteroduplex request and the control screen are not combined")
         if control is not None and control_seq is None:
             raise ValueError("control: a control_seq is needed (there is no built-in control)")
+        if coverage is not None and hd is not None:
+            raise ValueError("the heteroduplex request and the coverage screen are not combined")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
-                             control, control_seq, control_opts)
+                             control, control_seq, control_opts, coverage, coverage_opts, coverage_gate)
         t = C.c_int64()
         cb, cr = self._fused("submit", batch, res, requests, t)
         if not hasattr(self, "_inflight"):

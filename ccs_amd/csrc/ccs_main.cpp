@@ -82,6 +82,9 @@ struct Options {
     std::string control;          // --control FILE.fasta: screen the drafts for the spike-in control (fail class 0x2); control ZMWs leave the main output
     std::vector<uint8_t> control_codes;   // ... its bases
     ccsx_control_seq control_seq{};       // ... as the requests name them
+    bool coverage_filters = false;   // --coverage-filters: the coverage screen with all four gate bits (DESIGN.md §2 "Coverage rule"; off here)
+    int cov_drop_percent = -1, cov_block = -1;   // --coverage-drop-percent / --coverage-block: overrides of ccsx_coverage_opts (-1: the default)
+    ccsx_coverage_opts coverage_opts{};          // ... the options every ticket carries
     std::string fit_model;        // --fit-model OUT.json: the training mode (DESIGN.md §2 "Model training"): no consensus output
     int fit_iterations = 3;       // --fit-iterations: EM iterations over the file
     double fit_min_rq = 0.999;    // --fit-min-rq: a polished consensus is a truth to measure passes against from this predicted accuracy on
@@ -155,6 +158,8 @@ struct Batch {
     ccsx_fold_report frep{}; ccsx_fold_request freq{};   // --fail-reads (ccsx_fold_request: the report's arrays are in out_arena)
     ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_adapter_request: the report's arrays are in out_arena)
     ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_control_request: the report's arrays are in out_arena)
+    ccsx_coverage_report vrep{}; ccsx_coverage_request vreq{}; // --coverage-filters (ccsx_coverage_request: the report's arrays are in out_arena)
+    ccsx_requests reqs{};           // (read during the call only)
 };
 
 template <class T> class Channel {
@@ -216,6 +221,13 @@ void usage()
                  "      --adapters F|default  with --fail-reads: screen every draft for the adapters of FASTA file F (up to 8 records of 16-64 bases) or for the\n"
                  "                            built-in SMRTbell adapter; reads made of adapter copies (ff 0x10) or with an adapter close to an end (ff 0x40)\n"
                  "                            leave the main output for F.bam [off]\n"
+                 "      --coverage-filters    screen every draft's windows for coverage drops: a ZMW whose passes disagree on a block of bases, that too few\n"
+                 "                            passes span end to end, that too few passes align to, or that lost too many passes in the polish gets no\n"
+                 "                            consensus and is counted as 'Coverage drops', 'Insufficient draft cov', 'Draft too different' or 'Reads\n"
+                 "                            failed polishing' [off]\n"
+                 "      --coverage-drop-percent N  with --coverage-filters: a window drops at N %% or less of the best window's passes, 0-100 [50]\n"
+                 "      --coverage-block N    with --coverage-filters: a pass carries a block when its segment exceeds the window by more than N bases,\n"
+                 "                            1-4096 [30]\n"
                  "      --control F.fasta     screen every draft for the spike-in control of FASTA file F (one record of 64-4096 bases); control ZMWs leave\n"
                  "                            the main output and are counted as 'ZMW with control success / failure'; with --fail-reads those with a\n"
                  "                            consensus are written to F.bam with ff 0x2 [off: there is no built-in control]\n"
@@ -364,6 +376,17 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--fail-reads") o.fail_reads = need(a.c_str());
         else if (a == "--adapters") o.adapters = need(a.c_str());
         else if (a == "--control") o.control = need(a.c_str());
+        else if (a == "--coverage-filters") o.coverage_filters = true;
+        else if (a == "--coverage-drop-percent" || a == "--coverage-block") {
+            const bool pct = a == "--coverage-drop-percent";
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < (pct ? 0 : 1) || n > (pct ? 100 : 4096)) {
+                std::fprintf(stderr, "ccs: %s needs a number in %s, got '%s'\n", a.c_str(), pct ? "0 .. 100" : "1 .. 4096", v.c_str()); std::exit(2);
+            }
+            (pct ? o.cov_drop_percent : o.cov_block) = (int)n;
+        }
         else if (a == "--model-file") o.model_file = need(a.c_str());
         else if (a == "--fit-model") o.fit_model = need(a.c_str());
         else if (a == "--fit-iterations") o.fit_iterations = std::atoi(need(a.c_str()).c_str());
@@ -393,7 +416,8 @@ bool parse(int argc, char **argv, Options &o)
             refuse("options out of range (--fit-iterations >= 1, --fit-max-zmws >= 0, --fit-degree 0 .. 3, --fit-min-rq in [0, 1])");
         if (o.dump || o.host_only) refuse("combined with --dump-zmws or --host-only is not supported");
         // nothing of the output side runs in this mode: an option that would be ignored is refused, not dropped silently
-        if (!o.control.empty() || !o.adapters.empty()) refuse("runs no draft screen: --control and --adapters are not supported with it");
+        if (!o.control.empty() || !o.adapters.empty() || o.coverage_filters)
+            refuse("runs no draft screen: --control, --adapters and --coverage-filters are not supported with it");
         if (o.gpu_inflate) refuse("combined with --gpu-inflate is not supported");
         if (o.report_named || o.metrics_named || !o.report_json.empty() || !o.hifi_summary.empty() || o.suppress_reports)
             refuse("writes no reports: --report-file, --metrics-json, --report-json, --hifi-summary-json and --suppress-reports are not supported with it");
@@ -417,6 +441,12 @@ bool parse(int argc, char **argv, Options &o)
         if (!load_control(o.control, o.control_codes, err)) { std::fprintf(stderr, "ccs: --control %s: %s\n", o.control.c_str(), err.c_str()); std::exit(2); }
         o.control_seq = ccsx_control_seq{(int32_t)o.control_codes.size(), 0, o.control_codes.data()};
     }
+    if (!o.coverage_filters && (o.cov_drop_percent >= 0 || o.cov_block >= 0)) {
+        std::fprintf(stderr, "ccs: --coverage-drop-percent and --coverage-block need --coverage-filters\n"); std::exit(2);
+    }
+    ccsx_coverage_opts_default(&o.coverage_opts);
+    if (o.cov_drop_percent >= 0) o.coverage_opts.drop_percent = o.cov_drop_percent;
+    if (o.cov_block >= 0) o.coverage_opts.block = o.cov_block;
     // --top-passes 0 = unlimited (docs/faq/accuracy-vs-passes.md:49-52); the engine takes up to CCSX_MAX_PASSES = 255 per ZMW (SPEC v5)
     if (o.o.top_passes <= 0) o.o.top_passes = CCSX_MAX_PASSES;
     if (o.o.top_passes > CCSX_MAX_PASSES) {
@@ -658,16 +688,23 @@ struct Report {
     int64_t tandem = 0;           // ZMWs flagged as tandem repeats (--min-tandem-repeat-length; docs/faq/reports-aux-files.md:22)
     int64_t fail_records = 0;     // records written to --fail-reads
     int64_t control = 0;          // ZMWs the control screen found (--control), whatever their final status
+    int64_t coverage = 0;         // ZMWs the coverage screen's gate took (--coverage-filters)
 };
 
-const char *fail_label(int st)
+// cov: --coverage-filters.  Under it "Reads failed polishing" counts what the reference counts there, the reads lost while polishing; the engine's "more than
+// half of the passes must map" rule is an end-to-end alignment rule and moves to "Insufficient draft cov"
+const char *fail_label(int st, bool cov = false)
 {
     switch (st) {
+        case CCSX_COVERAGE_DROPS: return "Coverage drops";
+        case CCSX_INSUFFICIENT_SPANS: return "Insufficient draft cov";
+        case CCSX_DRAFT_TOO_DIFFERENT: return "Draft too different";
+        case CCSX_READS_FAILED_POLISHING: return "Reads failed polishing";
         case HS_POOR_SNR: return "Below SNR threshold";
         case HS_NO_SUBREADS: return "Median length filter";
         case HS_TOO_FEW: case CCSX_TOO_FEW_PASSES: return "Lacking full passes";
         case CCSX_DRAFT_FAILURE: return "Draft generation error";
-        case CCSX_TOO_MANY_UNUSABLE: return "Reads failed polishing";
+        case CCSX_TOO_MANY_UNUSABLE: return cov ? "Insufficient draft cov" : "Reads failed polishing";
         case CCSX_NON_CONVERGENT: return "CCS did not converge";
         case CCSX_TOO_SHORT: return "Draft below --min-length";
         case CCSX_TOO_LONG: case HS_TOO_LONG: return "Draft above --max-length";
@@ -683,15 +720,19 @@ const char *fail_label(int st)
     }
 }
 
-const char *status_name(int st)
+const char *status_name(int st, bool cov = false)
 {
     switch (st) {   // docs/faq/reports-aux-files.md:143-159
+        case CCSX_COVERAGE_DROPS: return "COVERAGE_DROPS";
+        case CCSX_INSUFFICIENT_SPANS: return "INSUFFICIENT_SPANS";
+        case CCSX_DRAFT_TOO_DIFFERENT: return "TOO_FEW_PASSES_AFTER_DRAFT_ALIGNMENT";
+        case CCSX_READS_FAILED_POLISHING: return "TOO_MANY_UNUSABLE";
         case CCSX_SUCCESS: return "SUCCESS";
         case HS_POOR_SNR: return "POOR_SNR";
         case HS_NO_SUBREADS: return "NO_SUBREADS";
         case HS_TOO_FEW: case CCSX_TOO_FEW_PASSES: return "TOO_FEW_PASSES";
         case CCSX_DRAFT_FAILURE: return "DRAFT_FAILURE";
-        case CCSX_TOO_MANY_UNUSABLE: return "TOO_MANY_UNUSABLE";
+        case CCSX_TOO_MANY_UNUSABLE: return cov ? "INSUFFICIENT_SPANS" : "TOO_MANY_UNUSABLE";
         case CCSX_NON_CONVERGENT: return "NON_CONVERGENT";
         case CCSX_TOO_SHORT: return "TOO_SHORT";
         case CCSX_TOO_LONG: case HS_TOO_LONG: return "TOO_LONG";
@@ -708,12 +749,12 @@ const char *status_name(int st)
 }
 
 // the rows of "Exclusive failed counts" this path can produce, in the order of docs/faq/reports-aux-files.md:24-46 (the rows of the subsystems
-// outside this path — heteroduplex, coverage drops, and without their options the adapter / control classes — cannot occur and are not listed)
+// outside this path — heteroduplex, and without their options the coverage, adapter and control classes — cannot occur and are not listed)
 const char *const kFailOrder[] = {"Below SNR threshold", "Median length filter", "Lacking full passes", "Draft generation error",
                                   "Draft above --max-length", "Draft below --min-length", "Reads failed polishing", "Empty coverage windows",
                                   "CCS did not converge", "CCS below minimum RQ", "Consensus outgrew its buffer", "Unknown error"};
 
-// the rows printed: with --fail-reads also "CCS adapter palindrome" (now a failure) and "ZMW with full-length subread" (the 0x8 records), with --control the two
+// the rows printed: with --coverage-filters the three coverage rows after "Lacking full passes", where the reference lists them; with --fail-reads also "CCS adapter palindrome" (now a failure) and "ZMW with full-length subread" (the 0x8 records), with --control the two
 // control rows, where the reference lists them
 std::vector<const char *> fail_order(const Options &o)
 {
@@ -726,6 +767,7 @@ std::vector<const char *> fail_order(const Options &o)
         }
         if (!o.control.empty() && std::string(k) == "CCS below minimum RQ") { v.push_back("ZMW with control failure"); v.push_back("ZMW with control success"); }
         v.push_back(k);
+        if (o.coverage_filters && std::string(k) == "Lacking full passes") { v.push_back("Coverage drops"); v.push_back("Insufficient draft cov"); v.push_back("Draft too different"); }
     }
     return v;
 }
@@ -1221,6 +1263,7 @@ int main(int argc, char **argv)
         const bool fail_reads = !opt.fail_reads.empty();
         const bool screen = !opt.adapters.empty();                  // (needs fail_reads)
         const bool control = !opt.control.empty();
+        const bool coverage = opt.coverage_filters;
         std::vector<std::thread> packers;
         const size_t n_packers = std::max<size_t>(1, handles.size()) * (size_t)opt.workers_per_gpu;
         std::vector<std::atomic<int>> packers_left(ndev_q);
@@ -1247,7 +1290,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
@@ -1286,6 +1329,13 @@ int main(int argc, char **argv)
                             b->crep = ccsx_control_report{n, c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]};
                             b->creq = ccsx_control_request{&opt.control_seq, nullptr, &b->crep, {0, 0}};
                         }
+                        if (coverage) {
+                            const auto v = planes(10);
+                            b->vrep = ccsx_coverage_report{n, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]};
+                            b->vreq = ccsx_coverage_request{&opt.coverage_opts, &b->vrep, 0x3cu, {0, 0}};   // all four gate bits
+                        }
+                        b->reqs = ccsx_requests{(opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr,
+                                              control ? &b->creq : nullptr, coverage ? &b->vreq : nullptr, {nullptr, nullptr, nullptr}};
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
                 us_pack += us_since(t0);
@@ -1385,8 +1435,7 @@ int main(int argc, char **argv)
                 t0 = now();
                 ccsx_ticket t = -1;
                 // the most general submit: NULL for the extras and for every request this run did not ask for (the narrower entry points stage the same)
-                if (ccsx_submit_control(h, &b->cb, &b->cr, (opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr,
-                                        screen ? &b->areq : nullptr, control ? &b->creq : nullptr, &t)) {
+                if (ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1509,14 +1558,15 @@ int main(int argc, char **argv)
                         std::snprintf(line, sizeof(line), "%s    {\"effective_coverage\": %.2f, \"has_tandem_repeat\": %s, \"insert_size\": %d, \"num_full_passes\": %d, "
                                       "\"polymerase_length\": %" PRId64 ", \"predicted_accuracy\": %.6f, \"status\": \"%s\", \"zmw\": \"%s/%d%s\"}",
                                       first_metric ? "" : ",\n", have ? bt.ec[s] : 0.0f, tandem ? "true" : "false", isz, have ? bt.np[s] : z.n_full, z.polymerase_len,
-                                      (have && bt.seq_len[s] > 0) ? bt.rq[s] : -1.0f, status_name(st), movie.c_str(), z.zm,
+                                      (have && bt.seq_len[s] > 0) ? bt.rq[s] : -1.0f, status_name(st, coverage), movie.c_str(), z.zm,
                                       z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                         metrics += line; first_metric = false;
                         flush_metrics(false);
                     }
                     const int64_t o = s >= 0 ? bt.seq_off[s] : 0; const int32_t len = (s >= 0 && bt.have_results) ? bt.seq_len[s] : 0;
                     if (st != CCSX_SUCCESS) {
-                        rep.fail[fail_label(st)]++;
+                        rep.fail[fail_label(st, coverage)]++;
+                        if (st >= CCSX_DRAFT_TOO_DIFFERENT && st <= CCSX_READS_FAILED_POLISHING) ++rep.coverage;
                         if (!fail_reads) continue;
                         if ((engine_st == CCSX_LOW_RQ || pal || abits || ctl) && len > 0) {     // a consensus: as the main writer builds it, plus ff
                             if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }
@@ -1630,11 +1680,12 @@ int main(int argc, char **argv)
                          eng.tickets, eng.zmws, eng.last - eng.first, (eng.last - eng.first) * k, eng.draft * k, eng.polish * k, eng.queue * k, eng.total * k);
         }
         if (opt.log_level >= 1)
-            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s\n", rep.input, rep.pass, el,
+            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",
                          opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "",
                          opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str(),
-                         control ? (", " + std::to_string(rep.control) + " control ZMWs").c_str() : "");
+                         control ? (", " + std::to_string(rep.control) + " control ZMWs").c_str() : "",
+                         coverage ? (", " + std::to_string(rep.coverage) + " ZMWs failed the coverage filters").c_str() : "");
         if (failed) {
             if (!err_msg.empty()) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
             // no plausible-looking partial output after a failed run

@@ -135,6 +135,7 @@ struct Slot {
     DevBuf d_fold;                                // adapter palindromes only (ccsx_fold_request): [4][n] report
     DevBuf d_adapt;                               // adapter screen only (ccsx_adapter_request): [9][n] report + [n][16] hits
     DevBuf d_ctl;                                 // control screen only (ccsx_control_request): the slot's own index, then the [8][n] report
+    DevBuf d_cov;                                 // coverage screen only (ccsx_coverage_request): the [10][n] report, then one byte per window slot
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
@@ -370,6 +371,7 @@ struct Wants {
     const ccsx_fold_request *fold = nullptr; ccsx_fold_opts fold_opts{};
     const ccsx_adapter_request *adapters = nullptr; ccsx_adapter_set adapter_set{}; ccsx_adapter_opts adapter_opts{};
     const ccsx_control_request *control = nullptr; ccsx_control_opts control_opts{}; std::vector<uint8_t> control_seq;
+    const ccsx_coverage_request *coverage = nullptr; ccsx_coverage_opts coverage_opts{};
 };
 
 // the longest draft of a slot's batch that can reach status SUCCESS (that needs length <= opts.max_length, and no draft exceeds its slot), at least `floor`:
@@ -989,6 +991,35 @@ static int control_attach(ccsx_handle h, Slot &S, const std::vector<uint8_t> &se
     return 0;
 }
 
+// ---- the coverage screen's host side (ccsx_coverage_request): the same three steps.  The checked options are copied into `o`
+static int coverage_request_check(const ccsx_coverage_request *q, const ccsx_batch *b, ccsx_coverage_opts *o, const char *fn)
+{
+    if (!q || !q->report) { ccsx_set_error(std::string(fn) + ": null coverage request or report"); return -1; }
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": coverage request: reserved must be 0"); return -1; }
+    if (q->gate & ~0x3cu) { ccsx_set_error(std::string(fn) + ": coverage request: gate has bits outside 2 .. 5"); return -1; }
+    if (q->opts) *o = *q->opts; else ccsx_coverage_opts_default(o);
+    if (o->drop_percent < 0 || o->drop_percent > 100 || o->max_lost_percent < 0 || o->max_lost_percent > 100 || o->block < 1 || o->block > 4096 ||
+        o->min_spans < 0 || o->min_spans > CCSX_MAX_PASSES) {
+        ccsx_set_error(std::string(fn) + ": coverage options out of range (0 <= drop_percent, max_lost_percent <= 100; 1 <= block <= 4096; 0 <= min_spans <= 255)"); return -1;
+    }
+    const ccsx_coverage_report *r = q->report;
+    if (r->n_zmw != b->n_zmw || !r->verdict || !r->np_aligned || !r->spans || !r->cov_max || !r->clean_min || !r->drop_window || !r->drop_windows || !r->reach_sum ||
+        !r->used_sum || !r->used_min) { ccsx_set_error(std::string(fn) + ": coverage report arrays missing, or sized for another batch"); return -1; }
+    return 0;
+}
+
+// the report's planes and the reach bytes of every window slot; min_spans 0 becomes the handle's min_passes here.  Nothing is enqueued: k_coverage writes every
+// plane of every ZMW and the byte of every window k_coverage_post reads
+static int coverage_attach(ccsx_handle h, Slot &S, const ccsx_coverage_opts &o, uint32_t gate)
+{
+    const size_t n = (size_t)S.P.n_zmw, wins = (size_t)S.P.total_wslots + 1;
+    if (S.d_cov.reserve(n * CCSX_COVERAGE_PLANES * 4 + wins)) return -2;
+    KParams &P = S.P;
+    P.cov = o; P.cov_gate = gate; P.cov_zi = (int32_t *)S.d_cov.p; P.cov_reach = (uint8_t *)(P.cov_zi + n * CCSX_COVERAGE_PLANES);
+    if (P.cov.min_spans == 0) P.cov.min_spans = h->opts.min_passes;
+    return 0;
+}
+
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
@@ -1005,15 +1036,17 @@ static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string
 // first, each refused by its own message, then the extras; the caller's null-argument check follows (without a batch there is nothing to measure a report
 // against, and that check refuses the call).
 static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
-                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W)
+                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr)
 {
     *W = Wants{};
+    if (coverage && hd) return refuse(fn, "the coverage and the heteroduplex requests are not combined");
+    if (coverage && b && coverage_request_check(coverage, b, &W->coverage_opts, fn)) return -1;
     if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
     if (fold && b && fold_request_check(fold, b, &W->fold_opts, fn)) return -1;
     if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
     if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
-    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control;
+    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
@@ -1027,6 +1060,7 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.pile && (rc = check_pile(S, W.pile))) return rc;
     if (W.fold && (rc = fold_attach(h, S, W.fold_opts))) return rc;
     if (W.adapters && (rc = adapter_attach(h, S, W.adapter_set, W.adapter_opts))) return rc;
+    if (W.coverage && (rc = coverage_attach(h, S, W.coverage_opts, W.coverage->gate))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
     return 0;
@@ -1053,6 +1087,11 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
     if (W.control) {
         const ccsx_control_report *r = W.control->report;
         if ((rc = download_planes({r->verdict, r->strand, r->hits, r->matched, r->ctl_start, r->ctl_end, r->draft_start, r->draft_end}, S.P.ctl_zi, n, s))) return rc;
+    }
+    if (W.coverage) {
+        const ccsx_coverage_report *r = W.coverage->report;
+        if ((rc = download_planes({r->verdict, r->np_aligned, r->spans, r->cov_max, r->clean_min, r->drop_window, r->drop_windows, r->reach_sum, r->used_sum, r->used_min},
+                                  S.P.cov_zi, n, s))) return rc;
     }
     return 0;
 }
@@ -1157,6 +1196,20 @@ int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
 {
     Wants W;
     if (build_wants(ex, nullptr, fold, adapters, control, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+// the members of a ccsx_requests as build_wants takes them (NULL: none); -1 for nonzero reserved words
+static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W)
+{
+    static const ccsx_requests none = {};
+    if (!rq) rq = &none;
+    if (rq->reserved[0] || rq->reserved[1] || rq->reserved[2]) return refuse(fn, "ccsx_requests: reserved must be NULL");
+    return build_wants(rq->ex, nullptr, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage);
+}
+int ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket)
+{
+    Wants W;
+    if (requests_wants(rq, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
@@ -1390,6 +1443,21 @@ int ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res
 {
     Wants W;
     if (build_wants(ex, nullptr, fold, adapters, control, b, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
+void ccsx_coverage_opts_default(ccsx_coverage_opts *o)
+{
+    if (!o) return;
+    o->drop_percent = 50; o->block = 30; o->min_spans = 0; o->max_lost_percent = 50;   // DESIGN.md §2 "Coverage rule": the build's own, the reasons for them
+}
+
+int ccsx_coverage_rule_version(void) { return 1; }
+
+int ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq)
+{
+    Wants W;
+    if (requests_wants(rq, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 

@@ -144,7 +144,14 @@ struct KParams {
     int64_t *train_tab;        // [n][400] posterior event counts x 2^32: match[16][12], stay[16][12], del[16]
     int64_t *train_ll;         // [n] log2-likelihood of the counted pairs x 65536, range shift removed
     int32_t *train_zi;         // [3][n] counted pairs, gated pairs, read bases of the counted pairs
+    // ---- coverage screen (ccsx_consensus_requests / ccsx_submit_requests with a coverage request; NULL otherwise): DESIGN.md §2 "Coverage rule"
+    ccsx_coverage_opts cov;    // min_spans already resolved (0 = opts.min_passes)
+    uint32_t cov_gate;         // bit v: a ZMW with verdict v = 2 .. 5 gets the status CCSX_DRAFT_TOO_DIFFERENT + (v - 2) and no consensus
+    int32_t *cov_zi;           // [10][n] verdict, np_aligned, spans, cov_max, clean_min, drop_window, drop_windows, reach_sum, used_sum, used_min
+    uint8_t *cov_reach;        // [wslots] reach_w of every window, indexed as wmeta is ((wb_off[z] - z) + w): k_coverage writes it, k_coverage_post reads it
 };
+#define CCSX_COVERAGE_PLANES 10
+#define CCSX_COVERAGE_PRE_GATE 0x1cu   // the gate bits of the verdicts k_coverage reaches before the polish (2, 3, 4)
 
 // k_adapter (DESIGN.md §2 "Adapter screen"): draft bases a lane owns per search, its workgroup, the hit keys one pass buffers in LDS and the bitmaps' LDS bound
 #define CCSX_ADAPTER_CHUNK     128

@@ -4471,6 +4471,115 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
     }
 }
 
+// ---- the coverage screen (DESIGN.md §2 "Coverage rule"; include/ccsx.h ccsx_coverage_*).  k_coverage: one wave per ZMW, longest first, on the draft stream after
+// the draft screens.  Lanes stride over the windows of the final draft; a lane walks the ZMW's passes and takes the segment between the window's two edge
+// columns from the entry rows exactly as k_polish's prologue does (before the 63-base limit, before trimming).  Per pass an LDS flag says "missed some window":
+// every lane that sets it stores the same 1, so the AND over the windows does not depend on lane order.  Windows by clean count go into an LDS histogram, from
+// which drop_windows is a sum once cov_max is known.  Counts, maxima, minima and integer sums only: nothing depends on the order in which lanes ran.
+__global__ __launch_bounds__(64) void k_coverage(KParams P)
+{
+    __shared__ int sLen[CCSX_MAX_PASSES + 1];               // pass r: its length, or -1 when it did not align (avalid)
+    __shared__ uint8_t sMiss[CCSX_MAX_PASSES + 1];          // pass r does not reach some window
+    __shared__ int sHist[CCSX_MAX_PASSES + 1];              // windows with clean_w = c
+    if ((int)blockIdx.x >= P.n_zmw) return;
+    const int lane = threadIdx.x;
+    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    const size_t n = (size_t)P.n_zmw;
+    int32_t *out = P.cov_zi + z;
+    if (rfl(P.zstat[z]) != CCSX_SUCCESS) {                  // UNTESTED: every plane 0
+        if (lane < CCSX_COVERAGE_PLANES) out[(size_t)lane * n] = 0;
+        return;
+    }
+    const int nw = rfl(P.nwin[z]), Ld = rfl(P.draft_len[z]);
+    const int r0 = rfl(P.read_off[z]);
+    int nreads = rfl(P.nreads_used[z]), nfull = rfl(P.nfull[z]);
+    if (nreads > CCSX_MAX_PASSES) nreads = CCSX_MAX_PASSES; // (never: the engine uses at most that many)
+    if (nfull > nreads) nfull = nreads;
+    const int32_t *wb = P.wbounds + P.wb_off[z];
+    const size_t w0 = (size_t)(P.wb_off[z] - z);
+    const int block = P.cov.block;
+    for (int r = lane; r <= CCSX_MAX_PASSES; r += LANES) {
+        sLen[r] = (r < nreads && P.avalid[r0 + r]) ? (int)(P.base_off[r0 + r + 1] - P.base_off[r0 + r]) : -1;
+        sMiss[r] = 0; sHist[r] = 0;
+    }
+    __syncthreads();
+    int cmax = 0, rsum = 0, key = 0x7fffffff;               // key = clean_w << 16 | w: its minimum is the FIRST window among those with the fewest clean passes
+    for (int w = lane; w < nw; w += LANES) {
+        int ws = wb[w] - CCSX_WIN_OVERHANG; if (ws < 0) ws = 0;
+        int we = wb[w + 1] + CCSX_WIN_OVERHANG; if (we > Ld) we = Ld;
+        const int idx_ws = (w == 0) ? 0 : 2 * w - 1, idx_we = (w == nw - 1) ? 2 * nw - 1 : 2 * (w + 1);
+        const int lim = (we - ws) + block;
+        int reach = 0, lng = 0;
+        for (int r = 0; r < nreads; ++r) {
+            const int L = sLen[r];                          // (uniform over the lanes: no divergence)
+            if (L < 0) continue;
+            const int64_t eo = P.ent_off[r0 + r];
+            const int nseg = P.ent[eo + idx_we] - P.ent[eo + idx_ws];
+            if (nseg >= 0 && nseg <= L) { ++reach; lng += nseg > lim ? 1 : 0; }
+            else sMiss[r] = 1;
+        }
+        P.cov_reach[w0 + w] = (uint8_t)reach;
+        const int clean = reach - lng;
+        atomicAdd(&sHist[clean], 1);
+        cmax = reach > cmax ? reach : cmax; rsum += reach;
+        const int k = (clean << 16) | (w & 0xffff);
+        key = k < key ? k : key;
+    }
+    __syncthreads();
+    int npa = 0, spans = 0;
+    for (int r = lane; r < nfull; r += LANES) if (sLen[r] >= 0) { ++npa; spans += sMiss[r] ? 0 : 1; }
+    npa = wave_reduce_add_i32(npa); spans = wave_reduce_add_i32(spans);
+    cmax = wave_reduce_max_i32(cmax); rsum = wave_reduce_add_i32(rsum);
+    key = -wave_reduce_max_i32(-key);
+    const int thr = P.cov.drop_percent * cmax;
+    int drops = 0;
+    for (int c = lane; c <= CCSX_MAX_PASSES; c += LANES) if (c * 100 <= thr) drops += sHist[c];
+    drops = wave_reduce_add_i32(drops);
+    if (lane == 0) {
+        const int clean_min = nw > 0 ? key >> 16 : 0, drop_window = nw > 0 ? key & 0xffff : 0;
+        const int verdict = npa < P.opts.min_passes ? CCSX_COVERAGE_DRAFT_TOO_DIFFERENT
+                          : spans < P.cov.min_spans ? CCSX_COVERAGE_INSUFFICIENT_SPANS
+                          : drops >= 1 ? CCSX_COVERAGE_COVERAGE_DROPS : CCSX_COVERAGE_NONE;
+        put_planes(out, n, verdict, npa, spans, cmax, clean_min, drop_window, drops, rsum, 0, 0);
+        // the gate: the ZMW leaves the polish stage here, as a split heteroduplex does (k_hd_verdict) — no windows, so the rebuilt window map gives k_polish
+        // nothing of it and k_stitch reports the status with an empty consensus.  Only this ZMW's words are written, after every lane has read them.
+        if (verdict >= CCSX_COVERAGE_DRAFT_TOO_DIFFERENT && ((P.cov_gate >> verdict) & 1u)) {
+            P.zstat[z] = CCSX_DRAFT_TOO_DIFFERENT + (verdict - CCSX_COVERAGE_DRAFT_TOO_DIFFERENT); P.nwin[z] = 0;
+        }
+    }
+}
+
+// k_coverage_post: one wave per ZMW on the polish stream after k_stitch.  For a ZMW that was polished (its status before the stitch is SUCCESS) it sums, over the
+// windows, the passes the polish used (wmeta.y & 255: what k_stitch's ec sums) beside the passes that reached them (k_coverage's bytes), and upgrades a NONE
+// verdict to READS_FAILED_POLISHING; with that verdict's gate bit the ZMW loses its consensus.
+__global__ __launch_bounds__(64) void k_coverage_post(KParams P)
+{
+    if ((int)blockIdx.x >= P.n_zmw) return;
+    const int lane = threadIdx.x;
+    const int z = rfl(P.zmw_perm[blockIdx.x]);
+    const size_t n = (size_t)P.n_zmw;
+    int32_t *out = P.cov_zi + z;
+    if (rfl(P.zstat[z]) != CCSX_SUCCESS) return;            // untested, or gated before the polish: used_sum = used_min = 0 as k_coverage left them
+    const int nw = rfl(P.nwin[z]);
+    const size_t w0 = (size_t)(P.wb_off[z] - z);
+    int usum = 0, umin = 0x7fffffff, rsum = 0;
+    for (int w = lane; w < nw; w += LANES) {
+        const int used = P.wmeta[w0 + w].y & 255;
+        usum += used; umin = used < umin ? used : umin; rsum += (int)P.cov_reach[w0 + w];
+    }
+    usum = wave_reduce_add_i32(usum); rsum = wave_reduce_add_i32(rsum);
+    umin = -wave_reduce_max_i32(-umin);
+    if (lane == 0) {
+        out[7 * n] = rsum; out[8 * n] = usum; out[9 * n] = nw > 0 ? umin : 0;
+        const int stat = P.out_status[z];
+        if (out[0] == CCSX_COVERAGE_NONE && (stat == CCSX_SUCCESS || stat == CCSX_LOW_RQ) &&
+            (long long)(rsum - usum) * 100 > (long long)P.cov.max_lost_percent * rsum) {
+            out[0] = CCSX_COVERAGE_READS_FAILED_POLISHING;
+            if ((P.cov_gate >> CCSX_COVERAGE_READS_FAILED_POLISHING) & 1u) { P.out_status[z] = CCSX_READS_FAILED_POLISHING; P.out_len[z] = 0; }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // The launch schedule of a batch: ccsx_launch_all at the end lists its stages, Schedule holds them.
 namespace {
@@ -4661,6 +4770,14 @@ struct Schedule {
         }
     }
 
+    // The coverage screen's first kernel (a fused run with a ccsx_coverage_request): on the draft stream after the draft screens, so that they see the statuses
+    // they see without it.  It reads what k_polish is given — final draft, window bounds, status after the cascade, entry rows — and no shared scratch.
+    void coverage()
+    {
+        launch("k_coverage", k_coverage, dim3(P.n_zmw), dim3(64), 0, st, P);
+        trace_sync(st, "k_coverage");
+    }
+
     // The heteroduplex finder's three kernels on the draft stream.  Its inputs are what k_polish gets: the final draft, its window bounds, the status after the
     // cascade and the entry rows (k_polish trims large insertions in LDS only).  It reads no shared POA / alignment scratch.
     // in_place_of_polish (ccsx_hd_batch): the verdict is what the run has for a stitch, CCSX_EV_POLISH_DONE is recorded before it.
@@ -4718,6 +4835,7 @@ struct Schedule {
         stage_event(CCSX_EV_POLISH_DONE, sp);
         launch("k_stitch", k_stitch, dim3(P.n_zmw), dim3(64), 0, sp, P);
         if (P.out_pile) launch("k_pile_stitch", k_pile_stitch, dim3(P.n_zmw), dim3(64), 0, sp, P);
+        if (P.cov_zi) launch("k_coverage_post", k_coverage_post, dim3(P.n_zmw), dim3(64), 0, sp, P);   // the coverage screen's post-polish planes
         stage_event(CCSX_EV_END, sp);
     }
 };
@@ -4744,6 +4862,10 @@ const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int m
             s.hd_finder(false);
             if (P.hd_split) s.window_map();                 // the split ZMWs have no windows now: the polish stage's map without them
             s.trace_sync(q.draft, "k_hd");
+        }
+        if (P.cov_zi) {
+            s.coverage();
+            if (P.cov_gate & CCSX_COVERAGE_PRE_GATE) s.window_map();   // the gated ZMWs have no windows now: the polish stage's map without them
         }
     }
     if (mode == CCSX_RUN_HD) {                              // the heteroduplex finder instead of the polish stage, on the same stream

@@ -50,14 +50,20 @@ enum ccsx_status {
     CCSX_SUCCESS               = 0,
     CCSX_TOO_FEW_PASSES        = 1,  /* fewer usable subreads than opts.min_passes                    */
     CCSX_DRAFT_FAILURE         = 2,  /* POA produced no draft / vertex capacity exceeded              */
-    CCSX_TOO_MANY_UNUSABLE     = 3,  /* <= 50 % of subreads map to the draft (accuracy-vs-passes.md:37-39) */
+    CCSX_TOO_MANY_UNUSABLE     = 3,  /* <= 50 % of subreads map to the draft (accuracy-vs-passes.md:37-39).  The `ccs` driver counts it under "Reads failed
+                                        polishing" (metrics TOO_MANY_UNUSABLE), and with --coverage-filters under "Insufficient draft cov" (INSUFFICIENT_SPANS) */
     CCSX_NON_CONVERGENT        = 4,  /* some window hit CCSX_MAX_ITER with favourable mutations left   */
     CCSX_TOO_SHORT             = 5,
     CCSX_TOO_LONG              = 6,
     CCSX_LOW_RQ                = 7,  /* predicted accuracy below opts.min_rq                          */
     CCSX_EMPTY_WINDOW          = 8,  /* EMPTY_WINDOW_DURING_POLISHING                                 */
     CCSX_CAPACITY              = 9,  /* the polished consensus outgrew its buffer (1.25 x longest subread + 64): reported, never truncated */
-    CCSX_HETERODUPLEX          = 10  /* ccsx_hd_request.split: the finder's verdict was HETERODUPLEX, the ZMW was not polished (see there)    */
+    CCSX_HETERODUPLEX          = 10, /* ccsx_hd_request.split: the finder's verdict was HETERODUPLEX, the ZMW was not polished (see there)    */
+    /* the coverage screen's gate (ccsx_coverage_request.gate; without that request no ZMW ever gets one of these four) */
+    CCSX_DRAFT_TOO_DIFFERENT   = 11, /* fewer than opts.min_passes full-length passes align to the draft; not polished                          */
+    CCSX_INSUFFICIENT_SPANS    = 12, /* fewer than min_spans full-length passes reach every window of the draft; not polished                   */
+    CCSX_COVERAGE_DROPS        = 13, /* some window is reached cleanly by too few of the passes; not polished                                   */
+    CCSX_READS_FAILED_POLISHING = 14 /* the polish dropped too many of the (pass, window) segments the alignment gave it; no consensus          */
 };
 
 /* ---- Arrow model parameter blob (interface of docs/faq/chemistry.md:27-56 the "arrow" json files) ----
@@ -527,6 +533,73 @@ int         ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_resu
                                    const ccsx_adapter_request *adapters, const ccsx_control_request *control);
 int         ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold,
                                 const ccsx_adapter_request *adapters, const ccsx_control_request *control, ccsx_ticket *ticket);
+
+/* ---- coverage screen (docs/faq/reports-aux-files.md:28-35,77-97,149-155: "Coverage drops", "Insufficient draft cov", "Draft too different", "Reads failed
+ * polishing"; the rule: DESIGN.md §2 "Coverage rule", its own version ccsx_coverage_rule_version; no result of the consensus changes).  When the draft lacks a
+ * block of bases that some passes carry, those passes go through the split alignment, are trimmed, and the ZMW comes out SUCCESS with whichever allele the draft
+ * took.  k_coverage counts, per window of the final draft (what k_polish is given), the passes that reach it and those that carry a block there, from the entry
+ * rows the alignment cascade left; k_coverage_post adds, after the stitch, how many (pass, window) segments the polish used.  Integer arithmetic only.
+ *   reach_w      passes r with avalid[r] and 0 <= n <= L_r, n = the pass's bases between the window's two edge columns (k_polish's segment test before the
+ *                63-base limit and before trimming); long_w those of them with n > J_w + block (J_w = the window's columns incl. overhangs); clean_w = reach_w - long_w
+ *   verdict      the first that holds: UNTESTED (the status after the cascade is not SUCCESS), DRAFT_TOO_DIFFERENT (np_aligned < opts.min_passes),
+ *                INSUFFICIENT_SPANS (spans < min_spans), COVERAGE_DROPS (drop_windows >= 1), READS_FAILED_POLISHING (final status SUCCESS or LOW_RQ and
+ *                (reach_sum - used_sum) * 100 > max_lost_percent * reach_sum), NONE
+ *   gate         bit v (v = 2 .. 5) set: a ZMW with verdict v gets the status CCSX_DRAFT_TOO_DIFFERENT + (v - 2) and no consensus (seq_len 0).  Verdicts 2 .. 4
+ *                are known before the polish: such a ZMW is not polished (n_windows = iters = 0, rq = ec = 0, np / fn / rn as the accounting counted them, as with
+ *                ccsx_hd_request.split) and its used_sum / used_min stay 0.  Every other ZMW is byte for byte as without the request.  gate 0: detection only.
+ * The request travels in a ccsx_requests (below).  A NULL report, a report sized for another batch, nonzero reserved words, percentages outside 0 .. 100, block
+ * outside 1 .. 4096, min_spans outside 0 .. 255 or gate bits outside 2 .. 5 are errors of the call: nothing is enqueued.  The report's arrays follow the lifetime
+ * rule of `res` and should be page-locked for the ticketed form; the request and options structs are read during the call only (every ticket carries its own
+ * options and gate).  Per batch slot the screen takes 40 bytes per ZMW and one byte per window slot, reserved by the first request on that slot; without a request
+ * nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered; the draft and polish seams take no request.                      */
+typedef struct ccsx_coverage_opts {
+    int32_t drop_percent;        /* a window drops when clean_w * 100 <= drop_percent * cov_max (0 .. 100)                                                        */
+    int32_t block;               /* a reaching pass carries a block in a window when its segment is more than this many bases longer than the window (1 .. 4096);
+                                    independent of opts.max_insertion_size                                                                                        */
+    int32_t min_spans;           /* INSUFFICIENT_SPANS below this many spanning passes; 0 = the handle's opts.min_passes (0 .. 255)                                */
+    int32_t max_lost_percent;    /* READS_FAILED_POLISHING when more than this share of the reaching (pass, window) segments was not used by the polish (0 .. 100)  */
+} ccsx_coverage_opts;
+enum ccsx_coverage_verdict {
+    CCSX_COVERAGE_UNTESTED = 0, CCSX_COVERAGE_NONE = 1, CCSX_COVERAGE_DRAFT_TOO_DIFFERENT = 2, CCSX_COVERAGE_INSUFFICIENT_SPANS = 3,
+    CCSX_COVERAGE_COVERAGE_DROPS = 4, CCSX_COVERAGE_READS_FAILED_POLISHING = 5
+};
+typedef struct ccsx_coverage_report {
+    int32_t  n_zmw;
+    int32_t *verdict;            /* [n_zmw] enum ccsx_coverage_verdict; every other plane of an UNTESTED ZMW is 0                                                  */
+    int32_t *np_aligned;         /* [n_zmw] full-length passes that align to the draft (the accounting's np)                                                      */
+    int32_t *spans;              /* [n_zmw] ... that also reach every window (a double-split pass with uncovered edge columns does not)                            */
+    int32_t *cov_max;            /* [n_zmw] max over the windows of reach_w                                                                                       */
+    int32_t *clean_min;          /* [n_zmw] min over the windows of clean_w                                                                                       */
+    int32_t *drop_window;        /* [n_zmw] the first window with clean_w = clean_min                                                                             */
+    int32_t *drop_windows;       /* [n_zmw] windows with clean_w * 100 <= drop_percent * cov_max                                                                  */
+    int32_t *reach_sum;          /* [n_zmw] sum over the windows of reach_w                                                                                       */
+    int32_t *used_sum;           /* [n_zmw] sum over the windows of the passes the polish used there (ec x n_windows); 0 for a ZMW that was not polished            */
+    int32_t *used_min;           /* [n_zmw] min over the windows of the same; 0 for a ZMW that was not polished                                                   */
+} ccsx_coverage_report;
+typedef struct ccsx_coverage_request {
+    const ccsx_coverage_opts *opts;      /* NULL = ccsx_coverage_opts_default                                                                                    */
+    ccsx_coverage_report     *report;
+    uint32_t                  gate;      /* bit mask, bit v for verdict v = 2 .. 5; 0 = detection only                                                           */
+    int32_t                   reserved[2];   /* must be 0                                                                                                        */
+} ccsx_coverage_request;
+void        ccsx_coverage_opts_default(ccsx_coverage_opts *o);
+int         ccsx_coverage_rule_version(void);
+
+/* ---- every optional request of the fused path in one struct: the argument lists of the ccsx_consensus_* / ccsx_submit_* family stop growing here; a new request
+ * joins this struct.  Every member may be NULL (all NULL, or a NULL ccsx_requests = ccsx_consensus_batch / ccsx_submit); reserved must be NULL.  The members mean
+ * what they mean in ccsx_consensus_control / ccsx_submit_control, which forward to the same path and give the same results for the same members.
+ *   ccsx_consensus_requests  synchronous (slot 0).
+ *   ccsx_submit_requests     ticketed like ccsx_submit; the ccsx_requests struct itself is read during the call only.                                             */
+typedef struct ccsx_requests {
+    const ccsx_extras           *ex;
+    const ccsx_fold_request     *fold;
+    const ccsx_adapter_request  *adapters;
+    const ccsx_control_request  *control;
+    const ccsx_coverage_request *coverage;
+    const void                  *reserved[3];
+} ccsx_requests;
+int         ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq);
+int         ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket);
 
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
