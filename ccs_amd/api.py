@@ -79,6 +79,7 @@ class CDrafts(C.Structure):
 
 
 QV_ONLY = 1     # ccsx_polish_batch flag (CCSX_QV_ONLY)
+POA_LOG_WORDS = 5   # CCSX_POA_LOG_WORDS: I, end score, end position, threaded, vertices after the pass
 
 
 # ---- the heteroduplex finder (include/ccsx.h ccsx_hd_*; DESIGN.md §2 "Heteroduplex rule")
@@ -637,6 +638,7 @@ EXPORTS = [
     "ccsx_build_flags", "ccsx_runtime_switches", "ccsx_pci_numa_node", "ccsx_device_numa_node", "ccsx_bind_thread_to_node", "ccsx_bind_thread_to_device", "ccsx_draft_layout", "ccsx_draft_batch", "ccsx_polish_batch", "ccsx_submit_draft", "ccsx_submit_polish",
     "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
     "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished", "ccsx_stage_align_ev",
+    "ccsx_poa_log", "ccsx_stage_poa",
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
     "ccsx_consensus_hd", "ccsx_submit_hd",
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
@@ -679,6 +681,8 @@ def lib() -> C.CDLL:
         L.ccsx_stage_windows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
         L.ccsx_stage_align_ev.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_uint8), C.c_int32]
+        L.ccsx_poa_log.argtypes = [C.c_void_p, C.c_int32]
+        L.ccsx_stage_poa.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
         L.ccsx_synth_generate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_uint64, C.POINTER(C.POINTER(CSynth))]
         L.ccsx_synth_free.argtypes = [C.POINTER(CSynth)]
@@ -1380,6 +1384,26 @@ class Handle:
         v, s = C.c_int32(), C.c_int32()
         self._check(self._L.ccsx_stage_align_ev(self._h, r, _ptr(buf, C.c_int32), ld + 1, C.byref(v), C.byref(s), _ptr(dirty, C.c_uint8), ld), "ccsx_stage_align_ev")
         return buf, v.value, s.value, dirty[:ld]
+
+    def poa_log(self, on: bool = True):
+        """ask for (or drop) the POA log: batches staged from now on keep one record per (ZMW, draft generator, pass); the layout is in
+        include/ccsx.h under "The POA log" """
+        self._check(self._L.ccsx_poa_log(self._h, int(bool(on))), "ccsx_poa_log")
+
+    def stage_poa(self, z: int):
+        """the POA log of ZMW z in the batch run last: per draft generator (0 = POA on pass 0, 1 = the fallback) an int32 array [k, 6] of the passes the
+        generator's DP saw, one row (rr, I, end score, end position or -1, threaded 0/1, vertices after the pass) per pass, rr = 1 .. in order"""
+        out = []
+        for gen in (0, 1):
+            buf, n = np.zeros((64, POA_LOG_WORDS), np.int32), C.c_int32(0)
+            rc = self._L.ccsx_stage_poa(self._h, z, gen, _ptr(buf, C.c_int32), len(buf), C.byref(n))
+            if rc != 0 and n.value > len(buf):           # refused for its size alone: the batch has a ZMW of more passes, n says how many
+                buf = np.zeros((n.value, POA_LOG_WORDS), np.int32)
+                rc = self._L.ccsx_stage_poa(self._h, z, gen, _ptr(buf, C.c_int32), len(buf), C.byref(n))
+            self._check(rc, "ccsx_stage_poa")
+            rr = [k for k in range(n.value) if buf[k, 0] >= 0]
+            out.append(np.array([[k, *buf[k]] for k in rr], np.int32).reshape(len(rr), POA_LOG_WORDS + 1))
+        return out
 
     def stage_windows(self, z: int) -> np.ndarray:
         cap = 1 << 14

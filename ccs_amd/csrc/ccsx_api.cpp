@@ -136,6 +136,7 @@ struct Slot {
     DevBuf d_adapt;                               // adapter screen only (ccsx_adapter_request): [9][n] report + [n][16] hits
     DevBuf d_ctl;                                 // control screen only (ccsx_control_request): the slot's own index, then the [8][n] report
     DevBuf d_cov;                                 // coverage screen only (ccsx_coverage_request): the [10][n] report, then one byte per window slot
+    DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
@@ -184,6 +185,7 @@ struct ccsx_handle_s {
     double epoch_ms = 0.0;            // minutes (epoch_ms = its distance from the creation), so that the float milliseconds HIP reports stay well below
                                       // 2^23 ms and keep their sub-microsecond resolution in long runs
     bool poisoned = false;            // a submit failed after work was enqueued: the handle refuses further batches
+    bool poa_log = false;             // ccsx_poa_log: batches staged from now on keep the POA log
     ccsx_model model;
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
@@ -651,6 +653,12 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, co
     }
     if ((rc = upload_inputs(S, b, kin, st, P)) || (rc = reserve_state(S, (size_t)n, (size_t)R, kin, pile, W.tandem, P))) return rc;
     if ((rc = grow_scratch(h, n, R, T, P))) return rc;
+    if (h->poa_log) {                                            // every record starts as -1: "this generator did not reach this pass"
+        const size_t bytes = (size_t)(n > 0 ? n : 1) * 2 * (size_t)T.nr_max * CCSX_POA_LOG_WORDS * 4;
+        if (S.d_poa_log.reserve(bytes)) return -2;
+        P.poa_log = (int32_t *)S.d_poa_log.p; P.poa_log_stride = T.nr_max;
+        HIPTRY(hipMemsetAsync(P.poa_log, 0xff, bytes, st));
+    }
     P.n_zmw = n; P.n_reads = R; P.maxL_max = (int32_t)T.maxL_max; P.vcap_max = (int32_t)T.vcap_max; P.need_max = T.need_max; P.max_reads = T.nr_max;
     P.n_quads = T.n_quads; P.total_wslots = T.total_wslots;
     P.opts = h->opts;
@@ -1571,6 +1579,30 @@ int ccsx_stage_align_ev(ccsx_handle h, int32_t r, int32_t *rstart, int32_t cap, 
         for (int k = 1; k < 2 * nw; ++k)
             for (int p = col(k - 1); p < col(k); ++p) dirty[p] = (p - col(k - 1) < 32) ? (uint8_t)((dm[k] >> (p - col(k - 1))) & 1u) : 0;
     }
+    return 0;
+}
+
+// the POA log of the batch the handle ran last (include/ccsx.h "The POA log")
+int ccsx_poa_log(ccsx_handle h, int32_t on)
+{
+    if (!h) { ccsx_set_error("ccsx_poa_log: null handle"); return -1; }
+    h->poa_log = on != 0;
+    return 0;
+}
+
+int ccsx_stage_poa(ccsx_handle h, int32_t z, int32_t generator, int32_t *rec, int32_t cap_records, int32_t *n_records)
+{
+    if (!h || !rec || !n_records) { ccsx_set_error("ccsx_stage_poa: null argument"); return -1; }
+    const Slot &S = h->slot[h->last];
+    if (!S.ran || S.inflight || !S.P.poa_log) { ccsx_set_error("ccsx_stage_poa: the last batch was not run with the POA log (ccsx_poa_log first), or is still in flight"); return -1; }
+    if (z < 0 || z >= S.P.n_zmw || generator < 0 || generator > 1) { ccsx_set_error("ccsx_stage_poa: bad index"); return -1; }
+    const int32_t n = S.P.poa_log_stride;
+    if (n > cap_records) { *n_records = n; ccsx_set_error("ccsx_stage_poa: buffer too small (n_records holds the records needed)"); return -1; }
+    HIPTRY(hipSetDevice(h->device));
+    HIPTRY(hipStreamSynchronize(h->s_draft));
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    HIPTRY(hipMemcpy(rec, S.P.poa_log + ((size_t)(2 * z + generator) * n) * CCSX_POA_LOG_WORDS, (size_t)n * CCSX_POA_LOG_WORDS * 4, hipMemcpyDeviceToHost));
+    *n_records = n;
     return 0;
 }
 

@@ -149,6 +149,9 @@ struct KParams {
     uint32_t cov_gate;         // bit v: a ZMW with verdict v = 2 .. 5 gets the status CCSX_DRAFT_TOO_DIFFERENT + (v - 2) and no consensus
     int32_t *cov_zi;           // [10][n] verdict, np_aligned, spans, cov_max, clean_min, drop_window, drop_windows, reach_sum, used_sum, used_min
     uint8_t *cov_reach;        // [wslots] reach_w of every window, indexed as wmeta is ((wb_off[z] - z) + w): k_coverage writes it, k_coverage_post reads it
+    // ---- POA log (ccsx_poa_log; NULL otherwise): include/ccsx.h "The POA log".  Filled with -1 when the batch is staged
+    int32_t *poa_log;          // [n][2 generators][poa_log_stride passes][CCSX_POA_LOG_WORDS], written by k_poa_thread
+    int32_t poa_log_stride;    // = max_reads
 };
 #define CCSX_COVERAGE_PLANES 10
 #define CCSX_COVERAGE_PRE_GATE 0x1cu   // the gate bits of the verdicts k_coverage reaches before the polish (2, 3, 4)

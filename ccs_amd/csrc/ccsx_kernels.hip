@@ -910,7 +910,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     const int I = rfl((int)(P.base_off[r + 1] - P.base_off[r]));
     const int kend = rfl(g.st[ST_KEND]), bsc = rfl(g.st[ST_BS]);
     // SPEC "POA gate": a pass is threaded only if its alignment reaches the read's last row with a score of at least 1.0 per base
-    if (kend < 0 || bsc < I) return;
+    // the POA log (ccsx_poa_log; a null pointer otherwise): one record per (ZMW, generator, pass), written by lane 0 wherever the pass ends
+    int32_t *const plog = (P.poa_log && pass < 2 && rr < P.poa_log_stride) ? P.poa_log + ((size_t)(2 * z + pass) * P.poa_log_stride + rr) * CCSX_POA_LOG_WORDS : nullptr;
+    auto log_pass = [&](int threaded, int nv) { if (plog && lane == 0) { plog[0] = I; plog[1] = bsc; plog[2] = kend; plog[3] = threaded; plog[4] = nv; } };
+    if (kend < 0 || bsc < I) { log_pass(0, g.st[ST_N]); return; }
     const int rev = rfl(((P.flags[r] & 1) != g.st[ST_REV0]) ? 1 : 0);
     const int vcap = rfl(P.vcap[z]);
     const int n0 = rfl(g.st[ST_N]);
@@ -1058,7 +1061,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         }
     }
     nnew = rfl(nnew);
-    if (n0 + nnew > vcap) { if (lane == 0) g.st[ST_OK] = 0; return; }
+    if (n0 + nnew > vcap) { if (lane == 0) g.st[ST_OK] = 0; log_pass(0, n0); return; }
     __threadfence_block();
     TPH(11);
     int carry = 0;
@@ -1158,6 +1161,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     }
     __threadfence_block();
     if (lane == 0) { g.st[ST_N] = n; g.st[ST_NADDED] += 1; g.st[ST_PAR] ^= 1; }
+    log_pass(1, n);
     (void)npoa;
     TPH(13);
 }

@@ -290,6 +290,20 @@ int         ccsx_stage_windows(ccsx_handle h, int32_t zmw_index, int32_t *bounds
  * split or partial pass is 1; dirty[] of a pass that is not valid is 0.  For parity tests (tests/test_align_gpu.py).                                            */
 int         ccsx_stage_align_ev(ccsx_handle h, int32_t read_index, int32_t *rstart, int32_t cap, int32_t *valid, int32_t *score,
                                 uint8_t *dirty, int32_t dirty_cap);
+/* The POA log: a per-pass witness of the draft stage, off by default.  ccsx_poa_log(h, 1) asks for it; it holds from the next batch the handle stages (any entry
+ * point) until ccsx_poa_log(h, 0).  While it is on, k_poa_thread writes one record of CCSX_POA_LOG_WORDS int32 per (ZMW, draft generator, pass rr of the POA):
+ *   [0] I              length of the pass (rr-th pass of the generator's order: backbone + rr, wrapping)
+ *   [1] end score      best M[v][I] over the graph (NEG = -2^28 when no vertex holds row I in its band)
+ *   [2] end position   topological position of the end cell's vertex before the pass is threaded, -1 when there is none
+ *   [3] threaded       1 = the pass went into the graph; 0 = the gate refused it, or threading it would overflow the vertex capacity (the generator then fails)
+ *   [4] vertices       of the graph after the pass
+ * With the log off the kernel is given a null pointer, stores nothing, and every output is byte for byte what it is with the log on.
+ * ccsx_stage_poa reads the log of the batch the handle ran last (any entry point, after it has been waited for): generator 0 = POA on pass 0, 1 = the fallback.
+ * rec receives `*n_records` records indexed by rr (cap_records >= the most passes of a ZMW in the batch; else refused, with that number in `*n_records`); record 0 (the backbone: k_poa_init chains
+ * it, no DP runs) and every pass the generator did not reach for this ZMW have I = -1 in all five words.  For parity tests (tests/test_poa_gpu.py).            */
+#define CCSX_POA_LOG_WORDS 5
+int         ccsx_poa_log(ccsx_handle h, int32_t on);
+int         ccsx_stage_poa(ccsx_handle h, int32_t zmw_index, int32_t generator, int32_t *rec, int32_t cap_records, int32_t *n_records);
 
 /* ---- the heteroduplex finder (docs/faq/mode-heteroduplex-filtering.md:25-33, docs/how-does-ccs-work.md:65-72; the rule: DESIGN.md §2 "Heteroduplex rule").
  * ccsx_hd_batch is the third seam beside ccsx_draft_batch and ccsx_polish_batch: on the caller's drafts it runs the polish seam's alignment cascade and window map,

@@ -114,6 +114,10 @@ static void orc_counts_flush(void)
 void orc_counts_sync(void) { orc_counts_flush(); }
 static __thread int g_poa_scores[64], g_poa_nscores = 0;   /* test hook: end scores of the passes threaded into the last POA */
 int orc_poa_last_scores(int *out) { for (int i = 0; i < g_poa_nscores; ++i) out[i] = g_poa_scores[i]; return g_poa_nscores; }
+/* ... and the whole per-pass record of the same passes, as the engine's POA log holds it (include/ccsx.h "The POA log"): I, end score, topological position of the end
+ * cell's vertex before threading (-1: none), threaded 0/1, vertices after the pass.  Record k belongs to score k: the k+1-th pass of the generator's order */
+static __thread int g_poa_rec[64][5];
+int orc_poa_last_records(int *out) { for (int i = 0; i < g_poa_nscores; ++i) for (int f = 0; f < 5; ++f) out[5 * i + f] = g_poa_rec[i][f]; return g_poa_nscores; }
 #define MAX_PASSES 255      /* passes of a ZMW that are used (include/ccsx.h CCSX_MAX_PASSES) */
 #define MAXPRED   7         /* in-edge cap of a POA vertex (SPEC v3; the device stores a move in a nibble) */
 #define WIN_CORE  22
@@ -470,12 +474,13 @@ static int poa_add_read(poa_t *g, const uint8_t *r, int I, int32_t *pathv /* scr
         dp_column(g->base[v], r, I, lo, np, plo, pM, g->M + (size_t)v * BAND, g->mv + (size_t)v * BAND, &g->colmax[v], &g->bestrow[v]);
     }
     /* end vertex: best M[v][I], first in topological order on ties */
-    int vend = -1; int32_t bs = NEG;
+    int vend = -1, kend = -1; int32_t bs = NEG;
     for (int k = 0; k < n0; ++k) {
         int v = g->order[k]; int o = I - g->lo[v];
-        if (o >= 0 && o < g_bw) { int32_t x = g->M[(size_t)v * BAND + o]; if (x > NEG / 2 && x > bs) { bs = x; vend = v; } }
+        if (o >= 0 && o < g_bw) { int32_t x = g->M[(size_t)v * BAND + o]; if (x > NEG / 2 && x > bs) { bs = x; vend = v; kend = k; } }
     }
-    if (g_poa_nscores < 64) g_poa_scores[g_poa_nscores++] = bs;
+    int *rec = NULL;
+    if (g_poa_nscores < 64) { rec = g_poa_rec[g_poa_nscores]; rec[0] = I; rec[1] = bs; rec[2] = kend; rec[3] = 0; rec[4] = n0; g_poa_scores[g_poa_nscores++] = bs; }
     /* SPEC "POA gate": a pass is threaded only if its alignment reaches the read's last row with a score of at least 1.0 per base
      * (the gate of step 3): a pass the band has lost, or junk, adds nothing to the graph                                        */
     if (vend < 0 || bs < I) return 0;   /* EXPERIMENT: lost band -> retry wide */
@@ -501,6 +506,7 @@ static int poa_add_read(poa_t *g, const uint8_t *r, int I, int32_t *pathv /* scr
         pathv[i] = w;
     }
     g->nadded += 1; poa_renumber(g);
+    if (rec) { rec[3] = 1; rec[4] = g->n; }
     if (g_path_align && pa_n < PA_MAXREADS) { pa_path[pa_n] = (int32_t *)malloc(sizeof(int32_t) * (I + 1)); memcpy(pa_path[pa_n], pathv, sizeof(int32_t) * I); pa_len[pa_n] = I; pa_read[pa_n] = pa_cur_read; ++pa_n; }
     return 1;
 }

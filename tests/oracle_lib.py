@@ -71,6 +71,24 @@ def poa_draft(batch, z, max_poa_cov=5):
     return draft[:n].copy()
 
 
+def poa_generator(reads, flags, max_poa_cov, backbone=0):
+    """orc_poa_draft_bb on one ZMW's full-length passes (native orientation): one draft generator with its backbone and coverage.
+    Returns (draft, or None where the generator fails; int array [k, 5] of orc_poa_last_records: I, end score, end position, threaded, vertices, one row per pass
+    after the backbone)"""
+    n = len(reads)
+    while n > 0 and (int(flags[n - 1]) & 2): n -= 1
+    rel = np.concatenate([[0], np.cumsum([len(r) for r in reads[:n]])]).astype(np.int64)
+    bases = np.ascontiguousarray(np.concatenate([np.asarray(r, np.uint8) for r in reads[:n]] + [np.zeros(1, np.uint8)]))
+    fl = np.ascontiguousarray(np.asarray(flags[:n], np.uint8))
+    maxL = int(np.max(np.diff(rel)))
+    dcap, vcap = maxL + maxL // 4 + 64, (5 * maxL) // 2 + 256
+    draft = np.zeros(dcap, np.uint8)
+    k = lib().orc_poa_draft_bb(n, _p(rel, C.c_int64), _p(bases, C.c_uint8), _p(fl, C.c_uint8), int(max_poa_cov), vcap, _p(draft, C.c_uint8), dcap, int(backbone))
+    rec = np.zeros((64, 5), np.int32)
+    m = lib().orc_poa_last_records(_p(rec, C.c_int32))
+    return (draft[:k].copy() if k > 0 else None), rec[:m].copy()
+
+
 def orient(bases, rev):
     return (3 - bases[::-1]).astype(np.uint8) if rev else bases.copy()
 
