@@ -638,7 +638,7 @@ EXPORTS = [
     "ccsx_build_flags", "ccsx_runtime_switches", "ccsx_pci_numa_node", "ccsx_device_numa_node", "ccsx_bind_thread_to_node", "ccsx_bind_thread_to_device", "ccsx_draft_layout", "ccsx_draft_batch", "ccsx_polish_batch", "ccsx_submit_draft", "ccsx_submit_polish",
     "ccsx_hd_opts_default", "ccsx_hd_rule_version", "ccsx_hd_batch",
     "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished", "ccsx_stage_align_ev",
-    "ccsx_poa_log", "ccsx_stage_poa",
+    "ccsx_poa_log", "ccsx_stage_poa", "ccsx_stage_wmeta",
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
     "ccsx_consensus_hd", "ccsx_submit_hd",
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
@@ -681,6 +681,7 @@ def lib() -> C.CDLL:
         L.ccsx_stage_windows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
         L.ccsx_stage_align_ev.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_uint8), C.c_int32]
+        L.ccsx_stage_wmeta.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
         L.ccsx_poa_log.argtypes = [C.c_void_p, C.c_int32]
         L.ccsx_stage_poa.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
         L.ccsx_synth_generate.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1411,6 +1412,15 @@ class Handle:
         n = C.c_int32()
         self._check(self._L.ccsx_stage_windows(self._h, z, _ptr(buf, C.c_int32), cap, C.byref(n)), "ccsx_stage_windows")
         return buf[: n.value + 1].copy()
+
+    def stage_wmeta(self, z: int) -> np.ndarray:
+        """what k_polish left per window of ZMW z: int32 [n_windows, 5] = (core length, usable reads of the last round over all passes, the same over the
+        full-length passes only, non-convergent 0/1, scoring rounds)"""
+        cap = 1 << 14
+        buf = np.zeros((cap, 5), np.int32)
+        n = C.c_int32()
+        self._check(self._L.ccsx_stage_wmeta(self._h, z, _ptr(buf, C.c_int32), cap, C.byref(n)), "ccsx_stage_wmeta")
+        return buf[: n.value].copy()
 
     def close(self):
         if self._h:

@@ -1632,6 +1632,28 @@ int ccsx_stage_polished(ccsx_handle h, int32_t z, uint8_t *tpl, int32_t *meta, i
     return 0;
 }
 
+// what k_polish left per window of ZMW z (P.wmeta, a plain copy): core length, usable reads of the last round (all passes / full-length passes only), non-convergence, rounds
+int ccsx_stage_wmeta(ccsx_handle h, int32_t z, int32_t *meta, int32_t cap, int32_t *n_windows)
+{
+    if (int rc = stage_guard(h, z, false, "ccsx_stage_wmeta")) return rc;
+    if (!meta || !n_windows) { ccsx_set_error("ccsx_stage_wmeta: null argument"); return -1; }
+    const Slot &S = h->slot[0];
+    int32_t st = 0, nw = 0;
+    HIPTRY(hipMemcpy(&st, S.P.zstat + z, 4, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(&nw, S.P.nwin + z, 4, hipMemcpyDeviceToHost));
+    if (st != CCSX_SUCCESS) nw = 0;                      // (a ZMW that failed before the polish has no polished window)
+    if (nw > cap) { ccsx_set_error("ccsx_stage_wmeta: buffer too small"); return -1; }
+    if (nw > 0) {
+        std::vector<int4> wm(nw);
+        HIPTRY(hipMemcpy(wm.data(), S.P.wmeta + (size_t)(S.wb_off[z] - z), (size_t)nw * sizeof(int4), hipMemcpyDeviceToHost));
+        for (int w = 0; w < nw; ++w) {
+            meta[5 * w] = wm[w].x; meta[5 * w + 1] = wm[w].y & 255; meta[5 * w + 2] = wm[w].y >> 8; meta[5 * w + 3] = wm[w].z; meta[5 * w + 4] = wm[w].w;
+        }
+    }
+    *n_windows = nw;
+    return 0;
+}
+
 // ---- the heteroduplex finder: the third seam (include/ccsx.h).  Synchronous, on slot 0 like ccsx_upload / ccsx_run, so that the stage accessors report what it used.
 void ccsx_hd_opts_default(ccsx_hd_opts *o)
 {

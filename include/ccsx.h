@@ -290,6 +290,10 @@ int         ccsx_stage_windows(ccsx_handle h, int32_t zmw_index, int32_t *bounds
  * split or partial pass is 1; dirty[] of a pass that is not valid is 0.  For parity tests (tests/test_align_gpu.py).                                            */
 int         ccsx_stage_align_ev(ccsx_handle h, int32_t read_index, int32_t *rstart, int32_t cap, int32_t *valid, int32_t *score,
                                 uint8_t *dirty, int32_t dirty_cap);
+/* What k_polish left per window of ZMW zmw_index, copied from the device as it stands: meta[5 w .. 5 w + 4] = core length after the polish, usable reads of the last
+ * round (after the alpha/beta and z-score gates) over all passes, the same over the full-length passes only, 1 if the window ended NON_CONVERGENT, scoring rounds.
+ * cap counts windows.  A ZMW that failed before the polish reports 0 windows.  For parity tests (tests/test_filter_gpu.py).                                       */
+int         ccsx_stage_wmeta(ccsx_handle h, int32_t zmw_index, int32_t *meta, int32_t cap, int32_t *n_windows);
 /* The POA log: a per-pass witness of the draft stage, off by default.  ccsx_poa_log(h, 1) asks for it; it holds from the next batch the handle stages (any entry
  * point) until ccsx_poa_log(h, 0).  While it is on, k_poa_thread writes one record of CCSX_POA_LOG_WORDS int32 per (ZMW, draft generator, pass rr of the POA):
  *   [0] I              length of the pass (rr-th pass of the generator's order: backbone + rr, wrapping)
