@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import weakref
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
@@ -383,6 +383,43 @@ def _coverage_request(opts: "CoverageOpts | None", gate: int, crep: CCoverageRep
     return CCoverageRequest(C.pointer(o), C.pointer(crep), int(gate), (C.c_int32 * 2)(0, 0)), o
 
 
+# ---- pass orientation (include/ccsx.h ccsx_orient_*; DESIGN.md §2 "Pass orientation")
+PASS_STRAND_UNKNOWN = 0x8     # flags bit 3: bit 0 of this pass is a guess; k_orient decides it against the ZMW's anchor pass
+ORIENT_GIVEN, ORIENT_ANCHOR, ORIENT_SAME, ORIENT_OPPOSITE, ORIENT_UNDETERMINED, ORIENT_NO_ANCHOR = range(6)
+ORIENT_CALL_NAMES = ["GIVEN", "ANCHOR", "SAME", "OPPOSITE", "UNDETERMINED", "NO_ANCHOR"]
+
+
+class OrientOpts(C.Structure):
+    _fields_ = [("min_votes", C.c_int32), ("ratio", C.c_int32)]
+
+
+class COrientReport(C.Structure):
+    _fields_ = [("n_reads", C.c_int32), ("strand", C.POINTER(C.c_uint8)), ("call", C.POINTER(C.c_uint8)), ("votes_same", C.POINTER(C.c_int32)),
+                ("votes_opp", C.POINTER(C.c_int32))]
+
+
+def orient_opts_default() -> OrientOpts:
+    o = OrientOpts()
+    lib().ccsx_orient_opts_default(C.byref(o))
+    return o
+
+
+class OrientReport:
+    """ccsx_orient_report: per pass the resolved strand bit, the call (ORIENT_*) and the two vote counts."""
+    FIELDS = ("strand", "call", "votes_same", "votes_opp")
+
+    def __init__(self, strand, call, votes_same, votes_opp):
+        self.strand, self.call, self.votes_same, self.votes_opp = strand, call, votes_same, votes_opp
+
+    @classmethod
+    def allocate(cls, n_reads: int) -> "OrientReport":
+        return cls(np.zeros(n_reads, np.uint8), np.zeros(n_reads, np.uint8), np.zeros(n_reads, np.int32), np.zeros(n_reads, np.int32))
+
+    def c_struct(self) -> COrientReport:
+        return COrientReport(len(self.strand), _ptr(self.strand, C.c_uint8), _ptr(self.call, C.c_uint8), _ptr(self.votes_same, C.c_int32),
+                             _ptr(self.votes_opp, C.c_int32))
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -645,6 +682,7 @@ EXPORTS = [
     "ccsx_adapter_opts_default", "ccsx_adapter_rule_version", "ccsx_adapter_set_default", "ccsx_consensus_screen", "ccsx_submit_screen",
     "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
     "ccsx_coverage_opts_default", "ccsx_coverage_rule_version", "ccsx_consensus_requests", "ccsx_submit_requests",
+    "ccsx_orient_opts_default", "ccsx_orient_rule_version", "ccsx_orient_batch", "ccsx_set_orient_opts", "ccsx_stage_orient",
     "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
     "ccsx_inflate_blocks_host",
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
@@ -736,6 +774,11 @@ def lib() -> C.CDLL:
         L.ccsx_coverage_opts_default.argtypes = [C.POINTER(CoverageOpts)]
         L.ccsx_consensus_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests)]
         L.ccsx_submit_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(C.c_int64)]
+        L.ccsx_orient_opts_default.restype = None
+        L.ccsx_orient_opts_default.argtypes = [C.POINTER(OrientOpts)]
+        L.ccsx_orient_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(OrientOpts), C.POINTER(COrientReport)]
+        L.ccsx_set_orient_opts.argtypes = [C.c_void_p, C.POINTER(OrientOpts)]
+        L.ccsx_stage_orient.argtypes = [C.c_void_p, C.POINTER(COrientReport)]
         _call = [C.POINTER(C.c_uint8), C.c_int64, C.POINTER(DeflateBlock), C.c_int32, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int32)]
         L.ccsx_inflater_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
         L.ccsx_inflater_destroy.argtypes = [C.c_void_p]
@@ -839,6 +882,16 @@ class Batch:
             arr[:] = src
             setattr(out, name, arr)
         out._pinned = keep
+        return out
+
+    def with_unknown_strands(self, guess=None) -> "Batch":
+        """a copy whose every pass carries PASS_STRAND_UNKNOWN; guess (one value per pass, or None: the batch's own bits) replaces bit 0, now only a prior"""
+        f = self.flags.copy()
+        if guess is not None:
+            f = (f & np.uint8(0xfe)) | (np.asarray(guess).astype(np.uint8) & np.uint8(1))
+        out = replace(self, flags=np.ascontiguousarray(f | np.uint8(PASS_STRAND_UNKNOWN)))
+        if hasattr(self, "_pinned"):
+            out._pinned = self._pinned                   # (the copy shares the page-locked arrays)
         return out
 
     def slice(self, z0: int, z1: int) -> "Batch":
@@ -1145,6 +1198,7 @@ class Handle:
         if rc != 0:
             raise RuntimeError("ccsx_create failed: " + self._L.ccsx_last_error().decode())
         self._keep = None
+        self._sync_reads = 0                             # passes of the last batch staged on slot 0 (stage_orient)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -1160,12 +1214,15 @@ class Handle:
             name, args = f"ccsx_{form}_requests", (_keep[-1],)
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
+        if form == "consensus":
+            self._sync_reads = int(batch.read_off[-1])
         return cb, cr
 
     def consensus(self, batch: Batch) -> Results:
         res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(self._L.ccsx_consensus_batch(self._h, C.byref(cb), C.byref(cr)), "ccsx_consensus_batch")
+        self._sync_reads = int(batch.read_off[-1])
         return res
 
     # ---- the two seams (docs/img/ccs-impl.png): draft stage alone, polish stage on caller-supplied drafts
@@ -1187,6 +1244,7 @@ class Handle:
         cb, cd, cr = batch.c_struct(), drafts.c_struct(), rep.c_struct()
         o = opts if opts is not None else hd_opts_default()
         self._check(self._L.ccsx_hd_batch(self._h, C.byref(cb), C.byref(cd), C.byref(o), C.byref(cr)), "ccsx_hd_batch")
+        self._sync_reads = int(batch.read_off[-1])
         return rep
 
     # ---- the fourth seam: the training counts on caller-supplied drafts (no polish runs; DESIGN.md §2 "Model training")
@@ -1194,7 +1252,26 @@ class Handle:
         tc = TrainCounts.allocate(batch)
         cb, cd, cc = batch.c_struct(), drafts.c_struct(), tc.c_struct()
         self._check(self._L.ccsx_train_batch(self._h, C.byref(cb), C.byref(cd), C.byref(cc)), "ccsx_train_batch")
+        self._sync_reads = int(batch.read_off[-1])
         return tc
+
+    # ---- pass orientation (DESIGN.md §2 "Pass orientation"): the seam, the options of every other path, the last synchronous run's report
+    def orient(self, batch: Batch, opts: "OrientOpts | None" = None) -> OrientReport:
+        rep = OrientReport.allocate(int(batch.read_off[-1]))
+        cb, cr = batch.c_struct(), rep.c_struct()
+        self._check(self._L.ccsx_orient_batch(self._h, C.byref(cb), C.byref(opts) if opts is not None else None, C.byref(cr)), "ccsx_orient_batch")
+        self._sync_reads = int(batch.read_off[-1])
+        return rep
+
+    def set_orient_opts(self, opts: "OrientOpts | None" = None):
+        self._check(self._L.ccsx_set_orient_opts(self._h, C.byref(opts) if opts is not None else None), "ccsx_set_orient_opts")
+
+    def stage_orient(self, n_reads: "int | None" = None) -> OrientReport:
+        """the report of the last synchronous run on slot 0 (n_reads: its passes; None = those of the last batch this object ran synchronously)"""
+        rep = OrientReport.allocate(self._sync_reads if n_reads is None else n_reads)
+        cr = rep.c_struct()
+        self._check(self._L.ccsx_stage_orient(self._h, C.byref(cr)), "ccsx_stage_orient")
+        return rep
 
     # ---- the pileup summary (sa sm sx): the fused path plus per-base planes from the kinetics alignment
     def consensus_pileup(self, batch: Batch) -> tuple["Results", "Pileup"]:
@@ -1293,6 +1370,7 @@ class Handle:
         self._keep = batch
         cb = batch.c_struct()
         self._check(self._L.ccsx_upload(self._h, C.byref(cb)), "ccsx_upload")
+        self._sync_reads = int(batch.read_off[-1])
 
     def run(self):
         self._check(self._L.ccsx_run(self._h), "ccsx_run")

@@ -460,6 +460,7 @@ struct Subread {
     bool has_snr = false, has_n = false;
     uint8_t strand = 0;         // 0 forward / 1 reverse pass (set by the driver: cx direction bits, else alternation)
     uint8_t partial = 0;        // ccsx_batch.flags bits 1-2: 2 = partial pass with the adapter at its start, 6 = ... at its end
+    uint8_t strand_unknown = 0; // ccsx_batch.flags bit 3 (--orient-passes: no cx direction bit, `strand` is the alternation guess)
     uint32_t len = 0;           // bases
     const uint8_t *seq = nullptr;                              // BAM nibbles, two per byte
     const uint8_t *pw_p = nullptr, *ip_p = nullptr;            // payload of the B arrays as stored

@@ -82,6 +82,7 @@ struct Options {
     std::string control;          // --control FILE.fasta: screen the drafts for the spike-in control (fail class 0x2); control ZMWs leave the main output
     std::vector<uint8_t> control_codes;   // ... its bases
     ccsx_control_seq control_seq{};       // ... as the requests name them
+    bool orient_passes = false;   // --orient-passes: subreads without cx direction bits are submitted strand-unknown (flags bit 3; DESIGN.md §2 "Pass orientation")
     bool coverage_filters = false;   // --coverage-filters: the coverage screen with all four gate bits (DESIGN.md §2 "Coverage rule"; off here)
     int cov_drop_percent = -1, cov_block = -1;   // --coverage-drop-percent / --coverage-block: overrides of ccsx_coverage_opts (-1: the default)
     ccsx_coverage_opts coverage_opts{};          // ... the options every ticket carries
@@ -210,6 +211,8 @@ void usage()
                  "      --min-rq F            minimum predicted accuracy [0.99]\n"
                  "      --maxPoaCoverage N    subreads used for the draft [5]\n"
                  "      --by-strand           one consensus per strand, read names end in /fwd or /rev\n"
+                 "      --orient-passes       the engine determines the strand of every subread whose cx tag carries no direction bit, against the ZMW's\n"
+                 "                            subread closest to the median length; alternation is then only a prior for passes it cannot call [off]\n"
                  "      --no-partial-passes   do not use the first / last (one-adapter) subread of a ZMW in the polish\n"
                  "      --qv-binning          write 7-bin per-base QVs (Q3 Q10 Q17 Q22 Q27 Q35 Q40)\n"
                  "      --hifi-kinetics       averaged per-strand kinetics: tags fi fp fn ri rp rn (ip pw with --by-strand)\n"
@@ -377,6 +380,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--adapters") o.adapters = need(a.c_str());
         else if (a == "--control") o.control = need(a.c_str());
         else if (a == "--coverage-filters") o.coverage_filters = true;
+        else if (a == "--orient-passes") o.orient_passes = true;
         else if (a == "--coverage-drop-percent" || a == "--coverage-block") {
             const bool pct = a == "--coverage-drop-percent";
             const std::string v = need(a.c_str());
@@ -424,6 +428,9 @@ bool parse(int argc, char **argv, Options &o)
         if (o.pileup || o.qv_binning || o.o.hifi_kinetics || o.min_tandem > 0)
             refuse("writes no reads: --pileup-summary, --qv-binning, --hifi-kinetics and --min-tandem-repeat-length are not supported with it");
         if (o.chunk_n > 1) refuse("reads the whole file: --chunk is not supported with it");
+    }
+    if (o.orient_passes && o.by_strand) {                    // the strands are split on the host, before the engine has seen a pass
+        std::fprintf(stderr, "ccs: --orient-passes combined with --by-strand is not supported\n"); std::exit(2);
     }
     if (!o.fail_reads.empty()) {
         if (o.fail_reads.size() < 5 || o.fail_reads.compare(o.fail_reads.size() - 4, 4, ".bam") != 0) {
@@ -651,8 +658,10 @@ struct ArenaPool {                          // free list of page-locked arenas: 
     void put(std::unique_ptr<Arena> a) { if (a) { std::lock_guard<std::mutex> l(m); free_.push_back(std::move(a)); } }
 };
 
-void pack(Batch &b, Arena &arena)
+// returns the passes packed strand-unknown (--orient-passes)
+long long pack(Batch &b, Arena &arena)
 {
+    long long unknown = 0;
     b.read_off.assign(1, 0); b.base_off.assign(1, 0);
     b.slot.assign(b.zmws.size(), -1);
     int64_t total = 0;
@@ -671,13 +680,15 @@ void pack(Batch &b, Arena &arena)
             const size_t L = r.size();
             r.decode_bases(bases + at); r.decode_pw(pw + at); r.decode_ip(ipd + at);      // the one and only decode: record -> staging
             at += (int64_t)L;
-            b.flags.push_back((uint8_t)(r.strand | r.partial));
+            b.flags.push_back((uint8_t)(r.strand | r.partial | (r.strand_unknown ? CCSX_PASS_STRAND_UNKNOWN : 0)));
+            unknown += r.strand_unknown;
             b.base_off.push_back(at);
             r.keep.reset(); r.seq = r.pw_p = r.ip_p = nullptr;                              // the inflated bytes may go
         }
         b.read_off.push_back((int32_t)b.flags.size());
     }
     b.bases = bases; b.pw = pw; b.ipd = ipd; b.n_bases = total;
+    return unknown;
 }
 
 struct Report {
@@ -1178,10 +1189,13 @@ int main(int argc, char **argv)
                 cur.order = nz++;
                 if (have_pbi && nz >= chunk_zmws) chunk_done = true;
                 if (mine) {
-                    // strand of every pass: cx REVERSE_PASS (32) / FORWARD_PASS (16) when present, else consecutive subreads alternate
+                    // strand of every pass: cx REVERSE_PASS (32) / FORWARD_PASS (16) when present, else consecutive subreads alternate — with
+                    // --orient-passes only as a prior: such a pass is submitted strand-unknown and the engine decides
                     for (size_t k = 0; k < cur.reads.size(); ++k) {
                         Subread &r = cur.reads[k];
-                        r.strand = (r.cx >= 0 && (r.cx & 48)) ? (uint8_t)((r.cx & 32) ? 1 : 0) : (uint8_t)(k & 1);
+                        const bool given = r.cx >= 0 && (r.cx & 48);
+                        r.strand = given ? (uint8_t)((r.cx & 32) ? 1 : 0) : (uint8_t)(k & 1);
+                        r.strand_unknown = (opt.orient_passes && !given) ? 1 : 0;
                     }
                     if (!opt.by_strand) emit_zmw(cur);
                     else {                                   // each strand is treated as an individual entity (mode-by-strand.md:16-23)
@@ -1256,6 +1270,7 @@ int main(int argc, char **argv)
         // second page-locked arena (the downloads are asynchronous DMA)
         std::vector<std::unique_ptr<ArenaPool>> in_pools, out_pools;
         for (size_t d = 0; d < ndev_q; ++d) { in_pools.emplace_back(new ArenaPool()); out_pools.emplace_back(new ArenaPool()); }
+        std::atomic<long long> unknown_passes{0};                          // --orient-passes: passes submitted strand-unknown
         std::atomic<long long> us_pack{0}, us_engine{0}, us_wait{0};       // summed over workers (--log-level INFO)
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto us_since = [](std::chrono::steady_clock::time_point t) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count(); };
@@ -1279,7 +1294,7 @@ int main(int argc, char **argv)
                 b->dev = dev;
                 try {
                     b->in_arena = in_pool.get();
-                    pack(*b, *b->in_arena);
+                    unknown_passes += pack(*b, *b->in_arena);
                     const int n = (int)b->zmw_id.size();
                     b->n = n;
                     if (n > 0 && !opt.host_only) {
@@ -1686,6 +1701,8 @@ int main(int argc, char **argv)
                          opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str(),
                          control ? (", " + std::to_string(rep.control) + " control ZMWs").c_str() : "",
                          coverage ? (", " + std::to_string(rep.coverage) + " ZMWs failed the coverage filters").c_str() : "");
+        if (opt.log_level >= 1 && opt.orient_passes)
+            std::fprintf(stderr, "ccs: --orient-passes: %lld passes submitted strand-unknown\n", unknown_passes.load());
         if (failed) {
             if (!err_msg.empty()) std::fprintf(stderr, "ccs: %s\n", err_msg.c_str());
             // no plausible-looking partial output after a failed run

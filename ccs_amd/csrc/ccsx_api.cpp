@@ -137,10 +137,13 @@ struct Slot {
     DevBuf d_ctl;                                 // control screen only (ccsx_control_request): the slot's own index, then the [8][n] report
     DevBuf d_cov;                                 // coverage screen only (ccsx_coverage_request): the [10][n] report, then one byte per window slot
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
+    DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
     PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
+    PinVec<int32_t> anchor;                       // pass orientation only: the anchor pass of every ZMW as uploaded
+    bool orient_pending = false, orient_ran = false;   // the staged batch carries the bit and k_orient has yet to run on it / has run (its report is on the device)
     KParams P;
     hipEvent_t ev[CCSX_EV_COUNT] = {}, ev_up = nullptr, ev_done = nullptr;   // ev: the stage events (ccsx_stage_event)
     hipEvent_t ev_aux[CCSX_ORD_COUNT] = {};                                  // the ordering events of the second stream (ccsx_order_event)
@@ -190,6 +193,8 @@ struct ccsx_handle_s {
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
+    DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
+    ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
     Slot slot[CCSX_SLOTS];
     int last = 0;                     // slot of the most recent stage / run (stage accessors, timings)
     int64_t next_ticket = 0;
@@ -351,6 +356,7 @@ int ccsx_create(int device_ordinal, const ccsx_model *model, const ccsx_opts *op
     if (h->opts.max_qv > 93) h->opts.max_qv = 93;
     if (const char *e = std::getenv("CCSX_SERIAL_STAGES")) h->opts.serial_stages = std::atoi(e) != 0;   // A/B switch without a rebuild
     h->handles_on_device = opts->handles_per_device > 1 ? opts->handles_per_device : 1;
+    ccsx_orient_opts_default(&h->orient_opts);
     const int rc = create_impl(h);
     if (rc) { destroy_handle(h); return rc; }        // no leak on a failed create (streams, events, device memory)
     *out = h;
@@ -374,6 +380,7 @@ struct Wants {
     const ccsx_adapter_request *adapters = nullptr; ccsx_adapter_set adapter_set{}; ccsx_adapter_opts adapter_opts{};
     const ccsx_control_request *control = nullptr; ccsx_control_opts control_opts{}; std::vector<uint8_t> control_seq;
     const ccsx_coverage_request *coverage = nullptr; ccsx_coverage_opts coverage_opts{};
+    const ccsx_orient_opts *orient = nullptr;   // ccsx_orient_batch's own options (NULL: the handle's, ccsx_set_orient_opts); already checked
 };
 
 // the longest draft of a slot's batch that can reach status SUCCESS (that needs length <= opts.max_length, and no draft exceeds its slot), at least `floor`:
@@ -631,6 +638,66 @@ static int grow_scratch(ccsx_handle h, int n, int R, const BatchTotals &T, KPara
     return 0;
 }
 
+// ---- pass orientation's host side (DESIGN.md §2 "Pass orientation")
+static int orient_opts_check(const ccsx_orient_opts *o, const char *fn)
+{
+    if (o->min_votes < 1 || o->ratio < 2 || o->ratio > 16) { ccsx_set_error(std::string(fn) + ": orient options out of range (min_votes >= 1; 2 <= ratio <= 16)"); return -1; }
+    return 0;
+}
+
+// The anchor pass of every ZMW into S.anchor (index within the ZMW; -1: no full-length pass) when some pass of the batch carries CCSX_PASS_STRAND_UNKNOWN: among the
+// full-length passes the one whose length is closest to the median (element n / 2 of the sorted lengths), ties to the first — the fallback draft's backbone
+// rule.  *longest: the longest anchor, 0 when no pass carries the bit (S.anchor is not touched then).
+static int orient_anchors(Slot &S, const ccsx_batch *b, int64_t *longest)
+{
+    *longest = 0;
+    bool any = false;
+    for (int r = 0; r < b->n_reads && !any; ++r) any = (b->flags[r] & CCSX_PASS_STRAND_UNKNOWN) != 0;
+    if (!any) return 0;
+    if (S.anchor.resize((size_t)b->n_zmw)) return -2;
+    std::vector<int64_t> len;
+    *longest = 1;
+    for (int z = 0; z < b->n_zmw; ++z) {
+        const int r0 = b->read_off[z];
+        len.clear();
+        for (int r = r0; r < b->read_off[z + 1] && !(b->flags[r] & 2); ++r) len.push_back(b->base_off[r + 1] - b->base_off[r]);   // (the partial passes follow)
+        int a = -1;
+        if (!len.empty()) {
+            std::vector<int64_t> sorted(len);
+            std::nth_element(sorted.begin(), sorted.begin() + sorted.size() / 2, sorted.end());
+            const int64_t med = sorted[sorted.size() / 2];
+            for (int i = 0; i < (int)len.size(); ++i)
+                if (a < 0 || std::llabs(len[i] - med) < std::llabs(len[a] - med)) a = i;
+            *longest = std::max(*longest, len[a]);
+        }
+        S.anchor[z] = a;
+    }
+    return 0;
+}
+
+// the report planes and the anchors of a staged batch that carries the bit (the anchors' upload enqueued on `st`), and the handle's tables grown to the batch's
+// longest anchor: growing waits for the draft stream, whose earlier batches may still use them
+static int orient_attach(ccsx_handle h, Slot &S, int64_t longest_anchor, const ccsx_orient_opts &o, hipStream_t st, KParams &P)
+{
+    const size_t n = (size_t)P.n_zmw, R1 = (size_t)(P.n_reads > 0 ? P.n_reads : 1), R = (size_t)P.n_reads;
+    if (S.d_orient.reserve(n * 4 + R1 * 8 + R1 * 2)) return -2;
+    P.orient = o;
+    P.orient_anchor = (const int32_t *)S.d_orient.p;
+    P.orient_votes = (int32_t *)S.d_orient.p + n;
+    P.orient_rep8 = (uint8_t *)(P.orient_votes + 2 * R);
+    P.orient_flags = (uint8_t *)S.d_flags.p;
+    P.orient_tab_words = ccsx_orient_slots((int)longest_anchor);
+    P.orient_wgs = (int32_t)std::min<size_t>(n, CCSX_ORIENT_MAX_WGS);
+    const size_t need = (size_t)P.orient_wgs * (size_t)P.orient_tab_words * 4;
+    if (need > h->d_orient.cap) {
+        HIPTRY(hipStreamSynchronize(h->s_draft));
+        if (h->d_orient.reserve(need)) return -2;
+    }
+    P.orient_tab = (uint32_t *)h->d_orient.p;
+    HIPTRY(hipMemcpyAsync(S.d_orient.p, S.anchor.p, n * 4, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
 // Stage a batch into a slot: host-derived layout, device buffers, H2D copies enqueued on `st` (nothing waits here except
 // hipMalloc growth).  The batch's own arrays must stay valid until the copies have run (pinned arrays copy by DMA).
 // W.pile: this run also computes the pileup summary (its buffers are reserved and its pointers set only then).
@@ -644,6 +711,8 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, co
     const int n = b->n_zmw, R = b->n_reads;
     int rc;
     if ((rc = layout(S, b, ccsx_top_passes(h->opts.top_passes), &S.T))) return rc;
+    int64_t longest_anchor = 0;                                  // > 0: some pass carries CCSX_PASS_STRAND_UNKNOWN
+    if ((rc = orient_anchors(S, b, &longest_anchor))) return rc;
     const BatchTotals &T = S.T;
     KParams P;
     std::memset(&P, 0, sizeof(P));
@@ -665,8 +734,10 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, co
     P.perr_floor = ccsx_perr_floor(h->opts.max_qv);
     P.model = (const ccsx_model *)h->d_model.p;
     if (ccsx_polish_lds(T.nr_max, &P.pw_obs_bytes, &P.pw_gb_floats)) { ccsx_set_error("ccsx_upload: cannot size the polish kernel's LDS"); return -2; }
+    if (longest_anchor > 0 && (rc = orient_attach(h, S, longest_anchor, W.orient ? *W.orient : h->orient_opts, st, P))) return rc;
     S.P = P;
     S.staged = true; S.ran = false; S.tm_ok = false;
+    S.orient_pending = longest_anchor > 0; S.orient_ran = false;
     return 0;
 }
 
@@ -686,8 +757,16 @@ static int launch(ccsx_handle h, Slot &S)
     }
     bind_scratch(h, P);
     if (!h->d_poa.p || !h->d_align.p) { ccsx_set_error("kernel launch refused: the POA / alignment scratch is not allocated (an earlier allocation failed)"); return -2; }
+    // k_orient runs once per staged batch: it resolves the flags in place, so a batch that is run again (ccsx_run twice) is oriented already and keeps its report
+    uint8_t *const orient_flags = P.orient_flags;
+    if (S.orient_pending) {
+        P.orient_tab = (uint32_t *)h->d_orient.p;                // (the tables only grow, like the scratch above)
+        if ((size_t)P.orient_wgs * (size_t)P.orient_tab_words * 4 > h->d_orient.cap) { ccsx_set_error("kernel launch refused: k_orient's tables are not allocated (an earlier allocation failed)"); return -2; }
+    } else P.orient_flags = nullptr;
     const char *failed = ccsx_launch_all(S.P, {h->s_draft, h->s_comp, h->s_aux, S.ev, h->s_aux ? S.ev_aux : nullptr}, S.mode);
+    P.orient_flags = orient_flags;
     if (failed) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    if (S.orient_pending) { S.orient_pending = false; S.orient_ran = true; }
     S.ran = true;
     return 0;
 }
@@ -1719,6 +1798,86 @@ int ccsx_train_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *draf
     }
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
+}
+
+// ---- pass orientation: the seam (include/ccsx.h; DESIGN.md §2 "Pass orientation").  Synchronous, on slot 0 like ccsx_hd_batch: upload, k_orient, the report.
+void ccsx_orient_opts_default(ccsx_orient_opts *o)
+{
+    if (!o) return;
+    o->min_votes = 16; o->ratio = 3;   // DESIGN.md §2 "Pass orientation": the study behind them
+}
+
+int ccsx_orient_rule_version(void) { return 1; }
+
+static int orient_report_check(const ccsx_orient_report *out, int32_t n_reads, const char *fn)
+{
+    if (!out) { ccsx_set_error(std::string(fn) + ": null report"); return -1; }
+    if (out->n_reads != n_reads || !out->strand || !out->call || !out->votes_same || !out->votes_opp) {
+        ccsx_set_error(std::string(fn) + ": report arrays missing, or sized for another batch"); return -1;
+    }
+    return 0;
+}
+
+int ccsx_set_orient_opts(ccsx_handle h, const ccsx_orient_opts *opts)
+{
+    if (!h) { ccsx_set_error("ccsx_set_orient_opts: null handle"); return -1; }
+    if (opts && orient_opts_check(opts, "ccsx_set_orient_opts")) return -1;
+    if (opts) h->orient_opts = *opts; else ccsx_orient_opts_default(&h->orient_opts);
+    return 0;
+}
+
+// the report of slot 0's staged batch on s_comp: what k_orient wrote, or — it did not run — every pass GIVEN with its own bit 0 (the slot's copy of the flags)
+static int orient_download(ccsx_handle h, Slot &S, ccsx_orient_report *out)
+{
+    const size_t R = (size_t)S.P.n_reads;
+    if (S.orient_ran) {
+        HIPTRY(hipMemcpyAsync(out->strand, S.P.orient_rep8, R, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->call, S.P.orient_rep8 + R, R, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->votes_same, S.P.orient_votes, R * 4, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipMemcpyAsync(out->votes_opp, S.P.orient_votes + R, R * 4, hipMemcpyDeviceToHost, h->s_comp));
+        HIPTRY(hipStreamSynchronize(h->s_comp));
+        return 0;
+    }
+    HIPTRY(hipMemcpyAsync(out->strand, S.P.flags, R, hipMemcpyDeviceToHost, h->s_comp));
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    for (size_t r = 0; r < R; ++r) { out->strand[r] &= 1; out->call[r] = CCSX_ORIENT_GIVEN; out->votes_same[r] = 0; out->votes_opp[r] = 0; }
+    return 0;
+}
+
+int ccsx_orient_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_orient_opts *opts, ccsx_orient_report *out)
+{
+    const char *fn = "ccsx_orient_batch";
+    if (!out) return refuse(fn, "null report");
+    if (!b) return refuse(fn, "null argument");
+    ccsx_orient_opts o;
+    if (opts) o = *opts; else ccsx_orient_opts_default(&o);
+    if (orient_report_check(out, b->n_reads, fn) || orient_opts_check(&o, fn)) return -1;
+    if (!h) return refuse(fn, "null argument");
+    if (h->poisoned) { ccsx_set_error("ccsx_orient_batch: an earlier submit failed after work had been enqueued; destroy the handle"); return -2; }
+    Wants W;
+    W.orient = &o;
+    int rc = upload_impl(h, b, W);
+    if (rc) return rc;
+    Slot &S = h->slot[0];
+    S.mode = CCSX_RUN_ORIENT;                                // (slot 0 is the seam's now: ccsx_run / ccsx_download refuse it until the next ccsx_upload)
+    if (S.orient_pending) {
+        if ((rc = launch(h, S)) || (rc = ccsx_sync(h))) return rc;
+        S.ran = false;                                       // (no stage but k_orient ran: the stage accessors other than ccsx_stage_orient have nothing to report)
+    }
+    return orient_download(h, S, out);
+}
+
+int ccsx_stage_orient(ccsx_handle h, ccsx_orient_report *out)
+{
+    const char *fn = "ccsx_stage_orient";
+    if (!out) return refuse(fn, "null report");
+    if (!h || !h->slot[0].staged) return refuse(fn, "no batch uploaded: a synchronous call first");
+    Slot &S = h->slot[0];
+    if (orient_report_check(out, S.P.n_reads, fn)) return -1;
+    HIPTRY(hipSetDevice(h->device));
+    HIPTRY(hipStreamSynchronize(h->s_draft));
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return orient_download(h, S, out);
 }
 
 }  // extern "C"

@@ -152,6 +152,15 @@ struct KParams {
     // ---- POA log (ccsx_poa_log; NULL otherwise): include/ccsx.h "The POA log".  Filled with -1 when the batch is staged
     int32_t *poa_log;          // [n][2 generators][poa_log_stride passes][CCSX_POA_LOG_WORDS], written by k_poa_thread
     int32_t poa_log_stride;    // = max_reads
+    // ---- pass orientation (a batch with a CCSX_PASS_STRAND_UNKNOWN pass; NULL otherwise): DESIGN.md §2 "Pass orientation"
+    ccsx_orient_opts orient;
+    uint8_t *orient_flags;     // [R] = flags, writable: k_orient resolves bit 0 of the flagged passes in place and clears their bit 3
+    const int32_t *orient_anchor;   // [n] the ZMW's anchor pass (index within the ZMW; host-built, layout()), -1 = no full-length pass
+    uint32_t *orient_tab;      // [orient_wgs][orient_tab_words] one open-addressing table of 13-mer codes per resident workgroup (shared scratch of the handle)
+    int32_t orient_tab_words;  // a power of two >= 2 x the 13-mer positions of the batch's longest anchor
+    int32_t orient_wgs;        // workgroups of the launch (each walks the ZMWs blockIdx.x, blockIdx.x + orient_wgs, ...)
+    uint8_t *orient_rep8;      // [2][R] strand, call
+    int32_t *orient_votes;     // [2][R] votes_same, votes_opp
 };
 #define CCSX_COVERAGE_PLANES 10
 #define CCSX_COVERAGE_PRE_GATE 0x1cu   // the gate bits of the verdicts k_coverage reaches before the polish (2, 3, 4)
@@ -184,6 +193,24 @@ struct KParams {
                                         // within the 64 KiB a launch gets by default
 static inline __host__ __device__ uint32_t ccsx_fmix32(uint32_t h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; }
 
+// k_orient (DESIGN.md §2 "Pass orientation"): the anchor's 13-mer codes (26 bits) live in a per-workgroup table in global scratch, slot of a code's first
+// probe = ccsx_fmix32(code) & (slots - 1), linear probing, slots = ccsx_orient_slots(M) for an anchor of M bases (load <= 1/2); in front of it an LDS bitmap of
+// CCSX_ORIENT_FILTER_BITS bits, bit = ccsx_fmix32(code) >> CCSX_ORIENT_FILTER_SHIFT, which may only reject.
+#define CCSX_ORIENT_K            13
+#define CCSX_ORIENT_THREADS      256
+#define CCSX_ORIENT_FILTER_BITS  262144   // 32 KiB of LDS: four workgroups per CU; an anchor of 10 kb sets 4 % of it, one of 65 535 bases 22 %
+#define CCSX_ORIENT_FILTER_SHIFT 14       // the hash's top 18 bits
+#define CCSX_ORIENT_MIN_SLOTS    64
+#define CCSX_ORIENT_MAX_WGS      1024     // resident workgroups of a launch = tables of the scratch (256 CUs x 4)
+#define CCSX_ORIENT_EMPTY        0xffffffffu
+static inline __host__ __device__ int ccsx_orient_slots(int M)
+{
+    const int npos = M >= CCSX_ORIENT_K ? M - CCSX_ORIENT_K + 1 : 0;
+    int s = CCSX_ORIENT_MIN_SLOTS;
+    while (s < 2 * npos) s <<= 1;
+    return s;
+}
+
 // k_sdust (DESIGN.md §2 "Tandem repeats"): window W bases, threshold T in tenths, dynamic LDS = two [64][64] word tables + two byte tables + the mask
 #define CCSX_SDUST_W 64
 #define CCSX_SDUST_T 20
@@ -195,7 +222,8 @@ static inline __host__ __device__ uint32_t ccsx_fmix32(uint32_t h) { h ^= h >> 1
 // which stages ccsx_launch_all enqueues: the fused path, the draft stage alone (ccsx_draft_batch), alignment cascade + polish on caller-supplied drafts, or
 // alignment cascade + the heteroduplex finder on caller-supplied drafts (ccsx_hd_batch), or alignment cascade + the training counts on caller-supplied drafts
 // (ccsx_train_batch)
-enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2, CCSX_RUN_HD = 3, CCSX_RUN_TRAIN = 4 };
+// or k_orient alone (ccsx_orient_batch)
+enum { CCSX_RUN_FUSED = 0, CCSX_RUN_DRAFT = 1, CCSX_RUN_POLISH = 2, CCSX_RUN_HD = 3, CCSX_RUN_TRAIN = 4, CCSX_RUN_ORIENT = 5 };
 
 // The stage events of a batch (Slot::ev, timing enabled), in the values they have always had — in time order POLISH_START lies between DRAFT_STAGE_DONE and
 // POLISH_DONE.  ccsx_launch_all records each of them exactly once on every path, in time order, so that ccsx_timings may read all seven after any run.

@@ -4021,10 +4021,10 @@ template <class... V> __device__ __forceinline__ void put_planes(int32_t *out, s
 // thread tid's contiguous share [p0, p1) of `count` positions split over nt threads (the last shares are short or empty)
 __device__ __forceinline__ void thread_share(int count, int nt, int tid, int &p0, int &p1) { const int ch = (count + nt - 1) / nt; p0 = min(tid * ch, count); p1 = min(p0 + ch, count); }
 
-// fn(i, F, R) for the 15-mer at every position i of [p0, e) of the draft d: F its code, R its reverse complement's, both rolled (a K - 1-base warm-up first)
-template <class Fn> __device__ __forceinline__ void kmer_scan(const uint8_t *d, int p0, int e, Fn fn)
+// fn(i, F, R) for the K-mer (the screens' 15-mer) at every position i of [p0, e) of the draft d: F its code, R its reverse complement's, both rolled (a K - 1-base
+// warm-up first)
+template <int K = CCSX_FOLD_K, class Fn> __device__ __forceinline__ void kmer_scan(const uint8_t *d, int p0, int e, Fn fn)
 {
-    constexpr int K = CCSX_FOLD_K;
     constexpr uint32_t KMASK = (1u << (2 * K)) - 1u;
     if (p0 >= e) return;
     uint32_t F = 0u, R = 0u;
@@ -4285,6 +4285,106 @@ __global__ __launch_bounds__(CCSX_CONTROL_THREADS) void k_control(KParams P)
         const int cs = sV[3], ce = sV[4] + K, ds = sV[0], de = sV[1] + K;
         const bool found = sV[2] >= o.min_matched && 10 * (ce - cs) >= o.min_ctl_tenths * M && 10ll * (de - ds) >= (long long)o.min_draft_tenths * L;
         put_planes(out, n, found ? CCSX_CONTROL_FOUND : CCSX_CONTROL_NONE, os, H, sV[2], cs, ce, ds, de);
+    }
+}
+
+// ---- k_orient: the orientation of the passes flagged CCSX_PASS_STRAND_UNKNOWN against their ZMW's anchor pass (DESIGN.md §2 "Pass orientation"), first kernel of
+// the draft stage.  CCSX_ORIENT_MAX_WGS 256-thread workgroups at most, each with its own table in the handle's scratch; a workgroup walks the ZMWs blockIdx.x,
+// blockIdx.x + gridDim.x, ... of the launch order (longest first).  A ZMW without a flagged pass gets its report rows (GIVEN) and is left at once.  Otherwise the
+// workgroup (1) clears the table's ccsx_orient_slots(M) words and the LDS prefilter and inserts the forward code of every 13-mer position of the anchor: thread t owns
+// a contiguous range and rolls F over it as k_fold's scan does; atomicCAS on the code's slot, linear probing (load <= 1/2: a probe ends), so the table holds the SET
+// of codes whatever the order of insertion; (2) per flagged pass rolls F and R over the pass the same way, looks each up — the prefilter bit, which may only
+// reject, then the probe sequence up to the code or an empty slot: membership is exact — and sums the two counts of positions; (3) thread 0 calls the pass and
+// writes its report row and its flags byte (bit 0 resolved, bit 3 cleared).  Every access of the table is an L2 atomic (clear, insert, look-up), so no look-up can
+// be served a line this CU's L1 kept from an earlier ZMW.  Counts only: the result does not depend on thread order.  tests/orient_ref.py restates the rule.
+__global__ __launch_bounds__(CCSX_ORIENT_THREADS) void k_orient(KParams P)
+{
+    constexpr int K = CCSX_ORIENT_K, NT = CCSX_ORIENT_THREADS, FW = CCSX_ORIENT_FILTER_BITS / 32, SH = CCSX_ORIENT_FILTER_SHIFT;
+    constexpr uint32_t EMPTY = CCSX_ORIENT_EMPTY;
+    static_assert(2 * K <= 30 && (32 - SH) == 18 && CCSX_ORIENT_FILTER_BITS == (1 << 18), "k_orient: a code is below EMPTY, the prefilter takes the hash's top 18 bits");
+    __shared__ uint32_t sFilt[FW];
+    __shared__ int sV[2];                 // v_same, v_opp of the current pass
+    const int tid = threadIdx.x;
+    const size_t R = (size_t)P.n_reads;
+    uint32_t *tab = P.orient_tab + (size_t)blockIdx.x * (size_t)P.orient_tab_words;
+    uint8_t *flags = P.orient_flags, *o_strand = P.orient_rep8, *o_call = P.orient_rep8 + R;
+    int32_t *o_same = P.orient_votes, *o_opp = P.orient_votes + R;
+    auto put = [&](int r, int f, int strand, int call, int vs, int vo) {
+        o_strand[r] = (uint8_t)strand; o_call[r] = (uint8_t)call; o_same[r] = vs; o_opp[r] = vo;
+        flags[r] = (uint8_t)((f & ~(CCSX_PASS_STRAND_UNKNOWN | 1)) | strand);
+    };
+    for (int zi = (int)blockIdx.x; zi < P.n_zmw; zi += (int)gridDim.x) {
+        const int z = rfl(P.zmw_perm[zi]), r0 = rfl(P.read_off[z]), nr = rfl(P.read_off[z + 1]) - r0;
+        int any = 0;
+        for (int q = tid; q < nr; q += NT) {
+            const int f = flags[r0 + q];
+            if (f & CCSX_PASS_STRAND_UNKNOWN) any = 1;
+            else { o_strand[r0 + q] = (uint8_t)(f & 1); o_call[r0 + q] = CCSX_ORIENT_GIVEN; o_same[r0 + q] = 0; o_opp[r0 + q] = 0; }
+        }
+        if (!__syncthreads_or(any)) continue;
+        const int a = rfl(P.orient_anchor[z]);
+        if (a < 0 || a >= nr) {                                       // no full-length pass: the caller's bits stay
+            for (int q = tid; q < nr; q += NT) { const int f = flags[r0 + q]; if (f & CCSX_PASS_STRAND_UNKNOWN) put(r0 + q, f, f & 1, CCSX_ORIENT_NO_ANCHOR, 0, 0); }
+            continue;
+        }
+        const int M = rfl((int)(P.base_off[r0 + a + 1] - P.base_off[r0 + a]));
+        const int slots = ccsx_orient_slots(M);
+        const int nposA = (M >= K && slots <= P.orient_tab_words) ? M - K + 1 : 0;   // (the second: a bounds guard, the host sizes the tables for the longest anchor)
+        const int anchor_rev = rfl(flags[r0 + a] & 1);
+        const uint32_t mask = (uint32_t)slots - 1u;
+        if (nposA > 0) {                                              // (1) the anchor's set
+            for (int w = tid; w < FW; w += NT) sFilt[w] = 0u;
+            for (int s = tid; s < slots; s += NT) __hip_atomic_store(tab + s, EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __threadfence();
+            __syncthreads();
+            int p0, p1;
+            thread_share(nposA, NT, tid, p0, p1);
+            kmer_scan<K>(P.bases + P.base_off[r0 + a], p0, p1, [&](int, uint32_t F, uint32_t) {
+                const uint32_t h = ccsx_fmix32(F), b = h >> SH;
+                atomicOr(&sFilt[b >> 5], 1u << (b & 31u));
+                for (uint32_t s = h & mask;; s = (s + 1u) & mask) {
+                    uint32_t k = __hip_atomic_load(tab + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (k == EMPTY) k = atomicCAS(tab + s, EMPTY, F);
+                    if (k == EMPTY || k == F) break;
+                }
+            });
+            __threadfence();
+            __syncthreads();
+        }
+        auto member = [&](uint32_t code) -> int {
+            const uint32_t h = ccsx_fmix32(code), b = h >> SH;
+            if (!((sFilt[b >> 5] >> (b & 31u)) & 1u)) return 0;
+            for (uint32_t s = h & mask;; s = (s + 1u) & mask) {
+                const uint32_t k = __hip_atomic_load(tab + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (k == code) return 1;
+                if (k == EMPTY) return 0;
+            }
+        };
+        for (int q = 0; q < nr; ++q) {                                // (2), (3) the flagged passes, one after the other
+            const int f = rfl(flags[r0 + q]);
+            if (!(f & CCSX_PASS_STRAND_UNKNOWN)) continue;
+            if (q == a) { if (tid == 0) put(r0 + q, f, f & 1, CCSX_ORIENT_ANCHOR, 0, 0); continue; }
+            const int N = rfl((int)(P.base_off[r0 + q + 1] - P.base_off[r0 + q]));
+            if (tid == 0) { sV[0] = 0; sV[1] = 0; }
+            __syncthreads();
+            int cs = 0, co = 0;
+            if (nposA > 0 && N >= K) {
+                int p0, p1;
+                thread_share(N - K + 1, NT, tid, p0, p1);
+                kmer_scan<K>(P.bases + P.base_off[r0 + q], p0, p1, [&](int, uint32_t F, uint32_t Rc) { cs += member(F); co += member(Rc); });
+            }
+            cs = wave_reduce_add_i32(cs); co = wave_reduce_add_i32(co);
+            if ((tid & 63) == 0 && (cs | co)) { atomicAdd(&sV[0], cs); atomicAdd(&sV[1], co); }
+            __syncthreads();
+            if (tid == 0) {
+                const int vs = sV[0], vo = sV[1], mv = P.orient.min_votes, ra = P.orient.ratio;
+                int call = CCSX_ORIENT_UNDETERMINED, strand = f & 1;  // (undetermined: the caller's bit, a prior)
+                if (vs >= mv && vs >= ra * vo) { call = CCSX_ORIENT_SAME; strand = anchor_rev; }
+                else if (vo >= mv && vo >= ra * vs) { call = CCSX_ORIENT_OPPOSITE; strand = anchor_rev ^ 1; }
+                put(r0 + q, f, strand, call, vs, vo);
+            }
+        }
+        __syncthreads();                                              // (the next ZMW clears the prefilter)
     }
 }
 
@@ -4738,8 +4838,17 @@ struct Schedule {
 
     // pass 0 = the draft; passes 1, 2 = the fallback drafts of the ZMWs k_post marked (their waves run, all others leave at once: a further round of launches
     // costs microseconds unless something failed)
+    // The passes flagged CCSX_PASS_STRAND_UNKNOWN are oriented before anything reads a pass's strand bit (a batch without one: nothing is launched).
+    void orient()
+    {
+        if (!P.orient_flags) return;
+        launch("k_orient", k_orient, dim3(P.orient_wgs), dim3(CCSX_ORIENT_THREADS), 0, st, P);
+        trace_sync(st, "k_orient");
+    }
+
     void draft_stage()
     {
+        orient();
         if (caller_drafts) launch("k_draft_in", k_draft_in, dim3(P.n_zmw), dim3(64), 0, st, P);
         const int passes = (P.opts.no_fallback_draft || caller_drafts) ? 1 : 3;
         for (int pass = 0; pass < passes; ++pass) {
@@ -4846,11 +4955,16 @@ struct Schedule {
 
 }  // namespace
 
-// The five run modes share one schedule and leave it at four places.  No stage synchronises with the host.
+// The run modes share one schedule and leave it at four places (ccsx_orient_batch's runs its first kernel only).  No stage synchronises with the host.  No stage synchronises with the host.
 const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode)
 {
     static const LaunchSwitches switches;
     Schedule s(P, q, mode, switches);
+    if (mode == CCSX_RUN_ORIENT) {                          // ccsx_orient_batch: k_orient alone, every stage event back to back behind it
+        s.orient();
+        s.close_timing(CCSX_EV_START, CCSX_EV_END);
+        return s.failed;
+    }
     s.tables();
     s.draft_stage();
     if (mode == CCSX_RUN_DRAFT) {                           // the draft seam ends here: drafts, window bounds, alignments and statuses are final

@@ -128,8 +128,11 @@ typedef struct ccsx_batch {
                                               polymerase read).  Not used for the draft, not counted in np; aligned to the draft anchored
                                               at one end and used by the polish where it reaches (docs/faq/accuracy-vs-passes.md:26-29:
                                               ec ~ np + 1).  A ZMW's partial passes must FOLLOW its full-length passes.
-                                        bit2: (partial only) the adapter is at the pass's END (cx ADAPTER_AFTER only), else at its start */
+                                        bit2: (partial only) the adapter is at the pass's END (cx ADAPTER_AFTER only), else at its start
+                                        bit3: CCSX_PASS_STRAND_UNKNOWN: bit0 of this pass is a guess; the engine decides it against the ZMW's
+                                              anchor pass before anything reads it ("Pass orientation" below).  A pass without it is never touched */
 } ccsx_batch;
+#define CCSX_PASS_STRAND_UNKNOWN 0x8
 
 /* ---- results: caller-allocated; seq/qual/raw_qv are laid out at seq_off[z] (capacity layout
  *      from ccsx_result_layout), seq_len[z] bases valid ---- */
@@ -618,6 +621,37 @@ typedef struct ccsx_requests {
 } ccsx_requests;
 int         ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq);
 int         ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket);
+
+/* ---- pass orientation (docs/faq/mode-by-strand.md:16-18: the orientation of the reads "with respect to the one closest to the median length"; the rule:
+ * DESIGN.md §2 "Pass orientation", its own version ccsx_orient_rule_version).  Opt-in per pass: flags bit 3 (CCSX_PASS_STRAND_UNKNOWN).  k_orient runs first in
+ * the draft stage of every batch that carries the bit, on every path that stages a batch (the fused forms, the draft and polish seams, ccsx_hd_batch,
+ * ccsx_train_batch): it votes every 13-mer position of a flagged pass, forward and reverse-complemented, against the exact set of the anchor's 13-mers, and writes
+ * the resolved bit 0 (bit 3 cleared) where every later kernel reads it.  Integer counts only.  A batch without the bit launches nothing and is byte for byte
+ * what it was.
+ *   ccsx_orient_batch      the seam: synchronous, slot 0: upload, k_orient, the report's download — for callers that need the strands on the host before they
+ *                          build batches.  opts NULL = ccsx_orient_opts_default.  ccsx_run / ccsx_download refuse slot 0 until the next ccsx_upload.
+ *   ccsx_set_orient_opts   the options of every other path (NULL = the defaults), from the next staged batch on.
+ *   ccsx_stage_orient      the report of the last synchronous run on slot 0 (as ccsx_stage_align_ev): what k_orient wrote, or every pass GIVEN with its own bit 0
+ *                          when the batch carried no bit 3.
+ * A NULL report, a report sized for another batch or options out of range are errors of the call: nothing is enqueued.                                         */
+typedef struct ccsx_orient_opts {
+    int32_t min_votes;           /* SAME / OPPOSITE: the winning orientation has at least this many votes (>= 1)                                               */
+    int32_t ratio;               /* ... and at least ratio times the votes of the other one (2 .. 16)                                                          */
+} ccsx_orient_opts;
+enum ccsx_orient_call { CCSX_ORIENT_GIVEN = 0, CCSX_ORIENT_ANCHOR = 1, CCSX_ORIENT_SAME = 2, CCSX_ORIENT_OPPOSITE = 3, CCSX_ORIENT_UNDETERMINED = 4,
+                        CCSX_ORIENT_NO_ANCHOR = 5 };
+typedef struct ccsx_orient_report {
+    int32_t  n_reads;
+    uint8_t *strand;             /* [n_reads] the resolved bit 0                                                                                                */
+    uint8_t *call;               /* [n_reads] enum ccsx_orient_call                                                                                             */
+    int32_t *votes_same;         /* [n_reads] positions of the pass whose 13-mer is among the anchor's; 0 for GIVEN, ANCHOR and NO_ANCHOR                       */
+    int32_t *votes_opp;          /* [n_reads] ... whose reverse-complemented 13-mer is                                                                          */
+} ccsx_orient_report;
+void        ccsx_orient_opts_default(ccsx_orient_opts *o);
+int         ccsx_orient_rule_version(void);
+int         ccsx_orient_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_orient_opts *opts, ccsx_orient_report *out);
+int         ccsx_set_orient_opts(ccsx_handle h, const ccsx_orient_opts *opts);
+int         ccsx_stage_orient(ccsx_handle h, ccsx_orient_report *out);
 
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
