@@ -2317,7 +2317,6 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     __shared__ int sCtl[12];                                 // 0:J 1:cs 2:ce 3:nacc 7:ev bits
     __shared__ float sZS[4];                                 // z-score sums: M fwd, V fwd, M rev, V rev
     __shared__ float sPskip[36];                             // error probability of a position if it is skipped (travels with the base)
-    __shared__ int sCnt[(PWT / 64)];
     __shared__ uint8_t sList[256];                           // compacted valid mutation lanes (a lane index < 256)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = rfl(tid >> 6);      // wave-uniform values are made scalar explicitly (rfl):
@@ -2560,26 +2559,56 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     int nvalid_last = 0, nvfull_last = 0;                    // usable reads of the last round: all / full-length passes only
     const int nfull = P.nfull[z];
     for (int it = 0; it < CCSX_MAX_ITER; ++it) {
-        // (round 4 measured the round without three of its barriers — this one in later rounds, the one after sT[1], the second one of the lane compaction:
-        // 155.6 -> 156.1 ms, no gain; the barriers stay where they make the hazards obvious)
+        // ---- the round set-up, from registers.  Everything up to the chunk-opening barrier depends on the window template (32 bytes) and two control words: every lane
+        // loads its column's base, J and the evidence bits ONCE and takes the neighbours, the reverse complement and both strands' contexts from its own wave's lanes
+        // (DPP shifts, one ds_bpermute); nothing the set-up writes is read back by the set-up, so no barrier stands inside it: three went (the one behind sT[1],
+        // the two of the lane compaction), two remain — this one in front of it and the chunk-opening one, which publishes what it wrote
+        // (profiles/polish_round_setup.txt).  Who wrote each word last, who reads it next, which barrier lies between:
+        //   sT[0], sCtl[0 / 7]    written by the prologue or by wave 0's selection of the round before, in front of this barrier; read here by every wave
+        //   sT[1]                 written here by wave 0; read by lane_mut in the scoring, behind the chunk-opening barrier (its readers of the round before: in front of
+        //                         the barrier that ends the round).  The tables and the z-score sums used to take their bases from it and needed a barrier behind it
+        //   sMvalid, sDeltaI,     written here, every entry by its own thread, every wave for its own 64-lane slice.  Read by the scoring (sList, the atomicAdd into
+        //   sList                 sDeltaI) behind the chunk-opening barrier, by the selection and the QV step (sMvalid, sDelta) behind the round's last barrier; their readers
+        //                         of the round before: in front of the barrier behind the selection.  Every wave evaluates the validity of all four slices (same column,
+        //                         slots 2 q + (lane >> 5)): its base offset and the round's lane count are popcounts of its own ballots — no counts through LDS, none of
+        //                         the compaction's two barriers
+        //   sTC, sDLC             written here, four entries + one per thread, from sCTX / sDL (prologue); read by the fill behind the chunk-opening barrier (the fill of
+        //                         the round before: in front of its own barrier)
+        //   sZS                   written here in round 0 by waves 0 and 1; read by the validity step behind the fill's barrier
+        // (Round 4 had measured the round without three of these barriers while every wave still walked the LDS chains between them: no gain then.  Measured with this
+        // set-up and not kept: the four z-score sums as four chains on wave 2, + 3.8 ms of 270; this barrier folded into the one behind the selection in later rounds —
+        // nothing is written between the two — + 0.5 ms.)
         __syncthreads();
         const int J = rfl(sCtl[0]);
+        const unsigned evb = (unsigned)rfl(sCtl[7]);         // evidence bits of the candidate filter (wave-uniform)
+        int tl = tid;
+        asm volatile("" : "+v"(tl));                         // (opaque: what the set-up derives from the thread index is formed here, not hoisted out of the rounds into registers that spill)
+        const int ll = tl & 63;
+        const int c = tl & 31;                               // the lane's column: PWT is a multiple of 32, so it is the column of the thread's mutation lane and of its table entries too
+        const int tc = (int)sT[0][c];                        // (columns from J on: stale bytes, never used)
         const float invJ2 = 1.0f / (float)(2 * J);           // band_row0's reciprocal
         const int S = (J + 2) & ~1;                          // EVEN row stride >= J+1: in the fill lane = row writes column t - row, so the
                                                              // lane-to-lane address stride is S - 1, which must be odd to be bank-conflict free
-        if (tid < J) sT[1][tid] = (uint8_t)(3 - sT[0][J - 1 - tid]);
-        __syncthreads();
+        const int lfr = (rf < 4) ? 3 - rf : 4;
+        // (the wave shifts and both ds_bpermute below take their values from other lanes and need ALL 64 lanes of the wave active: an inactive source lane gives
+        // the fill value / 0, not its base.  They stand in workgroup-uniform control flow; keep them out of any `if (tid < ...)`)
+        const int tm1 = wave_shr1_i32(tc, 0), tp1 = wave_shl1_i32(tc, 0);                    // t[c-1], t[c+1] (lanes 0 / 32 and 31 / 63: not a neighbour; c > 0 and c + 1 < J guard them)
+        const int rcc = 3 - __builtin_amdgcn_ds_bpermute(((J - 1 - c) & 31) << 2, tc);      // reverse complement: column c of strand 1 is 3 - t[J-1-c]
+        const int rm1 = wave_shr1_i32(rcc, 0);
+        if (tl < J) sT[1][tl] = (uint8_t)rcc;               // (lane_mut and the scoring read it, behind the chunk-opening barrier)
+        // the contexts of column c on both strands; from J on: entry 16 of a row of sCTX, the exact zero pair
+        const int fctx = c < J ? ctx_of(c > 0 ? tm1 : lf, tc) : CTXS - 1;
+        const int rctx = c < J ? ctx_of(c > 0 ? rm1 : lfr, rcc) : CTXS - 1;
         // the chunk plan of the round, when the round's first group is the one in LDS (nearly always: a ZMW of more than PW_MAXREADS passes ends a round on its
         // last group and plans after the reload below).  The last wave: it has no share in the z-score sums of round 0
         if (wave == (PWT / 64) - 1 && resident == 0) plan_chunks(nreads < PW_MAXREADS ? nreads : PW_MAXREADS, J, S);
-        auto tbase = [&](int sd, int j) -> int { return (int)sT[sd][j]; };   // base j of the window template on strand sd
-        const int lfr = (rf < 4) ? 3 - rf : 4;
         // z-score expectation of the window template on each strand, summed in column order (SPEC); the gate is decided in round 0
-        // only.  Lane j fetches column j's terms, the ordered sum takes them with v_readlane (no chain of dependent LDS loads).
+        // only.  Lane j holds column j's terms, the ordered sums take them with v_readlane (no chain of dependent LDS loads).
         if (it == 0 && wave < 2 && P.opts.min_zscore != 0.0f) {
-            const int j = lane < J ? lane : 0;
-            const int prev = j > 0 ? tbase(wave, j - 1) : (wave ? lfr : lf);
-            const int k = ctx_of(prev, tbase(wave, j));
+            // (a lane from column J on holds context CTXS - 1 = 16: it reads sZP[16] and sZP[32], the first float of the zeroed padding behind sZP — inside
+            // sTab only while that padding exists; the loop below takes the lanes q < J and never that value)
+            static_assert(CTXS == 17 && TAB_TAIL >= 1, "the z-score terms of a column from J on are read at sZP[CTXS - 1] and sZP[16 + CTXS - 1]");
+            const int k = wave ? rctx : fctx;
             const float mu = sZP[k], va = sZP[16 + k];
             float M = 0.0f, V = 0.0f;
             for (int q = 0; q < J; ++q) {
@@ -2590,66 +2619,66 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         }
         // positions skipped this round: evidence bit set and not inside a homopolymer of the CURRENT template
         {
-            const uint8_t *t = sT[0];
-            const int c = lane & 31;
-            const int tc = c < J ? t[c] : 9;
-            const int prev = c > 0 ? (c - 1 < J ? t[c - 1] : 8) : lf, next = c + 1 < J ? t[c + 1] : rf;
-            const bool hp = (prev == tc) || (next == tc);
-            skmask = (unsigned)__ballot(lane < J && (((unsigned)sCtl[7] >> c) & 1u) && !hp);
+            const int tcv = c < J ? tc : 9;
+            const int prev = c > 0 ? (c - 1 < J ? tm1 : 8) : lf, next = c + 1 < J ? tp1 : rf;
+            const bool hp = (prev == tcv) || (next == tcv);
+            skmask = (unsigned)__ballot(ll < J && ((evb >> c) & 1u) && !hp);
         }
         // valid mutation lanes of this round, compacted: lane m = slot*32 + c is valid iff the SPEC enumerates it;
         // thread t then scores the t-th valid lane, so unused lanes cost nothing
+        auto lane_valid = [&](int sl) -> int {               // slot sl (0 .. 7) of the lane's column
+            int v;
+            if (sl < 3) v = c < J;
+            else if (sl == 3) v = c < J && !(c > 0 && tm1 == tc);
+            else v = c <= J && !(c > 0 && tm1 == sl - 4);
+            const int cc = c < J ? c : J - 1;               // candidate filter (insertions after the last column follow J-1)
+            if (v && ((skmask >> cc) & 1u)) v = 0;
+            // a quiet position inside a homopolymer keeps only the mutations that change the run's LENGTH: deletion of the
+            // run's first base, insertion of the run's base before it (the enumeration admits both at run starts only)
+            else if (v && ((evb >> cc) & 1u) && !(c < J && (sl == 3 || (sl >= 4 && sl - 4 == tc)))) v = 0;
+            return v;
+        };
+        int nvm = 0;
         {
-            const uint8_t *t = sT[0];
-            const int sl0 = tid >> 5, c0 = tid & 31;
-            int v0;
-            if (sl0 < 3) v0 = c0 < J;
-            else if (sl0 == 3) v0 = c0 < J && !(c0 > 0 && t[c0 - 1] == t[c0]);
-            else if (sl0 < 8) v0 = c0 <= J && !(c0 > 0 && t[c0 - 1] == sl0 - 4);
-            else v0 = 0;                                                      // threads 256.. own no mutation lane
-            {                                                                 // candidate filter (insertions after the last column follow J-1)
-                const int cc = c0 < J ? c0 : J - 1;
-                if (v0 && ((skmask >> cc) & 1u)) v0 = 0;
-                // a quiet position inside a homopolymer keeps only the mutations that change the run's LENGTH: deletion of the
-                // run's first base, insertion of the run's base before it (the enumeration admits both at run starts only)
-                else if (v0 && (((unsigned)sCtl[7] >> cc) & 1u) && !(c0 < J && (sl0 == 3 || (sl0 >= 4 && sl0 - 4 == t[c0])))) v0 = 0;
-            }
-            const unsigned long long bal = __ballot(v0);
-            if (lane == 0) sCnt[wave] = __popcll(bal);
-            if (tid < 256) { sMvalid[tid] = (uint8_t)v0; sDeltaI[tid] = 0; }
-            __syncthreads();
+            static_assert(PWT == 256, "the set-up: eight slots of 32 columns, two per wave");
+            unsigned long long mine = 0ull;
             int basew = 0;
-            for (int q = 0; q < wave; ++q) basew += sCnt[q];
-            if (v0) sList[basew + __popcll(bal & ((1ull << lane) - 1ull))] = (uint8_t)tid;
-            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < (PWT / 64); ++q) {
+                const unsigned long long b = __ballot(lane_valid(2 * q + (ll >> 5)));
+                const int n = __popcll(b);
+                if (q < wave) basew += n;
+                if (q == wave) mine = b;
+                nvm += n;
+            }
+            const int v0 = (int)((mine >> ll) & 1ull);
+            sMvalid[tl] = (uint8_t)v0; sDeltaI[tl] = 0;
+            if (v0) sList[basew + __popcll(mine & ((1ull << ll) - 1ull))] = (uint8_t)tid;
         }
-        // the fill's per-column tables of this round's template (sT[1] is complete: barriers since).  sTC[strand][obs][column]: the pair of the column's context in
+        // the fill's per-column tables of this round's template.  sTC[strand][obs][column]: the pair of the column's context in
         // the observation's row of sCTX — zeros from column J on ("no stay in the final column") and for observation 12 ("no base": the zero row);
         // sDLC[strand][column]: DL of the column's context, 1 outside 0 .. J-1 (beta's start value passes through column J as 1 * beta).  Boundary cells are data,
         // not control: the sweeps are branch-free.
-        for (int e = tid; e < 2 * TC_STRAND; e += PWT) {
-            const int sd = e >= TC_STRAND ? 1 : 0, e2 = e - sd * TC_STRAND, o = e2 >> 5, j = e2 & 31;
-            float2 v = make_float2(0.0f, 0.0f);
-            if (j < J) {
-                const int prev = j > 0 ? tbase(sd, j - 1) : (sd ? lfr : lf);
-                v = sCTX[o * CTXS + ctx_of(prev, tbase(sd, j))];
+        {
+            static_assert(PWT == 256 && TC_ROW == 32 && 2 * TC_STRAND <= 4 * PWT && DLC_TOTAL <= PWT, "the set-up: four sTC entries and one sDLC entry per thread");
+            // entry tid + 256 k is row (tl >> 5) + 8 k of the 26 (strand, observation) rows, column c: one sCTX read per entry, all reads before the stores
+            const int row0 = tl >> 5;
+            const int ej = tl - TC_LO - (tl >= TC_LO + 33 ? DLC_S : 0);                   // the column of the thread's sDLC entry: its contexts sit in lane ej & 31
+            const int both = __builtin_amdgcn_ds_bpermute((ej & 31) << 2, fctx | (rctx << 8));
+            float2 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int r = row0 + 8 * k, sd = r >= CCSX_NOBS + 1 ? 1 : 0, o = r - sd * (CCSX_NOBS + 1);
+                v[k] = sCTX[r < 2 * (CCSX_NOBS + 1) ? o * CTXS + (sd ? rctx : fctx) : 0];
             }
-            sTC[e] = v;
-        }
-        for (int e = tid; e < DLC_TOTAL; e += PWT) {
-            const int sd = e >= TC_LO + 33 ? 1 : 0, j = e - TC_LO - sd * DLC_S;
-            float v = 1.0f;
-            if (j >= 0 && j < J) {
-                const int prev = j > 0 ? tbase(sd, j - 1) : (sd ? lfr : lf);
-                v = sDL[ctx_of(prev, tbase(sd, j))];
-            }
+            const bool inw = ej >= 0 && ej < J;
+            const float dv = sDL[inw ? (tl >= TC_LO + 33 ? both >> 8 : both & 255) : 0];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (row0 + 8 * k < 2 * (CCSX_NOBS + 1)) sTC[tl + PWT * k] = v[k];
             // (the entry right in front of sTC is column -1 of strand 0's observation row 0: row 1's lane reads it at step 0 while row 0's start value 1 is still in its
             // neighbour, so its ME has to be an exact zero like column 31 of the row before every other observation row — no lane uses a DL that far out)
-            sDLC[e] = e >= DLC_TOTAL - 2 ? 0.0f : v;
+            if (tl < DLC_TOTAL) sDLC[tl] = tl >= DLC_TOTAL - 2 ? 0.0f : (inw ? dv : 1.0f);
         }
-        int nvm = 0;
-#pragma unroll
-        for (int q = 0; q < (PWT / 64); ++q) nvm += rfl(sCnt[q]);
         const int nblk = (nvm + 63) >> 6;
         PHASE(1);
         int nvalid = 0, nvfull = 0;
