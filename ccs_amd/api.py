@@ -383,6 +383,112 @@ def _coverage_request(opts: "CoverageOpts | None", gate: int, crep: CCoverageRep
     return CCoverageRequest(C.pointer(o), C.pointer(crep), int(gate), (C.c_int32 * 2)(0, 0)), o
 
 
+# ---- polisher hand-off (include/ccsx.h ccsx_handoff_*; DESIGN.md §2 "Polisher hand-off")
+HANDOFF_NO_BASE, HANDOFF_NO_SEGMENT = 4, 5       # cell base codes beside 0-3: no base of the pass on the column; no usable segment, row or column
+
+
+class HandoffOpts(C.Structure):
+    _fields_ = [("tile_len", C.c_int32), ("max_rows", C.c_int32), ("skip_above", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CHandoffOut(C.Structure):
+    """ccsx_handoff_out: every array is host or device memory, so the mirror keeps plain addresses"""
+    _fields_ = [("max_tiles", C.c_int64)] + [(k, C.c_void_p) for k in ("counts", "tile_zmw", "tile_start", "tile_len", "tile_qsum", "tile_rows", "row_pass",
+                                                                     "row_strand", "cells")]
+
+
+class CHandoffRequest(C.Structure):
+    _fields_ = [("opts", C.POINTER(HandoffOpts)), ("out", C.POINTER(CHandoffOut)), ("reserved", C.c_int64 * 2)]
+
+
+def handoff_opts_default() -> HandoffOpts:
+    o = HandoffOpts()
+    lib().ccsx_handoff_opts_default(C.byref(o))
+    return o
+
+
+def handoff_tile_bound(batch: "Batch", tile_len: int) -> int:
+    """tiles a batch can have at most: every ZMW's consensus capacity (ccsx_result_layout) cut into tiles"""
+    off = np.zeros(batch.n_zmw + 1, np.int64)
+    cb = batch.c_struct()
+    lib().ccsx_result_layout(C.byref(cb), _ptr(off, C.c_int64))
+    return max(1, int(((np.diff(off) + tile_len - 1) // tile_len).sum()))
+
+
+class Handoff:
+    """ccsx_handoff_out with its options: the selected tiles of a batch as pass-by-column arrays.  counts [2] (tiles, selected tiles), tile_zmw / tile_start /
+    tile_len / tile_qsum / tile_rows [max_tiles] int32, row_pass / row_strand [max_tiles, R] uint8, cells [max_tiles, R, T, 4] uint8 = (base, pw, ip, ins).
+    The arrays are numpy (pageable or page-locked) or, with device=, torch tensors in the memory of that GPU: nothing of them crosses PCIe."""
+    FIELDS = ("counts", "tile_zmw", "tile_start", "tile_len", "tile_qsum", "tile_rows", "row_pass", "row_strand", "cells")
+
+    def __init__(self, opts: HandoffOpts, max_tiles: int, arrays: dict, on_device: bool, keep=None):
+        self.opts, self.max_tiles, self.on_device, self._keep = opts, int(max_tiles), on_device, keep
+        for k in self.FIELDS:
+            setattr(self, k, arrays[k])
+
+    @staticmethod
+    def shapes(max_tiles: int, opts: HandoffOpts) -> dict:
+        m, r, t = int(max_tiles), int(opts.max_rows), int(opts.tile_len)
+        d = {k: ((m,), np.int32) for k in Handoff.FIELDS[1:6]}
+        d.update(counts=((2,), np.int32), row_pass=((m, r), np.uint8), row_strand=((m, r), np.uint8), cells=((m, r, t, 4), np.uint8))
+        return d
+
+    @classmethod
+    def allocate(cls, batch: "Batch", max_tiles: "int | None" = None, opts: "HandoffOpts | None" = None, pinned: bool = False,
+                 device: "bool | int" = False) -> "Handoff":
+        """max_tiles None: room for every tile the batch can have.  pinned=True: page-locked arrays (Handle.submit).  device=True (GPU 0) or a device
+        ordinal: torch tensors on that GPU — it must be the handle's"""
+        o = opts if opts is not None else handoff_opts_default()
+        m = handoff_tile_bound(batch, int(o.tile_len)) if max_tiles is None else int(max_tiles)
+        shapes = cls.shapes(max(m, 0), o)
+        keep = []
+        if device is not False:
+            import torch
+            dev = torch.device("cuda", 0 if device is True else int(device))
+            dts = {np.int32: torch.int32, np.uint8: torch.uint8}
+            arrays = {k: torch.zeros(sh, dtype=dts[dt], device=dev) for k, (sh, dt) in shapes.items()}
+            torch.cuda.synchronize(dev)                      # the fills are done before the engine's own streams write
+        elif pinned:
+            arrays = {k: _pinned_array(int(np.prod(sh)), dt, keep).reshape(sh) for k, (sh, dt) in shapes.items()}
+            for a in arrays.values():
+                a[...] = 0
+        else:
+            arrays = {k: np.zeros(sh, dt) for k, (sh, dt) in shapes.items()}
+        return cls(o, m, arrays, device is not False, keep)
+
+    def c_struct(self) -> CHandoffOut:
+        c = CHandoffOut()
+        c.max_tiles = self.max_tiles
+        for k in self.FIELDS:
+            a = getattr(self, k)
+            setattr(c, k, a.data_ptr() if self.on_device else a.ctypes.data)
+        return c
+
+    def host(self) -> "Handoff":
+        """the same hand-off with numpy arrays (a device one is copied to the host; call after the run has ended)"""
+        if not self.on_device:
+            return self
+        return Handoff(self.opts, self.max_tiles, {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}, False)
+
+    @property
+    def n_tiles(self) -> int:
+        """slots that were written: min(selected tiles, max_tiles)"""
+        return min(int(self.counts[1]), self.max_tiles)
+
+    def tile(self, g: int) -> dict:
+        """slot g: zmw, start, len, qsum, rows, row_pass [R], row_strand [R], cells [R, len, 4]"""
+        if not 0 <= g < self.n_tiles:
+            raise IndexError(f"tile {g} of {self.n_tiles}")
+        ln = int(self.tile_len[g])
+        return dict(zmw=int(self.tile_zmw[g]), start=int(self.tile_start[g]), len=ln, qsum=int(self.tile_qsum[g]), rows=int(self.tile_rows[g]),
+                    row_pass=self.row_pass[g], row_strand=self.row_strand[g], cells=self.cells[g][:, :ln])
+
+
+def _handoff_request(ho: Handoff):
+    co = ho.c_struct()
+    return CHandoffRequest(C.pointer(ho.opts), C.pointer(co), (C.c_int64 * 2)(0, 0)), co
+
+
 # ---- pass orientation (include/ccsx.h ccsx_orient_*; DESIGN.md §2 "Pass orientation")
 PASS_STRAND_UNKNOWN = 0x8     # flags bit 3: bit 0 of this pass is a guess; k_orient decides it against the ZMW's anchor pass
 ORIENT_GIVEN, ORIENT_ANCHOR, ORIENT_SAME, ORIENT_OPPOSITE, ORIENT_UNDETERMINED, ORIENT_NO_ANCHOR = range(6)
@@ -683,6 +789,7 @@ EXPORTS = [
     "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
     "ccsx_coverage_opts_default", "ccsx_coverage_rule_version", "ccsx_consensus_requests", "ccsx_submit_requests",
     "ccsx_orient_opts_default", "ccsx_orient_rule_version", "ccsx_orient_batch", "ccsx_set_orient_opts", "ccsx_stage_orient",
+    "ccsx_handoff_opts_default", "ccsx_handoff_rule_version", "ccsx_consensus_handoff", "ccsx_submit_handoff",
     "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
     "ccsx_inflate_blocks_host",
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
@@ -774,6 +881,10 @@ def lib() -> C.CDLL:
         L.ccsx_coverage_opts_default.argtypes = [C.POINTER(CoverageOpts)]
         L.ccsx_consensus_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests)]
         L.ccsx_submit_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(C.c_int64)]
+        L.ccsx_handoff_opts_default.restype = None
+        L.ccsx_handoff_opts_default.argtypes = [C.POINTER(HandoffOpts)]
+        L.ccsx_consensus_handoff.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CHandoffRequest)]
+        L.ccsx_submit_handoff.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CHandoffRequest), C.POINTER(C.c_int64)]
         L.ccsx_orient_opts_default.restype = None
         L.ccsx_orient_opts_default.argtypes = [C.POINTER(OrientOpts)]
         L.ccsx_orient_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(OrientOpts), C.POINTER(COrientReport)]
@@ -1191,6 +1302,7 @@ class Handle:
 
     def __init__(self, device: int = 0, model: Model | None = None, opts: Opts | None = None):
         self._L = lib()
+        self.device = int(device)
         self.model = model or default_model()
         self.opts = opts or default_opts()
         self._h = C.c_void_p()
@@ -1204,14 +1316,21 @@ class Handle:
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
 
-    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket):
+    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
         ccsx_*_hd with a heteroduplex request, which combines with none of the screens, ccsx_*_requests when _requests made a CRequests (a coverage request,
-        or via_requests), else ccsx_*_control (NULL: not asked for).  Returns the C structs"""
+        or via_requests), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
+        structs join the requests' keep list.  Returns the C structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
             name, args = f"ccsx_{form}_requests", (_keep[-1],)
+        if handoff is not None:
+            if name != f"ccsx_{form}_requests":
+                raise ValueError("the hand-off goes with the members of ccsx_requests (not with the heteroduplex request)")
+            hreq = _handoff_request(handoff)
+            name, args = f"ccsx_{form}_handoff", (_keep[-1], hreq[0])
+            _keep.append(hreq)
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
         if form == "consensus":
@@ -1356,6 +1475,19 @@ class Handle:
                                                        coverage=vrep, coverage_opts=opts, coverage_gate=gate))
         return res, vrep, crep, frep, arep, tl, pile
 
+    # ---- the polisher hand-off (ccsx_consensus_handoff): the low-quality tiles of the consensus as pass-by-column arrays, alone or with the requests above
+    def consensus_handoff(self, batch: Batch, opts: "HandoffOpts | None" = None, max_tiles: "int | None" = None, device: bool = False,
+                          handoff: "Handoff | None" = None, res: "Results | None" = None, **requests) -> tuple["Results", "Handoff"]:
+        """(results, hand-off).  opts: the HandoffOpts (None: the defaults); max_tiles: the arrays' capacity (None: every tile the batch can have);
+        device=True: the arrays are torch tensors on this handle's GPU.  handoff: a Handoff of the caller's instead; res: the caller's Results.  requests:
+        Handle.submit's keyword arguments for the other requests of the same run (pileup=, tandem=, fold=, adapters=, control=, coverage= ... with their
+        reports; not hd=)"""
+        if res is None:
+            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        ho = handoff if handoff is not None else Handoff.allocate(batch, max_tiles, opts, device=self.device if device else False)
+        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), handoff=ho)
+        return res, ho
+
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""
         cap = 1 << 14
@@ -1395,7 +1527,7 @@ class Handle:
                fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None, adapters: "AdapterReport | None" = None,
                adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, control: "ControlReport | None" = None,
                control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None, coverage: "CoverageReport | None" = None,
-               coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0) -> int:
+               coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, handoff: "Handoff | None" = None) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
         receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd).  fold: a report
@@ -1404,7 +1536,9 @@ class Handle:
         pinned=True)) that receives the control screen for control_seq under control_opts.  fold, adapters and control go alone or together
         (ccsx_submit_control), none of them with hd.  Every ticket carries its own control: tickets in flight may screen for different ones.  coverage: a
         report (CoverageReport.allocate(n, pinned=True)) that receives the coverage screen under coverage_opts and coverage_gate (ccsx_submit_requests; with or
-        without the other screens, not with hd); every ticket carries its own options and gate"""
+        without the other screens, not with hd); every ticket carries its own options and gate.  handoff: a Handoff (Handoff.allocate(batch, max_tiles, opts,
+        pinned=True) or device=) that receives the polisher hand-off (ccsx_submit_handoff; not with hd): the whole capacity of its arrays is copied, complete
+        when the ticket is; every ticket carries its own options and capacity"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
@@ -1417,13 +1551,15 @@ class Handle:
             raise ValueError("control: a control_seq is needed (there is no built-in control)")
         if coverage is not None and hd is not None:
             raise ValueError("the heteroduplex request and the coverage screen are not combined")
+        if handoff is not None and hd is not None:
+            raise ValueError("the heteroduplex request and the hand-off are not combined")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
-                             control, control_seq, control_opts, coverage, coverage_opts, coverage_gate)
+                             control, control_seq, control_opts, coverage, coverage_opts, coverage_gate, via_requests=handoff is not None)
         t = C.c_int64()
-        cb, cr = self._fused("submit", batch, res, requests, t)
+        cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
-        self._inflight[t.value] = (batch, res, cb, cr, requests)  # the C structs and arrays must outlive the ticket
+        self._inflight[t.value] = (batch, res, cb, cr, requests, handoff)  # the C structs and arrays must outlive the ticket
         return t.value
 
     def wait(self, ticket: int) -> "Results":

@@ -137,6 +137,7 @@ struct Slot {
     DevBuf d_ctl;                                 // control screen only (ccsx_control_request): the slot's own index, then the [8][n] report
     DevBuf d_cov;                                 // coverage screen only (ccsx_coverage_request): the [10][n] report, then one byte per window slot
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
+    DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
@@ -381,6 +382,8 @@ struct Wants {
     const ccsx_control_request *control = nullptr; ccsx_control_opts control_opts{}; std::vector<uint8_t> control_seq;
     const ccsx_coverage_request *coverage = nullptr; ccsx_coverage_opts coverage_opts{};
     const ccsx_orient_opts *orient = nullptr;   // ccsx_orient_batch's own options (NULL: the handle's, ccsx_set_orient_opts); already checked
+    const ccsx_handoff_request *handoff = nullptr; ccsx_handoff_opts handoff_opts{}; ccsx_handoff_out handoff_out{};   // (the out struct is copied: it is read during the call only)
+    bool handoff_written_only = false;          // the synchronous form: counts is known when the copies are enqueued, only the written slots are copied
 };
 
 // the longest draft of a slot's batch that can reach status SUCCESS (that needs length <= opts.max_length, and no draft exceeds its slot), at least `floor`:
@@ -508,7 +511,7 @@ static int32_t sdust_mask_words(ccsx_handle h, const Slot &S)
 #define RES(dst, buf, bytes) do { if ((buf).reserve(bytes)) return -2; (dst) = (decltype(dst))(buf).p; } while (0)
 
 // the batch's arrays and the slot's layout into their device buffers, bound to P: H2D copies enqueued on `st`, in this order
-static int upload_inputs(Slot &S, const ccsx_batch *b, bool kin, hipStream_t st, KParams &P)
+static int upload_inputs(Slot &S, const ccsx_batch *b, bool ipd, hipStream_t st, KParams &P)
 {
     const size_t n = (size_t)b->n_zmw, R = (size_t)b->n_reads, R1 = R > 0 ? R : 1, NB = (size_t)b->n_bases;
 #define UP(dst, buf, src, bytes) do { RES(dst, buf, bytes); HIPTRY(hipMemcpyAsync((buf).p, (src), (bytes), hipMemcpyHostToDevice, st)); } while (0)
@@ -517,7 +520,7 @@ static int upload_inputs(Slot &S, const ccsx_batch *b, bool kin, hipStream_t st,
     UP(P.base_off, S.d_base_off, b->base_off, (R + 1) * 8);
     UP(P.bases, S.d_bases, b->bases, NB);
     UP(P.pw, S.d_pw, b->pw, NB);
-    if (kin) UP(P.ipd, S.d_ipd, b->ipd, NB);
+    if (ipd) UP(P.ipd, S.d_ipd, b->ipd, NB);
     UP(P.flags, S.d_flags, b->flags, R1);
     UP(P.read_zmw, S.d_read_zmw, S.read_zmw.p, R1 * 4);
     UP(P.vcap, S.d_vcap, S.vcap.p, n * 4);
@@ -533,7 +536,7 @@ static int upload_inputs(Slot &S, const ccsx_batch *b, bool kin, hipStream_t st,
 }
 
 // the slot's per-ZMW state, per-window and per-pass working arrays and outputs, sized by the layout and bound to P; the optional analyses' only when they run
-static int reserve_state(Slot &S, size_t n, size_t R, bool kin, bool pile, bool tandem, KParams &P)
+static int reserve_state(Slot &S, size_t n, size_t R, bool kin, bool pile, bool tandem, bool handoff, KParams &P)
 {
     const size_t R1 = R > 0 ? R : 1, wins = (size_t)S.T.total_wslots + 1, cap = (size_t)S.T.cap_total, ents = (size_t)(S.ent_off[R] + 1);
     RES(P.tabME, S.d_tabME, n * 192 * 4); RES(P.tabINS, S.d_tabINS, n * 192 * 4); RES(P.tabDL, S.d_tabDL, n * 16 * 4); RES(P.tabZ, S.d_tabZ, n * 32 * 4);
@@ -552,7 +555,7 @@ static int reserve_state(Slot &S, size_t n, size_t R, bool kin, bool pile, bool 
     RES(P.out_seq, S.d_out_seq, cap); RES(P.out_qual, S.d_out_qual, cap); RES(P.out_raw, S.d_out_raw, cap * 4);
     if (carve_planes<int32_t>({&P.out_status, &P.out_len, &P.out_iters, &P.out_nwin, &P.out_fn, &P.out_rn}, S.d_out_i32, n)) return -2;
     if (carve_planes<float>({&P.out_rq, &P.out_ec}, S.d_out_f32, n)) return -2;
-    if (kin || pile) { RES(P.wtpl, S.d_wtpl, wins * 32); RES(P.wtmeta, S.d_wtmeta, wins * 4); }   // k_polish keeps the converged templates
+    if (kin || pile || handoff) { RES(P.wtpl, S.d_wtpl, wins * 32); RES(P.wtmeta, S.d_wtmeta, wins * 4); }   // k_polish keeps the converged templates
     if (kin) { RES(P.wkin, S.d_wkin, wins * 32 * 4); RES(P.out_kin, S.d_out_kin, cap * 4); P.kin_plane = S.T.cap_total; }
     if (pile) { RES(P.wpile, S.d_wpile, wins * 32 * 4); RES(P.out_pile, S.d_out_pile, cap * 3); P.pile_plane = S.T.cap_total; }
     if (tandem) { RES(P.tflag, S.d_tflag, n * 4); RES(P.tlen, S.d_tlen, n * 4); }
@@ -720,7 +723,8 @@ static int stage(ccsx_handle h, Slot &S, const ccsx_batch *b, hipStream_t st, co
         P.min_tandem = W.min_tandem;
         if ((P.sdust_words = sdust_mask_words(h, S)) < 0) return -1;
     }
-    if ((rc = upload_inputs(S, b, kin, st, P)) || (rc = reserve_state(S, (size_t)n, (size_t)R, kin, pile, W.tandem, P))) return rc;
+    const bool handoff = W.handoff != nullptr;                   // (its cells carry the passes' ipd bytes when the batch has them)
+    if ((rc = upload_inputs(S, b, kin || (handoff && b->ipd), st, P)) || (rc = reserve_state(S, (size_t)n, (size_t)R, kin, pile, W.tandem, handoff, P))) return rc;
     if ((rc = grow_scratch(h, n, R, T, P))) return rc;
     if (h->poa_log) {                                            // every record starts as -1: "this generator did not reach this pass"
         const size_t bytes = (size_t)(n > 0 ? n : 1) * 2 * (size_t)T.nr_max * CCSX_POA_LOG_WORDS * 4;
@@ -1107,6 +1111,75 @@ static int coverage_attach(ccsx_handle h, Slot &S, const ccsx_coverage_opts &o, 
     return 0;
 }
 
+// ---- the polisher hand-off's host side (DESIGN.md §2 "Polisher hand-off")
+void ccsx_handoff_opts_default(ccsx_handoff_opts *o)
+{
+    if (!o) return;
+    o->tile_len = 100; o->max_rows = 20; o->skip_above = 45; o->reserved = 0;   // DESIGN.md §2 "Polisher hand-off": the reasons for them
+}
+
+int ccsx_handoff_rule_version(void) { return 1; }
+
+#define CCSX_HANDOFF_MAX_TILES (1ll << 26)   // the kernels index tiles, and M x R slots, with int32
+
+// a request as the caller gave it: every refusal by its own message; the options (NULL: the defaults) and the out struct copied
+static int handoff_request_check(const ccsx_handoff_request *q, ccsx_handoff_opts *o, ccsx_handoff_out *out, const char *fn)
+{
+    const std::string f(fn);
+    if (q->reserved[0] || q->reserved[1]) { ccsx_set_error(f + ": handoff request: reserved must be 0"); return -1; }
+    if (q->opts) *o = *q->opts; else ccsx_handoff_opts_default(o);
+    if (o->reserved) { ccsx_set_error(f + ": handoff options: reserved must be 0"); return -1; }
+    if (o->tile_len < 16 || o->tile_len > 128 || o->max_rows < 1 || o->max_rows > 32 || o->skip_above < 0 || o->skip_above > 94) {
+        ccsx_set_error(f + ": handoff options out of range (16 <= tile_len <= 128; 1 <= max_rows <= 32; 0 <= skip_above <= 94)");
+        return -1;
+    }
+    if (!q->out) { ccsx_set_error(f + ": null handoff out"); return -1; }
+    *out = *q->out;
+    if (!out->counts || !out->tile_zmw || !out->tile_start || !out->tile_len || !out->tile_qsum || !out->tile_rows || !out->row_pass || !out->row_strand || !out->cells) {
+        ccsx_set_error(f + ": handoff out arrays missing");
+        return -1;
+    }
+    if (out->max_tiles < 1 || out->max_tiles > CCSX_HANDOFF_MAX_TILES) { ccsx_set_error(f + ": handoff out: max_tiles must be 1 .. 2^26"); return -1; }
+    return 0;
+}
+
+// the slot's scratch and output arrays, reserved by the first request and grown by a larger one; nothing is enqueued: the kernels write every word they read
+static int handoff_attach(Slot &S, const ccsx_handoff_opts &o, int64_t max_tiles)
+{
+    KParams &P = S.P;
+    const size_t n = (size_t)P.n_zmw, wins = (size_t)P.total_wslots + 1, M = (size_t)max_tiles, R = (size_t)o.max_rows, T = (size_t)o.tile_len;
+    const size_t tiles = (size_t)ccsx_handoff_tile_off(S.T.cap_total, (int)n, o.tile_len) + 1;
+    if (tiles > 0x7fff0000ull) { ccsx_set_error("handoff: batch too large (more than 2^31 tiles): split it"); return -1; }
+    if (S.d_ho.reserve((2 * n + 2 * tiles + wins) * 4) || S.d_ho_out.reserve(M * R * T * 4 + (5 * M + 2) * 4 + 2 * M * R)) return -2;
+    P.ho = o; P.ho_max_tiles = (int32_t)M;
+    P.ho_zcnt = (int32_t *)S.d_ho.p; P.ho_tslot = P.ho_zcnt + 2 * n; P.ho_tqsum = P.ho_tslot + tiles; P.ho_woff = P.ho_tqsum + tiles;
+    P.ho_cells = (uchar4 *)S.d_ho_out.p; P.ho_hdr = (int32_t *)(P.ho_cells + M * R * T); P.ho_counts = P.ho_hdr + 5 * M; P.ho_rows = (uint8_t *)(P.ho_counts + 2);
+    return 0;
+}
+
+// the output arrays into the caller's, host or device memory (hipMemcpyDefault), on `s`: the whole capacity, or — written_only, when the run has ended — the
+// slots that were written
+static int enqueue_handoff_download(const Slot &S, const ccsx_handoff_out &out, bool written_only, hipStream_t s)
+{
+    const KParams &P = S.P;
+    const size_t M = (size_t)P.ho_max_tiles, R = (size_t)P.ho.max_rows, T = (size_t)P.ho.tile_len;
+    size_t m = M;
+    if (written_only) {
+        int32_t c[2] = {0, 0};
+        HIPTRY(hipMemcpyAsync(c, P.ho_counts, 8, hipMemcpyDeviceToHost, s));
+        HIPTRY(hipStreamSynchronize(s));
+        m = std::min<size_t>(M, (size_t)std::max(c[1], 0));
+    }
+    HIPTRY(hipMemcpyAsync(out.counts, P.ho_counts, 8, hipMemcpyDefault, s));
+    if (!m) return 0;
+    int32_t *const hdr[5] = {out.tile_zmw, out.tile_start, out.tile_len, out.tile_qsum, out.tile_rows};
+    for (int k = 0; k < 5; ++k) HIPTRY(hipMemcpyAsync(hdr[k], P.ho_hdr + (size_t)k * M, m * 4, hipMemcpyDefault, s));
+    HIPTRY(hipMemcpyAsync(out.row_pass, P.ho_rows, m * R, hipMemcpyDefault, s));
+    HIPTRY(hipMemcpyAsync(out.row_strand, P.ho_rows + M * R, m * R, hipMemcpyDefault, s));
+    HIPTRY(hipMemcpyAsync(out.cells, P.ho_cells, m * R * T * 4, hipMemcpyDefault, s));
+    return 0;
+}
+
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
@@ -1123,9 +1196,11 @@ static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string
 // first, each refused by its own message, then the extras; the caller's null-argument check follows (without a batch there is nothing to measure a report
 // against, and that check refuses the call).
 static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
-                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr)
+                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr,
+                       const ccsx_handoff_request *handoff = nullptr)
 {
     *W = Wants{};
+    if (handoff && handoff_request_check(handoff, &W->handoff_opts, &W->handoff_out, fn)) return -1;
     if (coverage && hd) return refuse(fn, "the coverage and the heteroduplex requests are not combined");
     if (coverage && b && coverage_request_check(coverage, b, &W->coverage_opts, fn)) return -1;
     if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
@@ -1133,7 +1208,7 @@ static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const c
     if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
     if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
-    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage;
+    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = handoff;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
@@ -1148,6 +1223,7 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.fold && (rc = fold_attach(h, S, W.fold_opts))) return rc;
     if (W.adapters && (rc = adapter_attach(h, S, W.adapter_set, W.adapter_opts))) return rc;
     if (W.coverage && (rc = coverage_attach(h, S, W.coverage_opts, W.coverage->gate))) return rc;
+    if (W.handoff && (rc = handoff_attach(S, W.handoff_opts, W.handoff_out.max_tiles))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
     return 0;
@@ -1180,6 +1256,7 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
         if ((rc = download_planes({r->verdict, r->np_aligned, r->spans, r->cov_max, r->clean_min, r->drop_window, r->drop_windows, r->reach_sum, r->used_sum, r->used_min},
                                   S.P.cov_zi, n, s))) return rc;
     }
+    if (W.handoff && (rc = enqueue_handoff_download(S, W.handoff_out, W.handoff_written_only, s))) return rc;
     return 0;
 }
 
@@ -1286,17 +1363,23 @@ int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 // the members of a ccsx_requests as build_wants takes them (NULL: none); -1 for nonzero reserved words
-static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W)
+static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_handoff_request *handoff = nullptr)
 {
     static const ccsx_requests none = {};
     if (!rq) rq = &none;
     if (rq->reserved[0] || rq->reserved[1] || rq->reserved[2]) return refuse(fn, "ccsx_requests: reserved must be NULL");
-    return build_wants(rq->ex, nullptr, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage);
+    return build_wants(rq->ex, nullptr, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff);
 }
 int ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket)
 {
     Wants W;
     if (requests_wants(rq, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho, ccsx_ticket *ticket)
+{
+    Wants W;
+    if (requests_wants(rq, b, __func__, &W, ho) || (!ho && refuse(__func__, "null handoff request"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
@@ -1545,6 +1628,14 @@ int ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *re
 {
     Wants W;
     if (requests_wants(rq, b, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
+int ccsx_consensus_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho)
+{
+    Wants W;
+    if (requests_wants(rq, b, __func__, &W, ho) || (!ho && refuse(__func__, "null handoff request"))) return -1;
+    W.handoff_written_only = true;
     return consensus_sync(h, b, res, W, __func__);
 }
 

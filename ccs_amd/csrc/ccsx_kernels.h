@@ -161,7 +161,22 @@ struct KParams {
     int32_t orient_wgs;        // workgroups of the launch (each walks the ZMWs blockIdx.x, blockIdx.x + orient_wgs, ...)
     uint8_t *orient_rep8;      // [2][R] strand, call
     int32_t *orient_votes;     // [2][R] votes_same, votes_opp
+    // ---- polisher hand-off (ccsx_consensus_handoff / ccsx_submit_handoff; NULL otherwise): DESIGN.md §2 "Polisher hand-off".  Needs wtpl / wtmeta as kinetics does.
+    // The tiles of ZMW z are indexed ccsx_handoff_tile_off(seq_off[z], z, T) + t
+    ccsx_handoff_opts ho;
+    int32_t ho_max_tiles;      // capacity of the output arrays in tiles
+    int32_t *ho_zcnt;          // [2][n] tiles of the ZMW, selected tiles of the ZMW (k_tile_select)
+    int32_t *ho_tslot;         // [tiles] k_tile_select: the selected tile's rank within its ZMW; k_tile_scan: its slot g; -1 = not selected or beyond the capacity
+    int32_t *ho_tqsum;         // [tiles] sum of the tile's qual bytes
+    int32_t *ho_woff;          // [wslots] offset of every window's core in SEQ, indexed as wmeta is
+    int32_t *ho_counts;        // [2] tiles, selected tiles
+    int32_t *ho_hdr;           // [5][max_tiles] tile_zmw, tile_start, tile_len, tile_qsum, tile_rows
+    uint8_t *ho_rows;          // [2][max_tiles][R] row_pass, row_strand
+    uchar4 *ho_cells;          // [max_tiles][R][T]
 };
+// first tile index of ZMW z whose outputs start at seq_off: consecutive ZMWs get disjoint ranges of at least ceil(capacity / T) tiles, with no table
+static inline __host__ __device__ int64_t ccsx_handoff_tile_off(int64_t seq_off, int z, int T) { return seq_off / T + z; }
+#define CCSX_TILE_SCAN_ZMWS 64   // ZMWs per workgroup of k_tile_scan
 #define CCSX_COVERAGE_PLANES 10
 #define CCSX_COVERAGE_PRE_GATE 0x1cu   // the gate bits of the verdicts k_coverage reaches before the polish (2, 3, 4)
 

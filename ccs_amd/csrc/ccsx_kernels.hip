@@ -16,6 +16,8 @@
 //                       and / or the pileup summary (sa sm sx) from the same alignment         (docs/faq/bam-output.md:25-27)
 //   k_stitch      step10 concatenate window cores, rq / np / ec, status                      (docs/how-does-ccs-work.md:108-112)
 //   k_pile_stitch       the pileup summary's per-base planes (only with a pileup request)
+//   k_tile_select / k_tile_scan / k_tile_rows   the polisher hand-off: low-quality tiles as pass-by-column cells (only with a hand-off request)
+//                                                                                            (docs/faq/revio.md:28-53)
 //
 // The arithmetic follows DESIGN.md §SPEC operation by operation (compiled with -ffp-contract=off, no
 // fast-math) so that sequences are bit-identical to the CPU restatement.  No MFMA: the recurrences are
@@ -3313,6 +3315,60 @@ __device__ __forceinline__ int kin_traceback_runs(int upm, unsigned long long nd
     return myrow;
 }
 
+// The kinetics alignment of one wave's task (k_kinetics_t, k_tile_rows): one segment of n > 31 bases in the wave's 64 lanes, or two of <= 31 in its halves
+// (paired: lanes 0-31 the segment of nA bases, 32-63 that of nB).  The lane of row i = lane - base holds read base i - 1 (rbv; 0 beyond the segment) and the
+// template's bit planes of the segment's strand (tlo, thi: bit c = column c).  Returns, for the lane of column c < J, the read row a DIAG cell puts on
+// column c of the read-oriented template, or -1.
+__device__ __forceinline__ int kin_align_rows(int rbv, unsigned tlo, unsigned thi, int J, bool paired, int half, int row, int nA, int nB, int lane)
+{
+    // bit c of mt: read base of this row == template column c (the two bit planes of the template come as ballots)
+    const unsigned mt = ~((tlo ^ ((rbv & 1) ? ~0u : 0u)) | (thi ^ ((rbv & 2) ? ~0u : 0u)));
+    // scores are kept shifted by +5 inside a column (h5 = h + 5): diag5 = x + 8*match, left5 = H + 1.  Rows beyond
+    // the read compute garbage that no lower lane and no traceback step ever reads.
+    const int c1 = 4 * row - 5;
+    int H = row * SC_INS;
+    int upm = 0, lfm = 0;
+    for (int j = 1; j <= J; ++j) {
+        int x = wave_shr1_i32(H, NEGV);
+        if (row == 0) x = NEGV;                          // (lane 32 of a pair would otherwise see the other read)
+        const int diag5 = x + (int)(((mt >> (j - 1)) & 1u) << 3);
+        const int left5 = H + 1;
+        const int h5 = diag5 >= left5 ? diag5 : left5;
+        // insertion chain: v(i) = max_k<=i h(k) + (i-k)*SC_INS, one fused DPP max-scan (per half when paired)
+        const int d0 = h5 + c1;
+        const int v = (paired ? half_scan_max_i32(d0) : wave_scan_max_i32(d0)) - 4 * row;     // = v(i) exactly
+        const unsigned bit = 1u << (j - 1);
+        if (v + 5 > h5) upm |= bit;
+        else if (diag5 < left5) lfm |= bit;
+        H = v;
+    }
+    int myrow;
+    if (nA <= 31) {
+        const unsigned long long nd = (unsigned long long)(unsigned)(upm | lfm) << (32 - (row & 31));
+        myrow = kin_traceback_runs(upm, nd, nA, J, 0, lane);
+        if (paired) {
+            const int rowB = kin_traceback_runs(upm, nd, nB, J, 32, lane);
+            if (half) myrow = rowB;
+        }
+    } else myrow = kin_traceback(upm, lfm, nA, J, 0, lane);
+    return myrow;
+}
+
+// the tasks of up to PW_MAXREADS segments (sN: their lengths, -1 = unusable), in segment order: two short segments share a wave (32 lanes each).  One thread
+__device__ __forceinline__ int kin_plan_tasks(const int *sN, int ng, short2 *sTask)
+{
+    int nt = 0, pend = -1;
+    for (int r = 0; r < ng; ++r) {
+        const int n = sN[r];
+        if (n < 0) continue;
+        if (n > 31) sTask[nt++] = make_short2((short)r, (short)-1);
+        else if (pend < 0) pend = r;
+        else { sTask[nt++] = make_short2((short)pend, (short)r); pend = -1; }
+    }
+    if (pend >= 0) sTask[nt++] = make_short2((short)pend, (short)-1);
+    return nt;
+}
+
 // KIN: the kinetics sums (--hifi-kinetics); PILE: the pileup summary (ccsx_consensus_pileup / ccsx_submit_pileup, DESIGN.md §2 "Pileup summary") — per core
 // column the passes with a usable segment, and of those the DIAG cells whose bases agree / differ.  Both read the ONE alignment below; <1, 0> is the kinetics
 // kernel as it always was.
@@ -3361,16 +3417,7 @@ __global__ __launch_bounds__(256) void k_kinetics_t(KParams P, int slot0)
     }
     __syncthreads();
     if (tid == 0) {                                          // tasks: two short segments share a wave (32 lanes each)
-        int nt = 0, pend = -1;
-        for (int r = 0; r < ng; ++r) {
-            const int n = sN[r];
-            if (n < 0) continue;
-            if (n > 31) sTask[nt++] = make_short2((short)r, (short)-1);
-            else if (pend < 0) pend = r;
-            else { sTask[nt++] = make_short2((short)pend, (short)r); pend = -1; }
-        }
-        if (pend >= 0) sTask[nt++] = make_short2((short)pend, (short)-1);
-        sNT = nt;
+        sNT = kin_plan_tasks(sN, ng, sTask);
         if (PILE) { int nc = 0; for (int r = 0; r < ng; ++r) nc += sN[r] >= 0 ? 1 : 0; sCov += nc; }
     }
     __syncthreads();
@@ -3390,37 +3437,7 @@ __global__ __launch_bounds__(256) void k_kinetics_t(KParams P, int slot0)
         const int64_t p0 = P.base_off[r0 + g0 + myr] + sOff[myr];
         const int rbv = (row >= 1 && row <= n) ? (P.bases[p0 + row - 1] & 3) : 0;   // lane of row i holds read base i-1
         const uint8_t *t = sT[st];
-        // bit c of mt: read base of this row == template column c (the two bit planes of the template come as ballots)
-        const unsigned mt = ~((tlo[st] ^ ((rbv & 1) ? ~0u : 0u)) | (thi[st] ^ ((rbv & 2) ? ~0u : 0u)));
-        // scores are kept shifted by +5 inside a column (h5 = h + 5): diag5 = x + 8*match, left5 = H + 1.  Rows beyond
-        // the read compute garbage that no lower lane and no traceback step ever reads.
-        const int c1 = 4 * row - 5;
-        int H = row * SC_INS;
-        int upm = 0, lfm = 0;
-        for (int j = 1; j <= J; ++j) {
-            int x = wave_shr1_i32(H, NEGV);
-            if (row == 0) x = NEGV;                          // (lane 32 of a pair would otherwise see the other read)
-            const int diag5 = x + (int)(((mt >> (j - 1)) & 1u) << 3);
-            const int left5 = H + 1;
-            const int h5 = diag5 >= left5 ? diag5 : left5;
-            // insertion chain: v(i) = max_k<=i h(k) + (i-k)*SC_INS, one fused DPP max-scan (per half when paired)
-            const int d0 = h5 + c1;
-            const int v = (paired ? half_scan_max_i32(d0) : wave_scan_max_i32(d0)) - 4 * row;     // = v(i) exactly
-            const unsigned bit = 1u << (j - 1);
-            if (v + 5 > h5) upm |= bit;
-            else if (diag5 < left5) lfm |= bit;
-            H = v;
-        }
-        int myrow;
-        const int nA = rfl(sN[task.x]);
-        if (nA <= 31) {
-            const unsigned long long nd = (unsigned long long)(unsigned)(upm | lfm) << (32 - (row & 31));
-            myrow = kin_traceback_runs(upm, nd, nA, J, 0, lane);
-            if (paired) {
-                const int rowB = kin_traceback_runs(upm, nd, rfl(sN[task.y]), J, 32, lane);
-                if (half) myrow = rowB;
-            }
-        } else myrow = kin_traceback(upm, lfm, nA, J, 0, lane);
+        const int myrow = kin_align_rows(rbv, tlo[st], thi[st], J, paired, half, row, rfl(sN[task.x]), paired ? rfl(sN[task.y]) : 0, lane);
         if (row < J && myrow >= 0) {
             const int jf = st ? J - 1 - row : row;
             const int64_t p = p0 + myrow;
@@ -3572,6 +3589,237 @@ __global__ __launch_bounds__(64) void k_pile_stitch(KParams P)
             }
         }
         run += __shfl(pre, 63);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The polisher hand-off (ccsx_consensus_handoff / ccsx_submit_handoff; DESIGN.md §2 "Polisher hand-off").  Three kernels on the polish stream after the stitch:
+//   k_tile_select  one wave per ZMW: the tiles of its consensus, their qual sums and selection flags, each selected tile's rank within the ZMW, the ZMW's counts,
+//                  and every window's core offset in SEQ (k_pile_stitch's scan)
+//   k_tile_scan    CCSX_TILE_SCAN_ZMWS ZMWs per workgroup: the exclusive scan of the counts (every workgroup sums the counts in front of it: integer sums, no
+//                  atomics, so slot g of a tile depends on the batch alone), the batch's counts, the headers and row tables of the tiles within the capacity,
+//                  the padding cells of a short last tile
+//   k_tile_rows    one workgroup per window slot, in k_kinetics_t's launch pieces: the kinetics alignment of the row passes' segments, the cells of the
+//                  window's core columns for all R rows.  Every cell has one writer
+static_assert(PW_MAXREADS >= 32, "k_tile_rows keeps up to 32 rows (ccsx_handoff_opts.max_rows) in the per-group arrays");
+
+__global__ __launch_bounds__(64) void k_tile_select(KParams P)
+{
+    const int z = blockIdx.x, lane = threadIdx.x;
+    const int T = P.ho.tile_len, L = P.out_len[z];
+    const int64_t so = P.seq_off[z], t0 = ccsx_handoff_tile_off(so, z, T);
+    const int nt = (L + T - 1) / T;
+    int nsel = 0;
+    for (int tb = 0; tb < nt; tb += LANES) {
+        const int t = tb + lane;
+        int qsum = 0, len = 0;
+        if (t < nt) {
+            len = L - t * T < T ? L - t * T : T;
+            const uint8_t *q = P.out_qual + so + (int64_t)t * T;
+            for (int k = 0; k < len; ++k) qsum += q[k];
+        }
+        const bool sel = t < nt && qsum < P.ho.skip_above * len;
+        const unsigned long long m = __ballot(sel);
+        if (t < nt) { P.ho_tqsum[t0 + t] = qsum; P.ho_tslot[t0 + t] = sel ? nsel + __popcll(m & ((1ull << lane) - 1ull)) : -1; }
+        nsel += __popcll(m);
+    }
+    if (lane == 0) { P.ho_zcnt[z] = nt; P.ho_zcnt[P.n_zmw + z] = nsel; }
+    if (L <= 0) return;                                      // (a ZMW with a consensus was stitched from all its windows)
+    const int nw = P.nwin[z];
+    const size_t w0 = (size_t)(P.wb_off[z] - z);
+    int run = 0;
+    for (int wbase = 0; wbase < nw; wbase += LANES) {
+        const int w = wbase + lane;
+        const int len = w < nw ? P.wmeta[w0 + w].x : 0;
+        int pre = len;                                      // inclusive scan of the core lengths
+#pragma unroll
+        for (int s = 1; s < LANES; s <<= 1) { int o = __shfl_up(pre, s); if (lane >= s) pre += o; }
+        if (w < nw) P.ho_woff[w0 + w] = run + pre - len;
+        run += __shfl(pre, 63);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tile_scan(KParams P)
+{
+    __shared__ int sRed[2][4];
+    __shared__ int sBase[CCSX_TILE_SCAN_ZMWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = P.n_zmw, zb = blockIdx.x * CCSX_TILE_SCAN_ZMWS;
+    const int T = P.ho.tile_len, R = P.ho.max_rows, M = P.ho_max_tiles;
+    int a = 0, s = 0;
+    for (int z = tid; z < zb; z += 256) { a += P.ho_zcnt[z]; s += P.ho_zcnt[n + z]; }
+    a = wave_reduce_add_i32(a); s = wave_reduce_add_i32(s);
+    if (lane == 0) { sRed[0][wave] = a; sRed[1][wave] = s; }
+    __syncthreads();
+    if (wave == 0) {
+        const int pre_all = sRed[0][0] + sRed[0][1] + sRed[0][2] + sRed[0][3], pre_sel = sRed[1][0] + sRed[1][1] + sRed[1][2] + sRed[1][3];
+        const int z = zb + lane;
+        const int c = z < n ? P.ho_zcnt[n + z] : 0, ta = z < n ? P.ho_zcnt[z] : 0;
+        const int inc = wave_scan_add_i32(c), tot = wave_reduce_add_i32(ta);
+        sBase[lane] = pre_sel + inc - c;
+        if (lane == 63 && zb + CCSX_TILE_SCAN_ZMWS >= n) { P.ho_counts[0] = pre_all + tot; P.ho_counts[1] = pre_sel + inc; }   // the last workgroup: the batch's counts
+    }
+    __syncthreads();
+    const int per = CCSX_TILE_SCAN_ZMWS / 4;
+    for (int i = 0; i < per; ++i) {                          // one wave per ZMW
+        const int zl = wave * per + i, z = zb + zl;
+        if (z >= n) break;
+        if (P.ho_zcnt[n + z] == 0) continue;
+        const int g0 = sBase[zl], nt = P.ho_zcnt[z], L = P.out_len[z];
+        const int64_t t0 = ccsx_handoff_tile_off(P.seq_off[z], z, T);
+        // the ZMW's rows: row k = the k-th valid pass among those used, in batch order
+        const int r0 = P.read_off[z], nreads = P.nreads_used[z];
+        unsigned long long vm[4] = {0, 0, 0, 0};
+        int nrows = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int p = c * 64 + lane;
+            vm[c] = __ballot(p < nreads && P.avalid[r0 + p] != 0);
+            nrows += __popcll(vm[c]);
+        }
+        if (nrows > R) nrows = R;
+        int rp = 255, rs = 0;
+        if (lane < nrows) {
+            int rem = lane;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int pc = __popcll(vm[c]);
+                if (rp == 255 && rem < pc) {
+                    unsigned long long x = vm[c];
+                    for (int q = 0; q < rem; ++q) x &= x - 1;
+                    rp = c * 64 + __builtin_ctzll(x);
+                }
+                rem -= pc;
+            }
+            rs = (P.flags[r0 + rp] ^ P.flags[r0 + (P.zref[z] & 255)]) & 1;
+        }
+        for (int tb = 0; tb < nt; tb += LANES) {
+            const int t = tb + lane;
+            int g = -1;
+            if (t < nt) {
+                const int loc = P.ho_tslot[t0 + t];
+                if (loc >= 0) {
+                    g = g0 + loc < M ? g0 + loc : -1;
+                    P.ho_tslot[t0 + t] = g;                  // from here on: the tile's slot, -1 beyond the capacity
+                }
+                if (g >= 0) {
+                    P.ho_hdr[g] = z; P.ho_hdr[M + g] = t * T; P.ho_hdr[2 * (size_t)M + g] = L - t * T < T ? L - t * T : T;
+                    P.ho_hdr[3 * (size_t)M + g] = P.ho_tqsum[t0 + t]; P.ho_hdr[4 * (size_t)M + g] = nrows;
+                }
+            }
+            unsigned long long todo = __ballot(g >= 0);
+            while (todo) {                                   // the row tables of each such tile, and the padding cells of a short one
+                const int src = __builtin_ctzll(todo);
+                todo &= todo - 1;
+                const int gg = __shfl(g, src), tt = tb + src;
+                if (lane < R) { P.ho_rows[(size_t)gg * R + lane] = (uint8_t)rp; P.ho_rows[((size_t)M + gg) * R + lane] = (uint8_t)rs; }
+                const int len = L - tt * T < T ? L - tt * T : T, pad = T - len;
+                for (int q = lane; q < R * pad; q += LANES)
+                    P.ho_cells[((size_t)gg * R + q / pad) * T + len + q % pad] = make_uchar4(5, 0, 0, 0);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tile_rows(KParams P, int slot0)
+{
+    __shared__ uint8_t sT[2][32];
+    __shared__ int sN[PW_MAXREADS], sOff[PW_MAXREADS], sPass[PW_MAXREADS];   // the rows' segments: length (-1 = unusable or no such row), offset in the pass, the pass
+    __shared__ uint8_t sSt[PW_MAXREADS];
+    __shared__ short2 sTask[PW_MAXREADS];
+    __shared__ int sNT, sWc[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bid = slot0 + xcd_contiguous(blockIdx.x, polish_piece_windows(P.wstart[P.n_zmw], slot0, (int)gridDim.x));   // (as k_polish)
+    if (bid < slot0) return;
+    const int z = P.wslot_zmw[bid];
+    if (P.out_len[z] <= 0) return;                           // no consensus: no tiles
+    const int w = bid - P.wstart[z];
+    const int nw = P.nwin[z];
+    const size_t wi = (size_t)(P.wb_off[z] - z) + w;
+    const int nc = P.wmeta[wi].x;
+    if (nc <= 0) return;
+    const short2 tm = P.wtmeta[wi];
+    const int J = tm.x, cs = tm.y, ce = cs + nc;
+    const int T = P.ho.tile_len, R = P.ho.max_rows;
+    // the tiles the core's columns fall into (<= 32 columns, tiles of >= 16: at most three) and their slots; none selected within the capacity: nothing to do
+    const int woff = P.ho_woff[wi];
+    const int64_t t0 = ccsx_handoff_tile_off(P.seq_off[z], z, T);
+    const int tf = woff / T, tl = (woff + nc - 1) / T;
+    const int g0 = P.ho_tslot[t0 + tf], g1 = tf + 1 <= tl ? P.ho_tslot[t0 + tf + 1] : -1, g2 = tf + 2 <= tl ? P.ho_tslot[t0 + tf + 2] : -1;
+    if ((g0 & g1 & g2) < 0) return;
+    uchar4 *const cells = P.ho_cells;                        // (captured by value: a reference to P would put the whole parameter block into scratch)
+    auto put = [cells, woff, T, R, tf, g0, g1, g2](int k, int col, uchar4 v) {   // row k, core column col
+        const int pos = woff + col, tq = pos / T - tf;
+        const int g = tq == 0 ? g0 : (tq == 1 ? g1 : g2);
+        if (g >= 0) cells[((size_t)g * R + k) * T + (pos - (tf + tq) * T)] = v;
+    };
+    const int r0 = P.read_off[z], nreads = P.nreads_used[z];
+    const int idx_ws = (w == 0) ? 0 : 2 * w - 1, idx_we = (w == nw - 1) ? 2 * nw - 1 : 2 * (w + 1);
+    if (tid < J) { const uint8_t b = P.wtpl[wi * 32 + tid]; sT[0][tid] = b; sT[1][J - 1 - tid] = (uint8_t)(3 - b); }
+    if (tid < PW_MAXREADS) sN[tid] = -1;
+    // the pass -> row map (at most CCSX_MAX_PASSES = 255 passes: one thread each)
+    const bool valid = tid < nreads && P.avalid[r0 + tid] != 0;
+    const unsigned long long vmask = __ballot(valid);
+    if (lane == 0) sWc[wave] = __popcll(vmask);
+    __syncthreads();
+    int k = __popcll(vmask & ((1ull << lane) - 1ull));
+    for (int q = 0; q < wave; ++q) k += sWc[q];
+    int nrows = sWc[0] + sWc[1] + sWc[2] + sWc[3];
+    if (nrows > R) nrows = R;
+    if (valid && k < R) {                                    // the row's segment inside this window (k_kinetics_t's)
+        const int rr = r0 + tid;
+        const int st = ((P.flags[rr] ^ P.flags[r0 + (P.zref[z] & 255)]) & 1) ? 1 : 0;
+        const int32_t *ent = P.ent + P.ent_off[rr];
+        const int a = ent[idx_ws], b = ent[idx_we];
+        int n = b - a;
+        if (n < 0 || n > CCSX_IMAX) n = -1;
+        sN[k] = n; sOff[k] = st ? (int)(P.base_off[rr + 1] - P.base_off[rr]) - b : a; sSt[k] = (uint8_t)st; sPass[k] = tid;
+    }
+    __syncthreads();
+    if (tid == 0) sNT = kin_plan_tasks(sN, nrows, sTask);
+    __syncthreads();
+    const int ntask = sNT;
+    unsigned tlo[2], thi[2];                                 // template bit planes per strand: bit c = column c (wave-uniform)
+    for (int sd = 0; sd < 2; ++sd) {
+        const int b = lane < J ? sT[sd][lane] : 0;
+        tlo[sd] = (unsigned)__ballot(b & 1); thi[sd] = (unsigned)__ballot(b & 2);
+    }
+    for (int tk = wave; tk < ntask; tk += 4) {
+        const short2 task = sTask[tk];
+        const bool paired = rfl((int)task.y) >= 0;
+        const int half = (paired && lane >= 32) ? 1 : 0;
+        const int base = half * 32, row = lane - base;
+        const int myr = half ? task.y : task.x;
+        const int n = sN[myr], st = sSt[myr];
+        const int64_t p0 = P.base_off[r0 + sPass[myr]] + sOff[myr];
+        const int rbv = (row >= 1 && row <= n) ? (P.bases[p0 + row - 1] & 3) : 0;   // lane of row i holds read base i-1
+        const int myrow = kin_align_rows(rbv, tlo[st], thi[st], J, paired, half, row, rfl(sN[task.x]), paired ? rfl(sN[task.y]) : 0, lane);
+        // the DIAG column next to this one on the side that is LEFT in SEQ: a lower column of a forward pass, a higher one of a pass on the opposite strand
+        const bool hit = row < J && myrow >= 0;
+        const unsigned dm = (unsigned)(__ballot(hit) >> base);
+        int nb = -1;
+        if (row < 32) {
+            if (!st) { const unsigned lo = dm & ((1u << row) - 1u); if (lo) nb = 31 - __builtin_clz(lo); }
+            else { const unsigned hi = row < 31 ? dm >> (row + 1) : 0u; if (hi) nb = row + 1 + __builtin_ctz(hi); }
+        }
+        const int rnb = __shfl(myrow, base + (nb < 0 ? 0 : nb));
+        if (row < J) {
+            const int jf = st ? J - 1 - row : row;
+            if (jf >= cs && jf < ce) {
+                uchar4 v = make_uchar4(4, 0, 0, 0);
+                if (myrow >= 0) {
+                    const int64_t p = p0 + myrow;
+                    const int b = P.bases[p] & 3;
+                    const int ins = st ? (nb >= 0 ? rnb - myrow - 1 : n - 1 - myrow) : (nb >= 0 ? myrow - rnb - 1 : myrow);
+                    v = make_uchar4((uint8_t)(st ? 3 - b : b), P.pw[p], P.ipd ? P.ipd[p] : (uint8_t)0, (uint8_t)ins);
+                }
+                put(myr, jf - cs, v);
+            }
+        }
+    }
+    for (int q = tid; q < R * nc; q += 256) {                // rows without a usable segment here, and the rows the ZMW does not have
+        const int kk = q / nc;
+        if (sN[kk] < 0) put(kk, q - kk * nc, make_uchar4(5, 0, 0, 0));
     }
 }
 
@@ -4978,6 +5226,16 @@ struct Schedule {
         launch("k_stitch", k_stitch, dim3(P.n_zmw), dim3(64), 0, sp, P);
         if (P.out_pile) launch("k_pile_stitch", k_pile_stitch, dim3(P.n_zmw), dim3(64), 0, sp, P);
         if (P.cov_zi) launch("k_coverage_post", k_coverage_post, dim3(P.n_zmw), dim3(64), 0, sp, P);   // the coverage screen's post-polish planes
+        if (P.ho_cells) {                                  // the polisher hand-off, on the final lengths and quals (a batch with a ccsx_handoff_request only)
+            launch("k_tile_select", k_tile_select, dim3(P.n_zmw), dim3(64), 0, sp, P);
+            trace_sync(sp, "k_tile_select");
+            launch("k_tile_scan", k_tile_scan, dim3((P.n_zmw + CCSX_TILE_SCAN_ZMWS - 1) / CCSX_TILE_SCAN_ZMWS), dim3(256), 0, sp, P);
+            trace_sync(sp, "k_tile_scan");
+            for_each_piece(P.total_wslots, sw.max_blocks, [&](long long s0, long long nb) {
+                launch("k_tile_rows", k_tile_rows, dim3(((unsigned)nb + 7u) & ~7u), dim3(256), 0, sp, P, (int)s0);
+            });
+            trace_sync(sp, "k_tile_rows");
+        }
         stage_event(CCSX_EV_END, sp);
     }
 };

@@ -622,6 +622,46 @@ typedef struct ccsx_requests {
 int         ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq);
 int         ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket);
 
+/* ---- polisher hand-off (docs/faq/revio.md:28-53: the low-quality windows of the Arrow consensus go to a second, learned polisher; the rule: DESIGN.md §2
+ * "Polisher hand-off", its own version ccsx_handoff_rule_version; no result of the consensus changes).  The consensus of every ZMW is cut into tiles of tile_len
+ * positions; a tile whose summed `qual` bytes are below skip_above x its length is selected, and for the selected tiles every pass is laid out column by column
+ * against the consensus — base, pulse width, inter-pulse duration, inserted bases — from the kinetics alignment of the pass's segments to the converged window
+ * templates (k_tile_select, k_tile_scan, k_tile_rows after k_stitch).  Integers only; the selected tiles are numbered in (ZMW, tile) order by a scan.
+ * Every array of ccsx_handoff_out may be host memory (page-locked preferred) or memory of the handle's device: each is copied with hipMemcpyDefault on the
+ * download stream, follows the lifetime rule of `res`, and is complete when ccsx_wait (or the synchronous call) returns.  Every byte of the slots
+ * g < min(counts[1], max_tiles) is written on every run; slots beyond are unspecified; nothing past an array's capacity is written.
+ *   ccsx_consensus_handoff  synchronous (slot 0); copies the written slots only.
+ *   ccsx_submit_handoff     ticketed like ccsx_submit; copies the WHOLE capacity of every array (max_tiles slots), since counts is not known when it is enqueued.
+ * rq may be NULL or carry any of ccsx_requests' members.  Options and capacity belong to the ticket.  A NULL out or array, max_tiles < 1, options out of range
+ * and nonzero reserved words are errors of the call: nothing is enqueued.                                                                                      */
+typedef struct ccsx_handoff_opts {
+    int32_t tile_len;            /* T: consensus positions per tile, 16 .. 128 [100]                                                                           */
+    int32_t max_rows;            /* R: rows (passes) per tile, 1 .. 32 [20]                                                                                    */
+    int32_t skip_above;          /* a tile is selected iff the sum of its qual bytes < skip_above x its length, 0 .. 94 [45]: 0 selects none, 94 all           */
+    int32_t reserved;            /* must be 0                                                                                                                  */
+} ccsx_handoff_opts;
+typedef struct ccsx_handoff_out {
+    int64_t  max_tiles;          /* capacity of the arrays below in tiles (>= 1)                                                                               */
+    int32_t *counts;             /* [2] tiles of the batch, tiles selected (may exceed max_tiles: the tiles g >= max_tiles are not written)                    */
+    int32_t *tile_zmw;           /* [max_tiles] ZMW index of slot g                                                                                            */
+    int32_t *tile_start;         /* [max_tiles] first consensus position of the tile                                                                           */
+    int32_t *tile_len;           /* [max_tiles] its length (<= T; only a ZMW's last tile is shorter)                                                           */
+    int32_t *tile_qsum;          /* [max_tiles] sum of the qual bytes of its positions                                                                         */
+    int32_t *tile_rows;          /* [max_tiles] min(R, valid passes of the ZMW)                                                                                */
+    uint8_t *row_pass;           /* [max_tiles][R] the row's pass (index within the ZMW), 255 = no such row                                                    */
+    uint8_t *row_strand;         /* [max_tiles][R] 0 = the strand of SEQ, 1 = the opposite strand (0 where there is no row)                                    */
+    uint8_t *cells;              /* [max_tiles][R][T][4] (base, pw, ip, ins): base 0-3, 4 = no base of the pass on the column, 5 = no segment / row / column   */
+} ccsx_handoff_out;
+typedef struct ccsx_handoff_request {
+    const ccsx_handoff_opts *opts;       /* NULL = ccsx_handoff_opts_default                                                                                     */
+    const ccsx_handoff_out  *out;
+    int64_t                  reserved[2];    /* must be 0                                                                                                        */
+} ccsx_handoff_request;
+void        ccsx_handoff_opts_default(ccsx_handoff_opts *o);
+int         ccsx_handoff_rule_version(void);
+int         ccsx_consensus_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho);
+int         ccsx_submit_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho, ccsx_ticket *ticket);
+
 /* ---- pass orientation (docs/faq/mode-by-strand.md:16-18: the orientation of the reads "with respect to the one closest to the median length"; the rule:
  * DESIGN.md §2 "Pass orientation", its own version ccsx_orient_rule_version).  Opt-in per pass: flags bit 3 (CCSX_PASS_STRAND_UNKNOWN).  k_orient runs first in
  * the draft stage of every batch that carries the bit, on every path that stages a batch (the fused forms, the draft and polish seams, ccsx_hd_batch,
