@@ -475,6 +475,21 @@ class Handoff:
         """slots that were written: min(selected tiles, max_tiles)"""
         return min(int(self.counts[1]), self.max_tiles)
 
+    def backbones(self, n_zmw: int) -> np.ndarray:
+        """per ZMW a pass that has the orientation of SEQ, for Handle.refine: the row_pass of the first row with row_strand 0 among the ZMW's slots; -1 where the
+        ZMW has no slot or no such row"""
+        ho = self.host()
+        bb = np.full(int(n_zmw), -1, np.int32)
+        for g in range(ho.n_tiles):
+            z = int(ho.tile_zmw[g])
+            if bb[z] >= 0:
+                continue
+            for k in range(int(ho.tile_rows[g])):
+                if ho.row_pass[g, k] != 255 and ho.row_strand[g, k] == 0:
+                    bb[z] = int(ho.row_pass[g, k])
+                    break
+        return bb
+
     def tile(self, g: int) -> dict:
         """slot g: zmw, start, len, qsum, rows, row_pass [R], row_strand [R], cells [R, len, 4]"""
         if not 0 <= g < self.n_tiles:
@@ -489,8 +504,148 @@ def _handoff_request(ho: Handoff):
     return CHandoffRequest(C.pointer(ho.opts), C.pointer(co), (C.c_int64 * 2)(0, 0)), co
 
 
+# ---- polisher hand-back (include/ccsx.h ccsx_refine_*; DESIGN.md §2 "Polisher hand-back")
+REFINE_SKIPPED, REFINE_RESCORED, REFINE_REFINED = 0, 1, 2
+REFINE_BAD_TILE, REFINE_BAD_ORDER, REFINE_BAD_SYMBOL, REFINE_TOO_LONG, REFINE_EMPTY, REFINE_BAD_BACKBONE, REFINE_BAD_LIST = -1, -2, -3, -4, -5, -6, -7
+REFINE_CODE_NAMES = {0: "SKIPPED", 1: "RESCORED", 2: "REFINED", -1: "BAD_TILE", -2: "BAD_ORDER", -3: "BAD_SYMBOL", -4: "TOO_LONG", -5: "EMPTY", -6: "BAD_BACKBONE",
+                     -7: "BAD_LIST"}
+
+
+class CRefineTiles(C.Structure):
+    """ccsx_refine_tiles: every array is host or device memory, so the mirror keeps plain addresses"""
+    _fields_ = [("n_tiles", C.c_int64), ("stride", C.c_int32), ("reserved0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("tile_zmw", "tile_start", "tile_len", "new_len", "new_seq", "new_qual")] + [("reserved", C.c_int64 * 2)]
+
+
+class CRefineReport(C.Structure):
+    _fields_ = [("counts", C.POINTER(C.c_int32)), ("code", C.POINTER(C.c_int32)), ("n_applied", C.POINTER(C.c_int32)), ("new_len", C.POINTER(C.c_int32)),
+                ("rq_merged", C.POINTER(C.c_float)), ("qual_merged", C.POINTER(C.c_uint8))]
+
+
+def refine_perr_table() -> np.ndarray:
+    """the engine's perr_fx[0 .. 93] (ccsx_refine_perr), uint64"""
+    return np.array([lib().ccsx_refine_perr(q) for q in range(94)], np.uint64)
+
+
+class RefineTiles:
+    """ccsx_refine_tiles: the second polisher's answer as replace-intervals on the consensus.  tile_zmw / tile_start / tile_len / new_len [n_tiles] int32,
+    new_seq / new_qual [n_tiles, stride] uint8.  The arrays are numpy (pageable or page-locked) or, with device=, torch tensors in the memory of that GPU."""
+    FIELDS = ("tile_zmw", "tile_start", "tile_len", "new_len", "new_seq", "new_qual")
+
+    def __init__(self, n_tiles: int, stride: int, arrays: dict, on_device: bool, keep=None):
+        self.n_tiles, self.stride, self.on_device, self._keep = int(n_tiles), int(stride), on_device, keep
+        for k in self.FIELDS:
+            setattr(self, k, arrays[k])
+
+    @staticmethod
+    def shapes(n_tiles: int, stride: int) -> dict:
+        m, u = int(n_tiles), int(stride)
+        d = {k: ((m,), np.int32) for k in RefineTiles.FIELDS[:4]}
+        d.update(new_seq=((m, u), np.uint8), new_qual=((m, u), np.uint8))
+        return d
+
+    @classmethod
+    def allocate(cls, n_tiles: int, stride: int = 128, device: "bool | int" = False, pinned: bool = False) -> "RefineTiles":
+        """zeroed arrays.  device=True (GPU 0) or a device ordinal: torch tensors on that GPU — it must be the handle's; pinned=True: page-locked arrays"""
+        shapes = cls.shapes(max(int(n_tiles), 0), stride)
+        keep = []
+        if device is not False:
+            import torch
+            dev = torch.device("cuda", 0 if device is True else int(device))
+            dts = {np.int32: torch.int32, np.uint8: torch.uint8}
+            arrays = {k: torch.zeros(sh, dtype=dts[dt], device=dev) for k, (sh, dt) in shapes.items()}
+            torch.cuda.synchronize(dev)
+        elif pinned:
+            arrays = {k: _pinned_array(int(np.prod(sh)), dt, keep).reshape(sh) for k, (sh, dt) in shapes.items()}
+            for a in arrays.values():
+                a[...] = 0
+        else:
+            arrays = {k: np.zeros(sh, dt) for k, (sh, dt) in shapes.items()}
+        return cls(n_tiles, stride, arrays, device is not False, keep)
+
+    @classmethod
+    def from_arrays(cls, tile_zmw, tile_start, tile_len, new_len, new_seq, new_qual, stride: "int | None" = None, device: "bool | int" = False,
+                    pinned: bool = False) -> "RefineTiles":
+        """new_seq / new_qual: [n_tiles, stride] arrays, or a list of per-tile sequences (then new_len may be None: their lengths) padded to `stride` [128]"""
+        m = len(tile_zmw)
+        if not isinstance(new_seq, np.ndarray) or new_seq.ndim != 2:
+            rows_s, rows_q = [np.asarray(r, np.uint8) for r in new_seq], [np.asarray(r, np.uint8) for r in new_qual]
+            u = int(stride) if stride is not None else 128
+            if new_len is None:
+                new_len = [len(r) for r in rows_s]
+            new_seq, new_qual = np.zeros((m, u), np.uint8), np.zeros((m, u), np.uint8)
+            for g in range(m):
+                k = min(len(rows_s[g]), u)
+                new_seq[g, :k], new_qual[g, :k] = rows_s[g][:k], rows_q[g][:k]
+        u = int(stride) if stride is not None else (int(new_seq.shape[1]) if m else 128)
+        t = cls.allocate(m, u, device=device, pinned=pinned)
+        src = dict(tile_zmw=tile_zmw, tile_start=tile_start, tile_len=tile_len, new_len=new_len, new_seq=new_seq, new_qual=new_qual)
+        for k, (sh, dt) in cls.shapes(m, u).items():
+            a = np.ascontiguousarray(np.asarray(src[k]).astype(dt, copy=False).reshape(sh))
+            if t.on_device:
+                import torch
+                getattr(t, k).copy_(torch.from_numpy(a))
+            else:
+                getattr(t, k)[...] = a
+        if t.on_device:
+            import torch
+            torch.cuda.synchronize(getattr(t, "tile_zmw").device)    # the copies are done before the engine's own streams read
+        return t
+
+    def c_struct(self) -> CRefineTiles:
+        c = CRefineTiles()
+        c.n_tiles, c.stride = self.n_tiles, self.stride
+        for k in self.FIELDS:
+            a = getattr(self, k)
+            setattr(c, k, (a.data_ptr() if self.on_device else a.ctypes.data) if self.n_tiles > 0 else None)
+        return c
+
+    def host(self) -> "RefineTiles":
+        if not self.on_device:
+            return self
+        return RefineTiles(self.n_tiles, self.stride, {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}, False)
+
+
+class RefineReport:
+    """ccsx_refine_report: counts [3] (ZMWs refined, tiles applied, list-order violations), code / n_applied / new_len [n] int32, rq_merged [n] float32,
+    qual_merged [capacity] uint8 or None"""
+    FIELDS = ("counts", "code", "n_applied", "new_len", "rq_merged", "qual_merged")
+
+    def __init__(self, seq_off, counts, code, n_applied, new_len, rq_merged, qual_merged, keep=None):
+        self.seq_off, self.counts, self.code, self.n_applied, self.new_len, self.rq_merged, self.qual_merged = seq_off, counts, code, n_applied, new_len, rq_merged, qual_merged
+        self._keep = keep
+
+    @classmethod
+    def allocate(cls, batch: "Batch", qual_merged: bool = True, pinned: bool = False) -> "RefineReport":
+        n = batch.n_zmw
+        off = np.zeros(n + 1, np.int64)
+        cb = batch.c_struct()
+        cap = lib().ccsx_result_layout(C.byref(cb), _ptr(off, C.c_int64))
+        keep = []
+
+        def z(count, dt):
+            if pinned:
+                a = _pinned_array(int(count), dt, keep)
+                a[...] = 0
+                return a
+            return np.zeros(count, dt)
+        return cls(off, z(3, np.int32), z(n, np.int32), z(n, np.int32), z(n, np.int32), z(n, np.float32), z(cap, np.uint8) if qual_merged else None, keep)
+
+    def c_struct(self) -> CRefineReport:
+        c = CRefineReport()
+        c.counts, c.code, c.n_applied, c.new_len = (_ptr(getattr(self, k), C.c_int32) for k in self.FIELDS[:4])
+        c.rq_merged = _ptr(self.rq_merged, C.c_float)
+        c.qual_merged = _ptr(self.qual_merged, C.c_uint8) if self.qual_merged is not None else None
+        return c
+
+    def quals(self, z: int) -> np.ndarray:
+        """the merged quals of ZMW z"""
+        o = int(self.seq_off[z])
+        return self.qual_merged[o:o + int(self.new_len[z])]
+
+
 # ---- pass orientation (include/ccsx.h ccsx_orient_*; DESIGN.md §2 "Pass orientation")
-PASS_STRAND_UNKNOWN = 0x8     # flags bit 3: bit 0 of this pass is a guess; k_orient decides it against the ZMW's anchor pass
+PASS_STRAND_UNKNOWN = 0x8    # flags bit 3: bit 0 of this pass is a guess; k_orient decides it against the ZMW's anchor pass
 ORIENT_GIVEN, ORIENT_ANCHOR, ORIENT_SAME, ORIENT_OPPOSITE, ORIENT_UNDETERMINED, ORIENT_NO_ANCHOR = range(6)
 ORIENT_CALL_NAMES = ["GIVEN", "ANCHOR", "SAME", "OPPOSITE", "UNDETERMINED", "NO_ANCHOR"]
 
@@ -790,6 +945,7 @@ EXPORTS = [
     "ccsx_coverage_opts_default", "ccsx_coverage_rule_version", "ccsx_consensus_requests", "ccsx_submit_requests",
     "ccsx_orient_opts_default", "ccsx_orient_rule_version", "ccsx_orient_batch", "ccsx_set_orient_opts", "ccsx_stage_orient",
     "ccsx_handoff_opts_default", "ccsx_handoff_rule_version", "ccsx_consensus_handoff", "ccsx_submit_handoff",
+    "ccsx_refine_tiles_init", "ccsx_refine_rule_version", "ccsx_refine_perr", "ccsx_refine_batch", "ccsx_submit_refine",
     "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
     "ccsx_inflate_blocks_host",
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
@@ -885,6 +1041,13 @@ def lib() -> C.CDLL:
         L.ccsx_handoff_opts_default.argtypes = [C.POINTER(HandoffOpts)]
         L.ccsx_consensus_handoff.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CHandoffRequest)]
         L.ccsx_submit_handoff.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CHandoffRequest), C.POINTER(C.c_int64)]
+        L.ccsx_refine_tiles_init.restype = None
+        L.ccsx_refine_tiles_init.argtypes = [C.POINTER(CRefineTiles)]
+        L.ccsx_refine_perr.restype = C.c_uint64
+        L.ccsx_refine_perr.argtypes = [C.c_int32]
+        _refine = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(C.c_int32), C.POINTER(CRefineTiles), C.POINTER(CResults), C.POINTER(CRefineReport)]
+        L.ccsx_refine_batch.argtypes = _refine
+        L.ccsx_submit_refine.argtypes = _refine + [C.POINTER(C.c_int64)]
         L.ccsx_orient_opts_default.restype = None
         L.ccsx_orient_opts_default.argtypes = [C.POINTER(OrientOpts)]
         L.ccsx_orient_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(OrientOpts), C.POINTER(COrientReport)]
@@ -1487,6 +1650,35 @@ class Handle:
         ho = handoff if handoff is not None else Handoff.allocate(batch, max_tiles, opts, device=self.device if device else False)
         self._fused("consensus", batch, res, _requests(via_requests=True, **requests), handoff=ho)
         return res, ho
+
+    # ---- the polisher hand-back (ccsx_refine_batch): refined tiles spliced into the base consensus on the GPU, QVs from one more Arrow round
+    @staticmethod
+    def _refine_args(batch: Batch, base: "Results", tiles: "RefineTiles", backbone, res: "Results", report: "RefineReport"):
+        bb = np.ascontiguousarray(np.asarray(backbone, np.int32))
+        if len(bb) != batch.n_zmw:
+            raise ValueError("backbone: one int32 per ZMW")
+        keep = (batch, base, tiles, bb, res, report, batch.c_struct(), base.c_struct(), tiles.c_struct(), res.c_struct(), report.c_struct())
+        cb, cbase, ct, cr, crep = keep[6:]
+        return (C.byref(cb), C.byref(cbase), _ptr(bb, C.c_int32), C.byref(ct), C.byref(cr), C.byref(crep)), keep
+
+    def refine(self, batch: Batch, base: "Results", tiles: "RefineTiles", backbone, report: "RefineReport | None" = None) -> tuple["Results", "RefineReport"]:
+        """(results, report).  base: the Results of an earlier run on `batch`; tiles: the RefineTiles; backbone: [n_zmw] a pass in SEQ's orientation per ZMW
+        (Handoff.backbones; < 0 leaves the ZMW out).  The results are those of polish(batch, spliced drafts, QV_ONLY); rq_merged is in the report"""
+        res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = report if report is not None else RefineReport.allocate(batch)
+        args, _keep = self._refine_args(batch, base, tiles, backbone, res, rep)
+        self._check(self._L.ccsx_refine_batch(self._h, *args), "ccsx_refine_batch")
+        return res, rep
+
+    def submit_refine(self, batch: Batch, base: "Results", tiles: "RefineTiles", backbone, res: "Results", report: "RefineReport") -> int:
+        """the ticketed form (wait / release as for submit): every array belongs to the ticket until it is waited for"""
+        args, keep = self._refine_args(batch, base, tiles, backbone, res, report)
+        t = C.c_int64()
+        self._check(self._L.ccsx_submit_refine(self._h, *args, C.byref(t)), "ccsx_submit_refine")
+        if not hasattr(self, "_inflight"):
+            self._inflight = {}
+        self._inflight[t.value] = (batch, res, keep)
+        return t.value
 
     def stage_polished(self, z: int):
         """after consensus_pileup: (templates [nw, 32] uint8, meta [nw, 3] int32 = J, cs, ce, passes used, backbone) of ZMW z's converged windows"""

@@ -24,6 +24,7 @@
 #include "ccsx.h"
 #include "ccsx_internal.h"
 #include "ccsx_kernels.h"
+#include "refine_core.h"
 
 #define HIPTRY(expr)                                                                                           \
     do {                                                                                                       \
@@ -139,6 +140,8 @@ struct Slot {
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
     DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
+    DevBuf d_rf_tiles, d_rf_base, d_rf_rep;       // polisher hand-back only (ccsx_submit_refine): the tile list and its classes; base lengths, backbones, seq, qual; the report
+    RefineParams RP{};                            // ... its kernels' parameters as enqueued (the report's download reads them)
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
@@ -1260,11 +1263,119 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
     return 0;
 }
 
+// ---- the polisher hand-back's host side (DESIGN.md §2 "Polisher hand-back"): a request as its entry points checked and copied it
+struct RefineReq {
+    const ccsx_results *base;
+    const int32_t *backbone;
+    ccsx_refine_tiles tiles;
+    ccsx_refine_report rep;
+};
+
+#define CCSX_REFINE_MAX_TILES (1ll << 26)
+
+void ccsx_refine_tiles_init(ccsx_refine_tiles *t)
+{
+    if (!t) return;
+    std::memset(t, 0, sizeof *t);
+    t->stride = 128;
+}
+
+int ccsx_refine_rule_version(void) { return 1; }
+
+uint64_t ccsx_refine_perr(int32_t q)
+{
+    static const uint64_t perr_fx[CCSX_REFINE_NQ] = {CCSX_REFINE_PERR_TABLE};
+    return q >= 0 && q < CCSX_REFINE_NQ ? perr_fx[q] : 0;
+}
+
+// every refusal that needs no staged batch, each by its own message; the tiles and report structs are copied (they are read during the call only)
+static int refine_request_check(const ccsx_batch *b, const ccsx_results *base, const int32_t *backbone, const ccsx_refine_tiles *t, const ccsx_refine_report *rep,
+                                RefineReq *rf, const char *fn)
+{
+    if (!b || !base || !backbone || !t || !rep) return refuse(fn, "null argument");
+    if (t->n_tiles < 0 || t->n_tiles > CCSX_REFINE_MAX_TILES) return refuse(fn, "refine tiles: n_tiles must be 0 .. 2^26");
+    if (t->stride < 1 || t->stride > 256) return refuse(fn, "refine tiles: stride must be 1 .. 256");
+    if (t->reserved0 || t->reserved[0] || t->reserved[1]) return refuse(fn, "refine tiles: reserved must be 0");
+    if (t->n_tiles > 0 && (!t->tile_zmw || !t->tile_start || !t->tile_len || !t->new_len || !t->new_seq || !t->new_qual)) return refuse(fn, "refine tiles: arrays missing");
+    if (!rep->counts || !rep->code || !rep->n_applied || !rep->new_len || !rep->rq_merged) return refuse(fn, "refine report: arrays missing");
+    if (base->n_zmw != b->n_zmw || !base->seq_off || !base->seq_len || !base->seq || !base->qual) return refuse(fn, "base: missing arrays, or sized for another batch");
+    *rf = RefineReq{base, backbone, *t, *rep};
+    return 0;
+}
+
+// `base` against the staged batch: the capacity layout, and no row longer than its slot
+static int refine_base_check(const Slot &S, const ccsx_results *base, const char *fn)
+{
+    const int n = S.P.n_zmw;
+    if (base->seq_capacity < S.seq_off[n]) return refuse(fn, "base: smaller than the capacity layout of this batch (ccsx_result_layout)");
+    for (int z = 0; z <= n; ++z) if (base->seq_off[z] != S.seq_off[z]) return refuse(fn, "base: seq_off is not the capacity layout of this batch (ccsx_result_layout)");
+    for (int z = 0; z < n; ++z) if (base->seq_len[z] > S.seq_off[z + 1] - S.seq_off[z]) return refuse(fn, "base: a sequence is longer than its slot");
+    return 0;
+}
+
+// The hand-back of a staged slot on `st`: the slot's buffers (reserved by the first request), the copies of the tile list (host or device memory), of base and
+// of the backbones, then k_refine_check, k_refine_plan and k_refine_splice, which leave the slot as upload_drafts would: the drafts in the draft buffer, din_len,
+// din_bb.
+static int refine_enqueue(Slot &S, const RefineReq &rf, hipStream_t st)
+{
+    const size_t n = (size_t)S.P.n_zmw, cap = (size_t)S.seq_off[n], M = (size_t)rf.tiles.n_tiles, U = (size_t)rf.tiles.stride;
+    if (S.d_din_len.reserve(n * 4) || S.d_din_bb.reserve(n * 4)) return -2;
+    if (S.d_rf_tiles.reserve(M * 5 * 4 + 2 * M * U + 16) || S.d_rf_base.reserve(n * 8 + 2 * cap + 16) || S.d_rf_rep.reserve(n * 8 + 16 + n * 16 + cap + 16)) return -2;
+    RefineParams R{};
+    R.n_zmw = (int32_t)n; R.stride = (int32_t)U; R.n_tiles = (int64_t)M;
+    R.read_off = S.P.read_off; R.seq_off = S.P.seq_off;
+    int32_t *ti = (int32_t *)S.d_rf_tiles.p;
+    R.tile_zmw = ti; R.tile_start = ti + M; R.tile_len = ti + 2 * M; R.tile_new_len = ti + 3 * M; R.tile_cls = (uint32_t *)(ti + 4 * M);
+    uint8_t *tb = (uint8_t *)(ti + 5 * M);
+    R.new_seq = tb; R.new_qual = tb + M * U;
+    int32_t *bi = (int32_t *)S.d_rf_base.p;
+    R.base_len = bi; R.backbone = bi + n;
+    uint8_t *bs = (uint8_t *)(bi + 2 * n);
+    R.base_seq = bs; R.base_qual = bs + cap;
+    R.tile_first = (int64_t *)S.d_rf_rep.p;
+    R.counts = (int32_t *)(R.tile_first + n);
+    R.code = R.counts + 4; R.n_applied = R.code + n; R.new_len = R.n_applied + n; R.rq_merged = (float *)(R.new_len + n);
+    R.qual_merged = rf.rep.qual_merged ? (uint8_t *)(R.rq_merged + n) : nullptr;
+    R.draft = (uint8_t *)S.d_draft.p; R.din_len = (int32_t *)S.d_din_len.p; R.din_bb = (int32_t *)S.d_din_bb.p;
+    if (M) {
+        const ccsx_refine_tiles &t = rf.tiles;
+        HIPTRY(hipMemcpyAsync(ti, t.tile_zmw, M * 4, hipMemcpyDefault, st));
+        HIPTRY(hipMemcpyAsync(ti + M, t.tile_start, M * 4, hipMemcpyDefault, st));
+        HIPTRY(hipMemcpyAsync(ti + 2 * M, t.tile_len, M * 4, hipMemcpyDefault, st));
+        HIPTRY(hipMemcpyAsync(ti + 3 * M, t.new_len, M * 4, hipMemcpyDefault, st));
+        HIPTRY(hipMemcpyAsync(tb, t.new_seq, M * U, hipMemcpyDefault, st));
+        HIPTRY(hipMemcpyAsync(tb + M * U, t.new_qual, M * U, hipMemcpyDefault, st));
+    }
+    HIPTRY(hipMemcpyAsync(bi, rf.base->seq_len, n * 4, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(bi + n, rf.backbone, n * 4, hipMemcpyHostToDevice, st));
+    if (cap) {
+        HIPTRY(hipMemcpyAsync(bs, rf.base->seq, cap, hipMemcpyHostToDevice, st));
+        HIPTRY(hipMemcpyAsync(bs + cap, rf.base->qual, cap, hipMemcpyHostToDevice, st));
+    }
+    if (const char *failed = ccsx_refine_launch(R, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    S.RP = R;
+    S.P.din_len = R.din_len; S.P.din_bb = R.din_bb;
+    S.P.opts.no_fallback_draft = 1;                       // (as upload_drafts: the alignment's outcome on a given draft is final)
+    return 0;
+}
+
+// the report of the slot's hand-back into the caller's host arrays, on `s` (after CCSX_EV_END)
+static int refine_download(const Slot &S, const ccsx_refine_report &rep, hipStream_t s)
+{
+    const RefineParams &R = S.RP;
+    const size_t n = (size_t)R.n_zmw;
+    HIPTRY(hipMemcpyAsync(rep.counts, R.counts, 12, hipMemcpyDeviceToHost, s));
+    if (int rc = download_planes({rep.code, rep.n_applied, rep.new_len}, R.code, n, s)) return rc;
+    HIPTRY(hipMemcpyAsync(rep.rq_merged, R.rq_merged, n * 4, hipMemcpyDeviceToHost, s));
+    if (rep.qual_merged && S.seq_off[n] > 0) HIPTRY(hipMemcpyAsync(rep.qual_merged, R.qual_merged, (size_t)S.seq_off[n], hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // one batch through the handle's pipeline: the fused path (ccsx_submit and its variants, with their Wants), the draft seam or the polish seam
 static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, ccsx_ticket *ticket, int mode, ccsx_drafts *dr_out, const ccsx_drafts *dr_in, uint32_t flags,
-                       const Wants &W, const char *fn)
+                       const Wants &W, const char *fn, const RefineReq *rf = nullptr)
 {
-    if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in)) return refuse(fn, "null argument");
+    if (!h || !b || !ticket || (mode != CCSX_RUN_DRAFT && !res) || (mode == CCSX_RUN_DRAFT && !dr_out) || (mode == CCSX_RUN_POLISH && !dr_in && !rf)) return refuse(fn, "null argument");
 #ifdef CCSX_FAULT_INJECTION                                          // test builds only (tests/test_cli_bam.py builds its own copy of the library)
     if (const char *e = std::getenv("CCSX_TEST_FAIL_SUBMIT"))        // fault injection for the driver's error-path test
         if (std::atoll(e) == (long long)h->next_ticket) { ++h->next_ticket; ccsx_set_error("injected failure (CCSX_TEST_FAIL_SUBMIT)"); return -2; }
@@ -1288,12 +1399,14 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
     int rc = stage(h, S, b, h->s_in, W);
     if (rc) return rc == -1 ? (S.staged = false, rc) : fail(rc);     // -1: rejected by validation before anything was enqueued
     if (mode != CCSX_RUN_DRAFT && (rc = check_results(S, res, S.P.out_kin != nullptr))) return unstage(rc);
-    if (mode != CCSX_RUN_FUSED && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) return unstage(rc);
+    if (mode != CCSX_RUN_FUSED && !rf && (rc = check_drafts(S, mode == CCSX_RUN_DRAFT ? dr_out : dr_in, mode == CCSX_RUN_POLISH))) return unstage(rc);
+    if (rf && (rc = refine_base_check(S, rf->base, fn))) return unstage(rc);
     if ((rc = attach(h, S, W, h->s_in))) return rc == -1 ? unstage(rc) : fail(rc);
     S.mode = mode;
     S.P.qv_only = (mode == CCSX_RUN_POLISH && (flags & CCSX_QV_ONLY)) ? 1 : 0;
 #define HIPTRY_F(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return fail(-2); } } while (0)
-    if (mode == CCSX_RUN_POLISH && (rc = upload_drafts(S, dr_in, h->s_in))) return fail(rc);
+    // the drafts of the polish seam: the caller's, or — the hand-back — spliced on the upload stream by the three kernels, ahead of ev_up
+    if (mode == CCSX_RUN_POLISH && (rc = rf ? refine_enqueue(S, *rf, h->s_in) : upload_drafts(S, dr_in, h->s_in))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_up, h->s_in));
     HIPTRY_F(hipStreamWaitEvent(h->s_draft, S.ev_up, 0));
     if ((rc = launch(h, S))) return fail(rc);
@@ -1310,6 +1423,7 @@ static int submit_impl(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
         if (dr_out->win_bounds) HIPTRY_F(hipMemcpyAsync(dr_out->win_bounds, P.wbounds, (size_t)S.wb_off[n] * 4, hipMemcpyDeviceToHost, h->s_out));
     } else if ((rc = enqueue_download(S, res, h->s_out))) return fail(rc);
     if ((rc = enqueue_wants_download(S, W, h->s_out))) return fail(rc);
+    if (rf && (rc = refine_download(S, rf->rep, h->s_out))) return fail(rc);
     HIPTRY_F(hipEventRecord(S.ev_done, h->s_out));
 #undef HIPTRY_F
     S.res = mode == CCSX_RUN_DRAFT ? nullptr : res; S.drafts_out = mode == CCSX_RUN_DRAFT ? dr_out : nullptr; S.inflight = true; S.ticket = h->next_ticket;
@@ -1400,6 +1514,21 @@ int ccsx_polish_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_drafts *dra
 {
     ccsx_ticket t;
     if (int rc = ccsx_submit_polish(h, b, drafts, res, flags, &t)) return rc;
+    return ccsx_wait(h, t);
+}
+
+int ccsx_submit_refine(ccsx_handle h, const ccsx_batch *b, const ccsx_results *base, const int32_t *backbone, const ccsx_refine_tiles *tiles, ccsx_results *res,
+                       ccsx_refine_report *report, ccsx_ticket *ticket)
+{
+    RefineReq rf;
+    if (refine_request_check(b, base, backbone, tiles, report, &rf, __func__)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_POLISH, nullptr, nullptr, CCSX_QV_ONLY, Wants{}, __func__, &rf);
+}
+int ccsx_refine_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_results *base, const int32_t *backbone, const ccsx_refine_tiles *tiles, ccsx_results *res,
+                      ccsx_refine_report *report)
+{
+    ccsx_ticket t;
+    if (int rc = ccsx_submit_refine(h, b, base, backbone, tiles, res, report, &t)) return rc;
     return ccsx_wait(h, t);
 }
 

@@ -662,6 +662,62 @@ int         ccsx_handoff_rule_version(void);
 int         ccsx_consensus_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho);
 int         ccsx_submit_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho, ccsx_ticket *ticket);
 
+/* ---- polisher hand-back (docs/faq/revio.md:35-51, steps 2 and 3: the refined windows are merged into the consensus, the read quality is calculated from the
+ * merged per-base values, and Arrow runs once more, for QVs only; the rule: DESIGN.md §2 "Polisher hand-back", its own version ccsx_refine_rule_version).  The
+ * second polisher's answer is a list of replace-intervals ("tiles") on the consensus of an earlier run, `base`: k_refine_check, k_refine_plan and k_refine_splice
+ * splice them into the base sequence on the device, where k_draft_in of the same ticket finds a caller's draft, and the polish seam scores the result with
+ * CCSX_QV_ONLY.  `res` is byte for byte what ccsx_polish_batch(h, b, drafts, res, CCSX_QV_ONLY) returns for drafts holding the spliced sequences, their lengths
+ * and backbone[z]; res->rq is that run's own.  The read quality of the merged values, the codes and — when asked — the merged quals come back in the report.
+ * Integers only except the one division of rq_merged; the same inputs give the same bytes on every run.
+ *   b         the passes the base consensus was made from (staged again, as by ccsx_submit_polish)
+ *   base      host arrays in the capacity layout of b (ccsx_result_layout); only seq_off, seq_len, seq and qual are read
+ *   backbone  [n_zmw], host: per ZMW a pass that has the orientation of SEQ (ccsx_drafts.backbone; any hand-off row with row_strand 0 names one in row_pass);
+ *             < 0 leaves the ZMW out (code SKIPPED)
+ * The list of tiles must be nondecreasing in tile_zmw with every tile_zmw in [0, n_zmw); the tiles of a ZMW must be in increasing order and disjoint.  Tiles need
+ * not coincide with the hand-off's tiling.  Every array of ccsx_refine_tiles may be host memory (page-locked preferred) or memory of the handle's device: each is
+ * copied with hipMemcpyDefault on the upload stream; they, base and backbone belong to the ticket and stay valid until it is retired.  A ZMW with a negative code
+ * has none of its tiles applied.  Errors of the call (nothing is enqueued, the handle stays usable): NULL arguments or report arrays, n_tiles < 0 or above 2^26,
+ * stride outside 1 .. 256, n_tiles > 0 with a NULL tile array, nonzero reserved words, base or res not in the capacity layout of b.
+ *   ccsx_refine_batch   synchronous: ccsx_submit_refine + ccsx_wait, as ccsx_polish_batch.
+ *   ccsx_submit_refine  ticketed like ccsx_submit_polish.                                                                                                      */
+#define CCSX_REFINE_SKIPPED        0   /* base.seq_len <= 0, or backbone < 0; the ZMW's tiles are ignored; refined draft of length 0                             */
+#define CCSX_REFINE_RESCORED       1   /* no tile: the base sequence                                                                                            */
+#define CCSX_REFINE_REFINED        2   /* every tile applied                                                                                                    */
+#define CCSX_REFINE_BAD_TILE     (-1)  /* a tile with start < 0, len < 1, start + len > L, new_len < 0 or new_len > stride: the base sequence                   */
+#define CCSX_REFINE_BAD_ORDER    (-2)  /* a tile that starts before its predecessor in the ZMW ends: the base sequence                                          */
+#define CCSX_REFINE_BAD_SYMBOL   (-3)  /* a code > 3 or a qual > 93 among the first new_len entries of a tile: the base sequence                                */
+#define CCSX_REFINE_TOO_LONG     (-4)  /* the spliced length exceeds the ZMW's slot: the base sequence                                                          */
+#define CCSX_REFINE_EMPTY        (-5)  /* the spliced length is below 1: the base sequence                                                                      */
+#define CCSX_REFINE_BAD_BACKBONE (-6)  /* backbone >= the ZMW's passes: refined draft of length 0                                                               */
+#define CCSX_REFINE_BAD_LIST     (-7)  /* the list breaks its order somewhere (counts[2] > 0): no tile is applied anywhere, the base sequence                   */
+typedef struct ccsx_refine_tiles {
+    int64_t  n_tiles;            /* >= 0                                                                                                                       */
+    int32_t  stride;             /* U: entries per row of new_seq / new_qual, 1 .. 256 [128]                                                                   */
+    int32_t  reserved0;          /* must be 0                                                                                                                  */
+    int32_t *tile_zmw;           /* [n_tiles]                                                                                                                  */
+    int32_t *tile_start;         /* [n_tiles] first replaced position of the base sequence                                                                     */
+    int32_t *tile_len;           /* [n_tiles] replaced positions (>= 1)                                                                                        */
+    int32_t *new_len;            /* [n_tiles] replacement length, 0 .. U                                                                                       */
+    uint8_t *new_seq;            /* [n_tiles][U] codes 0 .. 3; only the first new_len[g] entries of a row are read                                             */
+    uint8_t *new_qual;           /* [n_tiles][U] phred 0 .. 93, likewise                                                                                       */
+    int64_t  reserved[2];        /* must be 0                                                                                                                  */
+} ccsx_refine_tiles;
+typedef struct ccsx_refine_report {  /* host memory, complete when the ticket is retired                                                                       */
+    int32_t *counts;             /* [3] ZMWs with code REFINED, tiles applied, list-order violations                                                           */
+    int32_t *code;               /* [n_zmw] CCSX_REFINE_*                                                                                                      */
+    int32_t *n_applied;          /* [n_zmw] tiles applied                                                                                                      */
+    int32_t *new_len;            /* [n_zmw] length of the refined draft                                                                                        */
+    float   *rq_merged;          /* [n_zmw] 1 - mean error probability of the merged quals (0 for a draft of length 0)                                         */
+    uint8_t *qual_merged;        /* [seq_capacity] or NULL: the merged quals at seq_off[z], new_len[z] bytes; bytes beyond are unspecified                      */
+} ccsx_refine_report;
+void        ccsx_refine_tiles_init(ccsx_refine_tiles *t);   /* zeroes, stride 128 */
+int         ccsx_refine_rule_version(void);
+uint64_t    ccsx_refine_perr(int32_t q);                    /* round(10^(-q / 10) x 2^32) for q = 0 .. 93, else 0 */
+int         ccsx_refine_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_results *base, const int32_t *backbone, const ccsx_refine_tiles *tiles,
+                              ccsx_results *res, ccsx_refine_report *report);
+int         ccsx_submit_refine(ccsx_handle h, const ccsx_batch *b, const ccsx_results *base, const int32_t *backbone, const ccsx_refine_tiles *tiles,
+                               ccsx_results *res, ccsx_refine_report *report, ccsx_ticket *ticket);
+
 /* ---- pass orientation (docs/faq/mode-by-strand.md:16-18: the orientation of the reads "with respect to the one closest to the median length"; the rule:
  * DESIGN.md §2 "Pass orientation", its own version ccsx_orient_rule_version).  Opt-in per pass: flags bit 3 (CCSX_PASS_STRAND_UNKNOWN).  k_orient runs first in
  * the draft stage of every batch that carries the bit, on every path that stages a batch (the fused forms, the draft and polish seams, ccsx_hd_batch,
