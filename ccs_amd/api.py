@@ -799,6 +799,10 @@ class DeflateBlock(C.Structure):
     _fields_ = [("in_off", C.c_int64), ("in_len", C.c_int32), ("out_len", C.c_int32), ("out_off", C.c_int64)]
 
 
+class DeflateSpan(C.Structure):
+    _fields_ = [("in_off", C.c_int64), ("in_len", C.c_int32), ("out_cap", C.c_int32), ("out_off", C.c_int64)]
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("setup_ms", C.c_float), ("draft_ms", C.c_float), ("align_ms", C.c_float), ("polish_ms", C.c_float),
@@ -948,6 +952,8 @@ EXPORTS = [
     "ccsx_refine_tiles_init", "ccsx_refine_rule_version", "ccsx_refine_perr", "ccsx_refine_batch", "ccsx_submit_refine",
     "ccsx_inflate_rule_version", "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_blocks", "ccsx_inflate_submit", "ccsx_inflate_wait",
     "ccsx_inflate_blocks_host",
+    "ccsx_deflate_rule_version", "ccsx_deflate_bound", "ccsx_deflater_create", "ccsx_deflater_destroy", "ccsx_deflate_spans", "ccsx_deflate_submit",
+    "ccsx_deflate_wait", "ccsx_deflate_spans_host", "ccsx_deflate_crc", "ccsx_deflate_fill_spans", "ccsx_deflate_code_lengths",
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
     "ccsx_fit_opts_default", "ccsx_fitter_create", "ccsx_fitter_add", "ccsx_fitter_finish", "ccsx_fitter_destroy",
 ]
@@ -1060,6 +1066,21 @@ def lib() -> C.CDLL:
         L.ccsx_inflate_submit.argtypes = [C.c_void_p] + _call + [C.POINTER(C.c_int64)]
         L.ccsx_inflate_wait.argtypes = [C.c_void_p, C.c_int64]
         L.ccsx_inflate_blocks_host.argtypes = _call
+        _dcall = [C.POINTER(C.c_uint8), C.c_int64, C.POINTER(DeflateSpan), C.c_int32, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                  C.POINTER(C.c_int32)]
+        L.ccsx_deflate_bound.restype = C.c_int32
+        L.ccsx_deflate_bound.argtypes = [C.c_int32]
+        L.ccsx_deflater_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        L.ccsx_deflater_destroy.argtypes = [C.c_void_p]
+        L.ccsx_deflate_spans.argtypes = [C.c_void_p] + _dcall
+        L.ccsx_deflate_submit.argtypes = [C.c_void_p] + _dcall + [C.POINTER(C.c_int64)]
+        L.ccsx_deflate_wait.argtypes = [C.c_void_p, C.c_int64]
+        L.ccsx_deflate_spans_host.argtypes = _dcall
+        L.ccsx_deflate_crc.restype = C.c_uint32
+        L.ccsx_deflate_crc.argtypes = [C.POINTER(C.c_uint8), C.c_int64]
+        L.ccsx_deflate_code_lengths.argtypes = [C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
+        L.ccsx_deflate_fill_spans.restype = C.c_int32
+        L.ccsx_deflate_fill_spans.argtypes = [C.c_int]
         _i64p = C.POINTER(C.c_int64)
         L.ccsx_train_batch.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CDrafts), C.POINTER(CTrainCounts)]
         L.ccsx_train_pair_host.argtypes = [C.POINTER(Model), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -2072,6 +2093,120 @@ class Inflater:
     def close(self):
         if self._f:
             self._L.ccsx_inflater_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- BGZF deflate (include/ccsx.h "BGZF deflate on the device"; DESIGN.md §2 "BGZF deflate")
+DEFLATE_MAX_IN = 65536
+DEFLATE_STATUS_NAMES = ["OK", "OUTPUT_FULL"]
+
+
+def deflate_bound(in_len: int) -> int:
+    return int(lib().ccsx_deflate_bound(int(in_len)))
+
+
+def deflate_crc(data: bytes) -> int:
+    """ccsx_deflate_crc: the rule's sliced CRC32 alone, on the host"""
+    a = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
+    return int(lib().ccsx_deflate_crc(_ptr(a, C.c_uint8), len(data)))
+
+
+def deflate_code_lengths(freq, max_bits: int = 15) -> np.ndarray:
+    """ccsx_deflate_code_lengths: the rule's length-limited code lengths for these symbol counts (host)"""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    lens = np.zeros(len(f), dtype=np.uint8)
+    if lib().ccsx_deflate_code_lengths(_ptr(f, C.c_uint32), len(f), max_bits, _ptr(lens, C.c_uint8)) != 0:
+        raise RuntimeError("ccsx_deflate_code_lengths failed: " + lib().ccsx_last_error().decode())
+    return lens
+
+
+class DeflateCall:
+    """The buffers of one deflate call: spans packed back to back (gap bytes apart) in src, output ranges of out_caps[i] bytes (default: the bound) packed
+    (guard bytes before, between and behind them) in dst"""
+
+    def __init__(self, spans, out_caps=None, guard: int = 0, gap: int = 0, fill: int = 0):
+        n = len(spans)
+        caps = [deflate_bound(len(p)) for p in spans] if out_caps is None else [int(c) for c in out_caps]
+        assert n == len(caps)
+        self.spans = (DeflateSpan * max(n, 1))()
+        src, ioff, ooff = bytearray(), 0, guard
+        for i, (p, cap) in enumerate(zip(spans, caps)):
+            self.spans[i] = DeflateSpan(ioff, len(p), cap, ooff)
+            src += p + b"\0" * gap
+            ioff += len(p) + gap
+            ooff += cap + guard
+        self.n, self.guard = n, guard
+        self.src = np.frombuffer(bytes(src) or b"\0", dtype=np.uint8).copy()
+        self.src_len = len(src)
+        self.dst = np.full(max(ooff, 1), fill, dtype=np.uint8)
+        self.dst_len = ooff
+        self.out_len = np.full(max(n, 1), -1, dtype=np.int32)
+        self.crc = np.zeros(max(n, 1), dtype=np.uint32)
+        self.status = np.full(max(n, 1), -1, dtype=np.int32)
+
+    def args(self):
+        return (_ptr(self.src, C.c_uint8), self.src_len, self.spans, self.n, _ptr(self.dst, C.c_uint8), self.dst_len, _ptr(self.out_len, C.c_int32),
+                _ptr(self.crc, C.c_uint32), _ptr(self.status, C.c_int32))
+
+    def stream(self, i: int) -> bytes:
+        b = self.spans[i]
+        return self.dst[b.out_off:b.out_off + int(self.out_len[i])].tobytes()
+
+    def streams(self) -> list:
+        return [self.stream(i) for i in range(self.n)]
+
+
+def deflate_host(spans, out_caps=None, **layout):
+    """ccsx_deflate_spans_host: the encoder of k_deflate on the calling thread, no device.  Returns (the streams, status array, the call)"""
+    call = DeflateCall(spans, out_caps, **layout)
+    if lib().ccsx_deflate_spans_host(*call.args()) != 0:
+        raise RuntimeError("ccsx_deflate_spans_host failed: " + lib().ccsx_last_error().decode())
+    return call.streams(), call.status[:call.n].copy(), call
+
+
+class Deflater:
+    """One BGZF deflater bound to one GPU (ccsx_deflater_create): its own stream and buffers, nothing shared with a Handle or an Inflater.  Not thread-safe."""
+
+    def __init__(self, device: int = 0, max_in_bytes: int = 1 << 23, max_out_bytes: int = 1 << 23, max_spans: int = 256):
+        self._L = lib()
+        self._f = C.c_void_p()
+        self.max_in_bytes, self.max_out_bytes, self.max_spans = max_in_bytes, max_out_bytes, max_spans
+        if self._L.ccsx_deflater_create(device, max_in_bytes, max_out_bytes, max_spans, C.byref(self._f)) != 0:
+            raise RuntimeError("ccsx_deflater_create failed: " + self._L.ccsx_last_error().decode())
+        self._calls = {}
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
+
+    def submit(self, call: DeflateCall) -> int:
+        t = C.c_int64()
+        self._check(self._L.ccsx_deflate_submit(self._f, *call.args(), C.byref(t)), "ccsx_deflate_submit")
+        self._calls[t.value] = call      # the call's arrays stay alive until the ticket is waited for
+        return t.value
+
+    def wait(self, ticket: int) -> DeflateCall:
+        self._check(self._L.ccsx_deflate_wait(self._f, ticket), "ccsx_deflate_wait")
+        return self._calls.pop(ticket)
+
+    def run(self, call: DeflateCall) -> DeflateCall:
+        self._check(self._L.ccsx_deflate_spans(self._f, *call.args()), "ccsx_deflate_spans")
+        return call
+
+    def deflate(self, spans):
+        """spans: plain byte strings of at most DEFLATE_MAX_IN bytes.  Returns (the streams, the CRC32s, status array)"""
+        call = self.run(DeflateCall(spans))
+        return call.streams(), call.crc[:call.n].copy(), call.status[:call.n].copy()
+
+    def close(self):
+        if self._f:
+            self._L.ccsx_deflater_destroy(self._f)
             self._f = C.c_void_p()
 
     def __del__(self):

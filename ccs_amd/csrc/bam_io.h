@@ -334,6 +334,26 @@ private:
     size_t pos_ = 0;
 };
 
+// Another back end for the deflate step of a BgzfWriter (ccs --gpu-deflate), the counterpart of BgzfReader::set_inflate_backend.  The writer hands it raw blocks
+// (each at most 0xff00 bytes) a ticket at a time; submit() enqueues them without waiting and returns the call, wait() blocks until that call's streams are there:
+// per block the raw DEFLATE stream in dst[off[i], off[i] + len[i]) and the CRC32 of the block's plain bytes.  The back end keeps at most two calls in flight and
+// completes them in order; a writer that submits a third gets the oldest waited for on its behalf.  Both throw on an error of the back end.  It is not
+// thread-safe: the writers that share one run on one thread.
+struct BgzfDeflateCall {
+    std::vector<uint8_t> dst;
+    std::vector<int64_t> off;
+    std::vector<int32_t> len;
+    std::vector<uint32_t> crc;
+    virtual ~BgzfDeflateCall() {}
+};
+class BgzfDeflateBackend {
+public:
+    virtual ~BgzfDeflateBackend() {}
+    virtual size_t ticket_blocks() const = 0;          // the raw blocks of a ticket that fills the device
+    virtual std::shared_ptr<BgzfDeflateCall> submit(const std::vector<std::shared_ptr<std::vector<uint8_t>>> &blocks) = 0;
+    virtual void wait(BgzfDeflateCall &call) = 0;
+};
+
 class BgzfWriter {   // pooled deflate, in-order write
 public:
     BgzfWriter(const std::string &path, ThreadPool &pool, int level = 4) : pool_(pool), level_(level)
@@ -342,6 +362,9 @@ public:
         if (!f_) throw std::runtime_error("cannot create " + path);
     }
     ~BgzfWriter() { try { close(); } catch (...) {} }
+    // Deflate on a back end instead of the pool: raw blocks collect into tickets of ticket_blocks(), two tickets are kept in flight, and the streams that come
+    // back are wrapped (18-byte header, CRC32 + ISIZE trailer) and written in order on the caller's thread.  Set it before the first write.
+    void set_deflate_backend(BgzfDeflateBackend *b) { backend_ = b; }
     // position of the next byte as (block number << 16 | offset in that block); virtual_offset() resolves it after close()
     uint64_t mark() const { return ((uint64_t)nblocks_ << 16) | (uint64_t)buf_.size(); }
     uint64_t virtual_offset(uint64_t mark) const
@@ -364,6 +387,7 @@ public:
     {
         if (!f_) return;
         if (!buf_.empty()) flush_block();
+        if (backend_) { if (!raw_.empty()) submit_ticket(); while (!calls_.empty()) finish_ticket(); }     // a partial ticket goes out as it is
         drain(0);
         block_off_.push_back(written_);      // a mark taken at the very end resolves to the EOF block
         static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -380,6 +404,11 @@ private:
         auto sp = std::make_shared<std::vector<uint8_t>>(std::move(buf_));
         buf_.clear(); buf_.reserve(kBlock);
         ++nblocks_;
+        if (backend_) {
+            raw_.push_back(sp);
+            if (raw_.size() >= backend_->ticket_blocks()) submit_ticket();
+            return;
+        }
         const int lvl = level_;
         pending_.push_back(pool_.submit([sp, lvl] { return deflate_block(sp->data(), sp->size(), lvl); }));
         drain(128);
@@ -393,11 +422,42 @@ private:
             if (std::fwrite(c.data(), 1, c.size(), f_) != c.size()) throw std::runtime_error("short write");
         }
     }
+    struct Ticket { std::shared_ptr<BgzfDeflateCall> call; std::vector<uint32_t> isize; };
+    void submit_ticket()
+    {
+        while (calls_.size() >= 2) finish_ticket();
+        Ticket t;
+        for (const auto &b : raw_) t.isize.push_back((uint32_t)b->size());
+        try { t.call = backend_->submit(raw_); } catch (...) { raw_.clear(); throw; }
+        raw_.clear();
+        calls_.push_back(std::move(t));
+    }
+    void finish_ticket()
+    {
+        Ticket t = std::move(calls_.front()); calls_.pop_front();
+        backend_->wait(*t.call);
+        const BgzfDeflateCall &c = *t.call;
+        if (c.off.size() != t.isize.size() || c.len.size() != t.isize.size() || c.crc.size() != t.isize.size()) throw std::runtime_error("deflate back end: a ticket came back with another block count");
+        for (size_t i = 0; i < t.isize.size(); ++i) {
+            const size_t clen = (size_t)c.len[i], total = 18 + clen + 8;
+            if (c.len[i] <= 0 || c.off[i] < 0 || (size_t)c.off[i] + clen > c.dst.size()) throw std::runtime_error("deflate back end: a stream outside the ticket's buffer");
+            if (total > 65536) throw std::runtime_error("BGZF block too large");
+            uint8_t hdr[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)((total - 1) & 0xff), (uint8_t)((total - 1) >> 8)};
+            uint8_t tr[8];
+            for (int k = 0; k < 4; ++k) { tr[k] = (uint8_t)(c.crc[i] >> (8 * k)); tr[4 + k] = (uint8_t)(t.isize[i] >> (8 * k)); }
+            block_off_.push_back(written_);
+            written_ += total;
+            if (std::fwrite(hdr, 1, 18, f_) != 18 || std::fwrite(c.dst.data() + c.off[i], 1, clen, f_) != clen || std::fwrite(tr, 1, 8, f_) != 8) throw std::runtime_error("short write");
+        }
+    }
     ThreadPool &pool_;
     int level_;
     FILE *f_ = nullptr;
     std::vector<uint8_t> buf_;
     std::deque<std::future<std::vector<uint8_t>>> pending_;
+    BgzfDeflateBackend *backend_ = nullptr;
+    std::vector<std::shared_ptr<std::vector<uint8_t>>> raw_;   // raw blocks of the ticket being collected
+    std::deque<Ticket> calls_;               // tickets submitted and not yet written, oldest first
     size_t nblocks_ = 0;                     // blocks handed to the pool so far
     uint64_t written_ = 0;                   // compressed bytes written
     std::vector<uint64_t> block_off_;        // file offset of every written block

@@ -62,6 +62,7 @@ struct Options {
     std::string write_synth;      // "N,P,L[,seed]" -> write a synthetic subreads.bam to `out`
     bool dump = false;            // print one line per ZMW after the step-1 filters, no GPU
     bool gpu_inflate = false;     // --gpu-inflate: the BGZF blocks of IN are inflated by k_inflate (experimental)
+    bool gpu_deflate = false;     // --gpu-deflate: the BGZF blocks of OUT.bam and the --fail-reads BAM are deflated by k_deflate (experimental)
     bool host_only = false;       // reader -> filters -> packing into staging, no engine and no output: what the host side alone sustains
     bool by_strand = false;       // --by-strand: one consensus per strand (docs/faq/mode-by-strand.md:8-23)
     bool no_partial = false;      // --no-partial-passes: drop the subreads that are not flanked by adapters on both sides (as round 2 did)
@@ -252,6 +253,9 @@ void usage()
                  "      --max-qv Q            largest per-base QV reported; rq follows [50 = this build's calibrated cap; 93 = the reference's range]\n"
                  "      --gpu-inflate         inflate the BGZF blocks of IN on the GPU (k_inflate) instead of on the host threads; the CRC32 check, every\n"
                  "                            error and every output byte stay as they are [off; experimental]\n"
+                 "      --gpu-deflate         deflate the BGZF blocks of OUT.bam and of the --fail-reads BAM on the GPU (k_deflate, with their CRC32) instead of on\n"
+                 "                            the host threads; the records are the same, the compressed bytes are another valid BGZF encoding of them;\n"
+                 "                            OUT.fastq.gz, the .pbi files and the metrics stay on the host [off; experimental]\n"
                  "  test helpers (not in the reference):\n"
                  "      --write-synthetic N,P,L[,seed]  write a synthetic subreads.bam to OUT (no IN)\n"
                  "      --dump-zmws                     list ZMWs after the step-1 filters (no GPU, no OUT)\n"
@@ -261,7 +265,7 @@ void usage()
                  "                            triple: per iteration every batch is drafted and polished, the passes are measured against the polished reads of at\n"
                  "                            least --fit-min-rq (posterior event counts, k_train), and the fitter makes the next model.  Starts from the\n"
                  "                            chemistry's model or --model-file.  Not with a second positional, several GPUs, --chunk or any option of the\n"
-                 "                            output side (--fail-reads, --by-strand, --control, --adapters, reports, tags, --gpu-inflate): usage errors\n"
+                 "                            output side (--fail-reads, --by-strand, --control, --adapters, reports, tags, --gpu-inflate, --gpu-deflate): usage errors\n"
                  "      --fit-iterations N    EM iterations (default 3)\n"
                  "      --fit-min-rq X        predicted accuracy a polished read needs to serve as a truth (default 0.999)\n"
                  "      --fit-max-zmws N      use the first N ZMWs that pass the filters (default 0 = all)\n"
@@ -363,6 +367,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--dump-zmws") o.dump = true;
         else if (a == "--host-only") o.host_only = true;
         else if (a == "--gpu-inflate") o.gpu_inflate = true;
+        else if (a == "--gpu-deflate") o.gpu_deflate = true;
         else if (a == "--by-strand") o.by_strand = true;
         else if (a == "--no-partial-passes") o.no_partial = true;
         else if (a == "--qv-binning") o.qv_binning = true;
@@ -423,6 +428,7 @@ bool parse(int argc, char **argv, Options &o)
         if (!o.control.empty() || !o.adapters.empty() || o.coverage_filters)
             refuse("runs no draft screen: --control, --adapters and --coverage-filters are not supported with it");
         if (o.gpu_inflate) refuse("combined with --gpu-inflate is not supported");
+        if (o.gpu_deflate) refuse("combined with --gpu-deflate is not supported");
         if (o.report_named || o.metrics_named || !o.report_json.empty() || !o.hifi_summary.empty() || o.suppress_reports)
             refuse("writes no reports: --report-file, --metrics-json, --report-json, --hifi-summary-json and --suppress-reports are not supported with it");
         if (o.pileup || o.qv_binning || o.o.hifi_kinetics || o.min_tandem > 0)
@@ -939,6 +945,86 @@ struct GpuInflaters {
     }
 };
 
+// --gpu-deflate: the one deflater the run's BGZF writers share (the HiFi BAM and the --fail-reads BAM; both are written by the writer thread, the only thread
+// that calls this).  A ticket is as many raw 0xff00-byte blocks as fill the device: ccsx_deflate_fill_spans (CUs x resident workgroups of k_deflate), at least
+// 256.  submit() copies the blocks into one source buffer, enqueues and returns; two tickets are in flight at most, so a third submit first waits for the oldest
+// (its writer finds it done when it asks).  Every out_cap is ccsx_deflate_bound: no span can be OUTPUT_FULL.  After an error nothing more is sent to the device.
+// Page-locked memory: 2 call slots x (16.7 + 16.7) MB = 67 MB at 256 blocks.
+struct GpuDeflater : BgzfDeflateBackend {
+    struct Call : BgzfDeflateCall {
+        ccsx_ticket ticket = 0;
+        bool waited = false, bad = false;                // bad: waited for, and the ticket failed (its owner must not write it)
+        std::vector<uint8_t> src;
+        std::vector<ccsx_deflate_span> spans;
+        std::vector<int32_t> status;
+    };
+    ccsx_deflater f = nullptr;
+    size_t blocks = 256;
+    bool broken = false;
+    long long n_tickets = 0, n_blocks = 0, n_in = 0, n_out = 0, us_submit = 0, us_wait = 0;
+    std::deque<std::shared_ptr<Call>> inflight;      // oldest first
+    static long long us_since(std::chrono::steady_clock::time_point t) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count(); }
+    ~GpuDeflater() { if (f) ccsx_deflater_destroy(f); }
+    bool create(int device)
+    {
+        const int32_t fill = ccsx_deflate_fill_spans(device);
+        if (fill < 0) return false;
+        blocks = (size_t)std::max<int32_t>(256, fill);
+        return ccsx_deflater_create(device, (int64_t)blocks * 0xff00, (int64_t)blocks * ccsx_deflate_bound(0xff00), (int32_t)blocks, &f) == 0;
+    }
+    size_t ticket_blocks() const override { return blocks; }
+    void wait_oldest()
+    {
+        std::shared_ptr<Call> c = inflight.front(); inflight.pop_front();
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = ccsx_deflate_wait(f, c->ticket);
+        us_wait += us_since(t0);
+        c->waited = true;
+        c->bad = rc != 0 || std::any_of(c->status.begin(), c->status.end(), [](int32_t st) { return st != CCSX_DEFLATE_OK; });
+        if (rc) { broken = true; throw std::runtime_error(std::string("--gpu-deflate: ") + ccsx_last_error()); }
+        for (size_t i = 0; i < c->status.size(); ++i) {
+            if (c->status[i] != CCSX_DEFLATE_OK) { broken = true; throw std::runtime_error("--gpu-deflate: block " + std::to_string(i) + " of a ticket came back with status " + std::to_string(c->status[i])); }
+            n_out += c->len[i];
+        }
+    }
+    std::shared_ptr<BgzfDeflateCall> submit(const std::vector<std::shared_ptr<std::vector<uint8_t>>> &raw) override
+    {
+        if (broken) throw std::runtime_error("--gpu-deflate: the deflater failed earlier in this run");
+        if (raw.size() > blocks) throw std::runtime_error("--gpu-deflate: a ticket of more blocks than the deflater holds");
+        while (inflight.size() >= 2) wait_oldest();
+        const auto t0 = std::chrono::steady_clock::now();
+        auto c = std::make_shared<Call>();
+        const size_t n = raw.size();
+        size_t in = 0, out = 0;
+        c->spans.resize(n); c->off.resize(n); c->len.assign(n, 0); c->crc.assign(n, 0); c->status.assign(n, -1);
+        for (size_t i = 0; i < n; ++i) {
+            const int32_t len = (int32_t)raw[i]->size(), cap = ccsx_deflate_bound(len);
+            c->spans[i] = ccsx_deflate_span{(int64_t)in, len, cap, (int64_t)out};
+            c->off[i] = (int64_t)out;
+            in += (size_t)len; out += (size_t)cap;
+        }
+        c->src.resize(in); c->dst.resize(out);
+        for (size_t i = 0; i < n; ++i) std::memcpy(c->src.data() + c->spans[i].in_off, raw[i]->data(), raw[i]->size());
+        if (ccsx_deflate_submit(f, c->src.data(), (int64_t)in, c->spans.data(), (int32_t)n, c->dst.data(), (int64_t)out, c->len.data(), c->crc.data(), c->status.data(), &c->ticket)) {
+            broken = true;
+            throw std::runtime_error(std::string("--gpu-deflate: ") + ccsx_last_error());
+        }
+        inflight.push_back(c);
+        ++n_tickets; n_blocks += (long long)n; n_in += (long long)in;
+        us_submit += us_since(t0);
+        return c;
+    }
+    void wait(BgzfDeflateCall &call) override
+    {
+        Call &c = static_cast<Call &>(call);
+        while (!c.waited) {
+            if (inflight.empty()) throw std::runtime_error("--gpu-deflate: a ticket that is not in flight");
+            wait_oldest();
+        }
+        if (c.bad) throw std::runtime_error("--gpu-deflate: the deflater failed earlier in this run");
+    }
+};
+
 }  // namespace
 
 // ---- ccs --fit-model: EM over the packed batches of the file, serial, on one GPU (DESIGN.md §2 "Model training").  Per iteration a handle with the current
@@ -1090,6 +1176,23 @@ int main(int argc, char **argv)
                 if (rc_create) { std::fprintf(stderr, "ccs: %s\n", ccsx_last_error()); return 1; }
                 if (opt.log_level >= 2) std::fprintf(stderr, "ccs: device %d: NUMA node %d%s\n", d, ccsx_device_numa_node(d), node >= 0 ? " (its threads and page-locked staging are bound to it)" : " (no binding)");
                 handles.push_back(h);
+            }
+        }
+
+        // ---- --gpu-deflate: one deflater on the first engine device, shared by the run's BAM writers (declared here: it outlives the writer thread)
+        GpuDeflater gpu_deflater;
+        const bool fastq_out = opt.out.size() > 9 && opt.out.compare(opt.out.size() - 9, 9, ".fastq.gz") == 0;
+        bool use_gpu_deflate = false;
+        if (opt.gpu_deflate) {
+            if (opt.host_only || opt.dump) {
+                if (opt.log_level >= 2) std::fprintf(stderr, "ccs: --gpu-deflate ignored: no engine runs (--host-only, --dump-zmws)\n");
+            } else if (fastq_out && opt.fail_reads.empty()) {
+                if (opt.log_level >= 2) std::fprintf(stderr, "ccs: --gpu-deflate ignored: OUT.fastq.gz is written by gzip on the host and no BAM is written\n");
+            } else {
+                const int dev = opt.gpus[0];
+                if (!gpu_deflater.create(dev)) { std::fprintf(stderr, "ccs: %s\n", ccsx_last_error()); for (ccsx_handle h : handles) ccsx_destroy(h); return 1; }
+                if (opt.log_level >= 2) std::fprintf(stderr, "ccs: --gpu-deflate: tickets of %zu blocks on device %d, two in flight\n", gpu_deflater.ticket_blocks(), dev);
+                use_gpu_deflate = true;
             }
         }
 
@@ -1473,8 +1576,10 @@ int main(int argc, char **argv)
             gzFile gzq = nullptr;
             if (fastq) { gzq = gzopen(opt.out.c_str(), "wb4"); if (!gzq) throw std::runtime_error("cannot create " + opt.out); }
             else outp.reset(new BgzfWriter(opt.out, pool));
+            if (outp && use_gpu_deflate) outp->set_deflate_backend(&gpu_deflater);
             std::unique_ptr<BgzfWriter> failp;                      // --fail-reads: FAIL.bam under the main output's header, FAIL.bam.pbi beside it
             if (fail_reads) failp.reset(new BgzfWriter(opt.fail_reads, pool));
+            if (failp && use_gpu_deflate) failp->set_deflate_backend(&gpu_deflater);
             PbiIndex fpbi; std::vector<uint64_t> fmarks;
             std::string fq;
             bool header_done = false;
@@ -1694,6 +1799,10 @@ int main(int argc, char **argv)
                                  "draft + align %.2f ms, polish %.2f ms, between the stages %.2f ms, ticket start to end %.2f ms\n",
                          eng.tickets, eng.zmws, eng.last - eng.first, (eng.last - eng.first) * k, eng.draft * k, eng.polish * k, eng.queue * k, eng.total * k);
         }
+        if (opt.log_level >= 2 && use_gpu_deflate)
+            std::fprintf(stderr, "ccs: --gpu-deflate: %lld tickets, %lld blocks, %.1f MB in, %.1f MB out; writer thread: staging + submit %.2f s, waiting for tickets %.2f s\n",
+                         gpu_deflater.n_tickets, gpu_deflater.n_blocks, gpu_deflater.n_in * 1e-6, gpu_deflater.n_out * 1e-6, gpu_deflater.us_submit * 1e-6,
+                         gpu_deflater.us_wait * 1e-6);
         if (opt.log_level >= 1)
             std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",

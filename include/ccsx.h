@@ -793,6 +793,48 @@ int         ccsx_inflate_wait(ccsx_inflater f, ccsx_ticket ticket);
 int         ccsx_inflate_blocks_host(const uint8_t *src, int64_t src_len, const ccsx_deflate_block *blocks, int32_t n_blocks,
                                      uint8_t *dst, int64_t dst_len, int32_t *status);
 
+/* ---- BGZF deflate on the device (the rule: DESIGN.md §2 "BGZF deflate", its own version ccsx_deflate_rule_version; nothing of the consensus changes).  The other
+ * half of the inflater: a span of at most CCSX_DEFLATE_MAX_IN plain bytes becomes one raw DEFLATE stream (RFC 1951, the payload of a BGZF block) and its CRC32
+ * (zlib polynomial, what the BGZF trailer holds): k_deflate encodes one span per workgroup.  The stream and the CRC are a pure function of the span's bytes and
+ * the rule version: the device and ccsx_deflate_spans_host give the same bytes.  A deflater is its own object: its own non-blocking stream, device buffers and
+ * page-locked staging; it shares nothing with a ccsx_handle or an inflater and may run beside them.  It is not thread-safe.  Two calls may be in flight
+ * (ccsx_deflate_submit / ccsx_deflate_wait); tickets complete in order.
+ *   spans[i]    in_off / in_len: the plain bytes in src, in_len <= CCSX_DEFLATE_MAX_IN; out_off / out_cap: where the stream goes in dst and how long it may be.
+ *               ccsx_deflate_bound(in_len) is an out_cap that is never too small: the length of the stored form.
+ *   out_len[i]  the stream's bytes; crc[i] the CRC32 of the span's plain bytes (set whatever the status).
+ *   status[i]   enum ccsx_deflate_status.  A span whose stream does not fit its out_cap is OUTPUT_FULL, never an error of the call: its out_len is 0 and the bytes
+ *               of its output range are unspecified.  No byte of dst outside the spans' output ranges is written.
+ * Argument errors (< 0, ccsx_last_error) fail the call before anything is enqueued: a null argument, a span outside src or dst, overlapping output ranges,
+ * in_len > CCSX_DEFLATE_MAX_IN, src_len / dst_len / n_spans beyond the deflater's capacities, two tickets already in flight.
+ * src, spans, dst, out_len, crc and status must stay valid until the ticket is waited for.
+ * ccsx_deflate_spans_host runs the same encoder (deflate_core.h) on the calling thread, without a device: the reference of the tests.  ccsx_deflate_crc is the
+ * rule's CRC alone, on the host, for any length.                                                                                                              */
+#define CCSX_DEFLATE_MAX_IN 65536
+#ifndef CCSX_DEFLATE_STATUS_DEFINED
+#define CCSX_DEFLATE_STATUS_DEFINED
+enum ccsx_deflate_status {
+    CCSX_DEFLATE_OK          = 0,
+    CCSX_DEFLATE_OUTPUT_FULL = 1   /* the stream (coded or stored, whichever the rule picks) is longer than out_cap */
+};
+#endif
+typedef struct ccsx_deflater_s *ccsx_deflater;
+typedef struct ccsx_deflate_span { int64_t in_off; int32_t in_len; int32_t out_cap; int64_t out_off; } ccsx_deflate_span;
+int         ccsx_deflate_rule_version(void);
+int32_t     ccsx_deflate_bound(int32_t in_len);
+int         ccsx_deflater_create(int device, int64_t max_in_bytes, int64_t max_out_bytes, int32_t max_spans, ccsx_deflater *out);
+int         ccsx_deflater_destroy(ccsx_deflater f);
+int         ccsx_deflate_spans(ccsx_deflater f, const uint8_t *src, int64_t src_len, const ccsx_deflate_span *spans, int32_t n_spans,
+                               uint8_t *dst, int64_t dst_len, int32_t *out_len, uint32_t *crc, int32_t *status);   /* synchronous: submit + wait */
+int         ccsx_deflate_submit(ccsx_deflater f, const uint8_t *src, int64_t src_len, const ccsx_deflate_span *spans, int32_t n_spans,
+                                uint8_t *dst, int64_t dst_len, int32_t *out_len, uint32_t *crc, int32_t *status, ccsx_ticket *ticket);
+int         ccsx_deflate_wait(ccsx_deflater f, ccsx_ticket ticket);
+int         ccsx_deflate_spans_host(const uint8_t *src, int64_t src_len, const ccsx_deflate_span *spans, int32_t n_spans,
+                                    uint8_t *dst, int64_t dst_len, int32_t *out_len, uint32_t *crc, int32_t *status);
+uint32_t    ccsx_deflate_crc(const uint8_t *p, int64_t n);
+int         ccsx_deflate_code_lengths(const uint32_t *freq, int32_t n, int32_t max_bits, uint8_t *lens);   /* the rule's code construction alone, host: the lengths
+                                              (<= max_bits, 1 .. 15) of the 2 <= n <= 286 symbols with these counts, as one sub-block would get them; for the tests */
+int32_t     ccsx_deflate_fill_spans(int device);      /* spans of one call that fill the device: its CUs x the workgroups of k_deflate a CU holds (1); < 0 on error */
+
 /* ---- model training: Baum-Welch counts on the device, the M-step on the host (the rule: DESIGN.md §2 "Model training", its own version ccsx_train_rule_version;
  * no result of the consensus changes).  A pair is (window of a ZMW, pass): the window k_polish would cut on the caller's draft, the pass's segment between the
  * window's two entry rows.  Per pair the FULL forward and backward matrices are filled (no band), the pair is gated (alpha / beta agreement, opts.min_zscore), and
