@@ -681,6 +681,104 @@ class OrientReport:
                              _ptr(self.votes_opp, C.c_int32))
 
 
+# ---- barcode calls (include/ccsx.h ccsx_barcode_*; DESIGN.md §2 "Barcode calls")
+BARCODE_MAX, BARCODE_MIN_LEN, BARCODE_MAX_LEN, BARCODE_MAX_WINDOW = 384, 8, 64, 1024
+BARCODE_HEAD, BARCODE_TAIL = 1, 2                # the bits of BarcodeReport.call
+
+
+class BarcodeOpts(C.Structure):
+    _fields_ = [("window", C.c_int32), ("max_dist_pct", C.c_int32), ("min_margin", C.c_int32)]
+
+
+class BarcodeSet(C.Structure):
+    """ccsx_barcode_set: up to 384 barcodes of 8 .. 64 codes 0 .. 3.  The barcode at a read's tail is looked for on the reverse complement of the read"""
+    _fields_ = [("n_barcodes", C.c_int32), ("len", C.c_int32 * BARCODE_MAX), ("seq", (C.c_uint8 * BARCODE_MAX_LEN) * BARCODE_MAX)]
+
+    @staticmethod
+    def from_strings(seqs) -> "BarcodeSet":
+        """from ACGT strings (either case) or arrays of codes; lengths, codes and the count are checked by the call that takes the set"""
+        seqs = list(seqs)
+        if len(seqs) > BARCODE_MAX:
+            raise ValueError(f"at most {BARCODE_MAX} barcodes")
+        s = BarcodeSet()
+        s.n_barcodes = len(seqs)
+        flat = np.frombuffer(s, np.uint8, BARCODE_MAX * BARCODE_MAX_LEN, BarcodeSet.seq.offset).reshape(BARCODE_MAX, BARCODE_MAX_LEN)
+        for b, q in enumerate(seqs):
+            codes = ["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q]
+            if len(codes) > BARCODE_MAX_LEN:
+                raise ValueError(f"barcode {b}: more than {BARCODE_MAX_LEN} bases")
+            s.len[b] = len(codes)
+            flat[b, : len(codes)] = codes
+        return s
+
+    from_codes = from_strings
+
+    def codes(self) -> list:
+        return [np.array(self.seq[b][: self.len[b]], np.uint8) for b in range(self.n_barcodes)]
+
+
+class CBarcodeReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in ("tested", "call", "bq", "idx", "dist", "second", "clip")]
+
+
+class CBarcodeRequest(C.Structure):
+    """ccsx_barcode_request: barcode calls in the fused path (ccsx_consensus_barcodes / ccsx_submit_barcodes)"""
+    _fields_ = [("opts", C.POINTER(BarcodeOpts)), ("set", C.POINTER(BarcodeSet)), ("report", C.POINTER(CBarcodeReport)), ("reserved", C.c_int32 * 2)]
+
+
+def barcode_opts_default() -> BarcodeOpts:
+    o = BarcodeOpts()
+    lib().ccsx_barcode_opts_default(C.byref(o))
+    return o
+
+
+class BarcodeReport(_PlaneReport):
+    """ccsx_barcode_report: per read tested (0 / 1), call (BARCODE_HEAD | BARCODE_TAIL) and bq, and per end [n, 2] the best barcode, its distance, the runner-up's
+    distance and the clip"""
+    FIELDS = ("tested", "call", "bq", "idx", "dist", "second", "clip")
+    PLANES = _int_planes("tested", "call", "bq") + tuple((k, np.int32, (2,)) for k in ("idx", "dist", "second", "clip"))
+    CSTRUCT = CBarcodeReport
+
+    def c_struct(self) -> CBarcodeReport:
+        r = CBarcodeReport()
+        r.n_zmw = len(self.tested)
+        for k in self.FIELDS:
+            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
+        return r
+
+    def fields(self, z: int) -> dict:
+        return {k: getattr(self, k)[z].tolist() for k in self.FIELDS}
+
+
+def _barcode_request(bset: BarcodeSet, opts: "BarcodeOpts | None", crep: CBarcodeReport):
+    o = opts if opts is not None else barcode_opts_default()
+    return CBarcodeRequest(C.pointer(o), C.pointer(bset), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (bset, o, crep)
+
+
+def _barcode_reads_args(bset: BarcodeSet, opts: "BarcodeOpts | None", reads, report: "BarcodeReport | None"):
+    """the arguments of ccsx_barcode_reads[_host] for a list of code arrays: (args, report, keep)"""
+    reads = [np.ascontiguousarray(r, np.uint8) for r in reads]
+    n = len(reads)
+    seq_len = np.array([len(r) for r in reads], np.int32).reshape(n)
+    seq_off = np.zeros(n, np.int64)
+    if n:
+        seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64)
+    seq = np.concatenate(reads + [np.zeros(1, np.uint8)])
+    rep = report if report is not None else BarcodeReport.allocate(n)
+    crep = rep.c_struct()
+    o = opts if opts is not None else barcode_opts_default()
+    keep = (bset, o, seq, seq_off, seq_len, crep, rep)
+    return (C.byref(bset), C.byref(o), _ptr(seq, C.c_uint8), _ptr(seq_off, C.c_int64), _ptr(seq_len, C.c_int32), n, C.byref(crep)), rep, keep
+
+
+def barcode_reads_host(bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = None, report: "BarcodeReport | None" = None) -> BarcodeReport:
+    """ccsx_barcode_reads_host: the barcode rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
+    args, rep, _keep = _barcode_reads_args(bset, opts, reads, report)
+    if lib().ccsx_barcode_reads_host(*args) != 0:
+        raise RuntimeError("ccsx_barcode_reads_host failed: " + lib().ccsx_last_error().decode())
+    return rep
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -956,6 +1054,7 @@ EXPORTS = [
     "ccsx_deflate_wait", "ccsx_deflate_spans_host", "ccsx_deflate_crc", "ccsx_deflate_fill_spans", "ccsx_deflate_code_lengths",
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
     "ccsx_fit_opts_default", "ccsx_fitter_create", "ccsx_fitter_add", "ccsx_fitter_finish", "ccsx_fitter_destroy",
+    "ccsx_barcode_opts_default", "ccsx_barcode_rule_version", "ccsx_barcode_reads_host", "ccsx_barcode_reads", "ccsx_consensus_barcodes", "ccsx_submit_barcodes",
 ]
 
 _lib = None
@@ -1091,6 +1190,13 @@ def lib() -> C.CDLL:
         L.ccsx_fitter_add.argtypes = [C.c_void_p, C.POINTER(CTrainCounts), C.POINTER(C.c_float)]
         L.ccsx_fitter_finish.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(FitReport)]
         L.ccsx_fitter_destroy.argtypes = [C.c_void_p]
+        L.ccsx_barcode_opts_default.restype = None
+        L.ccsx_barcode_opts_default.argtypes = [C.POINTER(BarcodeOpts)]
+        _bcreads = [C.POINTER(BarcodeSet), C.POINTER(BarcodeOpts), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(CBarcodeReport)]
+        L.ccsx_barcode_reads_host.argtypes = _bcreads
+        L.ccsx_barcode_reads.argtypes = [C.c_void_p] + _bcreads
+        L.ccsx_consensus_barcodes.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CBarcodeRequest)]
+        L.ccsx_submit_barcodes.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CBarcodeRequest), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -1500,11 +1606,12 @@ class Handle:
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
 
-    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None):
+    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
         ccsx_*_hd with a heteroduplex request, which combines with none of the screens, ccsx_*_requests when _requests made a CRequests (a coverage request,
         or via_requests), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
-        structs join the requests' keep list.  Returns the C structs"""
+        structs join the requests' keep list.  barcodes: (report, set, opts), through ccsx_*_barcodes in the same way (not together with a hand-off).  Returns
+        the C structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
@@ -1515,6 +1622,15 @@ class Handle:
             hreq = _handoff_request(handoff)
             name, args = f"ccsx_{form}_handoff", (_keep[-1], hreq[0])
             _keep.append(hreq)
+        if barcodes is not None:
+            if handoff is not None or name != f"ccsx_{form}_requests":
+                raise ValueError("the barcode request goes with the members of ccsx_requests (not with the hand-off or the heteroduplex request)")
+            brep, bset, bopts = barcodes
+            if bset is None:
+                raise ValueError("barcodes: a barcode_set is needed")
+            breq = _barcode_request(bset, bopts, brep.c_struct())
+            name, args = f"ccsx_{form}_barcodes", (_keep[-1], breq[0])
+            _keep.append((breq, brep))
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
         if form == "consensus":
@@ -1672,6 +1788,24 @@ class Handle:
         self._fused("consensus", batch, res, _requests(via_requests=True, **requests), handoff=ho)
         return res, ho
 
+    # ---- barcode calls (ccsx_consensus_barcodes / ccsx_barcode_reads): the barcodes at both ends of the final reads
+    def consensus_barcodes(self, batch: Batch, bset: BarcodeSet, opts: "BarcodeOpts | None" = None, res: "Results | None" = None,
+                           **requests) -> tuple["Results", BarcodeReport]:
+        """(results, barcode report).  bset: the BarcodeSet; opts: the BarcodeOpts (None: the defaults); res: the caller's Results.  requests: Handle.submit's
+        keyword arguments for the other requests of the same run (pileup=, tandem=, fold=, adapters=, control=, coverage= ... with their reports; not hd=,
+        not handoff=)"""
+        if res is None:
+            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = BarcodeReport.allocate(batch.n_zmw)
+        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), barcodes=(rep, bset, opts))
+        return res, rep
+
+    def barcode_reads(self, bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = None, report: "BarcodeReport | None" = None) -> BarcodeReport:
+        """ccsx_barcode_reads: k_barcode on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
+        args, rep, _keep = _barcode_reads_args(bset, opts, reads, report)
+        self._check(self._L.ccsx_barcode_reads(self._h, *args), "ccsx_barcode_reads")
+        return rep
+
     # ---- the polisher hand-back (ccsx_refine_batch): refined tiles spliced into the base consensus on the GPU, QVs from one more Arrow round
     @staticmethod
     def _refine_args(batch: Batch, base: "Results", tiles: "RefineTiles", backbone, res: "Results", report: "RefineReport"):
@@ -1740,7 +1874,8 @@ class Handle:
                fold: "FoldReport | None" = None, fold_opts: FoldOpts | None = None, adapters: "AdapterReport | None" = None,
                adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, control: "ControlReport | None" = None,
                control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None, coverage: "CoverageReport | None" = None,
-               coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, handoff: "Handoff | None" = None) -> int:
+               coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, handoff: "Handoff | None" = None,
+               barcodes: "BarcodeReport | None" = None, barcode_set: "BarcodeSet | None" = None, barcode_opts: "BarcodeOpts | None" = None) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
         receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd).  fold: a report
@@ -1751,7 +1886,8 @@ class Handle:
         report (CoverageReport.allocate(n, pinned=True)) that receives the coverage screen under coverage_opts and coverage_gate (ccsx_submit_requests; with or
         without the other screens, not with hd); every ticket carries its own options and gate.  handoff: a Handoff (Handoff.allocate(batch, max_tiles, opts,
         pinned=True) or device=) that receives the polisher hand-off (ccsx_submit_handoff; not with hd): the whole capacity of its arrays is copied, complete
-        when the ticket is; every ticket carries its own options and capacity"""
+        when the ticket is; every ticket carries its own options and capacity.  barcodes: a report (BarcodeReport.allocate(n, pinned=True)) that receives the
+        barcode calls for barcode_set under barcode_opts (ccsx_submit_barcodes; not with hd or handoff); every ticket carries its own set and options"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
@@ -1766,10 +1902,14 @@ class Handle:
             raise ValueError("the heteroduplex request and the coverage screen are not combined")
         if handoff is not None and hd is not None:
             raise ValueError("the heteroduplex request and the hand-off are not combined")
+        if barcodes is not None and (hd is not None or handoff is not None):
+            raise ValueError("the barcode request is not combined with the heteroduplex request or the hand-off")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
-                             control, control_seq, control_opts, coverage, coverage_opts, coverage_gate, via_requests=handoff is not None)
+                             control, control_seq, control_opts, coverage, coverage_opts, coverage_gate,
+                             via_requests=handoff is not None or barcodes is not None)
         t = C.c_int64()
-        cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff)
+        cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff,
+                             barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
         self._inflight[t.value] = (batch, res, cb, cr, requests, handoff)  # the C structs and arrays must outlive the ticket

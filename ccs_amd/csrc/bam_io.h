@@ -763,6 +763,11 @@ struct RecordBuilder {
         b.push_back(t[0]); b.push_back(t[1]); b.push_back('B'); b.push_back('C'); u32(n);
         b.insert(b.end(), v, v + n);
     }
+    void tagBS(const char *t, const uint16_t *v, uint32_t n)
+    {
+        b.push_back(t[0]); b.push_back(t[1]); b.push_back('B'); b.push_back('S'); u32(n);
+        for (uint32_t i = 0; i < n; ++i) { b.push_back((uint8_t)(v[i] & 0xff)); b.push_back((uint8_t)(v[i] >> 8)); }
+    }
     void tagBI(const char *t, const uint32_t *v, uint32_t n)
     {
         b.push_back(t[0]); b.push_back(t[1]); b.push_back('B'); b.push_back('I'); u32(n);

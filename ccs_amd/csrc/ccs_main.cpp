@@ -87,6 +87,12 @@ struct Options {
     bool coverage_filters = false;   // --coverage-filters: the coverage screen with all four gate bits (DESIGN.md §2 "Coverage rule"; off here)
     int cov_drop_percent = -1, cov_block = -1;   // --coverage-drop-percent / --coverage-block: overrides of ccsx_coverage_opts (-1: the default)
     ccsx_coverage_opts coverage_opts{};          // ... the options every ticket carries
+    std::string barcodes;         // --barcodes FILE.fasta: call the barcodes of the set at both ends of every HiFi read (DESIGN.md §2 "Barcode calls"): tags bc, bq
+    int barcode_window = -1;      // --barcode-window N: bases of either end that are searched (-1: the default)
+    std::string barcode_counts;   // --barcode-counts FILE.tsv: reads per called pair
+    std::shared_ptr<ccsx_barcode_set> barcode_set;   // ... the set it names, the record names, the options every ticket carries
+    std::vector<std::string> barcode_names;
+    ccsx_barcode_opts barcode_opts{};
     std::string fit_model;        // --fit-model OUT.json: the training mode (DESIGN.md §2 "Model training"): no consensus output
     int fit_iterations = 3;       // --fit-iterations: EM iterations over the file
     double fit_min_rq = 0.999;    // --fit-min-rq: a polished consensus is a truth to measure passes against from this predicted accuracy on
@@ -161,6 +167,7 @@ struct Batch {
     ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_adapter_request: the report's arrays are in out_arena)
     ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_control_request: the report's arrays are in out_arena)
     ccsx_coverage_report vrep{}; ccsx_coverage_request vreq{}; // --coverage-filters (ccsx_coverage_request: the report's arrays are in out_arena)
+    ccsx_barcode_report brep{}; ccsx_barcode_request breq{};   // --barcodes (ccsx_barcode_request: the report's arrays are in out_arena)
     ccsx_requests reqs{};           // (read during the call only)
 };
 
@@ -235,6 +242,11 @@ void usage()
                  "      --control F.fasta     screen every draft for the spike-in control of FASTA file F (one record of 64-4096 bases); control ZMWs leave\n"
                  "                            the main output and are counted as 'ZMW with control success / failure'; with --fail-reads those with a\n"
                  "                            consensus are written to F.bam with ff 0x2 [off: there is no built-in control]\n"
+                 "      --barcodes F.fasta    call the barcodes of FASTA file F (1-384 records of 8-64 bases) at both ends of every HiFi read, on the GPU: a read\n"
+                 "                            with a barcode called at both ends gets the tags bc:B:S (the two record indices, head and tail; the tail's barcode\n"
+                 "                            as it reads on the opposite strand) and bq:i; nothing is clipped; the reports gain a barcode block [off]\n"
+                 "      --barcode-window N    with --barcodes: bases of either end that are searched, 8-1024 [64]\n"
+                 "      --barcode-counts F.tsv  with --barcodes: one line per called pair of barcodes (the two record names, the reads), sorted by index pair\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -304,6 +316,42 @@ bool load_adapters(const std::string &path, ccsx_adapter_set &set, std::string &
     set.n_adapters = (int32_t)names.size();
     for (size_t k = 0; k < names.size(); ++k)
         if (set.len[k] < CCSX_ADAPTER_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 16"; return false; }
+    return true;
+}
+
+// --barcodes: a FASTA of 1 .. 384 records of 8 .. 64 bases, ACGT in either case.  false + a message that names the record, as load_adapters
+bool load_barcodes(const std::string &path, ccsx_barcode_set &set, std::vector<std::string> &ids, std::string &err)
+{
+    std::ifstream f(path);
+    if (!f) { err = "cannot open the file"; return false; }
+    std::memset(&set, 0, sizeof set);
+    std::vector<std::string> names;
+    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + names[k] + ")"; };
+    std::string line;
+    while (std::getline(f, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            names.push_back(line.substr(0, 60));
+            if (names.size() > CCSX_BARCODE_MAX) { err = where(names.size() - 1) + ": more than 384 records"; return false; }
+            continue;
+        }
+        if (names.empty()) { err = "sequence before the first '>' line"; return false; }
+        const size_t a = names.size() - 1;
+        for (char c : line) {
+            const int u = std::toupper((unsigned char)c);
+            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
+            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
+            if (set.len[a] >= CCSX_BARCODE_MAX_LEN) { err = where(a) + ": more than 64 bases"; return false; }
+            set.seq[a][set.len[a]++] = (uint8_t)code;
+        }
+    }
+    if (names.empty()) { err = "no FASTA record"; return false; }
+    set.n_barcodes = (int32_t)names.size();
+    for (size_t k = 0; k < names.size(); ++k)
+        if (set.len[k] < CCSX_BARCODE_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 8"; return false; }
+    ids.clear();
+    for (const std::string &n : names) ids.push_back(n.substr(1, n.find_first_of(" \t", 1) == std::string::npos ? std::string::npos : n.find_first_of(" \t", 1) - 1));
     return true;
 }
 
@@ -384,6 +432,15 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--fail-reads") o.fail_reads = need(a.c_str());
         else if (a == "--adapters") o.adapters = need(a.c_str());
         else if (a == "--control") o.control = need(a.c_str());
+        else if (a == "--barcodes") o.barcodes = need(a.c_str());
+        else if (a == "--barcode-counts") o.barcode_counts = need(a.c_str());
+        else if (a == "--barcode-window") {
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < CCSX_BARCODE_MIN_LEN || n > CCSX_BARCODE_MAX_WINDOW) { std::fprintf(stderr, "ccs: --barcode-window needs a number in 8 .. 1024, got '%s'\n", v.c_str()); std::exit(2); }
+            o.barcode_window = (int)n;
+        }
         else if (a == "--coverage-filters") o.coverage_filters = true;
         else if (a == "--orient-passes") o.orient_passes = true;
         else if (a == "--coverage-drop-percent" || a == "--coverage-block") {
@@ -434,6 +491,7 @@ bool parse(int argc, char **argv, Options &o)
         if (o.pileup || o.qv_binning || o.o.hifi_kinetics || o.min_tandem > 0)
             refuse("writes no reads: --pileup-summary, --qv-binning, --hifi-kinetics and --min-tandem-repeat-length are not supported with it");
         if (o.chunk_n > 1) refuse("reads the whole file: --chunk is not supported with it");
+        if (!o.barcodes.empty()) refuse("writes no reads: --barcodes is not supported with it");
     }
     if (o.orient_passes && o.by_strand) {                    // the strands are split on the host, before the engine has seen a pass
         std::fprintf(stderr, "ccs: --orient-passes combined with --by-strand is not supported\n"); std::exit(2);
@@ -448,6 +506,17 @@ bool parse(int argc, char **argv, Options &o)
         if (o.fail_reads.empty()) { std::fprintf(stderr, "ccs: --adapters needs --fail-reads (the reads it flags are written there)\n"); std::exit(2); }
         std::string err;
         if (!load_adapters(o.adapters, o.adapter_set, err)) { std::fprintf(stderr, "ccs: --adapters %s: %s\n", o.adapters.c_str(), err.c_str()); std::exit(2); }
+    }
+    if (o.barcodes.empty() && (o.barcode_window >= 0 || !o.barcode_counts.empty())) {
+        std::fprintf(stderr, "ccs: --barcode-window and --barcode-counts need --barcodes\n"); std::exit(2);
+    }
+    if (!o.barcodes.empty()) {
+        if (o.by_strand) { std::fprintf(stderr, "ccs: --barcodes combined with --by-strand is not supported\n"); std::exit(2); }
+        std::string err;
+        o.barcode_set = std::make_shared<ccsx_barcode_set>();
+        if (!load_barcodes(o.barcodes, *o.barcode_set, o.barcode_names, err)) { std::fprintf(stderr, "ccs: --barcodes %s: %s\n", o.barcodes.c_str(), err.c_str()); std::exit(2); }
+        ccsx_barcode_opts_default(&o.barcode_opts);
+        if (o.barcode_window >= 0) o.barcode_opts.window = o.barcode_window;
     }
     if (!o.control.empty()) {
         std::string err;
@@ -706,6 +775,8 @@ struct Report {
     int64_t fail_records = 0;     // records written to --fail-reads
     int64_t control = 0;          // ZMWs the control screen found (--control), whatever their final status
     int64_t coverage = 0;         // ZMWs the coverage screen's gate took (--coverage-filters)
+    int64_t bc_tested = 0, bc_call[4] = {0, 0, 0, 0};           // --barcodes: HiFi reads tested, and by call: none, head only, tail only, both ends
+    std::map<std::pair<int, int>, int64_t> bc_pairs;              // ... reads per called pair (head, tail)
 };
 
 // cov: --coverage-filters.  Under it "Reads failed polishing" counts what the reference counts there, the reads lost while polishing; the engine's "more than
@@ -835,6 +906,14 @@ void write_report(const Options &o, const Report &r)
         std::fprintf(f, "ZMWs fail filters             : %" PRId64 " (%.2f%%)\n", failed, pct(failed, r.input));
         std::fprintf(f, "ZMWs shortcut filters         : 0 (0.00%%)\n\n");
         if (o.min_tandem > 0) std::fprintf(f, "ZMWs with tandem repeats      : %" PRId64 " (%.2f%%)\n\n", r.tandem, pct(r.tandem, r.input));
+        if (!o.barcodes.empty()) {                               // over the HiFi reads of the main output (DESIGN.md §2 "Barcode calls")
+            std::fprintf(f, "Barcode calls\n");
+            std::fprintf(f, "%-30s: %" PRId64 "\n", "HiFi reads tested", r.bc_tested);
+            static const char *const rows[4] = {"Barcodes at both ends", "Barcode at the head only", "Barcode at the tail only", "No barcode"};
+            static const int which[4] = {3, 1, 2, 0};
+            for (int k = 0; k < 4; ++k) std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", rows[k], r.bc_call[which[k]], pct(r.bc_call[which[k]], r.bc_tested));
+            std::fprintf(f, "\n");
+        }
         std::fprintf(f, "Exclusive failed counts\n");
         for (const char *k : fail_order(o)) {
             auto it = r.fail.find(k);
@@ -875,6 +954,9 @@ void write_report_json(const Options &o, const Report &r)
     std::fprintf(f, "{\n  \"zmws_input\": %" PRId64 ",\n  \"zmws_pass_filters\": %" PRId64 ",\n  \"zmws_fail_filters\": %" PRId64 ",\n  \"zmws_shortcut_filters\": 0,\n",
                  r.input, r.pass, r.input - r.pass);
     if (o.min_tandem > 0) std::fprintf(f, "  \"zmws_with_tandem_repeats\": %" PRId64 ",\n", r.tandem);
+    if (!o.barcodes.empty())
+        std::fprintf(f, "  \"barcode_calls\": {\"tested\": %" PRId64 ", \"both_ends\": %" PRId64 ", \"head_only\": %" PRId64 ", \"tail_only\": %" PRId64 ", \"none\": %" PRId64 "},\n",
+                     r.bc_tested, r.bc_call[3], r.bc_call[1], r.bc_call[2], r.bc_call[0]);
     std::fprintf(f, "  \"exclusive_failed_counts\": {");
     bool first = true;
     for (const char *k : fail_order(o)) {
@@ -883,6 +965,16 @@ void write_report_json(const Options &o, const Report &r)
         first = false;
     }
     std::fprintf(f, "\n  }\n}\n");
+    std::fclose(f);
+}
+
+// --barcode-counts: one line per called pair of barcodes, in increasing (head index, tail index): the two record names and the HiFi reads
+void write_barcode_counts(const Options &o, const Report &r)
+{
+    FILE *f = std::fopen(o.barcode_counts.c_str(), "w");
+    if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", o.barcode_counts.c_str()); return; }
+    for (const auto &kv : r.bc_pairs)
+        std::fprintf(f, "%s\t%s\t%" PRId64 "\n", o.barcode_names[kv.first.first].c_str(), o.barcode_names[kv.first.second].c_str(), kv.second);
     std::fclose(f);
 }
 
@@ -1382,6 +1474,7 @@ int main(int argc, char **argv)
         const bool screen = !opt.adapters.empty();                  // (needs fail_reads)
         const bool control = !opt.control.empty();
         const bool coverage = opt.coverage_filters;
+        const bool barcodes = !opt.barcodes.empty();
         std::vector<std::thread> packers;
         const size_t n_packers = std::max<size_t>(1, handles.size()) * (size_t)opt.workers_per_gpu;
         std::vector<std::atomic<int>> packers_left(ndev_q);
@@ -1408,7 +1501,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
@@ -1451,6 +1544,13 @@ int main(int argc, char **argv)
                             const auto v = planes(10);
                             b->vrep = ccsx_coverage_report{n, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]};
                             b->vreq = ccsx_coverage_request{&opt.coverage_opts, &b->vrep, 0x3cu, {0, 0}};   // all four gate bits
+                        }
+                        if (barcodes) {                          // tested, call, bq: n each; idx, dist, second, clip: [n][2]
+                            const auto b3 = planes(3);
+                            int32_t *two[4];
+                            for (auto &q : two) q = (int32_t *)take(2 * n4);
+                            b->brep = ccsx_barcode_report{n, b3[0], b3[1], b3[2], two[0], two[1], two[2], two[3]};
+                            b->breq = ccsx_barcode_request{&opt.barcode_opts, opt.barcode_set.get(), &b->brep, {0, 0}};
                         }
                         b->reqs = ccsx_requests{(opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr,
                                               control ? &b->creq : nullptr, coverage ? &b->vreq : nullptr, {nullptr, nullptr, nullptr}};
@@ -1553,7 +1653,7 @@ int main(int argc, char **argv)
                 t0 = now();
                 ccsx_ticket t = -1;
                 // the most general submit: NULL for the extras and for every request this run did not ask for (the narrower entry points stage the same)
-                if (ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
+                if (barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1720,6 +1820,11 @@ int main(int argc, char **argv)
                     // are present): only reads with rq >= 0.99 count, and the percentage is taken over their bases
                     if (bt.rq[s] >= 0.99f) for (int32_t q = 0; q < len; ++q) rep.bases_q30 += bt.qual[o + q] >= 30 ? 1 : 0;
                     const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
+                    const bool bc_both = barcodes && bt.brep.tested[s] && bt.brep.call[s] == 3;   // --barcodes: counted over the HiFi reads, tagged at both ends called
+                    if (barcodes && bt.brep.tested[s]) {
+                        ++rep.bc_tested; ++rep.bc_call[bt.brep.call[s] & 3];
+                        if (bc_both) ++rep.bc_pairs[{bt.brep.idx[2 * s], bt.brep.idx[2 * s + 1]}];
+                    }
                     if (fastq) {
                         fq.clear(); fq += '@'; fq += qname; fq += '\n';
                         for (int32_t q = 0; q < len; ++q) fq += "ACGT"[bt.seq[o + q] & 3];
@@ -1731,6 +1836,11 @@ int main(int argc, char **argv)
                         continue;
                     }
                     build(z, bt, s);
+                    if (bc_both) {
+                        const uint16_t pair[2] = {(uint16_t)bt.brep.idx[2 * s], (uint16_t)bt.brep.idx[2 * s + 1]};
+                        rb.tagBS("bc", pair, 2);
+                        rb.tagi("bq", bt.brep.bq[s]);
+                    }
                     marks.push_back(outp->mark());
                     pbi.rg_id.push_back(0); pbi.q_start.push_back(0); pbi.q_end.push_back(len); pbi.hole.push_back(z.zm);
                     pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
@@ -1785,6 +1895,7 @@ int main(int argc, char **argv)
         for (ccsx_handle h : handles) ccsx_destroy(h);
         if (!opt.suppress_reports || opt.report_named) write_report(opt, rep);
         if (!opt.report_json.empty()) write_report_json(opt, rep);            // named files are written even under --suppress-reports (docs/faq/sqiie.md:36-46
+        if (!opt.barcode_counts.empty()) write_barcode_counts(opt, rep);
         if (!opt.hifi_summary.empty()) write_hifi_summary(opt, rep);          //  combines --suppress-reports with explicit report names)
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         if (opt.log_level >= 2)

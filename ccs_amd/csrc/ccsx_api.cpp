@@ -140,12 +140,14 @@ struct Slot {
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
     DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
+    DevBuf d_bc;                                  // barcode calls only (ccsx_barcode_request): the set's masks and lengths, then the [11][n] report
     DevBuf d_rf_tiles, d_rf_base, d_rf_rep;       // polisher hand-back only (ccsx_submit_refine): the tile list and its classes; base lengths, backbones, seq, qual; the report
     RefineParams RP{};                            // ... its kernels' parameters as enqueued (the report's download reads them)
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
     PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
+    PinVec<unsigned long long> bc_set;            // barcode calls only: the masks and lengths as uploaded (a ticket's set is its own, as its control is)
     PinVec<int32_t> anchor;                       // pass orientation only: the anchor pass of every ZMW as uploaded
     bool orient_pending = false, orient_ran = false;   // the staged batch carries the bit and k_orient has yet to run on it / has run (its report is on the device)
     KParams P;
@@ -197,6 +199,7 @@ struct ccsx_handle_s {
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
+    DevBuf d_bc_reads;                // ccsx_barcode_reads only: the call's set, reads and report (no slot is touched)
     DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
     ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
     Slot slot[CCSX_SLOTS];
@@ -386,6 +389,7 @@ struct Wants {
     const ccsx_coverage_request *coverage = nullptr; ccsx_coverage_opts coverage_opts{};
     const ccsx_orient_opts *orient = nullptr;   // ccsx_orient_batch's own options (NULL: the handle's, ccsx_set_orient_opts); already checked
     const ccsx_handoff_request *handoff = nullptr; ccsx_handoff_opts handoff_opts{}; ccsx_handoff_out handoff_out{};   // (the out struct is copied: it is read during the call only)
+    const ccsx_barcode_request *barcodes = nullptr; ccsx_barcode_opts barcode_opts{}; std::vector<unsigned long long> barcode_set; int barcode_n = 0;   // (the set packed: barcode_words)
     bool handoff_written_only = false;          // the synchronous form: counts is known when the copies are enqueued, only the written slots are copied
 };
 
@@ -1183,6 +1187,63 @@ static int enqueue_handoff_download(const Slot &S, const ccsx_handoff_out &out, 
     return 0;
 }
 
+// ---- the barcode calls' host side (DESIGN.md §2 "Barcode calls"; the checks and the packing: ccsx_barcode_api.cpp).  A packed set is its masks, [n_barcodes][4]
+// words, then its lengths, one byte each, in whole words: what the slot uploads in one copy
+static size_t barcode_words(int nb) { return (size_t)nb * 4 + ((size_t)nb + 7) / 8; }
+static void barcode_pack(const ccsx_barcode_set *set, std::vector<unsigned long long> *packed)
+{
+    packed->assign(barcode_words(set->n_barcodes), 0ull);
+    ccsx_barcode_pack(set, packed->data(), reinterpret_cast<uint8_t *>(packed->data() + (size_t)set->n_barcodes * 4));
+}
+
+static int barcode_request_check(const ccsx_barcode_request *q, const ccsx_batch *b, std::vector<unsigned long long> *packed, ccsx_barcode_opts *o, const char *fn)
+{
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": barcode request: reserved must be 0"); return -1; }
+    if (ccsx_barcode_check(q->set, q->opts, q->report, b->n_zmw, fn, o)) return -1;
+    barcode_pack(q->set, packed);
+    return 0;
+}
+
+// k_barcode's parameters for a packed set at `dev` (the report's planes follow it) and the reads it is given
+static BarcodeParams barcode_params(void *dev, size_t words, int nb, int n, const ccsx_barcode_opts &o, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len)
+{
+    BarcodeParams B{};
+    B.n = n; B.n_barcodes = nb; B.opts = o; B.seq = seq; B.seq_off = seq_off; B.seq_len = seq_len;
+    B.masks = (const unsigned long long *)dev; B.len = (const uint8_t *)(B.masks + (size_t)nb * 4); B.rep = (int32_t *)(B.masks + words);
+    return B;
+}
+
+// The set is the slot's own, in page-locked memory that lives as long as the slot (as the control's index): its copy is enqueued on `st` with the slot's other
+// uploads.  k_barcode reads the results where k_stitch leaves them.
+static int barcode_attach(Slot &S, const std::vector<unsigned long long> &packed, int nb, const ccsx_barcode_opts &o, hipStream_t st)
+{
+    KParams &P = S.P;
+    const size_t n = (size_t)P.n_zmw, words = packed.size();
+    if (S.d_bc.reserve(words * 8 + n * CCSX_BC_PLANES * 4) || S.bc_set.resize(words)) return -2;
+    std::copy(packed.begin(), packed.end(), S.bc_set.p);
+    P.bc = barcode_params(S.d_bc.p, words, nb, (int)n, o, P.out_seq, P.seq_off, P.out_len);
+    if (hipError_t e = hipMemcpyAsync(S.d_bc.p, S.bc_set.p, words * 8, hipMemcpyHostToDevice, st)) {
+        ccsx_set_error(std::string("barcode calls: set upload: ") + hipGetErrorString(e)); return -2;
+    }
+    return 0;
+}
+
+// the report's planes into the caller's arrays, on `s`
+static int enqueue_barcode_download(const BarcodeParams &B, const ccsx_barcode_report *r, hipStream_t s)
+{
+    const size_t n = (size_t)B.n;
+    if (!n) return 0;
+    const BarcodeOut d = ccsx_bc_out(B.rep, n);
+    HIPTRY(hipMemcpyAsync(r->tested, d.tested, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->call, d.call, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->bq, d.bq, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->idx, d.idx, n * 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->dist, d.dist, n * 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->second, d.second, n * 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->clip, d.clip, n * 8, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
@@ -1200,9 +1261,12 @@ static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string
 // against, and that check refuses the call).
 static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                        const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr,
-                       const ccsx_handoff_request *handoff = nullptr)
+                       const ccsx_handoff_request *handoff = nullptr, const ccsx_barcode_request *barcodes = nullptr)
 {
     *W = Wants{};
+    if (barcodes && handoff) return refuse(fn, "the barcode request and the hand-off are not combined");
+    if (barcodes && hd) return refuse(fn, "the barcode and the heteroduplex requests are not combined");
+    if (barcodes && b && barcode_request_check(barcodes, b, &W->barcode_set, &W->barcode_opts, fn)) return -1;
     if (handoff && handoff_request_check(handoff, &W->handoff_opts, &W->handoff_out, fn)) return -1;
     if (coverage && hd) return refuse(fn, "the coverage and the heteroduplex requests are not combined");
     if (coverage && b && coverage_request_check(coverage, b, &W->coverage_opts, fn)) return -1;
@@ -1211,7 +1275,7 @@ static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const c
     if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
     if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
-    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = handoff;
+    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = handoff; W->barcodes = barcodes; W->barcode_n = barcodes && barcodes->set ? barcodes->set->n_barcodes : 0;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
@@ -1227,6 +1291,7 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.adapters && (rc = adapter_attach(h, S, W.adapter_set, W.adapter_opts))) return rc;
     if (W.coverage && (rc = coverage_attach(h, S, W.coverage_opts, W.coverage->gate))) return rc;
     if (W.handoff && (rc = handoff_attach(S, W.handoff_opts, W.handoff_out.max_tiles))) return rc;
+    if (W.barcodes && (rc = barcode_attach(S, W.barcode_set, W.barcode_n, W.barcode_opts, st))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
     return 0;
@@ -1260,6 +1325,7 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
                                   S.P.cov_zi, n, s))) return rc;
     }
     if (W.handoff && (rc = enqueue_handoff_download(S, W.handoff_out, W.handoff_written_only, s))) return rc;
+    if (W.barcodes && (rc = enqueue_barcode_download(S.P.bc, W.barcodes->report, s))) return rc;
     return 0;
 }
 
@@ -1477,12 +1543,13 @@ int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 // the members of a ccsx_requests as build_wants takes them (NULL: none); -1 for nonzero reserved words
-static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_handoff_request *handoff = nullptr)
+static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_handoff_request *handoff = nullptr,
+                          const ccsx_barcode_request *barcodes = nullptr)
 {
     static const ccsx_requests none = {};
     if (!rq) rq = &none;
     if (rq->reserved[0] || rq->reserved[1] || rq->reserved[2]) return refuse(fn, "ccsx_requests: reserved must be NULL");
-    return build_wants(rq->ex, nullptr, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff);
+    return build_wants(rq->ex, nullptr, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff, barcodes);
 }
 int ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket)
 {
@@ -1494,6 +1561,12 @@ int ccsx_submit_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
 {
     Wants W;
     if (requests_wants(rq, b, __func__, &W, ho) || (!ho && refuse(__func__, "null handoff request"))) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc, ccsx_ticket *ticket)
+{
+    Wants W;
+    if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
@@ -1766,6 +1839,51 @@ int ccsx_consensus_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res
     if (requests_wants(rq, b, __func__, &W, ho) || (!ho && refuse(__func__, "null handoff request"))) return -1;
     W.handoff_written_only = true;
     return consensus_sync(h, b, res, W, __func__);
+}
+
+int ccsx_consensus_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc)
+{
+    Wants W;
+    if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
+// k_barcode on the caller's reads: buffers of the handle's own on the polish stream, behind whatever tickets have enqueued there; no slot is staged, retired
+// or recycled.  Layout of the buffer: [set + report][seq_off: n x 8][seq_len: n x 4, padded][seq]
+static int barcode_reads_enqueue(ccsx_handle h, const std::vector<unsigned long long> &packed, int nb, const ccsx_barcode_opts &o, const uint8_t *seq,
+                                 const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes, const ccsx_barcode_report *report, hipStream_t st)
+{
+    const size_t words = packed.size(), head = words * 8 + (size_t)n * CCSX_BC_PLANES * 4, head8 = (head + 7) & ~(size_t)7, len4 = ((size_t)n * 4 + 7) & ~(size_t)7;
+    if (h->d_bc_reads.reserve(head8 + (size_t)n * 8 + len4 + (size_t)bytes)) return -2;
+    uint8_t *base = (uint8_t *)h->d_bc_reads.p;
+    int64_t *d_off = (int64_t *)(base + head8);
+    int32_t *d_len = (int32_t *)(base + head8 + (size_t)n * 8);
+    uint8_t *d_seq = base + head8 + (size_t)n * 8 + len4;
+    HIPTRY(hipMemcpyAsync(base, packed.data(), words * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (bytes) HIPTRY(hipMemcpyAsync(d_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
+    const BarcodeParams B = barcode_params(base, words, nb, n, o, d_seq, d_off, d_len);
+    (void)hipGetLastError();
+    if (const char *failed = ccsx_barcode_launch(B, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    return enqueue_barcode_download(B, report, st);
+}
+
+int ccsx_barcode_reads(ccsx_handle h, const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
+                       int32_t n, ccsx_barcode_report *report)
+{
+    ccsx_barcode_opts o;
+    int64_t bytes;
+    if (ccsx_barcode_check(set, opts, report, n, __func__, &o) || ccsx_barcode_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
+    if (!h) return refuse(__func__, "null argument");
+    if (n == 0) return 0;
+    std::vector<unsigned long long> packed;
+    barcode_pack(set, &packed);
+    HIPTRY(hipSetDevice(h->device));
+    const int rc = barcode_reads_enqueue(h, packed, set->n_barcodes, o, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
+    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
 }
 
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)

@@ -31,3 +31,12 @@ template <typename F> static inline void ccsx_for_each_zmw_caps(const ccsx_batch
         f(z, ccsx_caps_of(maxL));
     }
 }
+
+// ---- barcode calls (ccsx_barcode_api.cpp; DESIGN.md §2 "Barcode calls"): what every entry point shares.  A refusal sets the error under the exported function's
+// name `fn` and returns -1.
+// the set, the options (NULL: the defaults; the checked copy goes to *o) and a report for n reads
+int ccsx_barcode_check(const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const ccsx_barcode_report *report, int64_t n, const char *fn, ccsx_barcode_opts *o);
+// caller-supplied reads: *bytes = the bytes of seq the reads cover (the largest seq_off[z] + seq_len[z] over the reads with seq_len[z] > 0)
+int ccsx_barcode_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes);
+// k_barcode's view of a checked set: masks [n_barcodes][4], len [n_barcodes]
+void ccsx_barcode_pack(const ccsx_barcode_set *set, unsigned long long *masks, uint8_t *len);

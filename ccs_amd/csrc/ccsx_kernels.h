@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "ccsx.h"
+#include "barcode_core.h"
 
 // bytes of POA scratch per vertex (ccsx_kernels.hip poa_slot, all by topological position): the 32-row score column of far-read columns 128, five 16-byte
 // records (kinfo, column records x 2, overflow in-edges x 2), 16 move bytes (a nibble per band row), 3 words of consensus / band state, two flag bytes
@@ -173,6 +174,9 @@ struct KParams {
     int32_t *ho_hdr;           // [5][max_tiles] tile_zmw, tile_start, tile_len, tile_qsum, tile_rows
     uint8_t *ho_rows;          // [2][max_tiles][R] row_pass, row_strand
     uchar4 *ho_cells;          // [max_tiles][R][T]
+    // ---- barcode calls (ccsx_consensus_barcodes / ccsx_submit_barcodes; bc.rep NULL otherwise): DESIGN.md §2 "Barcode calls".  k_barcode's own parameters
+    // (ccsx_barcode.hip): it reads out_seq / out_len after k_stitch
+    BarcodeParams bc;
 };
 // first tile index of ZMW z whose outputs start at seq_off: consecutive ZMWs get disjoint ranges of at least ceil(capacity / T) tiles, with no table
 static inline __host__ __device__ int64_t ccsx_handoff_tile_off(int64_t seq_off, int z, int T) { return seq_off / T + z; }
@@ -271,6 +275,7 @@ struct ccsx_launch_queues {
     hipEvent_t *ev, *ev_aux;
 };
 const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode);   // NULL, or the name of the launch that failed
+const char *ccsx_barcode_launch(const BarcodeParams &B, hipStream_t st);                 // ccsx_barcode.hip: k_barcode, one workgroup per read; NULL, or what failed
 const char *ccsx_train_launch(const KParams &P, hipStream_t st, long long max_blocks);   // ccsx_train.hip: the count buffers zeroed + k_train; NULL, or what failed
 int ccsx_kernel_is_experiment();         // built with -DCCSX_EXPERIMENT (timing studies: wrong results)
 const char *ccsx_kernel_build_flags();   // "" for a product build; the experiment switches this translation unit was compiled with otherwise

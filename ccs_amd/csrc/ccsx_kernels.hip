@@ -4674,22 +4674,7 @@ __global__ __launch_bounds__(CCSX_ORIENT_THREADS) void k_orient(KParams P)
 // dist, length) goes to an LDS buffer; when the buffer overflows (a draft made of adapters) the pass is repeated for the hits that end at or before the 16th set
 // bit of a bitmap of the ends (at most 16 ends x 16 searches, so that pass cannot overflow).  The 16 smallest keys are selected by rank.  tests/adapter_ref.py
 // restates the rule.
-struct AdapterCol { unsigned long long Pv, Mv; int score; };
-
-__device__ __forceinline__ void adapter_step(AdapterCol &c, unsigned long long Eq, unsigned long long top, unsigned long long anchored)
-{
-    const unsigned long long Xv = Eq | c.Mv;
-    const unsigned long long Xh = (((Eq & c.Pv) + c.Pv) ^ c.Pv) | Eq;
-    unsigned long long Ph = c.Mv | ~(Xh | c.Pv);
-    unsigned long long Mh = c.Pv & Xh;
-    c.score += (Ph & top) ? 1 : 0;
-    c.score -= (Mh & top) ? 1 : 0;
-    Ph = (Ph << 1) | anchored;                                      // (anchored: row 0 of the table charges the start, its horizontal difference is +1)
-    Mh <<= 1;
-    c.Pv = Mh | ~(Xv | Ph);
-    c.Mv = Ph & Xv;
-}
-
+// (MyersCol / myers_step: barcode_core.h, shared with k_barcode)
 __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
 {
     constexpr int NT = CCSX_ADAPTER_THREADS, CH = CCSX_ADAPTER_CHUNK, CAP = CCSX_ADAPTER_BUF, MAXS = 2 * CCSX_ADAPTER_MAX_PATTERNS, NH = CCSX_ADAPTER_MAX_HITS;
@@ -4738,19 +4723,19 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
             const int m = sM[s], k = m * P.adapt.max_dist_pct / 100;
             const unsigned long long top = 1ull << (m - 1);
             const unsigned long long e0 = sPeq[s][0], e1 = sPeq[s][1], e2 = sPeq[s][2], e3 = sPeq[s][3];
-            AdapterCol col{~0ull, 0ull, m};
+            MyersCol col{~0ull, 0ull, m};
             bool prev = false, own = false, done = false;
             int best = 0, end = 0;
             // a closed run of this lane: its start by the anchored second pass
             auto emit = [&]() {
                 if (end > bound) return;
-                AdapterCol rc{~0ull, 0ull, m};
+                MyersCol rc{~0ull, 0ull, m};
                 const int xmax = min(end, m + best);
                 int x = 0;
                 while (x < xmax) {
                     const int b = d[end - 1 - x] & 3;
                     ++x;
-                    adapter_step(rc, sPeqR[s][b], top, 1ull);
+                    myers_step(rc, sPeqR[s][b], top, 1ull);
                     if (x >= m - best && rc.score == best) break;
                 }
                 fn(end - x, end, s, best);
@@ -4765,7 +4750,7 @@ __global__ __launch_bounds__(CCSX_ADAPTER_THREADS) void k_adapter(KParams P)
                 for (int q = 0; q < 8; ++q) {
                     if (q >= nb || done) continue;
                     const int b = ch[q] & 3;
-                    adapter_step(col, b == 0 ? e0 : b == 1 ? e1 : b == 2 ? e2 : e3, top, 0ull);
+                    myers_step(col, b == 0 ? e0 : b == 1 ? e1 : b == 2 ? e2 : e3, top, 0ull);
                     const int jj = j + q + 1;                       // E[jj] = col.score
                     const bool ok = col.score <= k;
                     if (jj > lo) {
@@ -5235,6 +5220,10 @@ struct Schedule {
                 launch("k_tile_rows", k_tile_rows, dim3(((unsigned)nb + 7u) & ~7u), dim3(256), 0, sp, P, (int)s0);
             });
             trace_sync(sp, "k_tile_rows");
+        }
+        if (P.bc.rep && !failed) {                         // barcode calls on the final consensus (a batch with a ccsx_barcode_request only)
+            failed = ccsx_barcode_launch(P.bc, sp);
+            trace_sync(sp, "k_barcode");
         }
         stage_event(CCSX_EV_END, sp);
     }

@@ -749,6 +749,65 @@ int         ccsx_orient_batch(ccsx_handle h, const ccsx_batch *b, const ccsx_ori
 int         ccsx_set_orient_opts(ccsx_handle h, const ccsx_orient_opts *opts);
 int         ccsx_stage_orient(ccsx_handle h, ccsx_orient_report *out);
 
+/* ---- barcode calls (the rule: DESIGN.md §2 "Barcode calls", its own version ccsx_barcode_rule_version; the reference leaves demultiplexing to a separate CPU
+ * tool, docs/faq/sqiie.md:104-105; no result of the consensus changes).  k_barcode looks for every barcode of a caller-supplied set at both ends of a read's final
+ * consensus by unit-cost edit distance (semi-global, bit-parallel): end 0 is the first min(L, window) bases of the read, end 1 the first min(L, window) bases of
+ * its reverse complement, so a barcode at the tail is given as it reads on the opposite strand.  Per end: the barcode of smallest distance (ties: the smallest
+ * index), its distance, the smallest prefix of the window that attains it (clip), and the smallest distance of any other barcode (255 with a set of one).  An end
+ * is called iff dist <= floor(m * max_dist_pct / 100) and second - dist >= min_margin, m the length of its barcode.  Integers only.  Detection only: nothing is
+ * clipped, and every result byte equals the same call without the request.
+ *   ccsx_barcode_reads_host  the rule on the calling thread, without a device: the reference of the tests.
+ *   ccsx_barcode_reads       k_barcode on caller-supplied reads (HiFi reads from anywhere).  Synchronous.  It uses buffers of the handle's own and the polish stream:
+ *                            no slot is staged or recycled (slot 0 and every ticket stay as they are, ccsx_run / ccsx_download keep working), and the call returns
+ *                            after the tickets in flight have left the polish stream.
+ *   ccsx_consensus_barcodes  synchronous (slot 0), as ccsx_consensus_requests: k_barcode runs on the polish stream after k_stitch, on res->seq / res->seq_len as they
+ *                            are on the device.
+ *   ccsx_submit_barcodes     ticketed like ccsx_submit_requests: the report's arrays follow the lifetime rule of `res` and should be page-locked; the request, set
+ *                            and options structs are read during the call only (every ticket carries its own set and options).
+ * rq may be NULL or carry any member of ccsx_requests.  The request is not combined with ccsx_handoff_request or ccsx_hd_request: no entry point takes both.
+ * The two ccsx_barcode_reads forms: opts NULL = ccsx_barcode_opts_default; read z is the seq_len[z] codes 0 .. 3 at seq + seq_off[z] (only the low two bits of a byte are
+ * read); seq_len[z] <= 0: untested.  Errors of the call (nothing is enqueued, reserved or launched): a null argument, n_barcodes outside 1 .. CCSX_BARCODE_MAX, a
+ * length outside 8 .. 64, a code above 3, options out of range, a nonzero reserved word, a report sized for another batch (n_zmw != n) or with a NULL array, n < 0,
+ * a negative seq_off.  Without a request nothing of it is launched, reserved or copied.                                                                        */
+#define CCSX_BARCODE_MAX        384
+#define CCSX_BARCODE_MIN_LEN    8
+#define CCSX_BARCODE_MAX_LEN    64
+#define CCSX_BARCODE_MAX_WINDOW 1024
+typedef struct ccsx_barcode_opts {
+    int32_t window;              /* bases of either end that are searched, 8 .. 1024 [64]                                                                        */
+    int32_t max_dist_pct;        /* an end is called at up to floor(m * max_dist_pct / 100) edits, 0 .. 30 [15]                                                  */
+    int32_t min_margin;          /* ... and when every other barcode is at least this many edits worse, 0 .. 64 [1]                                              */
+} ccsx_barcode_opts;
+typedef struct ccsx_barcode_set {
+    int32_t n_barcodes;          /* 1 .. CCSX_BARCODE_MAX                                                                                                        */
+    int32_t len[CCSX_BARCODE_MAX];                         /* CCSX_BARCODE_MIN_LEN .. CCSX_BARCODE_MAX_LEN; lengths may differ within a set                      */
+    uint8_t seq[CCSX_BARCODE_MAX][CCSX_BARCODE_MAX_LEN];   /* codes 0 .. 3 (A C G T)                                                                             */
+} ccsx_barcode_set;
+typedef struct ccsx_barcode_report {
+    int32_t  n_zmw;
+    int32_t *tested;             /* [n_zmw] 1: seq_len > 0; 0: untested (idx -1, dist / second 255, clip 0, call 0, bq -1)                                        */
+    int32_t *call;               /* [n_zmw] bit 0: end 0 (the head) is called, bit 1: end 1 (the tail)                                                            */
+    int32_t *bq;                 /* [n_zmw] min over the called ends of floor(100 * (m - dist) / m); -1 without a called end                                      */
+    int32_t *idx;                /* [n_zmw][2] per end: the barcode of smallest dist (ties: the smallest index)                                                   */
+    int32_t *dist;               /* [n_zmw][2] its edit distance to the best substring of the window                                                             */
+    int32_t *second;             /* [n_zmw][2] the smallest dist of any other barcode; 255 when n_barcodes == 1                                                   */
+    int32_t *clip;               /* [n_zmw][2] the smallest j such that a substring ending at window position j attains dist                                      */
+} ccsx_barcode_report;
+typedef struct ccsx_barcode_request {
+    const ccsx_barcode_opts *opts;       /* NULL = ccsx_barcode_opts_default                                                                                     */
+    const ccsx_barcode_set  *set;
+    ccsx_barcode_report     *report;
+    int32_t                  reserved[2];   /* must be 0                                                                                                         */
+} ccsx_barcode_request;
+void        ccsx_barcode_opts_default(ccsx_barcode_opts *o);
+int         ccsx_barcode_rule_version(void);
+int         ccsx_barcode_reads_host(const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
+                                    int32_t n, ccsx_barcode_report *report);
+int         ccsx_barcode_reads(ccsx_handle h, const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const uint8_t *seq, const int64_t *seq_off,
+                               const int32_t *seq_len, int32_t n, ccsx_barcode_report *report);
+int         ccsx_consensus_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc);
+int         ccsx_submit_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc, ccsx_ticket *ticket);
+
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
  * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one
