@@ -779,6 +779,62 @@ def barcode_reads_host(bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = Non
     return rep
 
 
+# ---- representative reads (include/ccsx.h ccsx_represent_*; DESIGN.md §2 "Representative rule")
+REPRESENT_POLISHED, REPRESENT_NONE, REPRESENT_DRAFT, REPRESENT_SUBREAD = 0, 1, 2, 3
+REPRESENT_NAMES = ("POLISHED", "NONE", "DRAFT", "SUBREAD")
+REPRESENT_QV = 10                                # qual / raw_qv of every base of an unpolished representative
+
+
+class CRepresentReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32), ("cls", C.POINTER(C.c_int32)), ("pass", C.POINTER(C.c_int32))]
+
+
+class CRepresentRequest(C.Structure):
+    """ccsx_represent_request: representative reads in the fused path (ccsx_consensus_represent / ccsx_submit_represent)"""
+    _fields_ = [("subread_fallback", C.c_int32), ("kinetics", C.c_int32), ("report", C.POINTER(CRepresentReport)), ("reserved", C.c_int32 * 2)]
+
+
+class RepresentReport(_PlaneReport):
+    """ccsx_represent_report: per ZMW cls (REPRESENT_*) and pass_ (SUBREAD: the representative pass, index within the ZMW; else -1)"""
+    PLANES = _int_planes("cls", "pass_")
+    CSTRUCT = CRepresentReport
+
+    def c_struct(self) -> CRepresentReport:
+        r = CRepresentReport()
+        r.n_zmw = len(self.cls)
+        r.cls = _ptr(self.cls, C.c_int32)
+        setattr(r, "pass", _ptr(self.pass_, C.c_int32))
+        return r
+
+
+def _represent_request(report: RepresentReport, subread_fallback, kinetics):
+    crep = report.c_struct()
+    return CRepresentRequest(int(subread_fallback), int(kinetics), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (crep, report)
+
+
+def represent_host(batch: "Batch", opts: "Opts", status, drafts, res: "Results", subread_fallback=False, kinetics=False,
+                   report: "RepresentReport | None" = None) -> RepresentReport:
+    """ccsx_represent_host: the representative rule on the calling thread, no device, applied in place to `res` (the Results of a finished run on `batch`, or
+    planes of the caller's making on the capacity layout).  status: [n_zmw] the final statuses; drafts: one array of codes per ZMW (an empty one: no draft)"""
+    n = batch.n_zmw
+    drafts = [np.ascontiguousarray(d, np.uint8) for d in drafts]
+    if len(drafts) != n:
+        raise ValueError("drafts: one array per ZMW")
+    st = np.ascontiguousarray(status, np.int32)
+    dlen = np.array([len(d) for d in drafts], np.int32).reshape(n)
+    doff = np.zeros(n, np.int64)
+    if n:
+        doff[1:] = np.cumsum(dlen[:-1], dtype=np.int64)
+    dseq = np.concatenate(drafts + [np.zeros(1, np.uint8)])
+    rep = report if report is not None else RepresentReport.allocate(n)
+    req, _keep = _represent_request(rep, subread_fallback, kinetics)
+    cb, cr = batch.c_struct(), res.c_struct()
+    if lib().ccsx_represent_host(C.byref(cb), C.byref(opts), _ptr(st, C.c_int32), _ptr(dseq, C.c_uint8), _ptr(doff, C.c_int64), _ptr(dlen, C.c_int32),
+                                 C.byref(req), C.byref(cr)) != 0:
+        raise RuntimeError("ccsx_represent_host failed: " + lib().ccsx_last_error().decode())
+    return rep
+
+
 class CPileup(C.Structure):
     _fields_ = [("seq_capacity", C.c_int64), ("coverage", C.POINTER(C.c_uint8)), ("matches", C.POINTER(C.c_uint8)),
                 ("mismatches", C.POINTER(C.c_uint8))]
@@ -1055,6 +1111,7 @@ EXPORTS = [
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
     "ccsx_fit_opts_default", "ccsx_fitter_create", "ccsx_fitter_add", "ccsx_fitter_finish", "ccsx_fitter_destroy",
     "ccsx_barcode_opts_default", "ccsx_barcode_rule_version", "ccsx_barcode_reads_host", "ccsx_barcode_reads", "ccsx_consensus_barcodes", "ccsx_submit_barcodes",
+    "ccsx_represent_rule_version", "ccsx_represent_host", "ccsx_consensus_represent", "ccsx_submit_represent",
 ]
 
 _lib = None
@@ -1197,6 +1254,10 @@ def lib() -> C.CDLL:
         L.ccsx_barcode_reads.argtypes = [C.c_void_p] + _bcreads
         L.ccsx_consensus_barcodes.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CBarcodeRequest)]
         L.ccsx_submit_barcodes.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CBarcodeRequest), C.POINTER(C.c_int64)]
+        L.ccsx_represent_host.argtypes = [C.POINTER(CBatch), C.POINTER(Opts), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                          C.POINTER(CRepresentRequest), C.POINTER(CResults)]
+        L.ccsx_consensus_represent.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CRepresentRequest)]
+        L.ccsx_submit_represent.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CRepresentRequest), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -1606,12 +1667,13 @@ class Handle:
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
 
-    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None):
+    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None, represent=None):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
         ccsx_*_hd with a heteroduplex request, which combines with none of the screens, ccsx_*_requests when _requests made a CRequests (a coverage request,
         or via_requests), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
-        structs join the requests' keep list.  barcodes: (report, set, opts), through ccsx_*_barcodes in the same way (not together with a hand-off).  Returns
-        the C structs"""
+        structs join the requests' keep list.  barcodes: (report, set, opts), through ccsx_*_barcodes in the same way (not together with a hand-off).
+        represent: (report, subread_fallback, kinetics), through ccsx_*_represent in the same way (not together with a hand-off or barcodes).  Returns the C
+        structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
@@ -1631,6 +1693,12 @@ class Handle:
             breq = _barcode_request(bset, bopts, brep.c_struct())
             name, args = f"ccsx_{form}_barcodes", (_keep[-1], breq[0])
             _keep.append((breq, brep))
+        if represent is not None:
+            if handoff is not None or barcodes is not None or name != f"ccsx_{form}_requests":
+                raise ValueError("the represent request goes with the members of ccsx_requests (not with the hand-off, the barcode or the heteroduplex request)")
+            rreq = _represent_request(*represent)
+            name, args = f"ccsx_{form}_represent", (_keep[-1], rreq[0])
+            _keep.append(rreq)
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
         if form == "consensus":
@@ -1800,6 +1868,18 @@ class Handle:
         self._fused("consensus", batch, res, _requests(via_requests=True, **requests), barcodes=(rep, bset, opts))
         return res, rep
 
+    # ---- representative reads (ccsx_consensus_represent): a draft or a subread in the result planes of every ZMW that was not polished
+    def consensus_represent(self, batch: Batch, subread_fallback: bool = False, kinetics: bool = False, res: "Results | None" = None,
+                            **requests) -> tuple["Results", RepresentReport]:
+        """(results, represent report).  subread_fallback: a ZMW that would get its draft gets a subread; kinetics: SUBREAD ZMWs get fi / fp (needs
+        opts.hifi_kinetics and batch.ipd); res: the caller's Results.  requests: Handle.submit's keyword arguments for the other requests of the same run
+        (pileup=, tandem=, fold=, adapters=, control=, coverage= without a gate ... with their reports; not hd=, handoff=, barcodes=)"""
+        if res is None:
+            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = RepresentReport.allocate(batch.n_zmw)
+        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), represent=(rep, subread_fallback, kinetics))
+        return res, rep
+
     def barcode_reads(self, bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = None, report: "BarcodeReport | None" = None) -> BarcodeReport:
         """ccsx_barcode_reads: k_barcode on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
         args, rep, _keep = _barcode_reads_args(bset, opts, reads, report)
@@ -1875,7 +1955,8 @@ class Handle:
                adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, control: "ControlReport | None" = None,
                control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None, coverage: "CoverageReport | None" = None,
                coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, handoff: "Handoff | None" = None,
-               barcodes: "BarcodeReport | None" = None, barcode_set: "BarcodeSet | None" = None, barcode_opts: "BarcodeOpts | None" = None) -> int:
+               barcodes: "BarcodeReport | None" = None, barcode_set: "BarcodeSet | None" = None, barcode_opts: "BarcodeOpts | None" = None,
+               represent: "RepresentReport | None" = None, represent_fallback: bool = False, represent_kinetics: bool = False) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
         receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd).  fold: a report
@@ -1887,7 +1968,10 @@ class Handle:
         without the other screens, not with hd); every ticket carries its own options and gate.  handoff: a Handoff (Handoff.allocate(batch, max_tiles, opts,
         pinned=True) or device=) that receives the polisher hand-off (ccsx_submit_handoff; not with hd): the whole capacity of its arrays is copied, complete
         when the ticket is; every ticket carries its own options and capacity.  barcodes: a report (BarcodeReport.allocate(n, pinned=True)) that receives the
-        barcode calls for barcode_set under barcode_opts (ccsx_submit_barcodes; not with hd or handoff); every ticket carries its own set and options"""
+        barcode calls for barcode_set under barcode_opts (ccsx_submit_barcodes; not with hd or handoff); every ticket carries its own set and options.  represent: a report
+        (RepresentReport.allocate(n, pinned=True)) that receives the representative classes; the ZMWs that were not polished get a draft or a subread in `res`
+        (ccsx_submit_represent; represent_fallback / represent_kinetics: the request's flags, every ticket its own; not with hd, handoff, barcodes or a
+        coverage gate)"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if hd is not None and fold is not None:
@@ -1904,12 +1988,15 @@ class Handle:
             raise ValueError("the heteroduplex request and the hand-off are not combined")
         if barcodes is not None and (hd is not None or handoff is not None):
             raise ValueError("the barcode request is not combined with the heteroduplex request or the hand-off")
+        if represent is not None and (hd is not None or handoff is not None or barcodes is not None):
+            raise ValueError("the represent request is not combined with the heteroduplex request, the hand-off or the barcode request")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
                              control, control_seq, control_opts, coverage, coverage_opts, coverage_gate,
-                             via_requests=handoff is not None or barcodes is not None)
+                             via_requests=handoff is not None or barcodes is not None or represent is not None)
         t = C.c_int64()
         cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff,
-                             barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None)
+                             barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None,
+                             represent=(represent, represent_fallback, represent_kinetics) if represent is not None else None)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
         self._inflight[t.value] = (batch, res, cb, cr, requests, handoff)  # the C structs and arrays must outlive the ticket

@@ -93,6 +93,10 @@ struct Options {
     std::shared_ptr<ccsx_barcode_set> barcode_set;   // ... the set it names, the record names, the options every ticket carries
     std::vector<std::string> barcode_names;
     ccsx_barcode_opts barcode_opts{};
+    bool reads_bam = false;       // --reads-bam: one representative read per productive ZMW (the reference's --all, DESIGN.md §2 "Representative rule")
+    bool reads_kinetics = false;  // --reads-bam-kinetics: --hifi-kinetics for the polished reads, fi / fp of the pass for the unaltered subreads (--all-kinetics)
+    bool reads_fallback = false;  // --reads-bam-subread-fallback: a subread where an unpolished draft would be written (--subread-fallback)
+    bool min_passes_set = false, min_rq_set = false, max_length_set = false;   // given on the command line (--reads-bam fixes them)
     std::string fit_model;        // --fit-model OUT.json: the training mode (DESIGN.md §2 "Model training"): no consensus output
     int fit_iterations = 3;       // --fit-iterations: EM iterations over the file
     double fit_min_rq = 0.999;    // --fit-min-rq: a polished consensus is a truth to measure passes against from this predicted accuracy on
@@ -168,6 +172,7 @@ struct Batch {
     ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_control_request: the report's arrays are in out_arena)
     ccsx_coverage_report vrep{}; ccsx_coverage_request vreq{}; // --coverage-filters (ccsx_coverage_request: the report's arrays are in out_arena)
     ccsx_barcode_report brep{}; ccsx_barcode_request breq{};   // --barcodes (ccsx_barcode_request: the report's arrays are in out_arena)
+    ccsx_represent_report rrep{}; ccsx_represent_request rreq{};   // --reads-bam (ccsx_represent_request: the report's arrays are in out_arena)
     ccsx_requests reqs{};           // (read during the call only)
 };
 
@@ -232,6 +237,10 @@ void usage()
                  "      --adapters F|default  with --fail-reads: screen every draft for the adapters of FASTA file F (up to 8 records of 16-64 bases) or for the\n"
                  "                            built-in SMRTbell adapter; reads made of adapter copies (ff 0x10) or with an adapter close to an end (ff 0x40)\n"
                  "                            leave the main output for F.bam [off]\n"
+                 "      --reads-bam           one read per productive ZMW (the reference's --all): the polished read, or the unpolished draft, or an unaltered\n"
+                 "                            subread, the last two with rq -1 and every QV 10; sets --min-passes 2, --min-rq 0 and the engine's maximum length\n"
+                 "      --reads-bam-kinetics  with --reads-bam: --hifi-kinetics for the polished reads, fi fp (fn 1, rn 0) for the subreads (--all-kinetics)\n"
+                 "      --reads-bam-subread-fallback  with --reads-bam: a subread where an unpolished draft would be written (--subread-fallback)\n"
                  "      --coverage-filters    screen every draft's windows for coverage drops: a ZMW whose passes disagree on a block of bases, that too few\n"
                  "                            passes span end to end, that too few passes align to, or that lost too many passes in the polish gets no\n"
                  "                            consensus and is counted as 'Coverage drops', 'Insufficient draft cov', 'Draft too different' or 'Reads\n"
@@ -395,12 +404,12 @@ bool parse(int argc, char **argv, Options &o)
         if (a == "-h" || a == "--help") { usage(); std::exit(0); }
         else if (a == "--version") { std::printf("ccs (ccs_amd, MI355X-native consensus path) abi %d spec %d\n", ccsx_abi_version(), ccsx_spec_version()); std::exit(0); }
         else if (a == "-j" || a == "--num-threads") o.threads = std::atoi(need("-j").c_str());
-        else if (a == "--min-passes") o.o.min_passes = std::atoi(need(a.c_str()).c_str());
+        else if (a == "--min-passes") { o.o.min_passes = std::atoi(need(a.c_str()).c_str()); o.min_passes_set = true; }
         else if (a == "--top-passes") o.o.top_passes = std::atoi(need(a.c_str()).c_str());
         else if (a == "--min-snr") o.min_snr = std::atof(need(a.c_str()).c_str());
         else if (a == "--min-length") o.o.min_length = std::atoi(need(a.c_str()).c_str());
-        else if (a == "--max-length") o.o.max_length = std::atoi(need(a.c_str()).c_str());
-        else if (a == "--min-rq") o.o.min_rq = (float)std::atof(need(a.c_str()).c_str());
+        else if (a == "--max-length") { o.o.max_length = std::atoi(need(a.c_str()).c_str()); o.max_length_set = true; }
+        else if (a == "--min-rq") { o.o.min_rq = (float)std::atof(need(a.c_str()).c_str()); o.min_rq_set = true; }
         else if (a == "--maxPoaCoverage") o.o.max_poa_cov = std::atoi(need(a.c_str()).c_str());
         else if (a == "--max-insertion-size") { const int v = std::atoi(need(a.c_str()).c_str()); o.o.max_insertion_size = v > 0 ? v : -1; }
         else if (a == "--max-qv") { const int v = std::atoi(need(a.c_str()).c_str()); o.o.max_qv = v < 1 ? 50 : (v > 93 ? 93 : v); }
@@ -442,6 +451,9 @@ bool parse(int argc, char **argv, Options &o)
             o.barcode_window = (int)n;
         }
         else if (a == "--coverage-filters") o.coverage_filters = true;
+        else if (a == "--reads-bam") o.reads_bam = true;
+        else if (a == "--reads-bam-kinetics") o.reads_kinetics = true;
+        else if (a == "--reads-bam-subread-fallback") o.reads_fallback = true;
         else if (a == "--orient-passes") o.orient_passes = true;
         else if (a == "--coverage-drop-percent" || a == "--coverage-block") {
             const bool pct = a == "--coverage-drop-percent";
@@ -472,6 +484,24 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if ((o.reads_kinetics || o.reads_fallback) && !o.reads_bam) {
+        std::fprintf(stderr, "ccs: --reads-bam-kinetics and --reads-bam-subread-fallback need --reads-bam\n"); std::exit(2);
+    }
+    if (o.reads_bam) {                                       // docs/faq/mode-all.md:13-37: the filters of the mode are fixed, and it is its own output mode
+        auto fixed = [](const char *what) { std::fprintf(stderr, "ccs: %s can't be changed with --reads-bam (it sets --min-passes 2, --min-rq 0 and the engine's maximum length)\n", what); std::exit(2); };
+        auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --reads-bam combined with %s is not supported\n", what); std::exit(2); };
+        if (o.min_passes_set) fixed("--min-passes");
+        if (o.min_rq_set) fixed("--min-rq");
+        if (o.max_length_set) fixed("--max-length");
+        if (o.by_strand) refuse("--by-strand");
+        if (!o.fail_reads.empty()) refuse("--fail-reads");
+        if (o.coverage_filters) refuse("--coverage-filters");
+        if (!o.barcodes.empty()) refuse("--barcodes");
+        if (!o.fit_model.empty()) refuse("--fit-model");
+        o.o.min_passes = 2; o.o.min_rq = 0.0f;
+        o.o.max_length = 65535 + 65535 / 4 + 64;             // the longest draft the engine holds: the slot of its longest subread
+        if (o.reads_kinetics) o.o.hifi_kinetics = 1;
     }
     if (!o.fit_model.empty()) {                              // the training mode takes nothing of the output side: refused before any of those options is looked at
         auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --fit-model %s\n", what); std::exit(2); };
@@ -680,7 +710,8 @@ void finish_zmw(ZmwIn &z, const Options &o)
         const bool full = (r.cx < 0) || ((r.cx & 3) == 3);       // flanked by adapters (docs/faq/accuracy-vs-passes.md:17-18)
         // partial passes (one adapter only: the first / last subread of the polymerase read) are not passes, but the polish uses them
         // where they reach (docs/faq/accuracy-vs-passes.md:26-29: ec ~ np + 1); they are shorter by nature: no lower length bound
-        const bool partial = !full && r.cx >= 0 && (r.cx & 3) != 0 && l >= 50.0 && l <= 2.0 * med && !o.no_partial;
+        // (--reads-bam: a subread with no adapter flag at all is submitted as a partial pass too)
+        const bool partial = !full && r.cx >= 0 && ((r.cx & 3) != 0 || o.reads_bam) && l >= 50.0 && l <= 2.0 * med && !o.no_partial;
         if (partial && !r.has_n) {
             // a subread inside [0.5, 2] x median is not a "Median length filter" case whatever its adapters (docs/faq/reports-aux-files.md:26-27:
             // that category means ALL subreads are outside); a ZMW with one-adapter subreads only ends as "Lacking full passes" 
@@ -701,7 +732,8 @@ void finish_zmw(ZmwIn &z, const Options &o)
     if (!any_len_ok) { z.host_status = HS_NO_SUBREADS; z.reads.clear(); return; }
     // the engine handles subreads up to 65535 bases; longer inserts cannot pass --max-length (<= 50000) anyway
     for (auto &r : z.reads) if (r.size() > 65535 || (double)r.size() > 1.3 * (double)o.o.max_length + 1000.0) { z.host_status = HS_TOO_LONG; z.reads.clear(); return; }
-    if ((int)z.reads.size() < o.o.min_passes) { z.host_status = HS_TOO_FEW; z.reads.clear(); return; }
+    // --reads-bam: a ZMW with any subread left is submitted; the engine says TOO_FEW_PASSES and the representative rule picks a subread
+    if ((int)z.reads.size() < o.o.min_passes && !(o.reads_bam && z.reads.size() + part.size() >= 1)) { z.host_status = HS_TOO_FEW; z.reads.clear(); return; }
     // --top-passes: "at most the top 60 full-length passes after sorting by median length" (docs/faq/accuracy-vs-passes.md:49-52):
     // the N passes whose length is closest to the median are kept, in their original order
     const size_t top = (size_t)o.o.top_passes;
@@ -771,6 +803,7 @@ struct Report {
     std::map<std::string, int64_t> fail;
     std::vector<int32_t> lens; std::vector<float> rqs; std::vector<int32_t> nps;   // one entry per written read
     int64_t bases_q30 = 0;        // written bases with a phred QV >= 30 ("Base quality >=Q30 (bp)", docs/faq/reports-aux-files.md:66)
+    int64_t rep_cls[4] = {0, 0, 0, 0};   // --reads-bam: submitted ZMWs per ccsx_represent_class (POLISHED, NONE, DRAFT, SUBREAD)
     int64_t tandem = 0;           // ZMWs flagged as tandem repeats (--min-tandem-repeat-length; docs/faq/reports-aux-files.md:22)
     int64_t fail_records = 0;     // records written to --fail-reads
     int64_t control = 0;          // ZMWs the control screen found (--control), whatever their final status
@@ -914,6 +947,12 @@ void write_report(const Options &o, const Report &r)
             for (int k = 0; k < 4; ++k) std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", rows[k], r.bc_call[which[k]], pct(r.bc_call[which[k]], r.bc_tested));
             std::fprintf(f, "\n");
         }
+        if (o.reads_bam) {                                       // DESIGN.md §2 "Representative rule": what the records of OUT are
+            std::fprintf(f, "Representative reads\n");
+            std::fprintf(f, "%-30s: %" PRId64 "\n", "Polished reads", r.rep_cls[CCSX_REPRESENT_POLISHED]);
+            std::fprintf(f, "%-30s: %" PRId64 "\n", "Unpolished drafts", r.rep_cls[CCSX_REPRESENT_DRAFT]);
+            std::fprintf(f, "%-30s: %" PRId64 "\n\n", "Unaltered subreads", r.rep_cls[CCSX_REPRESENT_SUBREAD]);
+        }
         std::fprintf(f, "Exclusive failed counts\n");
         for (const char *k : fail_order(o)) {
             auto it = r.fail.find(k);
@@ -957,6 +996,9 @@ void write_report_json(const Options &o, const Report &r)
     if (!o.barcodes.empty())
         std::fprintf(f, "  \"barcode_calls\": {\"tested\": %" PRId64 ", \"both_ends\": %" PRId64 ", \"head_only\": %" PRId64 ", \"tail_only\": %" PRId64 ", \"none\": %" PRId64 "},\n",
                      r.bc_tested, r.bc_call[3], r.bc_call[1], r.bc_call[2], r.bc_call[0]);
+    if (o.reads_bam)
+        std::fprintf(f, "  \"representative_reads\": {\"polished\": %" PRId64 ", \"draft\": %" PRId64 ", \"subread\": %" PRId64 "},\n",
+                     r.rep_cls[CCSX_REPRESENT_POLISHED], r.rep_cls[CCSX_REPRESENT_DRAFT], r.rep_cls[CCSX_REPRESENT_SUBREAD]);
     std::fprintf(f, "  \"exclusive_failed_counts\": {");
     bool first = true;
     for (const char *k : fail_order(o)) {
@@ -1501,7 +1543,7 @@ int main(int argc, char **argv)
                         b->cap = cap;
                         b->out_arena = out_pool.get();
                         const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (opt.reads_bam ? 2 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
                         auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
                         auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
                         b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
@@ -1551,6 +1593,11 @@ int main(int argc, char **argv)
                             for (auto &q : two) q = (int32_t *)take(2 * n4);
                             b->brep = ccsx_barcode_report{n, b3[0], b3[1], b3[2], two[0], two[1], two[2], two[3]};
                             b->breq = ccsx_barcode_request{&opt.barcode_opts, opt.barcode_set.get(), &b->brep, {0, 0}};
+                        }
+                        if (opt.reads_bam) {
+                            const auto r2 = planes(2);
+                            b->rrep = ccsx_represent_report{n, r2[0], r2[1]};
+                            b->rreq = ccsx_represent_request{opt.reads_fallback ? 1 : 0, opt.reads_kinetics ? 1 : 0, &b->rrep, {0, 0}};
                         }
                         b->reqs = ccsx_requests{(opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr,
                                               control ? &b->creq : nullptr, coverage ? &b->vreq : nullptr, {nullptr, nullptr, nullptr}};
@@ -1653,7 +1700,8 @@ int main(int argc, char **argv)
                 t0 = now();
                 ccsx_ticket t = -1;
                 // the most general submit: NULL for the extras and for every request this run did not ask for (the narrower entry points stage the same)
-                if (barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
+                if (opt.reads_bam ? ccsx_submit_represent(h, &b->cb, &b->cr, &b->reqs, &b->rreq, &t)
+                                  : barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1741,6 +1789,35 @@ int main(int argc, char **argv)
                     rb.tagBC("sx", cov + 2 * cap, (uint32_t)len);
                 }
             };
+            auto put_fastq = [&](const std::string &qname, const Batch &bt, int64_t o, int32_t len) {
+                fq.clear(); fq += '@'; fq += qname; fq += '\n';
+                for (int32_t q = 0; q < len; ++q) fq += "ACGT"[bt.seq[o + q] & 3];
+                fq += "\n+\n";
+                for (int32_t q = 0; q < len; ++q) fq += (char)(33 + (bt.qual[o + q] > 93 ? 93 : bt.qual[o + q]));
+                fq += '\n';
+                if (gzwrite(gzq, fq.data(), (unsigned)fq.size()) != (int)fq.size()) throw std::runtime_error("short write (fastq.gz)");
+            };
+            // --reads-bam: the record of a ZMW that was not polished, its draft or one of its subreads as k_represent left it in the result planes (rq -1, no ec;
+            // the subread's own ipd / pw as fi / fp with --reads-bam-kinetics: "as forward orientation", docs/faq/mode-all.md:24)
+            auto put_representative = [&](const ZmwIn &z, Batch &bt, int s, bool subread) {
+                const int64_t o = bt.seq_off[s]; const int32_t len = bt.seq_len[s];
+                const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs";
+                if (fastq) { put_fastq(qname, bt, o, len); return; }
+                rb.begin(qname, bt.seq + o, bt.qual + o, (uint32_t)len);
+                rb.tagi("zm", z.zm);
+                rb.tagZ("RG", "ccsamd01");
+                rb.tagBf("sn", z.snr, 4);
+                rb.tagi("np", bt.np[s]);
+                rb.tagf("rq", bt.rq[s]);
+                if (opt.reads_kinetics && subread) {
+                    rb.tagBC("fi", bt.kin + o, (uint32_t)len); rb.tagBC("fp", bt.kin + (size_t)bt.cap + o, (uint32_t)len);
+                    rb.tagi("fn", 1); rb.tagi("rn", 0);
+                }
+                marks.push_back(outp->mark());
+                pbi.rg_id.push_back(0); pbi.q_start.push_back(0); pbi.q_end.push_back(len); pbi.hole.push_back(z.zm);
+                pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
+                rb.finish(*outp);
+            };
             auto emit = [&](Batch &bt) {
                 if (!header_done) {
                     const std::string text = "@HD\tVN:1.6\tSO:unknown\tpb:5.0.0\n@RG\tID:ccsamd01\tPL:PACBIO\tDS:READTYPE=CCS" +
@@ -1784,8 +1861,11 @@ int main(int argc, char **argv)
                         flush_metrics(false);
                     }
                     const int64_t o = s >= 0 ? bt.seq_off[s] : 0; const int32_t len = (s >= 0 && bt.have_results) ? bt.seq_len[s] : 0;
+                    const int rcls = (opt.reads_bam && s >= 0 && bt.have_results) ? bt.rrep.cls[s] : CCSX_REPRESENT_NONE;
+                    if (opt.reads_bam && s >= 0 && bt.have_results) ++rep.rep_cls[rcls & 3];
                     if (st != CCSX_SUCCESS) {
                         rep.fail[fail_label(st, coverage)]++;
+                        if ((rcls == CCSX_REPRESENT_DRAFT || rcls == CCSX_REPRESENT_SUBREAD) && len > 0) put_representative(z, bt, s, rcls == CCSX_REPRESENT_SUBREAD);
                         if (st >= CCSX_DRAFT_TOO_DIFFERENT && st <= CCSX_READS_FAILED_POLISHING) ++rep.coverage;
                         if (!fail_reads) continue;
                         if ((engine_st == CCSX_LOW_RQ || pal || abits || ctl) && len > 0) {     // a consensus: as the main writer builds it, plus ff
@@ -1826,12 +1906,7 @@ int main(int argc, char **argv)
                         if (bc_both) ++rep.bc_pairs[{bt.brep.idx[2 * s], bt.brep.idx[2 * s + 1]}];
                     }
                     if (fastq) {
-                        fq.clear(); fq += '@'; fq += qname; fq += '\n';
-                        for (int32_t q = 0; q < len; ++q) fq += "ACGT"[bt.seq[o + q] & 3];
-                        fq += "\n+\n";
-                        for (int32_t q = 0; q < len; ++q) fq += (char)(33 + (bt.qual[o + q] > 93 ? 93 : bt.qual[o + q]));
-                        fq += '\n';
-                        if (gzwrite(gzq, fq.data(), (unsigned)fq.size()) != (int)fq.size()) throw std::runtime_error("short write (fastq.gz)");
+                        put_fastq(qname, bt, o, len);
                         rep.lens.push_back(len); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]);
                         continue;
                     }
@@ -1879,7 +1954,12 @@ int main(int argc, char **argv)
                 for (uint64_t m : fmarks) fpbi.file_offset.push_back((int64_t)failp->virtual_offset(m));
                 write_pbi(opt.fail_reads + ".pbi", pool, fpbi);
             }
-            if (gzm) { metrics += "\n  ]\n}\n"; flush_metrics(true); gzclose(gzm); }
+            if (gzm) {
+                metrics += "\n  ]";
+                if (opt.reads_bam) metrics += ",\n  \"representative_reads\": {\"polished\": " + std::to_string(rep.rep_cls[CCSX_REPRESENT_POLISHED]) + ", \"draft\": " +
+                                              std::to_string(rep.rep_cls[CCSX_REPRESENT_DRAFT]) + ", \"subread\": " + std::to_string(rep.rep_cls[CCSX_REPRESENT_SUBREAD]) + "}";
+                metrics += "\n}\n"; flush_metrics(true); gzclose(gzm);
+            }
             } catch (const std::exception &e) {
                 fail(std::string("writing ") + opt.out + ": " + e.what());
                 std::shared_ptr<Batch> drop;
@@ -1915,12 +1995,14 @@ int main(int argc, char **argv)
                          gpu_deflater.n_tickets, gpu_deflater.n_blocks, gpu_deflater.n_in * 1e-6, gpu_deflater.n_out * 1e-6, gpu_deflater.us_submit * 1e-6,
                          gpu_deflater.us_wait * 1e-6);
         if (opt.log_level >= 1)
-            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s%s\n", rep.input, rep.pass, el,
+            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",
                          opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "",
                          opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str(),
                          control ? (", " + std::to_string(rep.control) + " control ZMWs").c_str() : "",
-                         coverage ? (", " + std::to_string(rep.coverage) + " ZMWs failed the coverage filters").c_str() : "");
+                         coverage ? (", " + std::to_string(rep.coverage) + " ZMWs failed the coverage filters").c_str() : "",
+                         opt.reads_bam ? (", representative reads: " + std::to_string(rep.rep_cls[CCSX_REPRESENT_POLISHED]) + " polished, " + std::to_string(rep.rep_cls[CCSX_REPRESENT_DRAFT]) +
+                                          " drafts, " + std::to_string(rep.rep_cls[CCSX_REPRESENT_SUBREAD]) + " subreads").c_str() : "");
         if (opt.log_level >= 1 && opt.orient_passes)
             std::fprintf(stderr, "ccs: --orient-passes: %lld passes submitted strand-unknown\n", unknown_passes.load());
         if (failed) {

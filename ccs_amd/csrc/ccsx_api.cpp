@@ -141,6 +141,7 @@ struct Slot {
     DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
     DevBuf d_bc;                                  // barcode calls only (ccsx_barcode_request): the set's masks and lengths, then the [11][n] report
+    DevBuf d_rp;                                  // representative reads only (ccsx_represent_request): the [2][n] report
     DevBuf d_rf_tiles, d_rf_base, d_rf_rep;       // polisher hand-back only (ccsx_submit_refine): the tile list and its classes; base lengths, backbones, seq, qual; the report
     RefineParams RP{};                            // ... its kernels' parameters as enqueued (the report's download reads them)
     // host copies of the layout (page-locked: sources of the asynchronous uploads)
@@ -390,6 +391,7 @@ struct Wants {
     const ccsx_orient_opts *orient = nullptr;   // ccsx_orient_batch's own options (NULL: the handle's, ccsx_set_orient_opts); already checked
     const ccsx_handoff_request *handoff = nullptr; ccsx_handoff_opts handoff_opts{}; ccsx_handoff_out handoff_out{};   // (the out struct is copied: it is read during the call only)
     const ccsx_barcode_request *barcodes = nullptr; ccsx_barcode_opts barcode_opts{}; std::vector<unsigned long long> barcode_set; int barcode_n = 0;   // (the set packed: barcode_words)
+    bool represent = false; ccsx_represent_request represent_req{};   // (the request is copied: it is read during the call only)
     bool handoff_written_only = false;          // the synchronous form: counts is known when the copies are enqueued, only the written slots are copied
 };
 
@@ -1244,6 +1246,25 @@ static int enqueue_barcode_download(const BarcodeParams &B, const ccsx_barcode_r
     return 0;
 }
 
+// ---- the representative reads' host side (DESIGN.md §2 "Representative rule"; the request's checks: ccsx_represent_api.cpp).  k_represent's parameters are the
+// slot's own inputs, final drafts and result planes: nothing is uploaded, the [2][n] report is all it reserves.
+static int represent_attach(Slot &S, const ccsx_represent_request &q)
+{
+    KParams &P = S.P;
+    const size_t n = (size_t)P.n_zmw;
+    if (S.d_rp.reserve((n ? n : 1) * CCSX_RP_PLANES * 4)) return -2;
+    RepresentParams R{};
+    R.n = (int32_t)n; R.top_passes = P.opts.top_passes; R.subread_fallback = q.subread_fallback;
+    R.read_off = P.read_off; R.base_off = P.base_off; R.bases = P.bases; R.pw = P.pw; R.ipd = P.ipd; R.flags = P.flags;
+    R.seq_off = P.seq_off; R.draft = P.draft; R.draft_len = P.draft_len; R.status = P.out_status;
+    R.out_len = P.out_len; R.out_rq = P.out_rq; R.out_ec = P.out_ec; R.out_seq = P.out_seq; R.out_qual = P.out_qual; R.out_raw = P.out_raw;
+    R.out_kin = q.kinetics ? P.out_kin : nullptr; R.kin_plane = P.kin_plane;
+    R.rep = (int32_t *)S.d_rp.p;
+    if (q.kinetics && (!P.out_kin || !P.ipd)) { ccsx_set_error("represent request: kinetics needs opts.hifi_kinetics and batch.ipd"); return -1; }
+    P.rep = R;
+    return 0;
+}
+
 // what a ccsx_extras asks for (NULL: nothing); -1 for a malformed one
 static int extras_want(const ccsx_extras *ex, bool *tandem)
 {
@@ -1292,6 +1313,7 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.coverage && (rc = coverage_attach(h, S, W.coverage_opts, W.coverage->gate))) return rc;
     if (W.handoff && (rc = handoff_attach(S, W.handoff_opts, W.handoff_out.max_tiles))) return rc;
     if (W.barcodes && (rc = barcode_attach(S, W.barcode_set, W.barcode_n, W.barcode_opts, st))) return rc;
+    if (W.represent && (rc = represent_attach(S, W.represent_req))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
     return 0;
@@ -1326,6 +1348,10 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
     }
     if (W.handoff && (rc = enqueue_handoff_download(S, W.handoff_out, W.handoff_written_only, s))) return rc;
     if (W.barcodes && (rc = enqueue_barcode_download(S.P.bc, W.barcodes->report, s))) return rc;
+    if (W.represent && n) {
+        const ccsx_represent_report *r = W.represent_req.report;
+        if ((rc = download_planes({r->cls, r->pass}, S.P.rep.rep, n, s))) return rc;
+    }
     return 0;
 }
 
@@ -1567,6 +1593,23 @@ int ccsx_submit_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, 
 {
     Wants W;
     if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+// the Wants of a call with a representative request: the request checked against the batch and the handle's options and copied, then the members of rq
+static int represent_wants(ccsx_handle h, const ccsx_batch *b, const ccsx_requests *rq, const ccsx_represent_request *rp, const char *fn, Wants *W)
+{
+    if (!rp) return refuse(fn, "null represent request");
+    if (!h || !b) return refuse(fn, "null argument");
+    if (ccsx_represent_check(rp, b, &h->opts, fn)) return -1;
+    if (rq && rq->coverage && rq->coverage->gate != 0) return refuse(fn, "the represent request is not combined with the coverage gate");
+    if (requests_wants(rq, b, fn, W)) return -1;
+    W->represent_req = *rp; W->represent = true;
+    return 0;
+}
+int ccsx_submit_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rp, ccsx_ticket *ticket)
+{
+    Wants W;
+    if (represent_wants(h, b, rq, rp, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_draft(ccsx_handle h, const ccsx_batch *b, ccsx_drafts *drafts, ccsx_ticket *ticket)
@@ -1845,6 +1888,13 @@ int ccsx_consensus_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *re
 {
     Wants W;
     if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
+int ccsx_consensus_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rp)
+{
+    Wants W;
+    if (represent_wants(h, b, rq, rp, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 

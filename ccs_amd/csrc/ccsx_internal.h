@@ -40,3 +40,7 @@ int ccsx_barcode_check(const ccsx_barcode_set *set, const ccsx_barcode_opts *opt
 int ccsx_barcode_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes);
 // k_barcode's view of a checked set: masks [n_barcodes][4], len [n_barcodes]
 void ccsx_barcode_pack(const ccsx_barcode_set *set, unsigned long long *masks, uint8_t *len);
+
+// ---- representative reads (ccsx_represent_api.cpp; DESIGN.md §2 "Representative rule"): the request against the batch it is for and the options of the run — flags,
+// reserved words, the report's arrays and size, kinetics without opts.hifi_kinetics or batch.ipd.  A refusal sets the error under `fn` and returns -1.
+int ccsx_represent_check(const ccsx_represent_request *req, const ccsx_batch *b, const ccsx_opts *opts, const char *fn);

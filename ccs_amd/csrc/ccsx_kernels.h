@@ -6,6 +6,7 @@
 
 #include "ccsx.h"
 #include "barcode_core.h"
+#include "represent_core.h"
 
 // bytes of POA scratch per vertex (ccsx_kernels.hip poa_slot, all by topological position): the 32-row score column of far-read columns 128, five 16-byte
 // records (kinfo, column records x 2, overflow in-edges x 2), 16 move bytes (a nibble per band row), 3 words of consensus / band state, two flag bytes
@@ -177,6 +178,9 @@ struct KParams {
     // ---- barcode calls (ccsx_consensus_barcodes / ccsx_submit_barcodes; bc.rep NULL otherwise): DESIGN.md §2 "Barcode calls".  k_barcode's own parameters
     // (ccsx_barcode.hip): it reads out_seq / out_len after k_stitch
     BarcodeParams bc;
+    // ---- representative reads (ccsx_consensus_represent / ccsx_submit_represent; rep.rep NULL otherwise): DESIGN.md §2 "Representative rule".  k_represent's own
+    // parameters (ccsx_represent.hip): it reads the final draft and out_status and writes the result planes after k_stitch
+    RepresentParams rep;
 };
 // first tile index of ZMW z whose outputs start at seq_off: consecutive ZMWs get disjoint ranges of at least ceil(capacity / T) tiles, with no table
 static inline __host__ __device__ int64_t ccsx_handoff_tile_off(int64_t seq_off, int z, int T) { return seq_off / T + z; }
@@ -276,6 +280,7 @@ struct ccsx_launch_queues {
 };
 const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode);   // NULL, or the name of the launch that failed
 const char *ccsx_barcode_launch(const BarcodeParams &B, hipStream_t st);                 // ccsx_barcode.hip: k_barcode, one workgroup per read; NULL, or what failed
+const char *ccsx_represent_launch(const RepresentParams &R, hipStream_t st);             // ccsx_represent.hip: k_represent, one workgroup per ZMW; NULL, or what failed
 const char *ccsx_train_launch(const KParams &P, hipStream_t st, long long max_blocks);   // ccsx_train.hip: the count buffers zeroed + k_train; NULL, or what failed
 int ccsx_kernel_is_experiment();         // built with -DCCSX_EXPERIMENT (timing studies: wrong results)
 const char *ccsx_kernel_build_flags();   // "" for a product build; the experiment switches this translation unit was compiled with otherwise

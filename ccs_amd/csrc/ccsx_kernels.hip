@@ -5225,6 +5225,10 @@ struct Schedule {
             failed = ccsx_barcode_launch(P.bc, sp);
             trace_sync(sp, "k_barcode");
         }
+        if (P.rep.rep && !failed) {                        // representative reads into the result planes (a batch with a ccsx_represent_request only)
+            failed = ccsx_represent_launch(P.rep, sp);
+            trace_sync(sp, "k_represent");
+        }
         stage_event(CCSX_EV_END, sp);
     }
 };

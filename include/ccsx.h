@@ -808,6 +808,48 @@ int         ccsx_barcode_reads(ccsx_handle h, const ccsx_barcode_set *set, const
 int         ccsx_consensus_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc);
 int         ccsx_submit_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc, ccsx_ticket *ticket);
 
+/* ---- representative reads (the rule: DESIGN.md §2 "Representative rule", its own version ccsx_represent_rule_version; the reference's --all mode,
+ * docs/faq/mode-all.md:13-37: no productive ZMW is lost).  A ZMW that does not end in a polished consensus gets a representative sequence in the result planes
+ * instead of seq_len 0: its final draft, or one of its subreads unaltered.  k_represent runs on the polish stream after k_stitch, before the download.  Per ZMW the
+ * class is the first of these that holds (nall: its passes after the top_passes cut; nfull: those without flag bit 1; st: its final status; Ld: the length of the
+ * final draft, the one k_polish is given):
+ *   POLISHED  st is SUCCESS or LOW_RQ.  Nothing of the ZMW is touched.
+ *   NONE      nall == 0, or st is TOO_SHORT or TOO_LONG (or a draft longer than its slot: never truncated).  Nothing of the ZMW is touched.
+ *   DRAFT     Ld > 0, st is not TOO_FEW_PASSES, subread_fallback == 0: seq = the draft.
+ *   SUBREAD   everything else: seq = a pass in native orientation (low two bits of its bytes), whatever its strand flag — of the full-length passes when
+ *             nfull >= 1, else of all nall passes, the one of rank floor(|C| / 2) in (length, index within the ZMW) order.
+ * Written for a DRAFT or SUBREAD ZMW, and nothing else: seq_len, seq, qual = 10 and raw_qv = 10.0 for every base, rq = -1, ec = 0; with `kinetics`, for a SUBREAD
+ * ZMW, fi / fp = the pass's ipd / pw codes unaltered (ri / rp are not written; a DRAFT ZMW gets no kinetics).  status, np, fn, rn, iters and n_windows stay as
+ * the engine left them: the status says why the ZMW was not polished.  Every byte of a POLISHED or NONE ZMW equals the same call without the request.
+ *   ccsx_represent_host       the rule on the calling thread, without a device, on a results struct that holds a finished run (status as given, the drafts as
+ *                             given: draft z is draft_len[z] codes at draft_seq + draft_off[z]); res->seq_off must be the capacity layout (ccsx_result_layout).
+ *                             The reference of the tests.
+ *   ccsx_consensus_represent  synchronous (slot 0), as ccsx_consensus_requests.
+ *   ccsx_submit_represent     ticketed like ccsx_submit_requests: the report's arrays follow the lifetime rule of `res` and should be page-locked; the request
+ *                             struct is read during the call only (every ticket carries its own flags).
+ * rq may be NULL or carry any member of ccsx_requests except a coverage request with a gate (statuses 11 .. 14 are not combined with this request).  It is not
+ * combined with ccsx_hd_request, ccsx_handoff_request or ccsx_barcode_request: no entry point takes both.  Errors of the call (nothing is enqueued, reserved or
+ * launched): a null request or report, a report sized for another batch or with a NULL array, a nonzero reserved word, a flag other than 0 / 1, `kinetics`
+ * without opts.hifi_kinetics or without batch.ipd.  Without a request nothing of it is launched, reserved or copied.                                          */
+enum ccsx_represent_class { CCSX_REPRESENT_POLISHED = 0, CCSX_REPRESENT_NONE = 1, CCSX_REPRESENT_DRAFT = 2, CCSX_REPRESENT_SUBREAD = 3 };
+typedef struct ccsx_represent_report {
+    int32_t  n_zmw;
+    int32_t *cls;                /* [n_zmw] enum ccsx_represent_class                                                                                            */
+    int32_t *pass;               /* [n_zmw] SUBREAD: the representative pass, index within the ZMW; -1 otherwise                                                 */
+} ccsx_represent_report;
+typedef struct ccsx_represent_request {
+    int32_t                subread_fallback;   /* 1: a ZMW that would be DRAFT is SUBREAD (the reference's --subread-fallback); 0 / 1                              */
+    int32_t                kinetics;           /* 1: SUBREAD ZMWs get fi / fp (the reference's --all-kinetics); needs opts.hifi_kinetics and batch.ipd; 0 / 1      */
+    ccsx_represent_report *report;
+    int32_t                reserved[2];        /* must be 0                                                                                                        */
+} ccsx_represent_request;
+int         ccsx_represent_rule_version(void);
+int         ccsx_represent_host(const ccsx_batch *b, const ccsx_opts *opts, const int32_t *status, const uint8_t *draft_seq, const int64_t *draft_off,
+                                const int32_t *draft_len, const ccsx_represent_request *req, ccsx_results *res);
+int         ccsx_consensus_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rep);
+int         ccsx_submit_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rep,
+                                  ccsx_ticket *ticket);
+
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
  * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one
