@@ -155,7 +155,9 @@ typedef struct ccsx_results {
      * fn rn of docs/faq/bam-output.md:13-23; with --by-strand the forward pair is the record's ip / pw.           */
     uint8_t *fi, *fp;            /* [seq_capacity] mean IPD / pulse width of the passes on SEQ's strand         */
     uint8_t *ri, *rp;            /* [seq_capacity] same for the passes on the opposite strand                   */
-    int32_t *fn, *rn;            /* [n_zmw] passes used per strand (fn + rn = np); filled with or without kinetics */
+    int32_t *fn, *rn;            /* [n_zmw] full-length passes that align to the draft, on SEQ's strand (the backbone's) / on the other; filled with or
+                                    without kinetics.  fn + rn is the aligned count; np is the mode over windows of the passes the polish used, so
+                                    np <= fn + rn, equal unless most windows' gates drop an aligned pass */
 } ccsx_results;
 
 /* ---- per-kernel device timings of the last run, HIP events on the handle's stream (ms) ---- */

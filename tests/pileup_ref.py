@@ -25,6 +25,16 @@ class Zmw:
     reads: list = field(default_factory=list)     # (bases (native orientation), flags, valid, ent[2 nw])
 
 
+class Read(tuple):
+    """a pass of a Zmw: the 4-tuple (bases, flags, valid, ent) every reader of Zmw.reads unpacks, which also carries the pass's `ipd` and `pw` code bytes
+    (native orientation, one per base) for tests/kinetics_ref.py"""
+
+    def __new__(cls, bases, flags, valid, ent, ipd=None, pw=None):
+        self = super().__new__(cls, (bases, flags, valid, ent))
+        self.ipd, self.pw = ipd, pw
+        return self
+
+
 def diag_rows(segs, tpls, chunk=50_000):
     """global alignment of every segment to its template with the kinetics rule: H[i][0] = -4i, H[0][j] = -4j, diag = H[i-1][j-1] + (3 | -5),
     left = H[i][j-1] - 4, up = H[i-1][j] - 4, h = max(diag, left), cell = max(h, up); move UP iff up > h, else DIAG iff diag >= left, else LEFT.  The
@@ -136,7 +146,8 @@ def collect_stage(handle, batch, zmws=None):
             r0 = int(batch.read_off[z])
             for r in range(r0, r0 + nused):
                 rs, v, _ = handle.stage_align(r, len(d))
-                reads.append((batch.read(r)[0], int(batch.flags[r]), bool(v), np.array([rs[c] for c in cols], np.int64)))
+                a, b = int(batch.base_off[r]), int(batch.base_off[r + 1])
+                reads.append(Read(batch.bases[a:b], int(batch.flags[r]), bool(v), np.array([rs[c] for c in cols], np.int64), batch.ipd[a:b], batch.pw[a:b]))
         ref = int(batch.flags[int(batch.read_off[z]) + bb]) & 1 if nw else 0
         out.append(Zmw([tpl[w, :meta[w, 0]] for w in range(nw)], [(int(meta[w, 1]), int(meta[w, 2])) for w in range(nw)], ref, reads))
     return out
