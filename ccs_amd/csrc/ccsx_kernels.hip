@@ -2313,8 +2313,7 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     __shared__ float sBase[PW_MAXREADS], sB00[PW_MAXREADS];   // alpha(I,J) / beta(0,0) of the chunk's reads (the fill's two halves meet here)
     __shared__ short2 sTask[PW_MAXREADS];                    // .x: the fill tasks of a chunk (a read each: long units, then quad members), listed from the chunk's first read on;
                                                              // .y at a chunk's first read: its long units | quad members << 8
-    __shared__ int sDeltaI[256];                             // fixed-point sums of the per-read gains; converted in place to float
-    float *sDelta = (float *)sDeltaI;                        // (each thread converts its own entry after the scoring barrier)
+    __shared__ int sDeltaI[256];                             // fixed-point sums of the per-read gains (converted in registers at the round's end, never in place)
     __shared__ uint8_t sMvalid[256];
     __shared__ int sCtl[12];                                 // 0:J 1:cs 2:ce 3:nacc 7:ev bits
     __shared__ float sZS[4];                                 // z-score sums: M fwd, V fwd, M rev, V rev
@@ -2570,7 +2569,7 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         //   sT[1]                 written here by wave 0; read by lane_mut in the scoring, behind the chunk-opening barrier (its readers of the round before: in front of
         //                         the barrier that ends the round).  The tables and the z-score sums used to take their bases from it and needed a barrier behind it
         //   sMvalid, sDeltaI,     written here, every entry by its own thread, every wave for its own 64-lane slice.  Read by the scoring (sList, the atomicAdd into
-        //   sList                 sDeltaI) behind the chunk-opening barrier, by the selection and the QV step (sMvalid, sDelta) behind the round's last barrier; their readers
+        //   sList                 sDeltaI) behind the chunk-opening barrier, by every wave behind the round's last barrier (the round's end, the QV terms); their readers
         //                         of the round before: in front of the barrier behind the selection.  Every wave evaluates the validity of all four slices (same column,
         //                         slots 2 q + (lane >> 5)): its base offset and the round's lane count are popcounts of its own ballots — no counts through LDS, none of
         //                         the compaction's two barriers
@@ -2606,14 +2605,19 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         if (wave == (PWT / 64) - 1 && resident == 0) plan_chunks(nreads < PW_MAXREADS ? nreads : PW_MAXREADS, J, S);
         // z-score expectation of the window template on each strand, summed in column order (SPEC); the gate is decided in round 0
         // only.  Lane j holds column j's terms, the ordered sums take them with v_readlane (no chain of dependent LDS loads).
+        // No loop: CCSX_JMAX steps with immediate lane indices.  The lanes from J on contribute + 0.0f (their context CTXS - 1 = 16 reads sZP[16] and sZP[32], a variance
+        // and the first float of the zeroed padding behind sZP: replaced), and a sum that starts at + 0.0f cannot become - 0.0f under round-to-nearest, so the added
+        // zeros change no bit; the order of the real terms is the column order.  (A loop of J steps — a v_readlane with a scalar index, the dependent add and the branch
+        // per step — kept waves 2 and 3 waiting at the chunk-opening barrier for longer; one chain per wave on all four waves was measured and is slower than two
+        // chains on each of waves 0 and 1: profiles/polish_round_end.txt)
         if (it == 0 && wave < 2 && P.opts.min_zscore != 0.0f) {
-            // (a lane from column J on holds context CTXS - 1 = 16: it reads sZP[16] and sZP[32], the first float of the zeroed padding behind sZP — inside
-            // sTab only while that padding exists; the loop below takes the lanes q < J and never that value)
-            static_assert(CTXS == 17 && TAB_TAIL >= 1, "the z-score terms of a column from J on are read at sZP[CTXS - 1] and sZP[16 + CTXS - 1]");
+            static_assert(CTXS == 17 && TAB_TAIL >= 1 && CCSX_JMAX < 32, "the z-score terms of a column from J on are read at sZP[CTXS - 1] and sZP[16 + CTXS - 1]");
             const int k = wave ? rctx : fctx;
-            const float mu = sZP[k], va = sZP[16 + k];
+            const float t0 = sZP[k], t1 = sZP[16 + k];
+            const float mu = ll < J ? t0 : 0.0f, va = ll < J ? t1 : 0.0f;
             float M = 0.0f, V = 0.0f;
-            for (int q = 0; q < J; ++q) {
+#pragma unroll
+            for (int q = 0; q < CCSX_JMAX; ++q) {
                 M = M + __int_as_float(rl(__float_as_int(mu), q));
                 V = V + __int_as_float(rl(__float_as_int(va), q));
             }
@@ -3086,11 +3090,31 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         }
         ++iters;
         nvalid_last = nvalid; nvfull_last = nvfull;
+        // ---- the end of a round, behind ONE barrier.  Every wave loads the gains and validity bytes of all 256 mutation lanes, four per lane (entries lane + 64 k),
+        // and converts the gains in registers: whether any mutation is favourable is then the wave's own ballot — the same 256 words in every wave, nobody writes them
+        // between this barrier and the next, so the value is wave-uniform and identical in all four waves and every wave takes the exits below by itself.  The
+        // selection (wave 0) uses these registers; the QV step behind the loop loads the thread's own entry again.  Nothing is converted in place: sDeltaI stays
+        // integer until the next round's set-up zeroes it.  Who wrote each word last, who reads it next, which barrier lies between:
+        //   sDeltaI               zeroed by the round's set-up (own thread), summed by the scoring's atomicAdd, in front of this barrier; read here by every wave and, entry tid, behind the loop.  Next
+        //                         writer: the next round's set-up, behind the barrier that follows the selection and the round's top barrier
+        //   sMvalid               written by the round's set-up, in front of the chunk-opening barrier; read here by every wave and, entry tid, behind the loop (the QV step itself reads
+        //                         none: the terms of lanes that are not enumerated are stored as exact zeros).  Next writer: as sDeltaI
+        //   sGB[0 .. PWT-1]       gamma/beta of the round's last chunk, last read by the scoring in front of this barrier: dead behind it.  Written behind the loop by
+        //                         every thread (its own QV term), read by the core positions' threads behind the barrier in front of the QV step
+        //   sCtl[0 .. 3, 7],      written by the prologue or by wave 0's selection; read by every wave behind the barrier that follows the selection (sCtl[3]), behind the
+        //   sT[0], sPskip         round's top barrier (the set-up) or behind the barrier in front of the QV step.  While wave 0 selects, the other waves wait at the
+        //                         barrier behind the selection and read none of them: their last reads of the round (sT[1] is the scoring's) lie in front of this barrier
         __syncthreads();
-        float delta = 0.0f;
-        if (tid < 256) { delta = (float)sDeltaI[tid] * (1.0f / DQ_SCALE); sDelta[tid] = delta; }   // same slot, same thread
-        const int fav = (tid < 256 && sMvalid[tid] && delta > MUT_EPS) ? 1 : 0;
-        const int anyfav = __syncthreads_or(fav);
+        float dk[4];                                         // the lane's four gains
+        int candmask = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int m = lane + 64 * k;
+            const int mvk = sMvalid[m];
+            dk[k] = (float)sDeltaI[m] * (1.0f / DQ_SCALE);
+            if (mvk && dk[k] > MUT_EPS) candmask |= 1 << k;
+        }
+        const int anyfav = __ballot(candmask != 0) != 0ull;
 #ifdef CCSX_EXP_ONE_ROUND                                   // experiment (timing only): exactly one round per window whatever the gains say, so that variants which
         break;                                              // corrupt the gains (rows / logarithm compiled out) do not change the control flow they are compared under
 #endif
@@ -3098,10 +3122,6 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         if (it == CCSX_MAX_ITER - 1) { nonconv = 1; break; }
         // ---- A5: greedy selection (wave 0; lane l owns m = l, l+64, l+128, l+192 which share position l&31)
         if (wave == 0) {
-            int candmask = 0;
-            float dk[4];                                     // the lane's four gains stay in registers over the loop
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const int m = lane + 64 * k; dk[k] = sDelta[m]; if (sMvalid[m] && dk[k] > MUT_EPS) candmask |= 1 << k; }
             int Jn = J, nacc = 0;
             unsigned accpos = 0;                             // positions of the accepted mutations (at most one per position: they are >= MUT_SEP apart)
             int accm = 0;                                    // lane c (< 32): the mutation accepted at position c
@@ -3167,17 +3187,25 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         __syncthreads();
         if (sCtl[3] == 0) break;
     }
-    __syncthreads();
     PHASE(5);
     // ---- A6: QVs of the core positions from the last scoring round
+    // every mutation lane's term exp2(min(delta, 20)) is computed by the lane's own thread (all waves at once; the core threads below used to
+    // evaluate their 8 - 12 exponentials one after the other while three waves waited), then summed per position in the SPEC's order.  The terms go to the
+    // first PWT floats of the gamma/beta area, which nobody reads any more (see the table at the round's last barrier; ccsx_polish_lds guarantees the area
+    // holds that many): no barrier in front of the stores, unlike an image written in place over sDeltaI, which slower waves may still be reading.  A lane
+    // that is not enumerated stores an exact zero
+    {
+        const int vmine = sMvalid[tid];                      // (the thread's own lane, reloaded: held in registers since the round's end it costs a spill in the scoring loop)
+        float dv = (float)sDeltaI[tid] * (1.0f / DQ_SCALE);
+        if (dv > 20.0f) dv = 20.0f;
+#ifndef CCSX_EXP_NO_QV_EXP                                  // (experiment, timing only: the QV exponentials compiled out)
+        dv = det_exp2f(dv);
+#endif
+        sGB[tid] = vmine ? dv : 0.0f;
+    }
+    __syncthreads();
     const int J = sCtl[0], cs = sCtl[1], ce = sCtl[2];
     const size_t wi = (size_t)(P.wb_off[z] - z) + w;
-    // every mutation lane's term exp2(min(delta, 20)) is computed by the lane's own thread (all waves at once; the core threads below used to
-    // evaluate their 8 - 12 exponentials one after the other while three waves waited), then summed per position in the SPEC's order
-#ifndef CCSX_EXP_NO_QV_EXP                                  // (experiment, timing only: the QV exponentials compiled out)
-    if (tid < 256 && sMvalid[tid]) { float dv = sDelta[tid]; if (dv > 20.0f) dv = 20.0f; sDelta[tid] = det_exp2f(dv); }
-#endif
-    __syncthreads();
     // SPEC v7 "repeat-count floor": tandem tracts (period 1..4) of the converged template with its flanks, as wave masks (the core's threads sit in wave 0)
     unsigned long long tm1 = 0, tm2 = 0, tm3 = 0, tm4 = 0;
     const int voff = lf < 4 ? 1 : 0;
@@ -3204,13 +3232,13 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
             // non-negative finite s as it is (a chain of eight to twelve dependent load pairs before)
             const bool lastc = c == J - 1;                   // the insertions after the last column follow it
             const int ce_ = lastc ? J : c;
-            float dv[12]; bool mv[12];
+            float dv[12];                                    // (the terms: exact zeros where the lane is not enumerated)
 #pragma unroll
-            for (int sl = 0; sl < 8; ++sl) { const int m = sl * 32 + c; mv[sl] = sMvalid[m] != 0; dv[sl] = sDelta[m]; }
+            for (int sl = 0; sl < 8; ++sl) dv[sl] = sGB[sl * 32 + c];
 #pragma unroll
-            for (int sl = 4; sl < 8; ++sl) { const int m = sl * 32 + ce_; mv[sl + 4] = lastc && sMvalid[m] != 0; dv[sl + 4] = sDelta[m]; }
+            for (int sl = 4; sl < 8; ++sl) dv[sl + 4] = sGB[sl * 32 + ce_];
 #pragma unroll
-            for (int q = 0; q < 12; ++q) s = s + (mv[q] ? dv[q] : 0.0f);
+            for (int q = 0; q < 12; ++q) s = s + ((q < 8 || lastc) ? dv[q] : 0.0f);
             p = __fdiv_rn(s, 1.0f + s);
         }
         if (any_tract) {
@@ -3236,7 +3264,10 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     }
     if (wave == 0) {                                         // the core positions (<= 32) all sit in wave 0: ordered sum by v_readlane
         float wsum = 0.0f;
-        for (int k = 0; k < ce - cs; ++k) wsum = wsum + __int_as_float(rl(__float_as_int(pl), k));
+        // (32 steps with immediate lane indices, no loop: pl is + 0.0f in the lanes from ce - cs on, and x + 0.0f is x for every value the sum holds — it starts
+        // at + 0.0f and adds positive terms only)
+#pragma unroll
+        for (int k = 0; k < 32; ++k) wsum = wsum + __int_as_float(rl(__float_as_int(pl), k));
       if (tid == 0) {
         P.wsum[wi] = wsum;
         P.wmeta[wi] = make_int4(ce - cs, nvalid_last | (nvfull_last << 8), nonconv, iters);
@@ -4160,6 +4191,7 @@ int ccsx_polish_lds(int max_reads, int *obs_bytes, int *gb_floats)
     if (max_reads < 1) max_reads = 1;
     *obs_bytes = ((max_reads * 68) + 15) & ~15;
     *gb_floats = (PW_LDS_BYTES - static_bytes - *obs_bytes) / 4;
+    if (*gb_floats < PW_THREADS) return -1;                // (the kernel keeps a window's QV terms, one float per thread, at the head of the gamma/beta area)
     return 0;
 }
 
