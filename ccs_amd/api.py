@@ -1096,7 +1096,7 @@ EXPORTS = [
     "ccsx_pileup_rule_version", "ccsx_consensus_pileup", "ccsx_submit_pileup", "ccsx_stage_polished", "ccsx_stage_align_ev",
     "ccsx_poa_log", "ccsx_stage_poa", "ccsx_stage_wmeta",
     "ccsx_tandem_rule_version", "ccsx_consensus_extras", "ccsx_submit_extras",
-    "ccsx_consensus_hd", "ccsx_submit_hd",
+    "ccsx_consensus_hd", "ccsx_submit_hd", "ccsx_consensus_hd_requests", "ccsx_submit_hd_requests",
     "ccsx_fold_opts_default", "ccsx_fold_rule_version", "ccsx_consensus_fold", "ccsx_submit_fold",
     "ccsx_adapter_opts_default", "ccsx_adapter_rule_version", "ccsx_adapter_set_default", "ccsx_consensus_screen", "ccsx_submit_screen",
     "ccsx_control_opts_default", "ccsx_control_rule_version", "ccsx_consensus_control", "ccsx_submit_control",
@@ -1179,6 +1179,8 @@ def lib() -> C.CDLL:
         L.ccsx_submit_extras.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(C.c_int64)]
         L.ccsx_consensus_hd.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CHdRequest)]
         L.ccsx_submit_hd.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CHdRequest), C.POINTER(C.c_int64)]
+        L.ccsx_consensus_hd_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CHdRequest)]
+        L.ccsx_submit_hd_requests.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CHdRequest), C.POINTER(C.c_int64)]
         L.ccsx_fold_opts_default.restype = None
         L.ccsx_fold_opts_default.argtypes = [C.POINTER(FoldOpts)]
         L.ccsx_consensus_fold.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CExtras), C.POINTER(CFoldRequest)]
@@ -1616,10 +1618,13 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
               fold: "FoldReport | None" = None, fold_opts: "FoldOpts | None" = None,
               adapters: "AdapterReport | None" = None, adapter_set: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None,
               control: "ControlReport | None" = None, control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None,
-              coverage: "CoverageReport | None" = None, coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, via_requests: bool = False):
+              coverage: "CoverageReport | None" = None, coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, via_requests: bool = False,
+              hd_requests: bool = False):
     """The ctypes side of what one fused run is asked for beside the consensus: (CExtras, CHdRequest, CFoldRequest, CAdapterRequest, CControlRequest, keep), each
     request None where its report (for the extras: all of pileup, tandem and the threshold) is.  keep owns every array and struct the requests point to: it
-    must outlive the call, or the ticket.  With a coverage report, or via_requests, keep ends with the CRequests that carries them all (ccsx_*_requests)"""
+    must outlive the call, or the ticket.  With a coverage report, or via_requests, or a heteroduplex request beside a screen, keep ends with the CRequests
+    that carries every member but the heteroduplex request (ccsx_*_requests).  A heteroduplex request beside a CRequests is for ccsx_*_hd_requests, which takes
+    it as a further argument: the caller says so with hd_requests=True (Handle._fused then picks that entry point); without it the combination is refused"""
     keep = [pileup, tandem, hd, fold, adapters, control, coverage]
 
     def own(x):
@@ -1637,9 +1642,9 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
         aq = own(_adapter_request(adapter_set, adapter_opts, own(adapters.c_struct())))[0]
     if control is not None:
         cq = own(_control_request(control_seq, control_opts, own(control.c_struct())))[0]
-    if coverage is not None or via_requests:
-        if hq is not None:
-            raise ValueError("the heteroduplex request goes through ccsx_*_hd, not through ccsx_requests")
+    if coverage is not None or via_requests or (hq is not None and (fq is not None or aq is not None or cq is not None)):
+        if hq is not None and not hd_requests:
+            raise ValueError("the heteroduplex request goes beside ccsx_requests, through ccsx_*_hd_requests (hd_requests=True), not inside it")
         vq = own(_coverage_request(coverage_opts, coverage_gate, own(coverage.c_struct())))[0] if coverage is not None else None
 
         def p(x):
@@ -1669,15 +1674,15 @@ class Handle:
 
     def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None, represent=None):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
-        ccsx_*_hd with a heteroduplex request, which combines with none of the screens, ccsx_*_requests when _requests made a CRequests (a coverage request,
-        or via_requests), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
+        ccsx_*_hd with a heteroduplex request and nothing but extras, ccsx_*_requests when _requests made a CRequests (a coverage request, or
+        via_requests; ccsx_*_hd_requests when a heteroduplex request goes with it), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
         structs join the requests' keep list.  barcodes: (report, set, opts), through ccsx_*_barcodes in the same way (not together with a hand-off).
         represent: (report, subread_fallback, kinetics), through ccsx_*_represent in the same way (not together with a hand-off or barcodes).  Returns the C
         structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
-            name, args = f"ccsx_{form}_requests", (_keep[-1],)
+            name, args = (f"ccsx_{form}_hd_requests", (_keep[-1], hq)) if hq is not None else (f"ccsx_{form}_requests", (_keep[-1],))
         if handoff is not None:
             if name != f"ccsx_{form}_requests":
                 raise ValueError("the hand-off goes with the members of ccsx_requests (not with the heteroduplex request)")
@@ -1790,6 +1795,29 @@ class Handle:
         rep = HdReport.allocate(batch.n_zmw)
         self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length, hd=rep, hd_opts=opts, hd_split=split))
         return res, rep, tl, pile
+
+    # ---- the finder beside the other requests (ccsx_consensus_hd_requests): one run with the finder and any of the screens
+    def consensus_hd_requests(self, batch: Batch, opts: HdOpts | None = None, split: bool = False, coverage: "bool | CoverageOpts" = False, gate: int = 0,
+                              control: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None, fold: "bool | FoldOpts" = False,
+                              adapters: "AdapterSet | None" = None, adapter_opts: "AdapterOpts | None" = None, tandem: bool = False,
+                              min_tandem_repeat_length: int = 0, pileup: bool = False, via_requests: bool = True):
+        """(results, hd report, coverage report or None, control report or None, fold report or None, adapter report or None, tandem_len or None, pileup or
+        None).  opts / split as consensus_hd; coverage: True or a CoverageOpts asks for the coverage screen, gate its gate; the other arguments as
+        consensus_coverage.  The coverage gate gives its statuses before the finder's split does (include/ccsx.h).  via_requests=False: through
+        ccsx_consensus_hd when nothing but extras goes with the finder"""
+        res, tl, pile = self._outputs(batch, tandem, pileup)
+        rep = HdReport.allocate(batch.n_zmw)
+        vrep = CoverageReport.allocate(batch.n_zmw) if coverage else None
+        crep = ControlReport.allocate(batch.n_zmw) if control is not None else None
+        frep = FoldReport.allocate(batch.n_zmw) if fold else None
+        arep = AdapterReport.allocate(batch.n_zmw) if adapters is not None else None
+        self._fused("consensus", batch, res, _requests(pile, tl, min_tandem_repeat_length, hd=rep, hd_opts=opts, hd_split=split,
+                                                       fold=frep, fold_opts=fold if isinstance(fold, FoldOpts) else None,
+                                                       adapters=arep, adapter_set=adapters, adapter_opts=adapter_opts,
+                                                       control=crep, control_seq=control, control_opts=control_opts,
+                                                       coverage=vrep, coverage_opts=coverage if isinstance(coverage, CoverageOpts) else None,
+                                                       coverage_gate=gate, via_requests=via_requests, hd_requests=True))
+        return res, rep, vrep, crep, frep, arep, tl, pile
 
     # ---- adapter palindromes in the fused path (ccsx_consensus_fold): the consensus and the detector's report of one run (detection only)
     def consensus_fold(self, batch: Batch, opts: FoldOpts | None = None) -> tuple["Results", FoldReport]:
@@ -1959,13 +1987,14 @@ class Handle:
                represent: "RepresentReport | None" = None, represent_fallback: bool = False, represent_kinetics: bool = False) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
-        receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd).  fold: a report
+        receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd; with fold, adapters, control
+        or coverage in the same call: ccsx_submit_hd_requests, include/ccsx.h has the order in which the coverage gate and the split give a status).  fold: a report
         (FoldReport.allocate(n, pinned=True)) that receives the adapter-palindrome verdicts.  adapters: a report (AdapterReport.allocate(n, pinned=True))
         that receives the adapter screen of adapter_set (None: the built-in set) under adapter_opts.  control: a report (ControlReport.allocate(n,
         pinned=True)) that receives the control screen for control_seq under control_opts.  fold, adapters and control go alone or together
-        (ccsx_submit_control), none of them with hd.  Every ticket carries its own control: tickets in flight may screen for different ones.  coverage: a
+        (ccsx_submit_control).  Every ticket carries its own control: tickets in flight may screen for different ones.  coverage: a
         report (CoverageReport.allocate(n, pinned=True)) that receives the coverage screen under coverage_opts and coverage_gate (ccsx_submit_requests; with or
-        without the other screens, not with hd); every ticket carries its own options and gate.  handoff: a Handoff (Handoff.allocate(batch, max_tiles, opts,
+        without the other screens); every ticket carries its own options and gate.  handoff: a Handoff (Handoff.allocate(batch, max_tiles, opts,
         pinned=True) or device=) that receives the polisher hand-off (ccsx_submit_handoff; not with hd): the whole capacity of its arrays is copied, complete
         when the ticket is; every ticket carries its own options and capacity.  barcodes: a report (BarcodeReport.allocate(n, pinned=True)) that receives the
         barcode calls for barcode_set under barcode_opts (ccsx_submit_barcodes; not with hd or handoff); every ticket carries its own set and options.  represent: a report
@@ -1974,16 +2003,8 @@ class Handle:
         coverage gate)"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
-        if hd is not None and fold is not None:
-            raise ValueError("the heteroduplex and the adapter-palindrome requests are not combined")
-        if hd is not None and adapters is not None:
-            raise ValueError("the heteroduplex request and the adapter screen are not combined")
-        if control is not None and hd is not None:
-            raise ValueError("the heteroduplex request and the control screen are not combined")
         if control is not None and control_seq is None:
             raise ValueError("control: a control_seq is needed (there is no built-in control)")
-        if coverage is not None and hd is not None:
-            raise ValueError("the heteroduplex request and the coverage screen are not combined")
         if handoff is not None and hd is not None:
             raise ValueError("the heteroduplex request and the hand-off are not combined")
         if barcodes is not None and (hd is not None or handoff is not None):
@@ -1992,7 +2013,7 @@ class Handle:
             raise ValueError("the represent request is not combined with the heteroduplex request, the hand-off or the barcode request")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
                              control, control_seq, control_opts, coverage, coverage_opts, coverage_gate,
-                             via_requests=handoff is not None or barcodes is not None or represent is not None)
+                             via_requests=handoff is not None or barcodes is not None or represent is not None, hd_requests=True)
         t = C.c_int64()
         cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff,
                              barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None,
@@ -2156,10 +2177,33 @@ def consensus_hd(handle: "Handle", batch: Batch, opts: HdOpts | None = None):
     return recs, rep
 
 
-def consensus_hd_stream(handle: "Handle", batches, opts: HdOpts | None = None):
+def _stream_requests(b: Batch, res: "Results", fold=False, adapter_set=None, adapter_opts=None, control_seq=None, control_opts=None, coverage=False,
+                     coverage_gate=0, pileup=False, tandem=False, min_tandem_repeat_length=0) -> dict:
+    """Handle.submit's keywords for one ticket of consensus_hd_stream: the requests as the stream was given them, with page-locked reports of this batch's size"""
+    n, kw = b.n_zmw, dict(min_tandem_repeat_length=min_tandem_repeat_length)
+    if pileup:
+        kw["pileup"] = Pileup.allocate(res, pinned=True)
+    if tandem:
+        kw["tandem"] = tandem_buffer(n, pinned=True)
+    if fold:
+        kw.update(fold=FoldReport.allocate(n, pinned=True), fold_opts=fold if isinstance(fold, FoldOpts) else None)
+    if adapter_set is not None:
+        kw.update(adapters=AdapterReport.allocate(n, pinned=True), adapter_set=adapter_set, adapter_opts=adapter_opts)
+    if control_seq is not None:
+        kw.update(control=ControlReport.allocate(n, pinned=True), control_seq=control_seq, control_opts=control_opts)
+    if coverage:
+        kw.update(coverage=CoverageReport.allocate(n, pinned=True), coverage_opts=coverage if isinstance(coverage, CoverageOpts) else None,
+                  coverage_gate=coverage_gate)
+    return kw
+
+
+def consensus_hd_stream(handle: "Handle", batches, opts: HdOpts | None = None, tickets_out: "list | None" = None, **requests):
     """the heteroduplex mode, pipelined: every batch goes through ONE ticket with the finder and the split (ccsx_submit_hd, split = 1), and when that ticket
     is retired its HETERODUPLEX ZMWs become a single-strand batch (split_strands) for an ordinary ticket.  At most three tickets are in flight (the handle's
-    slots); yields (records, report) per input batch, in input order, with exactly the records consensus_hd gives."""
+    slots); yields (records, report) per input batch, in input order, with exactly the records consensus_hd gives.
+    requests: fold= (True or a FoldOpts), adapter_set= / adapter_opts=, control_seq= / control_opts=, coverage= (True or a CoverageOpts) / coverage_gate=,
+    pileup=, tandem=, min_tandem_repeat_length= go into every ticket (ccsx_submit_hd_requests); the strand ticket carries the same requests without the finder.
+    tickets_out: a list that receives (input index, "hd" or "strand", batch, results, Handle.submit's keywords with the reports) per retired ticket."""
     from collections import deque
     inflight = deque()                 # (ticket, input index, kind): retired oldest first, so the in-flight tickets are always the latest submitted
     state, done, nxt = {}, {}, 0
@@ -2186,6 +2230,9 @@ def consensus_hd_stream(handle: "Handle", batches, opts: HdOpts | None = None):
         t, i, kind = inflight.popleft()
         handle.wait(t)
         handle.release(t)
+        if tickets_out is not None:
+            st = state[i]
+            tickets_out.append((i, kind, st["sb"], st["sres"], st["skw"]) if kind == "strand" else (i, kind, st["batch"], st["res"], st["kw"]))
         if kind == "strand":
             st = state[i]
             finish(i, st["sres"], st["src"], st["strand"])
@@ -2196,16 +2243,18 @@ def consensus_hd_stream(handle: "Handle", batches, opts: HdOpts | None = None):
             return
         sb, src, strand = split_strands(state[i]["batch"], het)
         sres = Results.allocate(sb, kinetics=bool(handle.opts.hifi_kinetics), pinned=True)
-        state[i].update(sres=sres, src=src, strand=strand)
-        inflight.append((handle.submit(sb, sres), i, "strand"))      # (one ticket was just retired: at most three in flight)
+        skw = _stream_requests(sb, sres, **requests)
+        state[i].update(sb=sb, sres=sres, src=src, strand=strand, skw=skw)
+        inflight.append((handle.submit(sb, sres, **skw), i, "strand"))      # (one ticket was just retired: at most three in flight)
 
     for i, b in enumerate(batches):
         while len(inflight) >= 3:
             retire_oldest()
         res = Results.allocate(b, kinetics=bool(handle.opts.hifi_kinetics), pinned=True)
         rep = HdReport.allocate(b.n_zmw, pinned=True)
-        state[i] = dict(batch=b, res=res, rep=rep)
-        inflight.append((handle.submit(b, res, hd=rep, hd_opts=opts, hd_split=True), i, "hd"))
+        kw = _stream_requests(b, res, **requests)
+        state[i] = dict(batch=b, res=res, rep=rep, kw=kw)
+        inflight.append((handle.submit(b, res, hd=rep, hd_opts=opts, hd_split=True, **kw), i, "hd"))
         while nxt in done:
             yield done.pop(nxt)
             nxt += 1

@@ -97,6 +97,8 @@ struct Options {
     bool reads_kinetics = false;  // --reads-bam-kinetics: --hifi-kinetics for the polished reads, fi / fp of the pass for the unaltered subreads (--all-kinetics)
     bool reads_fallback = false;  // --reads-bam-subread-fallback: a subread where an unpolished draft would be written (--subread-fallback)
     bool min_passes_set = false, min_rq_set = false, max_length_set = false;   // given on the command line (--reads-bam fixes them)
+    int heteroduplexes = 0;       // --heteroduplexes split|drop: the finder in every ticket with the split (DESIGN.md §2 "Heteroduplex rule").  HD_SPLIT: a heteroduplex
+                                  // ZMW is written as up to two single-strand reads (the reference's --hd-finder); HD_DROP: it yields no read (how-does-ccs-work.md:65-72)
     std::string fit_model;        // --fit-model OUT.json: the training mode (DESIGN.md §2 "Model training"): no consensus output
     int fit_iterations = 3;       // --fit-iterations: EM iterations over the file
     double fit_min_rq = 0.999;    // --fit-min-rq: a polished consensus is a truth to measure passes against from this predicted accuracy on
@@ -104,6 +106,7 @@ struct Options {
     int fit_degree = -1;          // --fit-degree: polynomial degree of the transition weights (-1: the fitter's default)
 };
 
+enum HdMode { HD_OFF = 0, HD_SPLIT = 1, HD_DROP = 2 };
 enum HostStatus { HS_OK = 0, HS_POOR_SNR = 100, HS_NO_SUBREADS = 101, HS_TOO_FEW = 102, HS_TOO_LONG = 103, HS_ADAPTER_PALINDROME = 104, HS_ADAPTER_CONCAT = 105,
                   HS_ADAPTER_NEAR_END = 106, HS_CONTROL_SUCCESS = 107, HS_CONTROL_FAILURE = 108 };
 
@@ -173,7 +176,13 @@ struct Batch {
     ccsx_coverage_report vrep{}; ccsx_coverage_request vreq{}; // --coverage-filters (ccsx_coverage_request: the report's arrays are in out_arena)
     ccsx_barcode_report brep{}; ccsx_barcode_request breq{};   // --barcodes (ccsx_barcode_request: the report's arrays are in out_arena)
     ccsx_represent_report rrep{}; ccsx_represent_request rreq{};   // --reads-bam (ccsx_represent_request: the report's arrays are in out_arena)
+    ccsx_hd_report hrep{}; ccsx_hd_request hreq{};   // --heteroduplexes (ccsx_hd_request: the report's arrays are in out_arena)
     ccsx_requests reqs{};           // (read during the call only)
+    // --heteroduplexes split: the single-strand batch made of this batch's HETERODUPLEX ZMWs (the GPU worker builds it when the ticket retires), and per SoA
+    // slot s its two entities there: strand_slot[2 s] the forward strand's, strand_slot[2 s + 1] the reverse strand's, -1 = no such entity
+    std::shared_ptr<Batch> strand;
+    std::vector<int> strand_slot;
+    Batch *parent = nullptr;        // of a single-strand batch: the batch that goes to the writer when this one's ticket has retired
 };
 
 template <class T> class Channel {
@@ -224,6 +233,12 @@ void usage()
                  "      --min-rq F            minimum predicted accuracy [0.99]\n"
                  "      --maxPoaCoverage N    subreads used for the draft [5]\n"
                  "      --by-strand           one consensus per strand, read names end in /fwd or /rev\n"
+                 "      --heteroduplexes split|drop  run the heteroduplex finder on every draft (strand-biased substitutions, insertions / deletions of more\n"
+                 "                            than 20 bases on one strand).  split: such a ZMW is written as up to two single-strand reads named /fwd and /rev, each\n"
+                 "                            polished from its own strand's passes, in read groups of their own; ccs_report.txt gets a double-strand and a\n"
+                 "                            single-strand column; with --fail-reads the single-strand reads go to F.bam with ff 0x4.  drop: such a ZMW yields\n"
+                 "                            no read and is counted as 'Heteroduplex insertions'.  Not with --by-strand, --reads-bam, --barcodes, --fit-model,\n"
+                 "                            --orient-passes [off]\n"
                  "      --orient-passes       the engine determines the strand of every subread whose cx tag carries no direction bit, against the ZMW's\n"
                  "                            subread closest to the median length; alternation is then only a prior for passes it cannot call [off]\n"
                  "      --no-partial-passes   do not use the first / last (one-adapter) subread of a ZMW in the polish\n"
@@ -233,7 +248,8 @@ void usage()
                  "      --min-tandem-repeat-length N  a ZMW whose draft holds a tandem repeat (sDUST) of >= N bases runs with --disable-heuristics\n"
                  "                            for itself only; N > 0 [off: the reference's default is 1000]\n"
                  "      --fail-reads F.bam    also write one read per ZMW that yields no HiFi read, with the ff tag: 0x1 below --min-rq, 0x20 adapter\n"
-                 "                            palindrome (such reads leave the main output), 0x8 the median full-length subread of a ZMW without a consensus\n"
+                 "                            palindrome (such reads leave the main output), 0x8 the median full-length subread of a ZMW without a consensus,\n"
+                 "                            0x4 a single-strand read (--heteroduplexes split)\n"
                  "      --adapters F|default  with --fail-reads: screen every draft for the adapters of FASTA file F (up to 8 records of 16-64 bases) or for the\n"
                  "                            built-in SMRTbell adapter; reads made of adapter copies (ff 0x10) or with an adapter close to an end (ff 0x40)\n"
                  "                            leave the main output for F.bam [off]\n"
@@ -455,6 +471,11 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--reads-bam-kinetics") o.reads_kinetics = true;
         else if (a == "--reads-bam-subread-fallback") o.reads_fallback = true;
         else if (a == "--orient-passes") o.orient_passes = true;
+        else if (a == "--heteroduplexes") {
+            const std::string v = need(a.c_str());
+            o.heteroduplexes = v == "split" ? HD_SPLIT : (v == "drop" ? HD_DROP : HD_OFF);
+            if (!o.heteroduplexes) { std::fprintf(stderr, "ccs: --heteroduplexes needs 'split' or 'drop', got '%s'\n", v.c_str()); std::exit(2); }
+        }
         else if (a == "--coverage-drop-percent" || a == "--coverage-block") {
             const bool pct = a == "--coverage-drop-percent";
             const std::string v = need(a.c_str());
@@ -484,6 +505,14 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if (o.heteroduplexes) {                                  // its own output mode: the options that make another kind of record, or that need the strands on the host
+        auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --heteroduplexes combined with %s is not supported\n", what); std::exit(2); };
+        if (o.by_strand) refuse("--by-strand");
+        if (o.reads_bam) refuse("--reads-bam");
+        if (!o.barcodes.empty()) refuse("--barcodes");
+        if (!o.fit_model.empty()) refuse("--fit-model");
+        if (o.orient_passes) refuse("--orient-passes");      // (the host would need the strand bits the device resolved to split a ZMW's passes)
     }
     if ((o.reads_kinetics || o.reads_fallback) && !o.reads_bam) {
         std::fprintf(stderr, "ccs: --reads-bam-kinetics and --reads-bam-subread-fallback need --reads-bam\n"); std::exit(2);
@@ -810,6 +839,13 @@ struct Report {
     int64_t coverage = 0;         // ZMWs the coverage screen's gate took (--coverage-filters)
     int64_t bc_tested = 0, bc_call[4] = {0, 0, 0, 0};           // --barcodes: HiFi reads tested, and by call: none, head only, tail only, both ends
     std::map<std::pair<int, int>, int64_t> bc_pairs;              // ... reads per called pair (head, tail)
+    int64_t hd_zmws = 0;          // --heteroduplexes: ZMWs the split took (split: written as single-strand reads; drop: the "Heteroduplex insertions" row)
+    // --heteroduplexes split: the single-strand column of the report.  It counts reads, not ZMWs (mode-heteroduplex-filtering.md:86-90); `input`, `pass`, `fail`
+    // and `tandem` above are then the double-strand column plus hd_zmws in `input`
+    int64_t ss_input = 0, ss_pass = 0, ss_tandem = 0;
+    std::map<std::string, int64_t> ss_fail;
+    std::vector<uint8_t> ss;      // per written read, beside lens / rqs / nps: 1 = a single-strand read
+    std::vector<int32_t> holes;   // ... and its ZMW
 };
 
 // cov: --coverage-filters.  Under it "Reads failed polishing" counts what the reference counts there, the reads lost while polishing; the engine's "more than
@@ -821,6 +857,7 @@ const char *fail_label(int st, bool cov = false)
         case CCSX_INSUFFICIENT_SPANS: return "Insufficient draft cov";
         case CCSX_DRAFT_TOO_DIFFERENT: return "Draft too different";
         case CCSX_READS_FAILED_POLISHING: return "Reads failed polishing";
+        case CCSX_HETERODUPLEX: return "Heteroduplex insertions";
         case HS_POOR_SNR: return "Below SNR threshold";
         case HS_NO_SUBREADS: return "Median length filter";
         case HS_TOO_FEW: case CCSX_TOO_FEW_PASSES: return "Lacking full passes";
@@ -848,6 +885,7 @@ const char *status_name(int st, bool cov = false)
         case CCSX_INSUFFICIENT_SPANS: return "INSUFFICIENT_SPANS";
         case CCSX_DRAFT_TOO_DIFFERENT: return "TOO_FEW_PASSES_AFTER_DRAFT_ALIGNMENT";
         case CCSX_READS_FAILED_POLISHING: return "TOO_MANY_UNUSABLE";
+        case CCSX_HETERODUPLEX: return "HETERODUPLEXES";
         case CCSX_SUCCESS: return "SUCCESS";
         case HS_POOR_SNR: return "POOR_SNR";
         case HS_NO_SUBREADS: return "NO_SUBREADS";
@@ -870,7 +908,7 @@ const char *status_name(int st, bool cov = false)
 }
 
 // the rows of "Exclusive failed counts" this path can produce, in the order of docs/faq/reports-aux-files.md:24-46 (the rows of the subsystems
-// outside this path — heteroduplex, and without their options the coverage, adapter and control classes — cannot occur and are not listed)
+// outside this path, and without their options the heteroduplex, coverage, adapter and control classes, cannot occur and are not listed)
 const char *const kFailOrder[] = {"Below SNR threshold", "Median length filter", "Lacking full passes", "Draft generation error",
                                   "Draft above --max-length", "Draft below --min-length", "Reads failed polishing", "Empty coverage windows",
                                   "CCS did not converge", "CCS below minimum RQ", "Consensus outgrew its buffer", "Unknown error"};
@@ -888,6 +926,7 @@ std::vector<const char *> fail_order(const Options &o)
         }
         if (!o.control.empty() && std::string(k) == "CCS below minimum RQ") { v.push_back("ZMW with control failure"); v.push_back("ZMW with control success"); }
         v.push_back(k);
+        if (o.heteroduplexes == HD_DROP && std::string(k) == "Lacking full passes") v.push_back("Heteroduplex insertions");   // (where the reference lists it)
         if (o.coverage_filters && std::string(k) == "Lacking full passes") { v.push_back("Coverage drops"); v.push_back("Insufficient draft cov"); v.push_back("Draft too different"); }
     }
     return v;
@@ -934,6 +973,28 @@ void write_report(const Options &o, const Report &r)
     int64_t all_bases = 0;
     for (int32_t l : r.lens) all_bases += l;
     if (FILE *f = std::fopen(o.report.c_str(), "w")) {
+        if (o.heteroduplexes == HD_SPLIT) {
+            // the two columns of mode-heteroduplex-filtering.md:92-117: reads, not ZMWs.  Inputs: of the ZMWs; every other percentage: of its column's Inputs
+            // (Passed, Failed, Tandem repeats) or of its column's Failed (the exclusive counts).  Rows, labels and order are this driver's
+            const int64_t ds_in = r.input - r.hd_zmws, ds_fail = ds_in - r.pass, ss_failed = r.ss_input - r.ss_pass;
+            auto row2 = [&](const char *label, int64_t a, double pa, int64_t b, double pb) {
+                std::fprintf(f, "%-30s: %10" PRId64 " (%6.2f%%) %11" PRId64 " (%6.2f%%)\n", label, a, pa, b, pb);
+            };
+            std::fprintf(f, "%-30s  %20s %20s\n", "", "Double-Strand Reads", "Single-Strand Reads");
+            row2("Inputs", ds_in, pct(ds_in, r.input), r.ss_input, pct(r.ss_input, r.input));
+            std::fprintf(f, "\n");
+            row2("Passed", r.pass, pct(r.pass, ds_in), r.ss_pass, pct(r.ss_pass, r.ss_input));
+            row2("Failed", ds_fail, pct(ds_fail, ds_in), ss_failed, pct(ss_failed, r.ss_input));
+            std::fprintf(f, "\n");
+            if (o.min_tandem > 0) { row2("Tandem repeats", r.tandem, pct(r.tandem, ds_in), r.ss_tandem, pct(r.ss_tandem, r.ss_input)); std::fprintf(f, "\n"); }
+            std::fprintf(f, "Exclusive failed counts\n");
+            for (const char *k : fail_order(o)) {
+                auto a = r.fail.find(k), b = r.ss_fail.find(k);
+                const int64_t ca = a == r.fail.end() ? 0 : a->second, cb = b == r.ss_fail.end() ? 0 : b->second;
+                if (ca == 0 && cb == 0 && std::string(k) == "Consensus outgrew its buffer") continue;
+                row2(k, ca, pct(ca, ds_fail), cb, pct(cb, ss_failed));
+            }
+        } else {
         std::fprintf(f, "ZMWs input                    : %" PRId64 "\n\n", r.input);
         std::fprintf(f, "ZMWs pass filters             : %" PRId64 " (%.2f%%)\n", r.pass, pct(r.pass, r.input));
         std::fprintf(f, "ZMWs fail filters             : %" PRId64 " (%.2f%%)\n", failed, pct(failed, r.input));
@@ -959,6 +1020,7 @@ void write_report(const Options &o, const Report &r)
             const int64_t c = it == r.fail.end() ? 0 : it->second;
             if (c == 0 && std::string(k) == "Consensus outgrew its buffer") continue;      // (not a row of the reference: shown only when it happened)
             std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", k, c, pct(c, failed));
+        }
         }
         std::fprintf(f, "\n- - - - - - - - - - - - - - - : - - - - -\n\n");
         std::fprintf(f, "HiFi Reads                    : %s\n", with_commas(hifi.reads).c_str());
@@ -999,6 +1061,20 @@ void write_report_json(const Options &o, const Report &r)
     if (o.reads_bam)
         std::fprintf(f, "  \"representative_reads\": {\"polished\": %" PRId64 ", \"draft\": %" PRId64 ", \"subread\": %" PRId64 "},\n",
                      r.rep_cls[CCSX_REPRESENT_POLISHED], r.rep_cls[CCSX_REPRESENT_DRAFT], r.rep_cls[CCSX_REPRESENT_SUBREAD]);
+    if (o.heteroduplexes == HD_SPLIT) {                       // the two columns of ccs_report.txt: reads, not ZMWs (zmws_pass_filters / zmws_fail_filters count ZMWs)
+        const int64_t ds_in = r.input - r.hd_zmws;
+        std::fprintf(f, "  \"double_strand_reads\": {\"inputs\": %" PRId64 ", \"passed\": %" PRId64 ", \"failed\": %" PRId64 ", \"tandem_repeats\": %" PRId64 "},\n",
+                     ds_in, r.pass, ds_in - r.pass, r.tandem);
+        std::fprintf(f, "  \"single_strand_reads\": {\"inputs\": %" PRId64 ", \"passed\": %" PRId64 ", \"failed\": %" PRId64 ", \"tandem_repeats\": %" PRId64
+                        ", \"exclusive_failed_counts\": {", r.ss_input, r.ss_pass, r.ss_input - r.ss_pass, r.ss_tandem);
+        bool first_ss = true;
+        for (const char *k : fail_order(o)) {
+            auto it = r.ss_fail.find(k);
+            std::fprintf(f, "%s\"%s\": %" PRId64, first_ss ? "" : ", ", k, it == r.ss_fail.end() ? (int64_t)0 : it->second);
+            first_ss = false;
+        }
+        std::fprintf(f, "}},\n");
+    }
     std::fprintf(f, "  \"exclusive_failed_counts\": {");
     bool first = true;
     for (const char *k : fail_order(o)) {
@@ -1517,6 +1593,82 @@ int main(int argc, char **argv)
         const bool control = !opt.control.empty();
         const bool coverage = opt.coverage_filters;
         const bool barcodes = !opt.barcodes.empty();
+        // The views of a staged batch's results and reports, carved from a page-locked arena of its device's pool, and the requests that point to them: every
+        // ticket of the run is given the same (finder: plus the heteroduplex request, which the single-strand tickets of --heteroduplexes split do not carry)
+        static_assert(sizeof(ccsx_hd_site) == 24, "the finder's site list is carved as 96 words per ZMW");
+        auto carve_outputs = [&](const std::shared_ptr<Batch> &b, ArenaPool &out_pool, bool finder) {
+            const int n = b->n;
+            b->seq_off.resize(n + 1);
+            const int64_t cap = ccsx_result_layout(&b->cb, b->seq_off.data());
+            b->cap = cap;
+            b->out_arena = out_pool.get();
+            const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
+            uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (opt.reads_bam ? 2 : 0) + (finder ? 103 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+            auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
+            auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
+            b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
+            b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
+            b->rq = (float *)take(n4); b->ec = (float *)take(n4);
+            b->seq = take(c1); b->qual = take(c1);
+            b->cr = ccsx_results{n, cap, b->seq_off.data(), b->status, b->seq_len, b->seq, b->qual, nullptr, b->rq, b->np, b->ec, b->iters, b->n_windows};
+            b->cr.fn = b->fn; b->cr.rn = b->rn;
+            if (kin) {
+                b->kin = take(4 * c1);
+                // planes are cap bytes apart in the library's result layout
+                b->cr.fi = b->kin; b->cr.fp = b->kin + cap; b->cr.ri = b->kin + 2 * cap; b->cr.rp = b->kin + 3 * cap;
+            }
+            if (opt.pileup) {
+                b->pile = take(3 * c1);
+                b->cp = ccsx_pileup{cap, b->pile, b->pile + cap, b->pile + 2 * cap};
+            }
+            if (opt.min_tandem > 0) {
+                b->tlen = (int32_t *)take(n4);
+                b->ex = ccsx_extras{opt.pileup ? &b->cp : nullptr, b->tlen, opt.min_tandem, 0};
+            } else if (opt.pileup) b->ex = ccsx_extras{&b->cp, nullptr, 0, 0};
+            if (fail_reads) {
+                const auto f = planes(4);
+                b->fold = f[0];
+                b->frep = ccsx_fold_report{n, f[0], f[1], f[2], f[3]};
+                b->freq = ccsx_fold_request{nullptr, &b->frep, {0, 0}};
+            }
+            if (screen) {
+                const auto a9 = planes(9);
+                ccsx_adapter_hit *hits = (ccsx_adapter_hit *)take(3 * CCSX_ADAPTER_MAX_HITS * n4);
+                b->arep = ccsx_adapter_report{n, a9[0], a9[1], a9[2], a9[3], a9[4], a9[5], a9[6], a9[7], a9[8], hits};
+                b->areq = ccsx_adapter_request{&opt.adapter_set, nullptr, &b->arep, {0, 0}};
+            }
+            if (control) {
+                const auto c8 = planes(8);
+                b->crep = ccsx_control_report{n, c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]};
+                b->creq = ccsx_control_request{&opt.control_seq, nullptr, &b->crep, {0, 0}};
+            }
+            if (coverage) {
+                const auto v = planes(10);
+                b->vrep = ccsx_coverage_report{n, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]};
+                b->vreq = ccsx_coverage_request{&opt.coverage_opts, &b->vrep, 0x3cu, {0, 0}};   // all four gate bits
+            }
+            if (barcodes) {                          // tested, call, bq: n each; idx, dist, second, clip: [n][2]
+                const auto b3 = planes(3);
+                int32_t *two[4];
+                for (auto &q : two) q = (int32_t *)take(2 * n4);
+                b->brep = ccsx_barcode_report{n, b3[0], b3[1], b3[2], two[0], two[1], two[2], two[3]};
+                b->breq = ccsx_barcode_request{&opt.barcode_opts, opt.barcode_set.get(), &b->brep, {0, 0}};
+            }
+            if (opt.reads_bam) {
+                const auto r2 = planes(2);
+                b->rrep = ccsx_represent_report{n, r2[0], r2[1]};
+                b->rreq = ccsx_represent_request{opt.reads_fallback ? 1 : 0, opt.reads_kinetics ? 1 : 0, &b->rrep, {0, 0}};
+            }
+            if (finder) {                                // verdict, n_sub_sites, n_indel_sites, n_listed, status: n each; min_p: n doubles; sites: [n][16] of 24 bytes
+                const auto h5 = planes(5);
+                double *min_p = (double *)take(2 * n4);
+                ccsx_hd_site *sites = (ccsx_hd_site *)take(96 * n4);
+                b->hrep = ccsx_hd_report{n, h5[0], h5[1], h5[2], h5[3], min_p, sites, h5[4]};
+                b->hreq = ccsx_hd_request{nullptr, &b->hrep, 1, 0};   // ccsx_hd_opts_default, split = 1
+            }
+            b->reqs = ccsx_requests{(opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr,
+                                  control ? &b->creq : nullptr, coverage ? &b->vreq : nullptr, {nullptr, nullptr, nullptr}};
+        };
         std::vector<std::thread> packers;
         const size_t n_packers = std::max<size_t>(1, handles.size()) * (size_t)opt.workers_per_gpu;
         std::vector<std::atomic<int>> packers_left(ndev_q);
@@ -1538,69 +1690,7 @@ int main(int argc, char **argv)
                     if (n > 0 && !opt.host_only) {
                         b->cb = ccsx_batch{n, (int32_t)b->flags.size(), b->n_bases, b->zmw_id.data(), b->snr.data(), b->read_off.data(),
                                            b->base_off.data(), b->bases, b->pw, b->ipd, b->flags.data()};
-                        b->seq_off.resize(n + 1);
-                        const int64_t cap = ccsx_result_layout(&b->cb, b->seq_off.data());
-                        b->cap = cap;
-                        b->out_arena = out_pool.get();
-                        const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-                        uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (opt.reads_bam ? 2 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
-                        auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
-                        auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
-                        b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
-                        b->n_windows = (int32_t *)take(n4); b->fn = (int32_t *)take(n4); b->rn = (int32_t *)take(n4);
-                        b->rq = (float *)take(n4); b->ec = (float *)take(n4);
-                        b->seq = take(c1); b->qual = take(c1);
-                        b->cr = ccsx_results{n, cap, b->seq_off.data(), b->status, b->seq_len, b->seq, b->qual, nullptr, b->rq, b->np, b->ec, b->iters, b->n_windows};
-                        b->cr.fn = b->fn; b->cr.rn = b->rn;
-                        if (kin) {
-                            b->kin = take(4 * c1);
-                            // planes are cap bytes apart in the library's result layout
-                            b->cr.fi = b->kin; b->cr.fp = b->kin + cap; b->cr.ri = b->kin + 2 * cap; b->cr.rp = b->kin + 3 * cap;
-                        }
-                        if (opt.pileup) {
-                            b->pile = take(3 * c1);
-                            b->cp = ccsx_pileup{cap, b->pile, b->pile + cap, b->pile + 2 * cap};
-                        }
-                        if (opt.min_tandem > 0) {
-                            b->tlen = (int32_t *)take(n4);
-                            b->ex = ccsx_extras{opt.pileup ? &b->cp : nullptr, b->tlen, opt.min_tandem, 0};
-                        } else if (opt.pileup) b->ex = ccsx_extras{&b->cp, nullptr, 0, 0};
-                        if (fail_reads) {
-                            const auto f = planes(4);
-                            b->fold = f[0];
-                            b->frep = ccsx_fold_report{n, f[0], f[1], f[2], f[3]};
-                            b->freq = ccsx_fold_request{nullptr, &b->frep, {0, 0}};
-                        }
-                        if (screen) {
-                            const auto a9 = planes(9);
-                            ccsx_adapter_hit *hits = (ccsx_adapter_hit *)take(3 * CCSX_ADAPTER_MAX_HITS * n4);
-                            b->arep = ccsx_adapter_report{n, a9[0], a9[1], a9[2], a9[3], a9[4], a9[5], a9[6], a9[7], a9[8], hits};
-                            b->areq = ccsx_adapter_request{&opt.adapter_set, nullptr, &b->arep, {0, 0}};
-                        }
-                        if (control) {
-                            const auto c8 = planes(8);
-                            b->crep = ccsx_control_report{n, c8[0], c8[1], c8[2], c8[3], c8[4], c8[5], c8[6], c8[7]};
-                            b->creq = ccsx_control_request{&opt.control_seq, nullptr, &b->crep, {0, 0}};
-                        }
-                        if (coverage) {
-                            const auto v = planes(10);
-                            b->vrep = ccsx_coverage_report{n, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]};
-                            b->vreq = ccsx_coverage_request{&opt.coverage_opts, &b->vrep, 0x3cu, {0, 0}};   // all four gate bits
-                        }
-                        if (barcodes) {                          // tested, call, bq: n each; idx, dist, second, clip: [n][2]
-                            const auto b3 = planes(3);
-                            int32_t *two[4];
-                            for (auto &q : two) q = (int32_t *)take(2 * n4);
-                            b->brep = ccsx_barcode_report{n, b3[0], b3[1], b3[2], two[0], two[1], two[2], two[3]};
-                            b->breq = ccsx_barcode_request{&opt.barcode_opts, opt.barcode_set.get(), &b->brep, {0, 0}};
-                        }
-                        if (opt.reads_bam) {
-                            const auto r2 = planes(2);
-                            b->rrep = ccsx_represent_report{n, r2[0], r2[1]};
-                            b->rreq = ccsx_represent_request{opt.reads_fallback ? 1 : 0, opt.reads_kinetics ? 1 : 0, &b->rrep, {0, 0}};
-                        }
-                        b->reqs = ccsx_requests{(opt.min_tandem > 0 || opt.pileup) ? &b->ex : nullptr, fail_reads ? &b->freq : nullptr, screen ? &b->areq : nullptr,
-                                              control ? &b->creq : nullptr, coverage ? &b->vreq : nullptr, {nullptr, nullptr, nullptr}};
+                        carve_outputs(b, out_pool, opt.heteroduplexes != 0);
                     }
                 } catch (const std::exception &e) { fail(std::string("packing a batch: ") + e.what()); b->n = -1; }
                 us_pack += us_since(t0);
@@ -1655,34 +1745,109 @@ int main(int argc, char **argv)
 
         // ---- GPU workers: one per device; up to three batches in flight through the asynchronous boundary
         struct { long long tickets = 0, zmws = 0; double draft = 0, polish = 0, queue = 0, total = 0, first = 0, last = 0; } eng;   // ticket timings, --log-level INFO
+        decltype(eng) eng_ss;                                 // ... of the single-strand tickets (--heteroduplexes split)
         std::mutex eng_m;
+        const bool hd_split = opt.heteroduplexes == HD_SPLIT;
         std::vector<std::thread> workers;
         for (size_t wd = 0; wd < handles.size(); ++wd) workers.emplace_back([&, wd] {
             ccsx_handle h = handles[wd];
             ccsx_bind_thread_to_device(opt.gpus[wd]);
             ArenaPool &in_pool = *in_pools[wd];
             Channel<std::shared_ptr<Batch>> &to_gpu = *to_gpu_q[wd];
+            ArenaPool &out_pool = *out_pools[wd];
             std::deque<std::pair<ccsx_ticket, std::shared_ptr<Batch>>> inflight;
+            // --heteroduplexes split: the HETERODUPLEX ZMWs of a retired batch as single-strand entities (api.split_strands, the split the reader makes for
+            // --by-strand): per ZMW its forward passes as one entity, then its reverse passes as the next, both keeping zm and snr; within a strand the
+            // full-length passes first, each group in batch order; a strand without passes yields no entity.  Copied from the batch's staging, which is still
+            // held, into staging of its own (the pools hand out a new arena when none is free: nothing here waits for another batch).  nullptr: no such ZMW
+            std::vector<std::shared_ptr<Batch>> strand_parents;    // the batches whose strand ticket is in flight (a strand batch names its parent, it does not own it)
+            auto strand_batch = [&](Batch &b) -> std::shared_ptr<Batch> {
+                std::vector<int> het;
+                for (int s = 0; s < b.n; ++s) if (b.status[s] == CCSX_HETERODUPLEX) het.push_back(s);
+                if (het.empty()) return nullptr;
+                auto sb = std::make_shared<Batch>();
+                sb->index = b.index; sb->dev = b.dev; sb->parent = &b;
+                b.strand_slot.assign((size_t)2 * b.n, -1);
+                std::vector<int> reads;                             // the passes of the new batch, as indices into b's
+                sb->read_off.assign(1, 0); sb->base_off.assign(1, 0);
+                int64_t total = 0;
+                for (int s : het) for (int strand = 0; strand < 2; ++strand) {
+                    const size_t before = reads.size();
+                    for (int partial = 0; partial < 2; ++partial)
+                        for (int r = b.read_off[s]; r < b.read_off[s + 1]; ++r)
+                            if ((b.flags[r] & 1) == strand && ((b.flags[r] >> 1) & 1) == partial) reads.push_back(r);
+                    if (reads.size() == before) continue;
+                    b.strand_slot[2 * s + strand] = (int)sb->zmw_id.size();
+                    sb->zmw_id.push_back(b.zmw_id[s]);
+                    sb->snr.insert(sb->snr.end(), b.snr.begin() + 4 * s, b.snr.begin() + 4 * s + 4);
+                    sb->read_off.push_back((int32_t)reads.size());
+                }
+                for (int r : reads) total += b.base_off[r + 1] - b.base_off[r];
+                sb->in_arena = in_pool.get();
+                uint8_t *base = sb->in_arena->reserve((size_t)3 * (size_t)total);
+                uint8_t *planes[3] = {base, base + total, base + 2 * total};
+                const uint8_t *from[3] = {b.bases, b.pw, b.ipd};
+                int64_t at = 0;
+                for (int r : reads) {
+                    const int64_t o = b.base_off[r], L = b.base_off[r + 1] - o;
+                    for (int k = 0; k < 3; ++k) std::memcpy(planes[k] + at, from[k] + o, (size_t)L);
+                    at += L;
+                    sb->flags.push_back(b.flags[r]);
+                    sb->base_off.push_back(at);
+                }
+                sb->bases = planes[0]; sb->pw = planes[1]; sb->ipd = planes[2]; sb->n_bases = total;
+                sb->n = (int)sb->zmw_id.size();
+                sb->cb = ccsx_batch{sb->n, (int32_t)sb->flags.size(), sb->n_bases, sb->zmw_id.data(), sb->snr.data(), sb->read_off.data(),
+                                    sb->base_off.data(), sb->bases, sb->pw, sb->ipd, sb->flags.data()};
+                carve_outputs(sb, out_pool, false);
+                return sb;
+            };
             auto retire = [&] {
                 auto t0 = now();
                 auto fr = std::move(inflight.front()); inflight.pop_front();
-                std::shared_ptr<Batch> &b = fr.second;
+                std::shared_ptr<Batch> b = fr.second;
+                const bool is_strand = b->parent != nullptr;
                 if (ccsx_wait(h, fr.first)) fail(std::string("consensus engine: ") + ccsx_last_error());
                 else {
                     b->have_results = true;
                     ccsx_timings tm;
                     if (opt.log_level >= 2 && ccsx_ticket_timings(h, fr.first, &tm) == 0) {       // the engine's own device times of this ticket (HIP events)
                         std::lock_guard<std::mutex> l(eng_m);
-                        eng.tickets += 1; eng.zmws += b->n;
-                        eng.draft += tm.draft_ms + tm.align_ms; eng.polish += tm.polish_ms; eng.queue += tm.queue_ms; eng.total += tm.total_ms;
-                        if (eng.tickets == 1 || tm.start_ms < eng.first) eng.first = tm.start_ms;
-                        if (eng.tickets == 1 || tm.end_ms > eng.last) eng.last = tm.end_ms;
+                        auto &e = is_strand ? eng_ss : eng;
+                        e.tickets += 1; e.zmws += b->n;
+                        e.draft += tm.draft_ms + tm.align_ms; e.polish += tm.polish_ms; e.queue += tm.queue_ms; e.total += tm.total_ms;
+                        if (e.tickets == 1 || tm.start_ms < e.first) e.first = tm.start_ms;
+                        if (e.tickets == 1 || tm.end_ms > e.last) e.last = tm.end_ms;
                     }
+                }
+                // --heteroduplexes split: the second ticket.  The batch's HETERODUPLEX ZMWs become a single-strand batch while its staging is still held; that
+                // batch is submitted as an ordinary ticket with the run's other requests and no finder, into the slot this retirement has just freed (at most
+                // three in flight), and the batch goes to the writer when the strand ticket has retired: OUT keeps input order
+                std::shared_ptr<Batch> sb;
+                if (hd_split && !is_strand && b->have_results && !failed) {
+                    try { sb = strand_batch(*b); }
+                    catch (const std::exception &e) { fail(std::string("packing a single-strand batch: ") + e.what()); sb.reset(); b->have_results = false; }
                 }
                 in_pool.put(std::move(b->in_arena));                // inputs are on the device (and consumed): the staging is free again
                 b->bases = b->pw = b->ipd = nullptr;
+                if (sb) {
+                    ccsx_ticket t = -1;
+                    b->strand = sb;
+                    if (ccsx_submit_requests(h, &sb->cb, &sb->cr, &sb->reqs, &t)) {
+                        fail(std::string("consensus engine: ") + ccsx_last_error());
+                        sb->have_results = false;
+                        in_pool.put(std::move(sb->in_arena));
+                    } else {
+                        inflight.emplace_back(t, sb);
+                        strand_parents.push_back(b);
+                        us_engine += us_since(t0);
+                        return;                                     // (the writer gets b when sb retires)
+                    }
+                }
                 us_engine += us_since(t0);
-                to_writer.push(b);
+                if (!is_strand) { to_writer.push(b); return; }
+                // a retired strand ticket: its parent, which holds it, goes to the writer now
+                for (auto &held : strand_parents) if (held.get() == b->parent) { auto p = held; held = strand_parents.back(); strand_parents.pop_back(); to_writer.push(p); return; }
             };
             std::shared_ptr<Batch> b;
             for (;;) {
@@ -1696,11 +1861,12 @@ int main(int argc, char **argv)
                     to_writer.push(b);
                     continue;
                 }
-                if (inflight.size() >= 3) retire();
+                while (inflight.size() >= 3) retire();              // (a retirement may put a strand ticket into the slot it freed: --heteroduplexes split)
                 t0 = now();
                 ccsx_ticket t = -1;
                 // the most general submit: NULL for the extras and for every request this run did not ask for (the narrower entry points stage the same)
-                if (opt.reads_bam ? ccsx_submit_represent(h, &b->cb, &b->cr, &b->reqs, &b->rreq, &t)
+                if (opt.heteroduplexes ? ccsx_submit_hd_requests(h, &b->cb, &b->cr, &b->reqs, &b->hreq, &t)
+                    : opt.reads_bam ? ccsx_submit_represent(h, &b->cb, &b->cr, &b->reqs, &b->rreq, &t)
                                   : barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
@@ -1749,12 +1915,13 @@ int main(int argc, char **argv)
             static const uint8_t qvbin[94] = {3,3,3,3,3,3,3, 10,10,10,10,10,10,10, 17,17,17,17,17,17, 22,22,22,22,22, 27,27,27,27,27,
                                               35,35,35,35,35,35,35,35,35,35, 40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,
                                               40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40};
+            static const char *const kStrandRG[2] = {"ccsamd02", "ccsamd03"};   // --heteroduplexes split: the read groups of the /fwd and the /rev reads
             // a CCS record of ZMW slot s as the main output writes it (tags the run asks for); the caller adds its own and finishes it
             auto build = [&](const ZmwIn &z, Batch &bt, int s) {
                 const int64_t o = bt.seq_off[s]; const int32_t len = bt.seq_len[s];
                 const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                 rb.begin(qname, bt.seq + o, bt.qual + o, (uint32_t)len);
-                rb.tagZ("RG", "ccsamd01");
+                rb.tagZ("RG", hd_split && z.strand_tag ? kStrandRG[z.strand_tag - 1] : "ccsamd01");   // (--heteroduplexes split: a single-strand read names its strand's group)
                 rb.tagf("ec", bt.ec[s]);
                 rb.tagi("np", bt.np[s]);
                 rb.tagf("rq", bt.rq[s]);
@@ -1818,11 +1985,18 @@ int main(int argc, char **argv)
                 pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
                 rb.finish(*outp);
             };
+            std::function<void(const ZmwIn &, Batch &, int, std::string *)> emit_one;
             auto emit = [&](Batch &bt) {
                 if (!header_done) {
+                    // --heteroduplexes split: three read groups (mode-heteroduplex-filtering.md:44-51): today's serves the double-strand reads, one each the
+                    // /fwd and the /rev reads, with the kinetics keys their records use
+                    std::string strand_rg;
+                    for (int k = 0; hd_split && k < 2; ++k)
+                        strand_rg += std::string("@RG\tID:") + kStrandRG[k] + "\tPL:PACBIO\tDS:READTYPE=CCS;STRAND=" + (k ? "REVERSE" : "FORWARD") +
+                                     (opt.o.hifi_kinetics ? ";Ipd:CodecV1=ip;PulseWidth:CodecV1=pw" : "") + "\tPU:" + movie + "\tPM:SEQUELII\n";
                     const std::string text = "@HD\tVN:1.6\tSO:unknown\tpb:5.0.0\n@RG\tID:ccsamd01\tPL:PACBIO\tDS:READTYPE=CCS" +
                                              std::string(opt.o.hifi_kinetics && opt.by_strand ? ";Ipd:CodecV1=ip;PulseWidth:CodecV1=pw" : "") + "\tPU:" + movie +
-                                             "\tPM:SEQUELII\n@PG\tID:ccs\tPN:ccs\tVN:amd-mi355x-r1\tDS:Generate circular consensus sequences (ccs) from subreads.\n";
+                                             "\tPM:SEQUELII\n" + strand_rg + "@PG\tID:ccs\tPN:ccs\tVN:amd-mi355x-r1\tDS:Generate circular consensus sequences (ccs) from subreads.\n";
                     if (!fastq) write_header(*outp, text);
                     if (failp) write_header(*failp, text);
                 }
@@ -1830,10 +2004,34 @@ int main(int argc, char **argv)
                 for (size_t i = 0; i < bt.zmws.size(); ++i) {
                     ++rep.input;
                     const ZmwIn &z = bt.zmws[i];
-                    int st = z.host_status;
                     const int s = bt.slot[i];
+                    // --heteroduplexes split: a ZMW the split took is written as its single-strand entities, /fwd before /rev, at the ZMW's place; each is a read
+                    // of the single-strand column and an entry of the ZMW's "_strands" in the metrics file
+                    std::string strands;
+                    if (hd_split && s >= 0 && bt.have_results && z.host_status == HS_OK && bt.status[s] == CCSX_HETERODUPLEX) {
+                        ++rep.hd_zmws;
+                        for (int k = 0; k < 2 && bt.strand; ++k) {
+                            const int ks = bt.strand_slot[2 * s + k];
+                            if (ks < 0) continue;
+                            ZmwIn sz;
+                            sz.zm = z.zm; sz.strand_tag = k + 1; std::memcpy(sz.snr, z.snr, 16);
+                            emit_one(sz, *bt.strand, ks, &strands);
+                        }
+                        strands = "[" + strands + "]";
+                    }
+                    emit_one(z, bt, s, strands.empty() ? nullptr : &strands);
+                }
+            };
+            // One entity through the writer: ZMW `z` of batch bt at SoA slot s (s < 0: it failed on the host), or — z.strand_tag set under --heteroduplexes split —
+            // one strand of a split ZMW, bt being the single-strand batch.  strands: of a split ZMW the JSON list of its strands (the ZMW itself writes its
+            // metrics entry and nothing else), of a strand the list to append its entry to
+            emit_one = [&](const ZmwIn &z, Batch &bt, int s, std::string *strands) {
+                {                                                                  // (a block, so that the body stays where it stood as the body of emit's loop)
+                    const bool ss = hd_split && z.strand_tag != 0;
+                    int st = z.host_status;
                     if (st == HS_OK) st = bt.have_results ? bt.status[s] : -1;      // -1: EXCEPTION_THROWN / "Unknown error" (engine failure)
                     const int engine_st = st;
+                    const bool split_zmw = !ss && strands != nullptr;              // its strands have been written: the metrics entry remains
                     // --fail-reads: a palindrome with a consensus is a failure of its own (DESIGN.md §2 "Adapter palindromes")
                     if (fail_reads && s >= 0 && bt.have_results && bt.fold[s] == CCSX_FOLD_PALINDROME && (st == CCSX_SUCCESS || st == CCSX_LOW_RQ))
                         st = HS_ADAPTER_PALINDROME;
@@ -1845,9 +2043,17 @@ int main(int argc, char **argv)
                     // (DESIGN.md §2 "Control screen")
                     const bool pal = st == HS_ADAPTER_PALINDROME;
                     const bool ctl = control && s >= 0 && bt.have_results && bt.crep.verdict[s] == CCSX_CONTROL_FOUND;
-                    if (ctl) { st = engine_st == CCSX_SUCCESS ? HS_CONTROL_SUCCESS : HS_CONTROL_FAILURE; ++rep.control; }
+                    if (ctl && !split_zmw) { st = engine_st == CCSX_SUCCESS ? HS_CONTROL_SUCCESS : HS_CONTROL_FAILURE; rep.control += ss ? 0 : 1; }
                     const bool tandem = opt.min_tandem > 0 && s >= 0 && bt.have_results && bt.tlen[s] >= opt.min_tandem;
-                    rep.tandem += tandem ? 1 : 0;
+                    if (!split_zmw) (ss ? rep.ss_tandem : rep.tandem) += tandem ? 1 : 0;
+                    if (ss) {                                                      // a strand's entry in its ZMW's "_strands" (fields with a leading _ are implementation details: reports-aux-files.md:173)
+                        char line[256];
+                        const bool have = bt.have_results && bt.seq_len[s] > 0;
+                        std::snprintf(line, sizeof(line), "%s{\"strand\": \"%s\", \"status\": \"%s\", \"predicted_accuracy\": %.6f, \"insert_size\": %d}",
+                                      strands->empty() ? "" : ", ", z.strand_tag == 1 ? "fwd" : "rev", status_name(st, coverage), have ? bt.rq[s] : -1.0f, have ? bt.seq_len[s] : 0);
+                        *strands += line;
+                        ++rep.ss_input;
+                    } else
                     if (want_metrics) {
                         const bool have = (s >= 0 && bt.have_results);
                         const int32_t isz = (have && bt.seq_len[s] > 0) ? bt.seq_len[s] : z.median_len;
@@ -1858,26 +2064,29 @@ int main(int argc, char **argv)
                                       (have && bt.seq_len[s] > 0) ? bt.rq[s] : -1.0f, status_name(st, coverage), movie.c_str(), z.zm,
                                       z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                         metrics += line; first_metric = false;
+                        if (split_zmw) { metrics.pop_back(); metrics += ", \"_strands\": " + *strands + "}"; }
                         flush_metrics(false);
                     }
                     const int64_t o = s >= 0 ? bt.seq_off[s] : 0; const int32_t len = (s >= 0 && bt.have_results) ? bt.seq_len[s] : 0;
                     const int rcls = (opt.reads_bam && s >= 0 && bt.have_results) ? bt.rrep.cls[s] : CCSX_REPRESENT_NONE;
                     if (opt.reads_bam && s >= 0 && bt.have_results) ++rep.rep_cls[rcls & 3];
+                    if (split_zmw) return;
                     if (st != CCSX_SUCCESS) {
-                        rep.fail[fail_label(st, coverage)]++;
+                        if (st == CCSX_HETERODUPLEX) ++rep.hd_zmws;                 // (--heteroduplexes drop: no read; with --fail-reads the 0x8 rule below)
+                        (ss ? rep.ss_fail : rep.fail)[fail_label(st, coverage)]++;
                         if ((rcls == CCSX_REPRESENT_DRAFT || rcls == CCSX_REPRESENT_SUBREAD) && len > 0) put_representative(z, bt, s, rcls == CCSX_REPRESENT_SUBREAD);
                         if (st >= CCSX_DRAFT_TOO_DIFFERENT && st <= CCSX_READS_FAILED_POLISHING) ++rep.coverage;
-                        if (!fail_reads) continue;
+                        if (!fail_reads) return;
                         if ((engine_st == CCSX_LOW_RQ || pal || abits || ctl) && len > 0) {     // a consensus: as the main writer builds it, plus ff
                             if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }
                             build(z, bt, s);
-                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (ctl ? 0x2 : 0) | (pal ? 0x20 : 0) | ((abits & CCSX_ADAPTER_CONCAT) ? 0x10 : 0) |
+                            rb.tagi("ff", (engine_st == CCSX_LOW_RQ ? 0x1 : 0) | (ctl ? 0x2 : 0) | (ss ? 0x4 : 0) | (pal ? 0x20 : 0) | ((abits & CCSX_ADAPTER_CONCAT) ? 0x10 : 0) |
                                               ((abits & CCSX_ADAPTER_NEAR_END) ? 0x40 : 0));
                             fmarks.push_back(failp->mark());
-                            fpbi.rg_id.push_back(0); fpbi.q_start.push_back(0); fpbi.q_end.push_back(len); fpbi.hole.push_back(z.zm);
+                            fpbi.rg_id.push_back(ss ? z.strand_tag : 0); fpbi.q_start.push_back(0); fpbi.q_end.push_back(len); fpbi.hole.push_back(z.zm);
                             fpbi.read_qual.push_back(bt.rq[s]); fpbi.ctxt.push_back(0);
                             rb.finish(*failp); ++rep.fail_records;
-                        } else if (!z.fl_seq.empty()) {             // no consensus, at least one full pass: the median full-length subread
+                        } else if (!ss && !z.fl_seq.empty()) {      // no consensus, at least one full pass: the median full-length subread (a strand without a consensus writes nothing)
                             rep.fail["ZMW with full-length subread"]++;
                             const int32_t n = (int32_t)z.fl_seq.size();
                             rb.begin(z.fl_name, z.fl_seq.data(), nullptr, (uint32_t)n);
@@ -1892,12 +2101,21 @@ int main(int argc, char **argv)
                             fpbi.read_qual.push_back(-1.0f); fpbi.ctxt.push_back(0);
                             rb.finish(*failp); ++rep.fail_records;
                         }
-                        continue;
+                        return;
                     }
-                    ++rep.pass;
+                    ++(ss ? rep.ss_pass : rep.pass);
                     if (opt.qv_binning) for (int32_t q = 0; q < len; ++q) { uint8_t &v = bt.qual[o + q]; v = qvbin[v > 93 ? 93 : v]; }   // after rq (qv-binning.md:19-21)
                     // "Base quality >=Q30 (bp)" is a statement about the HiFi yield (docs/faq/reports-aux-files.md:66: 62,526 of the 63,881 HiFi bases while <Q20 reads
                     // are present): only reads with rq >= 0.99 count, and the percentage is taken over their bases
+                    if (ss && fail_reads) {                         // fail class 0x4 "Single-stranded CCS reads" (fail-reads.md): to FAIL.bam, not to OUT, not in the HiFi statistics
+                        build(z, bt, s);
+                        rb.tagi("ff", 0x4);
+                        fmarks.push_back(failp->mark());
+                        fpbi.rg_id.push_back(z.strand_tag); fpbi.q_start.push_back(0); fpbi.q_end.push_back(len); fpbi.hole.push_back(z.zm);
+                        fpbi.read_qual.push_back(bt.rq[s]); fpbi.ctxt.push_back(0);
+                        rb.finish(*failp); ++rep.fail_records;
+                        return;
+                    }
                     if (bt.rq[s] >= 0.99f) for (int32_t q = 0; q < len; ++q) rep.bases_q30 += bt.qual[o + q] >= 30 ? 1 : 0;
                     const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                     const bool bc_both = barcodes && bt.brep.tested[s] && bt.brep.call[s] == 3;   // --barcodes: counted over the HiFi reads, tagged at both ends called
@@ -1907,8 +2125,8 @@ int main(int argc, char **argv)
                     }
                     if (fastq) {
                         put_fastq(qname, bt, o, len);
-                        rep.lens.push_back(len); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]);
-                        continue;
+                        rep.lens.push_back(len); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]); rep.ss.push_back(ss); rep.holes.push_back(z.zm);
+                        return;
                     }
                     build(z, bt, s);
                     if (bc_both) {
@@ -1917,10 +2135,10 @@ int main(int argc, char **argv)
                         rb.tagi("bq", bt.brep.bq[s]);
                     }
                     marks.push_back(outp->mark());
-                    pbi.rg_id.push_back(0); pbi.q_start.push_back(0); pbi.q_end.push_back(len); pbi.hole.push_back(z.zm);
+                    pbi.rg_id.push_back(ss ? z.strand_tag : 0); pbi.q_start.push_back(0); pbi.q_end.push_back(len); pbi.hole.push_back(z.zm);
                     pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
                     rb.finish(*outp);
-                    rep.lens.push_back(len); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]);
+                    rep.lens.push_back(len); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]); rep.ss.push_back(ss); rep.holes.push_back(z.zm);
                 }
             };
             while (to_writer.pop(b)) {
@@ -1928,6 +2146,7 @@ int main(int argc, char **argv)
                 while (!hold.empty() && hold.begin()->first == next) {
                     emit(*hold.begin()->second);
                     out_pools[hold.begin()->second->dev]->put(std::move(hold.begin()->second->out_arena));
+                    if (hold.begin()->second->strand) out_pools[hold.begin()->second->dev]->put(std::move(hold.begin()->second->strand->out_arena));
                     hold.erase(hold.begin()); ++next;
                 }
                 const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
@@ -1990,17 +2209,43 @@ int main(int argc, char **argv)
                                  "draft + align %.2f ms, polish %.2f ms, between the stages %.2f ms, ticket start to end %.2f ms\n",
                          eng.tickets, eng.zmws, eng.last - eng.first, (eng.last - eng.first) * k, eng.draft * k, eng.polish * k, eng.queue * k, eng.total * k);
         }
+        if (opt.log_level >= 2 && eng_ss.tickets > 0 && handles.size() == 1) {
+            const double k = 1000.0 / (double)std::max<long long>(eng_ss.zmws, 1);
+            std::fprintf(stderr, "ccs: engine (single-strand tickets, %lld tickets, %lld strands): on the device %.1f ms in all; per 1000 strands: draft + align %.2f ms, polish %.2f ms, "
+                                 "between the stages %.2f ms, ticket start to end %.2f ms\n",
+                         eng_ss.tickets, eng_ss.zmws, eng_ss.total, eng_ss.draft * k, eng_ss.polish * k, eng_ss.queue * k, eng_ss.total * k);
+        }
+        if (opt.log_level >= 2 && hd_split) {                    // the DS / SS summary of mode-heteroduplex-filtering.md:72-82, over the reads of OUT
+            // a ZMW is written when OUT holds a read of it; UMY: the bases of the longest read of every written ZMW; HiFi: reads of predicted accuracy >= Q20
+            std::map<int32_t, std::pair<int32_t, int32_t>> longest[2];    // per ZMW: its longest read, its longest HiFi read; [0] DS, [1] SS
+            int64_t reads[2] = {0, 0}, hifi_bases = 0;
+            double q_sum = 0;
+            for (size_t i = 0; i < rep.lens.size(); ++i) {
+                auto &e = longest[rep.ss[i]][rep.holes[i]];
+                e.first = std::max(e.first, rep.lens[i]);
+                if (rep.rqs[i] >= 0.99f) { e.second = std::max(e.second, rep.lens[i]); ++reads[rep.ss[i]]; hifi_bases += rep.lens[i]; q_sum += rq_to_q(rep.rqs[i]); }
+            }
+            int64_t umy[2] = {0, 0}, hy[2] = {0, 0};
+            for (int c = 0; c < 2; ++c) for (const auto &kv : longest[c]) { umy[c] += kv.second.first; hy[c] += kv.second.second; }
+            const int64_t nr = reads[0] + reads[1];
+            std::fprintf(stderr, "ZMWs Input    : %" PRId64 "\nZMWs Written  : %zu\n - DS / SS    : %zu / %zu\nUMY           : %" PRId64 " bases\n - DS / SS    : %" PRId64 " / %" PRId64 "\n"
+                                 "HiFi Yield    : %" PRId64 " bases\n - DS / SS    : %" PRId64 " / %" PRId64 "\nHiFi Reads    : %" PRId64 "\n - DS / SS    : %" PRId64 " / %" PRId64 "\n"
+                                 "HiFi Avg Size : %" PRId64 " bases\nHiFi Avg QV   : %.1f\n",
+                         rep.input, longest[0].size() + longest[1].size(), longest[0].size(), longest[1].size(), umy[0] + umy[1], umy[0], umy[1], hy[0] + hy[1], hy[0], hy[1],
+                         nr, reads[0], reads[1], nr ? hifi_bases / nr : 0, nr ? q_sum / (double)nr : 0.0);
+        }
         if (opt.log_level >= 2 && use_gpu_deflate)
             std::fprintf(stderr, "ccs: --gpu-deflate: %lld tickets, %lld blocks, %.1f MB in, %.1f MB out; writer thread: staging + submit %.2f s, waiting for tickets %.2f s\n",
                          gpu_deflater.n_tickets, gpu_deflater.n_blocks, gpu_deflater.n_in * 1e-6, gpu_deflater.n_out * 1e-6, gpu_deflater.us_submit * 1e-6,
                          gpu_deflater.us_wait * 1e-6);
         if (opt.log_level >= 1)
-            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s%s%s\n", rep.input, rep.pass, el,
+            std::fprintf(stderr, "ccs: %" PRId64 " ZMWs in, %" PRId64 " HiFi reads out, %.2f s (%.1f ZMWs/s, %d host threads, %zu GPU worker%s)%s%s%s%s%s%s\n", rep.input, rep.pass, el,
                          rep.input / el, nthreads, handles.size(), handles.size() == 1 ? "" : "s",
                          opt.min_tandem > 0 ? (", " + std::to_string(rep.tandem) + " ZMWs with tandem repeats").c_str() : "",
                          opt.fail_reads.empty() ? "" : (", " + std::to_string(rep.fail_records) + " fail reads").c_str(),
                          control ? (", " + std::to_string(rep.control) + " control ZMWs").c_str() : "",
                          coverage ? (", " + std::to_string(rep.coverage) + " ZMWs failed the coverage filters").c_str() : "",
+                         opt.heteroduplexes ? (", " + std::to_string(rep.hd_zmws) + " heteroduplex ZMWs " + (hd_split ? "split" : "dropped")).c_str() : "",
                          opt.reads_bam ? (", representative reads: " + std::to_string(rep.rep_cls[CCSX_REPRESENT_POLISHED]) + " polished, " + std::to_string(rep.rep_cls[CCSX_REPRESENT_DRAFT]) +
                                           " drafts, " + std::to_string(rep.rep_cls[CCSX_REPRESENT_SUBREAD]) + " subreads").c_str() : "");
         if (opt.log_level >= 1 && opt.orient_passes)

@@ -1289,7 +1289,6 @@ static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const c
     if (barcodes && hd) return refuse(fn, "the barcode and the heteroduplex requests are not combined");
     if (barcodes && b && barcode_request_check(barcodes, b, &W->barcode_set, &W->barcode_opts, fn)) return -1;
     if (handoff && handoff_request_check(handoff, &W->handoff_opts, &W->handoff_out, fn)) return -1;
-    if (coverage && hd) return refuse(fn, "the coverage and the heteroduplex requests are not combined");
     if (coverage && b && coverage_request_check(coverage, b, &W->coverage_opts, fn)) return -1;
     if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
     if (fold && b && fold_request_check(fold, b, &W->fold_opts, fn)) return -1;
@@ -1542,12 +1541,6 @@ int ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, co
     if (build_wants(ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
-int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket)
-{
-    Wants W;
-    if (build_wants(ex, hd, nullptr, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
-    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
-}
 int ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket)
 {
     Wants W;
@@ -1570,17 +1563,36 @@ int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
 }
 // the members of a ccsx_requests as build_wants takes them (NULL: none); -1 for nonzero reserved words
 static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_handoff_request *handoff = nullptr,
-                          const ccsx_barcode_request *barcodes = nullptr)
+                          const ccsx_barcode_request *barcodes = nullptr, const ccsx_hd_request *hd = nullptr)
 {
     static const ccsx_requests none = {};
     if (!rq) rq = &none;
     if (rq->reserved[0] || rq->reserved[1] || rq->reserved[2]) return refuse(fn, "ccsx_requests: reserved must be NULL");
-    return build_wants(rq->ex, nullptr, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff, barcodes);
+    return build_wants(rq->ex, hd, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff, barcodes);
+}
+// the Wants of a call with a heteroduplex request beside the members of rq (the four ccsx_*_hd* entry points): the checks of ccsx_submit_hd, in its order
+static int hd_requests_wants(const ccsx_requests *rq, const ccsx_hd_request *hd, const ccsx_batch *b, const char *fn, Wants *W)
+{
+    if (requests_wants(rq, b, fn, W, nullptr, nullptr, hd) || (!hd && refuse(fn, "null request or report"))) return -1;
+    return 0;
 }
 int ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket)
 {
     Wants W;
     if (requests_wants(rq, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_hd_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_hd_request *hd, ccsx_ticket *ticket)
+{
+    Wants W;
+    if (hd_requests_wants(rq, hd, b, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd, ccsx_ticket *ticket)
+{
+    const ccsx_requests rq = {ex, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr}};
+    Wants W;
+    if (hd_requests_wants(&rq, hd, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho, ccsx_ticket *ticket)
@@ -1798,10 +1810,18 @@ int ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res,
     return consensus_sync(h, b, res, W, __func__);
 }
 
-int ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd)
+int ccsx_consensus_hd_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_hd_request *hd)
 {
     Wants W;
-    if (build_wants(ex, hd, nullptr, nullptr, nullptr, b, __func__, &W) || (!hd && refuse(__func__, "null request or report"))) return -1;
+    if (hd_requests_wants(rq, hd, b, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
+int ccsx_consensus_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_hd_request *hd)
+{
+    const ccsx_requests rq = {ex, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr}};
+    Wants W;
+    if (hd_requests_wants(&rq, hd, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 

@@ -5286,16 +5286,18 @@ const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int m
     s.window_map();
     if (mode == CCSX_RUN_FUSED) {
         s.draft_screens();
+        // The coverage screen before the finder (a call may carry both: ccsx_submit_hd_requests): k_coverage sees every status as the cascade left it, so its
+        // report does not depend on the finder; a ZMW its gate takes is not SUCCESS any more and the finder leaves it UNTESTED (DESIGN.md §2 "In the fused path").
+        if (P.cov_zi) {
+            s.coverage();
+            if (P.cov_gate & CCSX_COVERAGE_PRE_GATE) s.window_map();   // the gated ZMWs have no windows now: the finder's and the polish stage's map without them
+        }
         if (P.hd_zi) {
             // the heteroduplex finder in the fused path (ccsx_submit_hd / ccsx_consensus_hd): on the draft stream, so that it belongs to this batch's draft
             // stage and runs under the previous batch's polish stage
             s.hd_finder(false);
             if (P.hd_split) s.window_map();                 // the split ZMWs have no windows now: the polish stage's map without them
             s.trace_sync(q.draft, "k_hd");
-        }
-        if (P.cov_zi) {
-            s.coverage();
-            if (P.cov_gate & CCSX_COVERAGE_PRE_GATE) s.window_map();   // the gated ZMWs have no windows now: the polish stage's map without them
         }
     }
     if (mode == CCSX_RUN_HD) {                              // the heteroduplex finder instead of the polish stage, on the same stream

@@ -425,7 +425,7 @@ int         ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res
  *   ccsx_submit_fold     ticketed like ccsx_submit_extras: the report's arrays follow the lifetime rule of `res` (written by the ticket's download) and should be
  *                        page-locked; the request and options structs are read during the call only.
  * A NULL request or report, a report sized for another batch, nonzero reserved words or thresholds out of range are errors of the call: nothing is enqueued.
- * Without a request nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered.                                            */
+ * Without a request nothing of it is launched, reserved or copied.  With a ccsx_hd_request: ccsx_consensus_hd_requests / ccsx_submit_hd_requests.                                            */
 typedef struct ccsx_fold_opts {
     int32_t max_occ;             /* a canonical 15-mer sampled more often than this is dropped everywhere (1 .. 64)                                              */
     int32_t min_hits;            /* hits in the winning pair of anti-diagonal bins (>= 1)                                                                        */
@@ -460,7 +460,7 @@ int         ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *r
  *   ccsx_submit_screen     ticketed like ccsx_submit_fold: the reports' arrays follow the lifetime rule of `res` (written by the ticket's download) and should be
  *                          page-locked; the request, set and options structs are read during the call only.
  * A NULL report, a report sized for another batch, nonzero reserved words, options or pattern lengths out of range, a code above 3 or n_adapters outside 1 .. 8 are
- * errors of the call: nothing is enqueued.  Without a request nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered.     */
+ * errors of the call: nothing is enqueued.  Without a request nothing of it is launched, reserved or copied.  With a ccsx_hd_request: ccsx_consensus_hd_requests / ccsx_submit_hd_requests.     */
 #define CCSX_ADAPTER_MAX_PATTERNS 8
 #define CCSX_ADAPTER_MIN_LEN      16
 #define CCSX_ADAPTER_MAX_LEN      64
@@ -520,7 +520,7 @@ int         ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results 
  *                           be page-locked; the request, sequence and options structs are read during the call only (every ticket carries its own index: tickets
  *                           in flight may screen for different controls).
  * A NULL report or control sequence, a report sized for another batch, nonzero reserved words, a length outside 64 .. 4096, a code above 3 or options out of range
- * are errors of the call: nothing is enqueued.  Without a request nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered. */
+ * are errors of the call: nothing is enqueued.  Without a request nothing of it is launched, reserved or copied.  With a ccsx_hd_request: ccsx_consensus_hd_requests / ccsx_submit_hd_requests. */
 #define CCSX_CONTROL_MIN_LEN 64
 #define CCSX_CONTROL_MAX_LEN 4096
 typedef struct ccsx_control_opts {
@@ -574,7 +574,7 @@ int         ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results
  * outside 1 .. 4096, min_spans outside 0 .. 255 or gate bits outside 2 .. 5 are errors of the call: nothing is enqueued.  The report's arrays follow the lifetime
  * rule of `res` and should be page-locked for the ticketed form; the request and options structs are read during the call only (every ticket carries its own
  * options and gate).  Per batch slot the screen takes 40 bytes per ZMW and one byte per window slot, reserved by the first request on that slot; without a request
- * nothing of it is launched, reserved or copied.  Combining with ccsx_hd_request is not offered; the draft and polish seams take no request.                      */
+ * nothing of it is launched, reserved or copied.  With a ccsx_hd_request: ccsx_consensus_hd_requests / ccsx_submit_hd_requests; the draft and polish seams take no request.                      */
 typedef struct ccsx_coverage_opts {
     int32_t drop_percent;        /* a window drops when clean_w * 100 <= drop_percent * cov_max (0 .. 100)                                                        */
     int32_t block;               /* a reaching pass carries a block in a window when its segment is more than this many bases longer than the window (1 .. 4096);
@@ -623,6 +623,23 @@ typedef struct ccsx_requests {
 } ccsx_requests;
 int         ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq);
 int         ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket);
+
+/* The finder beside the other requests: ccsx_consensus_hd_requests (synchronous, slot 0) and ccsx_submit_hd_requests (ticketed like ccsx_submit_requests) are
+ * ccsx_consensus_requests / ccsx_submit_requests plus a ccsx_hd_request, which is a further argument as the barcode and represent requests are (struct
+ * ccsx_requests keeps its layout).  rq may be NULL or carry any member: extras with pileup planes and tandem detection, fold, adapters, control, coverage.  With
+ * only rq->ex set the call is ccsx_consensus_hd / ccsx_submit_hd, which forward to this path.  hd == NULL is an error of the call ("null request or report"), and
+ * every check of ccsx_submit_hd holds, by the same messages; nothing is enqueued.  It is not combined with the hand-off, barcode or represent requests.
+ * Who gives a ZMW its status in the draft stage (DESIGN.md §2 "In the fused path"), in this order:
+ *   1. the draft screens (fold, adapters, control) run on every draft whose status after the cascade is SUCCESS, heteroduplex or not: detection only;
+ *   2. the coverage screen's k_coverage, on the statuses the cascade left: its report does not depend on the finder.  With a gate bit for verdict 2 .. 4 the ZMW
+ *      gets CCSX_DRAFT_TOO_DIFFERENT .. CCSX_COVERAGE_DROPS here;
+ *   3. the finder, on every ZMW that is still SUCCESS: a ZMW the gate took is UNTESTED in the finder's report, and report.status holds its gate status.  Without
+ *      a gate bit the finder's report is that of ccsx_consensus_hd.  With split = 1 a HETERODUPLEX ZMW gets CCSX_HETERODUPLEX.
+ * So the coverage gate precedes the split, and no ZMW is given a status twice.  A CCSX_HETERODUPLEX ZMW keeps the pre-polish planes of its coverage report
+ * (verdict, np_aligned, spans, cov_max, clean_min, drop_window, drop_windows, reach_sum) and has used_sum = used_min = 0, as every ZMW that was not polished;
+ * verdict 5 (READS_FAILED_POLISHING) is never reached for it.  Nothing else about any request changes.                                                         */
+int         ccsx_consensus_hd_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_hd_request *hd);
+int         ccsx_submit_hd_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_hd_request *hd, ccsx_ticket *ticket);
 
 /* ---- polisher hand-off (docs/faq/revio.md:28-53: the low-quality windows of the Arrow consensus go to a second, learned polisher; the rule: DESIGN.md §2
  * "Polisher hand-off", its own version ccsx_handoff_rule_version; no result of the consensus changes).  The consensus of every ZMW is cut into tiles of tile_len
