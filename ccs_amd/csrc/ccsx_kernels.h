@@ -239,8 +239,9 @@ static inline __host__ __device__ int ccsx_orient_slots(int M)
 #define CCSX_SDUST_T 20
 #define CCSX_SDUST_TABLE_BYTES (2 * 64 * 64 * 4 + 2 * 64 * 64)
 
-#define CCSX_HD_LF_N (2 * CCSX_MAX_PASSES + 1)   // log-factorials 0 .. 510: a Fisher table never holds more passes than that
-#define CCSX_HD_IMAX 49                          // rows of a segment the pileup aligns: template columns (<= 29) + min_indel - 1 (<= 20)
+#define CCSX_HD_LF_N (2 * CCSX_MAX_PASSES + 1)   // log-factorials 0 .. 510; a Fisher table holds nf + nr <= CCSX_MAX_PASSES = 255 passes, so only 0 .. 255 are read
+#define CCSX_HD_IMAX 49                          // rows of a segment the pileup aligns.  A last window has up to 30 template columns (core <= 28 + one overhang), so
+                                                 // with min_indel 21 a segment of 50 rows exists: this clause, not |n - J| < min_indel, leaves it out of the pileup
 
 // which stages ccsx_launch_all enqueues: the fused path, the draft stage alone (ccsx_draft_batch), alignment cascade + polish on caller-supplied drafts, or
 // alignment cascade + the heteroduplex finder on caller-supplied drafts (ccsx_hd_batch), or alignment cascade + the training counts on caller-supplied drafts
