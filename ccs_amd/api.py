@@ -779,6 +779,120 @@ def barcode_reads_host(bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = Non
     return rep
 
 
+# ---- segmentation of concatenated-array reads (include/ccsx.h ccsx_segment_*; DESIGN.md §2 "Segment rule")
+SEGMENT_MAX_ADAPTERS, SEGMENT_MIN_LEN, SEGMENT_MAX_LEN, SEGMENT_MAX_HITS, SEGMENT_MAX_PIECES = 33, 8, 64, 64, 64
+SEGMENT_PIECE_DTYPE = np.dtype([("start", np.int32), ("end", np.int32), ("index", np.uint8), ("reverse", np.uint8), ("dist_left", np.uint8),
+                                ("dist_right", np.uint8)])
+
+
+class SegmentOpts(C.Structure):
+    _fields_ = [("max_dist_pct", C.c_int32), ("min_len", C.c_int32)]
+
+
+class SegmentSet(C.Structure):
+    """ccsx_segment_set: the 2 .. 33 adapters of an array, of 8 .. 64 codes 0 .. 3, in array order"""
+    _fields_ = [("n_adapters", C.c_int32), ("len", C.c_int32 * SEGMENT_MAX_ADAPTERS), ("seq", (C.c_uint8 * SEGMENT_MAX_LEN) * SEGMENT_MAX_ADAPTERS)]
+
+    @staticmethod
+    def from_codes(seqs) -> "SegmentSet":
+        """from ACGT strings (either case) or arrays of codes; lengths, codes and the count are checked by the call that takes the set"""
+        seqs = list(seqs)
+        if len(seqs) > SEGMENT_MAX_ADAPTERS:
+            raise ValueError(f"at most {SEGMENT_MAX_ADAPTERS} adapters")
+        s = SegmentSet()
+        s.n_adapters = len(seqs)
+        flat = np.frombuffer(s, np.uint8, SEGMENT_MAX_ADAPTERS * SEGMENT_MAX_LEN, SegmentSet.seq.offset).reshape(SEGMENT_MAX_ADAPTERS, SEGMENT_MAX_LEN)
+        for a, q in enumerate(seqs):
+            codes = ["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q]
+            if len(codes) > SEGMENT_MAX_LEN:
+                raise ValueError(f"adapter {a}: more than {SEGMENT_MAX_LEN} bases")
+            s.len[a] = len(codes)
+            flat[a, : len(codes)] = codes
+        return s
+
+    from_strings = from_codes
+
+    def codes(self) -> list:
+        return [np.array(self.seq[a][: self.len[a]], np.uint8) for a in range(self.n_adapters)]
+
+
+class CSegmentPiece(C.Structure):
+    _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("index", C.c_uint8), ("reverse", C.c_uint8), ("dist_left", C.c_uint8), ("dist_right", C.c_uint8)]
+
+
+SEGMENT_PLANES = ("tested", "overflow", "n_hits", "n_cuts", "n_segments", "complete", "orient", "leftover_bases")
+
+
+class CSegmentReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in SEGMENT_PLANES] + [("pieces", C.POINTER(CSegmentPiece))]
+
+
+class CSegmentRequest(C.Structure):
+    """ccsx_segment_request: segmentation in the fused path (ccsx_consensus_segments / ccsx_submit_segments)"""
+    _fields_ = [("opts", C.POINTER(SegmentOpts)), ("set", C.POINTER(SegmentSet)), ("report", C.POINTER(CSegmentReport)), ("reserved", C.c_int32 * 2)]
+
+
+def segment_opts_default() -> SegmentOpts:
+    o = SegmentOpts()
+    lib().ccsx_segment_opts_default(C.byref(o))
+    return o
+
+
+class SegmentReport(_PlaneReport):
+    """ccsx_segment_report: per read the eight int32 planes of SEGMENT_PLANES and pieces, [n, SEGMENT_MAX_PIECES] of SEGMENT_PIECE_DTYPE: the segments by
+    increasing start, zero beyond n_segments"""
+    FIELDS = SEGMENT_PLANES + ("pieces",)
+    PLANES = _int_planes(*SEGMENT_PLANES) + (("pieces", SEGMENT_PIECE_DTYPE, (SEGMENT_MAX_PIECES,)),)
+    CSTRUCT = CSegmentReport
+
+    def c_struct(self) -> CSegmentReport:
+        r = CSegmentReport()
+        r.n_zmw = len(self.tested)
+        for k in SEGMENT_PLANES:
+            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
+        r.pieces = self.pieces.ctypes.data_as(C.POINTER(CSegmentPiece))
+        return r
+
+    def segments(self, z: int) -> list:
+        """read z's segments as tuples (start, end, index, reverse, dist_left, dist_right)"""
+        return [tuple(int(v) for v in p) for p in self.pieces[z, : int(self.n_segments[z])]]
+
+    def fields(self, z: int) -> dict:
+        """every plane of read z, and all SEGMENT_MAX_PIECES list entries"""
+        d = {k: int(getattr(self, k)[z]) for k in SEGMENT_PLANES}
+        d["pieces"] = [tuple(int(v) for v in p) for p in self.pieces[z]]
+        return d
+
+
+def _segment_request(sset: SegmentSet, opts: "SegmentOpts | None", crep: CSegmentReport):
+    o = opts if opts is not None else segment_opts_default()
+    return CSegmentRequest(C.pointer(o), C.pointer(sset), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (sset, o, crep)
+
+
+def _segment_reads_args(sset: SegmentSet, opts: "SegmentOpts | None", reads, report: "SegmentReport | None"):
+    """the arguments of ccsx_segment_reads[_host] for a list of code arrays: (args, report, keep)"""
+    reads = [np.ascontiguousarray(r, np.uint8) for r in reads]
+    n = len(reads)
+    seq_len = np.array([len(r) for r in reads], np.int32).reshape(n)
+    seq_off = np.zeros(n, np.int64)
+    if n:
+        seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64)
+    seq = np.concatenate(reads + [np.zeros(1, np.uint8)])
+    rep = report if report is not None else SegmentReport.allocate(n)
+    crep = rep.c_struct()
+    o = opts if opts is not None else segment_opts_default()
+    keep = (sset, o, seq, seq_off, seq_len, crep, rep)
+    return (C.byref(sset), C.byref(o), _ptr(seq, C.c_uint8), _ptr(seq_off, C.c_int64), _ptr(seq_len, C.c_int32), n, C.byref(crep)), rep, keep
+
+
+def segment_reads_host(sset: SegmentSet, reads, opts: "SegmentOpts | None" = None, report: "SegmentReport | None" = None) -> SegmentReport:
+    """ccsx_segment_reads_host: the segment rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
+    args, rep, _keep = _segment_reads_args(sset, opts, reads, report)
+    if lib().ccsx_segment_reads_host(*args) != 0:
+        raise RuntimeError("ccsx_segment_reads_host failed: " + lib().ccsx_last_error().decode())
+    return rep
+
+
 # ---- representative reads (include/ccsx.h ccsx_represent_*; DESIGN.md §2 "Representative rule")
 REPRESENT_POLISHED, REPRESENT_NONE, REPRESENT_DRAFT, REPRESENT_SUBREAD = 0, 1, 2, 3
 REPRESENT_NAMES = ("POLISHED", "NONE", "DRAFT", "SUBREAD")
@@ -1111,6 +1225,8 @@ EXPORTS = [
     "ccsx_train_rule_version", "ccsx_train_batch", "ccsx_train_pair_host",
     "ccsx_fit_opts_default", "ccsx_fitter_create", "ccsx_fitter_add", "ccsx_fitter_finish", "ccsx_fitter_destroy",
     "ccsx_barcode_opts_default", "ccsx_barcode_rule_version", "ccsx_barcode_reads_host", "ccsx_barcode_reads", "ccsx_consensus_barcodes", "ccsx_submit_barcodes",
+    "ccsx_segment_opts_default", "ccsx_segment_rule_version", "ccsx_segment_chunk", "ccsx_segment_reads_host", "ccsx_segment_reads", "ccsx_consensus_segments",
+    "ccsx_submit_segments",
     "ccsx_represent_rule_version", "ccsx_represent_host", "ccsx_consensus_represent", "ccsx_submit_represent",
 ]
 
@@ -1256,6 +1372,13 @@ def lib() -> C.CDLL:
         L.ccsx_barcode_reads.argtypes = [C.c_void_p] + _bcreads
         L.ccsx_consensus_barcodes.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CBarcodeRequest)]
         L.ccsx_submit_barcodes.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CBarcodeRequest), C.POINTER(C.c_int64)]
+        L.ccsx_segment_opts_default.restype = None
+        L.ccsx_segment_opts_default.argtypes = [C.POINTER(SegmentOpts)]
+        _sgreads = [C.POINTER(SegmentSet), C.POINTER(SegmentOpts), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(CSegmentReport)]
+        L.ccsx_segment_reads_host.argtypes = _sgreads
+        L.ccsx_segment_reads.argtypes = [C.c_void_p] + _sgreads
+        L.ccsx_consensus_segments.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CSegmentRequest)]
+        L.ccsx_submit_segments.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CSegmentRequest), C.POINTER(C.c_int64)]
         L.ccsx_represent_host.argtypes = [C.POINTER(CBatch), C.POINTER(Opts), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                           C.POINTER(CRepresentRequest), C.POINTER(CResults)]
         L.ccsx_consensus_represent.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CRepresentRequest)]
@@ -1672,13 +1795,13 @@ class Handle:
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
 
-    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None, represent=None):
+    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None, represent=None, segments=None):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
         ccsx_*_hd with a heteroduplex request and nothing but extras, ccsx_*_requests when _requests made a CRequests (a coverage request, or
         via_requests; ccsx_*_hd_requests when a heteroduplex request goes with it), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
         structs join the requests' keep list.  barcodes: (report, set, opts), through ccsx_*_barcodes in the same way (not together with a hand-off).
-        represent: (report, subread_fallback, kinetics), through ccsx_*_represent in the same way (not together with a hand-off or barcodes).  Returns the C
-        structs"""
+        represent: (report, subread_fallback, kinetics), through ccsx_*_represent in the same way (not together with a hand-off or barcodes).
+        segments: (report, set, opts), through ccsx_*_segments in the same way (not together with a hand-off, barcodes or represent).  Returns the C structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
@@ -1704,6 +1827,15 @@ class Handle:
             rreq = _represent_request(*represent)
             name, args = f"ccsx_{form}_represent", (_keep[-1], rreq[0])
             _keep.append(rreq)
+        if segments is not None:
+            if handoff is not None or barcodes is not None or represent is not None or name != f"ccsx_{form}_requests":
+                raise ValueError("the segment request goes with the members of ccsx_requests (not with the hand-off, the barcode, the represent or the heteroduplex request)")
+            srep, sset, sopts = segments
+            if sset is None:
+                raise ValueError("segments: a segment_set is needed")
+            sreq = _segment_request(sset, sopts, srep.c_struct())
+            name, args = f"ccsx_{form}_segments", (_keep[-1], sreq[0])
+            _keep.append((sreq, srep))
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
         if form == "consensus":
@@ -1896,6 +2028,24 @@ class Handle:
         self._fused("consensus", batch, res, _requests(via_requests=True, **requests), barcodes=(rep, bset, opts))
         return res, rep
 
+    # ---- segmentation (ccsx_consensus_segments / ccsx_segment_reads): the segments of concatenated-array reads
+    def consensus_segments(self, batch: Batch, sset: SegmentSet, opts: "SegmentOpts | None" = None, res: "Results | None" = None,
+                           **requests) -> tuple["Results", SegmentReport]:
+        """(results, segment report).  sset: the SegmentSet; opts: the SegmentOpts (None: the defaults); res: the caller's Results.  requests: Handle.submit's
+        keyword arguments for the other requests of the same run (pileup=, tandem=, fold=, adapters=, control=, coverage= ... with their reports; not hd=,
+        handoff=, barcodes=, represent=)"""
+        if res is None:
+            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = SegmentReport.allocate(batch.n_zmw)
+        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), segments=(rep, sset, opts))
+        return res, rep
+
+    def segment_reads(self, sset: SegmentSet, reads, opts: "SegmentOpts | None" = None, report: "SegmentReport | None" = None) -> SegmentReport:
+        """ccsx_segment_reads: k_segment on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
+        args, rep, _keep = _segment_reads_args(sset, opts, reads, report)
+        self._check(self._L.ccsx_segment_reads(self._h, *args), "ccsx_segment_reads")
+        return rep
+
     # ---- representative reads (ccsx_consensus_represent): a draft or a subread in the result planes of every ZMW that was not polished
     def consensus_represent(self, batch: Batch, subread_fallback: bool = False, kinetics: bool = False, res: "Results | None" = None,
                             **requests) -> tuple["Results", RepresentReport]:
@@ -1984,7 +2134,8 @@ class Handle:
                control_seq: "ControlSeq | None" = None, control_opts: "ControlOpts | None" = None, coverage: "CoverageReport | None" = None,
                coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, handoff: "Handoff | None" = None,
                barcodes: "BarcodeReport | None" = None, barcode_set: "BarcodeSet | None" = None, barcode_opts: "BarcodeOpts | None" = None,
-               represent: "RepresentReport | None" = None, represent_fallback: bool = False, represent_kinetics: bool = False) -> int:
+               represent: "RepresentReport | None" = None, represent_fallback: bool = False, represent_kinetics: bool = False,
+               segments: "SegmentReport | None" = None, segment_set: "SegmentSet | None" = None, segment_opts: "SegmentOpts | None" = None) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
         receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd; with fold, adapters, control
@@ -2000,7 +2151,8 @@ class Handle:
         barcode calls for barcode_set under barcode_opts (ccsx_submit_barcodes; not with hd or handoff); every ticket carries its own set and options.  represent: a report
         (RepresentReport.allocate(n, pinned=True)) that receives the representative classes; the ZMWs that were not polished get a draft or a subread in `res`
         (ccsx_submit_represent; represent_fallback / represent_kinetics: the request's flags, every ticket its own; not with hd, handoff, barcodes or a
-        coverage gate)"""
+        coverage gate).  segments: a report (SegmentReport.allocate(n, pinned=True)) that receives the segmentation for segment_set under segment_opts
+        (ccsx_submit_segments; not with hd, handoff, barcodes or represent); every ticket carries its own set and options"""
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if control is not None and control_seq is None:
@@ -2011,13 +2163,16 @@ class Handle:
             raise ValueError("the barcode request is not combined with the heteroduplex request or the hand-off")
         if represent is not None and (hd is not None or handoff is not None or barcodes is not None):
             raise ValueError("the represent request is not combined with the heteroduplex request, the hand-off or the barcode request")
+        if segments is not None and (hd is not None or handoff is not None or barcodes is not None or represent is not None):
+            raise ValueError("the segment request is not combined with the heteroduplex request, the hand-off, the barcode or the represent request")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
                              control, control_seq, control_opts, coverage, coverage_opts, coverage_gate,
-                             via_requests=handoff is not None or barcodes is not None or represent is not None, hd_requests=True)
+                             via_requests=handoff is not None or barcodes is not None or represent is not None or segments is not None, hd_requests=True)
         t = C.c_int64()
         cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff,
                              barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None,
-                             represent=(represent, represent_fallback, represent_kinetics) if represent is not None else None)
+                             represent=(represent, represent_fallback, represent_kinetics) if represent is not None else None,
+                             segments=(segments, segment_set, segment_opts) if segments is not None else None)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
         self._inflight[t.value] = (batch, res, cb, cr, requests, handoff)  # the C structs and arrays must outlive the ticket

@@ -14,6 +14,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cctype>
 #include <cstring>
@@ -93,6 +94,11 @@ struct Options {
     std::shared_ptr<ccsx_barcode_set> barcode_set;   // ... the set it names, the record names, the options every ticket carries
     std::vector<std::string> barcode_names;
     ccsx_barcode_opts barcode_opts{};
+    std::string segment_adapters; // --segment-adapters FILE.fasta: cut every HiFi read of a concatenated array into its segments (DESIGN.md §2 "Segment rule"): tags di, dl, dr
+    int segment_min_length = -1;  // --segment-min-length N: a piece shorter than this is no segment (-1: the default)
+    std::string segment_counts;   // --segment-counts FILE.tsv: reads per (segments, orientation, complete) class
+    std::shared_ptr<ccsx_segment_set> segment_set;   // ... the set it names and the options every ticket carries
+    ccsx_segment_opts segment_opts{};
     bool reads_bam = false;       // --reads-bam: one representative read per productive ZMW (the reference's --all, DESIGN.md §2 "Representative rule")
     bool reads_kinetics = false;  // --reads-bam-kinetics: --hifi-kinetics for the polished reads, fi / fp of the pass for the unaltered subreads (--all-kinetics)
     bool reads_fallback = false;  // --reads-bam-subread-fallback: a subread where an unpolished draft would be written (--subread-fallback)
@@ -174,6 +180,7 @@ struct Batch {
     ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_adapter_request: the report's arrays are in out_arena)
     ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_control_request: the report's arrays are in out_arena)
     ccsx_coverage_report vrep{}; ccsx_coverage_request vreq{}; // --coverage-filters (ccsx_coverage_request: the report's arrays are in out_arena)
+    ccsx_segment_report srep{}; ccsx_segment_request sreq{};   // --segment-adapters (ccsx_segment_request: the report's arrays are in out_arena)
     ccsx_barcode_report brep{}; ccsx_barcode_request breq{};   // --barcodes (ccsx_barcode_request: the report's arrays are in out_arena)
     ccsx_represent_report rrep{}; ccsx_represent_request rreq{};   // --reads-bam (ccsx_represent_request: the report's arrays are in out_arena)
     ccsx_hd_report hrep{}; ccsx_hd_request hreq{};   // --heteroduplexes (ccsx_hd_request: the report's arrays are in out_arena)
@@ -272,6 +279,13 @@ void usage()
                  "                            as it reads on the opposite strand) and bq:i; nothing is clipped; the reports gain a barcode block [off]\n"
                  "      --barcode-window N    with --barcodes: bases of either end that are searched, 8-1024 [64]\n"
                  "      --barcode-counts F.tsv  with --barcodes: one line per called pair of barcodes (the two record names, the reads), sorted by index pair\n"
+                 "      --segment-adapters F.fasta  cut every HiFi read of a concatenated array (A0 S1 A1 .. SK AK, either strand) into its segments, on the GPU: F holds\n"
+                 "                            the 2-33 adapters of 8-64 bases in array order; a HiFi read is replaced by one record per segment, named\n"
+                 "                            <movie>/<zm>/ccs/<start>_<end>, with the tags di:i (segment index) and dl:i / dr:i (the adapters on its left and right);\n"
+                 "                            a read without a segment is not written; the reports gain a segment block.  Not with --by-strand, --barcodes,\n"
+                 "                            --reads-bam, --heteroduplexes, --fit-model [off]\n"
+                 "      --segment-min-length N  with --segment-adapters: a piece shorter than N bases is no segment, 1-65535 [50]\n"
+                 "      --segment-counts F.tsv  with --segment-adapters: one line per class of reads (segments per read, orientation, complete, the reads), sorted\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
                  "      --chunk i/N           process only the i-th of N ZMW chunks\n"
@@ -380,6 +394,41 @@ bool load_barcodes(const std::string &path, ccsx_barcode_set &set, std::vector<s
     return true;
 }
 
+// --segment-adapters: a FASTA of 2 .. 33 records of 8 .. 64 bases, ACGT in either case, in array order.  false + a message that names the record, as load_barcodes
+bool load_segment_adapters(const std::string &path, ccsx_segment_set &set, std::string &err)
+{
+    std::ifstream f(path);
+    if (!f) { err = "cannot open the file"; return false; }
+    std::memset(&set, 0, sizeof set);
+    std::vector<std::string> names;
+    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + names[k] + ")"; };
+    std::string line;
+    while (std::getline(f, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            names.push_back(line.substr(0, 60));
+            if (names.size() > CCSX_SEGMENT_MAX_ADAPTERS) { err = where(names.size() - 1) + ": more than 33 records"; return false; }
+            continue;
+        }
+        if (names.empty()) { err = "sequence before the first '>' line"; return false; }
+        const size_t a = names.size() - 1;
+        for (char c : line) {
+            const int u = std::toupper((unsigned char)c);
+            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
+            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
+            if (set.len[a] >= CCSX_SEGMENT_MAX_LEN) { err = where(a) + ": more than 64 bases"; return false; }
+            set.seq[a][set.len[a]++] = (uint8_t)code;
+        }
+    }
+    if (names.empty()) { err = "no FASTA record"; return false; }
+    if (names.size() < 2) { err = where(0) + ": the only record, an array has at least 2 adapters"; return false; }
+    set.n_adapters = (int32_t)names.size();
+    for (size_t k = 0; k < names.size(); ++k)
+        if (set.len[k] < CCSX_SEGMENT_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 8"; return false; }
+    return true;
+}
+
 // --control: a FASTA of exactly one record of 64 .. 4096 bases, ACGT in either case.  false + a message that names what is wrong
 bool load_control(const std::string &path, std::vector<uint8_t> &codes, std::string &err)
 {
@@ -459,6 +508,15 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--control") o.control = need(a.c_str());
         else if (a == "--barcodes") o.barcodes = need(a.c_str());
         else if (a == "--barcode-counts") o.barcode_counts = need(a.c_str());
+        else if (a == "--segment-adapters") o.segment_adapters = need(a.c_str());
+        else if (a == "--segment-counts") o.segment_counts = need(a.c_str());
+        else if (a == "--segment-min-length") {
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 1 || n > 65535) { std::fprintf(stderr, "ccs: --segment-min-length needs a number in 1 .. 65535, got '%s'\n", v.c_str()); std::exit(2); }
+            o.segment_min_length = (int)n;
+        }
         else if (a == "--barcode-window") {
             const std::string v = need(a.c_str());
             char *end = nullptr;
@@ -505,6 +563,14 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if (!o.segment_adapters.empty()) {                       // its own output mode: refused before any input is opened
+        auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --segment-adapters combined with %s is not supported\n", what); std::exit(2); };
+        if (o.by_strand) refuse("--by-strand");
+        if (!o.barcodes.empty()) refuse("--barcodes");
+        if (o.reads_bam) refuse("--reads-bam");
+        if (o.heteroduplexes) refuse("--heteroduplexes");
+        if (!o.fit_model.empty()) refuse("--fit-model");
     }
     if (o.heteroduplexes) {                                  // its own output mode: the options that make another kind of record, or that need the strands on the host
         auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --heteroduplexes combined with %s is not supported\n", what); std::exit(2); };
@@ -576,6 +642,16 @@ bool parse(int argc, char **argv, Options &o)
         if (!load_barcodes(o.barcodes, *o.barcode_set, o.barcode_names, err)) { std::fprintf(stderr, "ccs: --barcodes %s: %s\n", o.barcodes.c_str(), err.c_str()); std::exit(2); }
         ccsx_barcode_opts_default(&o.barcode_opts);
         if (o.barcode_window >= 0) o.barcode_opts.window = o.barcode_window;
+    }
+    if (o.segment_adapters.empty() && (o.segment_min_length >= 0 || !o.segment_counts.empty())) {
+        std::fprintf(stderr, "ccs: --segment-min-length and --segment-counts need --segment-adapters\n"); std::exit(2);
+    }
+    if (!o.segment_adapters.empty()) {
+        std::string err;
+        o.segment_set = std::make_shared<ccsx_segment_set>();
+        if (!load_segment_adapters(o.segment_adapters, *o.segment_set, err)) { std::fprintf(stderr, "ccs: --segment-adapters %s: %s\n", o.segment_adapters.c_str(), err.c_str()); std::exit(2); }
+        ccsx_segment_opts_default(&o.segment_opts);
+        if (o.segment_min_length >= 0) o.segment_opts.min_len = o.segment_min_length;
     }
     if (!o.control.empty()) {
         std::string err;
@@ -838,6 +914,8 @@ struct Report {
     int64_t control = 0;          // ZMWs the control screen found (--control), whatever their final status
     int64_t coverage = 0;         // ZMWs the coverage screen's gate took (--coverage-filters)
     int64_t bc_tested = 0, bc_call[4] = {0, 0, 0, 0};           // --barcodes: HiFi reads tested, and by call: none, head only, tail only, both ends
+    int64_t sg_tested = 0, sg_complete = 0, sg_with = 0, sg_without = 0, sg_overflow = 0, sg_written = 0, sg_leftover = 0;   // --segment-adapters, over the HiFi reads
+    std::map<std::array<int, 3>, int64_t> sg_classes;             // ... reads per (segments per read, orientation, complete)
     std::map<std::pair<int, int>, int64_t> bc_pairs;              // ... reads per called pair (head, tail)
     int64_t hd_zmws = 0;          // --heteroduplexes: ZMWs the split took (split: written as single-strand reads; drop: the "Heteroduplex insertions" row)
     // --heteroduplexes split: the single-strand column of the report.  It counts reads, not ZMWs (mode-heteroduplex-filtering.md:86-90); `input`, `pass`, `fail`
@@ -1008,6 +1086,16 @@ void write_report(const Options &o, const Report &r)
             for (int k = 0; k < 4; ++k) std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", rows[k], r.bc_call[which[k]], pct(r.bc_call[which[k]], r.bc_tested));
             std::fprintf(f, "\n");
         }
+        if (!o.segment_adapters.empty()) {                       // over the HiFi reads the run would write without the option (DESIGN.md §2 "Segment rule")
+            std::fprintf(f, "Segmentation\n");
+            std::fprintf(f, "%-30s: %" PRId64 "\n", "HiFi reads tested", r.sg_tested);
+            std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", "Complete arrays", r.sg_complete, pct(r.sg_complete, r.sg_tested));
+            std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", "Reads with segments", r.sg_with, pct(r.sg_with, r.sg_tested));
+            std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", "Reads without segments", r.sg_without, pct(r.sg_without, r.sg_tested));
+            std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", "Reads with adapter overflow", r.sg_overflow, pct(r.sg_overflow, r.sg_tested));
+            std::fprintf(f, "%-30s: %" PRId64 "\n", "Segments written", r.sg_written);
+            std::fprintf(f, "%-30s: %" PRId64 "\n\n", "Leftover bases", r.sg_leftover);
+        }
         if (o.reads_bam) {                                       // DESIGN.md §2 "Representative rule": what the records of OUT are
             std::fprintf(f, "Representative reads\n");
             std::fprintf(f, "%-30s: %" PRId64 "\n", "Polished reads", r.rep_cls[CCSX_REPRESENT_POLISHED]);
@@ -1058,6 +1146,10 @@ void write_report_json(const Options &o, const Report &r)
     if (!o.barcodes.empty())
         std::fprintf(f, "  \"barcode_calls\": {\"tested\": %" PRId64 ", \"both_ends\": %" PRId64 ", \"head_only\": %" PRId64 ", \"tail_only\": %" PRId64 ", \"none\": %" PRId64 "},\n",
                      r.bc_tested, r.bc_call[3], r.bc_call[1], r.bc_call[2], r.bc_call[0]);
+    if (!o.segment_adapters.empty())
+        std::fprintf(f, "  \"segmentation\": {\"tested\": %" PRId64 ", \"complete_arrays\": %" PRId64 ", \"with_segments\": %" PRId64 ", \"without_segments\": %" PRId64
+                        ", \"overflow\": %" PRId64 ", \"segments_written\": %" PRId64 ", \"leftover_bases\": %" PRId64 "},\n",
+                     r.sg_tested, r.sg_complete, r.sg_with, r.sg_without, r.sg_overflow, r.sg_written, r.sg_leftover);
     if (o.reads_bam)
         std::fprintf(f, "  \"representative_reads\": {\"polished\": %" PRId64 ", \"draft\": %" PRId64 ", \"subread\": %" PRId64 "},\n",
                      r.rep_cls[CCSX_REPRESENT_POLISHED], r.rep_cls[CCSX_REPRESENT_DRAFT], r.rep_cls[CCSX_REPRESENT_SUBREAD]);
@@ -1093,6 +1185,16 @@ void write_barcode_counts(const Options &o, const Report &r)
     if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", o.barcode_counts.c_str()); return; }
     for (const auto &kv : r.bc_pairs)
         std::fprintf(f, "%s\t%s\t%" PRId64 "\n", o.barcode_names[kv.first.first].c_str(), o.barcode_names[kv.first.second].c_str(), kv.second);
+    std::fclose(f);
+}
+
+// --segment-counts: one line per class of HiFi reads, in increasing (segments per read, orientation, complete): those three and the reads.  orientation: -1 no
+// segment, 0 forward, 1 reverse, 2 mixed
+void write_segment_counts(const Options &o, const Report &r)
+{
+    FILE *f = std::fopen(o.segment_counts.c_str(), "w");
+    if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", o.segment_counts.c_str()); return; }
+    for (const auto &kv : r.sg_classes) std::fprintf(f, "%d\t%d\t%d\t%" PRId64 "\n", kv.first[0], kv.first[1], kv.first[2], kv.second);
     std::fclose(f);
 }
 
@@ -1593,6 +1695,8 @@ int main(int argc, char **argv)
         const bool control = !opt.control.empty();
         const bool coverage = opt.coverage_filters;
         const bool barcodes = !opt.barcodes.empty();
+        const bool segments = !opt.segment_adapters.empty();
+        static_assert(sizeof(ccsx_segment_piece) * CCSX_SEGMENT_MAX_PIECES == 192 * 4, "the segment list is carved as 192 words per ZMW");
         // The views of a staged batch's results and reports, carved from a page-locked arena of its device's pool, and the requests that point to them: every
         // ticket of the run is given the same (finder: plus the heteroduplex request, which the single-strand tickets of --heteroduplexes split do not carry)
         static_assert(sizeof(ccsx_hd_site) == 24, "the finder's site list is carved as 96 words per ZMW");
@@ -1603,7 +1707,7 @@ int main(int argc, char **argv)
             b->cap = cap;
             b->out_arena = out_pool.get();
             const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-            uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (opt.reads_bam ? 2 : 0) + (finder ? 103 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+            uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (segments ? 8 + 192 : 0) + (opt.reads_bam ? 2 : 0) + (finder ? 103 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
             auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
             auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
             b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
@@ -1653,6 +1757,12 @@ int main(int argc, char **argv)
                 for (auto &q : two) q = (int32_t *)take(2 * n4);
                 b->brep = ccsx_barcode_report{n, b3[0], b3[1], b3[2], two[0], two[1], two[2], two[3]};
                 b->breq = ccsx_barcode_request{&opt.barcode_opts, opt.barcode_set.get(), &b->brep, {0, 0}};
+            }
+            if (segments) {                          // the eight planes: n each; the list: [n][64] of 12 bytes
+                const auto g = planes(8);
+                ccsx_segment_piece *list = (ccsx_segment_piece *)take(192 * n4);
+                b->srep = ccsx_segment_report{n, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], list};
+                b->sreq = ccsx_segment_request{&opt.segment_opts, opt.segment_set.get(), &b->srep, {0, 0}};
             }
             if (opt.reads_bam) {
                 const auto r2 = planes(2);
@@ -1867,7 +1977,8 @@ int main(int argc, char **argv)
                 // the most general submit: NULL for the extras and for every request this run did not ask for (the narrower entry points stage the same)
                 if (opt.heteroduplexes ? ccsx_submit_hd_requests(h, &b->cb, &b->cr, &b->reqs, &b->hreq, &t)
                     : opt.reads_bam ? ccsx_submit_represent(h, &b->cb, &b->cr, &b->reqs, &b->rreq, &t)
-                                  : barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
+                                  : barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t)
+                                  : segments ? ccsx_submit_segments(h, &b->cb, &b->cr, &b->reqs, &b->sreq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1916,10 +2027,12 @@ int main(int argc, char **argv)
                                               35,35,35,35,35,35,35,35,35,35, 40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,
                                               40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40};
             static const char *const kStrandRG[2] = {"ccsamd02", "ccsamd03"};   // --heteroduplexes split: the read groups of the /fwd and the /rev reads
-            // a CCS record of ZMW slot s as the main output writes it (tags the run asks for); the caller adds its own and finishes it
-            auto build = [&](const ZmwIn &z, Batch &bt, int s) {
-                const int64_t o = bt.seq_off[s]; const int32_t len = bt.seq_len[s];
-                const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
+            // a CCS record of ZMW slot s as the main output writes it (tags the run asks for); the caller adds its own and finishes it.  to >= 0: the record of
+            // the slice [from, to) of SEQ (--segment-adapters), named after it: SEQ, QUAL and every per-base tag are the slice, the scalar tags the read's
+            auto build = [&](const ZmwIn &z, Batch &bt, int s, int32_t from = 0, int32_t to = -1) {
+                const int64_t o = bt.seq_off[s] + from; const int32_t len = (to >= 0 ? to : bt.seq_len[s]) - from;
+                const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : "")) +
+                                          (to >= 0 ? "/" + std::to_string(from) + "_" + std::to_string(to) : "");
                 rb.begin(qname, bt.seq + o, bt.qual + o, (uint32_t)len);
                 rb.tagZ("RG", hd_split && z.strand_tag ? kStrandRG[z.strand_tag - 1] : "ccsamd01");   // (--heteroduplexes split: a single-strand read names its strand's group)
                 rb.tagf("ec", bt.ec[s]);
@@ -1935,7 +2048,7 @@ int main(int argc, char **argv)
                         rb.tagBC("ip", fi, nf); rb.tagBC("pw", fp, nf);
                     } else {
                         rb.tagBC("fi", fi, nf); rb.tagBC("fp", fp, nf); rb.tagi("fn", bt.fn[s]);
-                        kin_rev.assign(ri, ri + nr); std::reverse(kin_rev.begin(), kin_rev.end());   // reverse strand: its own orientation
+                        kin_rev.assign(ri, ri + nr); std::reverse(kin_rev.begin(), kin_rev.end());   // reverse strand: its own orientation (a slice: taken in SEQ coordinates first)
                         rb.tagBC("ri", kin_rev.data(), nr);
                         kin_rev.assign(rp, rp + nr); std::reverse(kin_rev.begin(), kin_rev.end());
                         rb.tagBC("rp", kin_rev.data(), nr); rb.tagi("rn", bt.rn[s]);
@@ -2116,6 +2229,32 @@ int main(int argc, char **argv)
                         rb.finish(*failp); ++rep.fail_records;
                         return;
                     }
+                    if (segments) {                                 // --segment-adapters: one record per segment in place of the read's (DESIGN.md §2 "Segment rule")
+                        const ccsx_segment_report &g = bt.srep;
+                        const int ns = g.tested[s] ? g.n_segments[s] : 0;
+                        rep.sg_tested += g.tested[s] ? 1 : 0; rep.sg_complete += g.complete[s]; rep.sg_leftover += g.leftover_bases[s];
+                        ++(g.overflow[s] ? rep.sg_overflow : ns ? rep.sg_with : rep.sg_without);
+                        ++rep.sg_classes[{ns, g.orient[s], g.complete[s]}];
+                        for (int k = 0; k < ns; ++k) {
+                            const ccsx_segment_piece &p = g.pieces[(size_t)s * CCSX_SEGMENT_MAX_PIECES + k];
+                            const int32_t plen = p.end - p.start;
+                            if (bt.rq[s] >= 0.99f) for (int32_t q = p.start; q < p.end; ++q) rep.bases_q30 += bt.qual[o + q] >= 30 ? 1 : 0;
+                            if (fastq) put_fastq(movie + "/" + std::to_string(z.zm) + "/ccs/" + std::to_string(p.start) + "_" + std::to_string(p.end), bt, o + p.start, plen);
+                            else {
+                                build(z, bt, s, p.start, p.end);
+                                // (di, dl, dr: the tag names are recalled from the vendor's segmentation tool, which is not in the reference mount, as bam_io.h
+                                // says of the .pbi layout; dl / dr: the adapters' numbers in the FASTA, as read left to right)
+                                rb.tagi("di", p.index); rb.tagi("dl", p.index + (p.reverse ? 1 : 0)); rb.tagi("dr", p.index + (p.reverse ? 0 : 1));
+                                marks.push_back(outp->mark());
+                                pbi.rg_id.push_back(0); pbi.q_start.push_back(p.start); pbi.q_end.push_back(p.end); pbi.hole.push_back(z.zm);
+                                pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
+                                rb.finish(*outp);
+                            }
+                            rep.lens.push_back(plen); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]); rep.ss.push_back(ss); rep.holes.push_back(z.zm);
+                            ++rep.sg_written;
+                        }
+                        return;
+                    }
                     if (bt.rq[s] >= 0.99f) for (int32_t q = 0; q < len; ++q) rep.bases_q30 += bt.qual[o + q] >= 30 ? 1 : 0;
                     const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                     const bool bc_both = barcodes && bt.brep.tested[s] && bt.brep.call[s] == 3;   // --barcodes: counted over the HiFi reads, tagged at both ends called
@@ -2195,6 +2334,7 @@ int main(int argc, char **argv)
         if (!opt.suppress_reports || opt.report_named) write_report(opt, rep);
         if (!opt.report_json.empty()) write_report_json(opt, rep);            // named files are written even under --suppress-reports (docs/faq/sqiie.md:36-46
         if (!opt.barcode_counts.empty()) write_barcode_counts(opt, rep);
+        if (!opt.segment_counts.empty()) write_segment_counts(opt, rep);
         if (!opt.hifi_summary.empty()) write_hifi_summary(opt, rep);          //  combines --suppress-reports with explicit report names)
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         if (opt.log_level >= 2)

@@ -140,6 +140,7 @@ struct Slot {
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
     DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
+    DevBuf d_sg;                                  // segmentation only (ccsx_segment_request): the set's masks and lengths, then the report (ccsx_sg_out)
     DevBuf d_bc;                                  // barcode calls only (ccsx_barcode_request): the set's masks and lengths, then the [11][n] report
     DevBuf d_rp;                                  // representative reads only (ccsx_represent_request): the [2][n] report
     DevBuf d_rf_tiles, d_rf_base, d_rf_rep;       // polisher hand-back only (ccsx_submit_refine): the tile list and its classes; base lengths, backbones, seq, qual; the report
@@ -148,6 +149,7 @@ struct Slot {
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
     PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
+    PinVec<unsigned long long> sg_set;            // segmentation only: the masks and lengths as uploaded (a ticket's set is its own)
     PinVec<unsigned long long> bc_set;            // barcode calls only: the masks and lengths as uploaded (a ticket's set is its own, as its control is)
     PinVec<int32_t> anchor;                       // pass orientation only: the anchor pass of every ZMW as uploaded
     bool orient_pending = false, orient_ran = false;   // the staged batch carries the bit and k_orient has yet to run on it / has run (its report is on the device)
@@ -200,6 +202,7 @@ struct ccsx_handle_s {
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
+    DevBuf d_sg_reads;                // ccsx_segment_reads only: the call's set, reads and report (no slot is touched)
     DevBuf d_bc_reads;                // ccsx_barcode_reads only: the call's set, reads and report (no slot is touched)
     DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
     ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
@@ -391,6 +394,7 @@ struct Wants {
     const ccsx_orient_opts *orient = nullptr;   // ccsx_orient_batch's own options (NULL: the handle's, ccsx_set_orient_opts); already checked
     const ccsx_handoff_request *handoff = nullptr; ccsx_handoff_opts handoff_opts{}; ccsx_handoff_out handoff_out{};   // (the out struct is copied: it is read during the call only)
     const ccsx_barcode_request *barcodes = nullptr; ccsx_barcode_opts barcode_opts{}; std::vector<unsigned long long> barcode_set; int barcode_n = 0;   // (the set packed: barcode_words)
+    const ccsx_segment_request *segments = nullptr; ccsx_segment_opts segment_opts{}; std::vector<unsigned long long> segment_set; int segment_n = 0;   // (the set packed: segment_words)
     bool represent = false; ccsx_represent_request represent_req{};   // (the request is copied: it is read during the call only)
     bool handoff_written_only = false;          // the synchronous form: counts is known when the copies are enqueued, only the written slots are copied
 };
@@ -1246,6 +1250,65 @@ static int enqueue_barcode_download(const BarcodeParams &B, const ccsx_barcode_r
     return 0;
 }
 
+// ---- the segmentation's host side (DESIGN.md §2 "Segment rule"; the checks and the packing: ccsx_segment_api.cpp), in the barcode calls' shape.  A packed set
+// is its masks, [2 * n_adapters][8] words, then the searches' lengths, one byte each, in whole words: what the slot uploads in one copy
+static size_t segment_words(int na) { return (size_t)na * 2 * CCSX_SG_MASK_WORDS + ((size_t)na * 2 + 7) / 8; }
+static void segment_pack(const ccsx_segment_set *set, std::vector<unsigned long long> *packed)
+{
+    packed->assign(segment_words(set->n_adapters), 0ull);
+    ccsx_segment_pack(set, packed->data(), reinterpret_cast<uint8_t *>(packed->data() + (size_t)set->n_adapters * 2 * CCSX_SG_MASK_WORDS));
+}
+
+static int segment_request_check(const ccsx_segment_request *q, const ccsx_batch *b, std::vector<unsigned long long> *packed, ccsx_segment_opts *o, const char *fn)
+{
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": segment request: reserved must be 0"); return -1; }
+    if (ccsx_segment_check(q->set, q->opts, q->report, b->n_zmw, fn, o)) return -1;
+    segment_pack(q->set, packed);
+    return 0;
+}
+
+// k_segment's parameters for a packed set at `dev` (the report follows it) and the reads it is given
+static SegmentParams segment_params(void *dev, size_t words, int na, int n, const ccsx_segment_opts &o, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len)
+{
+    SegmentParams G{};
+    G.n = n; G.n_adapters = na; G.opts = o; G.seq = seq; G.seq_off = seq_off; G.seq_len = seq_len;
+    G.masks = (const unsigned long long *)dev; G.len = (const uint8_t *)(G.masks + (size_t)na * 2 * CCSX_SG_MASK_WORDS); G.rep = (int32_t *)(G.masks + words);
+    return G;
+}
+
+// The set is the slot's own, in page-locked memory that lives as long as the slot: its copy is enqueued on `st` with the slot's other uploads.  k_segment reads
+// the results where k_stitch leaves them.
+static int segment_attach(Slot &S, const std::vector<unsigned long long> &packed, int na, const ccsx_segment_opts &o, hipStream_t st)
+{
+    KParams &P = S.P;
+    const size_t n = (size_t)P.n_zmw, words = packed.size();
+    if (S.d_sg.reserve(words * 8 + ccsx_sg_rep_bytes(n)) || S.sg_set.resize(words)) return -2;
+    std::copy(packed.begin(), packed.end(), S.sg_set.p);
+    P.sg = segment_params(S.d_sg.p, words, na, (int)n, o, P.out_seq, P.seq_off, P.out_len);
+    if (hipError_t e = hipMemcpyAsync(S.d_sg.p, S.sg_set.p, words * 8, hipMemcpyHostToDevice, st)) {
+        ccsx_set_error(std::string("segmentation: set upload: ") + hipGetErrorString(e)); return -2;
+    }
+    return 0;
+}
+
+// the report's planes and list into the caller's arrays, on `s`
+static int enqueue_segment_download(const SegmentParams &G, const ccsx_segment_report *r, hipStream_t s)
+{
+    const size_t n = (size_t)G.n;
+    if (!n) return 0;
+    const SegmentOut d = ccsx_sg_out(G.rep, n);
+    HIPTRY(hipMemcpyAsync(r->tested, d.tested, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->overflow, d.overflow, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->n_hits, d.n_hits, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->n_cuts, d.n_cuts, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->n_segments, d.n_segments, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->complete, d.complete, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->orient, d.orient, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->leftover_bases, d.leftover, n * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(r->pieces, d.pieces, n * CCSX_SEGMENT_MAX_PIECES * sizeof(ccsx_segment_piece), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // ---- the representative reads' host side (DESIGN.md §2 "Representative rule"; the request's checks: ccsx_represent_api.cpp).  k_represent's parameters are the
 // slot's own inputs, final drafts and result planes: nothing is uploaded, the [2][n] report is all it reserves.
 static int represent_attach(Slot &S, const ccsx_represent_request &q)
@@ -1282,9 +1345,13 @@ static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string
 // against, and that check refuses the call).
 static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                        const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr,
-                       const ccsx_handoff_request *handoff = nullptr, const ccsx_barcode_request *barcodes = nullptr)
+                       const ccsx_handoff_request *handoff = nullptr, const ccsx_barcode_request *barcodes = nullptr, const ccsx_segment_request *segments = nullptr)
 {
     *W = Wants{};
+    if (segments && handoff) return refuse(fn, "the segment request and the hand-off are not combined");
+    if (segments && hd) return refuse(fn, "the segment and the heteroduplex requests are not combined");
+    if (segments && barcodes) return refuse(fn, "the segment and the barcode requests are not combined");
+    if (segments && b && segment_request_check(segments, b, &W->segment_set, &W->segment_opts, fn)) return -1;
     if (barcodes && handoff) return refuse(fn, "the barcode request and the hand-off are not combined");
     if (barcodes && hd) return refuse(fn, "the barcode and the heteroduplex requests are not combined");
     if (barcodes && b && barcode_request_check(barcodes, b, &W->barcode_set, &W->barcode_opts, fn)) return -1;
@@ -1296,6 +1363,7 @@ static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const c
     if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
     W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = handoff; W->barcodes = barcodes; W->barcode_n = barcodes && barcodes->set ? barcodes->set->n_barcodes : 0;
+    W->segments = segments; W->segment_n = segments && segments->set ? segments->set->n_adapters : 0;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
@@ -1312,6 +1380,7 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.coverage && (rc = coverage_attach(h, S, W.coverage_opts, W.coverage->gate))) return rc;
     if (W.handoff && (rc = handoff_attach(S, W.handoff_opts, W.handoff_out.max_tiles))) return rc;
     if (W.barcodes && (rc = barcode_attach(S, W.barcode_set, W.barcode_n, W.barcode_opts, st))) return rc;
+    if (W.segments && (rc = segment_attach(S, W.segment_set, W.segment_n, W.segment_opts, st))) return rc;
     if (W.represent && (rc = represent_attach(S, W.represent_req))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
@@ -1347,6 +1416,7 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
     }
     if (W.handoff && (rc = enqueue_handoff_download(S, W.handoff_out, W.handoff_written_only, s))) return rc;
     if (W.barcodes && (rc = enqueue_barcode_download(S.P.bc, W.barcodes->report, s))) return rc;
+    if (W.segments && (rc = enqueue_segment_download(S.P.sg, W.segments->report, s))) return rc;
     if (W.represent && n) {
         const ccsx_represent_report *r = W.represent_req.report;
         if ((rc = download_planes({r->cls, r->pass}, S.P.rep.rep, n, s))) return rc;
@@ -1563,12 +1633,12 @@ int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, c
 }
 // the members of a ccsx_requests as build_wants takes them (NULL: none); -1 for nonzero reserved words
 static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_handoff_request *handoff = nullptr,
-                          const ccsx_barcode_request *barcodes = nullptr, const ccsx_hd_request *hd = nullptr)
+                          const ccsx_barcode_request *barcodes = nullptr, const ccsx_hd_request *hd = nullptr, const ccsx_segment_request *segments = nullptr)
 {
     static const ccsx_requests none = {};
     if (!rq) rq = &none;
     if (rq->reserved[0] || rq->reserved[1] || rq->reserved[2]) return refuse(fn, "ccsx_requests: reserved must be NULL");
-    return build_wants(rq->ex, hd, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff, barcodes);
+    return build_wants(rq->ex, hd, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff, barcodes, segments);
 }
 // the Wants of a call with a heteroduplex request beside the members of rq (the four ccsx_*_hd* entry points): the checks of ccsx_submit_hd, in its order
 static int hd_requests_wants(const ccsx_requests *rq, const ccsx_hd_request *hd, const ccsx_batch *b, const char *fn, Wants *W)
@@ -1605,6 +1675,12 @@ int ccsx_submit_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, 
 {
     Wants W;
     if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg, ccsx_ticket *ticket)
+{
+    Wants W;
+    if ((!sg && refuse(__func__, "null segment request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, nullptr, nullptr, sg)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 // the Wants of a call with a representative request: the request checked against the batch and the handle's options and copied, then the members of rq
@@ -1911,6 +1987,13 @@ int ccsx_consensus_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *re
     return consensus_sync(h, b, res, W, __func__);
 }
 
+int ccsx_consensus_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg)
+{
+    Wants W;
+    if ((!sg && refuse(__func__, "null segment request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, nullptr, nullptr, sg)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
 int ccsx_consensus_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rp)
 {
     Wants W;
@@ -1951,6 +2034,43 @@ int ccsx_barcode_reads(ccsx_handle h, const ccsx_barcode_set *set, const ccsx_ba
     barcode_pack(set, &packed);
     HIPTRY(hipSetDevice(h->device));
     const int rc = barcode_reads_enqueue(h, packed, set->n_barcodes, o, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
+    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+// k_segment on the caller's reads, as barcode_reads_enqueue.  Layout of the buffer: [set + report][seq_off: n x 8][seq_len: n x 4, padded][seq]
+static int segment_reads_enqueue(ccsx_handle h, const std::vector<unsigned long long> &packed, int na, const ccsx_segment_opts &o, const uint8_t *seq,
+                                 const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes, const ccsx_segment_report *report, hipStream_t st)
+{
+    const size_t words = packed.size(), head = words * 8 + ccsx_sg_rep_bytes((size_t)n), head8 = (head + 7) & ~(size_t)7, len4 = ((size_t)n * 4 + 7) & ~(size_t)7;
+    if (h->d_sg_reads.reserve(head8 + (size_t)n * 8 + len4 + (size_t)bytes)) return -2;
+    uint8_t *base = (uint8_t *)h->d_sg_reads.p;
+    int64_t *d_off = (int64_t *)(base + head8);
+    int32_t *d_len = (int32_t *)(base + head8 + (size_t)n * 8);
+    uint8_t *d_seq = base + head8 + (size_t)n * 8 + len4;
+    HIPTRY(hipMemcpyAsync(base, packed.data(), words * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (bytes) HIPTRY(hipMemcpyAsync(d_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
+    const SegmentParams G = segment_params(base, words, na, n, o, d_seq, d_off, d_len);
+    (void)hipGetLastError();
+    if (const char *failed = ccsx_segment_launch(G, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    return enqueue_segment_download(G, report, st);
+}
+
+int ccsx_segment_reads(ccsx_handle h, const ccsx_segment_set *set, const ccsx_segment_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
+                       int32_t n, ccsx_segment_report *report)
+{
+    ccsx_segment_opts o;
+    int64_t bytes;
+    if (ccsx_segment_check(set, opts, report, n, __func__, &o) || ccsx_barcode_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
+    if (!h) return refuse(__func__, "null argument");
+    if (n == 0) return 0;
+    std::vector<unsigned long long> packed;
+    segment_pack(set, &packed);
+    HIPTRY(hipSetDevice(h->device));
+    const int rc = segment_reads_enqueue(h, packed, set->n_adapters, o, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
     if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
     HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;

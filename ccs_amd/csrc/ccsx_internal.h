@@ -41,6 +41,12 @@ int ccsx_barcode_check_reads(const uint8_t *seq, const int64_t *seq_off, const i
 // k_barcode's view of a checked set: masks [n_barcodes][4], len [n_barcodes]
 void ccsx_barcode_pack(const ccsx_barcode_set *set, unsigned long long *masks, uint8_t *len);
 
+// ---- segmentation (ccsx_segment_api.cpp; DESIGN.md §2 "Segment rule"): what every entry point shares, in the barcode calls' shape.  Caller-supplied reads are
+// checked by ccsx_barcode_check_reads.
+int ccsx_segment_check(const ccsx_segment_set *set, const ccsx_segment_opts *opts, const ccsx_segment_report *report, int64_t n, const char *fn, ccsx_segment_opts *o);
+// k_segment's view of a checked set: masks [2 * n_adapters][8], len [2 * n_adapters]
+void ccsx_segment_pack(const ccsx_segment_set *set, unsigned long long *masks, uint8_t *len);
+
 // ---- representative reads (ccsx_represent_api.cpp; DESIGN.md §2 "Representative rule"): the request against the batch it is for and the options of the run — flags,
 // reserved words, the report's arrays and size, kinetics without opts.hifi_kinetics or batch.ipd.  A refusal sets the error under `fn` and returns -1.
 int ccsx_represent_check(const ccsx_represent_request *req, const ccsx_batch *b, const ccsx_opts *opts, const char *fn);

@@ -5257,6 +5257,10 @@ struct Schedule {
             failed = ccsx_barcode_launch(P.bc, sp);
             trace_sync(sp, "k_barcode");
         }
+        if (P.sg.rep && !failed) {                         // segmentation of the final consensus (a batch with a ccsx_segment_request only)
+            failed = ccsx_segment_launch(P.sg, sp);
+            trace_sync(sp, "k_segment");
+        }
         if (P.rep.rep && !failed) {                        // representative reads into the result planes (a batch with a ccsx_represent_request only)
             failed = ccsx_represent_launch(P.rep, sp);
             trace_sync(sp, "k_represent");

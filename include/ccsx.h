@@ -869,6 +869,74 @@ int         ccsx_consensus_represent(ccsx_handle h, const ccsx_batch *b, ccsx_re
 int         ccsx_submit_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rep,
                                   ccsx_ticket *ticket);
 
+/* ---- segmentation of concatenated-array reads (the rule: DESIGN.md §2 "Segment rule", its own version ccsx_segment_rule_version; this build's own, the
+ * reference documents none of it, as it documents none of the barcode calls; no result of the consensus changes).  A read of such a library is
+ * A0 S1 A1 S2 .. SK AK or the reverse complement of the whole: A0 .. AK are the adapters of a caller-supplied ordered set, S1 .. SK the segments.  k_segment looks
+ * for every adapter and its reverse complement over the whole read by unit-cost edit distance (search 2a: adapter a as given, search 2a + 1: its reverse
+ * complement; a hit is what ccsx_adapter_hit defines, at up to floor(m * max_dist_pct / 100) edits), orders the hits by (dist, start, search, end), takes a hit
+ * iff it intersects no hit taken before (the cuts), and classifies the pieces between neighbouring cuts: a piece of at least min_len bases between searches 2a
+ * and 2(a + 1) is segment a, forward; one between searches 2(a + 1) + 1 and 2a + 1 is segment a, reverse; every other piece of positive length, the read's head
+ * and tail included, is leftover.  More than CCSX_SEGMENT_MAX_HITS hits: overflow, no cuts and no segments.  Integers only.  Detection only: nothing is cut.
+ *   ccsx_segment_reads_host  the rule on the calling thread, without a device: the reference of the tests.
+ *   ccsx_segment_reads       k_segment on caller-supplied reads (HiFi reads from anywhere).  Synchronous.  It uses buffers of the handle's own and the polish stream:
+ *                            no slot is staged or recycled, and the call returns after the tickets in flight have left the polish stream (as ccsx_barcode_reads).
+ *   ccsx_consensus_segments  synchronous (slot 0), as ccsx_consensus_requests: k_segment runs on the polish stream after k_stitch, on res->seq / res->seq_len as they
+ *                            are on the device.
+ *   ccsx_submit_segments     ticketed like ccsx_submit_requests: the report's arrays follow the lifetime rule of `res` and should be page-locked; the request, set
+ *                            and options structs are read during the call only (every ticket carries its own set and options).
+ * rq may be NULL or carry any member of ccsx_requests.  The request is not combined with ccsx_hd_request, ccsx_handoff_request, ccsx_barcode_request or
+ * ccsx_represent_request: no entry point takes both.  The two ccsx_segment_reads forms: opts NULL = ccsx_segment_opts_default; reads as for ccsx_barcode_reads.
+ * Errors of the call (nothing is enqueued, reserved or launched): a null argument, n_adapters outside 2 .. CCSX_SEGMENT_MAX_ADAPTERS, a length outside 8 .. 64,
+ * a code above 3, options out of range, a nonzero reserved word, a report sized for another batch (n_zmw != n) or with a NULL array, n < 0, a negative seq_off.
+ * Without a request nothing of it is launched, reserved or copied.  ccsx_segment_chunk: the bases of one item of k_segment (the tests place hits at its edges). */
+#define CCSX_SEGMENT_MAX_ADAPTERS 33
+#define CCSX_SEGMENT_MIN_LEN      8
+#define CCSX_SEGMENT_MAX_LEN      64
+#define CCSX_SEGMENT_MAX_HITS     64
+#define CCSX_SEGMENT_MAX_PIECES   64
+typedef struct ccsx_segment_opts {
+    int32_t max_dist_pct;        /* an adapter of m bases hits at up to floor(m * max_dist_pct / 100) edits, 0 .. 30 [15]                                        */
+    int32_t min_len;             /* a piece shorter than this is no segment, 1 .. 65535 [50]                                                                     */
+} ccsx_segment_opts;
+typedef struct ccsx_segment_set {
+    int32_t n_adapters;          /* 2 .. CCSX_SEGMENT_MAX_ADAPTERS, in array order                                                                               */
+    int32_t len[CCSX_SEGMENT_MAX_ADAPTERS];                            /* CCSX_SEGMENT_MIN_LEN .. CCSX_SEGMENT_MAX_LEN; lengths may differ within a set          */
+    uint8_t seq[CCSX_SEGMENT_MAX_ADAPTERS][CCSX_SEGMENT_MAX_LEN];      /* codes 0 .. 3 (A C G T)                                                                 */
+} ccsx_segment_set;
+typedef struct ccsx_segment_piece {
+    int32_t start, end;          /* the segment is read[start, end): between its two cuts                                                                        */
+    uint8_t index;               /* a: the segment between adapters a and a + 1                                                                                  */
+    uint8_t reverse;             /* 0: as the set reads (adapter a on its left); 1: reverse complemented (adapter a + 1 on its left)                             */
+    uint8_t dist_left, dist_right;   /* the edit distances of the cuts on its left and right                                                                     */
+} ccsx_segment_piece;
+typedef struct ccsx_segment_report {
+    int32_t  n_zmw;
+    int32_t *tested;             /* [n_zmw] 1: seq_len > 0; 0: untested (orient -1, everything else 0)                                                            */
+    int32_t *overflow;           /* [n_zmw] 1: more than CCSX_SEGMENT_MAX_HITS hits (adapter junk): only tested and n_hits differ from an untested read           */
+    int32_t *n_hits;             /* [n_zmw] every hit of every search, not capped                                                                                */
+    int32_t *n_cuts;             /* [n_zmw] the hits taken by the selection                                                                                      */
+    int32_t *n_segments;         /* [n_zmw]                                                                                                                      */
+    int32_t *complete;           /* [n_zmw] 1: one orientation, segments 0 .. n_adapters - 2 each once, in array order                                           */
+    int32_t *orient;             /* [n_zmw] -1: no segment; 0: all forward; 1: all reverse; 2: mixed                                                             */
+    int32_t *leftover_bases;     /* [n_zmw] the bases of the pieces that are no segment                                                                          */
+    ccsx_segment_piece *pieces;  /* [n_zmw][CCSX_SEGMENT_MAX_PIECES] the segments by increasing start; entries beyond n_segments are zero                        */
+} ccsx_segment_report;
+typedef struct ccsx_segment_request {
+    const ccsx_segment_opts *opts;       /* NULL = ccsx_segment_opts_default                                                                                     */
+    const ccsx_segment_set  *set;
+    ccsx_segment_report     *report;
+    int32_t                  reserved[2];   /* must be 0                                                                                                         */
+} ccsx_segment_request;
+void        ccsx_segment_opts_default(ccsx_segment_opts *o);
+int         ccsx_segment_rule_version(void);
+int         ccsx_segment_chunk(void);
+int         ccsx_segment_reads_host(const ccsx_segment_set *set, const ccsx_segment_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
+                                    int32_t n, ccsx_segment_report *report);
+int         ccsx_segment_reads(ccsx_handle h, const ccsx_segment_set *set, const ccsx_segment_opts *opts, const uint8_t *seq, const int64_t *seq_off,
+                               const int32_t *seq_len, int32_t n, ccsx_segment_report *report);
+int         ccsx_consensus_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg);
+int         ccsx_submit_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg, ccsx_ticket *ticket);
+
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
  * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one
