@@ -681,6 +681,66 @@ class OrientReport:
                              _ptr(self.votes_opp, C.c_int32))
 
 
+# ---- the analyses on final reads (barcode calls, segmentation): what they share.  Each supplies a set (a _PatternSet), an opts struct and a report class that
+# names its request struct, its opts default and its ccsx_*_reads symbol (REQUEST, OPTS_DEFAULT, READS)
+class _PatternSet:
+    """a set struct of the C ABI: a count, len[max] and seq[max][max_len].  COUNT: the count's field; NOUN: what a message calls a pattern"""
+
+    @classmethod
+    def from_strings(cls, seqs):
+        """from ACGT strings (either case) or arrays of codes; lengths, codes and the count are checked by the call that takes the set"""
+        seqs = list(seqs)
+        max_n = cls.len.size // 4
+        max_len = cls.seq.size // max_n
+        if len(seqs) > max_n:
+            raise ValueError(f"at most {max_n} {cls.NOUN}s")
+        s = cls()
+        setattr(s, cls.COUNT, len(seqs))
+        flat = np.frombuffer(s, np.uint8, max_n * max_len, cls.seq.offset).reshape(max_n, max_len)
+        for k, q in enumerate(seqs):
+            codes = ["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q]
+            if len(codes) > max_len:
+                raise ValueError(f"{cls.NOUN} {k}: more than {max_len} bases")
+            s.len[k] = len(codes)
+            flat[k, : len(codes)] = codes
+        return s
+
+    from_codes = from_strings
+
+    def codes(self) -> list:
+        return [np.array(self.seq[k][: self.len[k]], np.uint8) for k in range(getattr(self, self.COUNT))]
+
+
+def _pattern_request(rep_cls, pset, opts, crep):
+    """the request struct of rep_cls's analysis: (struct, what must outlive it)"""
+    o = opts if opts is not None else rep_cls.OPTS_DEFAULT()
+    return rep_cls.REQUEST(C.pointer(o), C.pointer(pset), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (pset, o, crep)
+
+
+def _reads_args(rep_cls, pset, opts, reads, report):
+    """the arguments of ccsx_*_reads[_host] of rep_cls's analysis for a list of code arrays: (args, report, keep)"""
+    reads = [np.ascontiguousarray(r, np.uint8) for r in reads]
+    n = len(reads)
+    seq_len = np.array([len(r) for r in reads], np.int32).reshape(n)
+    seq_off = np.zeros(n, np.int64)
+    if n:
+        seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64)
+    seq = np.concatenate(reads + [np.zeros(1, np.uint8)])
+    rep = report if report is not None else rep_cls.allocate(n)
+    crep = rep.c_struct()
+    o = opts if opts is not None else rep_cls.OPTS_DEFAULT()
+    keep = (pset, o, seq, seq_off, seq_len, crep, rep)
+    return (C.byref(pset), C.byref(o), _ptr(seq, C.c_uint8), _ptr(seq_off, C.c_int64), _ptr(seq_len, C.c_int32), n, C.byref(crep)), rep, keep
+
+
+def _reads_host(rep_cls, pset, reads, opts, report):
+    args, rep, _keep = _reads_args(rep_cls, pset, opts, reads, report)
+    name = rep_cls.READS + "_host"
+    if getattr(lib(), name)(*args) != 0:
+        raise RuntimeError(name + " failed: " + lib().ccsx_last_error().decode())
+    return rep
+
+
 # ---- barcode calls (include/ccsx.h ccsx_barcode_*; DESIGN.md §2 "Barcode calls")
 BARCODE_MAX, BARCODE_MIN_LEN, BARCODE_MAX_LEN, BARCODE_MAX_WINDOW = 384, 8, 64, 1024
 BARCODE_HEAD, BARCODE_TAIL = 1, 2                # the bits of BarcodeReport.call
@@ -690,31 +750,10 @@ class BarcodeOpts(C.Structure):
     _fields_ = [("window", C.c_int32), ("max_dist_pct", C.c_int32), ("min_margin", C.c_int32)]
 
 
-class BarcodeSet(C.Structure):
+class BarcodeSet(_PatternSet, C.Structure):
     """ccsx_barcode_set: up to 384 barcodes of 8 .. 64 codes 0 .. 3.  The barcode at a read's tail is looked for on the reverse complement of the read"""
     _fields_ = [("n_barcodes", C.c_int32), ("len", C.c_int32 * BARCODE_MAX), ("seq", (C.c_uint8 * BARCODE_MAX_LEN) * BARCODE_MAX)]
-
-    @staticmethod
-    def from_strings(seqs) -> "BarcodeSet":
-        """from ACGT strings (either case) or arrays of codes; lengths, codes and the count are checked by the call that takes the set"""
-        seqs = list(seqs)
-        if len(seqs) > BARCODE_MAX:
-            raise ValueError(f"at most {BARCODE_MAX} barcodes")
-        s = BarcodeSet()
-        s.n_barcodes = len(seqs)
-        flat = np.frombuffer(s, np.uint8, BARCODE_MAX * BARCODE_MAX_LEN, BarcodeSet.seq.offset).reshape(BARCODE_MAX, BARCODE_MAX_LEN)
-        for b, q in enumerate(seqs):
-            codes = ["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q]
-            if len(codes) > BARCODE_MAX_LEN:
-                raise ValueError(f"barcode {b}: more than {BARCODE_MAX_LEN} bases")
-            s.len[b] = len(codes)
-            flat[b, : len(codes)] = codes
-        return s
-
-    from_codes = from_strings
-
-    def codes(self) -> list:
-        return [np.array(self.seq[b][: self.len[b]], np.uint8) for b in range(self.n_barcodes)]
+    COUNT, NOUN = "n_barcodes", "barcode"
 
 
 class CBarcodeReport(C.Structure):
@@ -737,7 +776,7 @@ class BarcodeReport(_PlaneReport):
     distance and the clip"""
     FIELDS = ("tested", "call", "bq", "idx", "dist", "second", "clip")
     PLANES = _int_planes("tested", "call", "bq") + tuple((k, np.int32, (2,)) for k in ("idx", "dist", "second", "clip"))
-    CSTRUCT = CBarcodeReport
+    CSTRUCT, REQUEST, OPTS_DEFAULT, READS = CBarcodeReport, CBarcodeRequest, staticmethod(barcode_opts_default), "ccsx_barcode_reads"
 
     def c_struct(self) -> CBarcodeReport:
         r = CBarcodeReport()
@@ -750,33 +789,9 @@ class BarcodeReport(_PlaneReport):
         return {k: getattr(self, k)[z].tolist() for k in self.FIELDS}
 
 
-def _barcode_request(bset: BarcodeSet, opts: "BarcodeOpts | None", crep: CBarcodeReport):
-    o = opts if opts is not None else barcode_opts_default()
-    return CBarcodeRequest(C.pointer(o), C.pointer(bset), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (bset, o, crep)
-
-
-def _barcode_reads_args(bset: BarcodeSet, opts: "BarcodeOpts | None", reads, report: "BarcodeReport | None"):
-    """the arguments of ccsx_barcode_reads[_host] for a list of code arrays: (args, report, keep)"""
-    reads = [np.ascontiguousarray(r, np.uint8) for r in reads]
-    n = len(reads)
-    seq_len = np.array([len(r) for r in reads], np.int32).reshape(n)
-    seq_off = np.zeros(n, np.int64)
-    if n:
-        seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64)
-    seq = np.concatenate(reads + [np.zeros(1, np.uint8)])
-    rep = report if report is not None else BarcodeReport.allocate(n)
-    crep = rep.c_struct()
-    o = opts if opts is not None else barcode_opts_default()
-    keep = (bset, o, seq, seq_off, seq_len, crep, rep)
-    return (C.byref(bset), C.byref(o), _ptr(seq, C.c_uint8), _ptr(seq_off, C.c_int64), _ptr(seq_len, C.c_int32), n, C.byref(crep)), rep, keep
-
-
 def barcode_reads_host(bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = None, report: "BarcodeReport | None" = None) -> BarcodeReport:
     """ccsx_barcode_reads_host: the barcode rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
-    args, rep, _keep = _barcode_reads_args(bset, opts, reads, report)
-    if lib().ccsx_barcode_reads_host(*args) != 0:
-        raise RuntimeError("ccsx_barcode_reads_host failed: " + lib().ccsx_last_error().decode())
-    return rep
+    return _reads_host(BarcodeReport, bset, reads, opts, report)
 
 
 # ---- segmentation of concatenated-array reads (include/ccsx.h ccsx_segment_*; DESIGN.md §2 "Segment rule")
@@ -789,31 +804,10 @@ class SegmentOpts(C.Structure):
     _fields_ = [("max_dist_pct", C.c_int32), ("min_len", C.c_int32)]
 
 
-class SegmentSet(C.Structure):
+class SegmentSet(_PatternSet, C.Structure):
     """ccsx_segment_set: the 2 .. 33 adapters of an array, of 8 .. 64 codes 0 .. 3, in array order"""
     _fields_ = [("n_adapters", C.c_int32), ("len", C.c_int32 * SEGMENT_MAX_ADAPTERS), ("seq", (C.c_uint8 * SEGMENT_MAX_LEN) * SEGMENT_MAX_ADAPTERS)]
-
-    @staticmethod
-    def from_codes(seqs) -> "SegmentSet":
-        """from ACGT strings (either case) or arrays of codes; lengths, codes and the count are checked by the call that takes the set"""
-        seqs = list(seqs)
-        if len(seqs) > SEGMENT_MAX_ADAPTERS:
-            raise ValueError(f"at most {SEGMENT_MAX_ADAPTERS} adapters")
-        s = SegmentSet()
-        s.n_adapters = len(seqs)
-        flat = np.frombuffer(s, np.uint8, SEGMENT_MAX_ADAPTERS * SEGMENT_MAX_LEN, SegmentSet.seq.offset).reshape(SEGMENT_MAX_ADAPTERS, SEGMENT_MAX_LEN)
-        for a, q in enumerate(seqs):
-            codes = ["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q]
-            if len(codes) > SEGMENT_MAX_LEN:
-                raise ValueError(f"adapter {a}: more than {SEGMENT_MAX_LEN} bases")
-            s.len[a] = len(codes)
-            flat[a, : len(codes)] = codes
-        return s
-
-    from_strings = from_codes
-
-    def codes(self) -> list:
-        return [np.array(self.seq[a][: self.len[a]], np.uint8) for a in range(self.n_adapters)]
+    COUNT, NOUN = "n_adapters", "adapter"
 
 
 class CSegmentPiece(C.Structure):
@@ -843,7 +837,7 @@ class SegmentReport(_PlaneReport):
     increasing start, zero beyond n_segments"""
     FIELDS = SEGMENT_PLANES + ("pieces",)
     PLANES = _int_planes(*SEGMENT_PLANES) + (("pieces", SEGMENT_PIECE_DTYPE, (SEGMENT_MAX_PIECES,)),)
-    CSTRUCT = CSegmentReport
+    CSTRUCT, REQUEST, OPTS_DEFAULT, READS = CSegmentReport, CSegmentRequest, staticmethod(segment_opts_default), "ccsx_segment_reads"
 
     def c_struct(self) -> CSegmentReport:
         r = CSegmentReport()
@@ -864,33 +858,18 @@ class SegmentReport(_PlaneReport):
         return d
 
 
-def _segment_request(sset: SegmentSet, opts: "SegmentOpts | None", crep: CSegmentReport):
-    o = opts if opts is not None else segment_opts_default()
-    return CSegmentRequest(C.pointer(o), C.pointer(sset), C.pointer(crep), (C.c_int32 * 2)(0, 0)), (sset, o, crep)
+# the arguments of one analysis' read calls under their earlier names (the tests of the argument checks build their calls from them)
+def _barcode_reads_args(bset, opts, reads, report):
+    return _reads_args(BarcodeReport, bset, opts, reads, report)
 
 
-def _segment_reads_args(sset: SegmentSet, opts: "SegmentOpts | None", reads, report: "SegmentReport | None"):
-    """the arguments of ccsx_segment_reads[_host] for a list of code arrays: (args, report, keep)"""
-    reads = [np.ascontiguousarray(r, np.uint8) for r in reads]
-    n = len(reads)
-    seq_len = np.array([len(r) for r in reads], np.int32).reshape(n)
-    seq_off = np.zeros(n, np.int64)
-    if n:
-        seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64)
-    seq = np.concatenate(reads + [np.zeros(1, np.uint8)])
-    rep = report if report is not None else SegmentReport.allocate(n)
-    crep = rep.c_struct()
-    o = opts if opts is not None else segment_opts_default()
-    keep = (sset, o, seq, seq_off, seq_len, crep, rep)
-    return (C.byref(sset), C.byref(o), _ptr(seq, C.c_uint8), _ptr(seq_off, C.c_int64), _ptr(seq_len, C.c_int32), n, C.byref(crep)), rep, keep
+def _segment_reads_args(sset, opts, reads, report):
+    return _reads_args(SegmentReport, sset, opts, reads, report)
 
 
 def segment_reads_host(sset: SegmentSet, reads, opts: "SegmentOpts | None" = None, report: "SegmentReport | None" = None) -> SegmentReport:
     """ccsx_segment_reads_host: the segment rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
-    args, rep, _keep = _segment_reads_args(sset, opts, reads, report)
-    if lib().ccsx_segment_reads_host(*args) != 0:
-        raise RuntimeError("ccsx_segment_reads_host failed: " + lib().ccsx_last_error().decode())
-    return rep
+    return _reads_host(SegmentReport, sset, reads, opts, report)
 
 
 # ---- representative reads (include/ccsx.h ccsx_represent_*; DESIGN.md §2 "Representative rule")
@@ -1776,6 +1755,35 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
     return ex, hq, fq, aq, cq, keep
 
 
+
+def _reads_request(key: str, noun: str):
+    """how Handle._fused builds the request of an analysis on final reads from (report, set, opts)"""
+    def build(what):
+        rep, pset, opts = what
+        if pset is None:
+            raise ValueError(f"{key}: a {noun}_set is needed")
+        return _pattern_request(type(rep), pset, opts, rep.c_struct()) + (rep,)
+    return build
+
+
+# The requests of which a fused run takes one at most, and none beside the heteroduplex request, as Handle._fused walks them: its keyword there (ccsx_*_<keyword>
+# is the entry point), how the refusal of a combination begins, and how its value becomes the C request (first element) and what must outlive the call
+_EXCLUSIVE = (("handoff", "the heteroduplex request and the hand-off are not combined", _handoff_request),
+              ("barcodes", "the barcode request is not combined", _reads_request("barcodes", "barcode")),
+              ("represent", "the represent request is not combined", lambda what: _represent_request(*what)),
+              ("segments", "the segment request is not combined", _reads_request("segments", "segment")))
+
+
+def _exclusive(other: bool, handoff=None, barcodes=None, represent=None, segments=None):
+    """the one request of _EXCLUSIVE among the arguments, as (row, value), or None.  ValueError for two of them, and for one when `other`: the run carries
+    the heteroduplex request (or goes through an entry point that does not take a ccsx_requests)"""
+    asked = [(row, what) for row, what in zip(_EXCLUSIVE, (handoff, barcodes, represent, segments)) if what is not None]
+    if asked and (len(asked) > 1 or other):
+        raise ValueError(asked[-1][0][1] + ": a run takes one of the hand-off, the barcode, the represent and the segment request, beside the members of "
+                         "ccsx_requests and without the heteroduplex request")
+    return asked[-1] if asked else None
+
+
 class Handle:
     """One consensus engine bound to one GPU (ccsx_create).  Not thread-safe: one per worker per GPU."""
 
@@ -1806,36 +1814,12 @@ class Handle:
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
             name, args = (f"ccsx_{form}_hd_requests", (_keep[-1], hq)) if hq is not None else (f"ccsx_{form}_requests", (_keep[-1],))
-        if handoff is not None:
-            if name != f"ccsx_{form}_requests":
-                raise ValueError("the hand-off goes with the members of ccsx_requests (not with the heteroduplex request)")
-            hreq = _handoff_request(handoff)
-            name, args = f"ccsx_{form}_handoff", (_keep[-1], hreq[0])
-            _keep.append(hreq)
-        if barcodes is not None:
-            if handoff is not None or name != f"ccsx_{form}_requests":
-                raise ValueError("the barcode request goes with the members of ccsx_requests (not with the hand-off or the heteroduplex request)")
-            brep, bset, bopts = barcodes
-            if bset is None:
-                raise ValueError("barcodes: a barcode_set is needed")
-            breq = _barcode_request(bset, bopts, brep.c_struct())
-            name, args = f"ccsx_{form}_barcodes", (_keep[-1], breq[0])
-            _keep.append((breq, brep))
-        if represent is not None:
-            if handoff is not None or barcodes is not None or name != f"ccsx_{form}_requests":
-                raise ValueError("the represent request goes with the members of ccsx_requests (not with the hand-off, the barcode or the heteroduplex request)")
-            rreq = _represent_request(*represent)
-            name, args = f"ccsx_{form}_represent", (_keep[-1], rreq[0])
-            _keep.append(rreq)
-        if segments is not None:
-            if handoff is not None or barcodes is not None or represent is not None or name != f"ccsx_{form}_requests":
-                raise ValueError("the segment request goes with the members of ccsx_requests (not with the hand-off, the barcode, the represent or the heteroduplex request)")
-            srep, sset, sopts = segments
-            if sset is None:
-                raise ValueError("segments: a segment_set is needed")
-            sreq = _segment_request(sset, sopts, srep.c_struct())
-            name, args = f"ccsx_{form}_segments", (_keep[-1], sreq[0])
-            _keep.append((sreq, srep))
+        one = _exclusive(name != f"ccsx_{form}_requests", handoff, barcodes, represent, segments)
+        if one is not None:
+            (key, _, build), what = one
+            req = build(what)
+            name, args = f"ccsx_{form}_{key}", (_keep[-1], req[0])
+            _keep.append(req)
         cb, cr = batch.c_struct(), res.c_struct()
         self._check(getattr(self._L, name)(self._h, cb, cr, *args, *ticket), name)
         if form == "consensus":
@@ -2016,17 +2000,26 @@ class Handle:
         self._fused("consensus", batch, res, _requests(via_requests=True, **requests), handoff=ho)
         return res, ho
 
+    # ---- the analyses on final reads: one fused run with the request `key` of _EXCLUSIVE, and the kernel alone on the caller's reads
+    def _consensus_reads(self, key: str, rep_cls, batch: Batch, pset, opts, res, requests):
+        if res is None:
+            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
+        rep = rep_cls.allocate(batch.n_zmw)
+        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), **{key: (rep, pset, opts)})
+        return res, rep
+
+    def _reads(self, rep_cls, pset, reads, opts, report):
+        args, rep, _keep = _reads_args(rep_cls, pset, opts, reads, report)
+        self._check(getattr(self._L, rep_cls.READS)(self._h, *args), rep_cls.READS)
+        return rep
+
     # ---- barcode calls (ccsx_consensus_barcodes / ccsx_barcode_reads): the barcodes at both ends of the final reads
     def consensus_barcodes(self, batch: Batch, bset: BarcodeSet, opts: "BarcodeOpts | None" = None, res: "Results | None" = None,
                            **requests) -> tuple["Results", BarcodeReport]:
         """(results, barcode report).  bset: the BarcodeSet; opts: the BarcodeOpts (None: the defaults); res: the caller's Results.  requests: Handle.submit's
         keyword arguments for the other requests of the same run (pileup=, tandem=, fold=, adapters=, control=, coverage= ... with their reports; not hd=,
         not handoff=)"""
-        if res is None:
-            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
-        rep = BarcodeReport.allocate(batch.n_zmw)
-        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), barcodes=(rep, bset, opts))
-        return res, rep
+        return self._consensus_reads("barcodes", BarcodeReport, batch, bset, opts, res, requests)
 
     # ---- segmentation (ccsx_consensus_segments / ccsx_segment_reads): the segments of concatenated-array reads
     def consensus_segments(self, batch: Batch, sset: SegmentSet, opts: "SegmentOpts | None" = None, res: "Results | None" = None,
@@ -2034,17 +2027,11 @@ class Handle:
         """(results, segment report).  sset: the SegmentSet; opts: the SegmentOpts (None: the defaults); res: the caller's Results.  requests: Handle.submit's
         keyword arguments for the other requests of the same run (pileup=, tandem=, fold=, adapters=, control=, coverage= ... with their reports; not hd=,
         handoff=, barcodes=, represent=)"""
-        if res is None:
-            res = Results.allocate(batch, kinetics=bool(self.opts.hifi_kinetics))
-        rep = SegmentReport.allocate(batch.n_zmw)
-        self._fused("consensus", batch, res, _requests(via_requests=True, **requests), segments=(rep, sset, opts))
-        return res, rep
+        return self._consensus_reads("segments", SegmentReport, batch, sset, opts, res, requests)
 
     def segment_reads(self, sset: SegmentSet, reads, opts: "SegmentOpts | None" = None, report: "SegmentReport | None" = None) -> SegmentReport:
         """ccsx_segment_reads: k_segment on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
-        args, rep, _keep = _segment_reads_args(sset, opts, reads, report)
-        self._check(self._L.ccsx_segment_reads(self._h, *args), "ccsx_segment_reads")
-        return rep
+        return self._reads(SegmentReport, sset, reads, opts, report)
 
     # ---- representative reads (ccsx_consensus_represent): a draft or a subread in the result planes of every ZMW that was not polished
     def consensus_represent(self, batch: Batch, subread_fallback: bool = False, kinetics: bool = False, res: "Results | None" = None,
@@ -2060,9 +2047,7 @@ class Handle:
 
     def barcode_reads(self, bset: BarcodeSet, reads, opts: "BarcodeOpts | None" = None, report: "BarcodeReport | None" = None) -> BarcodeReport:
         """ccsx_barcode_reads: k_barcode on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
-        args, rep, _keep = _barcode_reads_args(bset, opts, reads, report)
-        self._check(self._L.ccsx_barcode_reads(self._h, *args), "ccsx_barcode_reads")
-        return rep
+        return self._reads(BarcodeReport, bset, reads, opts, report)
 
     # ---- the polisher hand-back (ccsx_refine_batch): refined tiles spliced into the base consensus on the GPU, QVs from one more Arrow round
     @staticmethod
@@ -2153,21 +2138,14 @@ class Handle:
         (ccsx_submit_represent; represent_fallback / represent_kinetics: the request's flags, every ticket its own; not with hd, handoff, barcodes or a
         coverage gate).  segments: a report (SegmentReport.allocate(n, pinned=True)) that receives the segmentation for segment_set under segment_opts
         (ccsx_submit_segments; not with hd, handoff, barcodes or represent); every ticket carries its own set and options"""
+        one = _exclusive(hd is not None, handoff, barcodes, represent, segments)   # (refused before anything else is looked at)
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if control is not None and control_seq is None:
             raise ValueError("control: a control_seq is needed (there is no built-in control)")
-        if handoff is not None and hd is not None:
-            raise ValueError("the heteroduplex request and the hand-off are not combined")
-        if barcodes is not None and (hd is not None or handoff is not None):
-            raise ValueError("the barcode request is not combined with the heteroduplex request or the hand-off")
-        if represent is not None and (hd is not None or handoff is not None or barcodes is not None):
-            raise ValueError("the represent request is not combined with the heteroduplex request, the hand-off or the barcode request")
-        if segments is not None and (hd is not None or handoff is not None or barcodes is not None or represent is not None):
-            raise ValueError("the segment request is not combined with the heteroduplex request, the hand-off, the barcode or the represent request")
         requests = _requests(pileup, tandem, min_tandem_repeat_length, hd, hd_opts, hd_split, fold, fold_opts, adapters, adapter_set, adapter_opts,
                              control, control_seq, control_opts, coverage, coverage_opts, coverage_gate,
-                             via_requests=handoff is not None or barcodes is not None or represent is not None or segments is not None, hd_requests=True)
+                             via_requests=one is not None, hd_requests=True)
         t = C.c_int64()
         cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff,
                              barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None,

@@ -111,3 +111,30 @@ struct BarcodeParams {
     int32_t *rep;                        // [CCSX_BC_PLANES][n]; NULL: no request
 };
 #define CCSX_BARCODE_THREADS 256
+
+// ---- the set and the report in memory, for the host (the one definition: the library, the bench and the sanitize programs).  A packed set is the masks, then one
+// length byte per barcode, in whole 64-bit words; in one buffer the report of the reads stands behind it.
+CCSX_BC_HD size_t ccsx_bc_set_words(int nb) { return (size_t)nb * 4 + ((size_t)nb + 7) / 8; }
+CCSX_BC_HD size_t ccsx_bc_rep_bytes(size_t n) { return n * CCSX_BC_PLANES * 4; }
+// masks, len and rep of B for the packed set of B.n_barcodes at `base`, device or host memory (rep: where the report would follow)
+CCSX_BC_HD void ccsx_bc_bind(BarcodeParams &B, const void *base)
+{
+    B.masks = (const unsigned long long *)base;
+    B.len = (const uint8_t *)(B.masks + (size_t)B.n_barcodes * 4);
+    B.rep = (int32_t *)(B.masks + ccsx_bc_set_words(B.n_barcodes));
+}
+// a checked set, packed into ccsx_bc_set_words(n_barcodes) zeroed words
+inline void ccsx_bc_pack(const ccsx_barcode_set *set, unsigned long long *packed)
+{
+    BarcodeParams B{};
+    B.n_barcodes = set->n_barcodes;
+    ccsx_bc_bind(B, packed);
+    uint8_t *len = const_cast<uint8_t *>(B.len);
+    for (int b = 0; b < set->n_barcodes; ++b) {
+        const BarcodeMasks k = ccsx_bc_masks(set->seq[b], set->len[b]);
+        for (int c = 0; c < 4; ++c) packed[4 * b + c] = k.eq[c];
+        len[b] = (uint8_t)set->len[b];
+    }
+}
+// a caller's report as the rule writes it
+inline BarcodeOut ccsx_bc_out(const ccsx_barcode_report &r) { return {r.tested, r.call, r.bq, r.idx, r.dist, r.second, r.clip}; }

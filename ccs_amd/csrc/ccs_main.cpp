@@ -323,139 +323,92 @@ void usage()
                  "      --fit-degree D        polynomial degree of the transition weights in the SNR, 0 .. 3 (default 1)\n");
 }
 
-// --adapters: "default" = the built-in set; otherwise a FASTA of 1 .. 8 records of 16 .. 64 bases, ACGT in either case.  false + a message that names the record
+// The FASTA files of --adapters, --barcodes, --segment-adapters and --control: min_records .. max_records records of min_bases .. max_bases bases each, ACGT in
+// either case; CR, blanks and tabs at a line's end and empty lines are skipped.  names: the '>' lines, cut at 60 characters; codes: the bases as 0 .. 3.
+// too_few: what is said of the first record of a file with fewer than min_records (> 1) records.  false + a message that names the record.
+struct FastaLimits { size_t min_records, max_records, min_bases, max_bases; const char *too_few; };
+struct FastaSet { std::vector<std::string> names; std::vector<std::vector<uint8_t>> codes; };
+bool load_fasta_set(const std::string &path, const FastaLimits &lim, FastaSet &fa, std::string &err)
+{
+    std::ifstream f(path);
+    if (!f) { err = "cannot open the file"; return false; }
+    fa = FastaSet{};
+    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + fa.names[k] + ")"; };
+    std::string line;
+    while (std::getline(f, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            fa.names.push_back(line.substr(0, 60));
+            fa.codes.emplace_back();
+            if (fa.names.size() > lim.max_records) {
+                err = where(fa.names.size() - 1) + ": more than " + (lim.max_records == 1 ? std::string("one record") : std::to_string(lim.max_records) + " records"); return false;
+            }
+            continue;
+        }
+        if (fa.names.empty()) { err = "sequence before the first '>' line"; return false; }
+        const size_t a = fa.names.size() - 1;
+        for (char c : line) {
+            const int u = std::toupper((unsigned char)c);
+            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
+            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
+            if (fa.codes[a].size() >= lim.max_bases) { err = where(a) + ": more than " + std::to_string(lim.max_bases) + " bases"; return false; }
+            fa.codes[a].push_back((uint8_t)code);
+        }
+    }
+    if (fa.names.empty()) { err = "no FASTA record"; return false; }
+    if (fa.names.size() < lim.min_records) { err = where(0) + ": " + lim.too_few; return false; }
+    for (size_t k = 0; k < fa.names.size(); ++k)
+        if (fa.codes[k].size() < lim.min_bases) { err = where(k) + ": " + std::to_string(fa.codes[k].size()) + " bases, fewer than " + std::to_string(lim.min_bases); return false; }
+    return true;
+}
+// the records as the len / seq of a pattern set of the C ABI (the limits given to load_fasta_set were the set's); the number of records
+template <typename Set> int32_t fasta_patterns(const FastaSet &fa, Set &set)
+{
+    std::memset(&set, 0, sizeof set);
+    for (size_t k = 0; k < fa.codes.size(); ++k) {
+        set.len[k] = (int32_t)fa.codes[k].size();
+        std::copy(fa.codes[k].begin(), fa.codes[k].end(), set.seq[k]);
+    }
+    return (int32_t)fa.codes.size();
+}
+
+// --adapters: "default" = the built-in set; otherwise a FASTA of 1 .. 8 records of 16 .. 64 bases
 bool load_adapters(const std::string &path, ccsx_adapter_set &set, std::string &err)
 {
     if (path == "default") return ccsx_adapter_set_default(&set) == 0;
-    std::ifstream f(path);
-    if (!f) { err = "cannot open the file"; return false; }
-    std::memset(&set, 0, sizeof set);
-    std::vector<std::string> names;
-    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + names[k] + ")"; };
-    std::string line;
-    while (std::getline(f, line)) {
-        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
-        if (line.empty()) continue;
-        if (line[0] == '>') {
-            names.push_back(line.substr(0, 60));
-            if (names.size() > CCSX_ADAPTER_MAX_PATTERNS) { err = where(names.size() - 1) + ": more than 8 records"; return false; }
-            continue;
-        }
-        if (names.empty()) { err = "sequence before the first '>' line"; return false; }
-        const size_t a = names.size() - 1;
-        for (char c : line) {
-            const int u = std::toupper((unsigned char)c);
-            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
-            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
-            if (set.len[a] >= CCSX_ADAPTER_MAX_LEN) { err = where(a) + ": more than 64 bases"; return false; }
-            set.seq[a][set.len[a]++] = (uint8_t)code;
-        }
-    }
-    if (names.empty()) { err = "no FASTA record"; return false; }
-    set.n_adapters = (int32_t)names.size();
-    for (size_t k = 0; k < names.size(); ++k)
-        if (set.len[k] < CCSX_ADAPTER_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 16"; return false; }
+    FastaSet fa;
+    if (!load_fasta_set(path, {1, CCSX_ADAPTER_MAX_PATTERNS, CCSX_ADAPTER_MIN_LEN, CCSX_ADAPTER_MAX_LEN, nullptr}, fa, err)) return false;
+    set.n_adapters = fasta_patterns(fa, set);
     return true;
 }
 
-// --barcodes: a FASTA of 1 .. 384 records of 8 .. 64 bases, ACGT in either case.  false + a message that names the record, as load_adapters
+// --barcodes: a FASTA of 1 .. 384 records of 8 .. 64 bases.  ids: the names up to their first blank, without the '>'
 bool load_barcodes(const std::string &path, ccsx_barcode_set &set, std::vector<std::string> &ids, std::string &err)
 {
-    std::ifstream f(path);
-    if (!f) { err = "cannot open the file"; return false; }
-    std::memset(&set, 0, sizeof set);
-    std::vector<std::string> names;
-    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + names[k] + ")"; };
-    std::string line;
-    while (std::getline(f, line)) {
-        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
-        if (line.empty()) continue;
-        if (line[0] == '>') {
-            names.push_back(line.substr(0, 60));
-            if (names.size() > CCSX_BARCODE_MAX) { err = where(names.size() - 1) + ": more than 384 records"; return false; }
-            continue;
-        }
-        if (names.empty()) { err = "sequence before the first '>' line"; return false; }
-        const size_t a = names.size() - 1;
-        for (char c : line) {
-            const int u = std::toupper((unsigned char)c);
-            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
-            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
-            if (set.len[a] >= CCSX_BARCODE_MAX_LEN) { err = where(a) + ": more than 64 bases"; return false; }
-            set.seq[a][set.len[a]++] = (uint8_t)code;
-        }
-    }
-    if (names.empty()) { err = "no FASTA record"; return false; }
-    set.n_barcodes = (int32_t)names.size();
-    for (size_t k = 0; k < names.size(); ++k)
-        if (set.len[k] < CCSX_BARCODE_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 8"; return false; }
+    FastaSet fa;
+    if (!load_fasta_set(path, {1, CCSX_BARCODE_MAX, CCSX_BARCODE_MIN_LEN, CCSX_BARCODE_MAX_LEN, nullptr}, fa, err)) return false;
+    set.n_barcodes = fasta_patterns(fa, set);
     ids.clear();
-    for (const std::string &n : names) ids.push_back(n.substr(1, n.find_first_of(" \t", 1) == std::string::npos ? std::string::npos : n.find_first_of(" \t", 1) - 1));
+    for (const std::string &n : fa.names) ids.push_back(n.substr(1, n.find_first_of(" \t", 1) == std::string::npos ? std::string::npos : n.find_first_of(" \t", 1) - 1));
     return true;
 }
 
-// --segment-adapters: a FASTA of 2 .. 33 records of 8 .. 64 bases, ACGT in either case, in array order.  false + a message that names the record, as load_barcodes
+// --segment-adapters: a FASTA of 2 .. 33 records of 8 .. 64 bases, in array order
 bool load_segment_adapters(const std::string &path, ccsx_segment_set &set, std::string &err)
 {
-    std::ifstream f(path);
-    if (!f) { err = "cannot open the file"; return false; }
-    std::memset(&set, 0, sizeof set);
-    std::vector<std::string> names;
-    auto where = [&](size_t k) { return "record " + std::to_string(k + 1) + " (" + names[k] + ")"; };
-    std::string line;
-    while (std::getline(f, line)) {
-        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
-        if (line.empty()) continue;
-        if (line[0] == '>') {
-            names.push_back(line.substr(0, 60));
-            if (names.size() > CCSX_SEGMENT_MAX_ADAPTERS) { err = where(names.size() - 1) + ": more than 33 records"; return false; }
-            continue;
-        }
-        if (names.empty()) { err = "sequence before the first '>' line"; return false; }
-        const size_t a = names.size() - 1;
-        for (char c : line) {
-            const int u = std::toupper((unsigned char)c);
-            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
-            if (code < 0) { err = where(a) + ": '" + std::string(1, c) + "' is not one of ACGT"; return false; }
-            if (set.len[a] >= CCSX_SEGMENT_MAX_LEN) { err = where(a) + ": more than 64 bases"; return false; }
-            set.seq[a][set.len[a]++] = (uint8_t)code;
-        }
-    }
-    if (names.empty()) { err = "no FASTA record"; return false; }
-    if (names.size() < 2) { err = where(0) + ": the only record, an array has at least 2 adapters"; return false; }
-    set.n_adapters = (int32_t)names.size();
-    for (size_t k = 0; k < names.size(); ++k)
-        if (set.len[k] < CCSX_SEGMENT_MIN_LEN) { err = where(k) + ": " + std::to_string(set.len[k]) + " bases, fewer than 8"; return false; }
+    FastaSet fa;
+    if (!load_fasta_set(path, {2, CCSX_SEGMENT_MAX_ADAPTERS, CCSX_SEGMENT_MIN_LEN, CCSX_SEGMENT_MAX_LEN, "the only record, an array has at least 2 adapters"}, fa, err)) return false;
+    set.n_adapters = fasta_patterns(fa, set);
     return true;
 }
 
-// --control: a FASTA of exactly one record of 64 .. 4096 bases, ACGT in either case.  false + a message that names what is wrong
+// --control: a FASTA of exactly one record of 64 .. 4096 bases
 bool load_control(const std::string &path, std::vector<uint8_t> &codes, std::string &err)
 {
-    std::ifstream f(path);
-    if (!f) { err = "cannot open the file"; return false; }
-    codes.clear();
-    int records = 0;
-    std::string line, name;
-    while (std::getline(f, line)) {
-        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
-        if (line.empty()) continue;
-        if (line[0] == '>') {
-            if (++records > 1) { err = "record 2 (" + line.substr(0, 60) + "): more than one record"; return false; }
-            name = line.substr(0, 60);
-            continue;
-        }
-        if (!records) { err = "sequence before the first '>' line"; return false; }
-        for (char c : line) {
-            const int u = std::toupper((unsigned char)c);
-            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : -1;
-            if (code < 0) { err = "record 1 (" + name + "): '" + std::string(1, c) + "' is not one of ACGT"; return false; }
-            if (codes.size() >= CCSX_CONTROL_MAX_LEN) { err = "record 1 (" + name + "): more than 4096 bases"; return false; }
-            codes.push_back((uint8_t)code);
-        }
-    }
-    if (!records) { err = "no FASTA record"; return false; }
-    if (codes.size() < CCSX_CONTROL_MIN_LEN) { err = "record 1 (" + name + "): " + std::to_string(codes.size()) + " bases, fewer than 64"; return false; }
+    FastaSet fa;
+    if (!load_fasta_set(path, {1, 1, CCSX_CONTROL_MIN_LEN, CCSX_CONTROL_MAX_LEN, nullptr}, fa, err)) return false;
+    codes = fa.codes[0];
     return true;
 }
 
@@ -466,6 +419,14 @@ bool parse(int argc, char **argv, Options &o)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *n) -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", n); std::exit(2); } return argv[++i]; };
+        // the value of option `a`, a whole number in lo .. hi; otherwise "ccs: <a> needs <what>, got '<value>'" and exit 2
+        auto need_int = [&](long lo, long hi, const char *what) -> int {
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < lo || n > hi) { std::fprintf(stderr, "ccs: %s needs %s, got '%s'\n", a.c_str(), what, v.c_str()); std::exit(2); }
+            return (int)n;
+        };
         if (a == "-h" || a == "--help") { usage(); std::exit(0); }
         else if (a == "--version") { std::printf("ccs (ccs_amd, MI355X-native consensus path) abi %d spec %d\n", ccsx_abi_version(), ccsx_spec_version()); std::exit(0); }
         else if (a == "-j" || a == "--num-threads") o.threads = std::atoi(need("-j").c_str());
@@ -495,13 +456,7 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--qv-binning") o.qv_binning = true;
         else if (a == "--hifi-kinetics") o.o.hifi_kinetics = 1;
         else if (a == "--pileup-summary") o.pileup = true;
-        else if (a == "--min-tandem-repeat-length") {
-            const std::string v = need(a.c_str());
-            char *end = nullptr;
-            const long n = std::strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n <= 0 || n > 0x7fffffffL) { std::fprintf(stderr, "ccs: --min-tandem-repeat-length needs a positive number of bases, got '%s'\n", v.c_str()); std::exit(2); }
-            o.min_tandem = (int)n;
-        }
+        else if (a == "--min-tandem-repeat-length") o.min_tandem = need_int(1, 0x7fffffffL, "a positive number of bases");
         else if (a == "--suppress-reports") o.suppress_reports = true;
         else if (a == "--fail-reads") o.fail_reads = need(a.c_str());
         else if (a == "--adapters") o.adapters = need(a.c_str());
@@ -510,20 +465,8 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--barcode-counts") o.barcode_counts = need(a.c_str());
         else if (a == "--segment-adapters") o.segment_adapters = need(a.c_str());
         else if (a == "--segment-counts") o.segment_counts = need(a.c_str());
-        else if (a == "--segment-min-length") {
-            const std::string v = need(a.c_str());
-            char *end = nullptr;
-            const long n = std::strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < 1 || n > 65535) { std::fprintf(stderr, "ccs: --segment-min-length needs a number in 1 .. 65535, got '%s'\n", v.c_str()); std::exit(2); }
-            o.segment_min_length = (int)n;
-        }
-        else if (a == "--barcode-window") {
-            const std::string v = need(a.c_str());
-            char *end = nullptr;
-            const long n = std::strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < CCSX_BARCODE_MIN_LEN || n > CCSX_BARCODE_MAX_WINDOW) { std::fprintf(stderr, "ccs: --barcode-window needs a number in 8 .. 1024, got '%s'\n", v.c_str()); std::exit(2); }
-            o.barcode_window = (int)n;
-        }
+        else if (a == "--segment-min-length") o.segment_min_length = need_int(1, 65535, "a number in 1 .. 65535");
+        else if (a == "--barcode-window") o.barcode_window = need_int(CCSX_BARCODE_MIN_LEN, CCSX_BARCODE_MAX_WINDOW, "a number in 8 .. 1024");
         else if (a == "--coverage-filters") o.coverage_filters = true;
         else if (a == "--reads-bam") o.reads_bam = true;
         else if (a == "--reads-bam-kinetics") o.reads_kinetics = true;

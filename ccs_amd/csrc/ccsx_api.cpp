@@ -140,8 +140,7 @@ struct Slot {
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
     DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
-    DevBuf d_sg;                                  // segmentation only (ccsx_segment_request): the set's masks and lengths, then the report (ccsx_sg_out)
-    DevBuf d_bc;                                  // barcode calls only (ccsx_barcode_request): the set's masks and lengths, then the [11][n] report
+    DevBuf d_pattern;                             // barcode calls or segmentation only (a ticket carries one of them): the packed set, then the report
     DevBuf d_rp;                                  // representative reads only (ccsx_represent_request): the [2][n] report
     DevBuf d_rf_tiles, d_rf_base, d_rf_rep;       // polisher hand-back only (ccsx_submit_refine): the tile list and its classes; base lengths, backbones, seq, qual; the report
     RefineParams RP{};                            // ... its kernels' parameters as enqueued (the report's download reads them)
@@ -149,8 +148,7 @@ struct Slot {
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
     PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
-    PinVec<unsigned long long> sg_set;            // segmentation only: the masks and lengths as uploaded (a ticket's set is its own)
-    PinVec<unsigned long long> bc_set;            // barcode calls only: the masks and lengths as uploaded (a ticket's set is its own, as its control is)
+    PinVec<unsigned long long> pattern_set;       // barcode calls or segmentation only: the packed set as uploaded (a ticket's set is its own, as its control is)
     PinVec<int32_t> anchor;                       // pass orientation only: the anchor pass of every ZMW as uploaded
     bool orient_pending = false, orient_ran = false;   // the staged batch carries the bit and k_orient has yet to run on it / has run (its report is on the device)
     KParams P;
@@ -202,8 +200,7 @@ struct ccsx_handle_s {
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
-    DevBuf d_sg_reads;                // ccsx_segment_reads only: the call's set, reads and report (no slot is touched)
-    DevBuf d_bc_reads;                // ccsx_barcode_reads only: the call's set, reads and report (no slot is touched)
+    DevBuf d_reads;                   // ccsx_barcode_reads / ccsx_segment_reads only: the call's set, report and reads (no slot is touched; the call ends synchronised)
     DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
     ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
     Slot slot[CCSX_SLOTS];
@@ -276,6 +273,140 @@ static void destroy_handle(ccsx_handle h)
     if (h->s_comp) (void)hipStreamDestroy(h->s_comp);
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
     delete h;                         // frees every buffer of the handle and its slots (they were drained above; hipFree needs no stream)
+}
+
+static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string(fn) + ": " + what); return -1; }
+
+// ---- The analyses on final reads: barcode calls and segmentation (DESIGN.md §2 "Barcode calls", "Segment rule").  Each is described once, by a struct of its
+// types, its nouns, its check / pack / launch and the arrays of its report; everything between an entry point and the kernel is one template over that struct.
+// A third analysis supplies a core header (rule, packed set, report layout), a kernel with its launch, a check, such a struct and its member of KParams.
+struct ReadsCopy { void *host; const void *dev; size_t bytes_per_read; };
+
+struct Barcodes {
+    using Request = ccsx_barcode_request; using Set = ccsx_barcode_set; using Opts = ccsx_barcode_opts; using Report = ccsx_barcode_report; using Params = BarcodeParams;
+    static constexpr const char *noun = "barcode", *title = "barcode calls";
+    static int count(const Set &s) { return s.n_barcodes; }
+    static size_t set_words(int nb) { return ccsx_bc_set_words(nb); }
+    static size_t rep_bytes(size_t n) { return ccsx_bc_rep_bytes(n); }
+    static int check(const Set *s, const Opts *o, const Report *r, int64_t n, const char *fn, Opts *out) { return ccsx_barcode_check(s, o, r, n, fn, out); }
+    static void pack(const Set *s, unsigned long long *packed) { ccsx_bc_pack(s, packed); }
+    static Params params(int nb, int n, const Opts &o, const void *base) { Params B{}; B.n = n; B.n_barcodes = nb; B.opts = o; ccsx_bc_bind(B, base); return B; }
+    static const char *launch(const Params &B, hipStream_t st) { return ccsx_barcode_launch(B, st); }
+    static Params &of(KParams &P) { return P.bc; }
+    static std::vector<ReadsCopy> copies(const Report &r, const Params &B)
+    {
+        const BarcodeOut d = ccsx_bc_out(B.rep, (size_t)B.n);
+        return {{r.tested, d.tested, 4}, {r.call, d.call, 4}, {r.bq, d.bq, 4}, {r.idx, d.idx, 8}, {r.dist, d.dist, 8}, {r.second, d.second, 8}, {r.clip, d.clip, 8}};
+    }
+};
+
+struct Segments {
+    using Request = ccsx_segment_request; using Set = ccsx_segment_set; using Opts = ccsx_segment_opts; using Report = ccsx_segment_report; using Params = SegmentParams;
+    static constexpr const char *noun = "segment", *title = "segmentation";
+    static int count(const Set &s) { return s.n_adapters; }
+    static size_t set_words(int na) { return ccsx_sg_set_words(na); }
+    static size_t rep_bytes(size_t n) { return ccsx_sg_rep_bytes(n); }
+    static int check(const Set *s, const Opts *o, const Report *r, int64_t n, const char *fn, Opts *out) { return ccsx_segment_check(s, o, r, n, fn, out); }
+    static void pack(const Set *s, unsigned long long *packed) { ccsx_sg_pack(s, packed); }
+    static Params params(int na, int n, const Opts &o, const void *base) { Params G{}; G.n = n; G.n_adapters = na; G.opts = o; ccsx_sg_bind(G, base); return G; }
+    static const char *launch(const Params &G, hipStream_t st) { return ccsx_segment_launch(G, st); }
+    static Params &of(KParams &P) { return P.sg; }
+    static std::vector<ReadsCopy> copies(const Report &r, const Params &G)
+    {
+        const SegmentOut d = ccsx_sg_out(G.rep, (size_t)G.n);
+        return {{r.tested, d.tested, 4}, {r.overflow, d.overflow, 4}, {r.n_hits, d.n_hits, 4}, {r.n_cuts, d.n_cuts, 4}, {r.n_segments, d.n_segments, 4},
+                {r.complete, d.complete, 4}, {r.orient, d.orient, 4}, {r.leftover_bases, d.leftover, 4},
+                {r.pieces, d.pieces, CCSX_SEGMENT_MAX_PIECES * sizeof(ccsx_segment_piece)}};
+    }
+};
+
+// a request of analysis A as build_wants checked and copied it: the options, the set packed (A::set_words) and its count
+template <typename A> struct ReadsWant {
+    const typename A::Request *req = nullptr;
+    typename A::Opts opts{};
+    std::vector<unsigned long long> set;
+    int count = 0;
+};
+
+// the set of a checked request or call, packed
+template <typename A> static std::vector<unsigned long long> reads_pack(const typename A::Set *set)
+{
+    std::vector<unsigned long long> packed(A::set_words(A::count(*set)), 0ull);
+    A::pack(set, packed.data());
+    return packed;
+}
+
+template <typename A> static int reads_request_check(const typename A::Request *q, const ccsx_batch *b, ReadsWant<A> *w, const char *fn)
+{
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": " + A::noun + " request: reserved must be 0"); return -1; }
+    if (A::check(q->set, q->opts, q->report, b->n_zmw, fn, &w->opts)) return -1;
+    w->set = reads_pack<A>(q->set);
+    w->count = A::count(*q->set);
+    return 0;
+}
+
+// The set is the slot's own, in page-locked memory that lives as long as the slot (as the control's index): its copy is enqueued on `st` with the slot's other
+// uploads.  The kernel reads the results where k_stitch leaves them.  A ticket carries one analysis at most (build_wants), so the slot has one buffer for it.
+template <typename A> static int reads_attach(Slot &S, const ReadsWant<A> &w, hipStream_t st)
+{
+    KParams &P = S.P;
+    const size_t n = (size_t)P.n_zmw, words = w.set.size();
+    if (S.d_pattern.reserve(words * 8 + A::rep_bytes(n)) || S.pattern_set.resize(words)) return -2;
+    std::copy(w.set.begin(), w.set.end(), S.pattern_set.p);
+    typename A::Params &K = A::of(P);
+    K = A::params(w.count, (int)n, w.opts, S.d_pattern.p);
+    K.seq = P.out_seq; K.seq_off = P.seq_off; K.seq_len = P.out_len;
+    if (hipError_t e = hipMemcpyAsync(S.d_pattern.p, S.pattern_set.p, words * 8, hipMemcpyHostToDevice, st)) {
+        ccsx_set_error(std::string(A::title) + ": set upload: " + hipGetErrorString(e)); return -2;
+    }
+    return 0;
+}
+
+// the report's arrays into the caller's, on `s`
+template <typename A> static int reads_download(const typename A::Params &K, const typename A::Report *r, hipStream_t s)
+{
+    if (!K.n) return 0;
+    for (const ReadsCopy &c : A::copies(*r, K)) HIPTRY(hipMemcpyAsync(c.host, c.dev, (size_t)K.n * c.bytes_per_read, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// The kernel of analysis A on the caller's reads: a buffer of the handle's own on the polish stream, behind whatever tickets have enqueued there; no slot is
+// staged, retired or recycled.  Layout of the buffer: [set + report][seq_off: n x 8][seq_len: n x 4, padded][seq]
+template <typename A> static int reads_enqueue(ccsx_handle h, const std::vector<unsigned long long> &packed, int count, const typename A::Opts &o, const uint8_t *seq,
+                                               const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes, const typename A::Report *report, hipStream_t st)
+{
+    const size_t words = packed.size(), head = words * 8 + A::rep_bytes((size_t)n), head8 = (head + 7) & ~(size_t)7, len4 = ((size_t)n * 4 + 7) & ~(size_t)7;
+    if (h->d_reads.reserve(head8 + (size_t)n * 8 + len4 + (size_t)bytes)) return -2;
+    uint8_t *base = (uint8_t *)h->d_reads.p;
+    int64_t *d_off = (int64_t *)(base + head8);
+    int32_t *d_len = (int32_t *)(base + head8 + (size_t)n * 8);
+    uint8_t *d_seq = base + head8 + (size_t)n * 8 + len4;
+    HIPTRY(hipMemcpyAsync(base, packed.data(), words * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (bytes) HIPTRY(hipMemcpyAsync(d_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
+    typename A::Params K = A::params(count, n, o, base);
+    K.seq = d_seq; K.seq_off = d_off; K.seq_len = d_len;
+    (void)hipGetLastError();
+    if (const char *failed = A::launch(K, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    return reads_download<A>(K, report, st);
+}
+
+// the body of ccsx_barcode_reads / ccsx_segment_reads (`fn`)
+template <typename A> static int reads_sync(ccsx_handle h, const typename A::Set *set, const typename A::Opts *opts, const uint8_t *seq, const int64_t *seq_off,
+                                            const int32_t *seq_len, int32_t n, typename A::Report *report, const char *fn)
+{
+    typename A::Opts o;
+    int64_t bytes;
+    if (A::check(set, opts, report, n, fn, &o) || ccsx_check_reads(seq, seq_off, seq_len, n, fn, &bytes)) return -1;
+    if (!h) return refuse(fn, "null argument");
+    if (n == 0) return 0;
+    const std::vector<unsigned long long> packed = reads_pack<A>(set);
+    HIPTRY(hipSetDevice(h->device));
+    const int rc = reads_enqueue<A>(h, packed, A::count(*set), o, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
+    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
 }
 
 extern "C" {
@@ -393,8 +524,8 @@ struct Wants {
     const ccsx_coverage_request *coverage = nullptr; ccsx_coverage_opts coverage_opts{};
     const ccsx_orient_opts *orient = nullptr;   // ccsx_orient_batch's own options (NULL: the handle's, ccsx_set_orient_opts); already checked
     const ccsx_handoff_request *handoff = nullptr; ccsx_handoff_opts handoff_opts{}; ccsx_handoff_out handoff_out{};   // (the out struct is copied: it is read during the call only)
-    const ccsx_barcode_request *barcodes = nullptr; ccsx_barcode_opts barcode_opts{}; std::vector<unsigned long long> barcode_set; int barcode_n = 0;   // (the set packed: barcode_words)
-    const ccsx_segment_request *segments = nullptr; ccsx_segment_opts segment_opts{}; std::vector<unsigned long long> segment_set; int segment_n = 0;   // (the set packed: segment_words)
+    ReadsWant<Barcodes> barcodes;
+    ReadsWant<Segments> segments;
     bool represent = false; ccsx_represent_request represent_req{};   // (the request is copied: it is read during the call only)
     bool handoff_written_only = false;          // the synchronous form: counts is known when the copies are enqueued, only the written slots are copied
 };
@@ -1193,122 +1324,6 @@ static int enqueue_handoff_download(const Slot &S, const ccsx_handoff_out &out, 
     return 0;
 }
 
-// ---- the barcode calls' host side (DESIGN.md §2 "Barcode calls"; the checks and the packing: ccsx_barcode_api.cpp).  A packed set is its masks, [n_barcodes][4]
-// words, then its lengths, one byte each, in whole words: what the slot uploads in one copy
-static size_t barcode_words(int nb) { return (size_t)nb * 4 + ((size_t)nb + 7) / 8; }
-static void barcode_pack(const ccsx_barcode_set *set, std::vector<unsigned long long> *packed)
-{
-    packed->assign(barcode_words(set->n_barcodes), 0ull);
-    ccsx_barcode_pack(set, packed->data(), reinterpret_cast<uint8_t *>(packed->data() + (size_t)set->n_barcodes * 4));
-}
-
-static int barcode_request_check(const ccsx_barcode_request *q, const ccsx_batch *b, std::vector<unsigned long long> *packed, ccsx_barcode_opts *o, const char *fn)
-{
-    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": barcode request: reserved must be 0"); return -1; }
-    if (ccsx_barcode_check(q->set, q->opts, q->report, b->n_zmw, fn, o)) return -1;
-    barcode_pack(q->set, packed);
-    return 0;
-}
-
-// k_barcode's parameters for a packed set at `dev` (the report's planes follow it) and the reads it is given
-static BarcodeParams barcode_params(void *dev, size_t words, int nb, int n, const ccsx_barcode_opts &o, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len)
-{
-    BarcodeParams B{};
-    B.n = n; B.n_barcodes = nb; B.opts = o; B.seq = seq; B.seq_off = seq_off; B.seq_len = seq_len;
-    B.masks = (const unsigned long long *)dev; B.len = (const uint8_t *)(B.masks + (size_t)nb * 4); B.rep = (int32_t *)(B.masks + words);
-    return B;
-}
-
-// The set is the slot's own, in page-locked memory that lives as long as the slot (as the control's index): its copy is enqueued on `st` with the slot's other
-// uploads.  k_barcode reads the results where k_stitch leaves them.
-static int barcode_attach(Slot &S, const std::vector<unsigned long long> &packed, int nb, const ccsx_barcode_opts &o, hipStream_t st)
-{
-    KParams &P = S.P;
-    const size_t n = (size_t)P.n_zmw, words = packed.size();
-    if (S.d_bc.reserve(words * 8 + n * CCSX_BC_PLANES * 4) || S.bc_set.resize(words)) return -2;
-    std::copy(packed.begin(), packed.end(), S.bc_set.p);
-    P.bc = barcode_params(S.d_bc.p, words, nb, (int)n, o, P.out_seq, P.seq_off, P.out_len);
-    if (hipError_t e = hipMemcpyAsync(S.d_bc.p, S.bc_set.p, words * 8, hipMemcpyHostToDevice, st)) {
-        ccsx_set_error(std::string("barcode calls: set upload: ") + hipGetErrorString(e)); return -2;
-    }
-    return 0;
-}
-
-// the report's planes into the caller's arrays, on `s`
-static int enqueue_barcode_download(const BarcodeParams &B, const ccsx_barcode_report *r, hipStream_t s)
-{
-    const size_t n = (size_t)B.n;
-    if (!n) return 0;
-    const BarcodeOut d = ccsx_bc_out(B.rep, n);
-    HIPTRY(hipMemcpyAsync(r->tested, d.tested, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->call, d.call, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->bq, d.bq, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->idx, d.idx, n * 8, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->dist, d.dist, n * 8, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->second, d.second, n * 8, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->clip, d.clip, n * 8, hipMemcpyDeviceToHost, s));
-    return 0;
-}
-
-// ---- the segmentation's host side (DESIGN.md §2 "Segment rule"; the checks and the packing: ccsx_segment_api.cpp), in the barcode calls' shape.  A packed set
-// is its masks, [2 * n_adapters][8] words, then the searches' lengths, one byte each, in whole words: what the slot uploads in one copy
-static size_t segment_words(int na) { return (size_t)na * 2 * CCSX_SG_MASK_WORDS + ((size_t)na * 2 + 7) / 8; }
-static void segment_pack(const ccsx_segment_set *set, std::vector<unsigned long long> *packed)
-{
-    packed->assign(segment_words(set->n_adapters), 0ull);
-    ccsx_segment_pack(set, packed->data(), reinterpret_cast<uint8_t *>(packed->data() + (size_t)set->n_adapters * 2 * CCSX_SG_MASK_WORDS));
-}
-
-static int segment_request_check(const ccsx_segment_request *q, const ccsx_batch *b, std::vector<unsigned long long> *packed, ccsx_segment_opts *o, const char *fn)
-{
-    if (q->reserved[0] != 0 || q->reserved[1] != 0) { ccsx_set_error(std::string(fn) + ": segment request: reserved must be 0"); return -1; }
-    if (ccsx_segment_check(q->set, q->opts, q->report, b->n_zmw, fn, o)) return -1;
-    segment_pack(q->set, packed);
-    return 0;
-}
-
-// k_segment's parameters for a packed set at `dev` (the report follows it) and the reads it is given
-static SegmentParams segment_params(void *dev, size_t words, int na, int n, const ccsx_segment_opts &o, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len)
-{
-    SegmentParams G{};
-    G.n = n; G.n_adapters = na; G.opts = o; G.seq = seq; G.seq_off = seq_off; G.seq_len = seq_len;
-    G.masks = (const unsigned long long *)dev; G.len = (const uint8_t *)(G.masks + (size_t)na * 2 * CCSX_SG_MASK_WORDS); G.rep = (int32_t *)(G.masks + words);
-    return G;
-}
-
-// The set is the slot's own, in page-locked memory that lives as long as the slot: its copy is enqueued on `st` with the slot's other uploads.  k_segment reads
-// the results where k_stitch leaves them.
-static int segment_attach(Slot &S, const std::vector<unsigned long long> &packed, int na, const ccsx_segment_opts &o, hipStream_t st)
-{
-    KParams &P = S.P;
-    const size_t n = (size_t)P.n_zmw, words = packed.size();
-    if (S.d_sg.reserve(words * 8 + ccsx_sg_rep_bytes(n)) || S.sg_set.resize(words)) return -2;
-    std::copy(packed.begin(), packed.end(), S.sg_set.p);
-    P.sg = segment_params(S.d_sg.p, words, na, (int)n, o, P.out_seq, P.seq_off, P.out_len);
-    if (hipError_t e = hipMemcpyAsync(S.d_sg.p, S.sg_set.p, words * 8, hipMemcpyHostToDevice, st)) {
-        ccsx_set_error(std::string("segmentation: set upload: ") + hipGetErrorString(e)); return -2;
-    }
-    return 0;
-}
-
-// the report's planes and list into the caller's arrays, on `s`
-static int enqueue_segment_download(const SegmentParams &G, const ccsx_segment_report *r, hipStream_t s)
-{
-    const size_t n = (size_t)G.n;
-    if (!n) return 0;
-    const SegmentOut d = ccsx_sg_out(G.rep, n);
-    HIPTRY(hipMemcpyAsync(r->tested, d.tested, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->overflow, d.overflow, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->n_hits, d.n_hits, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->n_cuts, d.n_cuts, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->n_segments, d.n_segments, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->complete, d.complete, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->orient, d.orient, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->leftover_bases, d.leftover, n * 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipMemcpyAsync(r->pieces, d.pieces, n * CCSX_SEGMENT_MAX_PIECES * sizeof(ccsx_segment_piece), hipMemcpyDeviceToHost, s));
-    return 0;
-}
-
 // ---- the representative reads' host side (DESIGN.md §2 "Representative rule"; the request's checks: ccsx_represent_api.cpp).  k_represent's parameters are the
 // slot's own inputs, final drafts and result planes: nothing is uploaded, the [2][n] report is all it reserves.
 static int represent_attach(Slot &S, const ccsx_represent_request &q)
@@ -1338,32 +1353,36 @@ static int extras_want(const ccsx_extras *ex, bool *tandem)
     return 0;
 }
 
-static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string(fn) + ": " + what); return -1; }
+// The requests of which a call carries one at most (NULL: none): each changes what the polish stage leaves or reads
+struct Exclusive {
+    const ccsx_handoff_request *handoff = nullptr;
+    const ccsx_barcode_request *barcodes = nullptr;
+    const ccsx_segment_request *segments = nullptr;
+    const ccsx_hd_request *hd = nullptr;
+};
 
 // The Wants of one call of the exported function `fn` (NULL extras or request: none of it).  Enqueues nothing and needs no handle: the requests are checked
 // first, each refused by its own message, then the extras; the caller's null-argument check follows (without a batch there is nothing to measure a report
 // against, and that check refuses the call).
-static int build_wants(const ccsx_extras *ex, const ccsx_hd_request *hd, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
-                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr,
-                       const ccsx_handoff_request *handoff = nullptr, const ccsx_barcode_request *barcodes = nullptr, const ccsx_segment_request *segments = nullptr)
+static int build_wants(const ccsx_extras *ex, const Exclusive &x, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
+                       const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr)
 {
     *W = Wants{};
-    if (segments && handoff) return refuse(fn, "the segment request and the hand-off are not combined");
-    if (segments && hd) return refuse(fn, "the segment and the heteroduplex requests are not combined");
-    if (segments && barcodes) return refuse(fn, "the segment and the barcode requests are not combined");
-    if (segments && b && segment_request_check(segments, b, &W->segment_set, &W->segment_opts, fn)) return -1;
-    if (barcodes && handoff) return refuse(fn, "the barcode request and the hand-off are not combined");
-    if (barcodes && hd) return refuse(fn, "the barcode and the heteroduplex requests are not combined");
-    if (barcodes && b && barcode_request_check(barcodes, b, &W->barcode_set, &W->barcode_opts, fn)) return -1;
-    if (handoff && handoff_request_check(handoff, &W->handoff_opts, &W->handoff_out, fn)) return -1;
+    if (x.segments && x.handoff) return refuse(fn, "the segment request and the hand-off are not combined");
+    if (x.segments && x.hd) return refuse(fn, "the segment and the heteroduplex requests are not combined");
+    if (x.segments && x.barcodes) return refuse(fn, "the segment and the barcode requests are not combined");
+    if (x.segments && b && reads_request_check(x.segments, b, &W->segments, fn)) return -1;
+    if (x.barcodes && x.handoff) return refuse(fn, "the barcode request and the hand-off are not combined");
+    if (x.barcodes && x.hd) return refuse(fn, "the barcode and the heteroduplex requests are not combined");
+    if (x.barcodes && b && reads_request_check(x.barcodes, b, &W->barcodes, fn)) return -1;
+    if (x.handoff && handoff_request_check(x.handoff, &W->handoff_opts, &W->handoff_out, fn)) return -1;
     if (coverage && b && coverage_request_check(coverage, b, &W->coverage_opts, fn)) return -1;
-    if (hd && b && hd_request_check(hd, b, &W->hd_opts, fn)) return -1;
+    if (x.hd && b && hd_request_check(x.hd, b, &W->hd_opts, fn)) return -1;
     if (fold && b && fold_request_check(fold, b, &W->fold_opts, fn)) return -1;
     if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
     if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
-    W->hd = hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = handoff; W->barcodes = barcodes; W->barcode_n = barcodes && barcodes->set ? barcodes->set->n_barcodes : 0;
-    W->segments = segments; W->segment_n = segments && segments->set ? segments->set->n_adapters : 0;
+    W->hd = x.hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = x.handoff; W->barcodes.req = x.barcodes; W->segments.req = x.segments;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
@@ -1379,8 +1398,8 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.adapters && (rc = adapter_attach(h, S, W.adapter_set, W.adapter_opts))) return rc;
     if (W.coverage && (rc = coverage_attach(h, S, W.coverage_opts, W.coverage->gate))) return rc;
     if (W.handoff && (rc = handoff_attach(S, W.handoff_opts, W.handoff_out.max_tiles))) return rc;
-    if (W.barcodes && (rc = barcode_attach(S, W.barcode_set, W.barcode_n, W.barcode_opts, st))) return rc;
-    if (W.segments && (rc = segment_attach(S, W.segment_set, W.segment_n, W.segment_opts, st))) return rc;
+    if (W.barcodes.req && (rc = reads_attach(S, W.barcodes, st))) return rc;
+    if (W.segments.req && (rc = reads_attach(S, W.segments, st))) return rc;
     if (W.represent && (rc = represent_attach(S, W.represent_req))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
@@ -1415,8 +1434,8 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
                                   S.P.cov_zi, n, s))) return rc;
     }
     if (W.handoff && (rc = enqueue_handoff_download(S, W.handoff_out, W.handoff_written_only, s))) return rc;
-    if (W.barcodes && (rc = enqueue_barcode_download(S.P.bc, W.barcodes->report, s))) return rc;
-    if (W.segments && (rc = enqueue_segment_download(S.P.sg, W.segments->report, s))) return rc;
+    if (W.barcodes.req && (rc = reads_download<Barcodes>(S.P.bc, W.barcodes.req->report, s))) return rc;
+    if (W.segments.req && (rc = reads_download<Segments>(S.P.sg, W.segments.req->report, s))) return rc;
     if (W.represent && n) {
         const ccsx_represent_report *r = W.represent_req.report;
         if ((rc = download_planes({r->cls, r->pass}, S.P.rep.rep, n, s))) return rc;
@@ -1602,49 +1621,55 @@ int ccsx_submit_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, cc
 {
     const ccsx_extras ex = {pile, nullptr, 0, 0};
     Wants W;
-    if (build_wants(&ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
+    if (build_wants(&ex, {}, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
+    if (build_wants(ex, {}, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, nullptr, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
+    if (build_wants(ex, {}, fold, nullptr, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                        ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, nullptr, b, __func__, &W)) return -1;
+    if (build_wants(ex, {}, fold, adapters, nullptr, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters,
                         const ccsx_control_request *control, ccsx_ticket *ticket)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, control, b, __func__, &W)) return -1;
+    if (build_wants(ex, {}, fold, adapters, control, b, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 // the members of a ccsx_requests as build_wants takes them (NULL: none); -1 for nonzero reserved words
-static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_handoff_request *handoff = nullptr,
-                          const ccsx_barcode_request *barcodes = nullptr, const ccsx_hd_request *hd = nullptr, const ccsx_segment_request *segments = nullptr)
+static int requests_wants(const ccsx_requests *rq, const ccsx_batch *b, const char *fn, Wants *W, const Exclusive &x = {})
 {
     static const ccsx_requests none = {};
     if (!rq) rq = &none;
     if (rq->reserved[0] || rq->reserved[1] || rq->reserved[2]) return refuse(fn, "ccsx_requests: reserved must be NULL");
-    return build_wants(rq->ex, hd, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage, handoff, barcodes, segments);
+    return build_wants(rq->ex, x, rq->fold, rq->adapters, rq->control, b, fn, W, rq->coverage);
 }
 // the Wants of a call with a heteroduplex request beside the members of rq (the four ccsx_*_hd* entry points): the checks of ccsx_submit_hd, in its order
 static int hd_requests_wants(const ccsx_requests *rq, const ccsx_hd_request *hd, const ccsx_batch *b, const char *fn, Wants *W)
 {
-    if (requests_wants(rq, b, fn, W, nullptr, nullptr, hd) || (!hd && refuse(fn, "null request or report"))) return -1;
+    if (requests_wants(rq, b, fn, W, {nullptr, nullptr, nullptr, hd}) || (!hd && refuse(fn, "null request or report"))) return -1;
     return 0;
+}
+// the Wants of a call with a barcode or a segment request (x: it alone) beside the members of rq: neither it nor the batch may be NULL
+static int reads_wants(const ccsx_requests *rq, const ccsx_batch *b, const Exclusive &x, const char *noun, const char *fn, Wants *W)
+{
+    if (!x.barcodes && !x.segments) return refuse(fn, (std::string("null ") + noun + " request").c_str());
+    if (!b) return refuse(fn, "null argument");
+    return requests_wants(rq, b, fn, W, x);
 }
 int ccsx_submit_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, ccsx_ticket *ticket)
 {
@@ -1668,19 +1693,19 @@ int ccsx_submit_hd(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const 
 int ccsx_submit_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho, ccsx_ticket *ticket)
 {
     Wants W;
-    if (requests_wants(rq, b, __func__, &W, ho) || (!ho && refuse(__func__, "null handoff request"))) return -1;
+    if (requests_wants(rq, b, __func__, &W, {ho}) || (!ho && refuse(__func__, "null handoff request"))) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc, ccsx_ticket *ticket)
 {
     Wants W;
-    if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
+    if (reads_wants(rq, b, {nullptr, bc}, Barcodes::noun, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 int ccsx_submit_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg, ccsx_ticket *ticket)
 {
     Wants W;
-    if ((!sg && refuse(__func__, "null segment request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, nullptr, nullptr, sg)) return -1;
+    if (reads_wants(rq, b, {nullptr, nullptr, sg}, Segments::noun, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 // the Wants of a call with a representative request: the request checked against the batch and the handle's options and copied, then the members of rq
@@ -1873,7 +1898,7 @@ int ccsx_consensus_pileup(ccsx_handle h, const ccsx_batch *b, ccsx_results *res,
 {
     const ccsx_extras ex = {pile, nullptr, 0, 0};
     Wants W;
-    if (build_wants(&ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
+    if (build_wants(&ex, {}, nullptr, nullptr, nullptr, b, __func__, &W) || (!pile && refuse(__func__, "null argument"))) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1882,7 +1907,7 @@ int ccsx_tandem_rule_version(void) { return 1; }
 int ccsx_consensus_extras(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex)
 {
     Wants W;
-    if (build_wants(ex, nullptr, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
+    if (build_wants(ex, {}, nullptr, nullptr, nullptr, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1912,7 +1937,7 @@ int ccsx_fold_rule_version(void) { return 1; }
 int ccsx_consensus_fold(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, nullptr, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
+    if (build_wants(ex, {}, fold, nullptr, nullptr, b, __func__, &W) || (!fold && refuse(__func__, "null request or report"))) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1937,7 +1962,7 @@ int ccsx_adapter_set_default(ccsx_adapter_set *s)
 int ccsx_consensus_screen(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_extras *ex, const ccsx_fold_request *fold, const ccsx_adapter_request *adapters)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, nullptr, b, __func__, &W)) return -1;
+    if (build_wants(ex, {}, fold, adapters, nullptr, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1953,7 +1978,7 @@ int ccsx_consensus_control(ccsx_handle h, const ccsx_batch *b, ccsx_results *res
                            const ccsx_control_request *control)
 {
     Wants W;
-    if (build_wants(ex, nullptr, fold, adapters, control, b, __func__, &W)) return -1;
+    if (build_wants(ex, {}, fold, adapters, control, b, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -1975,7 +2000,7 @@ int ccsx_consensus_requests(ccsx_handle h, const ccsx_batch *b, ccsx_results *re
 int ccsx_consensus_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_handoff_request *ho)
 {
     Wants W;
-    if (requests_wants(rq, b, __func__, &W, ho) || (!ho && refuse(__func__, "null handoff request"))) return -1;
+    if (requests_wants(rq, b, __func__, &W, {ho}) || (!ho && refuse(__func__, "null handoff request"))) return -1;
     W.handoff_written_only = true;
     return consensus_sync(h, b, res, W, __func__);
 }
@@ -1983,14 +2008,14 @@ int ccsx_consensus_handoff(ccsx_handle h, const ccsx_batch *b, ccsx_results *res
 int ccsx_consensus_barcodes(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_barcode_request *bc)
 {
     Wants W;
-    if ((!bc && refuse(__func__, "null barcode request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, bc)) return -1;
+    if (reads_wants(rq, b, {nullptr, bc}, Barcodes::noun, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
 int ccsx_consensus_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg)
 {
     Wants W;
-    if ((!sg && refuse(__func__, "null segment request")) || (!b && refuse(__func__, "null argument")) || requests_wants(rq, b, __func__, &W, nullptr, nullptr, nullptr, sg)) return -1;
+    if (reads_wants(rq, b, {nullptr, nullptr, sg}, Segments::noun, __func__, &W)) return -1;
     return consensus_sync(h, b, res, W, __func__);
 }
 
@@ -2001,79 +2026,16 @@ int ccsx_consensus_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *r
     return consensus_sync(h, b, res, W, __func__);
 }
 
-// k_barcode on the caller's reads: buffers of the handle's own on the polish stream, behind whatever tickets have enqueued there; no slot is staged, retired
-// or recycled.  Layout of the buffer: [set + report][seq_off: n x 8][seq_len: n x 4, padded][seq]
-static int barcode_reads_enqueue(ccsx_handle h, const std::vector<unsigned long long> &packed, int nb, const ccsx_barcode_opts &o, const uint8_t *seq,
-                                 const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes, const ccsx_barcode_report *report, hipStream_t st)
-{
-    const size_t words = packed.size(), head = words * 8 + (size_t)n * CCSX_BC_PLANES * 4, head8 = (head + 7) & ~(size_t)7, len4 = ((size_t)n * 4 + 7) & ~(size_t)7;
-    if (h->d_bc_reads.reserve(head8 + (size_t)n * 8 + len4 + (size_t)bytes)) return -2;
-    uint8_t *base = (uint8_t *)h->d_bc_reads.p;
-    int64_t *d_off = (int64_t *)(base + head8);
-    int32_t *d_len = (int32_t *)(base + head8 + (size_t)n * 8);
-    uint8_t *d_seq = base + head8 + (size_t)n * 8 + len4;
-    HIPTRY(hipMemcpyAsync(base, packed.data(), words * 8, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (bytes) HIPTRY(hipMemcpyAsync(d_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
-    const BarcodeParams B = barcode_params(base, words, nb, n, o, d_seq, d_off, d_len);
-    (void)hipGetLastError();
-    if (const char *failed = ccsx_barcode_launch(B, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
-    return enqueue_barcode_download(B, report, st);
-}
-
 int ccsx_barcode_reads(ccsx_handle h, const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
                        int32_t n, ccsx_barcode_report *report)
 {
-    ccsx_barcode_opts o;
-    int64_t bytes;
-    if (ccsx_barcode_check(set, opts, report, n, __func__, &o) || ccsx_barcode_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
-    if (!h) return refuse(__func__, "null argument");
-    if (n == 0) return 0;
-    std::vector<unsigned long long> packed;
-    barcode_pack(set, &packed);
-    HIPTRY(hipSetDevice(h->device));
-    const int rc = barcode_reads_enqueue(h, packed, set->n_barcodes, o, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
-    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    return 0;
-}
-
-// k_segment on the caller's reads, as barcode_reads_enqueue.  Layout of the buffer: [set + report][seq_off: n x 8][seq_len: n x 4, padded][seq]
-static int segment_reads_enqueue(ccsx_handle h, const std::vector<unsigned long long> &packed, int na, const ccsx_segment_opts &o, const uint8_t *seq,
-                                 const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes, const ccsx_segment_report *report, hipStream_t st)
-{
-    const size_t words = packed.size(), head = words * 8 + ccsx_sg_rep_bytes((size_t)n), head8 = (head + 7) & ~(size_t)7, len4 = ((size_t)n * 4 + 7) & ~(size_t)7;
-    if (h->d_sg_reads.reserve(head8 + (size_t)n * 8 + len4 + (size_t)bytes)) return -2;
-    uint8_t *base = (uint8_t *)h->d_sg_reads.p;
-    int64_t *d_off = (int64_t *)(base + head8);
-    int32_t *d_len = (int32_t *)(base + head8 + (size_t)n * 8);
-    uint8_t *d_seq = base + head8 + (size_t)n * 8 + len4;
-    HIPTRY(hipMemcpyAsync(base, packed.data(), words * 8, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (bytes) HIPTRY(hipMemcpyAsync(d_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
-    const SegmentParams G = segment_params(base, words, na, n, o, d_seq, d_off, d_len);
-    (void)hipGetLastError();
-    if (const char *failed = ccsx_segment_launch(G, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
-    return enqueue_segment_download(G, report, st);
+    return reads_sync<Barcodes>(h, set, opts, seq, seq_off, seq_len, n, report, __func__);
 }
 
 int ccsx_segment_reads(ccsx_handle h, const ccsx_segment_set *set, const ccsx_segment_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
                        int32_t n, ccsx_segment_report *report)
 {
-    ccsx_segment_opts o;
-    int64_t bytes;
-    if (ccsx_segment_check(set, opts, report, n, __func__, &o) || ccsx_barcode_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
-    if (!h) return refuse(__func__, "null argument");
-    if (n == 0) return 0;
-    std::vector<unsigned long long> packed;
-    segment_pack(set, &packed);
-    HIPTRY(hipSetDevice(h->device));
-    const int rc = segment_reads_enqueue(h, packed, set->n_adapters, o, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
-    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
-    HIPTRY(hipStreamSynchronize(h->s_comp));
-    return 0;
+    return reads_sync<Segments>(h, set, opts, seq, seq_off, seq_len, n, report, __func__);
 }
 
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)

@@ -1,5 +1,5 @@
 // ccsx_barcode_api.cpp — the host side of the barcode calls that needs no device (DESIGN.md §2 "Barcode calls"): defaults, the argument checks every entry point
-// shares, the masks as k_barcode reads them, and ccsx_barcode_reads_host, the rule on the calling thread (barcode_core.h: the same walk and the same call as
+// shares, and ccsx_barcode_reads_host, the rule on the calling thread (barcode_core.h: the same walk and the same call as
 // the kernel's).  The entry points that take a handle are in ccsx_api.cpp.
 #include <string>
 #include <vector>
@@ -39,7 +39,7 @@ int ccsx_barcode_check(const ccsx_barcode_set *set, const ccsx_barcode_opts *opt
     return 0;
 }
 
-int ccsx_barcode_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes)
+int ccsx_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes)
 {
     const std::string f(fn);
     *bytes = 0;
@@ -54,27 +54,20 @@ int ccsx_barcode_check_reads(const uint8_t *seq, const int64_t *seq_off, const i
     return 0;
 }
 
-void ccsx_barcode_pack(const ccsx_barcode_set *set, unsigned long long *masks, uint8_t *len)
-{
-    for (int b = 0; b < set->n_barcodes; ++b) {
-        const BarcodeMasks k = ccsx_bc_masks(set->seq[b], set->len[b]);
-        for (int c = 0; c < 4; ++c) masks[4 * b + c] = k.eq[c];
-        len[b] = (uint8_t)set->len[b];
-    }
-}
-
 int ccsx_barcode_reads_host(const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
                             int32_t n, ccsx_barcode_report *report)
 {
     ccsx_barcode_opts o;
     int64_t bytes;
-    if (ccsx_barcode_check(set, opts, report, n, __func__, &o) || ccsx_barcode_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
+    if (ccsx_barcode_check(set, opts, report, n, __func__, &o) || ccsx_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
     const int nb = set->n_barcodes;
-    std::vector<unsigned long long> masks((size_t)nb * 4);
-    std::vector<uint8_t> len((size_t)nb);
+    std::vector<unsigned long long> packed(ccsx_bc_set_words(nb), 0ull);
     std::vector<int> dist((size_t)nb);
-    ccsx_barcode_pack(set, masks.data(), len.data());
-    const BarcodeOut out = {report->tested, report->call, report->bq, report->idx, report->dist, report->second, report->clip};
+    ccsx_bc_pack(set, packed.data());
+    BarcodeParams B{};
+    B.n_barcodes = nb;
+    ccsx_bc_bind(B, packed.data());
+    const BarcodeOut out = ccsx_bc_out(*report);
     for (int z = 0; z < n; ++z) {
         const int L = seq_len[z];
         if (L <= 0) { ccsx_bc_put_untested(out, z); continue; }
@@ -84,12 +77,12 @@ int ccsx_barcode_reads_host(const ccsx_barcode_set *set, const ccsx_barcode_opts
         for (int e = 0; e < 2; ++e) {
             int best = 0x7fffffff, clip = 0;
             for (int b = 0; b < nb; ++b) {
-                const unsigned long long *k = &masks[(size_t)b * 4];
-                const BarcodeHit h = ccsx_bc_walk(k[0], k[1], k[2], k[3], (int)len[b], W, [&](int j) { return ccsx_bc_base(c, L, e, j); });
+                const unsigned long long *k = &B.masks[(size_t)b * 4];
+                const BarcodeHit h = ccsx_bc_walk(k[0], k[1], k[2], k[3], (int)B.len[b], W, [&](int j) { return ccsx_bc_base(c, L, e, j); });
                 dist[b] = h.dist;
                 if (ccsx_bc_key(h.dist, b) < best) { best = ccsx_bc_key(h.dist, b); clip = h.clip; }
             }
-            idx[e] = best & 0xffff; d[e] = best >> 16; m[e] = len[idx[e]]; s2[e] = 255;
+            idx[e] = best & 0xffff; d[e] = best >> 16; m[e] = B.len[idx[e]]; s2[e] = 255;
             for (int b = 0; b < nb; ++b) if (b != idx[e]) s2[e] = std::min(s2[e], dist[b]);
             out.idx[2 * z + e] = idx[e]; out.dist[2 * z + e] = d[e]; out.second[2 * z + e] = s2[e]; out.clip[2 * z + e] = clip;
         }

@@ -32,20 +32,14 @@ template <typename F> static inline void ccsx_for_each_zmw_caps(const ccsx_batch
     }
 }
 
-// ---- barcode calls (ccsx_barcode_api.cpp; DESIGN.md §2 "Barcode calls"): what every entry point shares.  A refusal sets the error under the exported function's
-// name `fn` and returns -1.
+// ---- the analyses on final reads: barcode calls (ccsx_barcode_api.cpp; DESIGN.md §2 "Barcode calls") and segmentation (ccsx_segment_api.cpp; "Segment rule").
+// What every entry point of one shares; a refusal sets the error under the exported function's name `fn` and returns -1.  The packed set, the binding of its
+// buffer and the report's layout are in barcode_core.h / segment_core.h; the path both take through a handle is ccsx_api.cpp's (struct Barcodes, struct Segments).
 // the set, the options (NULL: the defaults; the checked copy goes to *o) and a report for n reads
 int ccsx_barcode_check(const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const ccsx_barcode_report *report, int64_t n, const char *fn, ccsx_barcode_opts *o);
-// caller-supplied reads: *bytes = the bytes of seq the reads cover (the largest seq_off[z] + seq_len[z] over the reads with seq_len[z] > 0)
-int ccsx_barcode_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes);
-// k_barcode's view of a checked set: masks [n_barcodes][4], len [n_barcodes]
-void ccsx_barcode_pack(const ccsx_barcode_set *set, unsigned long long *masks, uint8_t *len);
-
-// ---- segmentation (ccsx_segment_api.cpp; DESIGN.md §2 "Segment rule"): what every entry point shares, in the barcode calls' shape.  Caller-supplied reads are
-// checked by ccsx_barcode_check_reads.
 int ccsx_segment_check(const ccsx_segment_set *set, const ccsx_segment_opts *opts, const ccsx_segment_report *report, int64_t n, const char *fn, ccsx_segment_opts *o);
-// k_segment's view of a checked set: masks [2 * n_adapters][8], len [2 * n_adapters]
-void ccsx_segment_pack(const ccsx_segment_set *set, unsigned long long *masks, uint8_t *len);
+// caller-supplied reads, of either analysis: *bytes = the bytes of seq the reads cover (the largest seq_off[z] + seq_len[z] over the reads with seq_len[z] > 0)
+int ccsx_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes);
 
 // ---- representative reads (ccsx_represent_api.cpp; DESIGN.md §2 "Representative rule"): the request against the batch it is for and the options of the run — flags,
 // reserved words, the report's arrays and size, kinetics without opts.hifi_kinetics or batch.ipd.  A refusal sets the error under `fn` and returns -1.

@@ -1,5 +1,5 @@
 // ccsx_segment_api.cpp — the host side of the segmentation that needs no device (DESIGN.md §2 "Segment rule"): defaults, the argument checks every entry point
-// shares, the masks as k_segment reads them, and ccsx_segment_reads_host, the rule on the calling thread (segment_core.h: the same walks, key, selection and
+// shares, and ccsx_segment_reads_host, the rule on the calling thread (segment_core.h: the same walks, key, selection and
 // classification as the kernel's).  The entry points that take a handle are in ccsx_api.cpp.
 #include <algorithm>
 #include <string>
@@ -42,26 +42,19 @@ int ccsx_segment_check(const ccsx_segment_set *set, const ccsx_segment_opts *opt
     return 0;
 }
 
-void ccsx_segment_pack(const ccsx_segment_set *set, unsigned long long *masks, uint8_t *len)
-{
-    for (int s = 0; s < 2 * set->n_adapters; ++s) {
-        ccsx_sg_masks(set->seq[s >> 1], set->len[s >> 1], s & 1, masks + (size_t)s * CCSX_SG_MASK_WORDS);
-        len[s] = (uint8_t)set->len[s >> 1];
-    }
-}
-
 int ccsx_segment_reads_host(const ccsx_segment_set *set, const ccsx_segment_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
                             int32_t n, ccsx_segment_report *report)
 {
     ccsx_segment_opts o;
     int64_t bytes;
-    if (ccsx_segment_check(set, opts, report, n, __func__, &o) || ccsx_barcode_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
+    if (ccsx_segment_check(set, opts, report, n, __func__, &o) || ccsx_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
     const int A = set->n_adapters, S = 2 * A;
-    std::vector<unsigned long long> masks((size_t)S * CCSX_SG_MASK_WORDS);
-    std::vector<uint8_t> len((size_t)S);
-    ccsx_segment_pack(set, masks.data(), len.data());
-    const SegmentOut out = {report->tested, report->overflow, report->n_hits, report->n_cuts, report->n_segments, report->complete, report->orient,
-                            report->leftover_bases, report->pieces};
+    std::vector<unsigned long long> packed(ccsx_sg_set_words(A), 0ull);
+    ccsx_sg_pack(set, packed.data());
+    SegmentParams G{};
+    G.n_adapters = A;
+    ccsx_sg_bind(G, packed.data());
+    const SegmentOut out = ccsx_sg_out(*report);
     std::vector<unsigned long long> keys;
     for (int z = 0; z < n; ++z) {
         const int L = seq_len[z];
@@ -73,8 +66,8 @@ int ccsx_segment_reads_host(const ccsx_segment_set *set, const ccsx_segment_opts
         int n_hits = 0;
         keys.clear();
         for (int s = 0; s < S; ++s) {
-            const unsigned long long *w = &masks[(size_t)s * CCSX_SG_MASK_WORDS];
-            const int m = len[s];
+            const unsigned long long *w = &G.masks[(size_t)s * CCSX_SG_MASK_WORDS];
+            const int m = G.len[s];
             ccsx_sg_walk(w[0], w[1], w[2], w[3], m, ccsx_sg_k(m, o.max_dist_pct), L, 0, L, base, [&](int end, int dist) {
                 if (n_hits++ < CCSX_SEGMENT_MAX_HITS) keys.push_back(ccsx_sg_key(dist, ccsx_sg_start([&](int b) { return w[4 + b]; }, m, dist, end, base), s, end));
             });

@@ -159,7 +159,7 @@ CCSX_SG_HD void ccsx_sg_put(const SegmentOut &r, size_t z, int n_hits, const Seg
 }
 CCSX_SG_HD void ccsx_sg_zero_piece(ccsx_segment_piece &p) { p.start = 0; p.end = 0; p.index = 0; p.reverse = 0; p.dist_left = 0; p.dist_right = 0; }
 
-// what k_segment is given (ccsx_segment.hip).  masks / len: built once per request by the host (ccsx_segment_pack), 66 x 64 + 66 bytes for a full set
+// what k_segment is given (ccsx_segment.hip).  masks / len: built once per request by the host (ccsx_sg_pack), 66 x 64 + 66 bytes for a full set
 struct SegmentParams {
     int32_t n, n_adapters;
     ccsx_segment_opts opts;
@@ -170,3 +170,31 @@ struct SegmentParams {
     const uint8_t *len;                  // [2 * n_adapters] the pattern length of every search
     int32_t *rep;                        // ccsx_sg_out; NULL: no request
 };
+
+// ---- the set and the report in memory, for the host, as barcode_core.h has them.  A packed set is the masks of the 2 * n_adapters searches, then one length
+// byte per search, in whole 64-bit words; in one buffer the report of the reads (ccsx_sg_out, ccsx_sg_rep_bytes) stands behind it.
+CCSX_SG_HD size_t ccsx_sg_set_words(int na) { return (size_t)na * 2 * CCSX_SG_MASK_WORDS + ((size_t)na * 2 + 7) / 8; }
+// masks, len and rep of G for the packed set of G.n_adapters at `base`, device or host memory (rep: where the report would follow)
+CCSX_SG_HD void ccsx_sg_bind(SegmentParams &G, const void *base)
+{
+    G.masks = (const unsigned long long *)base;
+    G.len = (const uint8_t *)(G.masks + (size_t)G.n_adapters * 2 * CCSX_SG_MASK_WORDS);
+    G.rep = (int32_t *)(G.masks + ccsx_sg_set_words(G.n_adapters));
+}
+// a checked set, packed into ccsx_sg_set_words(n_adapters) zeroed words
+inline void ccsx_sg_pack(const ccsx_segment_set *set, unsigned long long *packed)
+{
+    SegmentParams G{};
+    G.n_adapters = set->n_adapters;
+    ccsx_sg_bind(G, packed);
+    uint8_t *len = const_cast<uint8_t *>(G.len);
+    for (int s = 0; s < 2 * set->n_adapters; ++s) {
+        ccsx_sg_masks(set->seq[s >> 1], set->len[s >> 1], s & 1, packed + (size_t)s * CCSX_SG_MASK_WORDS);
+        len[s] = (uint8_t)set->len[s >> 1];
+    }
+}
+// a caller's report as the rule writes it
+inline SegmentOut ccsx_sg_out(const ccsx_segment_report &r)
+{
+    return {r.tested, r.overflow, r.n_hits, r.n_cuts, r.n_segments, r.complete, r.orient, r.leftover_bases, r.pieces};
+}

@@ -31,9 +31,9 @@ int main(int argc, char **argv)
     std::vector<int64_t> off((size_t)n);
     std::vector<int32_t> len((size_t)n, L);
     for (int z = 0; z < n; ++z) off[z] = (int64_t)z * L;
-    uint8_t *d_seq; int64_t *d_off; int32_t *d_len, *d_rep; unsigned long long *d_set;
+    uint8_t *d_seq; int64_t *d_off; int32_t *d_len; unsigned long long *d_set;                  // d_set: the packed set, the report behind it
     CK(hipMalloc((void **)&d_seq, seq.size())); CK(hipMalloc((void **)&d_off, (size_t)n * 8)); CK(hipMalloc((void **)&d_len, (size_t)n * 4));
-    CK(hipMalloc((void **)&d_rep, (size_t)n * CCSX_BC_PLANES * 4)); CK(hipMalloc((void **)&d_set, (size_t)CCSX_BARCODE_MAX * 40));
+    CK(hipMalloc((void **)&d_set, ccsx_bc_set_words(CCSX_BARCODE_MAX) * 8 + ccsx_bc_rep_bytes((size_t)n)));
     CK(hipMemcpy(d_seq, seq.data(), seq.size(), hipMemcpyHostToDevice)); CK(hipMemcpy(d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_len, len.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -46,13 +46,14 @@ int main(int argc, char **argv)
             for (int b = 0; b < nb; ++b) { set->len[b] = 16; for (int i = 0; i < 16; ++i) set->seq[b][i] = (uint8_t)(rnd() & 3); }
             for (int z = 0; L >= 32 && z < 512 && z < n; z += 2) memcpy(&seq[(size_t)z * L + (z % 5)], set->seq[z % nb], 16);      // (some planted, so the check sees calls)
             CK(hipMemcpy(d_seq, seq.data(), std::min(seq.size(), (size_t)512 * L), hipMemcpyHostToDevice));
-            std::vector<unsigned long long> packed((size_t)nb * 4 + (nb + 7) / 8, 0ull);
-            ccsx_barcode_pack(set.get(), packed.data(), reinterpret_cast<uint8_t *>(packed.data() + (size_t)nb * 4));
+            std::vector<unsigned long long> packed(ccsx_bc_set_words(nb), 0ull);
+            ccsx_bc_pack(set.get(), packed.data());
             CK(hipMemcpy(d_set, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
             BarcodeParams B{};
             ccsx_barcode_opts_default(&B.opts);
             B.opts.window = window;
-            B.n = n; B.n_barcodes = nb; B.seq = d_seq; B.seq_off = d_off; B.seq_len = d_len; B.masks = d_set; B.len = (const uint8_t *)(d_set + (size_t)nb * 4); B.rep = d_rep;
+            B.n = n; B.n_barcodes = nb; B.seq = d_seq; B.seq_off = d_off; B.seq_len = d_len;
+            ccsx_bc_bind(B, d_set);
             std::vector<double> us;
             for (int r = 0; r <= rounds; ++r) {                      // round 0 warms up and is checked
                 CK(hipEventRecord(e0, s));
@@ -63,7 +64,7 @@ int main(int argc, char **argv)
                 if (r == 0) {
                     const int m = std::min(n, 512);
                     std::vector<int32_t> got((size_t)n * CCSX_BC_PLANES), want((size_t)m * CCSX_BC_PLANES);
-                    CK(hipMemcpy(got.data(), d_rep, got.size() * 4, hipMemcpyDeviceToHost));
+                    CK(hipMemcpy(got.data(), B.rep, got.size() * 4, hipMemcpyDeviceToHost));
                     const BarcodeOut g = ccsx_bc_out(got.data(), (size_t)n), w = ccsx_bc_out(want.data(), (size_t)m);
                     ccsx_barcode_report rep{m, w.tested, w.call, w.bq, w.idx, w.dist, w.second, w.clip};
                     if (ccsx_barcode_reads_host(set.get(), &B.opts, seq.data(), off.data(), len.data(), m, &rep)) { fprintf(stderr, "host rule: %s\n", g_err.c_str()); return 1; }

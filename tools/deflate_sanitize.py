@@ -4,33 +4,23 @@
 Encode, decode, compare; the CRC; out_cap == out_len and out_len - 1.  CPU only.  Usage: tools/deflate_sanitize.py [--keep DIR]"""
 import os
 import struct
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from host_sanitize import build_and_run  # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import deflate_ref as R  # noqa: E402
 
 
-def main() -> int:
-    keep = sys.argv[sys.argv.index("--keep") + 1] if "--keep" in sys.argv else None
-    work = keep or tempfile.mkdtemp(prefix="deflate_sanitize_")
-    os.makedirs(work, exist_ok=True)
+def write_cases(f) -> None:
     cases = [d for _, d in R.all_cases()]
     ccs = os.path.join(ROOT, "ccs_amd", "bin", "ccs")
     if os.path.exists(ccs):
         cases.append(R.synthetic_bam_slice(ccs))
-    path = os.path.join(work, "cases.bin")
-    with open(path, "wb") as f:
-        for d in cases:
-            f.write(struct.pack("<q", len(d)) + d)
-    exe = os.path.join(work, "deflate_sanitize")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "ccs_amd", "csrc"), os.path.join(ROOT, "tools", "deflate_sanitize", "main.cpp"),
-                           "-o", exe])
-    return subprocess.call([exe, path])
+    for d in cases:
+        f.write(struct.pack("<q", len(d)) + d)
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(build_and_run("deflate", write_cases))

@@ -32,10 +32,10 @@ int main(int argc, char **argv)
     std::vector<int64_t> off((size_t)n);
     std::vector<int32_t> len((size_t)n, L);
     for (int z = 0; z < n; ++z) off[z] = (int64_t)z * L;
-    const size_t set_bytes = (size_t)CCSX_SEGMENT_MAX_ADAPTERS * 2 * (CCSX_SG_MASK_WORDS * 8 + 1) + 8, rep_bytes = ccsx_sg_rep_bytes((size_t)n);
-    uint8_t *d_seq; int64_t *d_off; int32_t *d_len, *d_rep; unsigned long long *d_set;
+    const size_t rep_bytes = ccsx_sg_rep_bytes((size_t)n);
+    uint8_t *d_seq; int64_t *d_off; int32_t *d_len; unsigned long long *d_set;                  // d_set: the packed set, the report behind it
     CK(hipMalloc((void **)&d_seq, seq.size())); CK(hipMalloc((void **)&d_off, (size_t)n * 8)); CK(hipMalloc((void **)&d_len, (size_t)n * 4));
-    CK(hipMalloc((void **)&d_rep, rep_bytes)); CK(hipMalloc((void **)&d_set, set_bytes));
+    CK(hipMalloc((void **)&d_set, ccsx_sg_set_words(CCSX_SEGMENT_MAX_ADAPTERS) * 8 + rep_bytes));
     CK(hipMemcpy(d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_len, len.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -54,13 +54,13 @@ int main(int argc, char **argv)
         }
         CK(hipMemcpy(d_seq, seq.data(), seq.size(), hipMemcpyHostToDevice));
         const int S = 2 * na;
-        std::vector<unsigned long long> packed((size_t)S * CCSX_SG_MASK_WORDS + (S + 7) / 8, 0ull);
-        ccsx_segment_pack(set.get(), packed.data(), reinterpret_cast<uint8_t *>(packed.data() + (size_t)S * CCSX_SG_MASK_WORDS));
+        std::vector<unsigned long long> packed(ccsx_sg_set_words(na), 0ull);
+        ccsx_sg_pack(set.get(), packed.data());
         CK(hipMemcpy(d_set, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
         SegmentParams G{};
         ccsx_segment_opts_default(&G.opts);
-        G.n = n; G.n_adapters = na; G.seq = d_seq; G.seq_off = d_off; G.seq_len = d_len; G.masks = d_set;
-        G.len = (const uint8_t *)(d_set + (size_t)S * CCSX_SG_MASK_WORDS); G.rep = d_rep;
+        G.n = n; G.n_adapters = na; G.seq = d_seq; G.seq_off = d_off; G.seq_len = d_len;
+        ccsx_sg_bind(G, d_set);
         std::vector<double> us;
         long complete = 0;
         for (int r = 0; r <= rounds; ++r) {                          // round 0 warms up and is checked
@@ -72,7 +72,7 @@ int main(int argc, char **argv)
             if (r == 0) {
                 const int m = std::min(n, 512);
                 std::vector<uint8_t> got(rep_bytes), want(ccsx_sg_rep_bytes((size_t)m));
-                CK(hipMemcpy(got.data(), d_rep, rep_bytes, hipMemcpyDeviceToHost));
+                CK(hipMemcpy(got.data(), G.rep, rep_bytes, hipMemcpyDeviceToHost));
                 const SegmentOut g = ccsx_sg_out((int32_t *)got.data(), (size_t)n), w = ccsx_sg_out((int32_t *)want.data(), (size_t)m);
                 ccsx_segment_report rep{m, w.tested, w.overflow, w.n_hits, w.n_cuts, w.n_segments, w.complete, w.orient, w.leftover, w.pieces};
                 if (ccsx_segment_reads_host(set.get(), &G.opts, seq.data(), off.data(), len.data(), m, &rep)) { fprintf(stderr, "host rule: %s\n", g_err.c_str()); return 1; }

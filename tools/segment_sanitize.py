@@ -4,39 +4,29 @@ in the process) around ccsx_segment_reads_host, over every set and read of the t
 plus seeded random sets and reads of its own.  CPU only.  Usage: tools/segment_sanitize.py [--keep DIR]"""
 import os
 import struct
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from host_sanitize import build_and_run  # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import segment_ref as R  # noqa: E402
 
 
-def main() -> int:
-    keep = sys.argv[sys.argv.index("--keep") + 1] if "--keep" in sys.argv else None
-    work = keep or tempfile.mkdtemp(prefix="segment_sanitize_")
-    os.makedirs(work, exist_ok=True)
-    path = os.path.join(work, "cases.bin")
-    with open(path, "wb") as f:
-        for i, (_, S, o, reads) in enumerate(R.limit_cases()):
-            f.write(struct.pack("<4i", len(S), o["max_dist_pct"], o["min_len"], len(reads)))
-            for p in S:
-                f.write(struct.pack("<i", len(p)) + np.asarray(p, np.uint8).tobytes())
-            for r in reads:
-                f.write(struct.pack("<i", len(r)) + np.asarray(r, np.uint8).tobytes())
-            want = R.expected(i)
-            for k in R.PLANES:
-                f.write(np.ascontiguousarray(want[k], np.int32).tobytes())
-            f.write(np.ascontiguousarray(want["pieces"]).tobytes())
-    exe = os.path.join(work, "segment_sanitize")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "ccs_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tools", "segment_sanitize", "main.cpp"), "-o", exe])
-    return subprocess.call([exe, path])
+def write_cases(f) -> None:
+    for i, (_, S, o, reads) in enumerate(R.limit_cases()):
+        f.write(struct.pack("<4i", len(S), o["max_dist_pct"], o["min_len"], len(reads)))
+        for p in S:
+            f.write(struct.pack("<i", len(p)) + np.asarray(p, np.uint8).tobytes())
+        for r in reads:
+            f.write(struct.pack("<i", len(r)) + np.asarray(r, np.uint8).tobytes())
+        want = R.expected(i)
+        for k in R.PLANES:
+            f.write(np.ascontiguousarray(want[k], np.int32).tobytes())
+        f.write(np.ascontiguousarray(want["pieces"]).tobytes())
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(build_and_run("segment", write_cases))
