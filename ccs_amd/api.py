@@ -2425,16 +2425,18 @@ def bgzf_split(data: bytes) -> list:
     return out
 
 
-class InflateCall:
-    """The buffers of one inflate call: payloads packed back to back (gap bytes apart) in src, outputs packed (guard bytes before, between and behind them) in dst"""
+class _CodecCall:
+    """The buffers of one codec call: inputs packed back to back (gap bytes apart) in src, output ranges of range_lens[i] bytes packed (guard bytes before,
+    between and behind them) in dst, the list items (of the subclass's ITEM type: in_off, in_len, the range's length, out_off) and the status array"""
+    ITEM = None
 
-    def __init__(self, payloads, out_lens, guard: int = 0, gap: int = 0, fill: int = 0):
-        n = len(payloads)
-        assert n == len(out_lens)
-        self.blocks = (DeflateBlock * max(n, 1))()
+    def __init__(self, inputs, range_lens, guard: int = 0, gap: int = 0, fill: int = 0):
+        n = len(inputs)
+        assert n == len(range_lens)
+        self.items = (self.ITEM * max(n, 1))()
         src, ioff, ooff = bytearray(), 0, guard
-        for i, (p, ol) in enumerate(zip(payloads, out_lens)):
-            self.blocks[i] = DeflateBlock(ioff, len(p), int(ol), ooff)
+        for i, (p, ol) in enumerate(zip(inputs, range_lens)):
+            self.items[i] = self.ITEM(ioff, len(p), int(ol), ooff)
             src += p + b"\0" * gap
             ioff += len(p) + gap
             ooff += int(ol) + guard
@@ -2445,8 +2447,21 @@ class InflateCall:
         self.dst_len = ooff
         self.status = np.full(max(n, 1), -1, dtype=np.int32)
 
+    def _results(self):
+        """the result arrays as the entry points take them"""
+        return (_ptr(self.status, C.c_int32),)
+
     def args(self):
-        return (_ptr(self.src, C.c_uint8), self.src_len, self.blocks, self.n, _ptr(self.dst, C.c_uint8), self.dst_len, _ptr(self.status, C.c_int32))
+        return (_ptr(self.src, C.c_uint8), self.src_len, self.items, self.n, _ptr(self.dst, C.c_uint8), self.dst_len, *self._results())
+
+
+class InflateCall(_CodecCall):
+    """The buffers of one inflate call: payloads packed back to back (gap bytes apart) in src, outputs packed (guard bytes before, between and behind them) in dst"""
+    ITEM = DeflateBlock
+
+    def __init__(self, payloads, out_lens, guard: int = 0, gap: int = 0, fill: int = 0):
+        super().__init__(payloads, out_lens, guard, gap, fill)
+        self.blocks = self.items
 
     def output(self, i: int) -> bytes:
         b = self.blocks[i]
@@ -2456,52 +2471,50 @@ class InflateCall:
         return b"".join(self.output(i) for i in range(self.n))
 
 
+def _codec_host(fn: str, call: _CodecCall):
+    if getattr(lib(), fn)(*call.args()) != 0:
+        raise RuntimeError(fn + " failed: " + lib().ccsx_last_error().decode())
+    return call.status[:call.n].copy(), call
+
+
 def inflate_host(payloads, out_lens, **layout):
     """ccsx_inflate_blocks_host: the decoder of k_inflate on the calling thread, no device.  Returns (the outputs concatenated, status array, the call)"""
-    call = InflateCall(payloads, out_lens, **layout)
-    if lib().ccsx_inflate_blocks_host(*call.args()) != 0:
-        raise RuntimeError("ccsx_inflate_blocks_host failed: " + lib().ccsx_last_error().decode())
-    return call.outputs(), call.status[:call.n].copy(), call
+    status, call = _codec_host("ccsx_inflate_blocks_host", InflateCall(payloads, out_lens, **layout))
+    return call.outputs(), status, call
 
 
-class Inflater:
-    """One BGZF inflater bound to one GPU (ccsx_inflater_create): its own stream and buffers, nothing shared with a Handle.  Not thread-safe."""
+class _Codec:
+    """One codec object bound to one GPU: its own stream and buffers.  The subclass names its entry points (CREATE, DESTROY, SUBMIT, WAIT, RUN).  Not thread-safe."""
+    CREATE = DESTROY = SUBMIT = WAIT = RUN = ""
 
-    def __init__(self, device: int = 0, max_in_bytes: int = 1 << 21, max_out_bytes: int = 1 << 23, max_blocks: int = 256):
+    def __init__(self, device: int, max_in_bytes: int, max_out_bytes: int, max_items: int):
         self._L = lib()
         self._f = C.c_void_p()
-        self.max_in_bytes, self.max_out_bytes, self.max_blocks = max_in_bytes, max_out_bytes, max_blocks
-        if self._L.ccsx_inflater_create(device, max_in_bytes, max_out_bytes, max_blocks, C.byref(self._f)) != 0:
-            raise RuntimeError("ccsx_inflater_create failed: " + self._L.ccsx_last_error().decode())
+        self.max_in_bytes, self.max_out_bytes = max_in_bytes, max_out_bytes
+        self._check(getattr(self._L, self.CREATE)(device, max_in_bytes, max_out_bytes, max_items, C.byref(self._f)), self.CREATE)
         self._calls = {}
 
     def _check(self, rc, what):
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
 
-    def submit(self, call: InflateCall) -> int:
+    def submit(self, call) -> int:
         t = C.c_int64()
-        self._check(self._L.ccsx_inflate_submit(self._f, *call.args(), C.byref(t)), "ccsx_inflate_submit")
+        self._check(getattr(self._L, self.SUBMIT)(self._f, *call.args(), C.byref(t)), self.SUBMIT)
         self._calls[t.value] = call      # the call's arrays stay alive until the ticket is waited for
         return t.value
 
-    def wait(self, ticket: int) -> InflateCall:
-        self._check(self._L.ccsx_inflate_wait(self._f, ticket), "ccsx_inflate_wait")
+    def wait(self, ticket: int):
+        self._check(getattr(self._L, self.WAIT)(self._f, ticket), self.WAIT)
         return self._calls.pop(ticket)
 
-    def run(self, call: InflateCall) -> InflateCall:
-        self._check(self._L.ccsx_inflate_blocks(self._f, *call.args()), "ccsx_inflate_blocks")
+    def run(self, call):
+        self._check(getattr(self._L, self.RUN)(self._f, *call.args()), self.RUN)
         return call
-
-    def inflate(self, blocks, out_lens):
-        """blocks: raw DEFLATE payloads; out_lens: the bytes each inflates to.  Returns (the outputs concatenated, status array); the bytes of a block whose
-        status is not OK are unspecified"""
-        call = self.run(InflateCall(blocks, out_lens))
-        return call.outputs(), call.status[:call.n].copy()
 
     def close(self):
         if self._f:
-            self._L.ccsx_inflater_destroy(self._f)
+            getattr(self._L, self.DESTROY)(self._f)
             self._f = C.c_void_p()
 
     def __del__(self):
@@ -2509,6 +2522,21 @@ class Inflater:
             self.close()
         except Exception:
             pass
+
+
+class Inflater(_Codec):
+    """One BGZF inflater bound to one GPU (ccsx_inflater_create): its own stream and buffers, nothing shared with a Handle.  Not thread-safe."""
+    CREATE, DESTROY, SUBMIT, WAIT, RUN = "ccsx_inflater_create", "ccsx_inflater_destroy", "ccsx_inflate_submit", "ccsx_inflate_wait", "ccsx_inflate_blocks"
+
+    def __init__(self, device: int = 0, max_in_bytes: int = 1 << 21, max_out_bytes: int = 1 << 23, max_blocks: int = 256):
+        self.max_blocks = max_blocks
+        super().__init__(device, max_in_bytes, max_out_bytes, max_blocks)
+
+    def inflate(self, blocks, out_lens):
+        """blocks: raw DEFLATE payloads; out_lens: the bytes each inflates to.  Returns (the outputs concatenated, status array); the bytes of a block whose
+        status is not OK are unspecified"""
+        call = self.run(InflateCall(blocks, out_lens))
+        return call.outputs(), call.status[:call.n].copy()
 
 
 # ---- BGZF deflate (include/ccsx.h "BGZF deflate on the device"; DESIGN.md §2 "BGZF deflate")
@@ -2535,33 +2563,19 @@ def deflate_code_lengths(freq, max_bits: int = 15) -> np.ndarray:
     return lens
 
 
-class DeflateCall:
+class DeflateCall(_CodecCall):
     """The buffers of one deflate call: spans packed back to back (gap bytes apart) in src, output ranges of out_caps[i] bytes (default: the bound) packed
     (guard bytes before, between and behind them) in dst"""
+    ITEM = DeflateSpan
 
     def __init__(self, spans, out_caps=None, guard: int = 0, gap: int = 0, fill: int = 0):
-        n = len(spans)
-        caps = [deflate_bound(len(p)) for p in spans] if out_caps is None else [int(c) for c in out_caps]
-        assert n == len(caps)
-        self.spans = (DeflateSpan * max(n, 1))()
-        src, ioff, ooff = bytearray(), 0, guard
-        for i, (p, cap) in enumerate(zip(spans, caps)):
-            self.spans[i] = DeflateSpan(ioff, len(p), cap, ooff)
-            src += p + b"\0" * gap
-            ioff += len(p) + gap
-            ooff += cap + guard
-        self.n, self.guard = n, guard
-        self.src = np.frombuffer(bytes(src) or b"\0", dtype=np.uint8).copy()
-        self.src_len = len(src)
-        self.dst = np.full(max(ooff, 1), fill, dtype=np.uint8)
-        self.dst_len = ooff
-        self.out_len = np.full(max(n, 1), -1, dtype=np.int32)
-        self.crc = np.zeros(max(n, 1), dtype=np.uint32)
-        self.status = np.full(max(n, 1), -1, dtype=np.int32)
+        super().__init__(spans, [deflate_bound(len(p)) for p in spans] if out_caps is None else out_caps, guard, gap, fill)
+        self.spans = self.items
+        self.out_len = np.full(max(self.n, 1), -1, dtype=np.int32)
+        self.crc = np.zeros(max(self.n, 1), dtype=np.uint32)
 
-    def args(self):
-        return (_ptr(self.src, C.c_uint8), self.src_len, self.spans, self.n, _ptr(self.dst, C.c_uint8), self.dst_len, _ptr(self.out_len, C.c_int32),
-                _ptr(self.crc, C.c_uint32), _ptr(self.status, C.c_int32))
+    def _results(self):
+        return (_ptr(self.out_len, C.c_int32), _ptr(self.crc, C.c_uint32), _ptr(self.status, C.c_int32))
 
     def stream(self, i: int) -> bytes:
         b = self.spans[i]
@@ -2573,53 +2587,19 @@ class DeflateCall:
 
 def deflate_host(spans, out_caps=None, **layout):
     """ccsx_deflate_spans_host: the encoder of k_deflate on the calling thread, no device.  Returns (the streams, status array, the call)"""
-    call = DeflateCall(spans, out_caps, **layout)
-    if lib().ccsx_deflate_spans_host(*call.args()) != 0:
-        raise RuntimeError("ccsx_deflate_spans_host failed: " + lib().ccsx_last_error().decode())
-    return call.streams(), call.status[:call.n].copy(), call
+    status, call = _codec_host("ccsx_deflate_spans_host", DeflateCall(spans, out_caps, **layout))
+    return call.streams(), status, call
 
 
-class Deflater:
+class Deflater(_Codec):
     """One BGZF deflater bound to one GPU (ccsx_deflater_create): its own stream and buffers, nothing shared with a Handle or an Inflater.  Not thread-safe."""
+    CREATE, DESTROY, SUBMIT, WAIT, RUN = "ccsx_deflater_create", "ccsx_deflater_destroy", "ccsx_deflate_submit", "ccsx_deflate_wait", "ccsx_deflate_spans"
 
     def __init__(self, device: int = 0, max_in_bytes: int = 1 << 23, max_out_bytes: int = 1 << 23, max_spans: int = 256):
-        self._L = lib()
-        self._f = C.c_void_p()
-        self.max_in_bytes, self.max_out_bytes, self.max_spans = max_in_bytes, max_out_bytes, max_spans
-        if self._L.ccsx_deflater_create(device, max_in_bytes, max_out_bytes, max_spans, C.byref(self._f)) != 0:
-            raise RuntimeError("ccsx_deflater_create failed: " + self._L.ccsx_last_error().decode())
-        self._calls = {}
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
-
-    def submit(self, call: DeflateCall) -> int:
-        t = C.c_int64()
-        self._check(self._L.ccsx_deflate_submit(self._f, *call.args(), C.byref(t)), "ccsx_deflate_submit")
-        self._calls[t.value] = call      # the call's arrays stay alive until the ticket is waited for
-        return t.value
-
-    def wait(self, ticket: int) -> DeflateCall:
-        self._check(self._L.ccsx_deflate_wait(self._f, ticket), "ccsx_deflate_wait")
-        return self._calls.pop(ticket)
-
-    def run(self, call: DeflateCall) -> DeflateCall:
-        self._check(self._L.ccsx_deflate_spans(self._f, *call.args()), "ccsx_deflate_spans")
-        return call
+        self.max_spans = max_spans
+        super().__init__(device, max_in_bytes, max_out_bytes, max_spans)
 
     def deflate(self, spans):
         """spans: plain byte strings of at most DEFLATE_MAX_IN bytes.  Returns (the streams, the CRC32s, status array)"""
         call = self.run(DeflateCall(spans))
         return call.streams(), call.crc[:call.n].copy(), call.status[:call.n].copy()
-
-    def close(self):
-        if self._f:
-            self._L.ccsx_deflater_destroy(self._f)
-            self._f = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

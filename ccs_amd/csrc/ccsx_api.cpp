@@ -26,15 +26,6 @@
 #include "ccsx_kernels.h"
 #include "refine_core.h"
 
-#define HIPTRY(expr)                                                                                           \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) {                                                                                \
-            ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                                 \
-            return -2;                                                                                         \
-        }                                                                                                      \
-    } while (0)
-
 #define CCSX_SLOTS 3
 
 namespace {

@@ -8,6 +8,16 @@
 
 void ccsx_set_error(const std::string &s);
 
+// a HIP call of an entry point: its failure is the entry point's, -2 with the call and HIP's text as the error
+#define HIPTRY(expr)                                                                                           \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) {                                                                                \
+            ccsx_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                                 \
+            return -2;                                                                                         \
+        }                                                                                                      \
+    } while (0)
+
 // capacity of the draft / consensus of a ZMW whose longest subread has maxL bases
 static inline int64_t ccsx_draft_cap(int64_t maxL) { return maxL + maxL / 4 + 64; }
 // POA vertex capacity for the same ZMW

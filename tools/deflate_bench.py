@@ -15,33 +15,21 @@
 """
 import argparse
 import os
-import re
 import shutil
-import statistics
 import subprocess
 import sys
 import tempfile
-import time
 import zlib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KB_DIR = os.path.join(ROOT, "tools", "deflate_bench", "build")
-KB = os.path.join(KB_DIR, "kernel_bench")
-CCS = os.path.join(ROOT, "ccs_amd", "bin", "ccs")
+import codec_bench as B
+from codec_bench import CCS, ROOT
+
+KB = os.path.join(B.kb_dir("deflate"), "kernel_bench")
+LINES = r"GPU workers|ZMWs/s|engine \(ticket|--gpu-deflate: \d"
 
 
 def build():
-    os.makedirs(KB_DIR, exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "ccs_amd", "csrc")]
-    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-falign-loops=64", *inc,
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "ccs_amd", "csrc", "ccsx_deflate.hip"), "-o", os.path.join(KB_DIR, "ccsx_deflate.o")],
-                       capture_output=True, text=True, check=True)
-    keep = [l.split("remark:", 1)[1].replace(" [-Rpass-analysis=kernel-resource-usage]", "").strip() for l in p.stderr.splitlines() if "remark" in l]
-    with open(os.path.join(KB_DIR, "resources.txt"), "w") as f:
-        f.write("k_deflate resources (the library's flags, gfx950): " + "; ".join(" ".join(k.split()) for k in keep if not k.startswith("Function Name")) +
-                " -> LDS admits one workgroup of four wave64 per CU, 256 spans resident on the card\n")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", *inc, os.path.join(ROOT, "tools", "deflate_bench", "kernel_bench.hip"), "-o", KB, "-lz"])
+    B.build("deflate", "LDS admits one workgroup of four wave64 per CU, 256 spans resident on the card")
 
 
 def ratio_table():
@@ -72,18 +60,6 @@ def ratio_table():
     return lines
 
 
-def ccs_run(exe, bam, out, extra, log=None):
-    t0 = time.time()
-    p = subprocess.run([exe, bam, out, "-j", "16", "--log-level", "INFO", "--suppress-reports", *extra], capture_output=True, text=True, timeout=900)
-    dt = time.time() - t0
-    if p.returncode != 0:
-        raise RuntimeError(f"{exe} {extra}: exit {p.returncode}: {p.stderr[-2000:]}")
-    lines = [l for l in p.stderr.splitlines() if re.search(r"GPU workers|ZMWs/s|engine \(ticket|--gpu-deflate: \d", l)]
-    if log is not None:
-        log.extend("      " + l for l in lines[-8:])
-    return dt
-
-
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--build", action="store_true")
@@ -104,32 +80,21 @@ def main() -> int:
     rep = []
     try:
         rep.append(f"tools/deflate_bench.py --run --zmws {a.zmws} --rounds {a.rounds}" + (" --parent-ccs ..." if a.parent_ccs else "") + "   (one MI355X, 16 host threads; DESIGN.md §7 \"GPU deflate\")")
-        res = os.path.join(KB_DIR, "resources.txt")
-        rep.append(open(res).read().strip() if os.path.exists(res) else "k_deflate resources: not recorded (run --build first)")
+        rep.append(B.resources("deflate"))
         rep.extend(ratio_table())
         print("\n".join(rep), flush=True)
         bam = os.path.join(work, "s.subreads.bam")
-        subprocess.check_call([CCS, "--write-synthetic", f"{a.zmws},10,10000,1", bam, "-j", "16"], timeout=1500)
-        rep.append(f"input: {a.zmws} ZMWs x 10 passes x 10 kb, {os.path.getsize(bam) / 1e9:.2f} GB of BGZF")
+        rep.append(B.write_synthetic(a.zmws, bam))
         for wname, wextra in (("plain", []), ("--hifi-kinetics", ["--hifi-kinetics"])):
             arms = [("off", CCS, []), ("on", CCS, ["--gpu-deflate"])]
             if a.parent_ccs:
                 arms.insert(1, ("parent commit's binary, off", a.parent_ccs, []))
-            times = {n: [] for n, *_ in arms}
-            detail, size = {}, {}
             out = {n: os.path.join(work, f"o{k}.bam") for k, (n, *_) in enumerate(arms)}
-            for r in range(a.rounds):
-                for name, exe, extra in arms:
-                    log = []
-                    times[name].append(ccs_run(exe, bam, out[name], wextra + extra, log))
-                    detail[name] = log
-                    size[name] = os.path.getsize(out[name])
-                    print(f"{wname} round {r} {name}: {times[name][-1]:.2f} s = {a.zmws / times[name][-1]:.0f} ZMWs/s", flush=True)
+            times, detail = B.alternate(arms, a.rounds, a.zmws, lambda arm, log: B.ccs_run(arm[1], bam, out[arm[0]], wextra + arm[2], LINES, None, log), wname + " ")
+            size = {n: os.path.getsize(out[n]) for n, *_ in arms}
             rep.append(f"end to end, {wname}: ccs BAM -> BAM, -j 16, one card, {a.rounds} alternating rounds (wall seconds of the whole process; ZMWs/s = {a.zmws} / wall)")
             for name, *_ in arms:
-                t = times[name]
-                rep.append(f"  {name:28s} median {statistics.median(t):6.2f} s  min {min(t):6.2f}  max {max(t):6.2f}   = {a.zmws / statistics.median(t):7.0f} ZMWs/s   "
-                           f"OUT.bam {size[name] / 1e6:.1f} MB   rounds: " + " ".join(f"{x:.2f}" for x in t))
+                rep.append(f"  {name:28s} {B.spread(times[name], a.zmws)}   OUT.bam {size[name] / 1e6:.1f} MB   {B.rounds_of(times[name])}")
                 rep.extend(detail[name])
             p = subprocess.run([KB, out["off"], "2e8"], capture_output=True, text=True, timeout=600)
             rep.append(f"{wname}: " + (p.stdout.strip() or ("kernel_bench failed: " + p.stderr.strip()[-500:])))

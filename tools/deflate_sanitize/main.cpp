@@ -2,15 +2,22 @@
 // the project's own decoder (ccs_amd/csrc/inflate_core.h).  Reads the case file tools/deflate_sanitize.py writes (every test input), adds seeded random inputs of
 // its own, and for each: encodes from an input buffer of exactly in_len bytes into an output buffer of exactly the bound (so one byte out of range is a report),
 // decodes the stream back and compares, checks the CRC against a bitwise CRC32, then encodes again into a buffer of exactly out_len bytes (same stream) and of
-// out_len - 1 bytes (OUTPUT_FULL, nothing past the buffer).  Exit 0 = all of that held; a sanitizer report aborts.
+// out_len - 1 bytes (OUTPUT_FULL, nothing past the buffer).  Then the range / overlap check both codecs' entry points share (ccs_amd/csrc/codec_check.h) takes
+// hostile lists of both item types, each from an array of exactly its items: offsets at the ends of int64 are refused without a signed overflow.
+// Exit 0 = all of that held; a sanitizer report aborts.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "codec_check.h"
 #include "deflate_core.h"
 #include "inflate_core.h"
+
+static std::string last_error;
+void ccsx_set_error(const std::string &s) { last_error = s; }
 
 static ccsx_defl_work W;
 static ccsx_infl_tables T;
@@ -61,6 +68,49 @@ static int check(const std::vector<uint8_t> &in, size_t k)
     return 0;
 }
 
+// one list through the check: the items (in_off, in_len, out_len | out_cap, out_off) against src of 4 and dst of dst_len bytes; `want`: a part of the refusal's
+// text, or NULL for a list that is accepted
+template <typename D> static int hostile(const char *what, std::vector<typename D::Item> items, int64_t dst_len, const char *want)
+{
+    using Item = typename D::Item;
+    Item *a = (Item *)malloc(items.size() ? items.size() * sizeof(Item) : 1);
+    if (!items.empty()) memcpy(a, items.data(), items.size() * sizeof(Item));
+    uint8_t src[4] = {0}, dst[1] = {0};
+    std::vector<int32_t> order;
+    last_error.clear();
+    const int rc = ccsx_codec_check<D>("check", src, 4, a, (int32_t)items.size(), dst, dst_len, true, order);
+    free(a);
+    const bool ok = want ? (rc == -1 && last_error.find(want) != std::string::npos && last_error.find(D::noun) != std::string::npos) : rc == 0;
+    if (!ok) fprintf(stderr, "range check, %s %s: rc %d, \"%s\"\n", D::noun, what, rc, last_error.c_str());
+    return ok ? 0 : 1;
+}
+
+template <typename D> static int hostile_lists()
+{
+    const int64_t hi = INT64_MAX, lo = INT64_MIN, far = (int64_t)1 << 40;
+    int bad = 0;
+    bad += hostile<D>("ends at the ends", {{0, 2, 10, 0}, {2, 2, 10, 10}}, 20, nullptr);
+    bad += hostile<D>("descending", {{0, 2, 10, 10}, {2, 2, 10, 0}}, 20, nullptr);
+    bad += hostile<D>("input one past", {{0, 2, 10, 0}, {3, 2, 10, 10}}, 20, "input range outside src");
+    bad += hostile<D>("output one past", {{0, 2, 10, 0}, {2, 2, 10, 11}}, 20, "output range outside dst");
+    bad += hostile<D>("in_len -1", {{0, -1, 10, 0}}, 20, D::limited(typename D::Item{0, -1, 10, 0}) < 0 ? D::limit_text : "input range outside src");
+    bad += hostile<D>("range length -1", {{0, 2, -1, 0}}, 20, D::limited(typename D::Item{0, 2, -1, 0}) < 0 ? D::limit_text : "output range outside dst");
+    bad += hostile<D>("limit + 1", {{0, 65537, 65537, 0}}, far, D::limit_text);
+    for (const int64_t off : {hi, lo, far, hi - 1, lo + 1, (int64_t)-1}) {
+        bad += hostile<D>("in_off extreme", {{0, 2, 10, 0}, {off, 2, 10, 10}}, 20, "input range outside src");
+        bad += hostile<D>("out_off extreme", {{0, 2, 10, 0}, {2, 2, 10, off}}, 20, "output range outside dst");
+        bad += hostile<D>("out_off extreme in a dst as long as int64", {{0, 2, 10, 0}, {2, 2, 10, off}}, hi, off < 0 || off > hi - 10 ? "output range outside dst" : nullptr);
+    }
+    bad += hostile<D>("ends at the end of an int64 dst", {{0, 2, 10, hi - 10}, {2, 2, 10, 0}}, hi, nullptr);
+    bad += hostile<D>("overlap by one", {{0, 2, 10, 0}, {2, 2, 10, 9}}, 20, "0 and 1: output ranges overlap");
+    bad += hostile<D>("overlap by one, descending", {{0, 2, 10, 9}, {2, 2, 10, 0}}, 20, "1 and 0: output ranges overlap");
+    bad += hostile<D>("overlap at the end of an int64 dst", {{0, 2, 10, hi - 10}, {2, 2, 10, hi - 19}}, hi, "1 and 0: output ranges overlap");
+    bad += hostile<D>("empty range between two overlapping ones", {{0, 2, 10, 0}, {2, 0, 0, 5}, {2, 2, 10, 5}}, 15, "0 and 2: output ranges overlap");
+    bad += hostile<D>("empty range between two that touch", {{0, 2, 10, 0}, {2, 0, 0, 10}, {2, 2, 10, 10}}, 20, nullptr);
+    bad += hostile<D>("no items", {}, 0, nullptr);
+    return bad;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) { fprintf(stderr, "usage: deflate_sanitize CASES.bin\n"); return 2; }
@@ -92,6 +142,7 @@ int main(int argc, char **argv)
     }
     long bad = 0;
     for (size_t k = 0; k < cases.size(); ++k) bad += check(cases[k], k);
+    bad += hostile_lists<ccsx_inflate_items>() + hostile_lists<ccsx_deflate_items>();
     printf("deflate_sanitize: %zu inputs (%ld coded, %ld stored), %ld bytes in, %ld bytes out, %ld failures\n", cases.size(), n_coded, n_stored, bytes_in, bytes_out, bad);
     return bad ? 1 : 0;
 }

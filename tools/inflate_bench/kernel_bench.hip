@@ -5,15 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <vector>
 
 #include "../../ccs_amd/csrc/ccsx_inflate.hip"
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
+#include "../bgzf_bench.h"
 
 int main(int argc, char **argv)
 {
@@ -25,18 +20,10 @@ int main(int argc, char **argv)
     std::vector<uint8_t> src;
     std::vector<ccsx_deflate_block> blk;
     int64_t out = 0;
-    uint8_t h[18];
-    while (out < target && fread(h, 1, 18, f) == 18) {
-        if (h[0] != 0x1f || h[1] != 0x8b || h[12] != 'B' || h[13] != 'C' || (h[10] | h[11] << 8) != 6) { fprintf(stderr, "not a plain BGZF block\n"); return 2; }
-        const size_t bsize = (size_t)(h[16] | h[17] << 8) + 1, at = src.size();
-        src.resize(at + bsize - 18);
-        if (fread(src.data() + at, 1, bsize - 18, f) != bsize - 18) { fprintf(stderr, "truncated file\n"); return 2; }
-        const uint8_t *t = src.data() + src.size() - 4;
-        const uint32_t isize = t[0] | t[1] << 8 | t[2] << 16 | (uint32_t)t[3] << 24;
-        if (isize > 65536) { fprintf(stderr, "block larger than 64 KiB\n"); return 2; }
-        if (isize) blk.push_back({(int64_t)at, (int32_t)(bsize - 26), (int32_t)isize, out});
+    bgzf_walk(f, src, true, [&] { return out < target; }, [&](size_t at, size_t len, uint32_t isize) {
+        if (isize) blk.push_back({(int64_t)at, (int32_t)(len - 8), (int32_t)isize, out});
         out += isize;
-    }
+    });
     fclose(f);
     if (blk.empty()) { fprintf(stderr, "no blocks\n"); return 2; }
     uint8_t *d_src, *d_dst; ccsx_deflate_block *d_blk; int32_t *d_st;
@@ -44,29 +31,22 @@ int main(int argc, char **argv)
     CK(hipMalloc((void **)&d_blk, blk.size() * sizeof(blk[0]))); CK(hipMalloc((void **)&d_st, blk.size() * 4));
     CK(hipMemcpy(d_src, src.data(), src.size(), hipMemcpyHostToDevice));
     CK(hipMemcpy(d_blk, blk.data(), blk.size() * sizeof(blk[0]), hipMemcpyHostToDevice));
-    hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    std::vector<double> gbs;
-    for (int r = 0; r <= rounds; ++r) {                           // round 0 warms up and is checked
-        CK(hipEventRecord(e0, s));
-        if (ccsx_launch_inflate(s, d_src, (int64_t)src.size(), d_blk, (int32_t)blk.size(), d_dst, out, d_st)) { fprintf(stderr, "launch failed\n"); return 1; }
-        CK(hipEventRecord(e1, s));
-        CK(hipEventSynchronize(e1));
-        float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1));
-        if (r == 0) {
-            std::vector<uint8_t> got((size_t)out), ref(65536); std::vector<int32_t> st(blk.size());
-            CK(hipMemcpy(got.data(), d_dst, (size_t)out, hipMemcpyDeviceToHost)); CK(hipMemcpy(st.data(), d_st, st.size() * 4, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < blk.size(); ++i) {
-                z_stream zs; memset(&zs, 0, sizeof(zs)); inflateInit2(&zs, -15);
-                zs.next_in = src.data() + blk[i].in_off; zs.avail_in = (uInt)blk[i].in_len; zs.next_out = ref.data(); zs.avail_out = 65536;
-                const int rc = inflate(&zs, Z_FINISH); inflateEnd(&zs);
-                if (rc != Z_STREAM_END || st[i] != 0 || (int32_t)zs.total_out != blk[i].out_len || memcmp(ref.data(), got.data() + blk[i].out_off, zs.total_out)) {
-                    fprintf(stderr, "block %zu differs from zlib (status %d)\n", i, st[i]); return 1;
-                }
+    const auto launch = [&](hipStream_t s) { return ccsx_launch_inflate(s, d_src, (int64_t)src.size(), d_blk, (int32_t)blk.size(), d_dst, out, d_st); };
+    const auto check0 = [&]() -> int {
+        std::vector<uint8_t> got((size_t)out), ref(65536); std::vector<int32_t> st(blk.size());
+        CK(hipMemcpy(got.data(), d_dst, (size_t)out, hipMemcpyDeviceToHost)); CK(hipMemcpy(st.data(), d_st, st.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < blk.size(); ++i) {
+            z_stream zs; memset(&zs, 0, sizeof(zs)); inflateInit2(&zs, -15);
+            zs.next_in = src.data() + blk[i].in_off; zs.avail_in = (uInt)blk[i].in_len; zs.next_out = ref.data(); zs.avail_out = 65536;
+            const int rc = inflate(&zs, Z_FINISH); inflateEnd(&zs);
+            if (rc != Z_STREAM_END || st[i] != 0 || (int32_t)zs.total_out != blk[i].out_len || memcmp(ref.data(), got.data() + blk[i].out_off, zs.total_out)) {
+                fprintf(stderr, "block %zu differs from zlib (status %d)\n", i, st[i]); return 1;
             }
-        } else gbs.push_back(out / (ms * 1e6));
-    }
-    std::sort(gbs.begin(), gbs.end());
+        }
+        return 0;
+    };
+    std::vector<double> gbs;
+    if (bgzf_time_rounds(rounds, (double)out, launch, check0, &gbs)) return 1;
     printf("k_inflate alone: %zu blocks, %.1f MB compressed -> %.1f MB inflated (ratio %.2f), every block equals zlib; %d rounds: median %.2f GB/s inflated (min %.2f, max %.2f)\n",
            blk.size(), src.size() / 1e6, out / 1e6, (double)out / src.size(), rounds, gbs[gbs.size() / 2], gbs.front(), gbs.back());
     return 0;
