@@ -681,7 +681,7 @@ class OrientReport:
                              _ptr(self.votes_opp, C.c_int32))
 
 
-# ---- the analyses on final reads (barcode calls, segmentation): what they share.  Each supplies a set (a _PatternSet), an opts struct and a report class that
+# ---- the analyses on final reads (barcode calls, segmentation, cDNA reads): what they share.  Each supplies a set (a _PatternSet), an opts struct and a report class that
 # names its request struct, its opts default and its ccsx_*_reads symbol (REQUEST, OPTS_DEFAULT, READS)
 class _PatternSet:
     """a set struct of the C ABI: a count, len[max] and seq[max][max_len].  COUNT: the count's field; NOUN: what a message calls a pattern"""
@@ -870,6 +870,82 @@ def _segment_reads_args(sset, opts, reads, report):
 def segment_reads_host(sset: SegmentSet, reads, opts: "SegmentOpts | None" = None, report: "SegmentReport | None" = None) -> SegmentReport:
     """ccsx_segment_reads_host: the segment rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
     return _reads_host(SegmentReport, sset, reads, opts, report)
+
+
+# ---- full-length cDNA reads (include/ccsx.h ccsx_cdna_*; DESIGN.md §2 "cDNA rule")
+CDNA_MAX_PRIMERS, CDNA_MIN_LEN, CDNA_MAX_LEN = 64, 8, 64
+CDNA_NO_PRIMER, CDNA_ONE_END, CDNA_SAME_ROLE, CDNA_SHORT, CDNA_CONCATEMER, CDNA_NO_TAIL, CDNA_FULL_LENGTH = range(7)
+CDNA_NAMES = ("NO_PRIMER", "ONE_END", "SAME_ROLE", "SHORT", "CONCATEMER", "NO_TAIL", "FULL_LENGTH")
+CDNA_5P, CDNA_3P = 0, 1                          # the roles of CdnaPrimers.role
+
+
+class CdnaOpts(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("window", "max_dist_pct", "min_margin", "polya_mismatch", "polya_xdrop", "polya_max", "min_polya", "min_len")]
+
+
+class CdnaPrimers(_PatternSet, C.Structure):
+    """ccsx_cdna_set: 2 .. 64 primers of 8 .. 64 codes 0 .. 3, as the oligos, each with a role (CDNA_5P / CDNA_3P); at least one of each role"""
+    _fields_ = [("n_primers", C.c_int32), ("len", C.c_int32 * CDNA_MAX_PRIMERS), ("role", C.c_uint8 * CDNA_MAX_PRIMERS),
+                ("seq", (C.c_uint8 * CDNA_MAX_LEN) * CDNA_MAX_PRIMERS)]
+    COUNT, NOUN = "n_primers", "primer"
+
+    @classmethod
+    def from_strings(cls, seqs, roles):
+        """as _PatternSet.from_strings, with one role per primer; roles are checked by the call that takes the set"""
+        seqs, roles = list(seqs), [int(r) for r in roles]
+        if len(seqs) != len(roles):
+            raise ValueError("one role per primer")
+        s = super().from_strings(seqs)
+        for k, r in enumerate(roles):
+            s.role[k] = r & 0xff
+        return s
+
+    from_codes = from_strings
+
+    def roles(self) -> list:
+        return [int(self.role[k]) for k in range(self.n_primers)]
+
+
+CDNA_READ_PLANES = ("tested", "cls", "strand", "start", "end", "polya_len", "n_internal", "first_internal")
+CDNA_END_PLANES = ("idx", "dist", "second", "clip")
+
+
+class CCdnaReport(C.Structure):
+    _fields_ = [("n_zmw", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in CDNA_READ_PLANES + CDNA_END_PLANES]
+
+
+class CCdnaRequest(C.Structure):
+    """ccsx_cdna_request: full-length cDNA reads in the fused path (ccsx_consensus_cdna / ccsx_submit_cdna)"""
+    _fields_ = [("opts", C.POINTER(CdnaOpts)), ("set", C.POINTER(CdnaPrimers)), ("report", C.POINTER(CCdnaReport)), ("reserved", C.c_int32 * 2)]
+
+
+def cdna_opts_default() -> CdnaOpts:
+    o = CdnaOpts()
+    lib().ccsx_cdna_opts_default(C.byref(o))
+    return o
+
+
+class CdnaReport(_PlaneReport):
+    """ccsx_cdna_report: per read the eight int32 planes of CDNA_READ_PLANES (cls: CDNA_NAMES; the slice [start, end) of classes CONCATEMER .. FULL_LENGTH) and
+    per end [n, 2] the best primer, its distance, the runner-up's distance and the clip"""
+    FIELDS = CDNA_READ_PLANES + CDNA_END_PLANES
+    PLANES = _int_planes(*CDNA_READ_PLANES) + tuple((k, np.int32, (2,)) for k in CDNA_END_PLANES)
+    CSTRUCT, REQUEST, OPTS_DEFAULT, READS = CCdnaReport, CCdnaRequest, staticmethod(cdna_opts_default), "ccsx_cdna_reads"
+
+    def c_struct(self) -> CCdnaReport:
+        r = CCdnaReport()
+        r.n_zmw = len(self.tested)
+        for k in self.FIELDS:
+            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
+        return r
+
+    def fields(self, z: int) -> dict:
+        return {k: getattr(self, k)[z].tolist() for k in self.FIELDS}
+
+
+def cdna_reads_host(primers: CdnaPrimers, reads, opts: "CdnaOpts | None" = None, report: "CdnaReport | None" = None) -> CdnaReport:
+    """ccsx_cdna_reads_host: the cDNA rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
+    return _reads_host(CdnaReport, primers, reads, opts, report)
 
 
 # ---- representative reads (include/ccsx.h ccsx_represent_*; DESIGN.md §2 "Representative rule")
@@ -1206,6 +1282,7 @@ EXPORTS = [
     "ccsx_barcode_opts_default", "ccsx_barcode_rule_version", "ccsx_barcode_reads_host", "ccsx_barcode_reads", "ccsx_consensus_barcodes", "ccsx_submit_barcodes",
     "ccsx_segment_opts_default", "ccsx_segment_rule_version", "ccsx_segment_chunk", "ccsx_segment_reads_host", "ccsx_segment_reads", "ccsx_consensus_segments",
     "ccsx_submit_segments",
+    "ccsx_cdna_opts_default", "ccsx_cdna_rule_version", "ccsx_cdna_reads_host", "ccsx_cdna_reads", "ccsx_consensus_cdna", "ccsx_submit_cdna",
     "ccsx_represent_rule_version", "ccsx_represent_host", "ccsx_consensus_represent", "ccsx_submit_represent",
 ]
 
@@ -1358,6 +1435,13 @@ def lib() -> C.CDLL:
         L.ccsx_segment_reads.argtypes = [C.c_void_p] + _sgreads
         L.ccsx_consensus_segments.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CSegmentRequest)]
         L.ccsx_submit_segments.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CSegmentRequest), C.POINTER(C.c_int64)]
+        L.ccsx_cdna_opts_default.restype = None
+        L.ccsx_cdna_opts_default.argtypes = [C.POINTER(CdnaOpts)]
+        _cdreads = [C.POINTER(CdnaPrimers), C.POINTER(CdnaOpts), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(CCdnaReport)]
+        L.ccsx_cdna_reads_host.argtypes = _cdreads
+        L.ccsx_cdna_reads.argtypes = [C.c_void_p] + _cdreads
+        L.ccsx_consensus_cdna.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CCdnaRequest)]
+        L.ccsx_submit_cdna.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CCdnaRequest), C.POINTER(C.c_int64)]
         L.ccsx_represent_host.argtypes = [C.POINTER(CBatch), C.POINTER(Opts), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                           C.POINTER(CRepresentRequest), C.POINTER(CResults)]
         L.ccsx_consensus_represent.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CRepresentRequest)]
@@ -1756,12 +1840,12 @@ def _requests(pileup: "Pileup | None" = None, tandem: "np.ndarray | None" = None
 
 
 
-def _reads_request(key: str, noun: str):
-    """how Handle._fused builds the request of an analysis on final reads from (report, set, opts)"""
+def _reads_request(key: str, set_kw: str):
+    """how Handle._fused builds the request of an analysis on final reads from (report, set, opts); set_kw: Handle.submit's keyword for the set"""
     def build(what):
         rep, pset, opts = what
         if pset is None:
-            raise ValueError(f"{key}: a {noun}_set is needed")
+            raise ValueError(f"{key}: a {set_kw} is needed")
         return _pattern_request(type(rep), pset, opts, rep.c_struct()) + (rep,)
     return build
 
@@ -1769,17 +1853,18 @@ def _reads_request(key: str, noun: str):
 # The requests of which a fused run takes one at most, and none beside the heteroduplex request, as Handle._fused walks them: its keyword there (ccsx_*_<keyword>
 # is the entry point), how the refusal of a combination begins, and how its value becomes the C request (first element) and what must outlive the call
 _EXCLUSIVE = (("handoff", "the heteroduplex request and the hand-off are not combined", _handoff_request),
-              ("barcodes", "the barcode request is not combined", _reads_request("barcodes", "barcode")),
+              ("barcodes", "the barcode request is not combined", _reads_request("barcodes", "barcode_set")),
               ("represent", "the represent request is not combined", lambda what: _represent_request(*what)),
-              ("segments", "the segment request is not combined", _reads_request("segments", "segment")))
+              ("segments", "the segment request is not combined", _reads_request("segments", "segment_set")),
+              ("cdna", "the cdna request is not combined", _reads_request("cdna", "cdna_primers")))
 
 
-def _exclusive(other: bool, handoff=None, barcodes=None, represent=None, segments=None):
+def _exclusive(other: bool, handoff=None, barcodes=None, represent=None, segments=None, cdna=None):
     """the one request of _EXCLUSIVE among the arguments, as (row, value), or None.  ValueError for two of them, and for one when `other`: the run carries
     the heteroduplex request (or goes through an entry point that does not take a ccsx_requests)"""
-    asked = [(row, what) for row, what in zip(_EXCLUSIVE, (handoff, barcodes, represent, segments)) if what is not None]
+    asked = [(row, what) for row, what in zip(_EXCLUSIVE, (handoff, barcodes, represent, segments, cdna)) if what is not None]
     if asked and (len(asked) > 1 or other):
-        raise ValueError(asked[-1][0][1] + ": a run takes one of the hand-off, the barcode, the represent and the segment request, beside the members of "
+        raise ValueError(asked[-1][0][1] + ": a run takes one of the hand-off, the barcode, the represent, the segment and the cdna request, beside the members of "
                          "ccsx_requests and without the heteroduplex request")
     return asked[-1] if asked else None
 
@@ -1803,18 +1888,19 @@ class Handle:
         if rc != 0:
             raise RuntimeError(f"{what} failed: " + self._L.ccsx_last_error().decode())
 
-    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None, represent=None, segments=None):
+    def _fused(self, form: str, batch: Batch, res: "Results", requests, *ticket, handoff: "Handoff | None" = None, barcodes=None, represent=None, segments=None, cdna=None):
         """One fused run (form 'consensus', or 'submit' with the ticket to fill) through the most general entry point that takes what _requests made:
         ccsx_*_hd with a heteroduplex request and nothing but extras, ccsx_*_requests when _requests made a CRequests (a coverage request, or
         via_requests; ccsx_*_hd_requests when a heteroduplex request goes with it), else ccsx_*_control (NULL: not asked for).  handoff: through ccsx_*_handoff, with the CRequests _requests made (via_requests); its
         structs join the requests' keep list.  barcodes: (report, set, opts), through ccsx_*_barcodes in the same way (not together with a hand-off).
         represent: (report, subread_fallback, kinetics), through ccsx_*_represent in the same way (not together with a hand-off or barcodes).
-        segments: (report, set, opts), through ccsx_*_segments in the same way (not together with a hand-off, barcodes or represent).  Returns the C structs"""
+        segments: (report, set, opts), through ccsx_*_segments in the same way (not together with a hand-off, barcodes or represent).
+        cdna: (report, primers, opts), through ccsx_*_cdna in the same way (not together with any of the four).  Returns the C structs"""
         ex, hq, fq, aq, cq, _keep = requests
         name, args = (f"ccsx_{form}_hd", (ex, hq)) if hq is not None else (f"ccsx_{form}_control", (ex, fq, aq, cq))
         if _keep and isinstance(_keep[-1], CRequests):
             name, args = (f"ccsx_{form}_hd_requests", (_keep[-1], hq)) if hq is not None else (f"ccsx_{form}_requests", (_keep[-1],))
-        one = _exclusive(name != f"ccsx_{form}_requests", handoff, barcodes, represent, segments)
+        one = _exclusive(name != f"ccsx_{form}_requests", handoff, barcodes, represent, segments, cdna)
         if one is not None:
             (key, _, build), what = one
             req = build(what)
@@ -2033,6 +2119,18 @@ class Handle:
         """ccsx_segment_reads: k_segment on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
         return self._reads(SegmentReport, sset, reads, opts, report)
 
+    # ---- full-length cDNA reads (ccsx_consensus_cdna / ccsx_cdna_reads): primers, strand, poly(A) tail and concatemers of the final reads
+    def consensus_cdna(self, batch: Batch, primers: CdnaPrimers, opts: "CdnaOpts | None" = None, res: "Results | None" = None,
+                       **requests) -> tuple["Results", CdnaReport]:
+        """(results, cdna report).  primers: the CdnaPrimers; opts: the CdnaOpts (None: the defaults); res: the caller's Results.  requests: Handle.submit's
+        keyword arguments for the other requests of the same run (pileup=, tandem=, fold=, adapters=, control=, coverage= ... with their reports; not hd=,
+        handoff=, barcodes=, represent=, segments=)"""
+        return self._consensus_reads("cdna", CdnaReport, batch, primers, opts, res, requests)
+
+    def cdna_reads(self, primers: CdnaPrimers, reads, opts: "CdnaOpts | None" = None, report: "CdnaReport | None" = None) -> CdnaReport:
+        """ccsx_cdna_reads: k_cdna on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
+        return self._reads(CdnaReport, primers, reads, opts, report)
+
     # ---- representative reads (ccsx_consensus_represent): a draft or a subread in the result planes of every ZMW that was not polished
     def consensus_represent(self, batch: Batch, subread_fallback: bool = False, kinetics: bool = False, res: "Results | None" = None,
                             **requests) -> tuple["Results", RepresentReport]:
@@ -2120,7 +2218,8 @@ class Handle:
                coverage_opts: "CoverageOpts | None" = None, coverage_gate: int = 0, handoff: "Handoff | None" = None,
                barcodes: "BarcodeReport | None" = None, barcode_set: "BarcodeSet | None" = None, barcode_opts: "BarcodeOpts | None" = None,
                represent: "RepresentReport | None" = None, represent_fallback: bool = False, represent_kinetics: bool = False,
-               segments: "SegmentReport | None" = None, segment_set: "SegmentSet | None" = None, segment_opts: "SegmentOpts | None" = None) -> int:
+               segments: "SegmentReport | None" = None, segment_set: "SegmentSet | None" = None, segment_opts: "SegmentOpts | None" = None,
+               cdna: "CdnaReport | None" = None, cdna_primers: "CdnaPrimers | None" = None, cdna_opts: "CdnaOpts | None" = None) -> int:
         """pileup: also the pileup summary's planes, complete when the ticket is.  tandem: an int32 [n_zmw] array (tandem_buffer, pinned) that receives
         tandem_len; min_tandem_repeat_length > 0 switches the heuristics off for flagged ZMWs.  hd: a report (HdReport.allocate(n, pinned=True)) that
         receives the heteroduplex finder's verdicts, hd_split=True keeps HETERODUPLEX ZMWs out of the polish stage (ccsx_submit_hd; with fold, adapters, control
@@ -2137,8 +2236,10 @@ class Handle:
         (RepresentReport.allocate(n, pinned=True)) that receives the representative classes; the ZMWs that were not polished get a draft or a subread in `res`
         (ccsx_submit_represent; represent_fallback / represent_kinetics: the request's flags, every ticket its own; not with hd, handoff, barcodes or a
         coverage gate).  segments: a report (SegmentReport.allocate(n, pinned=True)) that receives the segmentation for segment_set under segment_opts
-        (ccsx_submit_segments; not with hd, handoff, barcodes or represent); every ticket carries its own set and options"""
-        one = _exclusive(hd is not None, handoff, barcodes, represent, segments)   # (refused before anything else is looked at)
+        (ccsx_submit_segments; not with hd, handoff, barcodes or represent); every ticket carries its own set and options.  cdna: a report
+        (CdnaReport.allocate(n, pinned=True)) that receives the cDNA analysis for cdna_primers under cdna_opts (ccsx_submit_cdna; not with hd, handoff, barcodes,
+        represent or segments); every ticket carries its own set and options"""
+        one = _exclusive(hd is not None, handoff, barcodes, represent, segments, cdna)   # (refused before anything else is looked at)
         if tandem is not None and (tandem.dtype != np.int32 or len(tandem) < batch.n_zmw or not tandem.flags.c_contiguous):
             raise ValueError("tandem: an int32 array of n_zmw elements (tandem_buffer)")
         if control is not None and control_seq is None:
@@ -2150,7 +2251,8 @@ class Handle:
         cb, cr = self._fused("submit", batch, res, requests, t, handoff=handoff,
                              barcodes=(barcodes, barcode_set, barcode_opts) if barcodes is not None else None,
                              represent=(represent, represent_fallback, represent_kinetics) if represent is not None else None,
-                             segments=(segments, segment_set, segment_opts) if segments is not None else None)
+                             segments=(segments, segment_set, segment_opts) if segments is not None else None,
+                             cdna=(cdna, cdna_primers, cdna_opts) if cdna is not None else None)
         if not hasattr(self, "_inflight"):
             self._inflight = {}
         self._inflight[t.value] = (batch, res, cb, cr, requests, handoff)  # the C structs and arrays must outlive the ticket

@@ -751,6 +751,7 @@ struct RecordBuilder {
     }
     void tagZ(const char *t, const std::string &v) { b.push_back(t[0]); b.push_back(t[1]); b.push_back('Z'); b.insert(b.end(), v.begin(), v.end()); b.push_back(0); }
     void tagi(const char *t, int32_t v) { b.push_back(t[0]); b.push_back(t[1]); b.push_back('i'); u32((uint32_t)v); }
+    void tagA(const char *t, char v) { b.push_back(t[0]); b.push_back(t[1]); b.push_back('A'); b.push_back((uint8_t)v); }
     void tagC(const char *t, uint8_t v) { b.push_back(t[0]); b.push_back(t[1]); b.push_back('C'); b.push_back(v); }
     void tagf(const char *t, float v) { uint32_t u; std::memcpy(&u, &v, 4); b.push_back(t[0]); b.push_back(t[1]); b.push_back('f'); u32(u); }
     void tagBf(const char *t, const float *v, uint32_t n)

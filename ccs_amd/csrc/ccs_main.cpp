@@ -99,6 +99,12 @@ struct Options {
     std::string segment_counts;   // --segment-counts FILE.tsv: reads per (segments, orientation, complete) class
     std::shared_ptr<ccsx_segment_set> segment_set;   // ... the set it names and the options every ticket carries
     ccsx_segment_opts segment_opts{};
+    std::string cdna_primers;     // --cdna-primers FILE.fasta: keep the full-length cDNA reads, clipped of primers and poly(A) tail (DESIGN.md §2 "cDNA rule"): tags ts, pa, pr, pq
+    int cdna_min_polya = -1;      // --cdna-min-polya N: a read with a shorter tail is not full-length; 0: a tail is not required (-1: the default)
+    int cdna_min_length = -1;     // --cdna-min-length N: a read whose insert without the tail is shorter is not full-length (-1: the default)
+    std::string cdna_counts;      // --cdna-counts FILE.tsv: reads per (class, strand)
+    std::shared_ptr<ccsx_cdna_set> cdna_set;         // ... the set it names and the options every ticket carries
+    ccsx_cdna_opts cdna_opts{};
     bool reads_bam = false;       // --reads-bam: one representative read per productive ZMW (the reference's --all, DESIGN.md §2 "Representative rule")
     bool reads_kinetics = false;  // --reads-bam-kinetics: --hifi-kinetics for the polished reads, fi / fp of the pass for the unaltered subreads (--all-kinetics)
     bool reads_fallback = false;  // --reads-bam-subread-fallback: a subread where an unpolished draft would be written (--subread-fallback)
@@ -180,6 +186,7 @@ struct Batch {
     ccsx_adapter_report arep{}; ccsx_adapter_request areq{};   // --adapters (ccsx_adapter_request: the report's arrays are in out_arena)
     ccsx_control_report crep{}; ccsx_control_request creq{};   // --control (ccsx_control_request: the report's arrays are in out_arena)
     ccsx_coverage_report vrep{}; ccsx_coverage_request vreq{}; // --coverage-filters (ccsx_coverage_request: the report's arrays are in out_arena)
+    ccsx_cdna_report drep{}; ccsx_cdna_request dreq{};         // --cdna-primers (ccsx_cdna_request: the report's arrays are in out_arena)
     ccsx_segment_report srep{}; ccsx_segment_request sreq{};   // --segment-adapters (ccsx_segment_request: the report's arrays are in out_arena)
     ccsx_barcode_report brep{}; ccsx_barcode_request breq{};   // --barcodes (ccsx_barcode_request: the report's arrays are in out_arena)
     ccsx_represent_report rrep{}; ccsx_represent_request rreq{};   // --reads-bam (ccsx_represent_request: the report's arrays are in out_arena)
@@ -285,6 +292,15 @@ void usage()
                  "                            a read without a segment is not written; the reports gain a segment block.  Not with --by-strand, --barcodes,\n"
                  "                            --reads-bam, --heteroduplexes, --fit-model [off]\n"
                  "      --segment-min-length N  with --segment-adapters: a piece shorter than N bases is no segment, 1-65535 [50]\n"
+                 "      --cdna-primers F.fasta  keep the full-length cDNA reads (5p . transcript . poly(A) . rc(3p), either strand), found on the GPU: F holds the 2-64\n"
+                 "                            primers of 8-64 bases as the oligos, each record's name ending in _5p or _3p; a HiFi read with a 5' primer at one end\n"
+                 "                            and a 3' primer at the other, no primer inside and a poly(A) tail becomes one record without primers and tail, named\n"
+                 "                            <movie>/<zm>/ccs/<start>_<end>, in the read's orientation, with the tags ts:A (+ sense, - antisense), pa:i (the poly(A)\n"
+                 "                            bases removed), pr:B:C (the 5' and the 3' primer's numbers in F) and pq:i; every other read is counted, not written; the\n"
+                 "                            reports gain a cDNA block.  Not with --by-strand, --barcodes, --segment-adapters, --reads-bam, --heteroduplexes, --fit-model\n"
+                 "      --cdna-min-polya N    with --cdna-primers: a tail shorter than N bases is no tail, 0-255; 0: a tail is not required [20]\n"
+                 "      --cdna-min-length N   with --cdna-primers: a read of fewer than N bases between primers and tail is not written, 1-65535 [50]\n"
+                 "      --cdna-counts F.tsv   with --cdna-primers: one line per class and strand of reads (class, strand, the reads), sorted\n"
                  "      --segment-counts F.tsv  with --segment-adapters: one line per class of reads (segments per read, orientation, complete, the reads), sorted\n"
                  "      --metrics-json F      per-ZMW metrics [<OUT prefix>.zmw_metrics.json.gz]\n"
                  "      --suppress-reports    do not write the default ccs_report.txt / zmw_metrics.json.gz (files named explicitly are still written)\n"
@@ -403,6 +419,25 @@ bool load_segment_adapters(const std::string &path, ccsx_segment_set &set, std::
     return true;
 }
 
+// --cdna-primers: a FASTA of 2 .. 64 records of 8 .. 64 bases, the primers as the oligos.  A record's role is its name's ending, _5p or _3p, up to the first
+// blank (the convention is recalled from the vendor's primer files, which are not in the reference mount, as bam_io.h says of the .pbi layout)
+bool load_cdna_primers(const std::string &path, ccsx_cdna_set &set, std::string &err)
+{
+    FastaSet fa;
+    if (!load_fasta_set(path, {2, CCSX_CDNA_MAX_PRIMERS, CCSX_CDNA_MIN_LEN, CCSX_CDNA_MAX_LEN, "the only record, a cDNA library has a 5' and a 3' primer"}, fa, err)) return false;
+    set.n_primers = fasta_patterns(fa, set);
+    int roles = 0;
+    for (size_t k = 0; k < fa.names.size(); ++k) {
+        const std::string id = fa.names[k].substr(0, fa.names[k].find_first_of(" \t"));
+        const std::string end = id.size() >= 3 ? id.substr(id.size() - 3) : std::string();
+        if (end != "_5p" && end != "_3p") { err = "record " + std::to_string(k + 1) + " (" + fa.names[k] + "): the name ends in neither _5p nor _3p"; return false; }
+        set.role[k] = end == "_3p";
+        roles |= 1 << set.role[k];
+    }
+    if (roles != 3) { err = "the file needs a _5p and a _3p record"; return false; }
+    return true;
+}
+
 // --control: a FASTA of exactly one record of 64 .. 4096 bases
 bool load_control(const std::string &path, std::vector<uint8_t> &codes, std::string &err)
 {
@@ -463,6 +498,10 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--control") o.control = need(a.c_str());
         else if (a == "--barcodes") o.barcodes = need(a.c_str());
         else if (a == "--barcode-counts") o.barcode_counts = need(a.c_str());
+        else if (a == "--cdna-primers") o.cdna_primers = need(a.c_str());
+        else if (a == "--cdna-counts") o.cdna_counts = need(a.c_str());
+        else if (a == "--cdna-min-polya") o.cdna_min_polya = need_int(0, 255, "a number in 0 .. 255");
+        else if (a == "--cdna-min-length") o.cdna_min_length = need_int(1, 65535, "a number in 1 .. 65535");
         else if (a == "--segment-adapters") o.segment_adapters = need(a.c_str());
         else if (a == "--segment-counts") o.segment_counts = need(a.c_str());
         else if (a == "--segment-min-length") o.segment_min_length = need_int(1, 65535, "a number in 1 .. 65535");
@@ -506,6 +545,15 @@ bool parse(int argc, char **argv, Options &o)
         }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if (!o.cdna_primers.empty()) {                           // its own output mode: refused before any input is opened
+        auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --cdna-primers combined with %s is not supported\n", what); std::exit(2); };
+        if (o.by_strand) refuse("--by-strand");
+        if (!o.barcodes.empty()) refuse("--barcodes");
+        if (!o.segment_adapters.empty()) refuse("--segment-adapters");
+        if (o.reads_bam) refuse("--reads-bam");
+        if (o.heteroduplexes) refuse("--heteroduplexes");
+        if (!o.fit_model.empty()) refuse("--fit-model");
     }
     if (!o.segment_adapters.empty()) {                       // its own output mode: refused before any input is opened
         auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --segment-adapters combined with %s is not supported\n", what); std::exit(2); };
@@ -595,6 +643,17 @@ bool parse(int argc, char **argv, Options &o)
         if (!load_segment_adapters(o.segment_adapters, *o.segment_set, err)) { std::fprintf(stderr, "ccs: --segment-adapters %s: %s\n", o.segment_adapters.c_str(), err.c_str()); std::exit(2); }
         ccsx_segment_opts_default(&o.segment_opts);
         if (o.segment_min_length >= 0) o.segment_opts.min_len = o.segment_min_length;
+    }
+    if (o.cdna_primers.empty() && (o.cdna_min_polya >= 0 || o.cdna_min_length >= 0 || !o.cdna_counts.empty())) {
+        std::fprintf(stderr, "ccs: --cdna-min-polya, --cdna-min-length and --cdna-counts need --cdna-primers\n"); std::exit(2);
+    }
+    if (!o.cdna_primers.empty()) {
+        std::string err;
+        o.cdna_set = std::make_shared<ccsx_cdna_set>();
+        if (!load_cdna_primers(o.cdna_primers, *o.cdna_set, err)) { std::fprintf(stderr, "ccs: --cdna-primers %s: %s\n", o.cdna_primers.c_str(), err.c_str()); std::exit(2); }
+        ccsx_cdna_opts_default(&o.cdna_opts);
+        if (o.cdna_min_polya >= 0) o.cdna_opts.min_polya = o.cdna_min_polya;
+        if (o.cdna_min_length >= 0) o.cdna_opts.min_len = o.cdna_min_length;
     }
     if (!o.control.empty()) {
         std::string err;
@@ -858,6 +917,8 @@ struct Report {
     int64_t coverage = 0;         // ZMWs the coverage screen's gate took (--coverage-filters)
     int64_t bc_tested = 0, bc_call[4] = {0, 0, 0, 0};           // --barcodes: HiFi reads tested, and by call: none, head only, tail only, both ends
     int64_t sg_tested = 0, sg_complete = 0, sg_with = 0, sg_without = 0, sg_overflow = 0, sg_written = 0, sg_leftover = 0;   // --segment-adapters, over the HiFi reads
+    int64_t cd_tested = 0, cd_cls[7] = {0, 0, 0, 0, 0, 0, 0};     // --cdna-primers, over the HiFi reads: per class of the rule
+    std::map<std::array<int, 2>, int64_t> cd_classes;             // ... reads per (class, strand)
     std::map<std::array<int, 3>, int64_t> sg_classes;             // ... reads per (segments per read, orientation, complete)
     std::map<std::pair<int, int>, int64_t> bc_pairs;              // ... reads per called pair (head, tail)
     int64_t hd_zmws = 0;          // --heteroduplexes: ZMWs the split took (split: written as single-strand reads; drop: the "Heteroduplex insertions" row)
@@ -1039,6 +1100,14 @@ void write_report(const Options &o, const Report &r)
             std::fprintf(f, "%-30s: %" PRId64 "\n", "Segments written", r.sg_written);
             std::fprintf(f, "%-30s: %" PRId64 "\n\n", "Leftover bases", r.sg_leftover);
         }
+        if (!o.cdna_primers.empty()) {                           // over the HiFi reads the run would write without the option (DESIGN.md §2 "cDNA rule")
+            static const char *const rows[7] = {"No primer", "Primer at one end only", "Both primers of one role", "Insert too short", "Concatemers", "No poly(A) tail",
+                                                "Full-length reads written"};
+            std::fprintf(f, "cDNA reads\n");
+            std::fprintf(f, "%-30s: %" PRId64 "\n", "HiFi reads tested", r.cd_tested);
+            for (int k = 6; k >= 0; --k) std::fprintf(f, "%-30s: %" PRId64 " (%.2f%%)\n", rows[k], r.cd_cls[k], pct(r.cd_cls[k], r.cd_tested));
+            std::fprintf(f, "\n");
+        }
         if (o.reads_bam) {                                       // DESIGN.md §2 "Representative rule": what the records of OUT are
             std::fprintf(f, "Representative reads\n");
             std::fprintf(f, "%-30s: %" PRId64 "\n", "Polished reads", r.rep_cls[CCSX_REPRESENT_POLISHED]);
@@ -1093,6 +1162,10 @@ void write_report_json(const Options &o, const Report &r)
         std::fprintf(f, "  \"segmentation\": {\"tested\": %" PRId64 ", \"complete_arrays\": %" PRId64 ", \"with_segments\": %" PRId64 ", \"without_segments\": %" PRId64
                         ", \"overflow\": %" PRId64 ", \"segments_written\": %" PRId64 ", \"leftover_bases\": %" PRId64 "},\n",
                      r.sg_tested, r.sg_complete, r.sg_with, r.sg_without, r.sg_overflow, r.sg_written, r.sg_leftover);
+    if (!o.cdna_primers.empty())
+        std::fprintf(f, "  \"cdna_reads\": {\"tested\": %" PRId64 ", \"full_length\": %" PRId64 ", \"no_tail\": %" PRId64 ", \"concatemer\": %" PRId64 ", \"short\": %" PRId64
+                        ", \"same_role\": %" PRId64 ", \"one_end\": %" PRId64 ", \"no_primer\": %" PRId64 "},\n",
+                     r.cd_tested, r.cd_cls[6], r.cd_cls[5], r.cd_cls[4], r.cd_cls[3], r.cd_cls[2], r.cd_cls[1], r.cd_cls[0]);
     if (o.reads_bam)
         std::fprintf(f, "  \"representative_reads\": {\"polished\": %" PRId64 ", \"draft\": %" PRId64 ", \"subread\": %" PRId64 "},\n",
                      r.rep_cls[CCSX_REPRESENT_POLISHED], r.rep_cls[CCSX_REPRESENT_DRAFT], r.rep_cls[CCSX_REPRESENT_SUBREAD]);
@@ -1138,6 +1211,17 @@ void write_segment_counts(const Options &o, const Report &r)
     FILE *f = std::fopen(o.segment_counts.c_str(), "w");
     if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", o.segment_counts.c_str()); return; }
     for (const auto &kv : r.sg_classes) std::fprintf(f, "%d\t%d\t%d\t%" PRId64 "\n", kv.first[0], kv.first[1], kv.first[2], kv.second);
+    std::fclose(f);
+}
+
+// --cdna-counts: one line per (class, strand) of HiFi reads, in increasing order: the class's number and name, the strand (-1 unknown, 0 sense, 1 antisense) and
+// the reads
+void write_cdna_counts(const Options &o, const Report &r)
+{
+    static const char *const names[7] = {"NO_PRIMER", "ONE_END", "SAME_ROLE", "SHORT", "CONCATEMER", "NO_TAIL", "FULL_LENGTH"};
+    FILE *f = std::fopen(o.cdna_counts.c_str(), "w");
+    if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", o.cdna_counts.c_str()); return; }
+    for (const auto &kv : r.cd_classes) std::fprintf(f, "%d\t%s\t%d\t%" PRId64 "\n", kv.first[0], names[kv.first[0]], kv.first[1], kv.second);
     std::fclose(f);
 }
 
@@ -1639,6 +1723,7 @@ int main(int argc, char **argv)
         const bool coverage = opt.coverage_filters;
         const bool barcodes = !opt.barcodes.empty();
         const bool segments = !opt.segment_adapters.empty();
+        const bool cdna = !opt.cdna_primers.empty();
         static_assert(sizeof(ccsx_segment_piece) * CCSX_SEGMENT_MAX_PIECES == 192 * 4, "the segment list is carved as 192 words per ZMW");
         // The views of a staged batch's results and reports, carved from a page-locked arena of its device's pool, and the requests that point to them: every
         // ticket of the run is given the same (finder: plus the heteroduplex request, which the single-strand tickets of --heteroduplexes split do not carry)
@@ -1650,7 +1735,7 @@ int main(int argc, char **argv)
             b->cap = cap;
             b->out_arena = out_pool.get();
             const size_t n4 = ((size_t)n * 4 + 63) & ~(size_t)63, c1 = ((size_t)cap + 63) & ~(size_t)63;
-            uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (segments ? 8 + 192 : 0) + (opt.reads_bam ? 2 : 0) + (finder ? 103 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
+            uint8_t *o = b->out_arena->reserve((9 + (opt.min_tandem > 0 ? 1 : 0) + (fail_reads ? 4 : 0) + (screen ? 9 + 3 * CCSX_ADAPTER_MAX_HITS : 0) + (control ? 8 : 0) + (coverage ? 10 : 0) + (barcodes ? 11 : 0) + (segments ? 8 + 192 : 0) + (cdna ? 16 : 0) + (opt.reads_bam ? 2 : 0) + (finder ? 103 : 0)) * n4 + ((kin ? 6 : 2) + (opt.pileup ? 3 : 0)) * c1);
             auto take = [&](size_t bytes) { uint8_t *r = o; o += bytes; return r; };
             auto planes = [&](int k) { std::vector<int32_t *> v(k); for (auto &p : v) p = (int32_t *)take(n4); return v; };   // a report's k arrays
             b->status = (int32_t *)take(n4); b->seq_len = (int32_t *)take(n4); b->np = (int32_t *)take(n4); b->iters = (int32_t *)take(n4);
@@ -1706,6 +1791,13 @@ int main(int argc, char **argv)
                 ccsx_segment_piece *list = (ccsx_segment_piece *)take(192 * n4);
                 b->srep = ccsx_segment_report{n, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], list};
                 b->sreq = ccsx_segment_request{&opt.segment_opts, opt.segment_set.get(), &b->srep, {0, 0}};
+            }
+            if (cdna) {                              // the eight planes: n each; idx, dist, second, clip: [n][2]
+                const auto d = planes(8);
+                int32_t *two[4];
+                for (auto &q : two) q = (int32_t *)take(2 * n4);
+                b->drep = ccsx_cdna_report{n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], two[0], two[1], two[2], two[3]};
+                b->dreq = ccsx_cdna_request{&opt.cdna_opts, opt.cdna_set.get(), &b->drep, {0, 0}};
             }
             if (opt.reads_bam) {
                 const auto r2 = planes(2);
@@ -1921,7 +2013,8 @@ int main(int argc, char **argv)
                 if (opt.heteroduplexes ? ccsx_submit_hd_requests(h, &b->cb, &b->cr, &b->reqs, &b->hreq, &t)
                     : opt.reads_bam ? ccsx_submit_represent(h, &b->cb, &b->cr, &b->reqs, &b->rreq, &t)
                                   : barcodes ? ccsx_submit_barcodes(h, &b->cb, &b->cr, &b->reqs, &b->breq, &t)
-                                  : segments ? ccsx_submit_segments(h, &b->cb, &b->cr, &b->reqs, &b->sreq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
+                                  : segments ? ccsx_submit_segments(h, &b->cb, &b->cr, &b->reqs, &b->sreq, &t)
+                                  : cdna ? ccsx_submit_cdna(h, &b->cb, &b->cr, &b->reqs, &b->dreq, &t) : ccsx_submit_requests(h, &b->cb, &b->cr, &b->reqs, &t)) {
                     // a failed batch must never reach the writer looking like SUCCESS records: it carries no results,
                     // the run is marked failed and ends with exit code 1 and no output file
                     fail(std::string("consensus engine: ") + ccsx_last_error());
@@ -1971,7 +2064,7 @@ int main(int argc, char **argv)
                                               40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40,40};
             static const char *const kStrandRG[2] = {"ccsamd02", "ccsamd03"};   // --heteroduplexes split: the read groups of the /fwd and the /rev reads
             // a CCS record of ZMW slot s as the main output writes it (tags the run asks for); the caller adds its own and finishes it.  to >= 0: the record of
-            // the slice [from, to) of SEQ (--segment-adapters), named after it: SEQ, QUAL and every per-base tag are the slice, the scalar tags the read's
+            // the slice [from, to) of SEQ (--segment-adapters, --cdna-primers), named after it: SEQ, QUAL and every per-base tag are the slice, the scalar tags the read's
             auto build = [&](const ZmwIn &z, Batch &bt, int s, int32_t from = 0, int32_t to = -1) {
                 const int64_t o = bt.seq_off[s] + from; const int32_t len = (to >= 0 ? to : bt.seq_len[s]) - from;
                 const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : "")) +
@@ -2198,6 +2291,30 @@ int main(int argc, char **argv)
                         }
                         return;
                     }
+                    if (cdna) {                                     // --cdna-primers: the full-length read's slice in place of the read (DESIGN.md §2 "cDNA rule")
+                        const ccsx_cdna_report &d = bt.drep;
+                        rep.cd_tested += d.tested[s] ? 1 : 0; ++rep.cd_cls[d.cls[s]]; ++rep.cd_classes[{d.cls[s], d.strand[s]}];
+                        if (d.cls[s] != CCSX_CDNA_FULL_LENGTH) return;
+                        const int32_t from = d.start[s], to = d.end[s], plen = to - from;
+                        if (bt.rq[s] >= 0.99f) for (int32_t q = from; q < to; ++q) rep.bases_q30 += bt.qual[o + q] >= 30 ? 1 : 0;
+                        if (fastq) put_fastq(movie + "/" + std::to_string(z.zm) + "/ccs/" + std::to_string(from) + "_" + std::to_string(to), bt, o + from, plen);
+                        else {
+                            build(z, bt, s, from, to);
+                            // (ts, pa, pr, pq: the tag names are this build's own.  pr: the 5' and the 3' primer's numbers in the FASTA; pq: the barcode rule's bq
+                            // over the two ends, the smaller of floor(100 * (m - dist) / m))
+                            const int st = d.strand[s];
+                            const uint8_t pr[2] = {(uint8_t)d.idx[2 * s + st], (uint8_t)d.idx[2 * s + 1 - st]};
+                            int pq = 100;
+                            for (int e = 0; e < 2; ++e) { const int m = opt.cdna_set->len[d.idx[2 * s + e]]; pq = std::min(pq, 100 * (m - d.dist[2 * s + e]) / m); }
+                            rb.tagA("ts", st ? '-' : '+'); rb.tagi("pa", d.polya_len[s]); rb.tagBC("pr", pr, 2); rb.tagi("pq", pq);
+                            marks.push_back(outp->mark());
+                            pbi.rg_id.push_back(0); pbi.q_start.push_back(from); pbi.q_end.push_back(to); pbi.hole.push_back(z.zm);
+                            pbi.read_qual.push_back(bt.rq[s]); pbi.ctxt.push_back(0);
+                            rb.finish(*outp);
+                        }
+                        rep.lens.push_back(plen); rep.rqs.push_back(bt.rq[s]); rep.nps.push_back(bt.np[s]); rep.ss.push_back(ss); rep.holes.push_back(z.zm);
+                        return;
+                    }
                     if (bt.rq[s] >= 0.99f) for (int32_t q = 0; q < len; ++q) rep.bases_q30 += bt.qual[o + q] >= 30 ? 1 : 0;
                     const std::string qname = movie + "/" + std::to_string(z.zm) + "/ccs" + (z.strand_tag == 1 ? "/fwd" : (z.strand_tag == 2 ? "/rev" : ""));
                     const bool bc_both = barcodes && bt.brep.tested[s] && bt.brep.call[s] == 3;   // --barcodes: counted over the HiFi reads, tagged at both ends called
@@ -2278,6 +2395,7 @@ int main(int argc, char **argv)
         if (!opt.report_json.empty()) write_report_json(opt, rep);            // named files are written even under --suppress-reports (docs/faq/sqiie.md:36-46
         if (!opt.barcode_counts.empty()) write_barcode_counts(opt, rep);
         if (!opt.segment_counts.empty()) write_segment_counts(opt, rep);
+        if (!opt.cdna_counts.empty()) write_cdna_counts(opt, rep);
         if (!opt.hifi_summary.empty()) write_hifi_summary(opt, rep);          //  combines --suppress-reports with explicit report names)
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         if (opt.log_level >= 2)

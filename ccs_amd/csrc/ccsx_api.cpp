@@ -131,7 +131,7 @@ struct Slot {
     DevBuf d_poa_log;                             // POA log only (ccsx_poa_log): [n][2][max_reads] records of CCSX_POA_LOG_WORDS int32
     DevBuf d_ho, d_ho_out;                        // polisher hand-off only (ccsx_handoff_request): counts, tile ranks / slots, qual sums, core offsets; the output arrays
     DevBuf d_orient;                              // pass orientation only (a batch with a CCSX_PASS_STRAND_UNKNOWN pass): [n] anchors, [2][R] votes, [2][R] strand / call
-    DevBuf d_pattern;                             // barcode calls or segmentation only (a ticket carries one of them): the packed set, then the report
+    DevBuf d_pattern;                             // barcode calls, segmentation or cDNA reads only (a ticket carries one of them): the packed set, then the report
     DevBuf d_rp;                                  // representative reads only (ccsx_represent_request): the [2][n] report
     DevBuf d_rf_tiles, d_rf_base, d_rf_rep;       // polisher hand-back only (ccsx_submit_refine): the tile list and its classes; base lengths, backbones, seq, qual; the report
     RefineParams RP{};                            // ... its kernels' parameters as enqueued (the report's download reads them)
@@ -139,7 +139,7 @@ struct Slot {
     PinVec<int32_t> read_zmw, vcap, dcap, zperm, rperm, wb_off, read_off, quads, qperm;
     PinVec<int64_t> seq_off, ent_off, base_off;
     PinVec<uint32_t> ctl_index;                   // control screen only: the index as uploaded (a ticket's control is its own: three may be in flight)
-    PinVec<unsigned long long> pattern_set;       // barcode calls or segmentation only: the packed set as uploaded (a ticket's set is its own, as its control is)
+    PinVec<unsigned long long> pattern_set;       // barcode calls, segmentation or cDNA reads only: the packed set as uploaded (a ticket's set is its own, as its control is)
     PinVec<int32_t> anchor;                       // pass orientation only: the anchor pass of every ZMW as uploaded
     bool orient_pending = false, orient_ran = false;   // the staged batch carries the bit and k_orient has yet to run on it / has run (its report is on the device)
     KParams P;
@@ -191,7 +191,7 @@ struct ccsx_handle_s {
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
-    DevBuf d_reads;                   // ccsx_barcode_reads / ccsx_segment_reads only: the call's set, report and reads (no slot is touched; the call ends synchronised)
+    DevBuf d_reads;                   // ccsx_barcode_reads / ccsx_segment_reads / ccsx_cdna_reads only: the call's set, report and reads (no slot is touched; the call ends synchronised)
     DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
     ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
     Slot slot[CCSX_SLOTS];
@@ -268,9 +268,10 @@ static void destroy_handle(ccsx_handle h)
 
 static int refuse(const char *fn, const char *what) { ccsx_set_error(std::string(fn) + ": " + what); return -1; }
 
-// ---- The analyses on final reads: barcode calls and segmentation (DESIGN.md §2 "Barcode calls", "Segment rule").  Each is described once, by a struct of its
-// types, its nouns, its check / pack / launch and the arrays of its report; everything between an entry point and the kernel is one template over that struct.
-// A third analysis supplies a core header (rule, packed set, report layout), a kernel with its launch, a check, such a struct and its member of KParams.
+// ---- The analyses on final reads: barcode calls, segmentation and full-length cDNA reads (DESIGN.md §2 "Barcode calls", "Segment rule", "cDNA rule").  Each is
+// described once, by a struct of its types, its nouns, its check / pack / launch and the arrays of its report; everything between an entry point and the kernel is
+// one template over that struct.  The third, struct Cdna, supplied a core header (rule, packed set, report layout), a kernel with its launch, a check, such a
+// struct and its member of KParams; no template changed for it.
 struct ReadsCopy { void *host; const void *dev; size_t bytes_per_read; };
 
 struct Barcodes {
@@ -308,6 +309,26 @@ struct Segments {
         return {{r.tested, d.tested, 4}, {r.overflow, d.overflow, 4}, {r.n_hits, d.n_hits, 4}, {r.n_cuts, d.n_cuts, 4}, {r.n_segments, d.n_segments, 4},
                 {r.complete, d.complete, 4}, {r.orient, d.orient, 4}, {r.leftover_bases, d.leftover, 4},
                 {r.pieces, d.pieces, CCSX_SEGMENT_MAX_PIECES * sizeof(ccsx_segment_piece)}};
+    }
+};
+
+struct Cdna {
+    using Request = ccsx_cdna_request; using Set = ccsx_cdna_set; using Opts = ccsx_cdna_opts; using Report = ccsx_cdna_report; using Params = CdnaParams;
+    static constexpr const char *noun = "cdna", *title = "cDNA reads";
+    static int count(const Set &s) { return s.n_primers; }
+    static size_t set_words(int np) { return ccsx_cd_set_words(np); }
+    static size_t rep_bytes(size_t n) { return ccsx_cd_rep_bytes(n); }
+    static int check(const Set *s, const Opts *o, const Report *r, int64_t n, const char *fn, Opts *out) { return ccsx_cdna_check(s, o, r, n, fn, out); }
+    static void pack(const Set *s, unsigned long long *packed) { ccsx_cd_pack(s, packed); }
+    static Params params(int np, int n, const Opts &o, const void *base) { Params D{}; D.n = n; D.n_primers = np; D.opts = o; ccsx_cd_bind(D, base); return D; }
+    static const char *launch(const Params &D, hipStream_t st) { return ccsx_cdna_launch(D, st); }
+    static Params &of(KParams &P) { return P.cd; }
+    static std::vector<ReadsCopy> copies(const Report &r, const Params &D)
+    {
+        const CdnaOut d = ccsx_cd_out(D.rep, (size_t)D.n);
+        return {{r.tested, d.tested, 4}, {r.cls, d.cls, 4}, {r.strand, d.strand, 4}, {r.start, d.start, 4}, {r.end, d.end, 4}, {r.polya_len, d.polya_len, 4},
+                {r.n_internal, d.n_internal, 4}, {r.first_internal, d.first_internal, 4}, {r.idx, d.idx, 8}, {r.dist, d.dist, 8}, {r.second, d.second, 8},
+                {r.clip, d.clip, 8}};
     }
 };
 
@@ -517,6 +538,7 @@ struct Wants {
     const ccsx_handoff_request *handoff = nullptr; ccsx_handoff_opts handoff_opts{}; ccsx_handoff_out handoff_out{};   // (the out struct is copied: it is read during the call only)
     ReadsWant<Barcodes> barcodes;
     ReadsWant<Segments> segments;
+    ReadsWant<Cdna> cdna;
     bool represent = false; ccsx_represent_request represent_req{};   // (the request is copied: it is read during the call only)
     bool handoff_written_only = false;          // the synchronous form: counts is known when the copies are enqueued, only the written slots are copied
 };
@@ -1350,6 +1372,7 @@ struct Exclusive {
     const ccsx_barcode_request *barcodes = nullptr;
     const ccsx_segment_request *segments = nullptr;
     const ccsx_hd_request *hd = nullptr;
+    const ccsx_cdna_request *cdna = nullptr;
 };
 
 // The Wants of one call of the exported function `fn` (NULL extras or request: none of it).  Enqueues nothing and needs no handle: the requests are checked
@@ -1359,6 +1382,11 @@ static int build_wants(const ccsx_extras *ex, const Exclusive &x, const ccsx_fol
                        const ccsx_control_request *control, const ccsx_batch *b, const char *fn, Wants *W, const ccsx_coverage_request *coverage = nullptr)
 {
     *W = Wants{};
+    if (x.cdna && x.handoff) return refuse(fn, "the cdna request and the hand-off are not combined");
+    if (x.cdna && x.hd) return refuse(fn, "the cdna and the heteroduplex requests are not combined");
+    if (x.cdna && x.barcodes) return refuse(fn, "the cdna and the barcode requests are not combined");
+    if (x.cdna && x.segments) return refuse(fn, "the cdna and the segment requests are not combined");
+    if (x.cdna && b && reads_request_check(x.cdna, b, &W->cdna, fn)) return -1;
     if (x.segments && x.handoff) return refuse(fn, "the segment request and the hand-off are not combined");
     if (x.segments && x.hd) return refuse(fn, "the segment and the heteroduplex requests are not combined");
     if (x.segments && x.barcodes) return refuse(fn, "the segment and the barcode requests are not combined");
@@ -1373,7 +1401,7 @@ static int build_wants(const ccsx_extras *ex, const Exclusive &x, const ccsx_fol
     if (adapters && b && adapter_request_check(adapters, b, &W->adapter_set, &W->adapter_opts, fn)) return -1;
     if (control && b && control_request_check(control, b, &W->control_seq, &W->control_opts, fn)) return -1;
     if (extras_want(ex, &W->tandem)) return -1;
-    W->hd = x.hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = x.handoff; W->barcodes.req = x.barcodes; W->segments.req = x.segments;
+    W->hd = x.hd; W->fold = fold; W->adapters = adapters; W->control = control; W->coverage = coverage; W->handoff = x.handoff; W->barcodes.req = x.barcodes; W->segments.req = x.segments; W->cdna.req = x.cdna;
     if (ex) { W->pile = ex->pile; W->tandem_len = ex->tandem_len; W->min_tandem = W->tandem ? ex->min_tandem_repeat_length : 0; }
     return 0;
 }
@@ -1391,6 +1419,7 @@ static int attach(ccsx_handle h, Slot &S, const Wants &W, hipStream_t st)
     if (W.handoff && (rc = handoff_attach(S, W.handoff_opts, W.handoff_out.max_tiles))) return rc;
     if (W.barcodes.req && (rc = reads_attach(S, W.barcodes, st))) return rc;
     if (W.segments.req && (rc = reads_attach(S, W.segments, st))) return rc;
+    if (W.cdna.req && (rc = reads_attach(S, W.cdna, st))) return rc;
     if (W.represent && (rc = represent_attach(S, W.represent_req))) return rc;
     if (W.control && (rc = control_attach(h, S, W.control_seq, W.control_opts, st))) return rc;
     if (W.hd && ((rc = hd_table(h)) || (rc = hd_attach(h, S, W.hd_opts, W.hd->split, st)))) return rc;
@@ -1427,6 +1456,7 @@ static int enqueue_wants_download(const Slot &S, const Wants &W, hipStream_t s)
     if (W.handoff && (rc = enqueue_handoff_download(S, W.handoff_out, W.handoff_written_only, s))) return rc;
     if (W.barcodes.req && (rc = reads_download<Barcodes>(S.P.bc, W.barcodes.req->report, s))) return rc;
     if (W.segments.req && (rc = reads_download<Segments>(S.P.sg, W.segments.req->report, s))) return rc;
+    if (W.cdna.req && (rc = reads_download<Cdna>(S.P.cd, W.cdna.req->report, s))) return rc;
     if (W.represent && n) {
         const ccsx_represent_report *r = W.represent_req.report;
         if ((rc = download_planes({r->cls, r->pass}, S.P.rep.rep, n, s))) return rc;
@@ -1655,10 +1685,10 @@ static int hd_requests_wants(const ccsx_requests *rq, const ccsx_hd_request *hd,
     if (requests_wants(rq, b, fn, W, {nullptr, nullptr, nullptr, hd}) || (!hd && refuse(fn, "null request or report"))) return -1;
     return 0;
 }
-// the Wants of a call with a barcode or a segment request (x: it alone) beside the members of rq: neither it nor the batch may be NULL
+// the Wants of a call with a barcode, a segment or a cdna request (x: it alone) beside the members of rq: neither it nor the batch may be NULL
 static int reads_wants(const ccsx_requests *rq, const ccsx_batch *b, const Exclusive &x, const char *noun, const char *fn, Wants *W)
 {
-    if (!x.barcodes && !x.segments) return refuse(fn, (std::string("null ") + noun + " request").c_str());
+    if (!x.barcodes && !x.segments && !x.cdna) return refuse(fn, (std::string("null ") + noun + " request").c_str());
     if (!b) return refuse(fn, "null argument");
     return requests_wants(rq, b, fn, W, x);
 }
@@ -1697,6 +1727,12 @@ int ccsx_submit_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, 
 {
     Wants W;
     if (reads_wants(rq, b, {nullptr, nullptr, sg}, Segments::noun, __func__, &W)) return -1;
+    return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
+}
+int ccsx_submit_cdna(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_cdna_request *cd, ccsx_ticket *ticket)
+{
+    Wants W;
+    if (reads_wants(rq, b, {nullptr, nullptr, nullptr, nullptr, cd}, Cdna::noun, __func__, &W)) return -1;
     return submit_impl(h, b, res, ticket, CCSX_RUN_FUSED, nullptr, nullptr, 0, W, __func__);
 }
 // the Wants of a call with a representative request: the request checked against the batch and the handle's options and copied, then the members of rq
@@ -2010,6 +2046,13 @@ int ccsx_consensus_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *re
     return consensus_sync(h, b, res, W, __func__);
 }
 
+int ccsx_consensus_cdna(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_cdna_request *cd)
+{
+    Wants W;
+    if (reads_wants(rq, b, {nullptr, nullptr, nullptr, nullptr, cd}, Cdna::noun, __func__, &W)) return -1;
+    return consensus_sync(h, b, res, W, __func__);
+}
+
 int ccsx_consensus_represent(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_represent_request *rp)
 {
     Wants W;
@@ -2027,6 +2070,12 @@ int ccsx_segment_reads(ccsx_handle h, const ccsx_segment_set *set, const ccsx_se
                        int32_t n, ccsx_segment_report *report)
 {
     return reads_sync<Segments>(h, set, opts, seq, seq_off, seq_len, n, report, __func__);
+}
+
+int ccsx_cdna_reads(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
+                    int32_t n, ccsx_cdna_report *report)
+{
+    return reads_sync<Cdna>(h, set, opts, seq, seq_off, seq_len, n, report, __func__);
 }
 
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)

@@ -42,12 +42,14 @@ template <typename F> static inline void ccsx_for_each_zmw_caps(const ccsx_batch
     }
 }
 
-// ---- the analyses on final reads: barcode calls (ccsx_barcode_api.cpp; DESIGN.md §2 "Barcode calls") and segmentation (ccsx_segment_api.cpp; "Segment rule").
-// What every entry point of one shares; a refusal sets the error under the exported function's name `fn` and returns -1.  The packed set, the binding of its
-// buffer and the report's layout are in barcode_core.h / segment_core.h; the path both take through a handle is ccsx_api.cpp's (struct Barcodes, struct Segments).
+// ---- the analyses on final reads: barcode calls (ccsx_barcode_api.cpp; DESIGN.md §2 "Barcode calls"), segmentation (ccsx_segment_api.cpp; "Segment rule") and
+// full-length cDNA reads (ccsx_cdna_api.cpp; "cDNA rule").  What every entry point of one shares; a refusal sets the error under the exported function's name
+// `fn` and returns -1.  The packed set, the binding of its buffer and the report's layout are in barcode_core.h / segment_core.h / cdna_core.h; the path all take
+// through a handle is ccsx_api.cpp's (struct Barcodes, struct Segments, struct Cdna).
 // the set, the options (NULL: the defaults; the checked copy goes to *o) and a report for n reads
 int ccsx_barcode_check(const ccsx_barcode_set *set, const ccsx_barcode_opts *opts, const ccsx_barcode_report *report, int64_t n, const char *fn, ccsx_barcode_opts *o);
 int ccsx_segment_check(const ccsx_segment_set *set, const ccsx_segment_opts *opts, const ccsx_segment_report *report, int64_t n, const char *fn, ccsx_segment_opts *o);
+int ccsx_cdna_check(const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const ccsx_cdna_report *report, int64_t n, const char *fn, ccsx_cdna_opts *o);
 // caller-supplied reads, of either analysis: *bytes = the bytes of seq the reads cover (the largest seq_off[z] + seq_len[z] over the reads with seq_len[z] > 0)
 int ccsx_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes);
 

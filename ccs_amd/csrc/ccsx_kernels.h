@@ -7,6 +7,7 @@
 #include "ccsx.h"
 #include "barcode_core.h"
 #include "segment_core.h"
+#include "cdna_core.h"
 #include "represent_core.h"
 
 // bytes of POA scratch per vertex (ccsx_kernels.hip poa_slot, all by topological position): the 32-row score column of far-read columns 128, five 16-byte
@@ -182,6 +183,9 @@ struct KParams {
     // ---- segmentation (ccsx_consensus_segments / ccsx_submit_segments; sg.rep NULL otherwise): DESIGN.md §2 "Segment rule".  k_segment's own parameters
     // (ccsx_segment.hip): it reads out_seq / out_len after k_stitch
     SegmentParams sg;
+    // ---- full-length cDNA reads (ccsx_consensus_cdna / ccsx_submit_cdna; cd.rep NULL otherwise): DESIGN.md §2 "cDNA rule".  k_cdna's own parameters
+    // (ccsx_cdna.hip): it reads out_seq / out_len after k_stitch
+    CdnaParams cd;
     // ---- representative reads (ccsx_consensus_represent / ccsx_submit_represent; rep.rep NULL otherwise): DESIGN.md §2 "Representative rule".  k_represent's own
     // parameters (ccsx_represent.hip): it reads the final draft and out_status and writes the result planes after k_stitch
     RepresentParams rep;
@@ -286,6 +290,7 @@ struct ccsx_launch_queues {
 const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int mode);   // NULL, or the name of the launch that failed
 const char *ccsx_barcode_launch(const BarcodeParams &B, hipStream_t st);                 // ccsx_barcode.hip: k_barcode, one workgroup per read; NULL, or what failed
 const char *ccsx_segment_launch(const SegmentParams &G, hipStream_t st);                 // ccsx_segment.hip: k_segment, one workgroup per read; NULL, or what failed
+const char *ccsx_cdna_launch(const CdnaParams &D, hipStream_t st);                       // ccsx_cdna.hip: k_cdna, one workgroup per read; NULL, or what failed
 const char *ccsx_represent_launch(const RepresentParams &R, hipStream_t st);             // ccsx_represent.hip: k_represent, one workgroup per ZMW; NULL, or what failed
 const char *ccsx_train_launch(const KParams &P, hipStream_t st, long long max_blocks);   // ccsx_train.hip: the count buffers zeroed + k_train; NULL, or what failed
 int ccsx_kernel_is_experiment();         // built with -DCCSX_EXPERIMENT (timing studies: wrong results)

@@ -5261,6 +5261,10 @@ struct Schedule {
             failed = ccsx_segment_launch(P.sg, sp);
             trace_sync(sp, "k_segment");
         }
+        if (P.cd.rep && !failed) {                         // full-length cDNA reads of the final consensus (a batch with a ccsx_cdna_request only)
+            failed = ccsx_cdna_launch(P.cd, sp);
+            trace_sync(sp, "k_cdna");
+        }
         if (P.rep.rep && !failed) {                        // representative reads into the result planes (a batch with a ccsx_represent_request only)
             failed = ccsx_represent_launch(P.rep, sp);
             trace_sync(sp, "k_represent");

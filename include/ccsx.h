@@ -937,6 +937,85 @@ int         ccsx_segment_reads(ccsx_handle h, const ccsx_segment_set *set, const
 int         ccsx_consensus_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg);
 int         ccsx_submit_segments(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_segment_request *sg, ccsx_ticket *ticket);
 
+/* ---- full-length cDNA reads (the rule: DESIGN.md §2 "cDNA rule", its own version ccsx_cdna_rule_version; this build's own, as the barcode and the segment rule
+ * are: the reference leaves primer removal, the poly(A) tail and concatemers to separate CPU tools; no result of the consensus changes).  A cDNA molecule reads
+ * 5p . transcript . poly(A) . rc(3p) on the sense strand, or the reverse complement of the whole.  The primers of a caller-supplied set are given as the oligos,
+ * each with a role: 0 = 5', 1 = 3'.  k_cdna, per read c[0, L):
+ *   ends      the barcode rule over the primers, whatever their role (window, max_dist_pct, min_margin as in ccsx_barcode_opts): idx, dist, second, clip per end.
+ *   strand    both ends called with primers of different roles: the role of the head's primer (0: sense; 1: antisense, the transcript is the reverse complement
+ *             of the read).  Otherwise strand -1, class NO_PRIMER, ONE_END or SAME_ROLE, and the rule ends: the later planes are 0, first_internal -1.
+ *   insert    [clip[0], L - clip[1]) in the read's coordinates, ins_len bases; ins_len < 1: class SHORT and the rule ends in the same way.
+ *   poly(A)   over the first K = min(polya_max, ins_len) insert bases counted from the 3' primer, x_k = 1 iff base k is A on the transcript strand:
+ *             s_0 = 0, s_k = s_(k-1) + (x_k ? 1 : -polya_mismatch), M_k = max of s_0 .. s_k; k* = the smallest k with M_k - s_k > polya_xdrop (K + 1 without one);
+ *             polya_len = the smallest k in [0, k*) that attains the maximum of s over [0, k*).
+ *   internal  every primer and its reverse complement over the whole read, hits and starts as the segment rule defines them at floor(m * max_dist_pct / 100)
+ *             edits; a hit is internal iff clip[0] <= start and end <= L - clip[1].  n_internal counts them (not capped), first_internal is their smallest start.
+ *   class     trimmed = ins_len - polya_len: SHORT if trimmed < min_len, else CONCATEMER if n_internal > 0, else NO_TAIL if min_polya > 0 and polya_len <
+ *             min_polya, else FULL_LENGTH.  Classes CONCATEMER .. FULL_LENGTH report the slice without primers and tail, [start, end) in the read's
+ *             coordinates: strand 0 [clip[0], L - clip[1] - polya_len), strand 1 [clip[0] + polya_len, L - clip[1]); every other class 0, 0.
+ * Integers only.  Detection only: nothing is clipped, and every result byte equals the same call without the request.
+ *   ccsx_cdna_reads_host  the rule on the calling thread, without a device: the reference of the tests.
+ *   ccsx_cdna_reads       k_cdna on caller-supplied reads (HiFi reads from anywhere).  Synchronous; buffers of the handle's own on the polish stream, no slot is
+ *                         staged or recycled (as ccsx_barcode_reads).
+ *   ccsx_consensus_cdna   synchronous (slot 0), as ccsx_consensus_requests: k_cdna runs on the polish stream after k_stitch, on res->seq / res->seq_len as they are
+ *                         on the device.
+ *   ccsx_submit_cdna      ticketed like ccsx_submit_requests: the report's arrays follow the lifetime rule of `res` and should be page-locked; the request, set
+ *                         and options structs are read during the call only (every ticket carries its own set and options).
+ * rq may be NULL or carry any member of ccsx_requests.  The request is not combined with ccsx_hd_request, ccsx_handoff_request, ccsx_barcode_request,
+ * ccsx_segment_request or ccsx_represent_request: no entry point takes both.  The two ccsx_cdna_reads forms: opts NULL = ccsx_cdna_opts_default; reads as for
+ * ccsx_barcode_reads.  Errors of the call (nothing is enqueued, reserved or launched): a null argument, n_primers outside 2 .. CCSX_CDNA_MAX_PRIMERS, a role above
+ * 1, a set without a primer of each role, a length outside 8 .. 64, a code above 3, options out of range, a nonzero reserved word, a report sized for another batch
+ * (n_zmw != n) or with a NULL array, n < 0, a negative seq_off.  Without a request nothing of it is launched, reserved or copied.                              */
+#define CCSX_CDNA_MAX_PRIMERS 64
+#define CCSX_CDNA_MIN_LEN     8
+#define CCSX_CDNA_MAX_LEN     64
+enum ccsx_cdna_class { CCSX_CDNA_NO_PRIMER = 0, CCSX_CDNA_ONE_END = 1, CCSX_CDNA_SAME_ROLE = 2, CCSX_CDNA_SHORT = 3, CCSX_CDNA_CONCATEMER = 4,
+                       CCSX_CDNA_NO_TAIL = 5, CCSX_CDNA_FULL_LENGTH = 6 };
+typedef struct ccsx_cdna_opts {
+    int32_t window;              /* bases of either end that are searched for a primer, 8 .. 1024 [64]                                                           */
+    int32_t max_dist_pct;        /* a primer of m bases is called, and hits inside the read, at up to floor(m * max_dist_pct / 100) edits, 0 .. 30 [15]           */
+    int32_t min_margin;          /* an end is called when every other primer is at least this many edits worse, 0 .. 64 [1]                                      */
+    int32_t polya_mismatch;      /* what a base other than A costs the poly(A) scan, 1 .. 8 [3]                                                                  */
+    int32_t polya_xdrop;         /* the scan stops when its score lies more than this below its maximum, 0 .. 64 [3]                                             */
+    int32_t polya_max;           /* insert bases the scan looks at, 16 .. 4096 [512]                                                                             */
+    int32_t min_polya;           /* a read with a shorter tail is NO_TAIL, 0 .. 255; 0: a tail is not required [20]                                               */
+    int32_t min_len;             /* a read whose insert without the tail is shorter is SHORT, 1 .. 65535 [50]                                                    */
+} ccsx_cdna_opts;
+typedef struct ccsx_cdna_set {
+    int32_t n_primers;           /* 2 .. CCSX_CDNA_MAX_PRIMERS                                                                                                   */
+    int32_t len[CCSX_CDNA_MAX_PRIMERS];                         /* CCSX_CDNA_MIN_LEN .. CCSX_CDNA_MAX_LEN; lengths may differ within a set                       */
+    uint8_t role[CCSX_CDNA_MAX_PRIMERS];                        /* 0: a 5' primer, 1: a 3' primer; the set has at least one of each                              */
+    uint8_t seq[CCSX_CDNA_MAX_PRIMERS][CCSX_CDNA_MAX_LEN];      /* codes 0 .. 3 (A C G T), the oligo as the vendor's primer file gives it                        */
+} ccsx_cdna_set;
+typedef struct ccsx_cdna_report {
+    int32_t  n_zmw;
+    int32_t *tested;             /* [n_zmw] 1: seq_len > 0; 0: untested (cls 0, strand -1, first_internal -1, idx -1, dist / second 255, everything else 0)       */
+    int32_t *cls;                /* [n_zmw] enum ccsx_cdna_class                                                                                                 */
+    int32_t *strand;             /* [n_zmw] 0: sense, 1: antisense, -1: classes NO_PRIMER, ONE_END, SAME_ROLE                                                    */
+    int32_t *start, *end;        /* [n_zmw] the slice of classes CONCATEMER, NO_TAIL and FULL_LENGTH; 0, 0 otherwise                                             */
+    int32_t *polya_len;          /* [n_zmw] the poly(A) bases next to the 3' primer                                                                              */
+    int32_t *n_internal;         /* [n_zmw] primer hits inside the insert, not capped                                                                            */
+    int32_t *first_internal;     /* [n_zmw] the smallest start among them; -1 without one                                                                        */
+    int32_t *idx;                /* [n_zmw][2] per end: the primer of smallest dist (ties: the smallest index)                                                   */
+    int32_t *dist;               /* [n_zmw][2] its edit distance to the best substring of the window                                                             */
+    int32_t *second;             /* [n_zmw][2] the smallest dist of any other primer, of either role                                                             */
+    int32_t *clip;               /* [n_zmw][2] the smallest j such that a substring ending at window position j attains dist                                      */
+} ccsx_cdna_report;
+typedef struct ccsx_cdna_request {
+    const ccsx_cdna_opts *opts;          /* NULL = ccsx_cdna_opts_default                                                                                        */
+    const ccsx_cdna_set  *set;
+    ccsx_cdna_report     *report;
+    int32_t               reserved[2];   /* must be 0                                                                                                            */
+} ccsx_cdna_request;
+void        ccsx_cdna_opts_default(ccsx_cdna_opts *o);
+int         ccsx_cdna_rule_version(void);
+int         ccsx_cdna_reads_host(const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len,
+                                 int32_t n, ccsx_cdna_report *report);
+int         ccsx_cdna_reads(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const uint8_t *seq, const int64_t *seq_off,
+                            const int32_t *seq_len, int32_t n, ccsx_cdna_report *report);
+int         ccsx_consensus_cdna(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_cdna_request *cd);
+int         ccsx_submit_cdna(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_cdna_request *cd, ccsx_ticket *ticket);
+
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
  * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one

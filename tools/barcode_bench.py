@@ -7,61 +7,37 @@
 For the kernel's time per ticket, a kernel trace in a run of its own:
     rocprofv3 --kernel-trace --stats -d OUT -o trace -- python tools/barcode_bench.py --child on --steps 3 --warmup 1
     python tools/barcode_bench.py --trace-summary OUT --out profiles/barcode_rocprofv3_summary.txt
---build-only: compile kernel_bench and stop (no GPU needed)."""
+--build-only: compile kernel_bench and stop (no GPU needed).  The build, the ticket loop and the rounds are tools/reads_bench.py's, shared with the other two."""
 import argparse
 import glob
-import json
 import os
 import sqlite3
 import subprocess
 import sys
-import time
 
 import numpy as np
 
-R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(R, "tools", "barcode_bench", "kernel_bench")
-SRC = os.path.join(R, "tools", "barcode_bench", "kernel_bench.hip")
+import reads_bench as RB
 
-
-def build_kernel_bench():
-    deps = [SRC] + [os.path.join(R, "ccs_amd", "csrc", f) for f in ("ccsx_barcode.hip", "ccsx_barcode_api.cpp", "barcode_core.h", "wave_ops.h")]
-    if os.path.exists(EXE) and all(os.path.getmtime(d) <= os.path.getmtime(EXE) for d in deps):
-        return
-    subprocess.check_call([os.environ.get("HIPCC", "hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(R, "include"),
-                           "-I" + os.path.join(R, "ccs_amd", "csrc"), SRC, "-o", EXE])
+DEPS = ("ccsx_barcode.hip", "ccsx_barcode_api.cpp", "barcode_core.h", "wave_ops.h")
 
 
 def child(a):
-    """one configuration in this process: a.steps tickets after a.warmup, three in flight; one JSON line"""
-    sys.path.insert(0, a.root or R)
+    """one configuration in this process (tools/reads_bench.py timed_tickets); one JSON line"""
+    sys.path.insert(0, a.root or RB.R)
     from ccs_amd import api
     b = api.synth(a.zmws, a.passes, a.length, seed=1).pinned()
-    h = api.Handle(0)
-    res = [api.Results.allocate(b, pinned=True, raw=False) for _ in range(3)]
-    kw = [{}] * 3
-    if a.child == "on":
-        rng = np.random.default_rng(11)
-        bset = api.BarcodeSet.from_codes([rng.integers(0, 4, 16).astype(np.uint8) for _ in range(96)])
-        kw = [dict(barcodes=api.BarcodeReport.allocate(b.n_zmw, pinned=True), barcode_set=bset) for _ in range(3)]
 
-    def run(k):
-        ts = [h.submit(b, res[i % 3], **kw[i % 3]) for i in range(k)]
-        for t in ts[-3:]:
-            h.wait(t)
-        for t in ts:
-            h.release(t)
-    run(a.warmup)
-    t0 = time.perf_counter()
-    run(a.steps)
-    wall = time.perf_counter() - t0
-    out = dict(config=a.child, step_ms=round(wall * 1e3 / a.steps, 2), zmws_per_s=round(a.steps * a.zmws / wall, 1), success=int((res[(a.steps - 1) % 3].status == 0).sum()))
-    if a.child == "on":
-        rep = kw[(a.steps - 1) % 3]["barcodes"]
-        out["tested"] = int(rep.tested.sum())
-        out["called_ends"] = int((rep.call & 1).sum() + (rep.call >> 1).sum())
-    h.close()
-    print("RESULT " + json.dumps(out))
+    def request(api, n):
+        if a.child != "on":
+            return None
+        rng = np.random.default_rng(11)
+        return dict(barcodes=api.BarcodeReport.allocate(n, pinned=True), barcode_set=api.BarcodeSet.from_codes([rng.integers(0, 4, 16).astype(np.uint8) for _ in range(96)]))
+
+    def summary(kw):
+        rep = kw["barcodes"]
+        return dict(tested=int(rep.tested.sum()), called_ends=int((rep.call & 1).sum() + (rep.call >> 1).sum()))
+    RB.timed_tickets(a, b, request, summary if a.child == "on" else None)
 
 
 def trace_summary(root, out):
@@ -87,55 +63,30 @@ def trace_summary(root, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--zmws", type=int, default=16384)
-    ap.add_argument("--passes", type=int, default=10)
-    ap.add_argument("--length", type=int, default=10000)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (its ccs_amd/libccsx.so is what its process loads)")
-    ap.add_argument("--child", choices=("off", "on", "parent"), default=None)
-    ap.add_argument("--root", default=None)
+    RB.add_step_arguments(ap)
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--build-only", action="store_true")
     ap.add_argument("--trace-summary", default=None)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.trace_summary:
         return trace_summary(a.trace_summary, a.out)
     if a.build_only:
-        return build_kernel_bench()
+        return RB.build_kernel_bench("barcode", DEPS)
     if a.child:
         return child(a)
-    lines = [f"python tools/barcode_bench.py   (MI355X)", ""]
+    lines = ["python tools/barcode_bench.py   (MI355X)", ""]
     if not a.skip_kernel:
-        build_kernel_bench()
-        lines += subprocess.run([EXE, str(a.zmws), str(a.length)], check=True, capture_output=True, text=True, timeout=600).stdout.splitlines() + [""]
+        exe = RB.build_kernel_bench("barcode", DEPS)
+        lines += subprocess.run([exe, str(a.zmws), str(a.length)], check=True, capture_output=True, text=True, timeout=600).stdout.splitlines() + [""]
     configs = ["off", "on"] + (["parent"] if a.parent else [])
-    every = {c: [] for c in configs}
-    last = {}
-    for _ in range(a.rounds):
-        for c in configs:
-            root = os.path.abspath(a.parent) if c == "parent" else R
-            env = {k: v for k, v in os.environ.items() if k != "CCSX_LIB"}
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", c, "--root", root, "--zmws", str(a.zmws), "--passes", str(a.passes),
-                                "--length", str(a.length), "--steps", str(a.steps), "--warmup", str(a.warmup)], capture_output=True, text=True, timeout=900, cwd=root, env=env)
-            got = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-            if p.returncode != 0 or not got:
-                sys.exit(f"configuration {c} failed (exit {p.returncode}):\n{p.stdout}\n{p.stderr}")   # (nothing more is started)
-            last[c] = json.loads(got[-1][7:])
-            every[c].append(last[c]["step_ms"])
-            print(got[-1], flush=True)
-    med = {c: float(np.median(v)) for c, v in every.items()}
+    every, last = RB.alternate(__file__, configs, a, lambda c: "off" if c == "parent" else c)
+    rows, med = RB.round_lines(configs, every)
     lines.append(f"the two-stage step: {a.zmws} ZMWs x {a.passes} passes x {a.length} bases, {a.steps} tickets with three in flight after {a.warmup} warm-up tickets, one process per "
                  f"configuration, alternating {a.rounds} rounds; request on: 96 16-mers at the default options")
-    for c in configs:
-        lines.append(f"  {c:7s} ms per step by round: " + " ".join(f"{x:.2f}" for x in every[c]) + f"   median {med[c]:.2f} (min {min(every[c]):.2f}, max {max(every[c]):.2f})")
+    lines += rows
     lines.append(f"  request on against off, median against median: {100 * (med['on'] / med['off'] - 1):+.2f} %")
     if a.parent:
-        inside = min(every["off"]) <= max(every["parent"]) and min(every["parent"]) <= max(every["off"])
-        lines.append(f"  off against the parent commit's library, median against median: {100 * (med['off'] / med['parent'] - 1):+.2f} %; the two spreads "
-                     f"{'overlap' if inside else 'DO NOT overlap'}")
+        lines.append(RB.parent_line(every, med))
     lines.append(f"  request on: {last['on']['tested']} reads tested, {last['on']['called_ends']} ends called; SUCCESS ZMWs on / off: {last['on']['success']} / {last['off']['success']}")
     text = "\n".join(lines) + "\n"
     print(text, end="")
