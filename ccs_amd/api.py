@@ -948,6 +948,91 @@ def cdna_reads_host(primers: CdnaPrimers, reads, opts: "CdnaOpts | None" = None,
     return _reads_host(CdnaReport, primers, reads, opts, report)
 
 
+# ---- duplicate reads (include/ccsx.h ccsx_dup_*; DESIGN.md §2 "Duplicate rule")
+DUP_MAX_BUCKET, DUP_MAX_READS = 512, 1 << 24
+DUP_UNTESTED, DUP_TESTED, DUP_OVERFLOW = 0, 1, 2
+DUP_SIG_DTYPE = np.dtype([("end", np.uint64, (2, 2)), ("mini", np.uint32, (2,)), ("len", np.int32), ("window", np.int32)])   # ccsx_dup_sig, 48 bytes
+
+
+class DupOpts(C.Structure):
+    _fields_ = [("window", C.c_int32), ("kmer", C.c_int32), ("max_dist_pct", C.c_int32), ("max_len_diff_pct", C.c_int32)]
+
+
+class CDupReport(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in ("status", "rep", "set_size", "dup")]
+
+
+def dup_opts_default() -> DupOpts:
+    o = DupOpts()
+    lib().ccsx_dup_opts_default(C.byref(o))
+    return o
+
+
+class DupReport(_PlaneReport):
+    """ccsx_dup_report: per read status (DUP_UNTESTED / DUP_TESTED / DUP_OVERFLOW), rep (the representative of its set), set_size and dup (0 / 1)"""
+    FIELDS = ("status", "rep", "set_size", "dup")
+    PLANES = _int_planes(*FIELDS)
+    CSTRUCT = CDupReport
+
+    def c_struct(self) -> CDupReport:
+        r = CDupReport()
+        r.n = len(self.status)
+        for k in self.FIELDS:
+            setattr(r, k, _ptr(getattr(self, k), C.c_int32))
+        return r
+
+    def fields(self, z: int) -> dict:
+        return {k: int(getattr(self, k)[z]) for k in self.FIELDS}
+
+
+def _dup_sign_args(reads, opts):
+    """the arguments of ccsx_dup_sign_reads[_host]: (args, signatures, keep).  reads: a list of code arrays, or the tuple (seq, seq_off, seq_len) of the C call"""
+    if isinstance(reads, tuple):
+        seq, seq_off, seq_len = (np.ascontiguousarray(a, t) for a, t in zip(reads, (np.uint8, np.int64, np.int32)))
+        n = len(seq_len)
+    else:
+        reads = [np.ascontiguousarray(r, np.uint8) for r in reads]
+        n = len(reads)
+        seq_len = np.array([len(r) for r in reads], np.int32).reshape(n)
+        seq_off = np.zeros(n, np.int64)
+        if n:
+            seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64)
+        seq = np.concatenate(reads + [np.zeros(1, np.uint8)])
+    sig = np.zeros(n, DUP_SIG_DTYPE)
+    o = opts if opts is not None else dup_opts_default()
+    return (C.byref(o), _ptr(seq, C.c_uint8), _ptr(seq_off, C.c_int64), _ptr(seq_len, C.c_int32), n, sig.ctypes.data_as(C.c_void_p)), sig, (o, seq, seq_off, seq_len)
+
+
+def _dup_cluster_args(sig, group, score, opts, report):
+    """the arguments of ccsx_dup_cluster[_host]: (args, report, keep).  group / score: None (all 0) or one int32 per read"""
+    sig = np.ascontiguousarray(sig, DUP_SIG_DTYPE)
+    n = len(sig)
+    g = None if group is None else np.ascontiguousarray(group, np.int32).reshape(n)
+    sc = None if score is None else np.ascontiguousarray(score, np.int32).reshape(n)
+    rep = report if report is not None else DupReport.allocate(n)
+    crep = rep.c_struct()
+    o = opts if opts is not None else dup_opts_default()
+    null = C.POINTER(C.c_int32)()
+    return (C.byref(o), sig.ctypes.data_as(C.c_void_p), null if g is None else _ptr(g, C.c_int32), null if sc is None else _ptr(sc, C.c_int32), n,
+            C.byref(crep)), rep, (o, sig, g, sc, crep)
+
+
+def dup_sign_host(reads, opts: "DupOpts | None" = None) -> np.ndarray:
+    """ccsx_dup_sign_reads_host: the signatures (DUP_SIG_DTYPE) of a list of arrays of codes 0 .. 3 on the calling thread, no device"""
+    args, sig, _keep = _dup_sign_args(reads, opts)
+    if lib().ccsx_dup_sign_reads_host(*args) != 0:
+        raise RuntimeError("ccsx_dup_sign_reads_host failed: " + lib().ccsx_last_error().decode())
+    return sig
+
+
+def dup_cluster_host(sig, group=None, score=None, opts: "DupOpts | None" = None, report: "DupReport | None" = None) -> DupReport:
+    """ccsx_dup_cluster_host: the duplicate sets of the signatures on the calling thread, no device"""
+    args, rep, _keep = _dup_cluster_args(sig, group, score, opts, report)
+    if lib().ccsx_dup_cluster_host(*args) != 0:
+        raise RuntimeError("ccsx_dup_cluster_host failed: " + lib().ccsx_last_error().decode())
+    return rep
+
+
 # ---- representative reads (include/ccsx.h ccsx_represent_*; DESIGN.md §2 "Representative rule")
 REPRESENT_POLISHED, REPRESENT_NONE, REPRESENT_DRAFT, REPRESENT_SUBREAD = 0, 1, 2, 3
 REPRESENT_NAMES = ("POLISHED", "NONE", "DRAFT", "SUBREAD")
@@ -1284,6 +1369,7 @@ EXPORTS = [
     "ccsx_submit_segments",
     "ccsx_cdna_opts_default", "ccsx_cdna_rule_version", "ccsx_cdna_reads_host", "ccsx_cdna_reads", "ccsx_consensus_cdna", "ccsx_submit_cdna",
     "ccsx_represent_rule_version", "ccsx_represent_host", "ccsx_consensus_represent", "ccsx_submit_represent",
+    "ccsx_dup_opts_default", "ccsx_dup_rule_version", "ccsx_dup_hash", "ccsx_dup_sign_reads_host", "ccsx_dup_sign_reads", "ccsx_dup_cluster_host", "ccsx_dup_cluster",
 ]
 
 _lib = None
@@ -1421,6 +1507,16 @@ def lib() -> C.CDLL:
         L.ccsx_fitter_add.argtypes = [C.c_void_p, C.POINTER(CTrainCounts), C.POINTER(C.c_float)]
         L.ccsx_fitter_finish.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(FitReport)]
         L.ccsx_fitter_destroy.argtypes = [C.c_void_p]
+        L.ccsx_dup_opts_default.restype = None
+        L.ccsx_dup_opts_default.argtypes = [C.POINTER(DupOpts)]
+        L.ccsx_dup_hash.restype = C.c_uint32
+        L.ccsx_dup_hash.argtypes = [C.c_uint32]
+        _dsign = [C.POINTER(DupOpts), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
+        _dclus = [C.POINTER(DupOpts), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.POINTER(CDupReport)]
+        L.ccsx_dup_sign_reads_host.argtypes = _dsign
+        L.ccsx_dup_sign_reads.argtypes = [C.c_void_p] + _dsign
+        L.ccsx_dup_cluster_host.argtypes = _dclus
+        L.ccsx_dup_cluster.argtypes = [C.c_void_p] + _dclus
         L.ccsx_barcode_opts_default.restype = None
         L.ccsx_barcode_opts_default.argtypes = [C.POINTER(BarcodeOpts)]
         _bcreads = [C.POINTER(BarcodeSet), C.POINTER(BarcodeOpts), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(CBarcodeReport)]
@@ -2130,6 +2226,23 @@ class Handle:
     def cdna_reads(self, primers: CdnaPrimers, reads, opts: "CdnaOpts | None" = None, report: "CdnaReport | None" = None) -> CdnaReport:
         """ccsx_cdna_reads: k_cdna on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
         return self._reads(CdnaReport, primers, reads, opts, report)
+
+    # ---- duplicate reads (ccsx_dup_sign_reads / ccsx_dup_cluster): the sets of reads that are the same molecule
+    def dup_sign(self, reads, opts: "DupOpts | None" = None) -> np.ndarray:
+        """ccsx_dup_sign_reads: k_dup_sign on the caller's reads, a list of arrays of codes 0 .. 3: their signatures (DUP_SIG_DTYPE).  Synchronous; no slot is touched"""
+        args, sig, _keep = _dup_sign_args(reads, opts)
+        self._check(self._L.ccsx_dup_sign_reads(self._h, *args), "ccsx_dup_sign_reads")
+        return sig
+
+    def dup_cluster(self, sig, group=None, score=None, opts: "DupOpts | None" = None, report: "DupReport | None" = None) -> DupReport:
+        """ccsx_dup_cluster: the duplicate sets of the signatures (group / score: None, or one int32 per read).  Synchronous; no slot is touched"""
+        args, rep, _keep = _dup_cluster_args(sig, group, score, opts, report)
+        self._check(self._L.ccsx_dup_cluster(self._h, *args), "ccsx_dup_cluster")
+        return rep
+
+    def mark_duplicates(self, reads, group=None, score=None, opts: "DupOpts | None" = None) -> DupReport:
+        """dup_sign, then dup_cluster on its signatures"""
+        return self.dup_cluster(self.dup_sign(reads, opts), group, score, opts)
 
     # ---- representative reads (ccsx_consensus_represent): a draft or a subread in the result planes of every ZMW that was not polished
     def consensus_represent(self, batch: Batch, subread_fallback: bool = False, kinetics: bool = False, res: "Results | None" = None,

@@ -116,6 +116,13 @@ struct Options {
     double fit_min_rq = 0.999;    // --fit-min-rq: a polished consensus is a truth to measure passes against from this predicted accuracy on
     long long fit_max_zmws = 0;   // --fit-max-zmws: ZMWs (after the step-1 filters) that are used, 0 = all
     int fit_degree = -1;          // --fit-degree: polynomial degree of the transition weights (-1: the fitter's default)
+    bool mark_duplicates = false; // --mark-duplicates IN.bam OUT.bam: the duplicate mode (DESIGN.md §2 "Duplicate rule"): reads in, the same reads out, marked
+    bool dup_remove = false;      // --dup-remove: duplicates are left out instead of marked
+    bool dup_within_barcodes = false;   // --dup-within-barcodes: only reads of equal bc tag are compared
+    int dup_window = -1, dup_kmer = -1, dup_max_dist_pct = -1, dup_max_len_diff_pct = -1;   // --dup-window ...: overrides of ccsx_dup_opts (-1: the default)
+    std::string dup_counts;       // --dup-counts FILE.tsv: sets per set size
+    ccsx_dup_opts dup_opts{};     // ... the options of the run
+    std::vector<std::string> seen;   // every option of the command line, as given (--mark-duplicates refuses what it does not take)
 };
 
 enum HdMode { HD_OFF = 0, HD_SPLIT = 1, HD_DROP = 2 };
@@ -327,6 +334,19 @@ void usage()
                  "      --write-synthetic N,P,L[,seed]  write a synthetic subreads.bam to OUT (no IN)\n"
                  "      --dump-zmws                     list ZMWs after the step-1 filters (no GPU, no OUT)\n"
                  "      --host-only                     read, filter and pack IN into batch staging, no engine (no GPU, no OUT): host throughput\n"
+                 "duplicate marking (ccs --mark-duplicates IN.bam OUT.bam; one GPU; IN: an unaligned BAM of reads, HiFi reads, segments or cDNA reads):\n"
+                 "      --mark-duplicates     find the reads of IN that are the same molecule (DESIGN.md, Duplicate rule: equal end minimizers, end windows\n"
+                 "                            within an edit distance, lengths within a tolerance; single linkage) and write every record of IN to OUT: a member\n"
+                 "                            of a set of two or more gains ds:i (the set's size), a duplicate also FLAG 0x400 and du:Z (the name of the set's\n"
+                 "                            representative, the member of largest rq).  No OUT.bam.pbi is written.  Not with any option of the consensus side,\n"
+                 "                            --chunk or input from stdin: usage errors\n"
+                 "      --dup-remove          leave the duplicates out of OUT instead of marking them\n"
+                 "      --dup-within-barcodes only reads with equal bc tags are compared\n"
+                 "      --dup-window W        bases of each end that are compared, 16 .. 64 [32]\n"
+                 "      --dup-kmer K          the minimizer's k, 8 .. 16 [12]\n"
+                 "      --dup-max-dist-pct P  two end windows agree within floor(W * P / 100) edits, 0 .. 30 [10]\n"
+                 "      --dup-max-len-diff-pct P  two reads agree in length within P percent of the shorter, 0 .. 20 [2]\n"
+                 "      --dup-counts F.tsv    sets per set size\n"
                  "model training (ccs --fit-model OUT.json IN.subreads.bam; one GPU, no HiFi output):\n"
                  "      --fit-model OUT.json  fit the Arrow parameter set to the subreads of IN by EM and write it as a ccsx-1 json with the header's chemistry\n"
                  "                            triple: per iteration every batch is drafted and polished, the passes are measured against the polished reads of at\n"
@@ -451,6 +471,7 @@ bool parse(int argc, char **argv, Options &o)
 {
     ccsx_opts_default(&o.o);
     std::vector<std::string> pos;
+    bool dash = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *n) -> std::string { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", n); std::exit(2); } return argv[++i]; };
@@ -462,6 +483,7 @@ bool parse(int argc, char **argv, Options &o)
             if (v.empty() || *end || n < lo || n > hi) { std::fprintf(stderr, "ccs: %s needs %s, got '%s'\n", a.c_str(), what, v.c_str()); std::exit(2); }
             return (int)n;
         };
+        if (a.size() > 1 && a[0] == '-') o.seen.push_back(a);
         if (a == "-h" || a == "--help") { usage(); std::exit(0); }
         else if (a == "--version") { std::printf("ccs (ccs_amd, MI355X-native consensus path) abi %d spec %d\n", ccsx_abi_version(), ccsx_spec_version()); std::exit(0); }
         else if (a == "-j" || a == "--num-threads") o.threads = std::atoi(need("-j").c_str());
@@ -532,6 +554,14 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--fit-min-rq") o.fit_min_rq = std::atof(need(a.c_str()).c_str());
         else if (a == "--fit-max-zmws") o.fit_max_zmws = std::atoll(need(a.c_str()).c_str());
         else if (a == "--fit-degree") o.fit_degree = std::atoi(need(a.c_str()).c_str());
+        else if (a == "--mark-duplicates") o.mark_duplicates = true;
+        else if (a == "--dup-remove") o.dup_remove = true;
+        else if (a == "--dup-within-barcodes") o.dup_within_barcodes = true;
+        else if (a == "--dup-window") o.dup_window = need_int(16, 64, "a number in 16 .. 64");
+        else if (a == "--dup-kmer") o.dup_kmer = need_int(8, 16, "a number in 8 .. 16");
+        else if (a == "--dup-max-dist-pct") o.dup_max_dist_pct = need_int(0, 30, "a number in 0 .. 30");
+        else if (a == "--dup-max-len-diff-pct") o.dup_max_len_diff_pct = need_int(0, 20, "a number in 0 .. 20");
+        else if (a == "--dup-counts") o.dup_counts = need(a.c_str());
         else if (a == "--disable-heuristics") o.o.disable_heuristics = 1;
         else if (a == "--metrics-json") { o.metrics = need(a.c_str()); o.metrics_named = true; }
         else if (a == "--report-json") o.report_json = need(a.c_str());
@@ -543,8 +573,33 @@ bool parse(int argc, char **argv, Options &o)
             std::fprintf(stderr, "ccs: %s is not supported by this build (the MI355X consensus path covers the default HiFi mode, --by-strand and --hifi-kinetics)\n", a.c_str());
             std::exit(2);
         }
+        else if (a == "-") dash = true;                      // (stdin: no mode reads it; --mark-duplicates says so, the others know no such option)
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
+    }
+    if (dash && !o.mark_duplicates) { std::fprintf(stderr, "unknown option -\n"); return false; }
+    if (!o.mark_duplicates && (o.dup_remove || o.dup_within_barcodes || o.dup_window >= 0 || o.dup_kmer >= 0 || o.dup_max_dist_pct >= 0 ||
+                               o.dup_max_len_diff_pct >= 0 || !o.dup_counts.empty())) {
+        std::fprintf(stderr, "ccs: the --dup-* options need --mark-duplicates\n"); std::exit(2);
+    }
+    if (o.mark_duplicates) {                                 // a mode of its own: reads in, the same reads out.  It takes its own options, the threads, one device, the
+        // log and the report file; every option of the consensus side is refused by name, before any input is opened
+        static const char *const takes[] = {"--mark-duplicates", "--dup-remove", "--dup-within-barcodes", "--dup-window", "--dup-kmer", "--dup-max-dist-pct",
+                                            "--dup-max-len-diff-pct", "--dup-counts", "-j", "--num-threads", "--gpus", "--log-level", "--log-file", "--report-file"};
+        for (const std::string &a : o.seen) {
+            bool ok = false;
+            for (const char *t : takes) ok = ok || a == t;
+            if (!ok) { std::fprintf(stderr, "ccs: --mark-duplicates combined with %s is not supported\n", a.c_str()); std::exit(2); }
+        }
+        if (dash) { std::fprintf(stderr, "ccs: --mark-duplicates reads IN twice: input from stdin (-) is not supported\n"); std::exit(2); }
+        if (o.all_gpus || o.gpus.size() > 1) { std::fprintf(stderr, "ccs: --mark-duplicates runs on one GPU: --gpus with more than one device is not supported\n"); std::exit(2); }
+        if (pos.size() != 2) { std::fprintf(stderr, "ccs: --mark-duplicates takes two positionals, IN.bam and OUT.bam\n"); std::exit(2); }
+        ccsx_dup_opts_default(&o.dup_opts);
+        if (o.dup_window >= 0) o.dup_opts.window = o.dup_window;
+        if (o.dup_kmer >= 0) o.dup_opts.kmer = o.dup_kmer;
+        if (o.dup_max_dist_pct >= 0) o.dup_opts.max_dist_pct = o.dup_max_dist_pct;
+        if (o.dup_max_len_diff_pct >= 0) o.dup_opts.max_len_diff_pct = o.dup_max_len_diff_pct;
+        if (o.dup_opts.kmer > o.dup_opts.window) { std::fprintf(stderr, "ccs: --dup-kmer %d is above --dup-window %d\n", o.dup_opts.kmer, o.dup_opts.window); std::exit(2); }
     }
     if (!o.cdna_primers.empty()) {                           // its own output mode: refused before any input is opened
         auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --cdna-primers combined with %s is not supported\n", what); std::exit(2); };
@@ -1438,6 +1493,186 @@ static int fit_model(const Options &opt, ccsx_handle &h0, const ccsx_model &star
     return 0;
 }
 
+// ---- ccs --mark-duplicates IN.bam OUT.bam (DESIGN.md §2 "Duplicate rule", §7): the reads of an unaligned BAM in, the same records out, the duplicate sets
+// marked.  Pass 1 streams the records and signs them on the device in bounded batches; per read it keeps the signature, a score (floor(rq * 10^6), 0 without
+// the tag), a group (0, or the bc pair under --dup-within-barcodes) and the name, of which only the representatives' outlive the clustering.  One
+// ccsx_dup_cluster call makes the sets.  Pass 2 reads IN again and writes every record through byte for byte; a member of a set of two or more gains ds:i (the
+// set's size), a duplicate also FLAG 0x400 and du:Z (the representative's name) — or is left out under --dup-remove.  No .pbi is written for OUT.
+struct DupTags { bool has_rq = false, has_bc = false, marked = false; float rq = 0.0f; uint32_t bc[2] = {0, 0}; };
+// the rq, bc, ds and du tags of a record body that parse_subread has accepted (every length in it has been checked there)
+static DupTags dup_scan_tags(const uint8_t *p, uint32_t bs)
+{
+    DupTags g;
+    const uint32_t l_name = p[8], n_cig = p[12] | (p[13] << 8), l_seq = rd32(p + 16);
+    const uint8_t *t = p + 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq, *end = p + bs;
+    while (t + 3 <= end) {
+        const char t0 = (char)t[0], t1 = (char)t[1], ty = (char)t[2];
+        t += 3;
+        if ((t0 == 'd' && t1 == 's') || (t0 == 'd' && t1 == 'u')) g.marked = true;
+        if (ty == 'Z' || ty == 'H') { while (t < end && *t) ++t; ++t; continue; }
+        if (ty == 'B') {
+            const char st = (char)t[0];
+            const uint32_t n = rd32(t + 1);
+            const uint8_t *q = t + 5;
+            if (t0 == 'b' && t1 == 'c' && (st == 'S' || st == 's') && n == 2) { g.has_bc = true; g.bc[0] = q[0] | (q[1] << 8); g.bc[1] = q[2] | (q[3] << 8); }
+            t = q + (size_t)n * tag_value_size(st);
+            continue;
+        }
+        if (t0 == 'r' && t1 == 'q' && ty == 'f') { std::memcpy(&g.rq, t, 4); g.has_rq = true; }
+        t += tag_value_size(ty);
+    }
+    return g;
+}
+
+static int mark_duplicates(const Options &opt, ThreadPool &pool)
+{
+    auto failed = [](const std::string &what) { std::fprintf(stderr, "ccs: --mark-duplicates: %s\n", what.c_str()); return 1; };
+    if (ccsx_device_count() <= 0) { std::fprintf(stderr, "ccs: no gfx950 GPU available (this build has no CPU path for the duplicate rule)\n"); return 1; }
+    ccsx_model model; ccsx_model_default(&model);
+    ccsx_opts eo; ccsx_opts_default(&eo);
+    ccsx_handle h = nullptr;
+    if (ccsx_create(opt.gpus.empty() ? 0 : opt.gpus[0], &model, &eo, &h)) { std::fprintf(stderr, "ccs: %s\n", ccsx_last_error()); return 1; }
+    struct Closer { ccsx_handle h; ~Closer() { ccsx_destroy(h); } } closer{h};
+    const ccsx_dup_opts &D = opt.dup_opts;
+    typedef std::chrono::steady_clock Clock;                         // (the phases' wall clock, one line at --log-level INFO: tools/dup_bench.py reads it)
+    auto seconds = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const Clock::time_point t_start = Clock::now();
+    double sign_s = 0.0;
+
+    // ---- pass 1: signatures in batches of at most kBatchReads reads or kBatchBases bases
+    constexpr size_t kBatchReads = 16384, kBatchBases = (size_t)64 << 20;
+    std::vector<ccsx_dup_sig> sig;
+    std::vector<int32_t> score, group;
+    std::vector<std::string> names;
+    std::string header_text;
+    {
+        BgzfReader in(opt.in, pool);
+        BamHeader hdr; read_header(in, hdr);
+        if (!hdr.refs.empty()) return failed("IN has reference sequences: aligned input is not supported");
+        header_text = hdr.text;
+        std::vector<uint8_t> seq;
+        std::vector<int64_t> off;
+        std::vector<int32_t> len;
+        auto flush = [&]() -> bool {
+            if (len.empty()) return true;
+            const size_t at = sig.size();
+            sig.resize(at + len.size());
+            seq.push_back(0);                                        // (never empty: the call wants a pointer)
+            const Clock::time_point t0 = Clock::now();
+            const int rc = ccsx_dup_sign_reads(h, &D, seq.data(), off.data(), len.data(), (int32_t)len.size(), sig.data() + at);
+            sign_s += seconds(t0, Clock::now());
+            seq.clear(); off.clear(); len.clear();
+            return rc == 0;
+        };
+        auto chunk = std::make_shared<RawChunk>();
+        Subread r;
+        while (read_raw_chunk(in, *chunk)) {
+            for (const auto &rec : chunk->recs) {
+                parse_subread(rec.first, rec.second, r);
+                const DupTags g = dup_scan_tags(rec.first, rec.second);
+                if (g.marked) return failed("read " + r.name + " already carries a ds or du tag: IN has been marked before");
+                if (sig.size() + len.size() >= (size_t)CCSX_DUP_MAX_READS) return failed("more than " + std::to_string(CCSX_DUP_MAX_READS) + " reads");
+                if (g.has_bc && g.bc[0] >= 32767u && opt.dup_within_barcodes) return failed("read " + r.name + ": a bc index above 32766");
+                const double sc = g.has_rq && g.rq == g.rq ? std::floor((double)g.rq * 1e6) : 0.0;
+                score.push_back((int32_t)std::min(2147483647.0, std::max(-2147483648.0, sc)));
+                group.push_back(opt.dup_within_barcodes && g.has_bc ? (int32_t)(1 + g.bc[0] * 65536u + g.bc[1]) : 0);
+                names.push_back(r.name);
+                off.push_back((int64_t)seq.size()); len.push_back((int32_t)r.len);
+                seq.resize(seq.size() + r.len);
+                if (r.len) r.decode_bases(seq.data() + seq.size() - r.len);
+                if (len.size() >= kBatchReads || seq.size() >= kBatchBases) { if (!flush()) return failed(ccsx_last_error()); }
+            }
+            chunk = std::make_shared<RawChunk>();
+        }
+        if (!flush()) return failed(ccsx_last_error());
+    }
+
+    // ---- the sets: one call over everything kept
+    const Clock::time_point t_pass1 = Clock::now();
+    const int32_t n = (int32_t)sig.size();
+    std::vector<int32_t> planes((size_t)n * 4 + 1);
+    ccsx_dup_report rep{n, planes.data(), planes.data() + n, planes.data() + 2 * (size_t)n, planes.data() + 3 * (size_t)n};
+    if (ccsx_dup_cluster(h, &D, sig.data(), group.data(), score.data(), n, &rep)) return failed(ccsx_last_error());
+    const Clock::time_point t_cluster = Clock::now();
+    int64_t tested = 0, untested = 0, overflowed = 0, sets = 0, dups = 0, largest = 0;
+    std::map<int32_t, int64_t> by_size;
+    for (int32_t z = 0; z < n; ++z) {
+        if (rep.status[z] == CCSX_DUP_UNTESTED) { ++untested; continue; }
+        if (rep.status[z] == CCSX_DUP_OVERFLOW) { ++overflowed; continue; }
+        ++tested; dups += rep.dup[z];
+        if (rep.rep[z] == z) { ++by_size[rep.set_size[z]]; sets += rep.set_size[z] >= 2; largest = std::max<int64_t>(largest, rep.set_size[z]); }
+    }
+    { std::vector<char> is_rep((size_t)n, 0);                         // only the names pass 2 writes stay
+      for (int32_t z = 0; z < n; ++z) if (rep.dup[z]) is_rep[rep.rep[z]] = 1;
+      for (int32_t z = 0; z < n; ++z) if (!is_rep[z]) std::string().swap(names[z]); }
+    std::vector<ccsx_dup_sig>().swap(sig);
+
+    // ---- pass 2: every record through, the members of a set marked
+    int64_t written = 0;
+    {
+        BgzfReader in(opt.in, pool);
+        BamHeader hdr; read_header(in, hdr);
+        BgzfWriter out(opt.out, pool);
+        write_header(out, header_text);
+        auto chunk = std::make_shared<RawChunk>();
+        std::vector<uint8_t> b;
+        int32_t z = 0;
+        while (read_raw_chunk(in, *chunk)) {
+            for (const auto &rec : chunk->recs) {
+                if (z >= n) return failed("IN changed between the two passes");
+                const int32_t k = z++;
+                if (rep.dup[k] && opt.dup_remove) continue;
+                ++written;
+                uint8_t b4[4];
+                auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) b4[i] = (uint8_t)(v >> (8 * i)); };
+                if (rep.set_size[k] < 2) { put32(rec.second); out.write(b4, 4); out.write(rec.first, rec.second); continue; }
+                b.assign(rec.first, rec.first + rec.second);
+                if (rep.dup[k]) { const unsigned flag = (b[14] | (b[15] << 8)) | 0x400u; b[14] = (uint8_t)(flag & 0xff); b[15] = (uint8_t)(flag >> 8); }
+                b.push_back('d'); b.push_back('s'); b.push_back('i');
+                put32((uint32_t)rep.set_size[k]); b.insert(b.end(), b4, b4 + 4);
+                if (rep.dup[k]) {
+                    const std::string &nm = names[rep.rep[k]];
+                    b.push_back('d'); b.push_back('u'); b.push_back('Z'); b.insert(b.end(), nm.begin(), nm.end()); b.push_back(0);
+                }
+                put32((uint32_t)b.size()); out.write(b4, 4); out.write(b.data(), b.size());
+            }
+            chunk = std::make_shared<RawChunk>();
+        }
+        if (z != n) return failed("IN changed between the two passes");
+        out.close();
+    }
+    const Clock::time_point t_pass2 = Clock::now();
+
+    // ---- the report block and the counts
+    if (!opt.report.empty()) {
+        FILE *f = std::fopen(opt.report.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", opt.report.c_str()); return 1; }
+        std::fprintf(f, "Duplicate marking (rule %d: window %d, kmer %d, max_dist_pct %d, max_len_diff_pct %d%s)\n", ccsx_dup_rule_version(), D.window, D.kmer,
+                     D.max_dist_pct, D.max_len_diff_pct, opt.dup_within_barcodes ? ", within barcodes" : "");
+        std::fprintf(f, "Reads input                 : %lld\n", (long long)n);
+        std::fprintf(f, "Reads tested                : %lld\n", (long long)tested);
+        std::fprintf(f, "Reads untested              : %lld\n", (long long)untested);
+        std::fprintf(f, "Reads in overflowed buckets : %lld\n", (long long)overflowed);
+        std::fprintf(f, "Duplicate sets              : %lld\n", (long long)sets);
+        std::fprintf(f, "Duplicates                  : %lld\n", (long long)dups);
+        std::fprintf(f, "Largest set                 : %lld\n", (long long)largest);
+        std::fprintf(f, "Reads written               : %lld\n", (long long)written);
+        std::fclose(f);
+    }
+    if (!opt.dup_counts.empty()) {
+        FILE *f = std::fopen(opt.dup_counts.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", opt.dup_counts.c_str()); return 1; }
+        std::fprintf(f, "set_size\tsets\n");
+        for (const auto &kv : by_size) std::fprintf(f, "%d\t%lld\n", kv.first, (long long)kv.second);
+        std::fclose(f);
+    }
+    if (opt.log_level >= 2)
+        std::fprintf(stderr, "ccs: --mark-duplicates: %lld reads, %lld sets, %lld duplicates %s; pass 1 %.3f s (of which ccsx_dup_sign_reads %.3f s, the rest inflate, "
+                             "parsing and base decoding), ccsx_dup_cluster %.3f s, pass 2 %.3f s (inflate, copy, deflate)\n", (long long)n, (long long)sets, (long long)dups,
+                     opt.dup_remove ? "removed" : "marked", seconds(t_start, t_pass1), sign_s, seconds(t_pass1, t_cluster), seconds(t_cluster, t_pass2));
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     Options opt;
@@ -1451,6 +1686,7 @@ int main(int argc, char **argv)
     try {
         ThreadPool pool(nthreads);
         if (!opt.write_synth.empty()) return write_synthetic(opt, pool);
+        if (opt.mark_duplicates) return mark_duplicates(opt, pool);
 
         // ---- --gpu-inflate: a free list of inflaters (declared before the reader, whose slab jobs use them)
         GpuInflaters gpu_inflaters;

@@ -192,6 +192,7 @@ struct ccsx_handle_s {
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
     DevBuf d_reads;                   // ccsx_barcode_reads / ccsx_segment_reads / ccsx_cdna_reads only: the call's set, report and reads (no slot is touched; the call ends synchronised)
+    DevBuf d_dup;                     // ccsx_dup_sign_reads / ccsx_dup_cluster only: the call's reads and signatures, or its signatures, keys, sort scratch and report
     DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
     ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
     Slot slot[CCSX_SLOTS];
@@ -2076,6 +2077,88 @@ int ccsx_cdna_reads(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_cdna_opt
                     int32_t n, ccsx_cdna_report *report)
 {
     return reads_sync<Cdna>(h, set, opts, seq, seq_off, seq_len, n, report, __func__);
+}
+
+// ---- duplicate reads (DESIGN.md §2 "Duplicate rule").  Both calls are synchronous on the polish stream, behind whatever tickets have enqueued there, in a buffer
+// of the handle's own: no slot is staged, retired or recycled.  Every part of the buffer starts on a multiple of 256 bytes
+static size_t dup_carve(size_t &at, size_t bytes) { const size_t p = at; at = (at + bytes + 255) & ~(size_t)255; return p; }
+
+static int dup_sign_enqueue(ccsx_handle h, const ccsx_dup_opts &o, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes,
+                            ccsx_dup_sig *sig, hipStream_t st)
+{
+    size_t at = 0;
+    const size_t o_sig = dup_carve(at, (size_t)n * sizeof(ccsx_dup_sig)), o_off = dup_carve(at, (size_t)n * 8), o_len = dup_carve(at, (size_t)n * 4),
+                 o_seq = dup_carve(at, (size_t)bytes);
+    if (h->d_dup.reserve(at)) return -2;
+    uint8_t *base = (uint8_t *)h->d_dup.p;
+    DupSignParams S{};
+    S.n = n; S.opts = o; S.seq = base + o_seq; S.seq_off = (const int64_t *)(base + o_off); S.seq_len = (const int32_t *)(base + o_len);
+    S.sig = (ccsx_dup_sig *)(base + o_sig);
+    HIPTRY(hipMemcpyAsync(base + o_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(base + o_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (bytes) HIPTRY(hipMemcpyAsync(base + o_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    if (const char *failed = ccsx_dup_sign_launch(S, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    HIPTRY(hipMemcpyAsync(sig, S.sig, (size_t)n * sizeof(ccsx_dup_sig), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+int ccsx_dup_sign_reads(ccsx_handle h, const ccsx_dup_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, ccsx_dup_sig *sig)
+{
+    ccsx_dup_opts o;
+    int64_t bytes;
+    if (ccsx_dup_check_sign(opts, seq, seq_off, seq_len, n, sig, __func__, &o, &bytes)) return -1;
+    if (!h) return refuse(__func__, "null argument");
+    if (n == 0) return 0;
+    HIPTRY(hipSetDevice(h->device));
+    const int rc = dup_sign_enqueue(h, o, seq, seq_off, seq_len, n, bytes, sig, h->s_comp);
+    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
+}
+
+static int dup_cluster_enqueue(ccsx_handle h, const ccsx_dup_opts &o, const ccsx_dup_sig *sig, const int32_t *group, const int32_t *score, int32_t n,
+                               const ccsx_dup_report *report, hipStream_t st)
+{
+    const size_t N = (size_t)n, tmp = ccsx_dup_sort_bytes(n);
+    size_t at = 0;
+    const size_t o_sig = dup_carve(at, N * sizeof(ccsx_dup_sig)), o_k0 = dup_carve(at, N * 8), o_k1 = dup_carve(at, N * 8), o_i0 = dup_carve(at, N * 4),
+                 o_i1 = dup_carve(at, N * 4), o_grp = dup_carve(at, N * 4), o_sc = dup_carve(at, N * 4), o_list = dup_carve(at, (1 + N / 2) * 4),
+                 o_rep = dup_carve(at, N * CCSX_DUP_PLANES * 4), o_tmp = dup_carve(at, tmp);
+    if (h->d_dup.reserve(at)) return -2;
+    uint8_t *base = (uint8_t *)h->d_dup.p;
+    DupClusterParams P{};
+    P.n = n; P.opts = o; P.sig = (const ccsx_dup_sig *)(base + o_sig);
+    P.group = group ? (const int32_t *)(base + o_grp) : nullptr; P.score = score ? (const int32_t *)(base + o_sc) : nullptr;
+    P.key[0] = (unsigned long long *)(base + o_k0); P.key[1] = (unsigned long long *)(base + o_k1);
+    P.idx[0] = (uint32_t *)(base + o_i0); P.idx[1] = (uint32_t *)(base + o_i1);
+    P.sort_tmp = base + o_tmp; P.sort_tmp_bytes = tmp;
+    P.list = (int32_t *)(base + o_list); P.rep = (int32_t *)(base + o_rep);
+    HIPTRY(hipMemcpyAsync(base + o_sig, sig, N * sizeof(ccsx_dup_sig), hipMemcpyHostToDevice, st));
+    if (group) HIPTRY(hipMemcpyAsync(base + o_grp, group, N * 4, hipMemcpyHostToDevice, st));
+    if (score) HIPTRY(hipMemcpyAsync(base + o_sc, score, N * 4, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    if (const char *failed = ccsx_dup_cluster_launch(P, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    const DupOut d = ccsx_dup_out(P.rep, N), r = ccsx_dup_out(*report);
+    HIPTRY(hipMemcpyAsync(r.status, d.status, N * 4, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(r.rep, d.rep, N * 4, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(r.set_size, d.set_size, N * 4, hipMemcpyDeviceToHost, st));
+    HIPTRY(hipMemcpyAsync(r.dup, d.dup, N * 4, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+int ccsx_dup_cluster(ccsx_handle h, const ccsx_dup_opts *opts, const ccsx_dup_sig *sig, const int32_t *group, const int32_t *score, int32_t n,
+                     ccsx_dup_report *report)
+{
+    ccsx_dup_opts o;
+    if (ccsx_dup_check_cluster(opts, sig, group, n, report, __func__, &o)) return -1;
+    if (!h) return refuse(__func__, "null argument");
+    if (n == 0) return 0;
+    HIPTRY(hipSetDevice(h->device));
+    const int rc = dup_cluster_enqueue(h, o, sig, group, score, n, report, h->s_comp);
+    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }
+    HIPTRY(hipStreamSynchronize(h->s_comp));
+    return 0;
 }
 
 int ccsx_get_timings(ccsx_handle h, ccsx_timings *t)

@@ -53,6 +53,14 @@ int ccsx_cdna_check(const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const 
 // caller-supplied reads, of either analysis: *bytes = the bytes of seq the reads cover (the largest seq_off[z] + seq_len[z] over the reads with seq_len[z] > 0)
 int ccsx_check_reads(const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const char *fn, int64_t *bytes);
 
+// ---- duplicate reads (ccsx_dup_api.cpp; DESIGN.md §2 "Duplicate rule"): the checks the host and the device form of each call share.  The checked options go to
+// *o (opts NULL: the defaults); *bytes as ccsx_check_reads.  The cluster check reads every signature's window and every group.  A refusal sets the error under `fn`
+// and returns -1.
+int ccsx_dup_check_sign(const ccsx_dup_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, const ccsx_dup_sig *sig,
+                        const char *fn, ccsx_dup_opts *o, int64_t *bytes);
+int ccsx_dup_check_cluster(const ccsx_dup_opts *opts, const ccsx_dup_sig *sig, const int32_t *group, int32_t n, const ccsx_dup_report *report, const char *fn,
+                           ccsx_dup_opts *o);
+
 // ---- representative reads (ccsx_represent_api.cpp; DESIGN.md §2 "Representative rule"): the request against the batch it is for and the options of the run — flags,
 // reserved words, the report's arrays and size, kinetics without opts.hifi_kinetics or batch.ipd.  A refusal sets the error under `fn` and returns -1.
 int ccsx_represent_check(const ccsx_represent_request *req, const ccsx_batch *b, const ccsx_opts *opts, const char *fn);

@@ -8,6 +8,7 @@
 #include "barcode_core.h"
 #include "segment_core.h"
 #include "cdna_core.h"
+#include "dup_core.h"
 #include "represent_core.h"
 
 // bytes of POA scratch per vertex (ccsx_kernels.hip poa_slot, all by topological position): the 32-row score column of far-read columns 128, five 16-byte
@@ -291,6 +292,9 @@ const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int m
 const char *ccsx_barcode_launch(const BarcodeParams &B, hipStream_t st);                 // ccsx_barcode.hip: k_barcode, one workgroup per read; NULL, or what failed
 const char *ccsx_segment_launch(const SegmentParams &G, hipStream_t st);                 // ccsx_segment.hip: k_segment, one workgroup per read; NULL, or what failed
 const char *ccsx_cdna_launch(const CdnaParams &D, hipStream_t st);                       // ccsx_cdna.hip: k_cdna, one workgroup per read; NULL, or what failed
+const char *ccsx_dup_sign_launch(const DupSignParams &S, hipStream_t st);                // ccsx_dup.hip: k_dup_sign, one wave per read; NULL, or what failed
+const char *ccsx_dup_cluster_launch(const DupClusterParams &P, hipStream_t st);          // ccsx_dup.hip: k_dup_keys, the sort, k_dup_buckets, k_dup_verify; NULL, or what failed
+size_t ccsx_dup_sort_bytes(int n);                                                       // ccsx_dup.hip: the sort's scratch for n pairs (no device work)
 const char *ccsx_represent_launch(const RepresentParams &R, hipStream_t st);             // ccsx_represent.hip: k_represent, one workgroup per ZMW; NULL, or what failed
 const char *ccsx_train_launch(const KParams &P, hipStream_t st, long long max_blocks);   // ccsx_train.hip: the count buffers zeroed + k_train; NULL, or what failed
 int ccsx_kernel_is_experiment();         // built with -DCCSX_EXPERIMENT (timing studies: wrong results)

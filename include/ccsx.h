@@ -1016,6 +1016,63 @@ int         ccsx_cdna_reads(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_
 int         ccsx_consensus_cdna(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_cdna_request *cd);
 int         ccsx_submit_cdna(ccsx_handle h, const ccsx_batch *b, ccsx_results *res, const ccsx_requests *rq, const ccsx_cdna_request *cd, ccsx_ticket *ticket);
 
+/* ---- duplicate reads (the rule: DESIGN.md §2 "Duplicate rule", its own version ccsx_dup_rule_version; this build's own, as the barcode, the segment and the
+ * cDNA rule are: the reference contains no duplicate rule; no result of the consensus changes).  The first analysis that looks across reads.  Integers only.
+ *   signature  of a read c[0, L): untested (window = 0, everything but len 0) when L < window.  Otherwise, per end e (end 0: c forwards, end 1: its reverse
+ *              complement, as the barcode rule's ends), the first `window` bases packed at 2 bits a base (base j: bits 2 (j % 32) of word j / 32), and the
+ *              minimizer: the smallest ccsx_dup_hash(x) over the window - kmer + 1 k-mers x of the end, a k-mer packed with its first base most significant.
+ *              ccsx_dup_hash is a bijection of 32-bit words, so equal minimizers are the same k-mer.
+ *   bucket     the tested reads of equal key (min(mini[0], mini[1]), max(mini[0], mini[1])): a read and its reverse complement share a key.  A bucket of more
+ *              than CCSX_DUP_MAX_BUCKET reads is overflowed: every read of it is reported CCSX_DUP_OVERFLOW and alone.
+ *   D(a, b)    of two end windows: the minimum over the last row and the last column of their start-anchored unit-cost edit table,
+ *              min(min_q ed(a, b[0, q)), min_p ed(a[0, p), b)).
+ *   pair       two reads i, j of one bucket are duplicates iff group[i] == group[j], |Li - Lj| * 100 <= max_len_diff_pct * min(Li, Lj), and with
+ *              kmax = window * max_dist_pct / 100 either D(e0i, e0j) <= kmax and D(e1i, e1j) <= kmax (same strand) or D(e0i, e1j) <= kmax and
+ *              D(e1i, e0j) <= kmax (opposite strands).
+ *   sets       the connected components of the pairs (single linkage).  The representative of a set is its member of largest score, ties: the smallest index.
+ * No output depends on the order of anything.
+ *   ccsx_dup_sign_reads_host / ccsx_dup_cluster_host   the rule on the calling thread, without a device: the reference of the tests.
+ *   ccsx_dup_sign_reads / ccsx_dup_cluster             k_dup_sign; k_dup_keys, a device radix sort, k_dup_buckets and k_dup_verify.  Synchronous, on the polish
+ *                                                      stream, in buffers of the handle's own grown on demand: no slot is staged or recycled and tickets in flight
+ *                                                      complete untouched (as ccsx_barcode_reads).
+ * opts NULL = ccsx_dup_opts_default; reads as for ccsx_barcode_reads (only the low two bits of a byte are read).  group / score NULL: all 0.  Errors of the call
+ * (nothing is reserved or launched): a null argument, options out of range, kmer > window, n < 0 or n > CCSX_DUP_MAX_READS, a negative seq_off, a signature
+ * whose window is neither 0 nor opts->window, a negative group, a report sized for another n or with a NULL array. */
+#define CCSX_DUP_MAX_BUCKET 512
+#define CCSX_DUP_MAX_READS  (1 << 24)
+#define CCSX_DUP_UNTESTED   0
+#define CCSX_DUP_TESTED     1
+#define CCSX_DUP_OVERFLOW   2
+typedef struct ccsx_dup_opts {
+    int32_t window;              /* bases of each end that are compared, 16 .. 64 [32]                                                                           */
+    int32_t kmer;                /* the minimizer's k, 8 .. 16 and <= window [12]                                                                                */
+    int32_t max_dist_pct;        /* two end windows agree when D <= floor(window * max_dist_pct / 100), 0 .. 30 [10]                                             */
+    int32_t max_len_diff_pct;    /* two reads agree in length when |Li - Lj| * 100 <= max_len_diff_pct * min(Li, Lj), 0 .. 20 [2]                                */
+} ccsx_dup_opts;
+typedef struct ccsx_dup_sig {    /* 48 bytes, no padding: every byte is written                                                                                  */
+    uint64_t end[2][2];          /* [end][word]: the window at 2 bits a base; bits past the window are 0                                                         */
+    uint32_t mini[2];            /* the minimizer of each end                                                                                                    */
+    int32_t  len;                /* L (0 for seq_len <= 0)                                                                                                       */
+    int32_t  window;             /* 0: untested; otherwise the window the signature was taken with                                                               */
+} ccsx_dup_sig;
+typedef struct ccsx_dup_report {
+    int32_t  n;
+    int32_t *status;             /* [n] CCSX_DUP_UNTESTED, CCSX_DUP_TESTED or CCSX_DUP_OVERFLOW                                                                   */
+    int32_t *rep;                /* [n] the representative of the read's set; an untested read, an overflowed one and a singleton report themselves               */
+    int32_t *set_size;           /* [n] the reads in the set                                                                                                      */
+    int32_t *dup;                /* [n] 1 iff the read is tested and is not its set's representative                                                              */
+} ccsx_dup_report;
+void        ccsx_dup_opts_default(ccsx_dup_opts *o);
+int         ccsx_dup_rule_version(void);
+uint32_t    ccsx_dup_hash(uint32_t x);
+int         ccsx_dup_sign_reads_host(const ccsx_dup_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, ccsx_dup_sig *sig);
+int         ccsx_dup_sign_reads(ccsx_handle h, const ccsx_dup_opts *opts, const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n,
+                                ccsx_dup_sig *sig);
+int         ccsx_dup_cluster_host(const ccsx_dup_opts *opts, const ccsx_dup_sig *sig, const int32_t *group, const int32_t *score, int32_t n,
+                                  ccsx_dup_report *report);
+int         ccsx_dup_cluster(ccsx_handle h, const ccsx_dup_opts *opts, const ccsx_dup_sig *sig, const int32_t *group, const int32_t *score, int32_t n,
+                             ccsx_dup_report *report);
+
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
  * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one
