@@ -948,6 +948,106 @@ def cdna_reads_host(primers: CdnaPrimers, reads, opts: "CdnaOpts | None" = None,
     return _reads_host(CdnaReport, primers, reads, opts, report)
 
 
+# ---- cell barcodes and UMIs (include/ccsx.h ccsx_cell_*; DESIGN.md §2 "Cell-tag rule")
+CELL_MAX_FIELD, CELL_MAX_WHITELIST = 16, 1 << 23
+CELL_NONE, CELL_RAW, CELL_EXACT, CELL_CORRECTED, CELL_AMBIGUOUS, CELL_ABSENT = range(6)
+CELL_NAMES = ("NONE", "RAW", "EXACT", "CORRECTED", "AMBIGUOUS", "ABSENT")
+CELL_PLANES = ("tag", "bc_raw", "bc", "bc_hi", "kind", "shift", "umi", "tag_clip")
+_CELL_UNSIGNED = ("bc_raw", "umi")
+
+
+class CellDesign(C.Structure):
+    """ccsx_cell_design: umi_len and bc_len (0 .. 16, at least one base together), side (0: at the 5' primer, 1: at the 3' primer), bc_first (1: the barcode is
+    next to the primer), indels (1: candidates with a lost or a gained base are tried)"""
+    _fields_ = [(k, C.c_int32) for k in ("umi_len", "bc_len", "side", "bc_first", "indels")] + [("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def default(cls) -> "CellDesign":
+        d = cls()
+        lib().ccsx_cell_design_default(C.byref(d))
+        return d
+
+
+class CCellReport(C.Structure):
+    _fields_ = [("cdna", CCdnaReport)] + [(k, C.POINTER(C.c_uint32 if k in _CELL_UNSIGNED else C.c_int32)) for k in CELL_PLANES]
+
+
+class CellWhitelist:
+    """ccsx_cell_whitelist: owns the host object and frees it.  barcodes: ACGT strings (either case) or arrays of codes, all of bc_len bases"""
+
+    def __init__(self, barcodes, bc_len: "int | None" = None):
+        if isinstance(barcodes, np.ndarray) and barcodes.ndim == 2:   # [n, bc_len] codes as they are
+            rows, self.bc_len = barcodes, int(barcodes.shape[1])
+        else:
+            rows = [["ACGT".index(c) for c in q.upper()] if isinstance(q, str) else [int(c) for c in q] for q in barcodes]
+            self.bc_len = int(bc_len) if bc_len is not None else (len(rows[0]) if rows else 0)
+            if any(len(r) != self.bc_len for r in rows):
+                raise ValueError(f"every barcode of a whitelist has bc_len = {self.bc_len} bases")
+        codes = np.ascontiguousarray(np.array(rows, np.uint8).reshape(len(rows), self.bc_len))
+        self.n = len(rows)
+        self._p = lib().ccsx_cell_whitelist_create(_ptr(codes, C.c_uint8) if codes.size else None, self.n, self.bc_len)
+        if not self._p:
+            raise RuntimeError("ccsx_cell_whitelist_create failed: " + lib().ccsx_last_error().decode())
+
+    @property
+    def table(self) -> np.ndarray:
+        """a copy of the table's uint64 slots"""
+        slots, tab = C.c_uint32(0), C.POINTER(C.c_uint64)()
+        lib().ccsx_cell_whitelist_info(self._p, None, None, C.byref(slots), C.byref(tab))
+        return np.ctypeslib.as_array(tab, (slots.value,)).copy()
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().ccsx_cell_whitelist_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cell_slot(key: int, slots: int) -> int:
+    """ccsx_cell_slot: the first slot of key in a table of `slots` slots"""
+    return int(lib().ccsx_cell_slot(key & 0xffffffff, slots))
+
+
+class CellReport(_PlaneReport):
+    """ccsx_cell_report: the planes of CdnaReport (clip: the primers' own) and per read the eight planes of CELL_PLANES (tag: CELL_NAMES; bc_raw and umi uint32)"""
+    FIELDS = CdnaReport.FIELDS + CELL_PLANES
+    PLANES = CdnaReport.PLANES + tuple((k, np.uint32 if k in _CELL_UNSIGNED else np.int32, ()) for k in CELL_PLANES)
+    CSTRUCT = CCellReport
+
+    def c_struct(self) -> CCellReport:
+        r = CCellReport()
+        r.cdna.n_zmw = len(self.tested)
+        for k in CdnaReport.FIELDS:
+            setattr(r.cdna, k, _ptr(getattr(self, k), C.c_int32))
+        for k in CELL_PLANES:
+            setattr(r, k, _ptr(getattr(self, k), C.c_uint32 if k in _CELL_UNSIGNED else C.c_int32))
+        return r
+
+    def fields(self, z: int) -> dict:
+        return {k: getattr(self, k)[z].tolist() for k in self.FIELDS}
+
+
+def _cell_reads_args(primers, opts, design, whitelist, reads, report):
+    """the arguments of ccsx_cell_reads[_host] for a list of code arrays: (args, report, keep)"""
+    (pset, o, seq, off, ln, n, crep), rep, keep = _reads_args(CellReport, primers, opts if opts is not None else cdna_opts_default(), reads, report)
+    d = design if design is not None else CellDesign.default()
+    return (pset, o, C.byref(d), whitelist._p if whitelist is not None else None, seq, off, ln, n, crep), rep, keep + (d, whitelist)
+
+
+def cell_reads_host(primers: CdnaPrimers, reads, design: "CellDesign | None" = None, whitelist: "CellWhitelist | None" = None, opts: "CdnaOpts | None" = None,
+                    report: "CellReport | None" = None) -> CellReport:
+    """ccsx_cell_reads_host: the cell-tag rule on the calling thread, no device.  reads: a list of arrays of codes 0 .. 3 (an empty one is untested)"""
+    args, rep, _keep = _cell_reads_args(primers, opts, design, whitelist, reads, report)
+    if lib().ccsx_cell_reads_host(*args) != 0:
+        raise RuntimeError("ccsx_cell_reads_host failed: " + lib().ccsx_last_error().decode())
+    return rep
+
+
 # ---- duplicate reads (include/ccsx.h ccsx_dup_*; DESIGN.md §2 "Duplicate rule")
 DUP_MAX_BUCKET, DUP_MAX_READS = 512, 1 << 24
 DUP_UNTESTED, DUP_TESTED, DUP_OVERFLOW = 0, 1, 2
@@ -1370,6 +1470,8 @@ EXPORTS = [
     "ccsx_cdna_opts_default", "ccsx_cdna_rule_version", "ccsx_cdna_reads_host", "ccsx_cdna_reads", "ccsx_consensus_cdna", "ccsx_submit_cdna",
     "ccsx_represent_rule_version", "ccsx_represent_host", "ccsx_consensus_represent", "ccsx_submit_represent",
     "ccsx_dup_opts_default", "ccsx_dup_rule_version", "ccsx_dup_hash", "ccsx_dup_sign_reads_host", "ccsx_dup_sign_reads", "ccsx_dup_cluster_host", "ccsx_dup_cluster",
+    "ccsx_cell_design_default", "ccsx_cell_rule_version", "ccsx_cell_slot", "ccsx_cell_whitelist_create", "ccsx_cell_whitelist_destroy", "ccsx_cell_whitelist_info",
+    "ccsx_cell_reads_host", "ccsx_cell_reads",
 ]
 
 _lib = None
@@ -1531,6 +1633,19 @@ def lib() -> C.CDLL:
         L.ccsx_segment_reads.argtypes = [C.c_void_p] + _sgreads
         L.ccsx_consensus_segments.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CSegmentRequest)]
         L.ccsx_submit_segments.argtypes = [C.c_void_p, C.POINTER(CBatch), C.POINTER(CResults), C.POINTER(CRequests), C.POINTER(CSegmentRequest), C.POINTER(C.c_int64)]
+        L.ccsx_cell_design_default.restype = None
+        L.ccsx_cell_design_default.argtypes = [C.POINTER(CellDesign)]
+        L.ccsx_cell_slot.restype = C.c_uint32
+        L.ccsx_cell_slot.argtypes = [C.c_uint32, C.c_uint32]
+        L.ccsx_cell_whitelist_create.restype = C.c_void_p
+        L.ccsx_cell_whitelist_create.argtypes = [C.POINTER(C.c_uint8), C.c_int32, C.c_int32]
+        L.ccsx_cell_whitelist_destroy.restype = None
+        L.ccsx_cell_whitelist_destroy.argtypes = [C.c_void_p]
+        L.ccsx_cell_whitelist_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint64))]
+        _clreads = [C.POINTER(CdnaPrimers), C.POINTER(CdnaOpts), C.POINTER(CellDesign), C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                    C.c_int32, C.POINTER(CCellReport)]
+        L.ccsx_cell_reads_host.argtypes = _clreads
+        L.ccsx_cell_reads.argtypes = [C.c_void_p] + _clreads
         L.ccsx_cdna_opts_default.restype = None
         L.ccsx_cdna_opts_default.argtypes = [C.POINTER(CdnaOpts)]
         _cdreads = [C.POINTER(CdnaPrimers), C.POINTER(CdnaOpts), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.POINTER(CCdnaReport)]
@@ -2226,6 +2341,15 @@ class Handle:
     def cdna_reads(self, primers: CdnaPrimers, reads, opts: "CdnaOpts | None" = None, report: "CdnaReport | None" = None) -> CdnaReport:
         """ccsx_cdna_reads: k_cdna on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched"""
         return self._reads(CdnaReport, primers, reads, opts, report)
+
+    # ---- cell barcodes and UMIs (ccsx_cell_reads): the cDNA analysis with the two fields behind one primer read, corrected against a whitelist and clipped
+    def cell_reads(self, primers: CdnaPrimers, reads, design: "CellDesign | None" = None, whitelist: "CellWhitelist | None" = None, opts: "CdnaOpts | None" = None,
+                   report: "CellReport | None" = None) -> CellReport:
+        """ccsx_cell_reads: k_cell on the caller's reads, a list of arrays of codes 0 .. 3 (an empty one is untested).  Synchronous; no slot is touched.  The
+        whitelist's table stays on the device until a call brings another one"""
+        args, rep, _keep = _cell_reads_args(primers, opts, design, whitelist, reads, report)
+        self._check(self._L.ccsx_cell_reads(self._h, *args), "ccsx_cell_reads")
+        return rep
 
     # ---- duplicate reads (ccsx_dup_sign_reads / ccsx_dup_cluster): the sets of reads that are the same molecule
     def dup_sign(self, reads, opts: "DupOpts | None" = None) -> np.ndarray:

@@ -122,7 +122,16 @@ struct Options {
     int dup_window = -1, dup_kmer = -1, dup_max_dist_pct = -1, dup_max_len_diff_pct = -1;   // --dup-window ...: overrides of ccsx_dup_opts (-1: the default)
     std::string dup_counts;       // --dup-counts FILE.tsv: sets per set size
     ccsx_dup_opts dup_opts{};     // ... the options of the run
-    std::vector<std::string> seen;   // every option of the command line, as given (--mark-duplicates refuses what it does not take)
+    bool dup_within_cells = false;   // --dup-within-cells: only reads of equal (CB, XM) tags are compared
+    bool cell_reads = false;      // --cell-reads IN.bam OUT.bam: the cell-tag mode (DESIGN.md §2 "Cell-tag rule"): reads in, the full-length cDNA reads out, tagged
+    std::string cell_design_text; // --cell-design STR: the fields in sense-strand order around T (T-12U-16B, 16B-10U-T)
+    std::string cell_whitelist;   // --cell-whitelist FILE: one barcode of bc_len ACGT per line
+    std::string cell_counts;      // --cell-counts FILE.tsv: reads per whitelist index, per tag status and per cDNA class
+    bool cell_no_indels = false, cell_require_barcode = false;   // --cell-no-indels, --cell-require-barcode
+    ccsx_cell_design cell_design{};   // ... the design, the whitelist's barcodes as read (CB is written from them) and the object made of them
+    std::vector<uint8_t> cell_codes;
+    std::shared_ptr<ccsx_cell_whitelist> cell_wl;
+    std::vector<std::string> seen;   // every option of the command line, as given (--mark-duplicates and --cell-reads refuse what they do not take)
 };
 
 enum HdMode { HD_OFF = 0, HD_SPLIT = 1, HD_DROP = 2 };
@@ -342,11 +351,26 @@ void usage()
                  "                            --chunk or input from stdin: usage errors\n"
                  "      --dup-remove          leave the duplicates out of OUT instead of marking them\n"
                  "      --dup-within-barcodes only reads with equal bc tags are compared\n"
+                 "      --dup-within-cells    only reads with equal CB and XM tags (cell barcode and UMI, as --cell-reads writes them) are compared; a read that\n"
+                 "                            lacks either is compared with its like.  Not with --dup-within-barcodes\n"
                  "      --dup-window W        bases of each end that are compared, 16 .. 64 [32]\n"
                  "      --dup-kmer K          the minimizer's k, 8 .. 16 [12]\n"
                  "      --dup-max-dist-pct P  two end windows agree within floor(W * P / 100) edits, 0 .. 30 [10]\n"
                  "      --dup-max-len-diff-pct P  two reads agree in length within P percent of the shorter, 0 .. 20 [2]\n"
                  "      --dup-counts F.tsv    sets per set size\n"
+                 "cell barcodes and UMIs (ccs --cell-reads IN.bam OUT.bam; one GPU; IN: an unaligned BAM of reads, HiFi reads or segments):\n"
+                 "      --cell-reads          read the UMI and the cell barcode behind one cDNA primer of every read of IN, on the GPU (DESIGN.md, Cell-tag rule), and\n"
+                 "                            write the full-length cDNA reads to OUT: the input record with SEQ, QUAL and every per-base B tag cut to the slice\n"
+                 "                            without primers, fields and poly(A) tail (ri / rp from the other end), every other tag as it is, and the tags ts:A, pa:i,\n"
+                 "                            pr:B:C, pq:i of --cdna-primers, XM:Z (the UMI), XC:Z (the barcode as read) and, for a barcode of the whitelist, exact or\n"
+                 "                            corrected, CB:Z.  No OUT.bam.pbi is written.  Needs --cdna-primers and --cell-design; takes --cdna-min-polya,\n"
+                 "                            --cdna-min-length, -j, --gpus with one device, --log-level, --log-file and --report-file; everything else: usage errors\n"
+                 "      --cell-design STR     the fields in sense-strand order around the transcript T, each a length 1-16 and U (UMI) or B (barcode): T-12U-16B has\n"
+                 "                            them at the 3' primer, the barcode next to it; 16B-10U-T at the 5' primer.  At most one U and one B, on one side of T\n"
+                 "      --cell-whitelist F    the known barcodes, plain text, one of exactly the design's length per line, ACGT in either case (not compressed)\n"
+                 "      --cell-no-indels      correct substitutions only [a lost or a gained base is corrected as well]\n"
+                 "      --cell-require-barcode  write only reads whose barcode is in the whitelist, exact or corrected\n"
+                 "      --cell-counts F.tsv   the reads written per whitelist index, sorted by index, then the reads of IN per tag status and per cDNA class\n"
                  "model training (ccs --fit-model OUT.json IN.subreads.bam; one GPU, no HiFi output):\n"
                  "      --fit-model OUT.json  fit the Arrow parameter set to the subreads of IN by EM and write it as a ccsx-1 json with the header's chemistry\n"
                  "                            triple: per iteration every batch is drafted and polished, the passes are measured against the polished reads of at\n"
@@ -467,6 +491,71 @@ bool load_control(const std::string &path, std::vector<uint8_t> &codes, std::str
     return true;
 }
 
+// --cell-design: the fields in sense-strand order around T.  T first: the fields stand between the transcript and the 3' primer, the last one next to the primer;
+// T last: between the 5' primer and the transcript, the first one next to the primer
+bool parse_cell_design(const std::string &text, ccsx_cell_design &d, std::string &err)
+{
+    ccsx_cell_design_default(&d);
+    d.umi_len = 0; d.bc_len = 0;
+    std::vector<std::string> tok(1);
+    for (char c : text) { if (c == '-') tok.emplace_back(); else tok.back().push_back(c); }
+    size_t n_t = 0;
+    for (const std::string &t : tok) n_t += t == "T";
+    if (n_t != 1) { err = "the design names the transcript T once"; return false; }
+    if (tok.size() < 2) { err = "the design has no field"; return false; }
+    if (tok.front() != "T" && tok.back() != "T") { err = "fields on both sides of T are not supported"; return false; }
+    d.side = tok.front() == "T" ? 1 : 0;
+    char next_to_primer = 0;
+    for (size_t k = 0; k < tok.size(); ++k) {
+        const std::string &t = tok[k];
+        if (t == "T") continue;
+        const char kind = t.empty() ? 0 : t.back();
+        char *end = nullptr;
+        const long n = std::strtol(t.c_str(), &end, 10);
+        if ((kind != 'U' && kind != 'B') || end != t.c_str() + t.size() - 1 || end == t.c_str() || n < 1 || n > CCSX_CELL_MAX_FIELD) {
+            err = "field '" + t + "' is not a length 1 .. 16 and U or B"; return false;
+        }
+        int32_t &len = kind == 'U' ? d.umi_len : d.bc_len;
+        if (len) { err = std::string("more than one ") + kind + " field"; return false; }
+        len = (int32_t)n;
+        if (d.side ? k + 1 == tok.size() : k == 0) next_to_primer = kind;
+    }
+    d.bc_first = next_to_primer == 'B';
+    return true;
+}
+
+// --cell-whitelist: plain text, one barcode of exactly bc_len ACGT (either case) per line; blank lines are ignored; anything else names its line
+bool load_cell_whitelist(const std::string &path, int bc_len, std::vector<uint8_t> &codes, std::string &err)
+{
+    if (bc_len < 1) { err = "the design has no barcode field"; return false; }
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) { err = "cannot read the file"; return false; }
+    std::string line;
+    size_t lineno = 0, n = 0;
+    bool ok = true, more = true;
+    while (ok && more) {
+        line.clear();
+        int c;
+        while ((c = std::fgetc(f)) != EOF && c != '\n') line.push_back((char)c);
+        more = c != EOF;
+        ++lineno;
+        if (lineno == 1 && line.size() >= 2 && (uint8_t)line[0] == 0x1f && (uint8_t)line[1] == 0x8b) { err = "line 1: compressed files are not read"; ok = false; break; }
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        if ((int)line.size() != bc_len) { err = "line " + std::to_string(lineno) + ": not a barcode of " + std::to_string(bc_len) + " bases"; ok = false; break; }
+        for (char ch : line) {
+            static const char bases[] = "ACGTacgt";
+            const char *at = ch ? std::strchr(bases, ch) : nullptr;
+            if (!at) { err = "line " + std::to_string(lineno) + ": not ACGT"; ok = false; break; }
+            codes.push_back((uint8_t)((at - bases) & 3));
+        }
+        if (ok && ++n > (size_t)CCSX_CELL_MAX_WHITELIST) { err = "line " + std::to_string(lineno) + ": more than 2^23 barcodes"; ok = false; }
+    }
+    std::fclose(f);
+    if (ok && !n) { err = "the file holds no barcode"; ok = false; }
+    return ok;
+}
+
 bool parse(int argc, char **argv, Options &o)
 {
     ccsx_opts_default(&o.o);
@@ -557,6 +646,13 @@ bool parse(int argc, char **argv, Options &o)
         else if (a == "--mark-duplicates") o.mark_duplicates = true;
         else if (a == "--dup-remove") o.dup_remove = true;
         else if (a == "--dup-within-barcodes") o.dup_within_barcodes = true;
+        else if (a == "--dup-within-cells") o.dup_within_cells = true;
+        else if (a == "--cell-reads") o.cell_reads = true;
+        else if (a == "--cell-design") o.cell_design_text = need(a.c_str());
+        else if (a == "--cell-whitelist") o.cell_whitelist = need(a.c_str());
+        else if (a == "--cell-counts") o.cell_counts = need(a.c_str());
+        else if (a == "--cell-no-indels") o.cell_no_indels = true;
+        else if (a == "--cell-require-barcode") o.cell_require_barcode = true;
         else if (a == "--dup-window") o.dup_window = need_int(16, 64, "a number in 16 .. 64");
         else if (a == "--dup-kmer") o.dup_kmer = need_int(8, 16, "a number in 8 .. 16");
         else if (a == "--dup-max-dist-pct") o.dup_max_dist_pct = need_int(0, 30, "a number in 0 .. 30");
@@ -577,14 +673,43 @@ bool parse(int argc, char **argv, Options &o)
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return false; }
         else pos.push_back(a);
     }
-    if (dash && !o.mark_duplicates) { std::fprintf(stderr, "unknown option -\n"); return false; }
-    if (!o.mark_duplicates && (o.dup_remove || o.dup_within_barcodes || o.dup_window >= 0 || o.dup_kmer >= 0 || o.dup_max_dist_pct >= 0 ||
+    if (dash && !o.mark_duplicates && !o.cell_reads) { std::fprintf(stderr, "unknown option -\n"); return false; }
+    if (!o.cell_reads && (!o.cell_design_text.empty() || !o.cell_whitelist.empty() || !o.cell_counts.empty() || o.cell_no_indels || o.cell_require_barcode)) {
+        std::fprintf(stderr, "ccs: the --cell-* options need --cell-reads\n"); std::exit(2);
+    }
+    if (o.cell_reads) {                                      // a mode of its own, as --mark-duplicates: what it does not take is refused by name, before any input is opened
+        static const char *const takes[] = {"--cell-reads", "--cell-design", "--cell-whitelist", "--cell-counts", "--cell-no-indels", "--cell-require-barcode",
+                                            "--cdna-primers", "--cdna-min-polya", "--cdna-min-length", "-j", "--num-threads", "--gpus", "--log-level", "--log-file",
+                                            "--report-file"};
+        for (const std::string &a : o.seen) {
+            bool ok = false;
+            for (const char *t : takes) ok = ok || a == t;
+            if (!ok) { std::fprintf(stderr, "ccs: --cell-reads combined with %s is not supported\n", a.c_str()); std::exit(2); }
+        }
+        if (dash) { std::fprintf(stderr, "ccs: --cell-reads: input from stdin (-) is not supported\n"); std::exit(2); }
+        if (o.all_gpus || o.gpus.size() > 1) { std::fprintf(stderr, "ccs: --cell-reads runs on one GPU: --gpus with more than one device is not supported\n"); std::exit(2); }
+        if (pos.size() != 2) { std::fprintf(stderr, "ccs: --cell-reads takes two positionals, IN.bam and OUT.bam\n"); std::exit(2); }
+        if (o.cdna_primers.empty() || o.cell_design_text.empty()) { std::fprintf(stderr, "ccs: --cell-reads needs --cdna-primers and --cell-design\n"); std::exit(2); }
+        std::string err;
+        if (!parse_cell_design(o.cell_design_text, o.cell_design, err)) { std::fprintf(stderr, "ccs: --cell-design %s: %s\n", o.cell_design_text.c_str(), err.c_str()); std::exit(2); }
+        if (o.cell_no_indels) o.cell_design.indels = 0;
+        if (!o.cell_whitelist.empty()) {
+            if (!load_cell_whitelist(o.cell_whitelist, o.cell_design.bc_len, o.cell_codes, err)) {
+                std::fprintf(stderr, "ccs: --cell-whitelist %s: %s\n", o.cell_whitelist.c_str(), err.c_str()); std::exit(2);
+            }
+            o.cell_wl.reset(ccsx_cell_whitelist_create(o.cell_codes.data(), (int32_t)(o.cell_codes.size() / (size_t)o.cell_design.bc_len), o.cell_design.bc_len),
+                            ccsx_cell_whitelist_destroy);
+            if (!o.cell_wl) { std::fprintf(stderr, "ccs: --cell-whitelist %s: %s\n", o.cell_whitelist.c_str(), ccsx_last_error()); std::exit(2); }
+        }
+        if (o.cell_require_barcode && !o.cell_wl) { std::fprintf(stderr, "ccs: --cell-require-barcode needs --cell-whitelist\n"); std::exit(2); }
+    }
+    if (!o.mark_duplicates && (o.dup_remove || o.dup_within_barcodes || o.dup_within_cells || o.dup_window >= 0 || o.dup_kmer >= 0 || o.dup_max_dist_pct >= 0 ||
                                o.dup_max_len_diff_pct >= 0 || !o.dup_counts.empty())) {
         std::fprintf(stderr, "ccs: the --dup-* options need --mark-duplicates\n"); std::exit(2);
     }
     if (o.mark_duplicates) {                                 // a mode of its own: reads in, the same reads out.  It takes its own options, the threads, one device, the
         // log and the report file; every option of the consensus side is refused by name, before any input is opened
-        static const char *const takes[] = {"--mark-duplicates", "--dup-remove", "--dup-within-barcodes", "--dup-window", "--dup-kmer", "--dup-max-dist-pct",
+        static const char *const takes[] = {"--mark-duplicates", "--dup-remove", "--dup-within-barcodes", "--dup-within-cells", "--dup-window", "--dup-kmer", "--dup-max-dist-pct",
                                             "--dup-max-len-diff-pct", "--dup-counts", "-j", "--num-threads", "--gpus", "--log-level", "--log-file", "--report-file"};
         for (const std::string &a : o.seen) {
             bool ok = false;
@@ -592,6 +717,7 @@ bool parse(int argc, char **argv, Options &o)
             if (!ok) { std::fprintf(stderr, "ccs: --mark-duplicates combined with %s is not supported\n", a.c_str()); std::exit(2); }
         }
         if (dash) { std::fprintf(stderr, "ccs: --mark-duplicates reads IN twice: input from stdin (-) is not supported\n"); std::exit(2); }
+        if (o.dup_within_cells && o.dup_within_barcodes) { std::fprintf(stderr, "ccs: --dup-within-cells combined with --dup-within-barcodes is not supported\n"); std::exit(2); }
         if (o.all_gpus || o.gpus.size() > 1) { std::fprintf(stderr, "ccs: --mark-duplicates runs on one GPU: --gpus with more than one device is not supported\n"); std::exit(2); }
         if (pos.size() != 2) { std::fprintf(stderr, "ccs: --mark-duplicates takes two positionals, IN.bam and OUT.bam\n"); std::exit(2); }
         ccsx_dup_opts_default(&o.dup_opts);
@@ -601,7 +727,7 @@ bool parse(int argc, char **argv, Options &o)
         if (o.dup_max_len_diff_pct >= 0) o.dup_opts.max_len_diff_pct = o.dup_max_len_diff_pct;
         if (o.dup_opts.kmer > o.dup_opts.window) { std::fprintf(stderr, "ccs: --dup-kmer %d is above --dup-window %d\n", o.dup_opts.kmer, o.dup_opts.window); std::exit(2); }
     }
-    if (!o.cdna_primers.empty()) {                           // its own output mode: refused before any input is opened
+    if (!o.cdna_primers.empty() && !o.cell_reads) {          // its own output mode: refused before any input is opened
         auto refuse = [](const char *what) { std::fprintf(stderr, "ccs: --cdna-primers combined with %s is not supported\n", what); std::exit(2); };
         if (o.by_strand) refuse("--by-strand");
         if (!o.barcodes.empty()) refuse("--barcodes");
@@ -1498,7 +1624,7 @@ static int fit_model(const Options &opt, ccsx_handle &h0, const ccsx_model &star
 // the tag), a group (0, or the bc pair under --dup-within-barcodes) and the name, of which only the representatives' outlive the clustering.  One
 // ccsx_dup_cluster call makes the sets.  Pass 2 reads IN again and writes every record through byte for byte; a member of a set of two or more gains ds:i (the
 // set's size), a duplicate also FLAG 0x400 and du:Z (the representative's name) — or is left out under --dup-remove.  No .pbi is written for OUT.
-struct DupTags { bool has_rq = false, has_bc = false, marked = false; float rq = 0.0f; uint32_t bc[2] = {0, 0}; };
+struct DupTags { bool has_rq = false, has_bc = false, marked = false, has_cb = false, has_xm = false; float rq = 0.0f; uint32_t bc[2] = {0, 0}; std::string cb, xm; };
 // the rq, bc, ds and du tags of a record body that parse_subread has accepted (every length in it has been checked there)
 static DupTags dup_scan_tags(const uint8_t *p, uint32_t bs)
 {
@@ -1509,7 +1635,13 @@ static DupTags dup_scan_tags(const uint8_t *p, uint32_t bs)
         const char t0 = (char)t[0], t1 = (char)t[1], ty = (char)t[2];
         t += 3;
         if ((t0 == 'd' && t1 == 's') || (t0 == 'd' && t1 == 'u')) g.marked = true;
-        if (ty == 'Z' || ty == 'H') { while (t < end && *t) ++t; ++t; continue; }
+        if (ty == 'Z' || ty == 'H') {
+            const uint8_t *v = t;
+            while (t < end && *t) ++t;
+            if (ty == 'Z' && t0 == 'C' && t1 == 'B') { g.has_cb = true; g.cb.assign((const char *)v, (size_t)(t - v)); }
+            if (ty == 'Z' && t0 == 'X' && t1 == 'M') { g.has_xm = true; g.xm.assign((const char *)v, (size_t)(t - v)); }
+            ++t; continue;
+        }
         if (ty == 'B') {
             const char st = (char)t[0];
             const uint32_t n = rd32(t + 1);
@@ -1544,6 +1676,7 @@ static int mark_duplicates(const Options &opt, ThreadPool &pool)
     std::vector<ccsx_dup_sig> sig;
     std::vector<int32_t> score, group;
     std::vector<std::string> names;
+    std::map<std::pair<std::string, std::string>, int32_t> cells;   // --dup-within-cells: the dense id, from 1, of every (CB, XM) pair seen
     std::string header_text;
     {
         BgzfReader in(opt.in, pool);
@@ -1575,7 +1708,9 @@ static int mark_duplicates(const Options &opt, ThreadPool &pool)
                 if (g.has_bc && g.bc[0] >= 32767u && opt.dup_within_barcodes) return failed("read " + r.name + ": a bc index above 32766");
                 const double sc = g.has_rq && g.rq == g.rq ? std::floor((double)g.rq * 1e6) : 0.0;
                 score.push_back((int32_t)std::min(2147483647.0, std::max(-2147483648.0, sc)));
-                group.push_back(opt.dup_within_barcodes && g.has_bc ? (int32_t)(1 + g.bc[0] * 65536u + g.bc[1]) : 0);
+                int32_t grp = opt.dup_within_barcodes && g.has_bc ? (int32_t)(1 + g.bc[0] * 65536u + g.bc[1]) : 0;
+                if (opt.dup_within_cells && g.has_cb && g.has_xm) grp = cells.emplace(std::make_pair(g.cb, g.xm), (int32_t)cells.size() + 1).first->second;
+                group.push_back(grp);
                 names.push_back(r.name);
                 off.push_back((int64_t)seq.size()); len.push_back((int32_t)r.len);
                 seq.resize(seq.size() + r.len);
@@ -1648,7 +1783,7 @@ static int mark_duplicates(const Options &opt, ThreadPool &pool)
         FILE *f = std::fopen(opt.report.c_str(), "w");
         if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", opt.report.c_str()); return 1; }
         std::fprintf(f, "Duplicate marking (rule %d: window %d, kmer %d, max_dist_pct %d, max_len_diff_pct %d%s)\n", ccsx_dup_rule_version(), D.window, D.kmer,
-                     D.max_dist_pct, D.max_len_diff_pct, opt.dup_within_barcodes ? ", within barcodes" : "");
+                     D.max_dist_pct, D.max_len_diff_pct, opt.dup_within_barcodes ? ", within barcodes" : opt.dup_within_cells ? ", within cells" : "");
         std::fprintf(f, "Reads input                 : %lld\n", (long long)n);
         std::fprintf(f, "Reads tested                : %lld\n", (long long)tested);
         std::fprintf(f, "Reads untested              : %lld\n", (long long)untested);
@@ -1673,6 +1808,204 @@ static int mark_duplicates(const Options &opt, ThreadPool &pool)
     return 0;
 }
 
+// ---- ccs --cell-reads IN.bam OUT.bam (DESIGN.md §2 "Cell-tag rule", §7): the reads of an unaligned BAM in, the full-length cDNA reads out.  One pass: the
+// records are streamed in batches of at most kBatchReads reads or kBatchBases bases (the chunks that hold a batch's records stay until it is written), every batch
+// is one ccsx_cell_reads call, and a FULL_LENGTH read is written as its input record cut to the slice, with the tags the rule gives.  No .pbi is written for OUT.
+static std::string cell_field_text(uint32_t x, int n)
+{
+    std::string s((size_t)n, 'A');
+    for (int j = 0; j < n; ++j) s[(size_t)j] = "ACGT"[(x >> (2 * (n - 1 - j))) & 3u];
+    return s;
+}
+
+// a record body that parse_subread has accepted carries an XM, XC or CB tag
+static bool cell_is_tagged(const uint8_t *p, uint32_t bs)
+{
+    const uint32_t l_name = p[8], n_cig = p[12] | (p[13] << 8), l_seq = rd32(p + 16);
+    const uint8_t *t = p + 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq, *end = p + bs;
+    while (t + 3 <= end) {
+        const char t0 = (char)t[0], t1 = (char)t[1], ty = (char)t[2];
+        if ((t0 == 'X' && (t1 == 'M' || t1 == 'C')) || (t0 == 'C' && t1 == 'B')) return true;
+        t += 3;
+        if (ty == 'Z' || ty == 'H') { while (t < end && *t) ++t; ++t; continue; }
+        if (ty == 'B') { t += 5 + (size_t)rd32(t + 1) * tag_value_size((char)t[0]); continue; }
+        t += tag_value_size(ty);
+    }
+    return false;
+}
+
+// the body of such a record with SEQ and QUAL cut to [from, to), every B tag of l_seq elements cut the same way (ri and rp, which run from the read's other end,
+// to [l_seq - to, l_seq - from)) and every other tag byte for byte; the caller appends its tags
+static void cell_cut_record(std::vector<uint8_t> &b, const uint8_t *p, uint32_t bs, uint32_t from, uint32_t to)
+{
+    const uint32_t l_name = p[8], n_cig = p[12] | (p[13] << 8), L = rd32(p + 16), n = to - from;
+    const uint8_t *seq = p + 32 + l_name + 4 * n_cig, *qual = seq + (L + 1) / 2, *t = qual + L, *end = p + bs;
+    auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) b.push_back((uint8_t)(v >> (8 * i))); };
+    auto nib = [&](uint32_t i) { return (uint8_t)((seq[i >> 1] >> ((i & 1) ? 0 : 4)) & 15); };
+    b.assign(p, seq);
+    for (int i = 0; i < 4; ++i) b[16 + (size_t)i] = (uint8_t)(n >> (8 * i));
+    for (uint32_t i = 0; i < n; i += 2) b.push_back((uint8_t)((nib(from + i) << 4) | (i + 1 < n ? nib(from + i + 1) : 0)));
+    b.insert(b.end(), qual + from, qual + to);
+    while (t + 3 <= end) {
+        const uint8_t *tag = t;
+        const char t0 = (char)t[0], t1 = (char)t[1], ty = (char)t[2];
+        t += 3;
+        if (ty == 'Z' || ty == 'H') { while (t < end && *t) ++t; ++t; b.insert(b.end(), tag, t); continue; }
+        if (ty == 'B') {
+            const char st = (char)t[0];
+            const uint32_t cnt = rd32(t + 1);
+            const size_t es = tag_value_size(st);
+            const uint8_t *q = t + 5;
+            t = q + (size_t)cnt * es;
+            if (cnt != L) { b.insert(b.end(), tag, t); continue; }
+            const bool rev = t0 == 'r' && (t1 == 'i' || t1 == 'p');
+            const uint32_t lo = rev ? L - to : from;
+            b.insert(b.end(), tag, tag + 4);
+            put32(n);
+            b.insert(b.end(), q + (size_t)lo * es, q + (size_t)(lo + n) * es);
+            continue;
+        }
+        t += tag_value_size(ty);
+        b.insert(b.end(), tag, t);
+    }
+}
+
+static int cell_reads(const Options &opt, ThreadPool &pool)
+{
+    auto failed = [](const std::string &what) { std::fprintf(stderr, "ccs: --cell-reads: %s\n", what.c_str()); return 1; };
+    if (ccsx_device_count() <= 0) { std::fprintf(stderr, "ccs: no gfx950 GPU available (this build has no CPU path for the cell-tag rule)\n"); return 1; }
+    ccsx_model model; ccsx_model_default(&model);
+    ccsx_opts eo; ccsx_opts_default(&eo);
+    ccsx_handle h = nullptr;
+    if (ccsx_create(opt.gpus.empty() ? 0 : opt.gpus[0], &model, &eo, &h)) { std::fprintf(stderr, "ccs: %s\n", ccsx_last_error()); return 1; }
+    struct Closer { ccsx_handle h; ~Closer() { ccsx_destroy(h); } } closer{h};
+    const ccsx_cell_design &D = opt.cell_design;
+    const ccsx_cdna_set &P = *opt.cdna_set;
+    typedef std::chrono::steady_clock Clock;                         // (the phases' wall clock, one line at --log-level INFO: tools/cell_bench.py reads it)
+    auto seconds = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const Clock::time_point t_start = Clock::now();
+    double call_s = 0.0, write_s = 0.0;
+    static const char *const cls_names[7] = {"NO_PRIMER", "ONE_END", "SAME_ROLE", "SHORT", "CONCATEMER", "NO_TAIL", "FULL_LENGTH"};
+    static const char *const tag_names[6] = {"NONE", "RAW", "EXACT", "CORRECTED", "AMBIGUOUS", "ABSENT"};
+    int64_t n_in = 0, written = 0, unlisted = 0, cls_n[7] = {0, 0, 0, 0, 0, 0, 0}, tag_n[6] = {0, 0, 0, 0, 0, 0};
+    std::map<int32_t, int64_t> per_bc;
+
+    constexpr size_t kBatchReads = 16384, kBatchBases = (size_t)64 << 20;
+    BgzfReader in(opt.in, pool);
+    BamHeader hdr; read_header(in, hdr);
+    if (!hdr.refs.empty()) return failed("IN has reference sequences: aligned input is not supported");
+    BgzfWriter out(opt.out, pool);
+    write_header(out, hdr.text);
+    std::vector<std::shared_ptr<RawChunk>> held;
+    std::vector<std::pair<const uint8_t *, uint32_t>> recs;
+    std::vector<uint8_t> seq, b;
+    std::vector<int64_t> off;
+    std::vector<int32_t> len, planes;
+    auto flush = [&]() -> bool {
+        const size_t n = len.size();
+        if (n) {
+            planes.assign(n * 24, 0);
+            int32_t *q = planes.data();
+            ccsx_cell_report rep{};
+            rep.cdna = ccsx_cdna_report{(int32_t)n, q, q + n, q + 2 * n, q + 3 * n, q + 4 * n, q + 5 * n, q + 6 * n, q + 7 * n, q + 8 * n, q + 10 * n, q + 12 * n, q + 14 * n};
+            q += 16 * n;
+            rep.tag = q; rep.bc_raw = (uint32_t *)(q + n); rep.bc = q + 2 * n; rep.bc_hi = q + 3 * n; rep.kind = q + 4 * n; rep.shift = q + 5 * n;
+            rep.umi = (uint32_t *)(q + 6 * n); rep.tag_clip = q + 7 * n;
+            seq.push_back(0);                                        // (never empty: the call wants a pointer)
+            const Clock::time_point t0 = Clock::now();
+            const int rc = ccsx_cell_reads(h, &P, &opt.cdna_opts, &D, opt.cell_wl.get(), seq.data(), off.data(), len.data(), (int32_t)n, &rep);
+            const Clock::time_point t1 = Clock::now();
+            call_s += seconds(t0, t1);
+            if (rc) return false;
+            const ccsx_cdna_report &d = rep.cdna;
+            for (size_t z = 0; z < n; ++z) {
+                ++cls_n[d.cls[z]]; ++tag_n[rep.tag[z]];
+                if (d.cls[z] != CCSX_CDNA_FULL_LENGTH) continue;
+                const bool listed = rep.tag[z] == CCSX_CELL_EXACT || rep.tag[z] == CCSX_CELL_CORRECTED;
+                if (opt.cell_require_barcode && !listed) { ++unlisted; continue; }
+                cell_cut_record(b, recs[z].first, recs[z].second, (uint32_t)d.start[z], (uint32_t)d.end[z]);
+                RecordBuilder rb;                                    // (the tags alone: ts, pa, pr and pq as --cdna-primers writes them)
+                const int st = d.strand[z];
+                const uint8_t pr[2] = {(uint8_t)d.idx[2 * z + st], (uint8_t)d.idx[2 * z + 1 - st]};
+                int pq = 100;
+                for (int e = 0; e < 2; ++e) { const int m = P.len[d.idx[2 * z + e]]; pq = std::min(pq, 100 * (m - d.dist[2 * z + e]) / m); }
+                rb.tagA("ts", st ? '-' : '+'); rb.tagi("pa", d.polya_len[z]); rb.tagBC("pr", pr, 2); rb.tagi("pq", pq);
+                if (D.umi_len > 0) rb.tagZ("XM", cell_field_text(rep.umi[z], D.umi_len));
+                if (D.bc_len > 0) rb.tagZ("XC", cell_field_text(rep.bc_raw[z], D.bc_len));
+                if (listed) {
+                    const uint8_t *w = opt.cell_codes.data() + (size_t)rep.bc[z] * (size_t)D.bc_len;
+                    std::string cb((size_t)D.bc_len, 'A');
+                    for (int j = 0; j < D.bc_len; ++j) cb[(size_t)j] = "ACGT"[w[j] & 3];
+                    rb.tagZ("CB", cb);
+                    ++per_bc[rep.bc[z]];
+                }
+                b.insert(b.end(), rb.b.begin(), rb.b.end());
+                uint8_t b4[4];
+                for (int i = 0; i < 4; ++i) b4[i] = (uint8_t)((uint32_t)b.size() >> (8 * i));
+                out.write(b4, 4); out.write(b.data(), b.size());
+                ++written;
+            }
+            write_s += seconds(t1, Clock::now());
+        }
+        seq.clear(); off.clear(); len.clear(); recs.clear(); held.clear();
+        return true;
+    };
+    auto chunk = std::make_shared<RawChunk>();
+    Subread r;
+    while (read_raw_chunk(in, *chunk)) {
+        held.push_back(chunk);
+        for (const auto &rec : chunk->recs) {
+            parse_subread(rec.first, rec.second, r);
+            if (cell_is_tagged(rec.first, rec.second)) return failed("read " + r.name + " already carries an XM, XC or CB tag: IN has been through --cell-reads before");
+            ++n_in;
+            recs.push_back(rec);
+            off.push_back((int64_t)seq.size()); len.push_back((int32_t)r.len);
+            seq.resize(seq.size() + r.len);
+            if (r.len) r.decode_bases(seq.data() + seq.size() - r.len);
+            if (len.size() >= kBatchReads || seq.size() >= kBatchBases) {
+                // (the records of this chunk that follow belong to the next batch: the chunk is held again)
+                if (!flush()) return failed(ccsx_last_error());
+                held.push_back(chunk);
+            }
+        }
+        chunk = std::make_shared<RawChunk>();
+    }
+    if (!flush()) return failed(ccsx_last_error());
+    out.close();
+    const Clock::time_point t_end = Clock::now();
+
+    const std::string listed_text = opt.cell_wl ? std::to_string(opt.cell_codes.size() / (size_t)D.bc_len) + " barcodes" : std::string("no whitelist");
+    if (!opt.report.empty()) {
+        FILE *f = std::fopen(opt.report.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", opt.report.c_str()); return 1; }
+        std::fprintf(f, "Cell reads (rule %d: design %s, %s, indels %s; cDNA rule %d: min_polya %d, min_len %d)\n", ccsx_cell_rule_version(), opt.cell_design_text.c_str(),
+                     listed_text.c_str(), D.indels ? "on" : "off", ccsx_cdna_rule_version(), opt.cdna_opts.min_polya, opt.cdna_opts.min_len);
+        std::fprintf(f, "Reads input                 : %lld\n", (long long)n_in);
+        for (int k = 0; k < 7; ++k) std::fprintf(f, "Class %-22s: %lld\n", cls_names[k], (long long)cls_n[k]);
+        for (int k = 0; k < 6; ++k) std::fprintf(f, "Tag %-24s: %lld\n", tag_names[k], (long long)tag_n[k]);
+        std::fprintf(f, "Full-length, no barcode     : %lld\n", (long long)unlisted);
+        std::fprintf(f, "Reads written               : %lld\n", (long long)written);
+        std::fclose(f);
+    }
+    if (!opt.cell_counts.empty()) {
+        FILE *f = std::fopen(opt.cell_counts.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "ccs: cannot write %s\n", opt.cell_counts.c_str()); return 1; }
+        std::fprintf(f, "index\tbarcode\treads\n");
+        for (const auto &kv : per_bc) {
+            std::string cb((size_t)D.bc_len, 'A');
+            for (int j = 0; j < D.bc_len; ++j) cb[(size_t)j] = "ACGT"[opt.cell_codes[(size_t)kv.first * (size_t)D.bc_len + (size_t)j] & 3];
+            std::fprintf(f, "%d\t%s\t%lld\n", kv.first, cb.c_str(), (long long)kv.second);
+        }
+        for (int k = 0; k < 6; ++k) std::fprintf(f, "tag\t%s\t%lld\n", tag_names[k], (long long)tag_n[k]);
+        for (int k = 0; k < 7; ++k) std::fprintf(f, "class\t%s\t%lld\n", cls_names[k], (long long)cls_n[k]);
+        std::fclose(f);
+    }
+    if (opt.log_level >= 2)
+        std::fprintf(stderr, "ccs: --cell-reads: %lld reads, %lld written; %.3f s (of which ccsx_cell_reads %.3f s, cutting and writing %.3f s, the rest inflate, parsing "
+                             "and base decoding)\n", (long long)n_in, (long long)written, seconds(t_start, t_end), call_s, write_s);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     Options opt;
@@ -1687,6 +2020,7 @@ int main(int argc, char **argv)
         ThreadPool pool(nthreads);
         if (!opt.write_synth.empty()) return write_synthetic(opt, pool);
         if (opt.mark_duplicates) return mark_duplicates(opt, pool);
+        if (opt.cell_reads) return cell_reads(opt, pool);
 
         // ---- --gpu-inflate: a free list of inflaters (declared before the reader, whose slab jobs use them)
         GpuInflaters gpu_inflaters;

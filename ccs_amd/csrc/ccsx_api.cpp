@@ -191,8 +191,10 @@ struct ccsx_handle_s {
     ccsx_opts opts;
     DevBuf d_model, d_poa, d_align;   // shared by all slots
     DevBuf d_hd_lf;                   // log-factorial table of the heteroduplex finder (built at its first use)
-    DevBuf d_reads;                   // ccsx_barcode_reads / ccsx_segment_reads / ccsx_cdna_reads only: the call's set, report and reads (no slot is touched; the call ends synchronised)
+    DevBuf d_reads;                   // ccsx_barcode_reads / ccsx_segment_reads / ccsx_cdna_reads / ccsx_cell_reads only: the call's set, report and reads (no slot is touched; the call ends synchronised)
     DevBuf d_dup;                     // ccsx_dup_sign_reads / ccsx_dup_cluster only: the call's reads and signatures, or its signatures, keys, sort scratch and report
+    DevBuf d_cell_wl;                 // ccsx_cell_reads only: the resident copy of a whitelist's table (DESIGN.md §2 "Cell-tag rule") ...
+    uint64_t cell_wl_serial = 0;      // ... and whose it is (0: nobody's); a call that brings another whitelist uploads it
     DevBuf d_orient;                  // k_orient's tables, shared by all slots like the POA scratch (reserved by the first batch that carries CCSX_PASS_STRAND_UNKNOWN)
     ccsx_orient_opts orient_opts;     // ccsx_set_orient_opts: the options of the batches staged from now on
     Slot slot[CCSX_SLOTS];
@@ -2100,6 +2102,58 @@ static int dup_sign_enqueue(ccsx_handle h, const ccsx_dup_opts &o, const uint8_t
     (void)hipGetLastError();
     if (const char *failed = ccsx_dup_sign_launch(S, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
     HIPTRY(hipMemcpyAsync(sig, S.sig, (size_t)n * sizeof(ccsx_dup_sig), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// k_cell on the caller's reads: ccsx_cdna_reads' path (the handle's d_reads on the polish stream, no slot touched) with the design and the whitelist's table, whose
+// device copy stays resident between calls.  Layout of d_reads as reads_enqueue's, the report being ccsx_cl_rep_bytes
+static int cell_enqueue(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_cdna_opts &o, const ccsx_cell_design &d, const ccsx_cell_whitelist *wl, const uint8_t *seq,
+                        const int64_t *seq_off, const int32_t *seq_len, int32_t n, int64_t bytes, const ccsx_cell_report *report, hipStream_t st)
+{
+    const std::vector<unsigned long long> packed = reads_pack<Cdna>(set);
+    const size_t N = (size_t)n, words = packed.size(), head = words * 8 + ccsx_cl_rep_bytes(N), head8 = (head + 7) & ~(size_t)7, len4 = (N * 4 + 7) & ~(size_t)7;
+    if (h->d_reads.reserve(head8 + N * 8 + len4 + (size_t)bytes)) return -2;
+    if (wl && wl->serial != h->cell_wl_serial) {
+        h->cell_wl_serial = 0;                                      // (a failed upload leaves nobody's table resident)
+        if (h->d_cell_wl.reserve((size_t)wl->slots * 8)) return -2;
+        HIPTRY(hipMemcpyAsync(h->d_cell_wl.p, wl->table, (size_t)wl->slots * 8, hipMemcpyHostToDevice, st));
+        h->cell_wl_serial = wl->serial;
+    }
+    uint8_t *base = (uint8_t *)h->d_reads.p;
+    int64_t *d_off = (int64_t *)(base + head8);
+    int32_t *d_len = (int32_t *)(base + head8 + N * 8);
+    uint8_t *d_seq = base + head8 + N * 8 + len4;
+    HIPTRY(hipMemcpyAsync(base, packed.data(), words * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_off, seq_off, N * 8, hipMemcpyHostToDevice, st));
+    HIPTRY(hipMemcpyAsync(d_len, seq_len, N * 4, hipMemcpyHostToDevice, st));
+    if (bytes) HIPTRY(hipMemcpyAsync(d_seq, seq, (size_t)bytes, hipMemcpyHostToDevice, st));
+    CellParams K{};
+    K.D = Cdna::params(set->n_primers, n, o, base);
+    K.D.seq = d_seq; K.D.seq_off = d_off; K.D.seq_len = d_len;
+    K.design = d;
+    K.table = wl ? (const unsigned long long *)h->d_cell_wl.p : nullptr; K.slots = wl ? wl->slots : 0u;
+    (void)hipGetLastError();
+    if (const char *failed = ccsx_cell_launch(K, st)) { ccsx_set_error(std::string("kernel launch failed: ") + failed); return -2; }
+    if (int rc = reads_download<Cdna>(K.D, &report->cdna, st)) return rc;
+    const CellOut c = ccsx_cl_out(K.D.rep, N);
+    const ReadsCopy planes[] = {{report->tag, c.tag, 4}, {report->bc_raw, c.bc_raw, 4}, {report->bc, c.bc, 4}, {report->bc_hi, c.bc_hi, 4}, {report->kind, c.kind, 4},
+                                {report->shift, c.shift, 4}, {report->umi, c.umi, 4}, {report->tag_clip, c.tag_clip, 4}};
+    for (const ReadsCopy &p : planes) HIPTRY(hipMemcpyAsync(p.host, p.dev, N * p.bytes_per_read, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+int ccsx_cell_reads(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const ccsx_cell_design *design, const ccsx_cell_whitelist *wl,
+                    const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, ccsx_cell_report *report)
+{
+    ccsx_cdna_opts o;
+    int64_t bytes;
+    if (ccsx_cell_check(set, opts, design, wl, report, n, __func__, &o) || ccsx_check_reads(seq, seq_off, seq_len, n, __func__, &bytes)) return -1;
+    if (!h) return refuse(__func__, "null argument");
+    if (n == 0) return 0;
+    HIPTRY(hipSetDevice(h->device));
+    const int rc = cell_enqueue(h, set, o, *design, wl, seq, seq_off, seq_len, n, bytes, report, h->s_comp);
+    if (rc) { (void)hipStreamSynchronize(h->s_comp); return rc; }   // (whatever was enqueued reads and writes the caller's arrays: it ends before the call does)
+    HIPTRY(hipStreamSynchronize(h->s_comp));
     return 0;
 }
 

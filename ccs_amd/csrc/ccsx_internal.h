@@ -61,6 +61,11 @@ int ccsx_dup_check_sign(const ccsx_dup_opts *opts, const uint8_t *seq, const int
 int ccsx_dup_check_cluster(const ccsx_dup_opts *opts, const ccsx_dup_sig *sig, const int32_t *group, int32_t n, const ccsx_dup_report *report, const char *fn,
                            ccsx_dup_opts *o);
 
+// ---- cell barcodes and UMIs (ccsx_cell_api.cpp; DESIGN.md §2 "Cell-tag rule"): the one check of ccsx_cell_reads_host and ccsx_cell_reads: everything
+// ccsx_cdna_check refuses, then the design, the whitelist against the design (wl NULL: none) and the report's own planes
+int ccsx_cell_check(const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const ccsx_cell_design *design, const ccsx_cell_whitelist *wl,
+                    const ccsx_cell_report *report, int64_t n, const char *fn, ccsx_cdna_opts *o);
+
 // ---- representative reads (ccsx_represent_api.cpp; DESIGN.md §2 "Representative rule"): the request against the batch it is for and the options of the run — flags,
 // reserved words, the report's arrays and size, kinetics without opts.hifi_kinetics or batch.ipd.  A refusal sets the error under `fn` and returns -1.
 int ccsx_represent_check(const ccsx_represent_request *req, const ccsx_batch *b, const ccsx_opts *opts, const char *fn);

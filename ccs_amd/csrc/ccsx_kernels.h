@@ -9,6 +9,7 @@
 #include "segment_core.h"
 #include "cdna_core.h"
 #include "dup_core.h"
+#include "cell_core.h"
 #include "represent_core.h"
 
 // bytes of POA scratch per vertex (ccsx_kernels.hip poa_slot, all by topological position): the 32-row score column of far-read columns 128, five 16-byte
@@ -292,6 +293,7 @@ const char *ccsx_launch_all(const KParams &P, const ccsx_launch_queues &q, int m
 const char *ccsx_barcode_launch(const BarcodeParams &B, hipStream_t st);                 // ccsx_barcode.hip: k_barcode, one workgroup per read; NULL, or what failed
 const char *ccsx_segment_launch(const SegmentParams &G, hipStream_t st);                 // ccsx_segment.hip: k_segment, one workgroup per read; NULL, or what failed
 const char *ccsx_cdna_launch(const CdnaParams &D, hipStream_t st);                       // ccsx_cdna.hip: k_cdna, one workgroup per read; NULL, or what failed
+const char *ccsx_cell_launch(const CellParams &C, hipStream_t st);                       // ccsx_cell.hip: k_cell, one workgroup per read; NULL, or what failed
 const char *ccsx_dup_sign_launch(const DupSignParams &S, hipStream_t st);                // ccsx_dup.hip: k_dup_sign, one wave per read; NULL, or what failed
 const char *ccsx_dup_cluster_launch(const DupClusterParams &P, hipStream_t st);          // ccsx_dup.hip: k_dup_keys, the sort, k_dup_buckets, k_dup_verify; NULL, or what failed
 size_t ccsx_dup_sort_bytes(int n);                                                       // ccsx_dup.hip: the sort's scratch for n pairs (no device work)

@@ -1073,6 +1073,63 @@ int         ccsx_dup_cluster_host(const ccsx_dup_opts *opts, const ccsx_dup_sig 
 int         ccsx_dup_cluster(ccsx_handle h, const ccsx_dup_opts *opts, const ccsx_dup_sig *sig, const int32_t *group, const int32_t *score, int32_t n,
                              ccsx_dup_report *report);
 
+/* ---- cell barcodes and UMIs (the rule: DESIGN.md §2 "Cell-tag rule", its own version ccsx_cell_rule_version; this build's own, as the barcode, the segment, the
+ * cDNA and the duplicate rule are; no result of the consensus changes and ccsx_cdna_* is untouched).  A single-cell cDNA molecule carries, between one primer and
+ * the transcript, a UMI and a cell barcode: T = umi_len + bc_len bases.  A field is packed into a uint32 at 2 bits a base, the first base most significant; fields
+ * are read on the strand of the end they adjoin, going away from the primer (the orientation of the oligo primer . field . field).  k_cell, per read c[0, L):
+ *   ends      the cDNA rule's ends and strand; a read at which that rule ends there (NO_PRIMER, ONE_END, SAME_ROLE, SHORT) has tag NONE.
+ *   tag end   e_t = (strand == side) ? 0 : 1, p0 = clip[e_t]; ins_len < T: class SHORT, tag NONE.
+ *   barcode   bc_raw = the bc_len bases of end e_t from p = p0 + (bc_first ? 0 : umi_len).  Without a whitelist or with bc_len 0: tag RAW, bc -1.  A member of the
+ *             whitelist: EXACT.  Otherwise the candidates: kind 1, the 3 bc_len substitutions; kind 2 (indels only; the read lost a base), the first bc_len - 1
+ *             bases with one base inserted at each of bc_len places; kind 3 (indels and ins_len >= T + 1 only; the read gained a base), bc_raw with one base
+ *             deleted and the base at p + bc_len appended.  bc / bc_hi = the smallest / largest whitelist index the candidates reach: none ABSENT (-1, -1),
+ *             two or more AMBIGUOUS, one CORRECTED with kind = the smallest kind that reaches it and shift = 0, -1, +1 for kinds 1, 2, 3.  Every status but
+ *             CORRECTED has kind 0 and shift 0.
+ *   umi       umi_len bases from bc_first ? p0 + bc_len + shift : p0.
+ *   the rest  the cDNA rule's poly(A) scan, internal hits, class and slice with clip[e_t] widened by tag_clip = T + shift (ins_len - tag_clip < 1: SHORT).  The
+ *             clip planes keep the primers' own clips.
+ * A whitelist is a host object, an open-addressing table of uint64 slots (key << 32) | (index + 1), 0 = empty; slots = the smallest power of two >= 2 n and >= 64;
+ * the first slot of key x is ccsx_cell_slot(x, slots) = ccsx_dup_hash(x) & (slots - 1), then linear probing.  The device copy belongs to the handle and is uploaded
+ * when a call brings a whitelist whose serial differs from the resident one.
+ *   ccsx_cell_reads_host  the rule on the calling thread, without a device: the reference of the tests.
+ *   ccsx_cell_reads       k_cell on caller-supplied reads.  Synchronous; buffers of the handle's own on the polish stream, no slot is staged or recycled.
+ * wl may be NULL (tags RAW).  Errors of the call (nothing is enqueued, reserved or launched): everything ccsx_cdna_reads refuses, a null design, T = 0, a field
+ * length outside 0 .. 16, side / bc_first / indels outside 0 .. 1, a nonzero reserved word, a whitelist of another bc_len, a report sized for another batch or with
+ * a NULL plane.  ccsx_cell_whitelist_create: codes [n][bc_len] of 0 .. 3; n 1 .. 2^23, bc_len 1 .. 16; NULL and the error set on a null argument, a code above 3,
+ * or a duplicate barcode (the message names both indices).  ccsx_cell_whitelist_info: n, bc_len, the number of slots and the table itself, each where the
+ * pointer is not NULL (the table lives as long as the whitelist).                                                                                               */
+#define CCSX_CELL_MAX_FIELD 16
+#define CCSX_CELL_MAX_WHITELIST (1 << 23)
+enum ccsx_cell_tag { CCSX_CELL_NONE = 0, CCSX_CELL_RAW = 1, CCSX_CELL_EXACT = 2, CCSX_CELL_CORRECTED = 3, CCSX_CELL_AMBIGUOUS = 4, CCSX_CELL_ABSENT = 5 };
+typedef struct ccsx_cell_design {
+    int32_t umi_len;             /* 0 .. 16                                                                                                                      */
+    int32_t bc_len;              /* 0 .. 16; umi_len + bc_len >= 1                                                                                               */
+    int32_t side;                /* 0: the fields adjoin the 5' primer, 1: the 3' primer                                                                          */
+    int32_t bc_first;            /* 1: the barcode is the field next to the primer, 0: the UMI is                                                                 */
+    int32_t indels;              /* 1: candidates of kinds 2 and 3 are tried [1]                                                                                  */
+    int32_t reserved[3];         /* must be 0                                                                                                                    */
+} ccsx_cell_design;
+typedef struct ccsx_cell_report {
+    ccsx_cdna_report cdna;       /* the cDNA planes (cdna.n_zmw sizes the whole report); clip: the primers' own                                                   */
+    int32_t  *tag;               /* [n_zmw] enum ccsx_cell_tag                                                                                                   */
+    uint32_t *bc_raw;            /* [n_zmw] the barcode field as read; 0 with tag NONE or bc_len 0                                                               */
+    int32_t  *bc, *bc_hi;        /* [n_zmw] the smallest and the largest whitelist index reached; -1 without one                                                  */
+    int32_t  *kind, *shift;      /* [n_zmw] of a CORRECTED read; 0 otherwise                                                                                      */
+    uint32_t *umi;               /* [n_zmw] the UMI field; 0 with tag NONE or umi_len 0                                                                           */
+    int32_t  *tag_clip;          /* [n_zmw] T + shift, what the tag end's clip was widened by; 0 with tag NONE                                                    */
+} ccsx_cell_report;
+typedef struct ccsx_cell_whitelist ccsx_cell_whitelist;
+void        ccsx_cell_design_default(ccsx_cell_design *d);       /* 12 U, 16 B, the 3' side, the barcode next to the primer, indels                               */
+int         ccsx_cell_rule_version(void);
+uint32_t    ccsx_cell_slot(uint32_t key, uint32_t slots);
+ccsx_cell_whitelist *ccsx_cell_whitelist_create(const uint8_t *codes, int32_t n, int32_t bc_len);
+void        ccsx_cell_whitelist_destroy(ccsx_cell_whitelist *wl);
+int         ccsx_cell_whitelist_info(const ccsx_cell_whitelist *wl, int32_t *n, int32_t *bc_len, uint32_t *slots, const uint64_t **table);
+int         ccsx_cell_reads_host(const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const ccsx_cell_design *design, const ccsx_cell_whitelist *wl,
+                                 const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, ccsx_cell_report *report);
+int         ccsx_cell_reads(ccsx_handle h, const ccsx_cdna_set *set, const ccsx_cdna_opts *opts, const ccsx_cell_design *design, const ccsx_cell_whitelist *wl,
+                            const uint8_t *seq, const int64_t *seq_off, const int32_t *seq_len, int32_t n, ccsx_cell_report *report);
+
 /* ---- BGZF inflate on the device (the rule: DESIGN.md §2 "BGZF inflate", its own version ccsx_inflate_rule_version; nothing of the consensus changes).  A BGZF
  * block is an independent raw DEFLATE stream (RFC 1951) of at most 64 KiB of output: k_inflate decodes one stream per wave.  An inflater is its own object: its
  * own non-blocking stream, device buffers and page-locked staging; it shares nothing with a ccsx_handle and may run beside one.  It is not thread-safe: one
