@@ -27,8 +27,10 @@ enum ccsx_inflate_status {
     CCSX_INFLATE_TRUNCATED_INPUT   = 1,  /* the stream needs bits beyond in_len                                              */
     CCSX_INFLATE_BAD_BLOCK_TYPE    = 2,  /* BTYPE 3                                                                          */
     CCSX_INFLATE_BAD_STORED_LENGTH = 3,  /* LEN != ~NLEN                                                                     */
-    CCSX_INFLATE_BAD_CODE_LENGTHS  = 4,  /* over- or under-subscribed code (except zlib's one-code distance tree), a repeat
-                                            without a previous length or past the end, more than 286 / 30 codes, no end-of-block code */
+    CCSX_INFLATE_BAD_CODE_LENGTHS  = 4,  /* over- or under-subscribed code (except zlib's `max == 1` rule: a literal / length or a distance
+                                            code of exactly one 1-bit codeword passes, its unused codeword reads as BAD_SYMBOL; the
+                                            code-length code is strict), a repeat without a previous length or past the end, more than
+                                            286 / 30 codes, no end-of-block code                                               */
     CCSX_INFLATE_BAD_SYMBOL        = 5,  /* a code that stands for no symbol (litlen 286/287, distance 30/31, unassigned)     */
     CCSX_INFLATE_BAD_DISTANCE      = 6,  /* a match reaches before the start of this stream's output                         */
     CCSX_INFLATE_OUTPUT_OVERRUN    = 7,  /* the stream holds more than out_len bytes                                          */
@@ -113,7 +115,9 @@ static inline CCSX_INFL_HD int ccsx_infl_build(const uint8_t *lens, int n, uint3
     for (int i = lane; i < (1 << P); i += nl) table[i] = 0;            // CCSX_INFL_K_INVALID: a code nothing was assigned to
     if (total == 0) { L::sync(); return kind == CCSX_INFL_DIST ? CCSX_INFLATE_OK : CCSX_INFLATE_BAD_CODE_LENGTHS; }   // a block of literals only may carry no distance code
     if (used > 32768u) { L::sync(); return CCSX_INFLATE_BAD_CODE_LENGTHS; }
-    if (used < 32768u && !(kind == CCSX_INFL_DIST && total == 1 && cnt[1] == 1)) { L::sync(); return CCSX_INFLATE_BAD_CODE_LENGTHS; }
+    // zlib's `max == 1` rule: a literal / length or distance code of exactly one 1-bit codeword is the one incomplete code that passes (its other codeword stays
+    // CCSX_INFL_K_INVALID); the code-length code is strict
+    if (used < 32768u && !(kind != CCSX_INFL_PRECODE && total == 1 && cnt[1] == 1)) { L::sync(); return CCSX_INFLATE_BAD_CODE_LENGTHS; }
     uint32_t offs[16], first[16];
     {
         uint32_t o = 0, c = 0;

@@ -1153,8 +1153,10 @@ enum ccsx_inflate_status {
     CCSX_INFLATE_TRUNCATED_INPUT   = 1,  /* the stream needs bits beyond in_len                                              */
     CCSX_INFLATE_BAD_BLOCK_TYPE    = 2,  /* BTYPE 3                                                                          */
     CCSX_INFLATE_BAD_STORED_LENGTH = 3,  /* LEN != ~NLEN                                                                     */
-    CCSX_INFLATE_BAD_CODE_LENGTHS  = 4,  /* over- or under-subscribed code (except zlib's one-code distance tree), a repeat
-                                            without a previous length or past the end, more than 286 / 30 codes, no end-of-block code */
+    CCSX_INFLATE_BAD_CODE_LENGTHS  = 4,  /* over- or under-subscribed code (except zlib's `max == 1` rule: a literal / length or a distance
+                                            code of exactly one 1-bit codeword passes, its unused codeword reads as BAD_SYMBOL; the
+                                            code-length code is strict), a repeat without a previous length or past the end, more than
+                                            286 / 30 codes, no end-of-block code                                               */
     CCSX_INFLATE_BAD_SYMBOL        = 5,  /* a code that stands for no symbol (litlen 286/287, distance 30/31, unassigned)     */
     CCSX_INFLATE_BAD_DISTANCE      = 6,  /* a match reaches before the start of this stream's output                         */
     CCSX_INFLATE_OUTPUT_OVERRUN    = 7,  /* the stream holds more than out_len bytes                                          */

@@ -119,6 +119,47 @@ def encoder_cases() -> tuple:
     return tuple(c)
 
 
+SUB = 8192               # CCSX_DEFL_SUB
+CHUNK = 256              # CCSX_DEFL_CHUNK
+MAX_MATCH = 258          # CCSX_DEFL_MAX_MATCH
+BOUNDARY_LENGTHS = [255, 256, 257, 8191, 8192, 8193, 8449, 8450, 8451, 16383, 16384, 16385, 57343, 57344, 57345, 65279, 65280, 65281]
+STRADDLE_PHRASE_AT = SUB - 100
+NEAR_COPIES_AT = (100, 520, 600)     # the phrase of 'nearer-copy-in-the-same-chunk': chunk 0, and twice in chunk 2
+
+
+def noise64(n: int, seed: int) -> bytes:
+    """random bytes of 64 values: six bits a byte, so a span of them stays coded, and a chance 4-byte match is rare"""
+    return bytes(0x30 + (b & 63) for b in random.Random(seed).randbytes(n))
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_cases() -> tuple:
+    """(name, bytes): every content at every length around a chunk, a sub-block, a sub-block + a longest match, several sub-blocks and the BGZF span, and the
+    shapes that put a match across a sub-block's end"""
+    longest = max(BOUNDARY_LENGTHS)
+    content = {"zeros": bytes(longest), "ab": b"ab" * (longest // 2 + 1), "acgt": IR.acgt(longest, 21), "text": IR.text(longest, 22), "qv": qv_like(longest, 23)}
+    c = [(f"{kind}-{n}", data[:n]) for kind, data in content.items() for n in BOUNDARY_LENGTHS]
+    phrase = IR.text(MAX_MATCH, 258)
+    straddle = noise64(1000, 1) + phrase + noise64(STRADDLE_PHRASE_AT - 1000 - len(phrase), 2) + phrase + noise64(1000, 3)
+    assert straddle[STRADDLE_PHRASE_AT:STRADDLE_PHRASE_AT + len(phrase)] == phrase
+    c.append(("match-straddles-the-sub-block", straddle))
+    c.append(("span-ends-inside-the-straddling-match", straddle[:SUB + 100]))
+    p40 = IR.text(40, 40)
+    a, b, far = NEAR_COPIES_AT
+    near = noise64(a, 4) + p40 + noise64(b - a - 40, 5) + p40 + noise64(far - b - 40, 6) + p40 + noise64(200, 7)
+    assert [near[k:k + 40] for k in NEAR_COPIES_AT] == [p40] * 3 and a // CHUNK < b // CHUNK == far // CHUNK
+    c.append(("nearer-copy-in-the-same-chunk", near))
+    c.append(("text-then-noise", IR.text(SUB, 1) + IR.noise(MAX_IN - SUB, 2)))
+    c.append(("noise-then-text", IR.noise(MAX_IN - SUB, 2) + IR.text(SUB, 1)))
+    return tuple(c)
+
+
+@functools.lru_cache(maxsize=None)
+def skew_spans() -> tuple:
+    """(skew of the span's first byte modulo 16, bytes): every length around the 16-byte pieces of the copy at every skew"""
+    return tuple((skew, IR.text(n, 16 * n + skew)) for n in (0, 1, 15, 16, 17, 31, 32, 33) for skew in range(16))
+
+
 @functools.lru_cache(maxsize=None)
 def all_cases() -> tuple:
     """encoder_cases() + the plain bytes of every valid and fuzz case of the inflate tests (names made unique)"""

@@ -14,7 +14,7 @@ import inflate_ref as R  # noqa: E402
 
 
 def write_cases(f) -> None:
-    cases = [(s, len(d), R.OK, d) for _, s, d in R.valid_cases() + R.fuzz_cases()]
+    cases = [(s, len(d), R.OK, d) for _, s, d in R.valid_cases() + R.fuzz_cases() + R.limit_cases()]
     cases += [(s, n, -1 if want is None else want, b"") for _, s, n, want in R.corrupt_cases()]
     cases += [(s, n, -1, b"") for s, n in R.flip_cases(n=4000)]
     for s, n, want, d in cases:
