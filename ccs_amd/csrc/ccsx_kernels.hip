@@ -2157,6 +2157,7 @@ struct ScoreChain {                  // running state of one (lane, read) mutati
     float2 pA, pB;
     lds_cf g, be;                    // gamma(i, c) and beta(i+1, q) of the row about to be processed: both advance by the read's pitch per row
     lds_cu8 op;                      // observation of that row (0..11, 12 = none)
+    unsigned w0, w1, w2;             // the observation bytes of the block's rows still to come, byte 0 of w0 = the row about to be loaded (obs_words)
     int dg;                          // SPEC v6/v8: gamma's diagonal relative to the read's band, c - i - dlo; the row's two cells are on the band iff 0 <= dg <= bw - 1 - (q - c - 1)
 };
 
@@ -2168,28 +2169,75 @@ __device__ __forceinline__ float lanes_or_zero(unsigned long long m, float v)
     return r;
 }
 
-// one row of the extend+link recursion.  tA / tB = the lane's columns of sCTX (context kA / kB).  Every lane walks
-// its own rows (the SPEC's band around the window diagonal starts at a per-lane row), so the row's observation code comes from LDS;
-// row I of a read carries code 12 = the all-zero row of sCTX ("no base left": the SPEC's i < I cases become exact +0 products).
+// What a wave keeps of a mutation lane ACROSS units (both strands, the whole round): the seven small integers of LaneMut in one word, and the two DL factors.
+// A unit unpacks its strand's word with a handful of v_bfe; the scoring rows then have 12 VGPRs more than when both strands' LaneMut stayed unpacked.
+struct LanePk { int pk; float dlA, dlL; };   // pk = c | q << 5 | kA << 10 | kB << 15 | isdel << 20 | fin << 21 | qoff << 22
+__device__ __forceinline__ LanePk lane_pack(const LaneMut &L)
+{
+    LanePk k;
+    k.pk = L.c | L.q << 5 | L.kA << 10 | L.kB << 15 | L.isdel << 20 | L.fin << 21 | L.qoff << 22;
+    k.dlA = L.dlA; k.dlL = L.dlL;
+    return k;
+}
+__device__ __forceinline__ LaneMut lane_unpack(const LanePk &k)
+{
+    LaneMut L;
+    const unsigned p = (unsigned)k.pk;
+    L.c = p & 31; L.q = (p >> 5) & 31; L.kA = (p >> 10) & 31; L.kB = (p >> 15) & 31; L.isdel = (p >> 20) & 1; L.fin = (p >> 21) & 1; L.qoff = (p >> 22) & 1;
+    L.dlA = k.dlA; L.dlL = k.dlL;
+    return L;
+}
+
+// ---- one row of the extend+link recursion = one ROW-STEP: its loads (rs_load) and its arithmetic (rs_compute).  tA / tB = the lane's columns of
+// sCTX (context kA / kB).  Every lane walks its own rows (the SPEC's band around the window diagonal starts at a per-lane row), so every lane has its own
+// observation code per row; row I of a read carries code 12 = the all-zero row of sCTX ("no base left": the SPEC's i < I cases become exact +0 products).
 // SPEC v6: gamma / beta are stored on the read's band only; a scoring band that is clamped into a corner of the window reads cells outside it, which are zeros
 // (the address of such a cell aliases a neighbouring row's: the value is replaced, never used).
-__device__ __forceinline__ void score_step(ScoreChain &s, const LaneMut &L, lds_cc tA, lds_cc tB, int pitch, unsigned lim)
+// The rows run as a two-deep pipeline (profiles/polish_scoring_loads.txt).  A row-step's six LDS words — gamma(i, c), beta(i+1, q) and the two table pairs — depend on
+// nothing the rows compute: the addresses run with the row, and the row's observation byte comes from REGISTERS (obs_words: the chain's next twelve bytes of sObs[r],
+// loaded once as aligned words and shifted into place per lane).  So a row-step's loads are issued while the row-step before it computes, into registers of their
+// own (RowLoads), and the wait in front of its arithmetic finds them there.  Until then a row waited three times in series: for its observation byte, for the table
+// pairs behind it, and for gamma / beta, which shared one temporary register with the next load.
+#define SCORE_OBS_ROWS 12             // rows per block of observation bytes: twelve bytes from any residue of the first row's address lie in four aligned words
+typedef const unsigned __attribute__((address_space(3))) *lds_cu32;
+struct RowLoads { float g, be; unsigned long long va, vb; };
+
+// the chain's observation bytes of rows i .. i + 11 (op = &sObs[r][i]) into w0 .. w2, byte 0 of w0 = row i.  The words behind the row's own 68 bytes belong to the
+// next row or to the gamma/beta area: their bytes are shifted in and never used
+__device__ __forceinline__ void obs_words(ScoreChain &s, lds_cu8 op)
+{
+    const unsigned sh = (unsigned)(unsigned long long)op & 3u;
+    lds_cu32 w = (lds_cu32)(op - sh);
+    const unsigned d0 = w[0], d1 = w[1], d2 = w[2], d3 = w[3];
+    s.w0 = __builtin_amdgcn_alignbyte(d1, d0, sh);
+    s.w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
+    s.w2 = __builtin_amdgcn_alignbyte(d3, d2, sh);
+}
+
+__device__ __forceinline__ void rs_load(ScoreChain &s, RowLoads &r, lds_cc tA, lds_cc tB, int pitch)
 {
     typedef const unsigned long long __attribute__((address_space(3))) *lds_cu64;
+    r.g = *s.g; r.be = *s.be;
+    const int o256 = __mul24((int)(s.w0 & 255u), CTXS * 8);   // byte offset of the observation's row in sCTX
+    r.va = *(lds_cu64)(tA + o256); r.vb = *(lds_cu64)(tB + o256);   // one ds_read_b64 each
+    s.g += pitch; s.be += pitch;
+    s.w0 = __builtin_amdgcn_alignbit(s.w1, s.w0, 8); s.w1 = __builtin_amdgcn_alignbit(s.w2, s.w1, 8); s.w2 >>= 8;
+}
+
+__device__ __forceinline__ void rs_compute(ScoreChain &s, const LaneMut &L, const RowLoads &r, unsigned lim)
+{
     // SPEC v8 "joint band test": gamma(i, c) and beta(i+1, q) of the row sit q - c - 1 diagonals apart; both are zeros unless both are on the band — one compare
     // (lim = bw - 1 - (q - c - 1)) whose mask serves both selects (v7: a test per cell)
 #ifndef CCSX_EXP_NO_BANDMASK                                // experiment (timing only, wrong results in the corners of a window): what the band test costs
     const unsigned long long on = __builtin_amdgcn_uicmp((unsigned)s.dg, lim, 37 /* ule */);
-    const float gmm = lanes_or_zero(on, *s.g);
-    const float bqn = lanes_or_zero(on, *s.be);
+    const float gmm = lanes_or_zero(on, r.g);
+    const float bqn = lanes_or_zero(on, r.be);
 #else
-    const float gmm = *s.g, bqn = *s.be;
+    const float gmm = r.g, bqn = r.be;
 #endif
-    const int o256 = __mul24((int)*s.op, CTXS * 8);   // byte offset of the observation's row in sCTX
-    const unsigned long long va = *(lds_cu64)(tA + o256), vb = *(lds_cu64)(tB + o256);   // one ds_read_b64 each
-    const float2 nA = make_float2(__uint_as_float((unsigned)va), __uint_as_float((unsigned)(va >> 32)));
-    const float2 nB = make_float2(__uint_as_float((unsigned)vb), __uint_as_float((unsigned)(vb >> 32)));
-    s.g += pitch; s.be += pitch; s.op += 1; s.dg -= 1;
+    const float2 nA = make_float2(__uint_as_float((unsigned)r.va), __uint_as_float((unsigned)(r.va >> 32)));
+    const float2 nB = make_float2(__uint_as_float((unsigned)r.vb), __uint_as_float((unsigned)(r.vb >> 32)));
+    s.dg -= 1;
     const float insA = s.pA.y, meA = s.pA.x, insB = s.pB.y;
     // SPEC v8 "fused recurrences": every multiply-add is one fma, nested as written in DESIGN.md §2
     const float a = __builtin_fmaf(s.ap, insA, gmm);
@@ -2198,7 +2246,9 @@ __device__ __forceinline__ void score_step(ScoreChain &s, const LaneMut &L, lds_
     else b = __builtin_fmaf(s.bp, insB, __builtin_fmaf(a, L.dlA, s.ap * meA));
     s.acc = __builtin_fmaf(b, __builtin_fmaf(L.dlL, s.bq, nB.x * bqn), s.acc);
     s.ap = a; s.bp = b; s.b = b; s.pA = nA; s.pB = nB; s.bq = bqn;
+    asm volatile("" : "+v"(s.acc), "+v"(s.bp));              // the arithmetic stays HERE, between its fences: sunk behind the later loads it would keep every RowLoads alive at once
 }
+#define RS_FENCE() __builtin_amdgcn_sched_barrier(0)   // nothing moves across: a row-step's loads stay in front of the arithmetic they overlap
 
 // first row of a lane's scoring band: floor((2 c I + J) / (2 J)) - Wr, clamped so that nrows rows fit into 0..I (SPEC "banded link");
 // the quotient through a float reciprocal with an exact remainder correction (all values < 2^12)
@@ -2301,7 +2351,8 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
     __shared__ uint8_t sTd[32];                              // the draft's window as it was (the large-insertion trim of a reloaded group compares with it)
     // dynamic LDS: observation codes of the batch's largest ZMW ([reads][68]: 63 codes + look-ahead slack), then gamma/beta.
     // One BYTE per read row (round 3 stored the 16-bit byte offset of the observation's sCTX row: at 30 passes those 4 KB left room for only three
-    // reads per gamma/beta chunk; the scoring rows are bound by their LDS round trips, the extra multiply per row is not measurable).
+    // reads per gamma/beta chunk; the extra multiply per row is not measurable).  The scoring takes a chain's bytes as aligned WORDS, twelve rows at a time (obs_words):
+    // rows of 68 bytes keep every row 4-byte aligned.
     uint8_t (*sObs)[68] = (uint8_t (*)[68])dyn_lds;
     float *sGB = (float *)((uint8_t *)dyn_lds + P.pw_obs_bytes);
     const int GB_FLOATS = P.pw_gb_floats;
@@ -2689,7 +2740,7 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
         PHASE(1);
         int nvalid = 0, nvfull = 0;
         int curblk = -1;                                     // the block whose lane constants this wave holds (they survive the chunks of a round)
-        LaneMut LF, LR;
+        LanePk LF, LR;
         int myM = 0; bool mval = false;
         // ---- groups of PW_MAXREADS passes (one group for nearly every ZMW), and in a group: chunks of reads whose gamma/beta fit the LDS budget
         for (int g0 = 0; g0 < nreads; g0 += PW_MAXREADS) {
@@ -2989,16 +3040,18 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                         else if (slot == 3) type = 1;
                         else { type = 2; x = slot - 4; }
                         if (mval) {
-                            LF = lane_mut(type, cpos, x, sT[0], J, lf, sDL);
-                            LR = lane_mut(type, (type == 2) ? J - cpos : J - 1 - cpos, 3 - x, sT[1], J, lfr, sDL);
-                        } else { LF = lane_mut(0, 0, 0, sT[0], J, lf, sDL); LR = LF; }
+                            LF = lane_pack(lane_mut(type, cpos, x, sT[0], J, lf, sDL));
+                            LR = lane_pack(lane_mut(type, (type == 2) ? J - cpos : J - 1 - cpos, 3 - x, sT[1], J, lfr, sDL));
+                        } else { LF = lane_pack(lane_mut(0, 0, 0, sT[0], J, lf, sDL)); LR = LF; }
                     }
                     int dq;
                     if (!two) {
                         // a single unit (the usual case with four reads per chunk and one block of lanes): one chain, and none of the
                         // second chain's set-up
                         const int ra = rl(vR, k0), Ia = rl(vI, k0);
-                        const LaneMut La = rl(vSt, k0) ? LR : LF;
+                        LanePk Ka = rl(vSt, k0) ? LR : LF;
+                        asm volatile("" : "+v"(Ka.pk));                       // (unpacked HERE, per unit: hoisted out of the unit loop the fields would be live across it again)
+                        const LaneMut La = lane_unpack(Ka);
                         const int gA_ = rl(vG, k0), bA_ = rl(vB, k0), bdA = rl(vBd, k0);
                         const int pA = bdA & 255, dloA = (int)((unsigned)bdA >> 24) - 128; const unsigned bwA = (unsigned)(bdA >> 16) & 255u;
                         const int dA = Ia > J ? Ia - J : J - Ia, WrA = SCORE_BAND + (dA > 2 ? dA - 2 : 0);
@@ -3018,11 +3071,24 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                         const unsigned limA = bwA - 1u - (unsigned)La.qoff;
                         ca.op = (lds_cu8)(&sObs[ra][0] + i0a);
                         asm volatile("" : "+v"(ca.g), "+v"(ca.be), "+v"(tAa), "+v"(tBa), "+v"(ca.op));
-                        {   // two rows per iteration: the chain's carried values (previous table pairs, beta, a, b) then rotate between two
-                            // register sets instead of being copied at every row (3 v_mov + a loop counter per row before)
+                        // one chain: the loads of row i + 1 are issued in front of row i's arithmetic (X and Y take turns)
+                        for (int k = 0; k < nrA; k += SCORE_OBS_ROWS) {
+                            const int na = nrA - k < SCORE_OBS_ROWS ? nrA - k : SCORE_OBS_ROWS;
+                            obs_words(ca, ca.op + k);
+                            RowLoads X, Y;
                             int ia = 0;
-                            for (; ia + 2 <= nrA; ia += 2) { score_step(ca, La, tAa, tBa, pA, limA); score_step(ca, La, tAa, tBa, pA, limA); }
-                            if (ia < nrA) score_step(ca, La, tAa, tBa, pA, limA);
+                            rs_load(ca, X, tAa, tBa, pA);
+                            for (; ia + 3 <= na; ia += 2) {                    // (two rows with a third behind them)
+                                rs_load(ca, Y, tAa, tBa, pA); RS_FENCE();
+                                rs_compute(ca, La, X, limA); RS_FENCE();
+                                rs_load(ca, X, tAa, tBa, pA); RS_FENCE();
+                                rs_compute(ca, La, Y, limA); RS_FENCE();
+                            }
+                            if (ia + 2 <= na) {                                // the block's last two rows
+                                rs_load(ca, Y, tAa, tBa, pA); RS_FENCE();
+                                rs_compute(ca, La, X, limA); RS_FENCE();
+                                rs_compute(ca, La, Y, limA);
+                            } else rs_compute(ca, La, X, limA);
                         }
                         const float res = La.fin ? ca.b : ca.acc;
 #ifdef CCSX_EXP_NO_SCORE_LOG                                // experiment (timing only): a unit without its logarithm and fixed-point conversion
@@ -3034,8 +3100,9 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                     const int k1 = k0 + 1;
                     const int ra = rl(vR, k0), rb = rl(vR, k1);
                     const int Ia = rl(vI, k0), Ib = rl(vI, k1);
-                    const LaneMut La = rl(vSt, k0) ? LR : LF;
-                    const LaneMut Lb = rl(vSt, k1) ? LR : LF;
+                    LanePk Ka = rl(vSt, k0) ? LR : LF, Kb = rl(vSt, k1) ? LR : LF;
+                    asm volatile("" : "+v"(Ka.pk), "+v"(Kb.pk));
+                    const LaneMut La = lane_unpack(Ka), Lb = lane_unpack(Kb);
                     const int gA_ = rl(vG, k0), bA_ = rl(vB, k0), gB_ = rl(vG, k1), bB_ = rl(vB, k1), bdA = rl(vBd, k0), bdB = rl(vBd, k1);
                     const int pA = bdA & 255, dloA = (int)((unsigned)bdA >> 24) - 128; const unsigned bwA = (unsigned)(bdA >> 16) & 255u;
                     const int pB = bdB & 255, dloB = (int)((unsigned)bdB >> 24) - 128; const unsigned bwB = (unsigned)(bdB >> 16) & 255u;
@@ -3062,16 +3129,48 @@ __global__ __launch_bounds__(PWT, PWMIN) void k_polish_t(KParams P, int slot0)
                     // opaque to the optimiser from here: the running pointers hold complete LDS addresses (otherwise the
                     // dynamic-LDS base is re-added at every use)
                     asm volatile("" : "+v"(ca.g), "+v"(ca.be), "+v"(cb.g), "+v"(cb.be), "+v"(tAa), "+v"(tBa), "+v"(tAb), "+v"(tBb), "+v"(ca.op), "+v"(cb.op));
-                    const int nmin = nrA < nrB ? nrA : nrB;
-                    int i = 0;
-                    for (; i + 2 <= nmin; i += 2) {                            // both chains, two rows per iteration (no register copies between rows)
-                        score_step(ca, La, tAa, tBa, pA, limA);
-                        score_step(cb, Lb, tAb, tBb, pB, limB);
-                        score_step(ca, La, tAa, tBa, pA, limA);
-                        score_step(cb, Lb, tAb, tBb, pB, limB);
+                    // both chains, row-steps in the order a, b, a, b: the loads of a row-step are issued in front of the arithmetic of the row-step before it, which is the
+                    // other chain's (X: chain a's loads, Y: chain b's)
+                    const int nmax = nrA > nrB ? nrA : nrB;
+                    for (int k = 0; k < nmax; k += SCORE_OBS_ROWS) {
+                        int na = nrA - k, nb = nrB - k;                        // the block's rows of each chain (0: the chain has ended)
+                        na = na < 0 ? 0 : (na < SCORE_OBS_ROWS ? na : SCORE_OBS_ROWS); nb = nb < 0 ? 0 : (nb < SCORE_OBS_ROWS ? nb : SCORE_OBS_ROWS);
+                        if (na > 0) obs_words(ca, ca.op + k);
+                        if (nb > 0) obs_words(cb, cb.op + k);
+                        const int nmin = na < nb ? na : nb;
+                        RowLoads X, Y;
+                        bool xl = false, yl = false;                           // X / Y hold the loads of the chain's next row
+                        int i = 0;
+                        if (nmin >= 2) {
+                            rs_load(ca, X, tAa, tBa, pA);
+                            for (; i + 4 <= nmin; i += 2) {                    // (a row pair with another behind it: straight-line, no test in front of chain a's next loads)
+                                rs_load(cb, Y, tAb, tBb, pB); RS_FENCE();
+                                rs_compute(ca, La, X, limA); RS_FENCE();
+                                rs_load(ca, X, tAa, tBa, pA); RS_FENCE();
+                                rs_compute(cb, Lb, Y, limB); RS_FENCE();
+                                rs_load(cb, Y, tAb, tBb, pB); RS_FENCE();
+                                rs_compute(ca, La, X, limA); RS_FENCE();
+                                rs_load(ca, X, tAa, tBa, pA); RS_FENCE();
+                                rs_compute(cb, Lb, Y, limB); RS_FENCE();
+                            }
+                            rs_load(cb, Y, tAb, tBb, pB); RS_FENCE();          // the last pair the two chains share
+                            rs_compute(ca, La, X, limA); RS_FENCE();
+                            rs_load(ca, X, tAa, tBa, pA); RS_FENCE();
+                            rs_compute(cb, Lb, Y, limB); RS_FENCE();
+                            rs_load(cb, Y, tAb, tBb, pB); RS_FENCE();
+                            rs_compute(ca, La, X, limA); RS_FENCE();
+                            i += 2;
+                            xl = i < na;
+                            if (xl) rs_load(ca, X, tAa, tBa, pA);
+                            RS_FENCE();
+                            rs_compute(cb, Lb, Y, limB); RS_FENCE();
+                        }
+                        // the tails (and a block with fewer than two shared rows) carry no fences on purpose: chain b's Y is issued ahead of chain a's tail, and the compiler may
+                        // sink it — a block ends with at most one odd row per chain at the usual eleven rows, nothing to measure
+                        if (i < nb) { rs_load(cb, Y, tAb, tBb, pB); yl = true; }
+                        for (int ia = i; ia < na; ++ia) { if (!xl) rs_load(ca, X, tAa, tBa, pA); xl = false; rs_compute(ca, La, X, limA); }
+                        for (int ib = i; ib < nb; ++ib) { if (!yl) rs_load(cb, Y, tAb, tBb, pB); yl = false; rs_compute(cb, Lb, Y, limB); }
                     }
-                    for (int ia = i; ia < nrA; ++ia) score_step(ca, La, tAa, tBa, pA, limA);
-                    for (int ib = i; ib < nrB; ++ib) score_step(cb, Lb, tAb, tBb, pB, limB);
                     {
                         const float res = La.fin ? ca.b : ca.acc;
                         dq = dq_fix(det_log2f(res) - __int_as_float(rl(__float_as_int(vBase), k0)));
